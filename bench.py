@@ -22,8 +22,12 @@ a step = all 96 guides.  --config 5: BASELINE config 5's shape, PAM-less 20-mer,
 (one variant per kilobase, seed 0xC5) through calitas_search_variants; its default --scale is reduced.
 
 value = candidate loci examined per second = 2 strands x reference bases x guide passes / wall time.
+
+A plain run does only what the headline needs; --full adds the CPU baseline and its parity sample (N=1), the sharded batch and the
+check of the gathered text (N>1).  --dump-outputs DIR writes what the last timed step returned as DIR/<name>.npy (hits_arrays).
 """
 import argparse
+import contextlib
 import json
 import os
 import socket
@@ -154,6 +158,68 @@ def synthetic_vcf(path, names, seqs, per_kb=1.0, seed=0xC5):
                 n_var += 1
             f.write("".join(lines))
     return n_var
+
+
+# --dump-outputs: what is written of a hits.txt text -- columns of hits.txt as numbers (the chromosome as its contig index, the strand as
+# +1 / -1, allele_frequency -1 on a row without a variant) of every row up to DUMP_ROWS rows, of a seeded sample above that; and whole
+# rows of DUMP_TEXT_BYTES at most as their byte values.  At most 29 + 16 MB.
+DUMP_COLUMNS = ("chromosome", "coordinate_start", "coordinate_end", "strand", "allele_frequency", "score", "guide_mm", "guide_gaps",
+                "guide_mm_plus_gaps", "pam_mm", "total_mm_plus_gaps", "unpadded_guide_sequence_length", "unpadded_target_sequence_length")
+DUMP_ROWS = 1 << 18
+DUMP_TEXT_BYTES = 4 << 20
+
+
+def hits_arrays(text, n_rows, contigs, max_rows=DUMP_ROWS, max_text=DUMP_TEXT_BYTES, seed=0xD5):
+    """The arrays --dump-outputs writes for one hits.txt (`text`: a bytes-like object holding the whole text, header line first):
+    hits_count = [rows, bytes]; hits_rows = per row its byte offset in the text and DUMP_COLUMNS, for every row when there are at most
+    max_rows, else for the rows that hold max_rows seeded byte offsets; hits_text = the bytes of a seeded choice of those rows (whole
+    rows, max_text bytes at most) as float32.  The same text gives the same arrays."""
+    import numpy as np
+    mv = memoryview(text).cast("B")
+    n = len(mv)
+    head_end = bytes(mv[:1 << 16]).index(b"\n") + 1
+    cols = [bytes(mv[:head_end - 1]).split(b"\t").index(c.encode()) for c in DUMP_COLUMNS]
+    if n_rows <= max_rows:
+        lines = bytes(mv[head_end:]).split(b"\n")[:-1]
+        offsets = head_end + np.cumsum([0] + [len(ln) + 1 for ln in lines[:-1]], dtype=np.int64)[:len(lines)]
+    else:
+        lines, offsets = [], []
+        for o in np.unique(np.random.default_rng(seed).integers(head_end, n, size=max_rows)).tolist():
+            w = 2048
+            while True:                      # the row that holds byte o: from the newline in front of it to the one that ends it
+                lo = max(head_end - 1, o - w)
+                chunk = bytes(mv[lo:o + w])
+                a, b = chunk.rfind(b"\n", 0, o - lo), chunk.find(b"\n", o - lo)
+                if a >= 0 and b >= 0:
+                    break
+                if w > n:
+                    raise ValueError("not a hits.txt text: no newline behind byte %d" % o)
+                w *= 2
+            if not offsets or offsets[-1] != lo + a + 1:
+                lines.append(chunk[a + 1:b]); offsets.append(lo + a + 1)
+    index = {c.encode(): i for i, c in enumerate(contigs)}
+    rows = np.zeros((len(lines), 1 + len(cols)), dtype=np.float64)
+    rows[:, 0] = offsets
+    for r, ln in enumerate(lines):
+        f = ln.split(b"\t")
+        v = [f[c] for c in cols]
+        rows[r, 1:] = [index[v[0]], float(v[1]), float(v[2]), 1.0 if v[3] == b"+" else -1.0, float(v[4]) if v[4] else -1.0] + [float(x) for x in v[5:]]
+    sizes = np.array([len(ln) + 1 for ln in lines], dtype=np.int64)
+    order = np.random.default_rng(seed + 1).permutation(len(lines))
+    take = np.sort(order[np.cumsum(sizes[order]) <= max_text])
+    sample = b"".join(lines[i] + b"\n" for i in take.tolist())
+    return {"hits_count": np.array([n_rows, n], dtype=np.float64), "hits_rows": rows,
+            "hits_text": np.frombuffer(sample, dtype=np.uint8).astype(np.float32)}
+
+
+def write_outputs(directory, arrays):
+    import numpy as np
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= 64 << 20, total
+    os.makedirs(directory, exist_ok=True)
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(directory, name + ".npy"), a)
 
 
 def host_cores():
@@ -339,13 +405,18 @@ def main():
                     help="N>1: windows (default) = consecutive window ranges of ONE pass, equal to within a window, contigs cut where the balance asks "
                          "for it (strong scaling; every rank owns the rows of its stretch); contigs = consecutive whole-contig ranges of one pass "
                          "(BASELINE's wording; 1.20x off balance at 8 ranks); guides = every rank its own guide pass over the whole genome (weak)")
-    ap.add_argument("--cpu-sample-mb", type=float, default=-1, help="CPU baseline sample in Mb (<0: auto, 0: skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="also what the headline does not need: the CPU baseline with its parity sample (N=1), the sharded batch and the "
+                         "gathered text against a single-process search (N>1)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned (its hits.txt as numbers, see hits_arrays) to DIR/<name>.npy")
+    ap.add_argument("--cpu-sample-mb", type=float, default=-1, help="--full: CPU baseline sample in Mb (<0: auto, 0: skip)")
     ap.add_argument("--secondary", action="store_true",
                     help="N>1: also measure the partition mode that is not the headline (every rank regenerates and re-uploads the genome for it)")
     ap.add_argument("--no-secondary", action="store_true", help=argparse.SUPPRESS)   # the default since round 3; accepted for old command lines
     ap.add_argument("--batch-sharded", dest="batch_sharded", action="store_true", default=None,
                     help="also measure BASELINE config 4's shape on this partition: every rank runs all 96 guides on its window range "
-                         "(calitas_search_hits_batch on a range), a sample of guides checked against single-process calls; default for N > 1")
+                         "(calitas_search_hits_batch on a range), a sample of guides checked against single-process calls; default for N > 1 with --full")
     ap.add_argument("--no-batch-sharded", dest="batch_sharded", action="store_false")
     ap.add_argument("--dry-run-fail-rank", type=int, default=-1, help=argparse.SUPPRESS)   # tests: this rank exits 3 before the rendezvous
     ap.add_argument("--text-block", choices=["caller", "library"], default="caller",
@@ -420,6 +491,10 @@ def main():
                 line["rank_cpus"] = cpus                          # (only when a topology was found: the affinity every rank ended up with)
             print(json.dumps(line), flush=True)
         return
+    if args.dump_outputs and (world > 1 or args.no_hits or args.two_stage or args.config == 4 or args.guides_per_step > 1
+                              or (args.config == 5 and args.text_block != "caller")):
+        raise SystemExit("bench.py: --dump-outputs writes the text of a single-guide step of one process: --gpus 1, --config 3 with one "
+                         "guide per step or --config 5 with --text-block caller")
     if args.steps is None:
         args.steps = {3: 20, 4: 2, 5: 2}[args.config]
     if args.warmup is None:
@@ -652,7 +727,7 @@ def main():
             c5_dst["addr"], c5_dst["cap"] = C.Context.alloc_host(cap), cap   # (hipHostMalloc: the copy engines write into it directly)
             log("config 5: %d bytes of text; a page-locked destination of %d bytes in %.1f s" % (n_first, cap, time.perf_counter() - t_b))
 
-        def step():
+        def step(hold=None):
             tp0 = time.perf_counter()
             if args.config == 5:
                 if c5_dst["addr"] is not None:
@@ -681,8 +756,13 @@ def main():
                 phase["search_hits"] += tp1 - tp0; phase["gather"] += time.perf_counter() - tp1
                 return tm, tm["accepted_alignments"], rows
             if not (args.no_hits or args.two_stage):
-                # calitas_search_hits: kernels through to the finished hits.txt text, one copy-back
-                text, rows = ctx.search_hits(G[0], "bench", params, "bench", "bench", decode=False)
+                # calitas_search_hits: kernels through to the finished hits.txt text, one copy-back.  (--dump-outputs: the last timed step
+                # makes the same call and hands the text back to the library after the timed region, once it is written.)
+                if hold is not None:
+                    view, rows = hold.enter_context(ctx.search_hits_view(G[0], "bench", params, "bench", "bench"))
+                    held_text.append(view)
+                else:
+                    text, rows = ctx.search_hits(G[0], "bench", params, "bench", "bench", decode=False)
                 tp1 = time.perf_counter()
                 tm = ctx.timing()
                 phase["search_hits"] += tp1 - tp0
@@ -723,8 +803,9 @@ def main():
         t0 = time.perf_counter()
         acc = {"scan": 0.0, "align": 0.0, "post": 0.0, "gpu": 0.0, "hitsk": 0.0, "copy": 0.0}
         last = None
-        for _ in range(args.steps):
-            tm, n_alns, rows = step()
+        hold, held_text = contextlib.ExitStack(), []
+        for i in range(args.steps):
+            tm, n_alns, rows = step(hold if args.dump_outputs and i == args.steps - 1 else None)
             acc["scan"] += tm["scan_kernel_ms"]; acc["align"] += tm["align_kernel_ms"]; acc["post"] += tm["host_post_ms"]
             acc["gpu"] += tm["gpu_total_ms"]; acc["hitsk"] += tm["hits_kernel_ms"]; acc["copy"] += tm["hits_copy_ms"]
             last = (tm, n_alns, rows)
@@ -739,6 +820,12 @@ def main():
             t = torch.tensor([dt], dtype=torch.float64, device="cpu" if args.rehearse_on_one_gpu else device)
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             dt = float(t.item())
+        if args.dump_outputs:
+            import ctypes
+            text = held_text[0] if args.config != 5 else (ctypes.c_char * last[0]["hits_bytes"]).from_address(c5_dst["addr"])
+            write_outputs(args.dump_outputs, hits_arrays(text, last[2], names))
+            log("outputs of the last step written to %s" % args.dump_outputs)
+        hold.close()
         text = None
         if keep_text and rank == 0 and args.config != 5:
             if len(G) > 1:
@@ -764,7 +851,7 @@ def main():
                 total = int(sum(int(tb[2 * r + 1]) for r in range(world)))
                 assert n_lines == total + 1, (n_lines, total)
                 log("%s partition: hits.txt gathered in shared memory has %d rows (%d bytes) from %d ranks" % (mode, total, n_bytes, world))
-                if mode == "windows":
+                if mode == "windows" and args.full:
                     # rank 0 holds the whole genome: the gathered file against ONE process's search, byte for byte (outside the timed region)
                     import zlib
                     gathered = b"".join((mm[4096 + r * shm["slot_bytes"]: 4096 + r * shm["slot_bytes"] + int(tb[2 * r])] if r == 0 else
@@ -779,7 +866,7 @@ def main():
                 os.unlink(shm["path"])
                 last = (last[0], last[1], total)
         batch_block = None
-        want_batch = args.batch_sharded if args.batch_sharded is not None else world > 1
+        want_batch = args.batch_sharded if args.batch_sharded is not None else (world > 1 and args.full)
         if want_batch and args.config == 3 and mode in ("windows", "none") and not (args.no_hits or args.two_stage):
             batch_block = measure_batch_sharded(ctx, params_rank, names, seqs)
         ctx.close()
@@ -792,7 +879,7 @@ def main():
     headline_mode = args.shard if world > 1 else "none"
     if headline_mode == "windows" and args.config != 3:
         headline_mode = "contigs"             # the guide batch and the variant branch are partitioned by contigs
-    m = measure(headline_mode, keep_text=(world == 1))
+    m = measure(headline_mode, keep_text=(world == 1 and args.full))
     second = None
     if world > 1 and args.secondary and not args.no_secondary and args.config == 3:
         other = "guides" if headline_mode in ("contigs", "windows") else "contigs"
@@ -920,7 +1007,7 @@ def main():
                 raise SystemExit("bench.py: the gathered text of the window partition differs from a single-process search")
         if second is not None:
             result["guide_sharded" if second["partition"] == "guides" else "contig_sharded"] = second
-        mb = args.cpu_sample_mb
+        mb = args.cpu_sample_mb if args.full else 0
         if mb < 0:
             # the oracle runs ~2.7 Mb/s per core and guide pass on the GPU box: ~15 s of CPU work
             mb = 40.0 * min(host_cores(), 16) / (2 if args.config == 4 else 4 if args.config == 5 else 1)

@@ -133,13 +133,15 @@ def test_lpt_partition_hg38_balance():
         assert max(loads) / (sum(loads) / n) < 1.06
 
 
-def test_bench_spawns_its_own_ranks():
+def test_bench_spawns_its_own_ranks(tmp_path):
     """`python bench.py --gpus 2` without a launcher: the script starts two fresh rank processes (RANK / LOCAL_RANK / WORLD_SIZE /
     MASTER_* set, 127.0.0.1), they rendezvous over gloo (--dry-run: no GPU work), and rank 0's line reports n_gpus = 2.  Under a
     launcher's WORLD_SIZE that disagrees with --gpus the script refuses to run."""
     import json
     import subprocess
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "MASTER_ADDR")}
+    # no topology to read, whatever the host has (a box with GPUs would pin the ranks and add rank_cpus to the line: the test below)
+    env["CALITAS_BENCH_SYSFS_ROOT"] = str(tmp_path / "no-sysfs")
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dry-run"], env=env, capture_output=True,
                          timeout=300)
     assert out.returncode == 0, out.stderr.decode()[-2000:]

@@ -6,10 +6,10 @@ TAG=${1:-r02}
 OUT="$ROOT/gpurun_out/$TAG"
 mkdir -p "$OUT"
 cd "$ROOT"
-python3 bench.py > "$OUT/${TAG}_bench_n1.json" 2> "$OUT/bench_n1.err"; echo "bench n1 $?"
+python3 bench.py --full > "$OUT/${TAG}_bench_n1.json" 2> "$OUT/bench_n1.err"; echo "bench n1 $?"
 CALITAS_CHUNKS=1 python3 bench.py --cpu-sample-mb 0 > "$OUT/${TAG}_bench_one_lane.json" 2> "$OUT/bench_one_lane.err"; echo "bench one lane $?"
-python3 bench.py --config 4 --steps 3 > "$OUT/${TAG}_bench_config4.json" 2> "$OUT/bench_config4.err"; echo "bench config4 $?"
-python3 bench.py --config 5 > "$OUT/${TAG}_bench_config5.json" 2> "$OUT/bench_config5.err"; echo "bench config5 $?"
+python3 bench.py --full --config 4 --steps 3 > "$OUT/${TAG}_bench_config4.json" 2> "$OUT/bench_config4.err"; echo "bench config4 $?"
+python3 bench.py --full --config 5 > "$OUT/${TAG}_bench_config5.json" 2> "$OUT/bench_config5.err"; echo "bench config5 $?"
 CALITAS_TRACE=1 STRESS_STREAM=1 python3 tools/stress_c5.py 1.0 8 2 > "$OUT/${TAG}_stress_c5_stream.txt" 2>&1; echo "stress stream $?"
 CALITAS_TRACE=1 python3 tools/c5_phases.py 1.0 > "$OUT/${TAG}_stress_c5_block.txt" 2>&1; echo "stress block $?"
 python3 tools/c2_speed.py > "$OUT/${TAG}_c2_speed.txt" 2>&1; echo "c2 $?"
