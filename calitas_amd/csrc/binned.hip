@@ -71,7 +71,6 @@ struct BinArgs {
   uint32_t* rows_list;               // bins with rows, in no particular order (one append per wave)
   uint32_t* rows_count;              // (zero at launch)
   unsigned long long* stamps;        // [0] align_kernel's start (written there), [1] bin_hits_small_kernel's: the device's wall clock
-  uint32_t dbg;                      // timing experiments (CALITAS_BINNED_SKIP; always 0 unless built with -DCALITAS_EXPERIMENTS)
 };
 
 __device__ __forceinline__ uint32_t wave_min_u32(uint32_t v) {
@@ -643,7 +642,7 @@ __global__ __launch_bounds__(64 * BIN_WAVES) void bin_rows_kernel(BinArgs a, Mid
       __hip_atomic_store(o.box, o.seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
     }
   }
-  if (flags != 0 || (a.dbg & 2u)) return;
+  if (flags != 0) return;
   if (n == 0) continue;
   const uint8_t* head = reinterpret_cast<const uint8_t*>(m.blob) + o.rc.head_off;     // constant pieces straight from global memory (L2-resident)
   const uint8_t* tail = reinterpret_cast<const uint8_t*>(m.blob) + o.rc.tail_off;
@@ -874,14 +873,8 @@ hipError_t binned_run(BinnedWork* pw, HitsWork** phw, const BinnedGeometry& geo,
   TRY(hipGetLastError());
   // the listed bins: a fixed grid that strides over the list (its length is on the device)
   const unsigned grid = std::min<uint32_t>(std::max<uint32_t>(geo.n_bins, 1u), 1024u);
-  int skip = 0;                                            // timing experiments only (the text is wrong): 1 = no wave-per-bin kernel, 2 = rows kernel posts and returns
-#ifdef CALITAS_EXPERIMENTS
-  if (const char* env = TUNE_GET("CALITAS_BINNED_SKIP")) skip = std::atoi(env);
-#endif
-  ba.dbg = (skip & 2) ? 2u : 0u;
-  if (!(skip & 1))
-    hipExtLaunchKernelGGL(bin_hits_kernel, dim3(grid), dim3(64), 0, stream, nullptr, ev_hits_done, 0, ba, ma, (const uint32_t*)w.complex_list,
-                          (const uint32_t*)w.complex_count);
+  hipExtLaunchKernelGGL(bin_hits_kernel, dim3(grid), dim3(64), 0, stream, nullptr, ev_hits_done, 0, ba, ma, (const uint32_t*)w.complex_list,
+                        (const uint32_t*)w.complex_count);
   TRY(hipGetLastError());
   if (!with_rows) return hipSuccess;                         // (the caller launches them itself: binned_rows)
   return launch_rows(w, hw, ba, ma, d_counters, stream, post, ev_rows_start, ev_rows_done);
@@ -893,11 +886,6 @@ hipError_t binned_rows(BinnedWork* pw, HitsWork** phw, const BinnedGeometry& geo
   if (!pw || !*phw) return hipErrorInvalidValue;
   BinArgs ba; MidArgs ma;
   fill_args(*pw, **phw, geo, ref, d_raw, d_guides, d_win_base, d_win, p, ba, ma);
-  int skip = 0;
-#ifdef CALITAS_EXPERIMENTS
-  if (const char* env = TUNE_GET("CALITAS_BINNED_SKIP")) skip = std::atoi(env);
-#endif
-  ba.dbg = (skip & 2) ? 2u : 0u;
   return launch_rows(*pw, **phw, ba, ma, d_counters, stream, post, nullptr, ev_rows_done, host_dst, host_dst_cap);
 }
 

@@ -144,7 +144,6 @@ struct SearchPlan {
   bool narrow_tail = false;           // a range of a chunked call that is not the last: its tail shares the chip with the next scan
   bool three_ranges = false;          // a range of a call cut into three or more
   bool last_range = false;            // ... and the last of them: no scan runs beside its tail
-  int range_index = 0;                // which range of a chunked call this is
   bool general_tail = false;          // the caller brings hits of its own into the row stage (HitsExt): the general kernels take them, the bins do not
 };
 
@@ -340,7 +339,6 @@ static void fill_kernel_args(calitas_ctx* ctx, const SearchPlan& pl, ScanArgs& s
   aa.slab = ctx->d_slab; aa.cand_count = ctx->d_counters + 4; aa.items = ctx->d_items; aa.item_count = ctx->d_counters + 3; aa.item_capacity = ctx->item_cap;
   aa.slab_bytes = pl.slab_bytes; aa.slots_per_rec = pl.slots_per_rec; aa.tile_words = (uint32_t)(ref.tile / 16);
   aa.gw_lo = pl.gw_lo; aa.gw_hi = pl.gw_hi;
-  if (const char* e = TUNE_GET("CALITAS_TAIL_PRIO_NARROW")) aa.low_prio = (pl.narrow_tail && std::atoi(e) == 0) ? 1 : 0;
   aa.sp.window_size = p.window_size; aa.sp.step = pl.step; aa.sp.n_guides = pl.n_guides;
   aa.sp.max_guide_diffs = p.max_guide_diffs; aa.sp.max_pam_mismatches = p.max_pam_mismatches;
   aa.sp.max_gaps = p.max_gaps_between_guide_and_pam;
@@ -440,6 +438,12 @@ static int narrow_blocks(const char* e, int fallback) {   // e = the switch's va
   if (e) { const int v = std::atoi(e); if (v >= 1 && v <= 8192) return v; }
   return fallback;
 }
+// align_kernel and trace_kernel of a plan on `stream` with the grids above; `trace_done` (may be null) is recorded behind trace_kernel.
+static hipError_t launch_align_trace(const SearchPlan& pl, const AlignArgs& aa, hipStream_t stream, hipEvent_t trace_done) {
+  hipError_t e = launch_align(aa, narrow_blocks(pl.narrow_tail ? TUNE_GET("CALITAS_ALIGN_BLOCKS_NARROW") : TUNE_GET("CALITAS_ALIGN_BLOCKS"), aa.pack16 && !aa.sp.per_matrix ? (pl.narrow_tail ? kAlignBlocksPackedNarrow : kAlignBlocksPacked) : kAlignBlocks), stream);
+  if (e != hipSuccess) return e;
+  return launch_trace(aa, narrow_blocks(pl.narrow_tail ? TUNE_GET("CALITAS_TRACE_BLOCKS_NARROW") : TUNE_GET("CALITAS_TRACE_BLOCKS"), kTraceBlocks), stream, trace_done);
+}
 
 // calitas_search; with dev != nullptr the accepted alignments stay on the device when the device filter handled them
 // (dev->valid), and *out stays NULL.  prelaunched: the scan stage of this lane was queued by the caller on another stream
@@ -483,10 +487,9 @@ static int search_run(calitas_ctx* ctx, const SearchPlan& pl, calitas_aln_t** ou
     }
     ScanArgs sa; AlignArgs aa;
     fill_kernel_args(ctx, pl, sa, aa);
-    HIP_TRY(ctx, launch_align(aa, narrow_blocks(pl.narrow_tail ? TUNE_GET("CALITAS_ALIGN_BLOCKS_NARROW") : TUNE_GET("CALITAS_ALIGN_BLOCKS"), aa.pack16 && !aa.sp.per_matrix ? (pl.narrow_tail ? kAlignBlocksPackedNarrow : kAlignBlocksPacked) : kAlignBlocks), ctx->stream));
     // (trace_kernel can post the counters itself from its last workgroup -- launch_trace's `post` -- but finding the last of 2048
     // workgroups is 2048 atomics on one word, ~8 ns each: 20-30 us against the ~10 us of this launch)
-    HIP_TRY(ctx, launch_trace(aa, narrow_blocks(pl.narrow_tail ? TUNE_GET("CALITAS_TRACE_BLOCKS_NARROW") : TUNE_GET("CALITAS_TRACE_BLOCKS"), kTraceBlocks), ctx->stream, ctx->ev[2]));
+    HIP_TRY(ctx, launch_align_trace(pl, aa, ctx->stream, ctx->ev[2]));
     if (speculate) {
       HIP_TRY(ctx, select_run_speculative(&ctx->select, ctx->d_raw, ctx->d_counters, ctx->rec_cap, ctx->raw_cap, ctx->item_cap, ctx->d_guides,
                                           own->d_win_base, own->d_win, pl.win_lo, pl.win_n, max_total, p.max_overlap, ctx->stream, &d_spec, &ctx->mbox));
@@ -773,25 +776,35 @@ static void dma_open_once(calitas_ctx* owner) {
   }
 }
 
+// Waits for a lane's row kernels: for rows_done if the caller recorded it (other work may be queued behind it on the stream), else
+// for the lane's stream.
+static hipError_t rows_sync(calitas_ctx* lane, hipEvent_t rows_done) {
+  return rows_done ? calitas_spin_sync(rows_done) : calitas_spin_sync(lane->stream);
+}
+
+// Once the binned rows kernel's text is complete: did it find a row whose length differs from the one its first kernel counted?
+static int binned_late_failed(calitas_ctx* lane) {
+  if (lane->binned_late_check && lane->mbox.host && lane->mbox.host[BIN_BOX_LATE] != 0)
+    return fail(lane, CALITAS_EHIP, "binned rows kernel: a row's length differs between the two kernels (internal error)");
+  return CALITAS_OK;
+}
+
 static int text_to_host(calitas_ctx* owner, calitas_ctx* lane, char* dst, const char* src, size_t n, std::mutex* copy_mu, double* ms_out,
                         hipEvent_t rows_done = nullptr) {
   dma_open_once(owner);
   if (lane->binned_late_check && src && src == binned_host_text(lane->binned)) {   // the rows kernel wrote the text into host memory itself
-    if (rows_done) HIP_TRY(lane, calitas_spin_sync(rows_done)); else HIP_TRY(lane, calitas_spin_sync(lane->stream));
+    HIP_TRY(lane, rows_sync(lane, rows_done));
     g_marks.mark("rows-done");
-    if (lane->mbox.host && lane->mbox.host[BIN_BOX_LATE] != 0)
-      return fail(lane, CALITAS_EHIP, "binned rows kernel: a row's length differs between the two kernels (internal error)");
+    if (int r = binned_late_failed(lane)) return r;
     std::memcpy(dst, src, n);
     if (ms_out) *ms_out = 0;
     return CALITAS_OK;
   }
   if (owner->dma.usable()) {
-    // (rows_done: the caller recorded it behind the row kernels and other work may already be queued behind it on the stream)
-    if (rows_done) HIP_TRY(lane, calitas_spin_sync(rows_done)); else HIP_TRY(lane, calitas_spin_sync(lane->stream));
+    HIP_TRY(lane, rows_sync(lane, rows_done));
     g_marks.mark("rows-done");
     const auto t0 = std::chrono::steady_clock::now();
-    if (lane->binned_late_check && lane->mbox.host && lane->mbox.host[BIN_BOX_LATE] != 0)
-      return fail(lane, CALITAS_EHIP, "binned rows kernel: a row's length differs between the two kernels (internal error)");
+    if (int r = binned_late_failed(lane)) return r;
     if (owner->dma.copy_to_host(dst, src, n)) {
       g_marks.mark("copied");
       if (ms_out) *ms_out = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
@@ -816,8 +829,7 @@ static int text_to_host(calitas_ctx* owner, calitas_ctx* lane, char* dst, const 
     HIP_TRY(lane, hipEventRecord(lane->ev[7], cs));
   }
   HIP_TRY(lane, calitas_spin_sync(lane->ev[7]));
-  if (lane->binned_late_check && lane->mbox.host && lane->mbox.host[BIN_BOX_LATE] != 0)
-    return fail(lane, CALITAS_EHIP, "binned rows kernel: a row's length differs between the two kernels (internal error)");
+  if (int r = binned_late_failed(lane)) return r;
   float ms = 0;
   (void)hipEventElapsedTime(&ms, lane->ev[6], lane->ev[7]);
   if (ms_out) *ms_out = ms;
@@ -840,6 +852,15 @@ struct LaneText {
   const uint64_t* ext_place = nullptr; // ... and where (HitsResult::ext_place)
   calitas_timing_t tm{};
 };
+
+// A lane's kernel times and counts added to the call's.
+static void add_lane_timing(calitas_timing_t& tm, const calitas_timing_t& l) {
+  tm.scan_kernel_ms += l.scan_kernel_ms; tm.align_kernel_ms += l.align_kernel_ms; tm.gpu_total_ms += l.gpu_total_ms;
+  tm.host_post_ms += l.host_post_ms; tm.bases_scanned += l.bases_scanned; tm.packed_bytes += l.packed_bytes;
+  tm.scan_records += l.scan_records; tm.candidate_columns += l.candidate_columns; tm.raw_alignments += l.raw_alignments;
+  tm.accepted_alignments += l.accepted_alignments; tm.retries += l.retries;
+  tm.hits_kernel_ms += l.hits_kernel_ms; tm.hits_copy_ms += l.hits_copy_ms; tm.binned_lanes += l.binned_lanes; tm.owned_general_lanes += l.owned_general_lanes;
+}
 
 // After the text of a lane has been copied (so its rows kernel is done): did the rows kernel of the general stage object to anything?
 static int rows_late_check(calitas_ctx* lane, const LaneText& lt) {
@@ -868,11 +889,9 @@ static int compact_rows_to_host(calitas_ctx* owner, calitas_ctx* lane, LaneText&
     return CALITAS_OK;
   };
   if (!owner->dma.usable() || in_host_text || nbytes < std::min<size_t>(1u << 20, 2 * piece)) return whole();   // (a short text: one copy, then the rows)
-  // (rows_done: the caller recorded it behind the row kernels and other work may already be queued behind it on the stream)
-  if (rows_done) HIP_TRY(lane, calitas_spin_sync(rows_done)); else HIP_TRY(lane, calitas_spin_sync(lane->stream));
+  HIP_TRY(lane, rows_sync(lane, rows_done));
   g_marks.mark("rows-done");
-  if (lane->binned_late_check && lane->mbox.host && lane->mbox.host[BIN_BOX_LATE] != 0)
-    return fail(lane, CALITAS_EHIP, "binned rows kernel: a row's length differs between the two kernels (internal error)");
+  if (int r = binned_late_failed(lane)) return r;
   const auto t0 = std::chrono::steady_clock::now();
   std::vector<unsigned long long> tickets;
   if (!owner->dma.start_pieces(staging, lt.d_text, nbytes, piece, tickets)) {
@@ -938,7 +957,6 @@ static bool binned_possible(calitas_ctx* lane, const SearchPlan& pl) {
   bool want = !pl.three_ranges || pl.owned || pl.last_range;   // (a stretch that cuts a contig: only the bins can own it)
   if (const char* e = TUNE_GET("CALITAS_BINNED")) {
     if (std::strcmp(e, "last") == 0) want = !pl.narrow_tail;
-    else if (std::strcmp(e, "from1") == 0) want = !pl.three_ranges || pl.owned || pl.range_index >= 1;   // (experiment: every range but the first)
     else want = std::atoi(e) != 0;
   }
   if (!want) return false;
@@ -1167,9 +1185,8 @@ static int lane_rows_binned(calitas_ctx* lane, const SearchPlan& pl, bool prelau
   ScanArgs sa; AlignArgs aa;
   fill_kernel_args(lane, pl, sa, aa);
   binned_fill_align_args(lane->binned, geo, aa);
-  HIP_TRY(lane, launch_align(aa, narrow_blocks(pl.narrow_tail ? TUNE_GET("CALITAS_ALIGN_BLOCKS_NARROW") : TUNE_GET("CALITAS_ALIGN_BLOCKS"), aa.pack16 && !aa.sp.per_matrix ? (pl.narrow_tail ? kAlignBlocksPackedNarrow : kAlignBlocksPacked) : kAlignBlocks), lane->stream));
   // (no events on these dispatches: each would hold back the kernel behind it by ~5 us; the kernels stamp the device's wall clock instead)
-  HIP_TRY(lane, launch_trace(aa, narrow_blocks(pl.narrow_tail ? TUNE_GET("CALITAS_TRACE_BLOCKS_NARROW") : TUNE_GET("CALITAS_TRACE_BLOCKS"), kTraceBlocks), lane->stream, nullptr));
+  HIP_TRY(lane, launch_align_trace(pl, aa, lane->stream, nullptr));
   HIP_TRY(lane, binned_run(lane->binned, &lane->hits, geo, hr, lane->d_raw, lane->d_guides, own->d_win_base, own->d_win, bp, lane->d_counters, lane->stream,
                            &lane->mbox, nullptr, nullptr, lane->ev[5], dest == nullptr));
   char* host_dst = nullptr;
@@ -1323,12 +1340,7 @@ static int ensure_lanes(calitas_ctx* ctx, size_t k) {
   while (ctx->lanes.size() < k) {
     calitas_ctx* c = new calitas_ctx();
     c->device = ctx->device; c->parent = ctx;
-    int lane_prio = greatest;
-    if (const char* e = TUNE_GET("CALITAS_LANE_PRIO")) {       // experiment: the tails do not outrank the scan ("low": none does; "low0" / "low01": the first / the first two lanes)
-      const size_t idx = ctx->lanes.size();
-      if (std::strcmp(e, "low") == 0 || (std::strcmp(e, "low0") == 0 && idx == 0) || (std::strcmp(e, "low01") == 0 && idx <= 1)) lane_prio = least;
-    }
-    bool ok = hipStreamCreateWithPriority(&c->stream, hipStreamNonBlocking, lane_prio) == hipSuccess;
+    bool ok = hipStreamCreateWithPriority(&c->stream, hipStreamNonBlocking, greatest) == hipSuccess;
     for (int i = 0; i < 8; i++) ok = ok && hipEventCreateWithFlags(&c->ev[i], i < 6 ? hipEventReleaseToDevice : hipEventDefault) == hipSuccess;   // as in calitas_create
     ok = ok && hipEventCreateWithFlags(&c->scan_done, hipEventReleaseToDevice) == hipSuccess;   // timed: it also brackets the scan
     ok = ok && hipEventCreateWithFlags(&c->rows_ready, hipEventDisableTiming | hipEventReleaseToDevice) == hipSuccess;
@@ -1370,7 +1382,6 @@ void calitas_destroy_lanes(calitas_ctx* ctx) {
   for (calitas_ctx* c : ctx->lanes) calitas_destroy(c);
   ctx->lanes.clear();
   if (ctx->scan_stream) { (void)hipStreamDestroy(ctx->scan_stream); ctx->scan_stream = nullptr; }
-  for (auto& st : ctx->scan_more) if (st) { (void)hipStreamDestroy(st); st = nullptr; }
   if (ctx->copy_stream) { (void)hipStreamDestroy(ctx->copy_stream); ctx->copy_stream = nullptr; }
 }
 
@@ -1598,11 +1609,7 @@ static int search_hits_sequential(calitas_ctx* ctx, const calitas_guide_t* guide
         if ((rc = rows_late_check(ctx, lt)) != CALITAS_OK) break;
         total += full_bytes;
         rows += lt.rows;
-        tm.scan_kernel_ms += lt.tm.scan_kernel_ms; tm.align_kernel_ms += lt.tm.align_kernel_ms; tm.gpu_total_ms += lt.tm.gpu_total_ms;
-        tm.host_post_ms += lt.tm.host_post_ms; tm.bases_scanned += lt.tm.bases_scanned; tm.packed_bytes += lt.tm.packed_bytes;
-        tm.scan_records += lt.tm.scan_records; tm.candidate_columns += lt.tm.candidate_columns; tm.raw_alignments += lt.tm.raw_alignments;
-        tm.accepted_alignments += lt.tm.accepted_alignments; tm.retries += lt.tm.retries; tm.hits_copy_ms += lt.tm.hits_copy_ms;
-        tm.binned_lanes += lt.tm.binned_lanes; tm.owned_general_lanes += lt.tm.owned_general_lanes;
+        add_lane_timing(tm, lt.tm);
         { std::lock_guard<std::mutex> lk(mu); sl.state = 0; }
         cv.notify_all();
         continue;
@@ -1684,11 +1691,7 @@ static int search_hits_sequential(calitas_ctx* ctx, const calitas_guide_t* guide
       total += (size_t)lt.bytes;
     }
     rows += lt.rows;
-    tm.scan_kernel_ms += lt.tm.scan_kernel_ms; tm.align_kernel_ms += lt.tm.align_kernel_ms; tm.gpu_total_ms += lt.tm.gpu_total_ms;
-    tm.host_post_ms += lt.tm.host_post_ms; tm.bases_scanned += lt.tm.bases_scanned; tm.packed_bytes += lt.tm.packed_bytes;
-    tm.scan_records += lt.tm.scan_records; tm.candidate_columns += lt.tm.candidate_columns; tm.raw_alignments += lt.tm.raw_alignments;
-    tm.accepted_alignments += lt.tm.accepted_alignments; tm.retries += lt.tm.retries; tm.hits_copy_ms += lt.tm.hits_copy_ms;
-    tm.binned_lanes += lt.tm.binned_lanes; tm.owned_general_lanes += lt.tm.owned_general_lanes;
+    add_lane_timing(tm, lt.tm);
     {
       std::lock_guard<std::mutex> lk(mu);
       sl.state = 0;
@@ -2167,8 +2170,7 @@ static int search_hits_attempt(calitas_ctx* ctx, const calitas_guide_t* guide, c
       if (lt.d_text != text_dev + hlen + offset) return fail(lane, CALITAS_EHIP, "a lane's text was written to another place than the one it belongs to (internal error)");
       HIP_TRY(lane, calitas_spin_sync(lane->stream));
       g_marks.mark("rows-done");
-      if (lane->binned_late_check && lane->mbox.host && lane->mbox.host[BIN_BOX_LATE] != 0)
-        return fail(lane, CALITAS_EHIP, "binned rows kernel: a row's length differs between the two kernels (internal error)");
+      if (int r = binned_late_failed(lane)) return r;
       lt.tm.hits_copy_ms = 0;
       lt.tm.hits_kernel_ms = rows_stage_ms(lane, lt.tm);
       return CALITAS_OK;
@@ -2214,7 +2216,7 @@ static int search_hits_attempt(calitas_ctx* ctx, const calitas_guide_t* guide, c
       for (int k = ranges[c].first; k < ranges[c].second; k++) { q.bases += ref.contigs[k].len; q.win_n += window_count(ref.contigs[k].len, q.step); }
       plan_bins(ctx, q, ranges[c].first, ranges[c].second);
       }
-      q.narrow_tail = c + 1 < K; q.three_ranges = K >= 3; q.last_range = K >= 3 && c + 1 == K; q.range_index = (int)c;
+      q.narrow_tail = c + 1 < K; q.three_ranges = K >= 3; q.last_range = K >= 3 && c + 1 == K;
       rc = lane_prepare(lanes[c], q);
       if (rc) ctx->err = lanes[c]->err;
     }
@@ -2248,56 +2250,40 @@ static int search_hits_attempt(calitas_ctx* ctx, const calitas_guide_t* guide, c
     // (Holding the scan of a range back until the aligner kernels of the range before it are done -- they take half as long again
     // beside a scan, the scan twice as long beside them -- was tried: 2.77 against 2.55 ms per pass.)
     // The inputs of all ranges (guide constants, cleared counters: a 272-byte upload and a fill per lane, 60-140 us of the scan stream
-    // each when they sit between two scans) are queued ahead of the scans; CALITAS_INPUTS_FIRST=0: each before its own scan, 1: all of
-    // them ahead of the first scan on the scan stream (round 2), 2 (default, round 3: 2.320 against 2.335 ms per hg38-sized call, 0.510
-    // against 0.517 for an eighth, interleaved):
-    bool inputs_first = true;
-    int inputs_mode = 2;
-    if (const char* e = TUNE_GET("CALITAS_INPUTS_FIRST")) { inputs_mode = std::atoi(e); inputs_first = inputs_mode != 0; }
-    // mode 2: the first range's inputs ahead of its scan on the scan stream, the later ranges' on their own streams (which have nothing
-    // else to do yet); the scan stream waits for each with an event that has long fired when its turn comes.  A range's small inputs
-    // are ONE launch (queue_lane_setup) where they used to be two stream commands for the scan and three or four for the row stage.
+    // each when they sit between two scans) are queued ahead of the scans (round 3: 2.320 against 2.335 ms per hg38-sized call, 0.510
+    // against 0.517 for an eighth, interleaved, than all of them ahead of the first scan on the scan stream as in round 2): the first
+    // range's inputs ahead of its scan on the scan stream, the later ranges' on their own streams (which have nothing else to do yet);
+    // the scan stream waits for each with an event that has long fired when its turn comes.  A range's small inputs are ONE launch
+    // (queue_lane_setup) where they used to be two stream commands for the scan and three or four for the row stage.
     std::vector<char> rows_queued(K, 0);                      // the lane's row constants went out with its scan inputs (one launch for both)
     const bool device_rows_early = !TUNE_GET("CALITAS_HOST_HITS");
-    if (inputs_mode == 2) {
-      // the first range: its scan inputs (one launch: queue_lane_setup) and its scan, before anything else is prepared
-      bool one = false;
-      rc = queue_lane_setup(lanes[0], plans[0], nullptr, ctx->scan_stream, &one);
-      if (!rc && !one) rc = queue_scan_inputs(lanes[0], plans[0], ctx->scan_stream);
-      if (!rc) rc = launch_scan_stage(lanes[0], plans[0], ctx->scan_stream, true);
-      if (rc) ctx->err = lanes[0]->err;
+    // the first range: its scan inputs (one launch: queue_lane_setup) and its scan, before anything else is prepared
+    bool one = false;
+    rc = queue_lane_setup(lanes[0], plans[0], nullptr, ctx->scan_stream, &one);
+    if (!rc && !one) rc = queue_scan_inputs(lanes[0], plans[0], ctx->scan_stream);
+    if (!rc) rc = launch_scan_stage(lanes[0], plans[0], ctx->scan_stream, true);
+    if (rc) ctx->err = lanes[0]->err;
+    g_marks.mark("scan-queued");
+    if (!rc) make_rows();
+    g_marks.mark("row-strings");
+    // the later ranges: scan inputs and row constants in one launch on the range's own stream, then its scan behind the event
+    for (size_t c = 1; c < K && !rc; c++) {
+      one = false;
+      if (device_rows_early) rc = queue_lane_setup(lanes[c], plans[c], &rs_lane(c), lanes[c]->stream, &one);
+      if (!rc && one) rows_queued[c] = 1;
+      if (!rc && !one) rc = queue_scan_inputs(lanes[c], plans[c], lanes[c]->stream);
+      if (!rc) rc = hip_rc(hipEventRecord(lanes[c]->inputs_ready, lanes[c]->stream), "hipEventRecord");
+      if (!rc) rc = hip_rc(hipStreamWaitEvent(ctx->scan_stream, lanes[c]->inputs_ready, 0), "hipStreamWaitEvent");
+      if (!rc) rc = launch_scan_stage(lanes[c], plans[c], ctx->scan_stream, true);           // records lanes[c]->scan_done
+      if (rc && ctx->err.empty()) ctx->err = lanes[c]->err;
       g_marks.mark("scan-queued");
-      if (!rc) make_rows();
-      g_marks.mark("row-strings");
-      // the later ranges: scan inputs and row constants in one launch on the range's own stream, then its scan behind the event
-      for (size_t c = 1; c < K && !rc; c++) {
-        one = false;
-        if (device_rows_early) rc = queue_lane_setup(lanes[c], plans[c], &rs_lane(c), lanes[c]->stream, &one);
-        if (!rc && one) rows_queued[c] = 1;
-        if (!rc && !one) rc = queue_scan_inputs(lanes[c], plans[c], lanes[c]->stream);
-        if (!rc) rc = hip_rc(hipEventRecord(lanes[c]->inputs_ready, lanes[c]->stream), "hipEventRecord");
-        if (!rc) rc = hip_rc(hipStreamWaitEvent(ctx->scan_stream, lanes[c]->inputs_ready, 0), "hipStreamWaitEvent");
-        if (!rc) rc = launch_scan_stage(lanes[c], plans[c], ctx->scan_stream, true);           // records lanes[c]->scan_done
-        if (rc && ctx->err.empty()) ctx->err = lanes[c]->err;
-        g_marks.mark("scan-queued");
-      }
-      // ... and the first range's row constants (its tail starts when its scan ends)
-      if (!rc && device_rows_early) {
-        one = false;
-        rc = queue_lane_setup(lanes[0], plans[0], &rs_lane(0), lanes[0]->stream, &one, false);
-        if (!rc && one) rows_queued[0] = 1;
-        if (rc) ctx->err = lanes[0]->err;
-      }
-    } else {
-      if (inputs_first)
-        for (size_t c = 0; c < K && !rc; c++) { rc = queue_scan_inputs(lanes[c], plans[c], ctx->scan_stream); if (rc) ctx->err = lanes[c]->err; }
-      for (size_t c = 0; c < K && !rc; c++) {
-        rc = launch_scan_stage(lanes[c], plans[c], ctx->scan_stream, inputs_first);           // records lanes[c]->scan_done
-        if (rc) ctx->err = lanes[c]->err;
-        g_marks.mark("scan-queued");
-      }
-      if (!rc) make_rows();
-      g_marks.mark("row-strings");
+    }
+    // ... and the first range's row constants (its tail starts when its scan ends)
+    if (!rc && device_rows_early) {
+      one = false;
+      rc = queue_lane_setup(lanes[0], plans[0], &rs_lane(0), lanes[0]->stream, &one, false);
+      if (!rc && one) rows_queued[0] = 1;
+      if (rc) ctx->err = lanes[0]->err;
     }
     for (size_t c = 0; c < K && !rc; c++) {
       // the row constants of a range go onto its stream before the wait for its scan: in place while the scan runs
@@ -2439,11 +2425,7 @@ static int search_hits_attempt(calitas_ctx* ctx, const calitas_guide_t* guide, c
   uint64_t rows = 0;
   for (auto& lt : parts) {
     total += lt.bytes; rows += lt.rows;
-    tm.scan_kernel_ms += lt.tm.scan_kernel_ms; tm.align_kernel_ms += lt.tm.align_kernel_ms; tm.gpu_total_ms += lt.tm.gpu_total_ms;
-    tm.host_post_ms += lt.tm.host_post_ms; tm.bases_scanned += lt.tm.bases_scanned; tm.packed_bytes += lt.tm.packed_bytes;
-    tm.scan_records += lt.tm.scan_records; tm.candidate_columns += lt.tm.candidate_columns; tm.raw_alignments += lt.tm.raw_alignments;
-    tm.accepted_alignments += lt.tm.accepted_alignments; tm.retries += lt.tm.retries;
-    tm.hits_kernel_ms += lt.tm.hits_kernel_ms; tm.hits_copy_ms += lt.tm.hits_copy_ms; tm.binned_lanes += lt.tm.binned_lanes; tm.owned_general_lanes += lt.tm.owned_general_lanes;
+    add_lane_timing(tm, lt.tm);
   }
   text[total] = 0;
   tm.hit_rows = rows; tm.hits_bytes = total; tm.lanes = (uint32_t)parts.size();
@@ -2523,7 +2505,7 @@ int calitas_search_hits_batch_impl(calitas_ctx* ctx, int32_t n_guides, const cal
   // runs on a stretch, which only the bins can own.  (Round 3 got there by accident: the first guide that crowded a bin switched the
   // bins off for every guide behind it; with the decline remembered per guide the batch took 328 instead of 295 ms per 96 guides.)
   // (A reference below 2 Gb keeps the bins, as a single call on it does: fewer launches, and its scans are short.)
-  if (!ranged && ctx->ref.total_bases >= (2048ull << 20) && !TUNE_GET("CALITAS_BATCH_BINNED")) for (auto& q : plans) q.three_ranges = true;
+  if (!ranged && ctx->ref.total_bases >= (2048ull << 20)) for (auto& q : plans) q.three_ranges = true;
   std::vector<char> owned_ok((size_t)n_guides, 1);
   if (ranged) {
     if (params->first_window < 0 || params->n_windows <= 0 || (uint64_t)params->first_window + (uint64_t)params->n_windows > plans[0].win_n)
@@ -2537,15 +2519,6 @@ int calitas_search_hits_batch_impl(calitas_ctx* ctx, int32_t n_guides, const cal
   if (rc) return rc;
   rc = ensure_window_table(ctx, plans[0], ctx->scan_stream);
   if (rc) return rc;
-  int n_scan_streams = 1;
-  if (const char* e = TUNE_GET("CALITAS_BATCH_SCAN_STREAMS")) n_scan_streams = std::max(1, std::min(4, std::atoi(e)));
-  if (n_scan_streams > 1) {
-    int least = 0, greatest = 0;
-    (void)hipDeviceGetStreamPriorityRange(&least, &greatest);
-    for (int k = 0; k + 1 < n_scan_streams; k++)
-      if (!ctx->scan_more[k]) HIP_TRY(ctx, hipStreamCreateWithPriority(&ctx->scan_more[k], hipStreamNonBlocking, least));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->scan_stream));         // (the window table, if it was just built, is there for all of them)
-  }
   const PackedRef& ref = ctx->ref;
   std::mutex scan_mu, copy_mu;
   const bool device_rows = !TUNE_GET("CALITAS_HOST_HITS");
@@ -2575,8 +2548,7 @@ int calitas_search_hits_batch_impl(calitas_ctx* ctx, int32_t n_guides, const cal
     // for this scan
     if (device_rows) HIP_TRY(lane, queue_row_constants(lane, pl, f.rs));   // before the wait for the scan is queued
     std::lock_guard<std::mutex> lk(scan_mu);
-    const int turn = g % n_scan_streams;
-    return launch_scan_stage(lane, pl, turn == 0 ? ctx->scan_stream : ctx->scan_more[turn - 1]);       // records lane->scan_done
+    return launch_scan_stage(lane, pl, ctx->scan_stream);       // records lane->scan_done
   };
   auto run_tail = [&](calitas_ctx* lane, InFlight& f, hipEvent_t scans_done) -> int {
     HIP_TRY(lane, hipStreamWaitEvent(lane->stream, scans_done, 0));
@@ -2595,17 +2567,6 @@ int calitas_search_hits_batch_impl(calitas_ctx* ctx, int32_t n_guides, const cal
     if (!text) return fail(lane, CALITAS_EINVAL, "out of memory");
     std::memcpy(text, rs.header.data(), hlen);
     if (lt.bytes && lt.on_host) std::memcpy(text + hlen, lt.host_rows.data(), (size_t)lt.bytes);
-#ifdef CALITAS_EXPERIMENTS
-    else if (const char* mode = TUNE_GET("CALITAS_BATCH_TEXT")) {   // what the batch costs without its texts' way home (the texts are wrong)
-      if (!std::strcmp(mode, "copy") && lt.bytes) {
-        char* staging = (char*)calitas_out_alloc_pinned((size_t)lt.bytes);
-        if (!staging) { calitas_free(text); return fail(lane, CALITAS_EINVAL, "out of memory"); }
-        int cr = text_to_host(ctx, lane, staging, lt.d_text, (size_t)lt.bytes, &copy_mu, &lt.tm.hits_copy_ms);
-        calitas_free(staging);
-        if (cr) { calitas_free(text); return cr; }
-      } else HIP_TRY(lane, calitas_spin_sync(lane->stream));
-    }
-#endif
     else if (lt.bytes && expand) {
       char* staging = (char*)calitas_out_alloc_pinned((size_t)lt.bytes);
       if (!staging) { calitas_free(text); return fail(lane, CALITAS_EINVAL, "out of memory"); }

@@ -1057,14 +1057,10 @@ static int search_variants_impl(calitas_ctx* ctx, const calitas_guide_t* guide, 
   source.compact_rows = device_merge && TUNE_ON("CALITAS_VARIANTS_COMPACT");
   // Rows on demand (hits.hpp, HitsExt::rows_for): an entry's row is made when the device's walk has kept it -- one in ten at BASELINE config
   // 5's size; the rows of all two million entries were 0.37-0.42 s of the lifter thread's 0.7 s per call, and 1.1 GB on their way to the
-  // device.  CALITAS_VARIANTS_ROWS=all: every entry's row up front, as before (the two give the same bytes: tests/test_gpu_variants.py).
-  bool rows_on_demand = device_merge;
-  if (const char* e = TUNE_GET("CALITAS_VARIANTS_ROWS")) rows_on_demand = rows_on_demand && std::strcmp(e, "all") != 0;
-  // ... and the rows of the entries the device keeps never go to the device: the rows kernel leaves holes, the host fills them once the
-  // text is there (HitsExtRows::fill_on_host).  CALITAS_VARIANTS_ROWS=device: the kept rows go up and the rows kernel copies them, as in
-  // the first half of round 5; compact rows (CALITAS_VARIANTS_COMPACT) imply it -- a hole's place is known in the text the device wrote.
-  bool fill_on_host = rows_on_demand && !source.compact_rows;
-  if (const char* e = TUNE_GET("CALITAS_VARIANTS_ROWS")) fill_on_host = fill_on_host && std::strcmp(e, "device") != 0;
+  // device (finish_rows).  And the rows of the entries the device keeps never go to the device: the rows kernel leaves holes, the host
+  // fills them once the text is there (HitsExtRows::fill_on_host).  Compact rows (CALITAS_VARIANTS_COMPACT) send the kept rows up instead
+  // and the rows kernel copies them -- a hole's place is known in the text the device wrote.
+  const bool fill_on_host = device_merge && !source.compact_rows;
   if (fill_on_host) filler.start(-1);
   struct JoinHelper {                                                                               // (declared behind everything the helper thread uses)
     std::thread& t; decltype(publish)& pub; size_t all;
@@ -1221,7 +1217,7 @@ static int search_variants_impl(calitas_ctx* ctx, const calitas_guide_t* guide, 
   // per call at BASELINE config 5's size, and every other stage of the variant half waited for it).
   // The placed entries -- kept by the walks of their own groups, so their rows are wanted whatever the device decides -- get their rows
   // now; the plain ones when the device's walk has kept them (next to none: they repeat reference hits), on the helper thread inside the
-  // contig's row stage.
+  // contig's row stage.  (The device merge's only: the host merge makes no rows here.)
   auto finish_rows = [&](size_t c) -> int {
     ContigExt& x = cx[c];
     const size_t n = x.entry.size(), n_plain = x.n_plain;
@@ -1260,24 +1256,15 @@ static int search_variants_impl(calitas_ctx* ctx, const calitas_guide_t* guide, 
         auto held = std::make_shared<std::vector<uint64_t>>(place, place + cx[c].entry.size());   // (place[] is the device stage's: valid during this call only)
         return filler.enqueue([work, held](std::string&) -> int { return work(held->data()); }, 64, nullptr);
       };
-    if (rows_on_demand) {
-      // (runs on the helper thread; cx[c] is this contig's alone from here on)
-      x.ext.rows_for = [&, c, n_plain](const uint8_t* kept, HitsExtRows* out) -> int {
-        const auto t_d = std::chrono::steady_clock::now();
-        std::fill(cx[c].row_len.begin(), cx[c].row_len.begin() + (std::ptrdiff_t)n_plain, 0u);   // (a second row stage of the same contig starts afresh)
-        make_rows(c, 0, n_plain, kept, cx[c].segs);
-        const int r = rows_of(c, out);
-        ns_demand += (long long)(ms_since(t_d) * 1e6);
-        return r;
-      };
-      ms_make += ms_since(t1);
-      return CALITAS_OK;
-    }
-    make_rows(c, 0, n_plain, nullptr, x.segs);
-    HitsExtRows made;
-    const int r = rows_of(c, &made);
-    if (r) return r;
-    x.ext.row_off = made.row_off; x.ext.rows = nullptr; x.ext.n_seg = made.n_seg; x.ext.seg = made.seg; x.ext.seg_off = made.seg_off;
+    // (runs on the helper thread; cx[c] is this contig's alone from here on)
+    x.ext.rows_for = [&, c, n_plain](const uint8_t* kept, HitsExtRows* out) -> int {
+      const auto t_d = std::chrono::steady_clock::now();
+      std::fill(cx[c].row_len.begin(), cx[c].row_len.begin() + (std::ptrdiff_t)n_plain, 0u);   // (a second row stage of the same contig starts afresh)
+      make_rows(c, 0, n_plain, kept, cx[c].segs);
+      const int r = rows_of(c, out);
+      ns_demand += (long long)(ms_since(t_d) * 1e6);
+      return r;
+    };
     ms_make += ms_since(t1);
     return CALITAS_OK;
   };

@@ -396,30 +396,31 @@ def test_callers_on_several_threads_share_the_worker_pool(C, tmp_path):
 def test_every_environment_switch_is_in_the_table():
     """calitas_switches() (calitas_amd/csrc/tuning.hpp) lists every CALITAS_* switch the library reads, and nothing else: the sources
     read them through TUNE_GET / TUNE_ON / TUNE_SET only (a name missing from the table does not compile -- nothing in the library
-    stops the process over a switch), and no std::getenv of a CALITAS_ name is left.  Switches that trade correct output for a timing
-    experiment (CALITAS_BINNED_SKIP) exist in `make EXPERIMENTS=1` builds only: the shipped library does not list or read them."""
+    stops the process over a switch), and no std::getenv of a CALITAS_ name is left.  There is one build of the library -- no source
+    names an experiments-only macro -- and none of its switches trades correct output for a timing experiment."""
     import glob
     import re
     import calitas_amd  # noqa: F401
     from calitas_amd import _lib
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    listed = {ln.split(" ", 1)[0] for ln in _lib.lib.calitas_switches().decode().splitlines() if ln}
+    table = [ln for ln in _lib.lib.calitas_switches().decode().splitlines() if ln]
+    listed = {ln.split(" ", 1)[0] for ln in table}
     used, raw, aborts = set(), [], []
     for f in glob.glob(os.path.join(root, "calitas_amd", "csrc", "*.[ch]*")):
         if f.endswith(".o"):
             continue
         text = open(f, errors="replace").read()
+        assert "CALITAS_EXPERIMENT" not in text, f
         aborts += [os.path.basename(f)] if re.search(r"\babort\s*\(", re.sub(r"//[^\n]*", "", text)) and not f.endswith("dbg_alloc.hpp") else []
         if f.endswith("tuning.hpp"):
             continue
-        text = re.sub(r"#ifdef CALITAS_EXPERIMENTS.*?#endif", "", text, flags=re.S)   # (not in the shipped build)
         used |= set(re.findall(r'TUNE_(?:GET|ON|SET)\("(CALITAS_[A-Z0-9_]+)"\)', text))
         raw += re.findall(r'[^:]getenv\("(CALITAS_[A-Z0-9_]+)"\)', text)
         assert not re.findall(r"tune::(?:get|on|is_set)\(", text), f
     assert not raw, raw
     assert not aborts, aborts                                  # the library reports, it does not stop the process
     assert used == listed, (sorted(used - listed), sorted(listed - used))
-    assert "CALITAS_BINNED_SKIP" not in listed
+    assert not [ln for ln in table if "wrong" in ln], table    # (no switch whose output is wrong on purpose)
 
 
 def test_worker_threads_and_resident_contigs_of_a_rank(tmp_path):

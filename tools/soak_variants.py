@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Soak of the variant search at BASELINE config 5's size: the same call again and again -- into a block of the library's, into a
-page-locked block of the caller's, with the kept rows sent to the device (CALITAS_VARIANTS_ROWS=device) -- every text's CRC must be
+page-locked block of the caller's, with compact texts and the kept rows sent to the device (CALITAS_VARIANTS_COMPACT=1) -- every text's CRC must be
 the first one's (the stages of the call are seven threads and a worker pool: a race shows as a different byte sooner or later).
 Usage: python3 tools/soak_variants.py [calls] [scale]"""
 import ctypes, os, sys, time, zlib
@@ -45,11 +45,11 @@ bad = 0
 t0 = time.time()
 try:
     for k in range(calls):
-        mode = ("into", "library", "device-rows")[k % 3]
-        if mode == "device-rows":
-            os.environ["CALITAS_VARIANTS_ROWS"] = "device"
+        mode = ("into", "library", "compact")[k % 3]
+        if mode == "compact":
+            os.environ["CALITAS_VARIANTS_COMPACT"] = "1"
         else:
-            os.environ.pop("CALITAS_VARIANTS_ROWS", None)
+            os.environ.pop("CALITAS_VARIANTS_COMPACT", None)
         t = time.time()
         if mode == "library":
             C._lib.check(ctx._h, lib.calitas_search_variants(ctx._h, ctypes.byref(g), b"soak", ctypes.byref(params), vcf.encode(), None, None, b"v", b"t",
