@@ -635,9 +635,12 @@ __global__ __launch_bounds__(64) void align_kernel(AlignArgs a) {
       // "Row 0" (score 0 in all three matrices, ties -> Diag) is what row 1 finds above it: lane 0 gets it as the `old` operand of the
       // lane shift; the first lane of a later job reads the last lane of the job before it, which is no row of that job when its guide
       // is shorter than LPJ and then simply holds row 0 -- always so with three jobs per wave (the host picks LPJ = 21 for guides of
-      // up to 20 rows only).  (Two jobs, a 32-base guide in the first: lane 32 is patched in the loop.)
-      const bool row0_in_lane31 = LPJ != 32 || __builtin_amdgcn_readlane(L, 0) < 32;
-      if (row0_in_lane31 && r == LPJ - 1) { curD = TR_DIAG; curL = NEG * 4 + TR_LEFT; curU = TR_UP; }
+      // up to 20 rows only).  Each job decides for its own last lane: with two jobs of different L (guides of several lengths in one
+      // launch) lane 63 can be row 32 of the second job while lane 31 holds row 0 for it.  Lane 32 is patched in the loop unless lane
+      // 31 is known to hold row 0 -- also when the first job of the wave has nothing to do this round: its lanes are off and their
+      // registers (L among them) hold whatever an earlier round left, so nothing may be read from them.
+      if (r == LPJ - 1 && r >= L) { curD = TR_DIAG; curL = NEG * 4 + TR_LEFT; curU = TR_UP; }
+      const bool row0_in_lane31 = LPJ != 32 || ((__ballot(r == LPJ - 1 && r >= L) >> 31) & 1ull) != 0ull;
       int curP = max(max(curD, curL), curU);
       const int t_first = r + 1, t_last = r < L ? r + ncols : -1;     // the steps at which this row has a column of the strip
       const int nsteps = ncols + L - 1;

@@ -745,6 +745,7 @@ int calitas_scan_candidates_impl(calitas_ctx* ctx, int32_t n_guides, const calit
   (void)hipEventElapsedTime(&ms, ctx->t_scan0, ctx->t_scan1);
   ctx->timing = calitas_timing_t{};
   ctx->timing.scan_kernel_ms = ms; ctx->timing.scan_records = n_rec; ctx->timing.bases_scanned = pl.bases; ctx->timing.packed_bytes = (pl.bases + 3) / 4;
+  if (!columnwise) ctx->timing.scan_variant = (uint32_t)ref_owner(ctx)->ref.chunk << 8 | (uint32_t)pl.warm_words;
   *records = (uint32_t*)recs;
   *n_records = n_rec;
   return CALITAS_OK;

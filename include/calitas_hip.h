@@ -133,7 +133,8 @@ typedef struct {
                                   * per-bin kernels (binned.hpp); the others ran on the general kernels (same text) */
   uint32_t owned_general_lanes;  /* a window range (first_window / n_windows): pieces whose bins were crowded and whose owned rows the general
                                   * kernels decided from the same alignments (round 4; before, such a range searched its contigs whole) */
-  uint32_t reserved;
+  uint32_t scan_variant;          /* calitas_scan_candidates: the scan_rows_kernel instantiation it launched, lane chunk << 8 | warm-up words
+                                  * (0 for the column-wise kernel and after every other call) */
 } calitas_timing_t;
 
 /* Context ------------------------------------------------------------------------------------------------------- */

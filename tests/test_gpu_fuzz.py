@@ -17,3 +17,14 @@ def test_random_configurations_against_the_oracle(seed, monkeypatch):
     spec.loader.exec_module(fuzz)
     monkeypatch.setenv("CALITAS_CHUNKS", "1")          # run() sets it per call; restored afterwards
     assert fuzz.run(60, seed) == 0
+
+
+@pytest.mark.parametrize("seed", [101, 102])
+def test_wide_random_configurations_against_the_oracle(seed, monkeypatch):
+    """tools/fuzz.py's wide draw: L up to 32, PAMs up to 16 nt with up to 7 auxiliary ones, g up to 16, d up to the scan's
+    L + E <= 64 edge, cost ratios up to 5, contigs up to 300 kb -- every shape one the host accepts, so a refusal fails too."""
+    spec = importlib.util.spec_from_file_location("calitas_fuzz", os.path.join(ROOT, "tools", "fuzz.py"))
+    fuzz = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(fuzz)
+    monkeypatch.setenv("CALITAS_CHUNKS", "1")          # run() sets it per call; restored afterwards
+    assert fuzz.run(20, seed, wide=True) == 0
