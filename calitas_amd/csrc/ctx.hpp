@@ -85,7 +85,7 @@ struct calitas_ctx {
   calitas_ctx* side2 = nullptr;     // ... and a second one: two batches of variant windows are aligned side by side
   calitas_ctx* side = nullptr;      // a child context of its own (stream, buffers) for work that runs beside a search of this context: the
                                     // variant windows' alignment while the reference passes of the same call are under way (calitas_side_context)
-  struct LaneThreads* lane_threads = nullptr;   // parent: the host threads that drive lanes 1.. (search.cpp)
+  struct LaneThreads* lane_threads = nullptr;   // parent: the host threads that drive lanes 1.. (search_internal.hpp)
   hipStream_t scan_stream = nullptr;
   hipStream_t copy_stream = nullptr;  // parent: the text copies of all lanes
   hipEvent_t scan_done = nullptr;   // lane: recorded on the parent's scan stream after this lane's scan
@@ -113,7 +113,7 @@ void* calitas_out_shrink(void* p, size_t size);  // gives back what a block has 
 void* calitas_out_take_big(size_t min_bytes);   // the parked pageable block of >= 1 GB, if there is one with that much room (api.cpp)
 void* calitas_out_alloc_pinned(size_t size);   // page-locked: the destination of the text copy-back
 void* calitas_out_grow(void* p, size_t keep, size_t size);   // pageable block grown in place (realloc); p may be NULL
-// search.cpp
+// search_run.cpp / search_hits.cpp / search_batch.cpp / search_lane.cpp
 int calitas_search_impl(calitas_ctx* ctx, int32_t n_guides, const calitas_guide_t* guides, const calitas_params_t* params,
                         calitas_aln_t** out, uint64_t* n_out);
 int calitas_search_hits_impl(calitas_ctx* ctx, const calitas_guide_t* guide, const std::string& guide_id, const calitas_params_t* params,

@@ -97,7 +97,7 @@ struct HitsExt {
   // offsets (an entry that was not kept has length 0) and the text from `rows` -- memory of the caller's that stays valid until
   // hits_run returns.  != 0: the caller gave up, hits_run returns hipErrorUnknown.  One more host round trip per call of hits_run.
   std::function<int(const uint8_t* kept, HitsExtRows* rows)> rows_for;
-  // HitsExtRows::fill_on_host: called by whoever brought the text to the host (search.cpp, the per-contig passes) with
+  // HitsExtRows::fill_on_host: called by whoever brought the text to the host (search_sequential.cpp, the per-contig passes) with
   // HitsResult::ext_place and the text's address: the rows of the kept entries go to text + place[e].  stays: the text is where it will
   // be when the call returns (a buffer of the caller's), so the callee may do the work later, on a thread of its own that it joins
   // before its call ends (place[] is only valid during fill); otherwise the rows must be in the text when fill returns.

@@ -31,7 +31,7 @@
 //   lifter       lifts a batch's alignments back, lists them as hits (HitList: pieces that never move); at a contig's end the groups' own
 //                walks, the entries' tie order and keys (finish_contig)
 //   finisher     the rows of the contig's placed entries (with a placeholder where the identifier goes), then publishes the contig
-//   helper       the reference's per-contig passes (search.cpp, calitas_search_hits_ext_impl): asks for a contig's entries when its row stage
+//   helper       the reference's per-contig passes (search_hits.cpp, calitas_search_hits_ext_impl): asks for a contig's entries when its row stage
 //                is due (HitsExtSource::get, blocks until published), makes the rows of the plain entries the device's walk kept
 //                (HitsExt::rows_for), and its copying thread hands every contig's text to ...
 //   filler       ... which waits for the identifier once and writes the kept entries' rows into the holes the rows kernel left

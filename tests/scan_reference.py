@@ -1,7 +1,7 @@
 """The candidate filter (scan_rows.hip) by definition, in plain numpy: what calitas_scan_candidates must return.
 
 The filter keeps every end column, on both strands, whose seamless glocal bottom-row score reaches minGuideScore.  With linear
-costs that is "semi-global edit distance of the protospacer <= E" for E = scan_edits(L, d, costs) (search.cpp, build_guide_dev):
+costs that is "semi-global edit distance of the protospacer <= E" for E = scan_edits(L, d, costs) (search_plan.cpp, build_guide_dev):
 an exact test at default costs, a superset of the passing columns otherwise.  tests/test_scan_reference.py holds this module
 against the oracle's glocal enumeration; tests/test_gpu_scan.py holds the kernels against this module.
 """

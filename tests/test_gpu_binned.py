@@ -212,7 +212,7 @@ def test_lanes_and_batch_take_the_binned_tail(C, tmp_path, monkeypatch):
 
 
 def test_compact_rows_arrive_in_pieces(C, tmp_path, monkeypatch):
-    """The ranges of a chunked call move compact rows over PCIe in pieces and the worker pool expands what has landed (search.cpp
+    """The ranges of a chunked call move compact rows over PCIe in pieces and the worker pool expands what has landed (search_lane.cpp
     compact_rows_to_host, post.cpp RowExpansion).  On a dense genome with 64 KB pieces and the job's hand-overs forced onto several
     workers: the same text as full rows over the bus, as one copy per range, and as the call in one pass."""
     rng = np.random.default_rng(77)

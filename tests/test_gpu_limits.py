@@ -1,4 +1,4 @@
-"""GPU: end-to-end searches at the limits the host accepts (post.cpp make_guide_host, search.cpp plan_search / build_guide_dev), against
+"""GPU: end-to-end searches at the limits the host accepts (post.cpp make_guide_host, search_plan.cpp plan_search / build_guide_dev), against
 the CPU oracle, every column -- and one step past each limit, which must be refused with CalitasError and leave the context usable.
 
 | limit                                  | at the limit                                   | one past it                         |

@@ -21,13 +21,13 @@ def _wide_costs(rng):
 
 
 def scan_budget(L, d, costs):
-    """The scan's edit budget E (search.cpp build_guide_dev): |worst net cost| x d in units of the cheapest edit."""
+    """The scan's edit budget E (search_plan.cpp build_guide_dev): |worst net cost| x d in units of the cheapest edit."""
     m, b, B = (abs(costs.get(k, v)) for k, v in (("guide_mismatch_net_cost", -120), ("genome_gap_net_cost", -122), ("guide_gap_net_cost", -121)))
     return max(m, b, B) * d // min(m, b, B)
 
 
 def _max_d(L, costs):
-    """Largest max-guide-diffs the host takes for L rows (search.cpp build_guide_dev): L + E <= 64 and a strip of L + E_del + 17 <= 96."""
+    """Largest max-guide-diffs the host takes for L rows (search_plan.cpp build_guide_dev): L + E <= 64 and a strip of L + E_del + 17 <= 96."""
     m, b, B = (abs(costs.get(k, v)) for k, v in (("guide_mismatch_net_cost", -120), ("genome_gap_net_cost", -122), ("guide_gap_net_cost", -121)))
     d = 0
     while L + max(m, b, B) * (d + 1) // min(m, b, B) <= 64 and L + max(m, b, B) * (d + 1) // B + 17 <= 96:
