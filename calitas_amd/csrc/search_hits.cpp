@@ -699,7 +699,7 @@ int calitas_search_hits_impl(calitas_ctx* ctx, const calitas_guide_t* guide, con
   return rc;
 }
 
-// calitas_search_hits with hits of the caller's own brought into every contig's row stage (the variant branch, variants.cpp): one pass per
+// calitas_search_hits with hits of the caller's own brought into every contig's row stage (the variant branch, variants.cpp: VariantSearch::start_threads): one pass per
 // contig on the general kernels.  kExtDeclined is returned as CALITAS_ESTATE + *declined: a stage left the device path, the caller
 // merges on the host instead.
 int calitas_search_hits_ext_impl(calitas_ctx* ctx, const calitas_guide_t* guide, const std::string& guide_id, const calitas_params_t* params,

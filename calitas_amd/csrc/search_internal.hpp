@@ -1,6 +1,6 @@
 // search_internal.hpp -- private to the search_*.cpp units: the types one search hands from stage to stage (SearchPlan, DeviceSel,
 // LaneText, HitsCall), the lane threads, the CALITAS_TRACE=2 time line, and the prototypes the units share.  What api.cpp,
-// align_windows.cpp and variants.cpp call is in ctx.hpp.  Everything here stays out of the library's dynamic symbol table.
+// align_windows.cpp and the variants*.cpp units call is in ctx.hpp.  Everything here stays out of the library's dynamic symbol table.
 #pragma once
 #include <atomic>
 #include <chrono>

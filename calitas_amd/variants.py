@@ -2,7 +2,7 @@
 
 The branch itself -- variantWindowIterator and its helpers (SearchReference.scala:217-399), the per-window align calls, lift-back,
 window flanks, variant columns and the merge with the reference hits -- is calitas_search_variants in the library
-(calitas_amd/csrc/variants.cpp); search_variants() below calls it.  This module adds what sits around it: a VCF reader for the
+(calitas_amd/csrc/variants.cpp and the variants_*.cpp units beside it); search_variants() below calls it.  This module adds what sits around it: a VCF reader for the
 subset the path needs (fgbio vcf.api: CHROM POS ID REF ALT FILTER INFO(AF, END)), the `name:md5` identifier of a VCF
 (ReferenceHit.scala:175-183) and PrepareVcf.  (A second, pure-Python implementation of the branch used as a cross-check lives with
 the tests: tests/variants_twin.py.)"""

@@ -1,5 +1,5 @@
 """TEST INFRASTRUCTURE: the variant branch of SearchReference (SearchReference.scala:101-400, 570-630) written a second time, in Python,
-as a cross-check of the product's implementation (calitas_amd/csrc/variants.cpp behind calitas_search_variants).  Window production
+as a cross-check of the product's implementation (calitas_amd/csrc/variants*.cpp behind calitas_search_variants).  Window production
 (nextChunk / reChunk / alleleCombos / buildVariantWindow), lift-back and the variant columns follow the Scala; the windows are aligned
 on the GPU through calitas_align_windows like the product does.  Only tests/ and tools/fuzz_variants.py import this module; it used to
 live in the package (calitas_amd/variants.py) and was moved out so that the package holds one implementation."""
