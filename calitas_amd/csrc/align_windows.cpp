@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "ctx.hpp"
+#include "slab.hpp"
 #include "tuning.hpp"
 
 namespace {
@@ -123,9 +124,7 @@ extern "C" int calitas_align_windows(calitas_ctx* ctx, int32_t n_tasks, const ca
       std::string e = build_guide_dev(gh[t], p, sc, task_d[t], task_p[t], gd[s]);
       if (!e.empty()) return calitas_fail(ctx, CALITAS_EINVAL, "task " + std::to_string(t) + ": " + e);
       gd[s].cli_length = 0;     // SGA.align itself has no length filter (that is SearchReference.scala:536)
-      const uint32_t ncols_max = 16 + gd[s].span + 1, stride_max = (ncols_max + 4) & ~3u;
-      const uint32_t ntb_max = (ncols_max + p.max_gaps_between_guide_and_pam + MAX_PAM_LEN + 3) & ~3u;
-      slab_bytes = std::max<uint32_t>(slab_bytes, (uint32_t)((sizeof(SlabHeader) + ntb_max + gd[s].L * stride_max + 15) & ~15u));
+      slab_bytes = std::max(slab_bytes, slab_bytes_for(gd[s].L, gd[s].span, p.max_gaps_between_guide_and_pam));
     }
 
     ms_prep += ms_since(t_sec); t_sec = clk::now();

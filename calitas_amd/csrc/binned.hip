@@ -1,7 +1,7 @@
 // binned.hip -- everything behind trace_kernel for one guide, one wave per reference bin (see binned.hpp for the why).
 //
 // A bin is a power-of-two stretch of ONE contig (32 kb for the default window).  trace_kernel drops every raw alignment into the bin
-// its window STARTS in (kernels.hip); bin_hits_kernel's wave for bin b owns the hits whose coordinate_start -- the first key of
+// its window STARTS in (trace.hip); bin_hits_kernel's wave for bin b owns the hits whose coordinate_start -- the first key of
 // ReferenceHit.sort (ReferenceHit.scala:284) -- lies in [lo, hi) = the bin's stretch, so the rows of consecutive bins are consecutive
 // pieces of hits.txt.  What the wave needs to decide those hits exactly:
 //   * every window that can hold such a hit: windows starting in (lo - W, hi) -- its own bin and the tail of bin b-1;

@@ -20,6 +20,7 @@
 
 #if defined(__HIPCC__)
 #define CAL_HD __host__ __device__
+#define CAL_DEV __device__ inline __attribute__((always_inline))   // (__forceinline__ without the HIP runtime header)
 #else
 #define CAL_HD
 #endif
@@ -179,30 +180,6 @@ CAL_HD inline OpCounts count_ops(const OpsWords& w, int n_ops) {
   return c;
 }
 
-// One aligner job = one scan record x one window that holds some of its candidate columns; one slab per job.  The slab is the job's
-// whole life: expand_kernel writes its head (the strip's geometry, the guide's row sets, the target masks tb[ntb]) with one lane
-// group per job, align_kernel reads exactly that -- one 16-byte load per lane, issued a job ahead --, fills the strip and adds the
-// trace bytes tr[L][stride] and which candidate columns passed, trace_kernel walks it.  Slabs have a fixed size per search and the
-// job's number as their address, so the hand-overs need no atomics beyond the one that numbers the jobs.
-struct SlabHeader {
-  uint32_t pass_mask;     // (align_kernel) bit x: the x-th candidate column of this job reached min_guide_score; 0 from expand_kernel
-  uint32_t contig;
-  uint32_t window_k;
-  int32_t n;              // window length
-  int32_t c0;             // strip boundary column (strip columns are c0+1 .. c0+ncols)
-  uint16_t ncols, ntb;
-  uint8_t dir, guide, true_border, L;
-  uint16_t stride, pad;
-  uint16_t j[16];         // (align_kernel) strand-space end column (1-based) of candidate x, for the candidates that passed
-  // what align_kernel needs besides the geometry above, so that a job is ONE read of its slab's head:
-  uint8_t qmask[MAX_L];   // IUPAC set of each query row (GuideDev::qmask of the job's guide)
-  int32_t min_score;      // GuideDev::min_guide_score
-  uint32_t sel;           // candidate columns of the record's 16-base word that lie inside this window (bit b = base b)
-  int32_t jbase;          // strand-space column of bit 0: j = jbase + b (dir 0) or jbase - b (dir 1)
-  int32_t reserved[5];
-};
-static_assert(sizeof(SlabHeader) == 128, "slab header layout");
-
 }  // namespace calitas
 
 // Wave priority of the kernels that follow a scan (align ... rows).  They share SIMDs with the scan of the next contig range, whose
@@ -210,6 +187,19 @@ static_assert(sizeof(SlabHeader) == 128, "slab header layout");
 // five to nine and took 40-70 us instead of 5-10 (rocprofv3 timeline).  The scan stays at priority 0.
 #if defined(__HIPCC__)
 #define CALITAS_TAIL_PRIO() __builtin_amdgcn_s_setprio(3)
+
+// One wave handing LDS from some of its lanes to others: the writes before, the reads behind.  wave_release() is the first half alone,
+// where the next access of that memory has a wave_sync() of its own in front of it.
+namespace calitas {
+CAL_DEV void wave_release() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+}
+CAL_DEV void wave_sync() {
+  wave_release();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+}  // namespace calitas
 #endif
 
 #ifdef CALITAS_ALLOC_DEBUG

@@ -1,4 +1,4 @@
-// kernels.hpp -- launch interface of kernels.hip (device pointers only).
+// kernels.hpp -- launch interface of scan_columns.hip, scan_rows.hip, align.hip, trace.hip and setup.hip (device pointers only).
 #pragma once
 #include "mailbox.hpp"
 #include <hip/hip_runtime_api.h>
@@ -39,7 +39,7 @@ struct AlignArgs {
   uint32_t* out_count;
   uint32_t* anomalies;
   uint32_t* trace_done;     // trace_kernel: workgroups finished (zero at launch); the last one posts the counters to the mailbox
-  uint8_t* slab;            // one slab per aligner job (SlabHeader): rec_capacity x slots_per_rec of them
+  uint8_t* slab;            // one slab per aligner job (slab.hpp): rec_capacity x slots_per_rec of them
   uint32_t* job_count;      // jobs numbered by expand_kernel (zero at launch)
   uint32_t* cand_count;     // statistics only
   uint64_t* items;          // passing candidates, (slab index << 4 | candidate slot): align_kernel appends, trace_kernel consumes

@@ -5,7 +5,7 @@
 // glocal DP reaches minGuideScore at that end column.  With the reference's linear gap costs that is "semi-global edit distance
 // <= E" (SearchReference.scala:432-441), computed exactly with Myers' bit-vector recurrence.
 //
-// Orientation.  The first version of this kernel (kernels.hip, scan_kernel) kept one DP *column* (the L protospacer rows) in a
+// Orientation.  The first version of this kernel (scan_columns.hip, scan_kernel) kept one DP *column* (the L protospacer rows) in a
 // 32-bit word and walked the text base by base: 13 VALU instructions per base and strand for L = 20 cells, 12 of the 32 bits idle,
 // plus a table lookup per base.  Here the bit-vector runs along the *text*: a lane owns NW consecutive 32-base words of the
 // reference as one long integer (plus NWARM warm-up words from its neighbour), and one step of the recurrence handles one

@@ -5,6 +5,7 @@
 #include <cstring>
 
 #include "search_internal.hpp"
+#include "slab.hpp"
 
 std::string build_guide_dev(const GuideHost& gh, const calitas_params_t& p, const Scores& sc, int max_guide_diffs, int max_pam_mismatches,
                             GuideDev& gd) {
@@ -154,12 +155,7 @@ int plan_search(calitas_ctx* ctx, int32_t n_guides, const calitas_guide_t* guide
   pl.slots_per_rec = (uint32_t)((p.window_size + 14) / pl.step + 1);   // windows a 16-base word can fall into
   if (pl.slots_per_rec > 8) return fail(ctx, CALITAS_EINVAL, "window step is too small relative to the window size (more than 8 windows per position)");
   pl.slab_bytes = 0;
-  for (int i = 0; i < n_guides; i++) {
-    const uint32_t ncols_max = 16 + pl.gd[i].span + 1;
-    const uint32_t stride_max = (ncols_max + 4) & ~3u;
-    const uint32_t ntb_max = (ncols_max + p.max_gaps_between_guide_and_pam + MAX_PAM_LEN + 3) & ~3u;
-    pl.slab_bytes = std::max<uint32_t>(pl.slab_bytes, (uint32_t)((sizeof(SlabHeader) + ntb_max + pl.gd[i].L * stride_max + 15) & ~15u));
-  }
+  for (int i = 0; i < n_guides; i++) pl.slab_bytes = std::max(pl.slab_bytes, slab_bytes_for(pl.gd[i].L, pl.gd[i].span, p.max_gaps_between_guide_and_pam));
   pl.slab_per_rec = (uint64_t)pl.slab_bytes * pl.slots_per_rec;
   pl.tile_lo = 0; pl.n_tiles = (uint32_t)ref.tiles.size();
   pl.bin_shift = binned_shift(p.window_size);

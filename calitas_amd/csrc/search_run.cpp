@@ -25,7 +25,7 @@ int queue_scan_inputs(calitas_ctx* ctx, const SearchPlan& pl, hipStream_t stream
   return CALITAS_OK;
 }
 
-// columnwise: round 1's column-wise scan_kernel (kernels.hip) instead of scan_rows_kernel.  Only calitas_scan_candidates_columnwise
+// columnwise: round 1's column-wise scan_kernel (scan_columns.hip) instead of scan_rows_kernel.  Only calitas_scan_candidates_columnwise
 // asks for it -- a test hook that holds the two kernels' record sets against each other; no search path does.
 int launch_scan_stage(calitas_ctx* ctx, const SearchPlan& pl, hipStream_t stream, bool inputs_queued, bool columnwise) {
   { int rc = check_resident(ctx, pl); if (rc) return rc; }

@@ -196,9 +196,7 @@ __global__ __launch_bounds__(64) void filter_wave_kernel(const Derived* ders, co
           if (__ballot(clash) == 0) {
             if (lane == 0) { out_pos[s + nk] = s + (uint32_t)owner + 64u * (uint32_t)b_q; s_ks[nk] = b_start; s_ke[nk] = b_end; }
             nk++;
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");      // one wave: the LDS writes above before the next round's reads
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            wave_sync();                                                // one wave: the LDS writes above before the next round's reads
           }
         }
       }
