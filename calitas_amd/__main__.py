@@ -37,6 +37,8 @@ def main(argv=None):
     sr.add_argument("-D", "--max-total-diffs", type=int)
     sr.add_argument("-O", "--max-overlap", type=int, default=Defaults.MaxOverlap)
     sr.add_argument("-c", "--chrom")
+    sr.add_argument("--counts", action="store_true",
+                    help="write the off-target table (guide_id strand guide_mm guide_gaps pam_mm hits; non-zero cells) instead of hits.txt")
     _costs(sr)
 
     a2r = sub.add_parser("AlignToReference")
@@ -73,7 +75,7 @@ def main(argv=None):
                         max_overlap=a.max_overlap, guide_mismatch_net_cost=a.guide_mismatch_net_cost,
                         pam_mismatch_net_cost=a.pam_mismatch_net_cost, genome_gap_net_cost=a.genome_gap_net_cost,
                         guide_gap_net_cost=a.guide_gap_net_cost, chrom=a.chrom, variants=a.variants, max_variants=a.max_variants,
-                        device=a.device).execute()
+                        device=a.device).execute(counts=a.counts)
     elif a.tool == "AlignToReference":
         text = align_to_reference(a.input, a.ref, a.output, window_size=a.window_size, max_guide_diffs=a.max_guide_diffs,
                                   max_pam_mismatches=a.max_pam_mismatches, max_gaps_between_guide_and_pam=a.max_gaps_between_guide_and_pam,

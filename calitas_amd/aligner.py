@@ -10,7 +10,7 @@ import ctypes
 import time
 
 from . import _lib
-from ._lib import AlnT, CalitasError, GuideT, ParamsT, TimingT, lib
+from ._lib import AlnT, CalitasError, CountsT, GuideT, ParamsT, TimingT, lib
 
 
 class Defaults:  # SequentialGuideAligner.scala:17-28
@@ -444,6 +444,50 @@ class Context:
             lib.calitas_free(tsv[i])
         return out
 
+    @staticmethod
+    def _take_counts(ptr):
+        """A calitas_counts_t block as a numpy uint64 array of shape (2, n_mm, n_gaps, n_pam); the block is freed."""
+        import numpy as np
+        try:
+            c = ptr.contents
+            shape = (2, c.n_mm, c.n_gaps, c.n_pam)
+            n = 2 * c.n_mm * c.n_gaps * c.n_pam
+            table = np.ctypeslib.as_array(c.counts, shape=(n,)).astype(np.uint64).reshape(shape)   # (astype copies)
+            if int(table.sum()) != c.rows:
+                raise CalitasError(_lib.EHIP, "the counts table does not add up to its rows")
+            return table
+        finally:
+            lib.calitas_free(ptr)
+
+    def search_counts(self, guide, params):
+        """calitas_search_counts: the off-target table of one guide -- how many rows the hits.txt of search_hits (same guide, same
+        params, window range included) has per (strand, guide_mm, guide_gaps, pam_mm) -- as a numpy uint64 array of shape
+        (2, n_mm, n_gaps, n_pam), strand '+' first.  No text is built or copied.  The shape depends on guide and params only."""
+        g = guide.to_c()
+        out = ctypes.POINTER(CountsT)()
+        _lib.check(self._h, lib.calitas_search_counts(self._h, ctypes.byref(g), ctypes.byref(params), ctypes.byref(out)))
+        return self._take_counts(out)
+
+    def search_counts_batch(self, guides, params):
+        """calitas_search_counts_batch: a list of tables, one per guide (all of one length), pipelined on the device like
+        search_hits_batch."""
+        n = len(guides)
+        keep = [g.to_c() for g in guides]
+        garr = (GuideT * n)(*keep)
+        out = (ctypes.POINTER(CountsT) * n)()
+        _lib.check(self._h, lib.calitas_search_counts_batch(self._h, n, garr, ctypes.byref(params), out))
+        return [self._take_counts(out[i]) for i in range(n)]
+
+    def hits_counts(self, guide, params, alignments):
+        """calitas_hits_counts: removeOverlaps on a guide's alignments (as search() returns them), then the table -- the host stage,
+        usable on a host-only context."""
+        g = guide.to_c()
+        n = len(alignments)
+        arr = (AlnT * max(1, n))(*[a.to_c() for a in alignments])
+        out = ctypes.POINTER(CountsT)()
+        _lib.check(self._h, lib.calitas_hits_counts(self._h, ctypes.byref(g), ctypes.byref(params), arr, n, ctypes.byref(out)))
+        return self._take_counts(out)
+
     def timing(self):
         t = TimingT()
         _lib.check(self._h, lib.calitas_get_timing(self._h, ctypes.byref(t)))
@@ -548,14 +592,82 @@ class SearchReference:
             if own:
                 ctx.close()
 
-    def execute(self):
-        text, _ = self.run()
+    def counts(self):
+        """The off-target table instead of hits.txt (Context.search_counts): a numpy uint64 array of shape (2, n_mm, n_gaps, n_pam)."""
+        if self.variants is not None:
+            raise ValueError("counts() covers the reference-genome branch only (no --variants)")
+        ctx = self.context
+        own = ctx is None
+        if own:
+            ctx = Context(self.device)
+            ctx.set_reference_fasta(self.ref)
+        try:
+            chrom_index = -1
+            if self.chrom is not None:
+                if self.chrom not in ctx.contig_names:
+                    raise ValueError("Unknown chromosome: %s" % self.chrom)
+                chrom_index = ctx.contig_names.index(self.chrom)
+            params = make_params(chrom_index=chrom_index, **self._kw)
+            t0 = time.perf_counter()
+            table = ctx.search_counts(self.query, params)
+            self.timing = ctx.timing()
+            self.wall_ms = (time.perf_counter() - t0) * 1e3
+            return table
+        finally:
+            if own:
+                ctx.close()
+
+    def execute(self, counts=False):
+        """counts=True (`--counts`): the table as a TSV (counts_tsv) instead of hits.txt."""
+        text = counts_tsv(self.guide_id, self.counts()) if counts else self.run()[0]
         if self.output is None:
             import sys
             sys.stdout.write(text)
         else:
             with open(self.output, "w") as f:
                 f.write(text)
+
+
+COUNTS_COLUMNS = ("guide_id", "strand", "guide_mm", "guide_gaps", "pam_mm", "hits")
+
+
+def counts_of_rows(rows, shape):
+    """The table search_counts returns, built from hits.txt rows (read_hits output): cell [s][m][g][p] = rows with strand s ('+' = 0,
+    '-' = 1), guide_mm m, guide_gaps g and pam_mm p.  A row outside `shape` = (2, n_mm, n_gaps, n_pam) is an error, never dropped."""
+    import numpy as np
+    table = np.zeros(shape, dtype=np.uint64)
+    for r in rows:
+        cell = ({"+": 0, "-": 1}[r["strand"]], int(r["guide_mm"]), int(r["guide_gaps"]), int(r["pam_mm"]))
+        if any(not 0 <= c < n for c, n in zip(cell, shape)):
+            raise ValueError("a hit at %r lies outside the table's extents %r" % (cell, tuple(shape)))
+        table[cell] += 1
+    return table
+
+
+def counts_tsv(guide_id, table):
+    """`SearchReference --counts`: header guide_id strand guide_mm guide_gaps pam_mm hits, then the non-zero cells in table order."""
+    import numpy as np
+    lines = ["\t".join(COUNTS_COLUMNS)]
+    for s, m, g, p in np.argwhere(table):                   # (row-major: table order)
+        lines.append("%s\t%s\t%d\t%d\t%d\t%d" % (guide_id, "+-"[s], m, g, p, int(table[s, m, g, p])))
+    return "\n".join(lines) + "\n"
+
+
+def read_counts_tsv(path_or_text, shape):
+    """A --counts TSV back into the array of that shape."""
+    import numpy as np
+    text = path_or_text
+    if "\n" not in path_or_text:
+        with open(path_or_text) as f:
+            text = f.read()
+    lines = text.splitlines()
+    if tuple(lines[0].split("\t")) != COUNTS_COLUMNS:
+        raise ValueError("not a counts TSV: %r" % lines[0])
+    table = np.zeros(shape, dtype=np.uint64)
+    for ln in lines[1:]:
+        _, s, m, g, p, n = ln.split("\t")
+        table[{"+": 0, "-": 1}[s], int(m), int(g), int(p)] += np.uint64(int(n))
+    return table
 
 
 def read_hits(path_or_text):

@@ -691,6 +691,50 @@ int calitas_search_hits_batch(calitas_ctx* ctx, int32_t n_guides, const calitas_
   return calitas_search_hits_batch_impl(ctx, n_guides, guides, guide_ids, params, aligner_version, time_stamp, tsv, tsv_bytes, n_rows);
 }
 
+// A table as the ABI hands it over: struct and cells in one block of the library's.
+static calitas_counts_t* counts_block(const CountsShape& shape, const uint64_t* table, uint64_t rows) {
+  const size_t cells = shape.cells();
+  calitas_counts_t* c = (calitas_counts_t*)out_alloc(sizeof(calitas_counts_t) + cells * sizeof(uint64_t));
+  if (!c) return nullptr;
+  c->n_mm = shape.n_mm; c->n_gaps = shape.n_gaps; c->n_pam = shape.n_pam; c->rows = rows;
+  c->counts = reinterpret_cast<uint64_t*>(c + 1);
+  std::memcpy(c->counts, table, cells * sizeof(uint64_t));
+  return c;
+}
+
+int calitas_search_counts(calitas_ctx* ctx, const calitas_guide_t* guide, const calitas_params_t* params, calitas_counts_t** out) {
+  if (!ctx) return CALITAS_EINVAL;
+  if (!guide || !params || !out) return fail(ctx, CALITAS_EINVAL, "NULL argument");
+  *out = nullptr;
+  CountsShape shape;
+  std::vector<uint64_t> table;
+  uint64_t rows = 0;
+  const int rc = calitas_search_counts_impl(ctx, guide, params, &shape, &table, &rows);
+  if (rc) return rc;
+  *out = counts_block(shape, table.data(), rows);
+  return *out ? CALITAS_OK : fail(ctx, CALITAS_EINVAL, "out of memory");
+}
+
+int calitas_search_counts_batch(calitas_ctx* ctx, int32_t n_guides, const calitas_guide_t* guides, const calitas_params_t* params,
+                                calitas_counts_t** out) {
+  if (!ctx) return CALITAS_EINVAL;
+  if (n_guides <= 0 || !guides || !params || !out) return fail(ctx, CALITAS_EINVAL, "bad argument");
+  for (int i = 0; i < n_guides; i++) out[i] = nullptr;
+  std::vector<std::vector<uint64_t>> tables((size_t)n_guides);
+  std::vector<uint64_t> rows((size_t)n_guides, 0);
+  int rc = calitas_search_hits_batch_impl(ctx, n_guides, guides, nullptr, params, nullptr, nullptr, nullptr, nullptr, rows.data(), &tables);
+  for (int i = 0; i < n_guides && !rc; i++) {
+    GuideHost gh;
+    CountsShape shape;
+    std::string e = make_guide_host(guides[i], gh);
+    if (e.empty()) e = counts_shape(gh, *params, shape);
+    if (!e.empty() || tables[(size_t)i].size() != shape.cells()) rc = fail(ctx, CALITAS_EINVAL, e.empty() ? "a guide's table has another shape than its plan (internal error)" : e);
+    else if (!(out[i] = counts_block(shape, tables[(size_t)i].data(), rows[(size_t)i]))) rc = fail(ctx, CALITAS_EINVAL, "out of memory");
+  }
+  if (rc) for (int i = 0; i < n_guides; i++) { calitas_free(out[i]); out[i] = nullptr; }
+  return rc;
+}
+
 int calitas_scan_candidates(calitas_ctx* ctx, int32_t n_guides, const calitas_guide_t* guides, const calitas_params_t* params,
                             uint32_t** records, uint64_t* n_records) {
   return calitas_scan_candidates_impl(ctx, n_guides, guides, params, records, n_records);
@@ -768,6 +812,25 @@ int calitas_hits_tsv_ext(const calitas_ctx* ctx, const calitas_guide_t* guide, c
   *tsv = hits_tsv(ctx->ref, gh, guide_id ? guide_id : "", *params, alns, n_alns, version, stamp, n_rows, ctx->pool, out_alloc, ext, n_ext);
   if (!*tsv) return fail(c, CALITAS_EINVAL, "out of memory");
   return CALITAS_OK;
+}
+
+int calitas_hits_counts(const calitas_ctx* ctx, const calitas_guide_t* guide, const calitas_params_t* params, const calitas_aln_t* alns,
+                        uint64_t n_alns, calitas_counts_t** out) {
+  if (!ctx || !guide || !params || !out || (n_alns && !alns)) return CALITAS_EINVAL;
+  calitas_ctx* c = const_cast<calitas_ctx*>(ctx);
+  *out = nullptr;
+  if (!ctx->has_ref) return fail(c, CALITAS_ESTATE, "calitas_set_reference has not been called");
+  GuideHost gh;
+  CountsShape shape;
+  std::string e = make_guide_host(*guide, gh);
+  if (e.empty()) e = counts_shape(gh, *params, shape);
+  if (!e.empty()) return fail(c, CALITAS_EINVAL, e);
+  std::vector<uint64_t> table(shape.cells(), 0);
+  uint64_t rows = 0;
+  e = hits_counts(ctx->ref, gh, *params, alns, n_alns, shape.n_mm, shape.n_gaps, shape.n_pam, table.data(), &rows, ctx->pool);
+  if (!e.empty()) return fail(c, CALITAS_EINVAL, e);
+  *out = counts_block(shape, table.data(), rows);
+  return *out ? CALITAS_OK : fail(c, CALITAS_EINVAL, "out of memory");
 }
 
 int calitas_padded_strings(const calitas_ctx* ctx, const calitas_guide_t* guide, const calitas_aln_t* aln, char* padded_guide,

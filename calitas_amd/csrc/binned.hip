@@ -689,6 +689,51 @@ __global__ __launch_bounds__(64 * BIN_WAVES) void bin_rows_kernel(BinArgs a, Mid
   }
 }
 
+// Counts mode: the bins' kept hits (bin_hits_small_kernel / bin_hits_kernel listed the bins that have any, with their rows' alignments
+// in final order) counted into the call's table instead of being built as rows.  One lane per listed bin (a bin keeps 0-2 hits, at most
+// BIN_ROWS); the cell comes from the same arithmetic the row's length does (hits_dev.hpp: hit_key).  The workgroup that finishes last
+// brings the table to the host and posts what bin_rows_kernel posts when it starts.
+__global__ __launch_bounds__(COUNTS_BLOCK) void bin_counts_kernel(BinArgs a, CountsOut co, RowsArgs o) {
+  CALITAS_TAIL_PRIO();
+  __shared__ uint32_t hist[COUNTS_LDS_CELLS];
+  counts_begin(hist, co);
+  const uint32_t n_todo = *a.rows_count;
+  if (*a.flags == 0) {                                     // (a bin declined: the general kernels count this range)
+    for (uint32_t it = blockIdx.x * COUNTS_BLOCK + threadIdx.x; it < n_todo; it += gridDim.x * COUNTS_BLOCK) {
+      const uint32_t rel = a.rows_list[it];
+      const uint32_t n = min(a.bin_rows[rel], BIN_ROWS);
+      for (uint32_t k = 0; k < n; k++) {
+        const RawAln* rp = a.raw + a.rows[(size_t)rel * BIN_ROWS + k].raw;
+        const uint32_t pam5 = a.guides[rp->guide].pam5;
+        const bool plus = pam5 ? (rp->dir == 1) : (rp->dir == 0);      // as hit_record
+        const int cell = counts_cell(rp, plus ? 0u : 1u, co.shape);
+        if (cell < 0) { atomicOr(a.flags, BIN_FLAG_EXTENT); continue; }
+        counts_add(hist, co, cell);
+      }
+    }
+  }
+  if (!counts_flush(hist, co)) return;
+  counts_publish(co);
+  if (threadIdx.x >= 64) return;                            // the post: the first wave of the last workgroup
+  const int lane = (int)threadIdx.x;
+  uint32_t rows_tot = 0, acc_tot = 0;
+  for (uint32_t ch = (uint32_t)lane; ch < o.n_chunks; ch += 64) { rows_tot += a.chunk_rows[ch]; acc_tot += a.chunk_acc[ch]; }
+  rows_tot = (uint32_t)wave_sum_u64(rows_tot); acc_tot = (uint32_t)wave_sum_u64(acc_tot);
+  if (lane == 0) {
+    for (int i = 0; i < 8; i++) o.box[BIN_BOX_COUNTERS + i] = __hip_atomic_load(o.counters + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    o.box[BIN_BOX_ROWS] = rows_tot; o.box[BIN_BOX_BYTES] = 0u; o.box[BIN_BOX_BYTES + 1] = 0u;
+    o.box[BIN_BOX_FLAGS] = __hip_atomic_load(a.flags, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    o.box[BIN_BOX_ACCEPTED] = acc_tot; o.box[BIN_BOX_COMPLEX] = *o.complex_count;
+    const unsigned long long now = (unsigned long long)wall_clock64();
+    for (int i = 0; i < 3; i++) {
+      const unsigned long long t = i < 2 ? a.stamps[i] : now;
+      o.box[BIN_BOX_STAMPS + 2 * i] = (uint32_t)t; o.box[BIN_BOX_STAMPS + 2 * i + 1] = (uint32_t)(t >> 32);
+    }
+    __threadfence_system();
+    __hip_atomic_store(o.box, o.seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+  }
+}
+
 template <typename T>
 hipError_t grow_to(T** p, size_t& cap, size_t need) {
   if (need <= cap) return hipSuccess;
@@ -888,6 +933,28 @@ hipError_t binned_rows(BinnedWork* pw, HitsWork** phw, const BinnedGeometry& geo
   fill_args(*pw, **phw, geo, ref, d_raw, d_guides, d_win_base, d_win, p, ba, ma);
   return launch_rows(*pw, **phw, ba, ma, d_counters, stream, post, nullptr, ev_rows_done, host_dst, host_dst_cap);
 }
+
+hipError_t binned_counts(BinnedWork* pw, HitsWork** phw, const BinnedGeometry& geo, const HitsRef& ref, const RawAln* d_raw, const GuideDev* d_guides,
+                         const uint64_t* d_win_base, const int2* d_win, const BinnedParams& p, const uint32_t* d_counters, hipStream_t stream,
+                         Mailbox* post, hipEvent_t ev_done, const CountsShape& shape) {
+  if (!pw || !*phw) return hipErrorInvalidValue;
+  BinnedWork& w = *pw;
+  HitsWork& hw = **phw;
+  hipError_t e;
+  BinArgs ba; MidArgs ma;
+  fill_args(w, hw, geo, ref, d_raw, d_guides, d_win_base, d_win, p, ba, ma);
+  CountsOut co{};
+  TRY(counts_buffers(hw, shape, &co));
+  TRY(mailbox_open(*post));
+  RowsArgs ro{};
+  ro.counters = d_counters; ro.box = post->dev; ro.seq = ++post->seq;
+  ro.n_chunks = w.n_chunks; ro.n_supers = w.n_supers; ro.complex_count = w.complex_count;
+  post->host[BIN_BOX_LATE] = 0;
+  hipExtLaunchKernelGGL(bin_counts_kernel, dim3(counts_grid(geo.n_bins)), dim3(COUNTS_BLOCK), 0, stream, nullptr, ev_done, 0, ba, co, ro);
+  return hipGetLastError();
+}
+
+const uint64_t* binned_counts_table(const HitsWork* hits) { return hits ? reinterpret_cast<const uint64_t*>(hits->cnt_host) : nullptr; }
 
 hipError_t binned_rerun_rows(BinnedWork* pw, HitsWork** phw, const BinnedGeometry& geo, const HitsRef& ref, const RawAln* d_raw, const GuideDev* d_guides,
                              const uint64_t* d_win_base, const int2* d_win, const BinnedParams& p, const uint32_t* d_counters,

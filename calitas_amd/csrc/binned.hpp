@@ -30,6 +30,7 @@ constexpr uint32_t BIN_FLAG_HALO = 2;       // removeOverlaps: a hit of the bin 
 constexpr uint32_t BIN_FLAG_ROW = 4;        // a row has more padded columns (or a longer span) than the row builder lays out
 constexpr uint32_t BIN_FLAG_RANGE = 8;      // a coordinate outside the key's range
 constexpr uint32_t BIN_FLAG_TEXT = 16;      // the text buffer is too small: only the rows kernel has to run again
+constexpr uint32_t BIN_FLAG_EXTENT = 64;    // counts mode: a hit lies outside the table's extents (the general kernels then say so: the call fails)
 constexpr uint32_t BIN_FLAG_INTERNAL = 32;  // a row's length differs between the two kernels (a bug, never a property of the input)
 
 // Mailbox words of the post of the rows kernel (after the sequence word).
@@ -83,6 +84,15 @@ hipError_t binned_run(BinnedWork* work, HitsWork** hits, const BinnedGeometry& g
 hipError_t binned_rows(BinnedWork* work, HitsWork** hits, const BinnedGeometry& geo, const HitsRef& ref, const RawAln* d_raw, const GuideDev* d_guides,
                        const uint64_t* d_win_base, const int2* d_win, const BinnedParams& p, const uint32_t* d_counters, hipStream_t stream,
                        Mailbox* post, hipEvent_t ev_rows_done, char* host_dst, unsigned long long host_dst_cap);
+// The table of calitas_search_counts instead of rows, behind a binned_run(..., with_rows = false): bin_counts_kernel counts the bins'
+// kept hits (hits_dev.hpp: one histogram per workgroup in LDS) and the workgroup that finishes last writes the table into page-locked
+// host memory and then posts what the rows kernel posts (counters, rows, flags, accepted alignments, stamps; no bytes) -- the lane still
+// makes one host round trip, and the table is complete when the post arrives: binned_counts_table(), `shape.cells()` words, valid until
+// the next counts call on this HitsWork.
+hipError_t binned_counts(BinnedWork* work, HitsWork** hits, const BinnedGeometry& geo, const HitsRef& ref, const RawAln* d_raw, const GuideDev* d_guides,
+                         const uint64_t* d_win_base, const int2* d_win, const BinnedParams& p, const uint32_t* d_counters, hipStream_t stream,
+                         Mailbox* post, hipEvent_t ev_done, const CountsShape& shape);
+const uint64_t* binned_counts_table(const HitsWork* hits);
 // After BIN_FLAG_TEXT: the text buffer grown to `bytes`, the rows kernel once more.
 hipError_t binned_rerun_rows(BinnedWork* work, HitsWork** hits, const BinnedGeometry& geo, const HitsRef& ref, const RawAln* d_raw, const GuideDev* d_guides,
                              const uint64_t* d_win_base, const int2* d_win, const BinnedParams& p, const uint32_t* d_counters,

@@ -17,6 +17,7 @@ static void usage() {
     "         [-D max-total-diffs] [-O max-overlap=10] [-m guide-mismatch-net-cost=-120] [-M pam-mismatch-net-cost=-260]\n"
     "         [-b genome-gap-net-cost=-122] [-B guide-gap-net-cost=-121] [-c chrom] [-t threads (ignored)]\n"
     "         [-v variants.vcf[.gz]] [-V max-variants=16]\n"
+    "         [--counts (the table guide_id strand guide_mm guide_gaps pam_mm hits instead of hits.txt)]\n"
     "         [--device N]\n");
 }
 
@@ -40,6 +41,7 @@ int main(int argc, char** argv) {
   p.max_overlap = 10; p.guide_mismatch_net_cost = -120; p.pam_mismatch_net_cost = -260; p.genome_gap_net_cost = -122;
   p.guide_gap_net_cost = -121; p.chrom_index = -1; p.eqx_by_score = 0; p.max_variants = 16;
   int device = 0;
+  bool counts = false;
   for (int i = 2; i < argc; i++) {
     std::string a = argv[i], val;
     size_t eq = a.find('=');
@@ -69,10 +71,12 @@ int main(int argc, char** argv) {
     else if (a == "-V") p.max_variants = std::atoi(next().c_str());
     else if (a == "-t") (void)next();
     else if (a == "--device") device = std::atoi(next().c_str());
+    else if (a == "--counts") counts = true;
     else if (a == "-v") variants = next();
     else { std::fprintf(stderr, "unknown argument %s\n", a.c_str()); usage(); return 2; }
   }
   if (guide.empty() || guide_id.empty() || ref.empty()) { usage(); return 2; }
+  if (counts && !variants.empty()) { std::fprintf(stderr, "--counts covers the reference-genome branch only (no --variants)\n"); return 2; }
 
   // Guide.apply(sequence, auxPams): split by case (SequentialGuideAligner.scala:81-107)
   std::vector<std::string> parts;
@@ -118,7 +122,19 @@ int main(int argc, char** argv) {
   }
   FILE* f = output.empty() ? stdout : std::fopen(output.c_str(), "w");
   if (!f) { std::fprintf(stderr, "cannot write %s\n", output.c_str()); return 1; }
-  if (variants.empty()) {     // straight to the file: a hits.txt of tens of gigabytes (PAM-less, many diffs) is never held in memory
+  if (counts) {               // the off-target table instead of hits.txt: the non-zero cells in table order
+    calitas_counts_t* t = nullptr;
+    if (calitas_search_counts(ctx, &g, &p, &t) != CALITAS_OK) die("search");
+    std::fprintf(f, "guide_id\tstrand\tguide_mm\tguide_gaps\tpam_mm\thits\n");
+    uint64_t cell = 0;
+    for (uint32_t s = 0; s < 2; s++)
+      for (uint32_t m = 0; m < t->n_mm; m++)
+        for (uint32_t gp = 0; gp < t->n_gaps; gp++)
+          for (uint32_t pm = 0; pm < t->n_pam; pm++, cell++)
+            if (t->counts[cell]) std::fprintf(f, "%s\t%c\t%u\t%u\t%u\t%llu\n", guide_id.c_str(), s ? '-' : '+', m, gp, pm, (unsigned long long)t->counts[cell]);
+    rows = t->rows;
+    calitas_free(t);
+  } else if (variants.empty()) {     // straight to the file: a hits.txt of tens of gigabytes (PAM-less, many diffs) is never held in memory
     auto to_file = [](const char* piece, uint64_t n, void* user) -> int { return std::fwrite(piece, 1, n, (FILE*)user) == n ? 0 : 1; };
     if (calitas_search_hits_stream(ctx, &g, guide_id.c_str(), &p, nullptr, nullptr, to_file, f, &bytes, &rows) != CALITAS_OK) die("search");
   } else std::fwrite(tsv, 1, bytes, f);

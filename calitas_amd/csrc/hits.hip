@@ -336,6 +336,43 @@ __global__ __launch_bounds__(256) void rows_kernel(MidArgs a, OutArgs o, char* t
   }
 }
 
+// Counts mode: behind the walks, instead of len_kernel / rows_kernel.  One lane per sorted position k: keep[k] and order[k] lead to the
+// alignment fin[order[k]] and its record; a kept hit the call owns (HitsOwn, as len_kernel applies it) adds one to its cell of the
+// workgroup's histogram (hits_dev.hpp: counts_cell, CountsOut).  The workgroup that finishes last brings the table to the host and
+// posts what total_kernel posts for a text: no bytes, the rows it counted, the flags.
+__global__ __launch_bounds__(COUNTS_BLOCK) void counts_kernel(MidArgs a, CountsOut o, uint64_t* counts, uint32_t* flags, uint32_t* box, uint32_t seq) {
+  CALITAS_TAIL_PRIO();
+  __shared__ uint32_t hist[COUNTS_LDS_CELLS];
+  __shared__ uint32_t s_rows;
+  if (threadIdx.x == 0) s_rows = 0;
+  counts_begin(hist, o);
+  uint32_t mine = 0;
+  for (uint32_t k = blockIdx.x * COUNTS_BLOCK + threadIdx.x; k < a.n; k += gridDim.x * COUNTS_BLOCK) {
+    if (!a.keep[k]) continue;
+    const uint32_t v = a.order[k];
+    if (v >= a.n_dev) continue;                             // (a hit of the caller's own: not in a counts call)
+    const HitRec h = a.hits[v];
+    const unsigned long long key = ((unsigned long long)(uint32_t)h.contig << 32) | (uint32_t)h.gstart;
+    if (key < a.own_lo || key >= a.own_hi) continue;
+    const int cell = counts_cell(a.fin + v, h.minus, o.shape);
+    if (cell < 0) { atomicOr(flags, HITS_FLAG_EXTENT); continue; }
+    counts_add(hist, o, cell);
+    mine++;
+  }
+  // rows of the call: one LDS add per lane that counted, one global add per workgroup
+  if (mine) (void)__hip_atomic_fetch_add(&s_rows, mine, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+  __syncthreads();
+  if (threadIdx.x == 0 && s_rows) (void)__hip_atomic_fetch_add(a.n_rows, s_rows, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  if (!counts_flush(hist, o)) return;
+  counts_publish(o);
+  if (threadIdx.x == 0) {
+    const uint32_t* src = reinterpret_cast<const uint32_t*>(counts);   // [0] bytes: none, [1] rows, [2] flags
+    for (int i = 0; i < 6; i++) box[1 + i] = __hip_atomic_load(src + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __threadfence_system();
+    __hip_atomic_store(box, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+  }
+}
+
 // Length of the text = end of the last row; posted with the other two counts (rows, flags) to the host's mailbox (mailbox.hpp) by the
 // same thread -- a kernel of its own for the post was one more launch on the path every call waits for.
 __global__ void total_kernel(const uint64_t* offs, const uint64_t* lens, uint32_t n, uint64_t* counts, uint32_t* box, uint32_t seq) {
@@ -389,6 +426,8 @@ void hits_destroy(HitsWork* w) {
   if (w->h_ext_keep) (void)hipHostFree(w->h_ext_keep);
   if (w->h_ext_place) (void)hipHostFree(w->h_ext_place);
   if (w->h_counts) (void)hipHostFree(w->h_counts);
+  (void)hipFree(w->cnt_table);
+  if (w->cnt_host) (void)hipHostFree(w->cnt_host);
   mailbox_close(w->mbox);
   delete w;
 }
@@ -447,15 +486,23 @@ hipError_t hits_prepare_host(HitsWork** pw, const RowStrings& st, HitsSetup* out
 
 hipError_t hits_run(HitsWork** pw, const HitsRef& ref, const RawAln* d_final, uint32_t n_in, const GuideDev* d_guides,
                     const uint64_t* d_win_base, const int2* d_win, const RowStrings& st, int max_overlap, int score_hi,
-                    int max_ops, uint32_t window_reach, hipStream_t stream, HitsResult* res, const HitsExt* ext, const HitsOwn* own) {
+                    int max_ops, uint32_t window_reach, hipStream_t stream, HitsResult* res, const HitsExt* ext, const HitsOwn* own,
+                    const CountsShape* counts) {
   if (!*pw) *pw = new HitsWork();
   HitsWork& w = **pw;
   hipError_t e;
   *res = HitsResult{};
   const uint32_t n_ext = ext ? ext->n : 0;
+  if (counts && n_ext) return hipErrorInvalidValue;      // (a table of the reference's own hits)
   if (ext && ext->kept) *ext->kept = 0;
   if ((uint64_t)n_in + n_ext > 0xFFFFFFF0ull) { res->flags = HITS_FLAG_CLUSTER; return hipSuccess; }
   const size_t n = (size_t)n_in + n_ext;
+  CountsOut co{};
+  if (counts) {
+    TRY(counts_buffers(w, *counts, &co));
+    if (n == 0) std::memset(co.host, 0, (size_t)co.cells * sizeof(unsigned long long));
+    res->counts = reinterpret_cast<const uint64_t*>(co.host);
+  }
   if (n == 0) return hipSuccess;
   if (n_ext) window_reach = 0;                         // the caller's hits have no window: the general stable sort
   n_in = (uint32_t)n;                                  // every stage behind hit_kernel runs over both; n_dev is the device's share
@@ -552,6 +599,21 @@ hipError_t hits_run(HitsWork** pw, const HitsRef& ref, const RawAln* d_final, ui
     HitsExtRows made;
     if (ext->rows_for(w.h_ext_keep, &made) != 0) return hipErrorUnknown;
     TRY(upload_ext_rows(made));
+  }
+  if (counts) {
+    // 4, counts mode: the table of the kept hits instead of their rows -- one launch, and the post the host waits for comes from it
+    MidArgs ca{};
+    ca.fin = d_final; ca.hits = w.hits; ca.guides = d_guides; ca.keep = w.keep; ca.order = w.vals2; ca.n = n_in; ca.n_dev = n_dev;
+    ca.n_rows = d_kept; ca.own_lo = ho.lo; ca.own_hi = ho.hi;
+    TRY(mailbox_open(w.mbox));
+    w.mbox.seq++;
+    hipLaunchKernelGGL(counts_kernel, dim3(counts_grid(n)), dim3(COUNTS_BLOCK), 0, stream, ca, co, w.d_counts, d_flags, w.mbox.dev, w.mbox.seq);
+    TRY(hipGetLastError());
+    TRY(mailbox_wait(w.mbox, stream));
+    for (int k = 0; k < 3; k++) w.h_counts[k] = (uint64_t)w.mbox.host[1 + 2 * k] | ((uint64_t)w.mbox.host[2 + 2 * k] << 32);
+    res->flags = (uint32_t)w.h_counts[2];
+    res->n_rows = (uint32_t)w.h_counts[1];
+    return hipSuccess;
   }
   // 4: rows
   // (a row with more padded columns than a wave has lanes raises HITS_FLAG_ROW and the caller finishes on the host)

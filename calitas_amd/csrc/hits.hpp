@@ -25,9 +25,19 @@ struct HitsRef {   // the resident reference
   int n_contigs;
 };
 
+// The extents of the off-target table of calitas_search_counts (calitas_hip.h, calitas_counts_t): a function of the guide and the
+// params alone (search_plan.cpp, counts_shape).
+struct CountsShape {
+  uint32_t n_mm = 0, n_gaps = 0, n_pam = 0;
+  uint32_t cells() const { return 2u * n_mm * n_gaps * n_pam; }
+};
+
 struct HitsResult {
   uint32_t flags;        // != 0: the device path declined (see HITS_FLAG_*); nothing else is valid
   uint32_t n_rows;
+  // counts mode: the table (CountsShape::cells() words, page-locked host memory of the work's, complete when hits_run returns and valid
+  // until the next hits_run on this work); n_rows is its sum, there is no text
+  const uint64_t* counts;
   uint64_t text_bytes;   // bytes of row text at d_text
   const char* d_text;
   // HitsExtRows::fill_on_host: per entry of the HitsExt, the offset of its row's hole in the text, ~0 for an entry that was not kept.
@@ -41,6 +51,7 @@ constexpr uint32_t HITS_FLAG_CLUSTER = 2;       // an overlap cluster is longer 
 
 constexpr uint32_t HITS_FLAG_ROW = 4;           // a row has more padded columns than max_ops allows
 constexpr uint32_t HITS_FLAG_INTERNAL = 16;     // a row's length differs between len_kernel and rows_kernel (a bug, never a property of the input)
+constexpr uint32_t HITS_FLAG_EXTENT = 32;       // counts mode: a hit lies outside the table's extents (the call fails: a hit is never dropped or clamped)
 constexpr uint32_t HITS_FLAG_HALO = 8;          // HitsOwn: an owned hit hangs on a removeOverlaps cluster that starts where not every hit is known
 
 // Whether the sort keys can represent this search at all.
@@ -121,11 +132,12 @@ struct HitsExtSource { std::function<int(int contig, const HitsExt** ext)> get; 
 // synchronisation to learn the text size.  max_ops bounds the padded columns of any alignment of this search (it sizes the
 // per-row LDS slots).  window_reach: the number of window steps after which two windows share no base (the final order then comes
 // from a count among neighbouring windows), or 0 for the general sort (crowded windows).  On success the rows are at res->d_text in
-// final order.
+// final order.  counts: no rows -- counts_kernel takes the place of the row kernels behind the walks and res->counts is the table of the
+// kept (and owned) hits; still one host round trip.
 hipError_t hits_run(HitsWork** work, const HitsRef& ref, const RawAln* d_final, uint32_t n, const GuideDev* d_guides,
                     const uint64_t* d_win_base, const int2* d_win, const RowStrings& strings, int max_overlap, int score_hi,
                     int max_ops, uint32_t window_reach, hipStream_t stream, HitsResult* res, const HitsExt* ext = nullptr,
-                    const HitsOwn* own = nullptr);
+                    const HitsOwn* own = nullptr, const CountsShape* counts = nullptr);
 // Flags raised while the rows of the last hits_run were being written (HITS_FLAG_INTERNAL); valid once the stream the rows kernel ran
 // on is done.
 uint32_t hits_late(const HitsWork* work);

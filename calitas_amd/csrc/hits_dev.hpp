@@ -4,6 +4,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstddef>
 #include <string>
 
@@ -335,6 +336,19 @@ hipError_t grow(T** p, size_t& cap, size_t need) {
 
 }  // namespace
 
+// guide_mm, guide_gaps and pam_mm of a hit (the hits.txt columns, GA:103, 104, 106) from the alignment's op counts -- the one place this
+// arithmetic lives: middle_length formats the three into a row's length, the counts kernels (counts_kernel, bin_counts_kernel) make a
+// table cell of them.
+struct HitKey { int guide_mm, guide_gaps, pam_mm; };
+__device__ __forceinline__ HitKey hit_key(const OpCounts& oc, int pam, int offset, uint32_t pam_x) {
+  const int gap = pam >= 0 ? offset : 0;
+  HitKey k;
+  k.guide_mm = oc.non_eq - oc.gaps;                      // 'X' columns by the case of the query base (GA:103)
+  k.pam_mm = pam >= 0 ? __popc(pam_x) : 0;               // GA:106
+  k.guide_gaps = oc.gaps + gap;                          // every gap column has a protospacer base on one side (GA:104, 168-182)
+  return k;
+}
+
 // Length of the middle part of a row = what build_middle computes with ballots, for one lane: the field lengths of RH:210-254 from
 // the alignment's op counts (GA:99-115, 139-183) and the run-length encoding of its cigar.  -1: the row builder does not lay it out.
 __device__ __forceinline__ int middle_length(const RawAln* rp, const HitRec& h, int L, int pam_len, int pu_len, int n_max, int mid_bound) {
@@ -347,8 +361,8 @@ __device__ __forceinline__ int middle_length(const RawAln* rp, const HitRec& h, 
   const OpsWords ow = load_ops_words(rp->ops);
   const OpCounts oc = count_ops(ow, ng);
   const int utn = oc.not_ins - oc.lead_d - oc.trail_d;                 // target bases under the first .. last protospacer column (GA:111-115)
-  const int gmm = oc.non_eq - oc.gaps, pam_mm = pam >= 0 ? __popc(pam_x) : 0;   // 'X' columns by the case of the query base (GA:103, 106)
-  const int ggp = oc.gaps + gap;                                       // every gap column has a protospacer base on one side (GA:104, 168-182)
+  const HitKey hk = hit_key(oc, pam, rp->offset, pam_x);
+  const int gmm = hk.guide_mm, pam_mm = hk.pam_mm, ggp = hk.guide_gaps;
   const int edits = oc.non_eq + gap + pam_mm;                          // GA:101
   // Cigar.coalesce + toString over the columns: guide part (aligner order = traceback order reversed), the gap, the PAM; the number of
   // runs and of two-digit run lengths does not depend on the direction the columns are read in (5' PAM)
@@ -369,6 +383,78 @@ __device__ __forceinline__ int middle_length(const RawAln* rp, const HitRec& h, 
                     digits(gmm + ggp) + digits(pam_mm) + digits(edits) + 3 * n + 8 + 8 + cigar_len + digits(L) + digits(utn);
   return total > mid_bound ? -1 : total;
 }
+
+// ---- the off-target table (calitas_search_counts) ---------------------------------------------------------------------------------
+// Both counts kernels work the same way: a histogram per workgroup in LDS (non-returning ds_add_u32), its non-zero cells flushed once
+// into the call's table in device memory (non-returning 64-bit adds), and the workgroup that finishes last -- a ticket per workgroup,
+// never an atomic whose value a hit waits for -- writes the table into page-locked host memory, clears table and ticket for the next
+// call and posts the lane's mailbox: the host reads the table behind the wait it makes anyway.  A table with more cells than
+// COUNTS_LDS_CELLS (extents of a search with very many differences) adds every hit to the device table directly: slower, same table.
+constexpr uint32_t COUNTS_LDS_CELLS = 4096;    // 16 KB of a workgroup's LDS
+constexpr uint32_t COUNTS_BLOCK = 256;
+
+struct CountsOut {
+  CountsShape shape;
+  uint32_t cells;
+  unsigned long long* table;   // device memory, `cells` words: zero at launch, zero again when the kernel ends
+  uint32_t* tickets;           // one word, likewise
+  unsigned long long* host;    // page-locked host memory, `cells` words
+};
+
+// The cell of a hit, or -1 when it lies outside the extents.
+__device__ __forceinline__ int counts_cell(const RawAln* rp, uint32_t minus, const CountsShape& s) {
+  const OpCounts oc = count_ops(load_ops_words(rp->ops), rp->n_ops);
+  const HitKey k = hit_key(oc, rp->pam, rp->offset, rp->pam_x);
+  if (k.guide_mm < 0 || k.guide_gaps < 0 || (uint32_t)k.guide_mm >= s.n_mm || (uint32_t)k.guide_gaps >= s.n_gaps || (uint32_t)k.pam_mm >= s.n_pam) return -1;
+  return (int)((((minus & 1u) * s.n_mm + (uint32_t)k.guide_mm) * s.n_gaps + (uint32_t)k.guide_gaps) * s.n_pam + (uint32_t)k.pam_mm);
+}
+
+__device__ __forceinline__ void counts_begin(uint32_t* hist, const CountsOut& o) {
+  if (o.cells <= COUNTS_LDS_CELLS) for (uint32_t i = threadIdx.x; i < o.cells; i += blockDim.x) hist[i] = 0u;
+  __syncthreads();
+}
+
+__device__ __forceinline__ void counts_add(uint32_t* hist, const CountsOut& o, int cell) {
+  if (o.cells <= COUNTS_LDS_CELLS) (void)__hip_atomic_fetch_add(hist + cell, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+  else (void)__hip_atomic_fetch_add(o.table + cell, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// The workgroup's histogram into the call's table; true in every thread of the workgroup that finished last, which then sees every
+// workgroup's adds (and whatever else they wrote with device-scope atomics).
+__device__ __forceinline__ bool counts_flush(uint32_t* hist, const CountsOut& o) {
+  __shared__ uint32_t s_ticket;
+  __syncthreads();
+  if (o.cells <= COUNTS_LDS_CELLS)
+    for (uint32_t i = threadIdx.x; i < o.cells; i += blockDim.x) {
+      const uint32_t v = hist[i];
+      if (v) (void)__hip_atomic_fetch_add(o.table + i, (unsigned long long)v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");        // this wave's adds have been performed ...
+  __syncthreads();                                        // ... and every wave's of the workgroup
+  if (threadIdx.x == 0) {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    s_ticket = __hip_atomic_fetch_add(o.tickets, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+  __syncthreads();
+  if (s_ticket != gridDim.x - 1) return false;
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+  return true;
+}
+
+// The last workgroup: the table to the host, table and ticket cleared.  The caller posts the mailbox behind this (thread 0).
+__device__ __forceinline__ void counts_publish(const CountsOut& o) {
+  for (uint32_t i = threadIdx.x; i < o.cells; i += blockDim.x) {
+    o.host[i] = __hip_atomic_load(o.table + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_store(o.table + i, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+  if (threadIdx.x == 0) __hip_atomic_store(o.tickets, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  __threadfence_system();                                 // every thread's words are on the host before thread 0 posts
+  __syncthreads();
+}
+
+// Workgroups of a counts kernel over `items` items (each strides over them).
+static inline unsigned counts_grid(size_t items) { return (unsigned)std::min<size_t>(std::max<size_t>((items + COUNTS_BLOCK - 1) / COUNTS_BLOCK, 1), 128); }
 
 struct HitsWork {
   HitRec* hits = nullptr; size_t hits_cap = 0;
@@ -392,11 +478,40 @@ struct HitsWork {
   uint64_t* h_ext_place = nullptr; size_t h_ext_place_cap = 0;
   uint64_t* d_counts = nullptr;   // [0] text bytes, [1] low word: kept rows, high word: kept hits of the caller's own, [2] low word: flags
   uint64_t* h_counts = nullptr;   // pinned
+  // counts mode (CountsOut): the call's table on the device with its ticket word behind it, and the table's page-locked copy
+  unsigned long long* cnt_table = nullptr; size_t cnt_cap = 0;
+  unsigned long long* cnt_host = nullptr; size_t cnt_host_cap = 0;
   Mailbox mbox;                   // carries d_counts to the host (mailbox.hpp)
   RowConstDev rc{};               // set by hits_prepare
   size_t blob_bytes = 0;
   std::string blob_host;
   bool prepared = false;
 };
+
+// The buffers of a call's table in the work (zero on the device: the kernels leave them so).
+inline hipError_t counts_buffers(HitsWork& w, const CountsShape& shape, CountsOut* out) {
+  const size_t cells = shape.cells();
+  if (cells == 0) return hipErrorInvalidValue;
+  if (cells + 2 > w.cnt_cap) {
+    (void)hipFree(w.cnt_table); w.cnt_table = nullptr; w.cnt_cap = 0;
+    const size_t cap = ((cells + 2) + 1) & ~(size_t)1;     // (a multiple of 16 bytes)
+    hipError_t e = hipMalloc((void**)&w.cnt_table, cap * sizeof(unsigned long long));
+    if (e != hipSuccess) return e;
+    e = hipMemset(w.cnt_table, 0, cap * sizeof(unsigned long long));
+    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);   // (the kernels run on streams nothing orders against the null stream)
+    if (e != hipSuccess) return e;
+    w.cnt_cap = cap;
+  }
+  if (cells > w.cnt_host_cap) {
+    if (w.cnt_host) (void)hipHostFree(w.cnt_host);
+    w.cnt_host = nullptr; w.cnt_host_cap = 0;
+    hipError_t e = hipHostMalloc((void**)&w.cnt_host, cells * sizeof(unsigned long long), hipHostMallocDefault);
+    if (e != hipSuccess) return e;
+    w.cnt_host_cap = cells;
+  }
+  out->shape = shape; out->cells = (uint32_t)cells; out->table = w.cnt_table; out->tickets = reinterpret_cast<uint32_t*>(w.cnt_table + w.cnt_cap - 1);
+  out->host = w.cnt_host;
+  return hipSuccess;
+}
 
 }  // namespace calitas

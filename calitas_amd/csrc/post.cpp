@@ -573,15 +573,10 @@ static size_t row_bound(const PackedRef& ref, const RowStrings& rc) {
   return rc.head.size() + rc.tail.size() + name + 5 * (CALITAS_MAX_OPS + 4) + 256;
 }
 
-char* hits_tsv(const PackedRef& ref, const GuideHost& g, const std::string& guide_id, const calitas_params_t& p,
-               const calitas_aln_t* alns, uint64_t n, const std::string& version, const std::string& time_stamp,
-               uint64_t* n_rows, WorkerPool* pool, void* (*alloc)(size_t), const calitas_ext_hit_t* ext, uint64_t n_ext, ExtRowFn ext_row,
-               void* ext_user) {
-  WorkerPool serial(1);
-  if (!pool) pool = &serial;
-  const bool trace = TUNE_GET("CALITAS_TRACE") != nullptr;
-  auto tnow = [] { return std::chrono::steady_clock::now(); };
-  auto t_start = tnow();
+// removeOverlaps (SR:653-675) and ReferenceHit.sort (SR:647) on one guide's alignments and the caller's own hits: the kept hits in
+// final order (idx < n: alns[idx], else ext[idx - n]).  What hits_tsv builds rows of and hits_counts counts.
+static std::vector<Lite> kept_hits(const PackedRef& ref, const calitas_params_t& p, const calitas_aln_t* alns, uint64_t n, WorkerPool* pool,
+                                   const calitas_ext_hit_t* ext, uint64_t n_ext) {
   auto by_hit_order = [](const Lite& x, const Lite& y) {   // RH:284
     if (x.contig != y.contig) return x.contig < y.contig;
     if (x.start != y.start) return x.start < y.start;
@@ -677,6 +672,19 @@ char* hits_tsv(const PackedRef& ref, const GuideHost& g, const std::string& guid
   }
   std::vector<Lite> keepers;
   for (auto& v : kept_by_contig) keepers.insert(keepers.end(), v.begin(), v.end());
+  return keepers;
+}
+
+char* hits_tsv(const PackedRef& ref, const GuideHost& g, const std::string& guide_id, const calitas_params_t& p,
+               const calitas_aln_t* alns, uint64_t n, const std::string& version, const std::string& time_stamp,
+               uint64_t* n_rows, WorkerPool* pool, void* (*alloc)(size_t), const calitas_ext_hit_t* ext, uint64_t n_ext, ExtRowFn ext_row,
+               void* ext_user) {
+  WorkerPool serial(1);
+  if (!pool) pool = &serial;
+  const bool trace = TUNE_GET("CALITAS_TRACE") != nullptr;
+  auto tnow = [] { return std::chrono::steady_clock::now(); };
+  auto t_start = tnow();
+  const std::vector<Lite> keepers = kept_hits(ref, p, alns, n, pool, ext, n_ext);
   auto t_dedup = tnow();
 
   // ---- rows (RH:210-254), built in parallel blocks and concatenated in order ----
@@ -744,6 +752,36 @@ char* hits_tsv(const PackedRef& ref, const GuideHost& g, const std::string& guid
                  ms(t_start, t_dedup), ms(t_dedup, t_rows), ms(t_rows, tnow()), keepers.size(), total);
   }
   return out;
+}
+
+std::string hits_counts(const PackedRef& ref, const GuideHost& g, const calitas_params_t& p, const calitas_aln_t* alns, uint64_t n, uint32_t n_mm,
+                        uint32_t n_gaps, uint32_t n_pam, uint64_t* table, uint64_t* n_rows, WorkerPool* pool) {
+  WorkerPool serial(1);
+  if (!pool) pool = &serial;
+  const std::vector<Lite> keepers = kept_hits(ref, p, alns, n, pool, nullptr, 0);
+  for (const Lite& k : keepers) {
+    const calitas_aln_t& a = alns[k.idx];
+    const std::string q = g.query_for(a.pam_index);
+    char pg[CALITAS_MAX_OPS + 1], pa[CALITAS_MAX_OPS + 1];
+    const int len = a.n_ops;
+    size_t qi = 0;
+    for (int i = 0; i < len; i++) {                        // the padded guide and alignment strings, as write_row lays them out (SGA:511)
+      const bool has_q = a.ops[i] != 'D';
+      if (has_q && qi >= q.size()) return "an alignment has more guide columns than its guide has bases";
+      pg[i] = has_q ? q[qi++] : '-';
+      pa[i] = a.ops[i] == '=' ? '|' : a.ops[i] == 'X' ? '.' : '~';
+    }
+    const int gmm = ga_count_raw(pg, pa, len, false, false, true, false);    // guide_mm GA:103
+    const int ggp = ga_count_raw(pg, pa, len, false, false, false, true);    // guide_gaps GA:104
+    const int pmm = ga_count_raw(pg, pa, len, true, true, true, false);      // pam_mm GA:106
+    if ((uint32_t)gmm >= n_mm || (uint32_t)ggp >= n_gaps || (uint32_t)pmm >= n_pam)
+      return "a hit with guide_mm " + std::to_string(gmm) + ", guide_gaps " + std::to_string(ggp) + ", pam_mm " + std::to_string(pmm) +
+             " lies outside the table's extents (" + std::to_string(n_mm) + " x " + std::to_string(n_gaps) + " x " + std::to_string(n_pam) + ")";
+    const uint32_t s = a.strand == '-' ? 1u : 0u;
+    table[((s * n_mm + (uint32_t)gmm) * n_gaps + (uint32_t)ggp) * n_pam + (uint32_t)pmm]++;
+  }
+  if (n_rows) *n_rows = keepers.size();
+  return "";
 }
 
 }  // namespace calitas

@@ -81,4 +81,10 @@ char* hits_tsv(const PackedRef& ref, const GuideHost& g, const std::string& guid
                uint64_t* n_rows, WorkerPool* pool = nullptr, void* (*alloc)(size_t) = nullptr, const calitas_ext_hit_t* ext = nullptr,
                uint64_t n_ext = 0, ExtRowFn ext_row = nullptr, void* ext_user = nullptr);
 
+// The twin of hits_tsv for calitas_hits_counts: removeOverlaps on one guide's alignments, then the kept hits counted by (strand,
+// guide_mm, guide_gaps, pam_mm) -- the values hits_tsv writes into the columns of those names -- into table[2 * n_mm * n_gaps * n_pam],
+// which the caller has cleared.  *n_rows: the kept hits.  An error text when a hit lies outside the extents, else "".
+std::string hits_counts(const PackedRef& ref, const GuideHost& g, const calitas_params_t& p, const calitas_aln_t* alns, uint64_t n, uint32_t n_mm,
+                        uint32_t n_gaps, uint32_t n_pam, uint64_t* table, uint64_t* n_rows, WorkerPool* pool = nullptr);
+
 }  // namespace calitas

@@ -65,12 +65,27 @@ static calitas_timing_t batch_timing(const std::vector<calitas_timing_t>& tms) {
 // guide g's tail runs.  Each guide's text goes to its own pinned buffer.
 int calitas_search_hits_batch_impl(calitas_ctx* ctx, int32_t n_guides, const calitas_guide_t* guides, const char* const* guide_ids,
                                   const calitas_params_t* params, const char* aligner_version, const char* time_stamp, char** tsv,
-                                  uint64_t* tsv_bytes, uint64_t* n_rows) {
+                                  uint64_t* tsv_bytes, uint64_t* n_rows, std::vector<std::vector<uint64_t>>* tables) {
+  // tables (calitas_search_counts_batch): every guide's tail runs in counts mode and `finish` takes its table -- no text is built, copied
+  // or expanded, tsv is not touched; (*tables)[i] and n_rows[i] receive what calitas_search_counts returns for guides[i]
+  const bool counting = tables != nullptr;
   const auto t_call = std::chrono::steady_clock::now();
-  for (int i = 0; i < n_guides; i++) { tsv[i] = nullptr; if (tsv_bytes) tsv_bytes[i] = 0; if (n_rows) n_rows[i] = 0; }
+  for (int i = 0; i < n_guides; i++) { if (tsv) tsv[i] = nullptr; if (tsv_bytes) tsv_bytes[i] = 0; if (n_rows) n_rows[i] = 0; }
+  // one guide through the single-guide call: when there is nothing to pipeline, and for a guide the pipeline could not finish
+  auto single = [&](int i, const std::string& version, const std::string& stamp) -> int {
+    if (counting) {
+      CountsShape shape;
+      uint64_t rows = 0;
+      const int rc = calitas_search_counts_impl(ctx, &guides[i], params, &shape, &(*tables)[(size_t)i], &rows);
+      if (!rc && n_rows) n_rows[i] = rows;
+      return rc;
+    }
+    return calitas_search_hits_impl(ctx, &guides[i], guide_ids && guide_ids[i] ? guide_ids[i] : "", params, version.c_str(), stamp.c_str(), &tsv[i],
+                                    tsv_bytes ? &tsv_bytes[i] : nullptr, n_rows ? &n_rows[i] : nullptr);
+  };
   std::string version, stamp;
   calitas_default_version_and_stamp(aligner_version, time_stamp, version, stamp);
-  auto release = [&]() { for (int i = 0; i < n_guides; i++) { calitas_free(tsv[i]); tsv[i] = nullptr; } };
+  auto release = [&]() { if (tsv) for (int i = 0; i < n_guides; i++) { calitas_free(tsv[i]); tsv[i] = nullptr; } };
   // Five guides in flight: with three the bus idled a sixth of the time between the texts of a 96-guide batch on an hg38-sized genome
   // (15.3 GB per batch: 328.6 ms; four lanes 298.0, five 292.1 = 52 GB/s, six 300.6, eight 295.5).
   int n_lanes = 5;
@@ -78,8 +93,7 @@ int calitas_search_hits_batch_impl(calitas_ctx* ctx, int32_t n_guides, const cal
   n_lanes = std::min(n_lanes, (int)n_guides);
   if (n_lanes < 2) {   // nothing to pipeline
     for (int i = 0; i < n_guides; i++) {
-      int rc = calitas_search_hits_impl(ctx, &guides[i], guide_ids && guide_ids[i] ? guide_ids[i] : "", params, version.c_str(), stamp.c_str(), &tsv[i],
-                                tsv_bytes ? &tsv_bytes[i] : nullptr, n_rows ? &n_rows[i] : nullptr);
+      int rc = single(i, version, stamp);
       if (rc) { release(); return rc; }
     }
     return CALITAS_OK;
@@ -88,6 +102,7 @@ int calitas_search_hits_batch_impl(calitas_ctx* ctx, int32_t n_guides, const cal
   std::vector<char> owned_ok((size_t)n_guides, 1);
   int rc = plan_batch(ctx, n_guides, guides, params, n_lanes, plans, owned_ok);
   if (rc) return rc;
+  if (counting) for (auto& q : plans) q.counts = true;
   const PackedRef& ref = ctx->ref;
   std::mutex scan_mu, copy_mu;
   const bool device_rows = !TUNE_GET("CALITAS_HOST_HITS");
@@ -127,6 +142,13 @@ int calitas_search_hits_batch_impl(calitas_ctx* ctx, int32_t n_guides, const cal
   auto finish = [&](calitas_ctx* lane, InFlight& f) -> int {
     const int g = f.g;
     LaneText& lt = f.lt;
+    if (counting) {                                            // the table is on the host already: nothing to bring in
+      if (lt.counts.size() != plans[g].cshape.cells()) return fail(lane, CALITAS_EHIP, "a guide's tail returned no counts table (internal error)");
+      (*tables)[(size_t)g] = std::move(lt.counts);
+      if (n_rows) n_rows[g] = lt.rows;
+      tms[g] = lt.tm; tms[g].hit_rows = lt.rows; tms[g].hits_bytes = 0;
+      return CALITAS_OK;
+    }
     const RowStrings& rs = f.rs;
     const RowStrings& rs_full = f.rs_full;
     const bool expand = compact_rows && !lt.on_host;           // (rows the host stages built are whole already)
@@ -188,8 +210,7 @@ int calitas_search_hits_batch_impl(calitas_ctx* ctx, int32_t n_guides, const cal
   for (int g = 0; g < n_guides; g++) {
     if (rcs[g] == CALITAS_OK) continue;
     if (rcs[g] == CALITAS_ESTATE || rcs[g] == CALITAS_ENOMEM || rcs[g] == kOwnedDeclined) {   // a lane's buffers overflowed / did not fit / the bins declined a stretch: this guide again through calitas_search_hits (retry logic, per-contig passes, the whole-contig path of a stretch)
-      int r = calitas_search_hits_impl(ctx, &guides[g], guide_ids && guide_ids[g] ? guide_ids[g] : "", params, version.c_str(), stamp.c_str(), &tsv[g],
-                               tsv_bytes ? &tsv_bytes[g] : nullptr, n_rows ? &n_rows[g] : nullptr);
+      int r = single(g, version, stamp);
       if (r) { release(); return r; }
       tms[g] = ctx->timing;
       continue;

@@ -125,7 +125,7 @@ static int search_hits_owned(calitas_ctx* ctx, const HitsCall& call, HitsOut& ou
     // the stretch on the per-bin kernels, cut into lanes like any other call (search_hits_attempt): everything it returns is final
     const uint64_t range[2] = {(uint64_t)params->first_window, (uint64_t)params->n_windows};
     bool declined = false;
-    const HitsCall all{call.guide, call.guide_id, &whole, call.aligner_version, call.time_stamp, call.user_dst, call.user_cap};
+    const HitsCall all{call.guide, call.guide_id, &whole, call.aligner_version, call.time_stamp, call.user_dst, call.user_cap, nullptr, nullptr, nullptr, call.counts};
     rc = search_hits_attempt(ctx, all, out, range, &declined);
     if (rc || !declined) return rc;
     HIP_TRY(ctx, calitas_spin_sync(ctx->stream));
@@ -144,6 +144,26 @@ static int search_hits_owned(calitas_ctx* ctx, const HitsCall& call, HitsOut& ou
   std::string body;
   uint64_t rows = 0;
   calitas_timing_t tm{};
+  // counts mode on this (rare, slow) path: the kept rows are counted by their columns strand (6), guide_mm (16), guide_gaps (17) and
+  // pam_mm (19) of RH:99-132 -- the text calls of the touched contigs decide the rows either way
+  std::vector<uint64_t> table(call.counts ? pl.cshape.cells() : 0, 0);
+  auto count_row = [&](const char* q, const char* row_end) -> bool {
+    const char* f = q;
+    uint32_t minus = 0;
+    long v[3] = {0, 0, 0};
+    for (int k = 0; k < 20 && f < row_end; k++) {
+      if (k == 6) minus = *f == '-' ? 1u : 0u;
+      if (k == 16) v[0] = std::strtol(f, nullptr, 10);
+      if (k == 17) v[1] = std::strtol(f, nullptr, 10);
+      if (k == 19) v[2] = std::strtol(f, nullptr, 10);
+      const char* tab = (const char*)std::memchr(f, '\t', (size_t)(row_end - f));
+      f = tab ? tab + 1 : row_end;
+    }
+    const CountsShape& cs = pl.cshape;
+    if (v[0] < 0 || v[1] < 0 || v[2] < 0 || (uint32_t)v[0] >= cs.n_mm || (uint32_t)v[1] >= cs.n_gaps || (uint32_t)v[2] >= cs.n_pam) return false;
+    table[((minus * cs.n_mm + (uint32_t)v[0]) * cs.n_gaps + (uint32_t)v[1]) * cs.n_pam + (uint32_t)v[2]]++;
+    return true;
+  };
   for (size_t c = 0; c < ref.contigs.size(); c++) {
     if (wb[c + 1] <= first || wb[c] >= last || wb[c + 1] == wb[c]) continue;
     calitas_params_t pc = whole;
@@ -163,11 +183,21 @@ static int search_hits_owned(calitas_ctx* ctx, const HitsCall& call, HitsOut& ou
       for (int k = 0; k < 4 && f < row_end; k++) { const char* tab = (const char*)std::memchr(f, '\t', (size_t)(row_end - f)); f = tab ? tab + 1 : row_end; }
       const uint64_t pos = std::strtoull(f, nullptr, 10);
       const uint64_t key = ((uint64_t)c << 32) | pos;
-      if (key >= own_lo && key < own_hi) { body.append(q, (size_t)(row_end - q)); rows++; }
+      if (key >= own_lo && key < own_hi) {
+        if (!call.counts) body.append(q, (size_t)(row_end - q));
+        else if (!count_row(q, row_end)) { calitas_free(t); return fail(ctx, CALITAS_EHIP, "a hit lies outside the extents of the counts table (internal error)"); }
+        rows++;
+      }
       q = row_end;
     }
     calitas_free(t);
     add_lane_timing(tm, ctx->timing);                          // (a whole call's timing each)
+  }
+  if (call.counts) {
+    tm.hit_rows = rows; tm.hits_bytes = 0; tm.lanes = 1;
+    ctx->timing = tm;
+    out.counts = std::move(table); out.shape = pl.cshape; out.rows = rows;
+    return CALITAS_OK;
   }
   const size_t total = hlen + body.size();
   if (call.user_dst && call.user_cap < total + 1) return fail(ctx, CALITAS_EINVAL, "the caller's buffer is too small for the text");
@@ -265,7 +295,7 @@ struct TextBlock {
     }
     return text != nullptr;
   }
-  void release() { if (!user_dst) calitas_free(text); text = nullptr; }
+  void release() { if (!user_dst && text) calitas_free(text); text = nullptr; }
 };
 
 // A one-pass call under way: what its stages, and the threads of its lanes, share.
@@ -458,7 +488,7 @@ static void run_lane(Attempt& a, size_t c) {
     return true;
   };
   lt.rc = lane_rows(a.lanes[c], a.plans[c], true, a.rs_lane(c), a.call.guide_id, a.version, a.stamp, lt, a.device_rows,
-                    c + 1 == K && a.device_rows && !a.lane_compact[c] ? &dest : nullptr);
+                    c + 1 == K && a.device_rows && !a.lane_compact[c] && !a.call.counts ? &dest : nullptr);
   if (lt.rc == CALITAS_OK && a.lane_compact[c] && !lt.on_host && !lt.in_place && lt.bytes) {   // what the lanes behind it place their text by: the expanded size
     lt.compact_bytes = lt.bytes;
     lt.bytes += lt.rows * (uint64_t)(a.rs.head.size() + a.rs.tail.size() - 1);
@@ -547,7 +577,8 @@ static int attempt_chunked(Attempt& a, const std::vector<std::pair<int, int>>& r
   const size_t K = a.parts.size();
   int rc = queue_ranges(a, ranges, owned_plans);
   if (rc) return rc;
-  if (!a.tb.alloc(a.rs.header, text_guess(ctx->last_text_bytes))) {
+  // (counts mode: no text block -- the lanes' tables are summed when they are all in)
+  if (!a.call.counts && !a.tb.alloc(a.rs.header, text_guess(ctx->last_text_bytes))) {
     (void)hipDeviceSynchronize();
     return fail(ctx, CALITAS_EINVAL, "out of memory");
   }
@@ -606,6 +637,7 @@ int search_hits_attempt(calitas_ctx* ctx, const HitsCall& call, HitsOut& out, co
   out = HitsOut();
   int rc = plan_search(ctx, 1, call.guide, call.params, pl);
   if (rc) return rc;
+  pl.counts = call.counts;
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   rc = ensure_bin_base(ctx, pl, ctx->stream);                // (built once per reference and window size)
   if (rc) return rc;
@@ -642,10 +674,27 @@ int search_hits_attempt(calitas_ctx* ctx, const HitsCall& call, HitsOut& out, co
     if (rc == kOwnedDeclined) { if (owned_declined) *owned_declined = true; return CALITAS_OK; }
     if (rc) return rc;
     g_marks.mark("lane-done");
-    if (!a.tb.alloc(a.rs.header, (size_t)a.parts[0].bytes) || a.parts[0].bytes > a.tb.capacity) return fail(ctx, CALITAS_EINVAL, call.user_dst ? kNoRoom : "out of memory");
-    rc = place(a, 0, 0);
-    if (rc) { a.tb.release(); return rc; }
-    g_marks.mark("text-copied");
+    if (!call.counts) {                                      // (counts mode: no text to place)
+      if (!a.tb.alloc(a.rs.header, (size_t)a.parts[0].bytes) || a.parts[0].bytes > a.tb.capacity) return fail(ctx, CALITAS_EINVAL, call.user_dst ? kNoRoom : "out of memory");
+      rc = place(a, 0, 0);
+      if (rc) { a.tb.release(); return rc; }
+      g_marks.mark("text-copied");
+    }
+  }
+  if (call.counts) {                                         // the ranges' tables summed: no text, no copy
+    calitas_timing_t tm{};
+    out.counts.assign(pl.cshape.cells(), 0);
+    out.shape = pl.cshape;
+    for (auto& lt : a.parts) {
+      if (lt.counts.size() != out.counts.size()) return fail(ctx, CALITAS_EHIP, "a lane returned no counts table (internal error)");
+      add_counts(out.counts, lt.counts);
+      out.rows += lt.rows;
+      add_lane_timing(tm, lt.tm);
+    }
+    tm.hit_rows = out.rows; tm.hits_bytes = 0; tm.lanes = (uint32_t)a.parts.size();
+    ctx->timing = tm;
+    if (trace) trace_attempt(a, tm, chunked, out.rows, 0);
+    return CALITAS_OK;
   }
   size_t total = a.hlen;
   calitas_timing_t tm{};
@@ -679,7 +728,7 @@ static int search_hits_fitted(calitas_ctx* ctx, const HitsCall& call, HitsOut& o
     (void)known_not_to_fit(ctx, call.guide, call.params, true);
   }
   out = HitsOut();
-  const int rc = search_hits_sequential(ctx, call, out);
+  const int rc = call.counts ? search_counts_sequential(ctx, call, out) : search_hits_sequential(ctx, call, out);
   if (rc == CALITAS_ENOMEM) release_scratch(ctx);   // leave the context usable for smaller searches
   return rc;
 }
@@ -697,6 +746,24 @@ int calitas_search_hits_impl(calitas_ctx* ctx, const calitas_guide_t* guide, con
                      ? search_hits_attempt(ctx, call, out) : search_hits_fitted(ctx, call, out, "search_hits", &one_pass);
   out.store(tsv, tsv_bytes, n_rows);
   return rc;
+}
+
+// calitas_search_counts: the ways of calitas_search_hits (one pass in lanes, a window range, one pass per contig) with HitsCall::counts set.
+int calitas_search_counts_impl(calitas_ctx* ctx, const calitas_guide_t* guide, const calitas_params_t* params, CountsShape* shape,
+                               std::vector<uint64_t>* table, uint64_t* rows) {
+  g_marks.start();
+  struct Dump { ~Dump() { g_marks.mark("return"); g_marks.dump(); } } dump_at_exit;
+  static const std::string no_id;
+  HitsCall call{guide, no_id, params, "-", "-"};             // (no row carries them: nothing to format)
+  call.counts = true;
+  HitsOut out;
+  bool one_pass = false;
+  const int rc = params && (params->first_window != 0 || params->n_windows != 0)
+                     ? search_hits_attempt(ctx, call, out) : search_hits_fitted(ctx, call, out, "search_counts", &one_pass);
+  if (rc) return rc;
+  if (out.counts.size() != out.shape.cells() || out.counts.empty()) return fail(ctx, CALITAS_EHIP, "the search returned no counts table (internal error)");
+  *shape = out.shape; *table = std::move(out.counts); *rows = out.rows;
+  return CALITAS_OK;
 }
 
 // calitas_search_hits with hits of the caller's own brought into every contig's row stage (the variant branch, variants.cpp: VariantSearch::start_threads): one pass per

@@ -68,6 +68,10 @@ struct SearchPlan {
   bool narrow_tail = false;           // a range of a chunked call that is not the last: its tail shares the chip with the next scan
   bool three_ranges = false;          // a range of a call cut into three or more
   bool last_range = false;            // ... and the last of them: no scan runs beside its tail
+  // calitas_search_counts: the lanes count the kept hits into a table of these extents instead of building rows.  The extents are
+  // always planned (counts_shape: from the guide and the params alone); `counts` is set by the entry point
+  bool counts = false;
+  CountsShape cshape;
   bool general_tail = false;          // the caller brings hits of its own into the row stage (HitsExt): the general kernels take them, the bins do not
 };
 
@@ -93,6 +97,7 @@ struct LaneText {
   const HitsWork* rows_by = nullptr;   // the general row stage that wrote d_text (its late flags are looked at once the text has been copied)
   const HitsExt* ext = nullptr;        // the caller's hits whose rows the caller writes into the text itself (HitsExtRows::fill_on_host) ...
   const uint64_t* ext_place = nullptr; // ... and where (HitsResult::ext_place)
+  std::vector<uint64_t> counts;        // counts mode (SearchPlan::counts): the lane's table, SearchPlan::cshape.cells() words; no text, bytes = 0
   calitas_timing_t tm{};
 };
 
@@ -115,11 +120,14 @@ struct HitsCall {
   calitas_text_sink_t sink = nullptr;       // per-contig passes: the pieces of the text are handed over as they arrive ...
   void* sink_user = nullptr;
   const HitsExtSource* ext_source = nullptr;   // ... and hits of the caller's own are brought into every contig's row stage
+  bool counts = false;                      // calitas_search_counts: no text at all, HitsOut::counts receives the table of the rows
 };
 // ... and what it gets back (tsv stays NULL where the text went to a sink).
 struct HitsOut {
   char* tsv = nullptr;
   uint64_t bytes = 0, rows = 0;
+  std::vector<uint64_t> counts;             // HitsCall::counts: the table, shape.cells() words
+  CountsShape shape;
   void store(char** t, uint64_t* b, uint64_t* r) const { if (t) *t = tsv; if (b) *b = bytes; if (r) *r = rows; }
 };
 
@@ -169,6 +177,12 @@ void release_scratch(calitas_ctx* ctx);
 // on the per-bin kernels; *owned_declined: they could not decide it (the caller then takes the slow path), nothing is returned.
 int search_hits_attempt(calitas_ctx* ctx, const HitsCall& call, HitsOut& out, const uint64_t* owned = nullptr, bool* owned_declined = nullptr);
 int search_hits_sequential(calitas_ctx* ctx, const HitsCall& call, HitsOut& out);
+int search_counts_sequential(calitas_ctx* ctx, const HitsCall& call, HitsOut& out);
+// b += a, element by element (tables of one shape: of ranges, contigs, lanes)
+inline void add_counts(std::vector<uint64_t>& b, const std::vector<uint64_t>& a) {
+  if (b.size() < a.size()) b.resize(a.size(), 0);
+  for (size_t i = 0; i < a.size(); i++) b[i] += a[i];
+}
 
 }  // namespace calitas
 

@@ -315,10 +315,14 @@ static int lane_rows_binned(calitas_ctx* lane, const SearchPlan& pl, bool prelau
   // (no events on these dispatches: each would hold back the kernel behind it by ~5 us; the kernels stamp the device's wall clock instead)
   HIP_TRY(lane, launch_align_trace(pl, aa, lane->stream, nullptr));
   HIP_TRY(lane, binned_run(lane->binned, &lane->hits, geo, hr, lane->d_raw, lane->d_guides, own->d_win_base, own->d_win, bp, lane->d_counters, lane->stream,
-                           &lane->mbox, nullptr, nullptr, lane->ev[5], dest == nullptr));
+                           &lane->mbox, nullptr, nullptr, lane->ev[5], dest == nullptr && !pl.counts));
   char* host_dst = nullptr;
   uint64_t host_dst_cap = 0;
-  if (dest) {
+  if (pl.counts) {
+    // the table instead of rows: bin_counts_kernel where the rows kernel would go, with the same post behind it
+    HIP_TRY(lane, binned_counts(lane->binned, &lane->hits, geo, hr, lane->d_raw, lane->d_guides, own->d_win_base, own->d_win, bp, lane->d_counters, lane->stream,
+                                &lane->mbox, lane->ev[5], pl.cshape));
+  } else if (dest) {
     // the rows kernel goes out once the text's final place is known (the byte counts of the ranges before this one: their row kernels
     // have started by then) and writes there itself -- no copy behind it
     if (!dest->get(&host_dst, &host_dst_cap)) { host_dst = nullptr; host_dst_cap = 0; }
@@ -347,6 +351,13 @@ static int lane_rows_binned(calitas_ctx* lane, const SearchPlan& pl, bool prelau
     return CALITAS_OK;
   }
   uint64_t bytes = (uint64_t)lane->mbox.host[BIN_BOX_BYTES] | ((uint64_t)lane->mbox.host[BIN_BOX_BYTES + 1] << 32);
+  if (pl.counts) {                                           // the table arrived ahead of the post
+    const uint64_t* table = binned_counts_table(lane->hits);
+    lt.counts.assign(table, table + pl.cshape.cells());
+    uint64_t sum = 0;
+    for (uint64_t v : lt.counts) sum += v;
+    if (sum != lane->mbox.host[BIN_BOX_ROWS]) return fail(lane, CALITAS_EHIP, "binned counts kernel: the table does not add up to the bins' kept hits (internal error)");
+  }
   if (flags & BIN_FLAG_TEXT) {                               // the text buffer was a guess: grow it, the rows kernel once more
     HIP_TRY(lane, binned_rerun_rows(lane->binned, &lane->hits, geo, hr, lane->d_raw, lane->d_guides, own->d_win_base, own->d_win, bp, lane->d_counters, bytes,
                                     lane->stream, &lane->mbox, lane->ev[5]));
@@ -371,10 +382,11 @@ static int lane_rows_binned(calitas_ctx* lane, const SearchPlan& pl, bool prelau
   lane->timing = tm;
   lt.tm = tm;
   // (a short text is already on its way into the lane's page-locked buffer: text_to_host only waits for the kernel)
-  if (host_dst) { lt.in_place = bytes <= host_dst_cap; lt.d_text = lt.in_place ? host_dst : binned_text(lane->hits); }
+  if (pl.counts) lt.d_text = nullptr;
+  else if (host_dst) { lt.in_place = bytes <= host_dst_cap; lt.d_text = lt.in_place ? host_dst : binned_text(lane->hits); }
   else lt.d_text = bytes <= binned_host_cap(lane->binned) ? binned_host_text(lane->binned) : binned_text(lane->hits);
   lt.bytes = bytes; lt.rows = lane->mbox.host[BIN_BOX_ROWS];
-  lane->binned_late_check = true;
+  lane->binned_late_check = !pl.counts;
   return CALITAS_OK;
 }
 
@@ -456,10 +468,20 @@ int lane_rows(calitas_ctx* lane, const SearchPlan& pl, bool prelaunched, const R
       lane->rows_ev0 = 4;
       HIP_TRY(lane, hits_run(&lane->hits, hr, dev.d_final, dev.n_sel, lane->d_guides, own->d_win_base, own->d_win, rs, p.max_overlap, score_hi,
                              widest_hit(pl, max_pam), dev.crowded ? 0u : (uint32_t)((p.window_size + pl.step - 1) / pl.step),
-                             lane->stream, &res, ext, own_general ? &ho : nullptr));
+                             lane->stream, &res, ext, own_general ? &ho : nullptr, pl.counts ? &pl.cshape : nullptr));
       HIP_TRY(lane, hipEventRecord(lane->ev[5], lane->stream));
       g_marks.mark("rows-queued");
       kernel_times(lane, lt.tm);          // while out_kernel runs
+      if (pl.counts && (res.flags & HITS_FLAG_EXTENT)) return fail(lane, CALITAS_EHIP, "a hit lies outside the extents of the counts table (internal error)");
+      if (res.flags == 0 && pl.counts) {
+        lt.counts.assign(res.counts, res.counts + pl.cshape.cells());
+        uint64_t sum = 0;
+        for (uint64_t v : lt.counts) sum += v;
+        if (sum != res.n_rows) return fail(lane, CALITAS_EHIP, "counts kernel: the table does not add up to the kept hits (internal error)");
+        lt.rows = res.n_rows;
+        if (own_general) lt.tm.owned_general_lanes = 1;
+        return CALITAS_OK;
+      }
       if (res.flags == 0) {
         lt.d_text = res.d_text; lt.bytes = res.text_bytes; lt.rows = res.n_rows; lt.rows_by = lane->hits;
         if (res.ext_place) { lt.ext = ext; lt.ext_place = res.ext_place; }
@@ -480,6 +502,15 @@ int lane_rows(calitas_ctx* lane, const SearchPlan& pl, bool prelaunched, const R
     n_alns = dev.n_sel;
   }
   uint64_t rows = 0;
+  if (pl.counts) {                                           // the host stage of calitas_hits_counts
+    lt.counts.assign(pl.cshape.cells(), 0);
+    const std::string e = hits_counts(ref, gh, p, alns, n_alns, pl.cshape.n_mm, pl.cshape.n_gaps, pl.cshape.n_pam, lt.counts.data(), &rows, own->pool);
+    calitas_free(alns);
+    if (!e.empty()) return fail(lane, CALITAS_EHIP, e);
+    lt.on_host = true;
+    lt.rows = rows;
+    return CALITAS_OK;
+  }
   char* text = hits_tsv(ref, gh, guide_id, p, alns, n_alns, version, stamp, &rows, own->pool, out_alloc, nullptr, 0);
   calitas_free(alns);
   if (!text) return fail(lane, CALITAS_EINVAL, "out of memory");

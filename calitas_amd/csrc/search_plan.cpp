@@ -49,6 +49,24 @@ std::string build_guide_dev(const GuideHost& gh, const calitas_params_t& p, cons
   return "";
 }
 
+static CountsShape shape_of(const GuideDev& gd, const calitas_params_t& p) {
+  CountsShape s;
+  s.n_mm = (uint32_t)gd.scan_max_edits + 1u;
+  s.n_gaps = (uint32_t)gd.scan_max_edits + (uint32_t)p.max_gaps_between_guide_and_pam + 1u;
+  s.n_pam = (gd.n_pams > 0 ? (uint32_t)p.max_pam_mismatches : 0u) + 1u;
+  return s;
+}
+
+std::string counts_shape(const GuideHost& gh, const calitas_params_t& p, CountsShape& shape) {
+  if (p.max_guide_diffs < 0 || p.max_pam_mismatches < 0 || p.max_gaps_between_guide_and_pam < 0 || p.max_gaps_between_guide_and_pam > 16)
+    return "limits out of range (max-gaps-between-guide-and-pam must be 0..16)";
+  const Scores sc = derive_scores(p.guide_mismatch_net_cost, p.pam_mismatch_net_cost, p.genome_gap_net_cost, p.guide_gap_net_cost);
+  GuideDev gd;
+  const std::string e = build_guide_dev(gh, p, sc, p.max_guide_diffs, p.max_pam_mismatches, gd);
+  if (e.empty()) shape = shape_of(gd, p);
+  return e;
+}
+
 int ensure_buffers(calitas_ctx* ctx, uint32_t rec_cap, uint32_t raw_cap, uint64_t slab_per_rec, uint32_t item_cap) {
   rec_cap = std::max(rec_cap, ctx->rec_cap);
   if (const char* e = TUNE_GET("CALITAS_DEVICE_BUDGET_MB")) {   // refuse instead of trying: what a caller sharing the card can set
@@ -151,6 +169,7 @@ int plan_search(calitas_ctx* ctx, int32_t n_guides, const calitas_guide_t* guide
     if ((pl.gd[i].L + pl.gd[i].scan_max_edits + 15) / 16 > ref.chunk / 16) return fail(ctx, CALITAS_EINVAL, "scan warm-up exceeds the lane chunk");
     pl.warm_words = std::max(pl.warm_words, (pl.gd[i].L + pl.gd[i].scan_max_edits - 1 + 31) / 32);
   }
+  pl.cshape = shape_of(pl.gd[0], p);
   // Strip slabs (align_kernel -> trace_kernel): fixed size and fixed address per (record, window slot).
   pl.slots_per_rec = (uint32_t)((p.window_size + 14) / pl.step + 1);   // windows a 16-base word can fall into
   if (pl.slots_per_rec > 8) return fail(ctx, CALITAS_EINVAL, "window step is too small relative to the window size (more than 8 windows per position)");

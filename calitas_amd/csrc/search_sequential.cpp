@@ -327,4 +327,38 @@ int search_hits_sequential(calitas_ctx* ctx, const HitsCall& call, HitsOut& out)
   return CALITAS_OK;
 }
 
+// calitas_search_counts as one pass per contig: every contig's table is a few KB on the host when its pass returns, so the passes simply
+// follow each other on this context's stream -- no second scratch set, no helper thread, nothing to copy -- and the tables are summed
+// (removeOverlaps never crosses a contig).
+int search_counts_sequential(calitas_ctx* ctx, const HitsCall& call, HitsOut& out) {
+  SearchPlan pl;
+  int rc = plan_search(ctx, 1, call.guide, call.params, pl);
+  if (rc) return rc;
+  pl.counts = true;
+  std::string version, stamp;
+  calitas_default_version_and_stamp(call.aligner_version, call.time_stamp, version, stamp);
+  const RowStrings rs = make_row_strings(ctx->ref, pl.gh[0], call.guide_id, pl.p, version, stamp);
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  rc = ensure_bin_base(ctx, pl, ctx->stream);
+  if (rc) return rc;
+  Passes ps;
+  plan_passes(ctx, pl, ps);
+  out = HitsOut();
+  out.shape = pl.cshape;
+  out.counts.assign(pl.cshape.cells(), 0);
+  calitas_timing_t tm{};
+  for (size_t i = 0; i < ps.plans.size(); i++) {
+    LaneText lt;
+    rc = lane_rows(ctx, ps.plans[i], false, rs, call.guide_id, version, stamp, lt);
+    if (rc) return rc;
+    if (lt.counts.size() != out.counts.size()) return fail(ctx, CALITAS_EHIP, "a contig pass returned no counts table (internal error)");
+    add_counts(out.counts, lt.counts);
+    out.rows += lt.rows;
+    add_lane_timing(tm, lt.tm);
+  }
+  tm.hit_rows = out.rows; tm.hits_bytes = 0; tm.lanes = 1; tm.contig_passes = (uint32_t)ps.plans.size();
+  ctx->timing = tm;
+  return CALITAS_OK;
+}
+
 }  // namespace calitas

@@ -244,6 +244,31 @@ int calitas_search_hits_batch(calitas_ctx* ctx, int32_t n_guides, const calitas_
                               const calitas_params_t* params, const char* aligner_version, const char* time_stamp, char** tsv,
                               uint64_t* tsv_bytes, uint64_t* n_rows);
 
+/* The off-target table of one guide: how many rows the hits.txt of calitas_search_hits (same guide, same params: after the per-window
+ * filter and removeOverlaps; with first_window / n_windows, the rows the range owns) has per strand, guide_mm, guide_gaps and pam_mm
+ * -- the hits.txt columns of those names (GuideAlignment.scala:103, 104, 106; the gap between guide and PAM counts as guide gaps).
+ * Cell [s][m][g][p] of counts (strand '+' = 0, '-' = 1) is at ((s * n_mm + m) * n_gaps + g) * n_pam + p.  The extents depend on the
+ * guide and the params only, never on the reference: n_mm = E + 1 with E the most edits the protospacer can have at this
+ * max_guide_diffs and these net costs (max_guide_diffs itself for the default costs, more when an edit is cheaper than the dearest),
+ * n_gaps = E + max_gaps_between_guide_and_pam + 1, n_pam = max_pam_mismatches + 1 (1 for a PAM-less guide) -- so the tables of window
+ * ranges, contigs and ranks of one job add up element by element.  A hit outside the extents fails the call (it is never dropped or
+ * clamped).  The struct and its counts are one block: one calitas_free. */
+typedef struct {
+  uint32_t n_mm, n_gaps, n_pam;
+  uint64_t rows;               /* == n_rows of calitas_search_hits == the sum of counts */
+  uint64_t* counts;            /* [2][n_mm][n_gaps][n_pam] */
+} calitas_counts_t;
+
+/* calitas_search_hits without the text: the table alone.  The alignments never leave the device and no row is built -- behind
+ * removeOverlaps one kernel counts the kept hits into a histogram per workgroup and the few KB of the table reach the host with the
+ * counters the call waits for anyway.  Accepts whatever calitas_search_hits accepts (the whole reference, chrom_index, a window range);
+ * where a device stage declines, the host stages of calitas_hits_counts finish the call. */
+int calitas_search_counts(calitas_ctx* ctx, const calitas_guide_t* guide, const calitas_params_t* params, calitas_counts_t** out);
+/* ... for a batch of guides, pipelined through the lanes as in calitas_search_hits_batch (same same-length rule, same meaning of a
+ * window range): out[i] receives the table of guides[i], each freed with calitas_free. */
+int calitas_search_counts_batch(calitas_ctx* ctx, int32_t n_guides, const calitas_guide_t* guides, const calitas_params_t* params,
+                                calitas_counts_t** out);
+
 /* SequentialGuideAligner.align on explicit (guide, target) pairs -- the per-task call of PairwiseAlignSequences
  * (PairwiseAlignSequences.scala:64 -> alignBest, SequentialGuideAligner.scala:333-345) and AlignToReference
  * (AlignToReference.scala:114-135 -> alignToRef / alignToRefBest, SequentialGuideAligner.scala:359-418).  Task t aligns
@@ -273,6 +298,11 @@ int calitas_window_filter(const calitas_aln_t* alns, int32_t n, int32_t max_tota
 int calitas_hits_tsv(const calitas_ctx* ctx, const calitas_guide_t* guide, const char* guide_id, const calitas_params_t* params,
                      const calitas_aln_t* alns, uint64_t n_alns, const char* aligner_version, const char* time_stamp,
                      char** tsv, uint64_t* n_rows);
+
+/* The twin of calitas_hits_tsv for the table: removeOverlaps on the alignments of one guide, then the kept hits counted (the host stage
+ * calitas_search_counts falls back to; works on a host-only context). */
+int calitas_hits_counts(const calitas_ctx* ctx, const calitas_guide_t* guide, const calitas_params_t* params, const calitas_aln_t* alns,
+                        uint64_t n_alns, calitas_counts_t** out);
 
 /* A hit row built by the caller -- the variant branch of SearchReference.execute (SearchReference.scala:570-630) builds its
  * ReferenceHits from variant windows on the host.  calitas_hits_tsv_ext lets such hits take part in removeOverlaps (grouped by
