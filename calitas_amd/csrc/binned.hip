@@ -18,6 +18,9 @@
 // (<= 64, one per lane), (4) their order by counting, restart points, the cluster walks, (5) the row lengths of the kept hits of the
 // bin (the row builder's own arithmetic without the text: build_middle<false>) and the bin's (rows, bytes) with a two-level sum.
 // bin_rows_kernel then places every bin from those sums and builds its rows at their final offsets -- no staging copy of the text.
+// The bounds above are stated once, in bin_context (both bin kernels open with it); the two also share derive_in_contig, order_key
+// (select_dev.hpp), hit_record, sort_cmp, own_key, middle_length and row_length (hits_dev.hpp).  bin_rows_kernel builds and writes a row
+// with the general rows kernel's load_row_in, row_guide, checked_middle and write_row; it and bin_counts_kernel post through bin_post.
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 
@@ -88,26 +91,35 @@ __device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v)
   return v;
 }
 
-// What the filter looks at of a raw alignment of a contig whose windows start at wbase in the window table (select_dev.hpp derive()
-// without the dependent load of win_base[contig]: the contig is the bin's).
-__device__ __forceinline__ Derived derive_in_contig(const RawAln* rp, const GuideDev* guides, uint32_t wbase, const int2* win) {
-  const uint32_t window_k = rp->window_k, guide = rp->guide;
-  const int pam = rp->pam, offset = rp->offset, n_ops = rp->n_ops, dir = rp->dir;
-  const OpCounts oc = count_ops(load_ops_words(rp->ops), n_ops);
-  int diffs = oc.non_eq, gaps = oc.gaps, pam_len = 0;
-  if (pam >= 0) { pam_len = guides[guide].pam_len[pam]; diffs += offset + __popc((unsigned)rp->pam_x); gaps += offset; }
-  const uint32_t wi = wbase + window_k;
-  const int2 w = win[wi];
-  const int start_s = (int)rp->t_start - 1, end_s = (int)rp->t_end_guide + offset + pam_len;
-  Derived d;
-  if (dir == 0) { d.start = w.x + start_s; d.end = w.x + end_s; }
-  else          { d.start = w.y - end_s;   d.end = w.y - start_s; }
-  d.score = rp->score; d.gaps = (uint16_t)gaps; d.edits = (uint16_t)diffs;
-  const uint32_t pam5 = guides[guide].pam5;
-  const uint32_t list = pam5 ? (dir == 1 ? 0u : 1u) : (dir == 0 ? 0u : 1u);   // 0 = forward-strand list (SGA:316)
-  d.ekey = (list << 19) | ((uint32_t)rp->t_end_guide << 6) | ((uint32_t)rp->pad << 4) | (uint32_t)(pam + 1);
-  d.widx = wi;
-  return d;
+// A bin's context (the header of this file says why it is enough): bin `rel` of the call's range owns the hits that start in [lo, hi) on
+// contig c and takes the alignments of the previous, the own and the next bin whose window starts in [ctx_lo, ctx_hi) = [lo - 2W, hi + 128);
+// all hits are known from known_from = lo - W on (restart points are certain HIT_MAX_LEN further right; at the start of a contig nothing
+// is missing).  false: no window that could hold a hit of this bin has alignments -- nothing to do.  The bounds are functions of
+// (bb, shift, W), not fields: as values they are live through all of bin_hits_wave, ten scalar registers that kernel does not have.
+struct BinCtx {
+  uint32_t c, wbase;                  // the bin's contig, and the contig's first entry of the window table
+  uint32_t n_prev, n_own, n_next;     // alignments listed in the previous / own / next bin (0 for a neighbour on another contig or outside the range)
+  uint32_t bb, shift;                 // the bin's index inside its contig; bases per bin as a shift
+  int W;
+  __device__ __forceinline__ int64_t lo() const { return (int64_t)bb << shift; }
+  __device__ __forceinline__ int64_t hi() const { return lo() + ((int64_t)1 << shift); }
+  __device__ __forceinline__ int64_t ctx_lo() const { return lo() - 2 * (int64_t)W; }
+  __device__ __forceinline__ int64_t ctx_hi() const { return hi() + HIT_MAX_LEN; }
+  __device__ __forceinline__ int64_t known_from() const { return ctx_lo() <= 0 ? -((int64_t)1 << 40) : lo() - (int64_t)W; }
+};
+__device__ __forceinline__ bool bin_context(const BinArgs& a, const uint32_t rel, BinCtx& x) {
+  const uint32_t b = a.bin_first + rel;
+  x.n_own = a.bin_count[rel];
+  const uint32_t n_prev_raw = rel > 0 ? a.bin_count[rel - 1] : 0u;
+  if (n_prev_raw == 0 && x.n_own == 0) return false;
+  x.c = a.bin_contig[b];
+  x.wbase = (uint32_t)a.win_base[x.c];
+  x.bb = b - a.bin_base[x.c];
+  const bool has_prev = x.bb > 0 && rel > 0, has_next = b + 1 < a.bin_base[x.c + 1] && rel + 1 < a.n_bins;
+  x.n_prev = has_prev ? n_prev_raw : 0u; x.n_next = has_next ? a.bin_count[rel + 1] : 0u;
+  if (x.n_prev == 0 && x.n_own == 0) return false;
+  x.shift = a.bin_shift; x.W = a.W;
+  return true;
 }
 
 // One bin by a whole wave: the bins whose context holds more than SMALL_MAX alignments (bin_hits_kernel's waves stride over the
@@ -123,7 +135,6 @@ __device__ __forceinline__ void bin_hits_wave(const BinArgs& a, const MidArgs& m
   constexpr uint32_t wv = 0;                                            // one wave per workgroup
   wave_lds_sync();                                                      // the previous bin of this wave is done with the arrays
   if (rel >= a.n_bins) return;
-  const uint32_t b = a.bin_first + rel;
   auto finish = [&](uint32_t n_rows, uint32_t bytes, uint32_t n_acc) {
     if (lane == 0) {
       a.bin_rows[rel] = n_rows; a.bin_bytes[rel] = bytes;
@@ -136,20 +147,9 @@ __device__ __forceinline__ void bin_hits_wave(const BinArgs& a, const MidArgs& m
     }
   };
   auto decline = [&](uint32_t why) { if (lane == 0) atomicOr(a.flags, why); finish(0, 0, 0); };
-  const uint32_t n_own = a.bin_count[rel];
-  const uint32_t n_prev_raw = rel > 0 ? a.bin_count[rel - 1] : 0u;
-  if (n_prev_raw == 0 && n_own == 0) { finish(0, 0, 0); return; }       // no window that could hold a hit of this bin has alignments
-  const uint32_t c = a.bin_contig[b];
-  const uint32_t wbase = (uint32_t)a.win_base[c];                       // the contig's first entry of the window table
-  const uint32_t bb = b - a.bin_base[c];                                // bin inside its contig
-  const bool has_prev = bb > 0 && rel > 0, has_next = b + 1 < a.bin_base[c + 1] && rel + 1 < a.n_bins;
-  const uint32_t n_prev = has_prev ? n_prev_raw : 0u, n_next = has_next ? a.bin_count[rel + 1] : 0u;
-  if (n_prev == 0 && n_own == 0) { finish(0, 0, 0); return; }
-  if (n_prev > BIN_CAP || n_own > BIN_CAP || n_next > BIN_CAP) { decline(BIN_FLAG_CROWDED); return; }
-  const int64_t lo = (int64_t)bb << a.bin_shift, hi = lo + ((int64_t)1 << a.bin_shift);
-  const int64_t ctx_lo = lo - 2 * (int64_t)a.W, ctx_hi = hi + HIT_MAX_LEN;
-  // hits are all known from here on; restart points are certain HIT_MAX_LEN further right.  At the start of a contig nothing is missing.
-  const int64_t known_from = ctx_lo <= 0 ? -((int64_t)1 << 40) : lo - (int64_t)a.W;
+  BinCtx x;
+  if (!bin_context(a, rel, x)) { finish(0, 0, 0); return; }
+  if (x.n_prev > BIN_CAP || x.n_own > BIN_CAP || x.n_next > BIN_CAP) { decline(BIN_FLAG_CROWDED); return; }
 
   // ---- 1. the context's raw alignments: lane l holds alignment l of the previous, the own and the next bin (those whose window
   //         starts in [lo - 2W, hi + 128)) in registers ----
@@ -158,15 +158,15 @@ __device__ __forceinline__ void bin_hits_wave(const BinArgs& a, const MidArgs& m
   uint32_t ed[3], widx[3], src[3], wk[3];
 #pragma unroll
   for (int q = 0; q < 3; q++) {
-    const uint32_t nq = q == 0 ? n_prev : q == 1 ? n_own : n_next;
+    const uint32_t nq = q == 0 ? x.n_prev : q == 1 ? x.n_own : x.n_next;
     key[q] = 0; st[q] = 0; en[q] = 0; ed[q] = 0; widx[q] = 0xFFFFFFFFu; src[q] = 0; wk[q] = 0;
     if ((uint32_t)lane < nq) {
       const uint32_t idx = a.bin_idx[(size_t)((int64_t)rel + q - 1) * BIN_CAP + (uint32_t)lane];
       const RawAln* rp = a.raw + idx;
       const uint32_t window_k = rp->window_k;
       const int64_t ws = (int64_t)window_k * (int64_t)a.step;            // where the window starts on the contig
-      if (ws >= ctx_lo && ws < ctx_hi) {
-        const Derived d = derive_in_contig(rp, a.guides, wbase, a.win);      // widx = the window's index in the table
+      if (ws >= x.ctx_lo() && ws < x.ctx_hi()) {
+        const Derived d = derive_in_contig(rp, a.guides, x.wbase, a.win);    // widx = the window's index in the table
         key[q] = order_key(d); st[q] = d.start; en[q] = d.end; ed[q] = d.edits; widx[q] = d.widx; src[q] = idx; wk[q] = window_k;
       }
     }
@@ -210,7 +210,7 @@ __device__ __forceinline__ void bin_hits_wave(const BinArgs& a, const MidArgs& m
           else over = true;
           nk++; nA++;
           const int64_t ws = (int64_t)b_wk * (int64_t)a.step;            // (statistics) counted by the bin the window starts in
-          if (ws >= lo && ws < hi) nA_own++;
+          if (ws >= x.lo() && ws < x.hi()) nA_own++;
           wave_lds_sync();
         }
       }
@@ -238,9 +238,8 @@ __device__ __forceinline__ void bin_hits_wave(const BinArgs& a, const MidArgs& m
     for (uint32_t j = 0; j < nA; j++) {
       const int gs = t_start[wv][j], sc = t_score[wv][j];
       const uint32_t mi = t_minus[wv][j];
-      const bool less = gs < h.gstart || (gs == h.gstart && (mi < h.minus || (mi == h.minus && sc > h.score)));
-      const bool same = gs == h.gstart && mi == h.minus && sc == h.score;
-      rank += (less || (same && j < (uint32_t)lane)) ? 1u : 0u;
+      const SortCmp cmp = sort_cmp(gs, mi, sc, h.gstart, h.minus, h.score);
+      rank += (cmp.less || (cmp.same && j < (uint32_t)lane)) ? 1u : 0u;
     }
     s_start[wv][rank] = h.gstart; s_end[wv][rank] = h.rh_end; s_score[wv][rank] = h.score; s_cs[wv][rank] = (uint8_t)h.minus;
     s_idx[wv][rank] = (uint8_t)lane;
@@ -260,7 +259,7 @@ __device__ __forceinline__ void bin_hits_wave(const BinArgs& a, const MidArgs& m
     s_head[wv][r] = head ? 1 : 0; s_keep[wv][r] = 0; s_done[wv][r] = 0;
   }
   wave_lds_sync();
-  if (r < nA && head && (int64_t)s_start[wv][r] >= known_from + HIT_MAX_LEN) {   // hits.hip cluster_body: the reference's loop, SR:661-671
+  if (r < nA && head && (int64_t)s_start[wv][r] >= x.known_from() + HIT_MAX_LEN) {   // hits.hip cluster_body: the reference's loop, SR:661-671
     const uint32_t cs = s_cs[wv][r];
     auto next = [&](uint32_t j) { for (j++; j < nA; j++) if (s_cs[wv][j] == cs) return j; return nA; };
     uint32_t j = r;
@@ -284,8 +283,8 @@ __device__ __forceinline__ void bin_hits_wave(const BinArgs& a, const MidArgs& m
     }
   }
   wave_lds_sync();
-  const unsigned long long okey = r < nA ? (((unsigned long long)c << 32) | (unsigned long long)(uint32_t)s_start[wv][r]) : 0ull;
-  const bool mine = r < nA && (int64_t)s_start[wv][r] >= lo && (int64_t)s_start[wv][r] < hi && okey >= a.own_lo && okey < a.own_hi;
+  const unsigned long long okey = r < nA ? own_key(x.c, s_start[wv][r]) : 0ull;
+  const bool mine = r < nA && (int64_t)s_start[wv][r] >= x.lo() && (int64_t)s_start[wv][r] < x.hi() && okey >= a.own_lo && okey < a.own_hi;
   if (__ballot(mine && !s_done[wv][r]) != 0) { decline(BIN_FLAG_HALO); return; }
   const unsigned long long kept = __ballot(mine && s_keep[wv][r] != 0);
   const uint32_t n_rows = (uint32_t)__popcll(kept);
@@ -297,13 +296,9 @@ __device__ __forceinline__ void bin_hits_wave(const BinArgs& a, const MidArgs& m
   int len = 0;
   uint32_t row_bytes = 0;
   if (kept_here) {
-    const RawAln* rp = a.raw + hsrc;
-    const GuideDev* gp = a.guides + rp->guide;
-    const int pam = rp->pam;
-    len = middle_length(rp, h, gp->L, pam >= 0 ? gp->pam_len[pam] : 0, (int)m.rc.pu_len[pam + 1], (int)m.n_max, (int)m.mid_bound);
+    len = middle_length(m, a.raw + hsrc, h);
     if (len >= 0) {
-      const uint32_t name_len = m.name_off[h.contig + 1] - m.name_off[h.contig];
-      row_bytes = m.rc.head_len + name_len + 1u + (uint32_t)len + m.rc.tail_len;
+      row_bytes = row_length(m.rc, m.name_off, h.contig, (uint32_t)len);
       a.rows[(size_t)rel * BIN_ROWS + (uint32_t)__popcll(kept & bits_below((int)my_rank))] = BinRow{hsrc, (uint32_t)len};
     }
   }
@@ -348,202 +343,185 @@ __global__ __launch_bounds__(64) void bin_hits_small_kernel(BinArgs a, MidArgs m
 #pragma unroll
   for (int k = 0; k < SMALL_MAX; k++) out_row[k] = BinRow{0u, 0u};
   if (in_range) {
-    const uint32_t b = a.bin_first + rel;
-    const uint32_t n_own = a.bin_count[rel];
-    const uint32_t n_prev_raw = rel > 0 ? a.bin_count[rel - 1] : 0u;
-    if (n_prev_raw != 0 || n_own != 0) {
-      const uint32_t c = a.bin_contig[b];
-      const uint32_t wbase = (uint32_t)a.win_base[c];
-      const uint32_t bb = b - a.bin_base[c];
-      const bool has_prev = bb > 0 && rel > 0, has_next = b + 1 < a.bin_base[c + 1] && rel + 1 < a.n_bins;
-      const uint32_t n_prev = has_prev ? n_prev_raw : 0u, n_next = has_next ? a.bin_count[rel + 1] : 0u;
-      if (n_prev != 0 || n_own != 0) {
-        if (n_prev + n_own + n_next > (uint32_t)SMALL_MAX || sa.force_complex) is_complex = true;
-        else {
-          const int64_t lo = (int64_t)bb << a.bin_shift, hi = lo + ((int64_t)1 << a.bin_shift);
-          const int64_t ctx_lo = lo - 2 * (int64_t)a.W, ctx_hi = hi + HIT_MAX_LEN;
-          const int64_t known_from = ctx_lo <= 0 ? -((int64_t)1 << 40) : lo - (int64_t)a.W;
-          // ---- 1. context: candidate j of (previous | own | next) bin ----
-          unsigned long long key[SMALL_MAX];
-          int st[SMALL_MAX], en[SMALL_MAX];
-          uint32_t ed[SMALL_MAX], widx[SMALL_MAX], src[SMALL_MAX], wk[SMALL_MAX];
+    BinCtx x;
+    if (bin_context(a, rel, x)) {
+      const uint32_t n_prev = x.n_prev, n_own = x.n_own, n_next = x.n_next;
+      if (n_prev + n_own + n_next > (uint32_t)SMALL_MAX || sa.force_complex) is_complex = true;
+      else {
+        // ---- 1. context: candidate j of (previous | own | next) bin ----
+        unsigned long long key[SMALL_MAX];
+        int st[SMALL_MAX], en[SMALL_MAX];
+        uint32_t ed[SMALL_MAX], widx[SMALL_MAX], src[SMALL_MAX], wk[SMALL_MAX];
 #pragma unroll
-          for (int j = 0; j < SMALL_MAX; j++) {
-            key[j] = 0; st[j] = 0; en[j] = 0; ed[j] = 0; widx[j] = 0xFFFFFFFFu; src[j] = 0; wk[j] = 0;
-            const uint32_t uj = (uint32_t)j;
-            if (uj < n_prev + n_own + n_next) {
-              const int q = uj < n_prev ? 0 : uj < n_prev + n_own ? 1 : 2;
-              const uint32_t e = q == 0 ? uj : q == 1 ? uj - n_prev : uj - n_prev - n_own;
-              const uint32_t idx = a.bin_idx[(size_t)((int64_t)rel + q - 1) * BIN_CAP + e];
-              const RawAln* rp = a.raw + idx;
-              const uint32_t window_k = rp->window_k;
-              const int64_t ws = (int64_t)window_k * (int64_t)a.step;
-              if (ws >= ctx_lo && ws < ctx_hi) {
-                const Derived d = derive_in_contig(rp, a.guides, wbase, a.win);
-                key[j] = order_key(d); st[j] = d.start; en[j] = d.end; ed[j] = d.edits; widx[j] = d.widx; src[j] = idx; wk[j] = window_k;
-              }
+        for (int j = 0; j < SMALL_MAX; j++) {
+          key[j] = 0; st[j] = 0; en[j] = 0; ed[j] = 0; widx[j] = 0xFFFFFFFFu; src[j] = 0; wk[j] = 0;
+          const uint32_t uj = (uint32_t)j;
+          if (uj < n_prev + n_own + n_next) {
+            const int q = uj < n_prev ? 0 : uj < n_prev + n_own ? 1 : 2;
+            const uint32_t e = q == 0 ? uj : q == 1 ? uj - n_prev : uj - n_prev - n_own;
+            const uint32_t idx = a.bin_idx[(size_t)((int64_t)rel + q - 1) * BIN_CAP + e];
+            const RawAln* rp = a.raw + idx;
+            const uint32_t window_k = rp->window_k;
+            const int64_t ws = (int64_t)window_k * (int64_t)a.step;
+            if (ws >= x.ctx_lo() && ws < x.ctx_hi()) {
+              const Derived d = derive_in_contig(rp, a.guides, x.wbase, a.win);
+              key[j] = order_key(d); st[j] = d.start; en[j] = d.end; ed[j] = d.edits; widx[j] = d.widx; src[j] = idx; wk[j] = window_k;
             }
           }
-          // ---- 2. the greedy of SGA:315-320 window by window; acc_*[] = accepted alignments in arrival order ----
-          uint32_t acc_src[SMALL_MAX];
+        }
+        // ---- 2. the greedy of SGA:315-320 window by window; acc_*[] = accepted alignments in arrival order ----
+        uint32_t acc_src[SMALL_MAX];
 #pragma unroll
-          for (int k = 0; k < SMALL_MAX; k++) acc_src[k] = 0;
-          uint32_t nA = 0;
-          uint32_t cur = 0;
+        for (int k = 0; k < SMALL_MAX; k++) acc_src[k] = 0;
+        uint32_t nA = 0;
+        uint32_t cur = 0;
 #pragma unroll
-          for (int wround = 0; wround < SMALL_MAX; wround++) {             // at most SMALL_MAX distinct windows
-            uint32_t w = 0xFFFFFFFFu;
+        for (int wround = 0; wround < SMALL_MAX; wround++) {             // at most SMALL_MAX distinct windows
+          uint32_t w = 0xFFFFFFFFu;
 #pragma unroll
-            for (int j = 0; j < SMALL_MAX; j++) if (widx[j] != 0xFFFFFFFFu && widx[j] >= cur && widx[j] < w) w = widx[j];
-            if (__ballot(w != 0xFFFFFFFFu) == 0) break;                     // (wave-uniform: no lane of the wave has another window)
-            if (w != 0xFFFFFFFFu) {
-              cur = w + 1u;
-              int ks[SMALL_MAX], ke[SMALL_MAX];
+          for (int j = 0; j < SMALL_MAX; j++) if (widx[j] != 0xFFFFFFFFu && widx[j] >= cur && widx[j] < w) w = widx[j];
+          if (__ballot(w != 0xFFFFFFFFu) == 0) break;                     // (wave-uniform: no lane of the wave has another window)
+          if (w != 0xFFFFFFFFu) {
+            cur = w + 1u;
+            int ks[SMALL_MAX], ke[SMALL_MAX];
 #pragma unroll
-              for (int k = 0; k < SMALL_MAX; k++) { ks[k] = 0; ke[k] = 0; }
-              uint32_t nk = 0;
+            for (int k = 0; k < SMALL_MAX; k++) { ks[k] = 0; ke[k] = 0; }
+            uint32_t nk = 0;
 #pragma unroll
-              for (int list = 0; list < 2; list++) {
-                const uint32_t first_kept = nk;
+            for (int list = 0; list < 2; list++) {
+              const uint32_t first_kept = nk;
 #pragma unroll
-                for (int round = 0; round < SMALL_MAX; round++) {
-                  unsigned long long bk = 0;
+              for (int round = 0; round < SMALL_MAX; round++) {
+                unsigned long long bk = 0;
 #pragma unroll
-                  for (int j = 0; j < SMALL_MAX; j++) if (widx[j] == w && (uint32_t)(key[j] >> 63) == (uint32_t)list && key[j] > bk) bk = key[j];
-                  if (__ballot(bk != 0) == 0) break;                        // (no lane has another alignment in this list)
-                  if (bk != 0) {
-                    int b_start = 0, b_end = 0;
-                    uint32_t b_edits = 0, b_src = 0, b_wk = 0;
+                for (int j = 0; j < SMALL_MAX; j++) if (widx[j] == w && (uint32_t)(key[j] >> 63) == (uint32_t)list && key[j] > bk) bk = key[j];
+                if (__ballot(bk != 0) == 0) break;                        // (no lane has another alignment in this list)
+                if (bk != 0) {
+                  int b_start = 0, b_end = 0;
+                  uint32_t b_edits = 0, b_src = 0, b_wk = 0;
 #pragma unroll
-                    for (int j = 0; j < SMALL_MAX; j++)
-                      if (widx[j] == w && key[j] == bk) { b_start = st[j]; b_end = en[j]; b_edits = ed[j]; b_src = src[j]; b_wk = wk[j]; key[j] = 0; }
-                    if ((int)b_edits <= a.max_total_diffs) {
-                      bool clash = false;
+                  for (int j = 0; j < SMALL_MAX; j++)
+                    if (widx[j] == w && key[j] == bk) { b_start = st[j]; b_end = en[j]; b_edits = ed[j]; b_src = src[j]; b_wk = wk[j]; key[j] = 0; }
+                  if ((int)b_edits <= a.max_total_diffs) {
+                    bool clash = false;
 #pragma unroll
-                      for (int k = 0; k < SMALL_MAX; k++)
-                        if ((uint32_t)k >= first_kept && (uint32_t)k < nk) clash = clash || (min(b_end, ke[k]) - max(b_start, ks[k]) > a.max_overlap);   // GA:119-122
-                      if (!clash) {
+                    for (int k = 0; k < SMALL_MAX; k++)
+                      if ((uint32_t)k >= first_kept && (uint32_t)k < nk) clash = clash || (min(b_end, ke[k]) - max(b_start, ks[k]) > a.max_overlap);   // GA:119-122
+                    if (!clash) {
 #pragma unroll
-                        for (int k = 0; k < SMALL_MAX; k++) {
-                          if ((uint32_t)k == nk) { ks[k] = b_start; ke[k] = b_end; }
-                          if ((uint32_t)k == nA) acc_src[k] = b_src;
-                        }
-                        nk++; nA++;
-                        const int64_t ws = (int64_t)b_wk * (int64_t)a.step;
-                        if (ws >= lo && ws < hi) out_acc++;
+                      for (int k = 0; k < SMALL_MAX; k++) {
+                        if ((uint32_t)k == nk) { ks[k] = b_start; ke[k] = b_end; }
+                        if ((uint32_t)k == nA) acc_src[k] = b_src;
                       }
+                      nk++; nA++;
+                      const int64_t ws = (int64_t)b_wk * (int64_t)a.step;
+                      if (ws >= x.lo() && ws < x.hi()) out_acc++;
                     }
                   }
                 }
               }
             }
           }
-          // ---- 3. coordinates; 4. order by counting, restart points, the walk of SR:661-671 over the (at most four) sorted hits ----
-          HitRec hr[SMALL_MAX];
+        }
+        // ---- 3. coordinates; 4. order by counting, restart points, the walk of SR:661-671 over the (at most four) sorted hits ----
+        HitRec hr[SMALL_MAX];
 #pragma unroll
-          for (int i = 0; i < SMALL_MAX; i++) hr[i] = HitRec{};
+        for (int i = 0; i < SMALL_MAX; i++) hr[i] = HitRec{};
 #pragma unroll
-          for (int i = 0; i < SMALL_MAX; i++) {
-            if (__ballot((uint32_t)i < nA) == 0) break;                   // (no lane accepted that many)
-            if ((uint32_t)i < nA) { hr[i] = hit_record(a.raw + acc_src[i], a.guides, a.win_base, a.win); if (hr[i].gstart < 0) out_flags |= BIN_FLAG_RANGE; }
-          }
-          int s_start[SMALL_MAX], s_end[SMALL_MAX], s_score[SMALL_MAX], s_arr[SMALL_MAX];
-          uint32_t s_cs[SMALL_MAX];
+        for (int i = 0; i < SMALL_MAX; i++) {
+          if (__ballot((uint32_t)i < nA) == 0) break;                   // (no lane accepted that many)
+          if ((uint32_t)i < nA) { hr[i] = hit_record(a.raw + acc_src[i], a.guides, a.win_base, a.win); if (hr[i].gstart < 0) out_flags |= BIN_FLAG_RANGE; }
+        }
+        int s_start[SMALL_MAX], s_end[SMALL_MAX], s_score[SMALL_MAX], s_arr[SMALL_MAX];
+        uint32_t s_cs[SMALL_MAX];
 #pragma unroll
-          for (int p = 0; p < SMALL_MAX; p++) { s_start[p] = 0; s_end[p] = 0; s_score[p] = 0; s_cs[p] = 0; s_arr[p] = 0; }
+        for (int p = 0; p < SMALL_MAX; p++) { s_start[p] = 0; s_end[p] = 0; s_score[p] = 0; s_cs[p] = 0; s_arr[p] = 0; }
 #pragma unroll
-          for (int i = 0; i < SMALL_MAX; i++) {
-            if (__ballot((uint32_t)i < nA) == 0) break;
-            if ((uint32_t)i < nA) {
-              uint32_t rank = 0;
+        for (int i = 0; i < SMALL_MAX; i++) {
+          if (__ballot((uint32_t)i < nA) == 0) break;
+          if ((uint32_t)i < nA) {
+            uint32_t rank = 0;
 #pragma unroll
-              for (int j = 0; j < SMALL_MAX; j++) {
-                if ((uint32_t)j < nA) {
-                  const bool less = hr[j].gstart < hr[i].gstart ||
-                                    (hr[j].gstart == hr[i].gstart && (hr[j].minus < hr[i].minus || (hr[j].minus == hr[i].minus && hr[j].score > hr[i].score)));
-                  const bool same = hr[j].gstart == hr[i].gstart && hr[j].minus == hr[i].minus && hr[j].score == hr[i].score;
-                  rank += (less || (same && j < i)) ? 1u : 0u;
-                }
+            for (int j = 0; j < SMALL_MAX; j++) {
+              if ((uint32_t)j < nA) {
+                const SortCmp cmp = sort_cmp(hr[j].gstart, hr[j].minus, hr[j].score, hr[i].gstart, hr[i].minus, hr[i].score);
+                rank += (cmp.less || (cmp.same && j < i)) ? 1u : 0u;
               }
+            }
 #pragma unroll
-              for (int p = 0; p < SMALL_MAX; p++)
-                if ((uint32_t)p == rank) { s_start[p] = hr[i].gstart; s_end[p] = hr[i].rh_end; s_score[p] = hr[i].score; s_cs[p] = hr[i].minus; s_arr[p] = i; }
+            for (int p = 0; p < SMALL_MAX; p++)
+              if ((uint32_t)p == rank) { s_start[p] = hr[i].gstart; s_end[p] = hr[i].rh_end; s_score[p] = hr[i].score; s_cs[p] = hr[i].minus; s_arr[p] = i; }
+          }
+        }
+        bool head[SMALL_MAX], keep[SMALL_MAX], done[SMALL_MAX];
+#pragma unroll
+        for (int p = 0; p < SMALL_MAX; p++) {
+          head[p] = (uint32_t)p < nA; keep[p] = false; done[p] = false;
+          bool stop = false;                                            // hits.hip prep_body: look back over the hits that can reach into this one
+#pragma unroll
+          for (int j = SMALL_MAX - 1; j >= 0; j--) {
+            if (j < p && (uint32_t)p < nA && !stop) {
+              if (s_start[j] + HIT_MAX_LEN - 1 - s_start[p] < a.max_overlap) stop = true;
+              else if (s_cs[j] == s_cs[p] && s_end[j] - s_start[p] >= a.max_overlap) { head[p] = false; stop = true; }
             }
           }
-          bool head[SMALL_MAX], keep[SMALL_MAX], done[SMALL_MAX];
+        }
+#pragma unroll
+        for (uint32_t cs = 0; cs < 2; cs++) {                            // one (chromosome, strand) group after the other, left to right
+          int curp = -1;                                                // position of the walk's current hit (cluster_body's `hit`)
+          bool active = false;                                          // the walk started at a certain restart point
+          int c_s = 0, c_e = 0, c_sc = 0;
 #pragma unroll
           for (int p = 0; p < SMALL_MAX; p++) {
-            head[p] = (uint32_t)p < nA; keep[p] = false; done[p] = false;
-            bool stop = false;                                            // hits.hip prep_body: look back over the hits that can reach into this one
+            if ((uint32_t)p < nA && s_cs[p] == cs) {
+              if (head[p]) {
+                if (curp >= 0 && active) {                              // the cluster before ends: !more
 #pragma unroll
-            for (int j = SMALL_MAX - 1; j >= 0; j--) {
-              if (j < p && (uint32_t)p < nA && !stop) {
-                if (s_start[j] + HIT_MAX_LEN - 1 - s_start[p] < a.max_overlap) stop = true;
-                else if (s_cs[j] == s_cs[p] && s_end[j] - s_start[p] >= a.max_overlap) { head[p] = false; stop = true; }
-              }
-            }
-          }
-#pragma unroll
-          for (uint32_t cs = 0; cs < 2; cs++) {                            // one (chromosome, strand) group after the other, left to right
-            int curp = -1;                                                // position of the walk's current hit (cluster_body's `hit`)
-            bool active = false;                                          // the walk started at a certain restart point
-            int c_s = 0, c_e = 0, c_sc = 0;
-#pragma unroll
-            for (int p = 0; p < SMALL_MAX; p++) {
-              if ((uint32_t)p < nA && s_cs[p] == cs) {
-                if (head[p]) {
-                  if (curp >= 0 && active) {                              // the cluster before ends: !more
+                  for (int k = 0; k < SMALL_MAX; k++) if (k == curp) keep[k] = true;
+                }
+                active = (int64_t)s_start[p] >= x.known_from() + HIT_MAX_LEN;
+                curp = p; c_s = s_start[p]; c_e = s_end[p]; c_sc = s_score[p];
+                if (active) done[p] = true;
+              } else if (active) {
+                const int ov = max(0, min(s_end[p], c_e) - max(s_start[p], c_s));   // RH:141-144
+                done[p] = true;
+                if (!(ov >= a.max_overlap && s_score[p] <= c_sc)) {      // not swallowed: the walk goes on from here
+                  if (ov < a.max_overlap) {
 #pragma unroll
                     for (int k = 0; k < SMALL_MAX; k++) if (k == curp) keep[k] = true;
                   }
-                  active = (int64_t)s_start[p] >= known_from + HIT_MAX_LEN;
                   curp = p; c_s = s_start[p]; c_e = s_end[p]; c_sc = s_score[p];
-                  if (active) done[p] = true;
-                } else if (active) {
-                  const int ov = max(0, min(s_end[p], c_e) - max(s_start[p], c_s));   // RH:141-144
-                  done[p] = true;
-                  if (!(ov >= a.max_overlap && s_score[p] <= c_sc)) {      // not swallowed: the walk goes on from here
-                    if (ov < a.max_overlap) {
-#pragma unroll
-                      for (int k = 0; k < SMALL_MAX; k++) if (k == curp) keep[k] = true;
-                    }
-                    curp = p; c_s = s_start[p]; c_e = s_end[p]; c_sc = s_score[p];
-                  }
                 }
               }
             }
-            if (curp >= 0 && active) {
-#pragma unroll
-              for (int k = 0; k < SMALL_MAX; k++) if (k == curp) keep[k] = true;
-            }
           }
-          // ---- 5. the bin's kept hits in final order ----
+          if (curp >= 0 && active) {
 #pragma unroll
-          for (int p = 0; p < SMALL_MAX; p++) {
-            const unsigned long long okey = ((unsigned long long)c << 32) | (unsigned long long)(uint32_t)s_start[p];
-            const bool mine = (uint32_t)p < nA && (int64_t)s_start[p] >= lo && (int64_t)s_start[p] < hi && okey >= a.own_lo && okey < a.own_hi;
-            if (mine && !done[p]) out_flags |= BIN_FLAG_HALO;
-            if (mine && keep[p]) {
-              uint32_t rsrc = 0;
-              HitRec hh{};
-#pragma unroll
-              for (int i = 0; i < SMALL_MAX; i++) if (s_arr[p] == i) { rsrc = acc_src[i]; hh = hr[i]; }
-              const RawAln* rp = a.raw + rsrc;
-              const GuideDev* gp = a.guides + rp->guide;
-              const int pam = rp->pam;
-              const int len = middle_length(rp, hh, gp->L, pam >= 0 ? gp->pam_len[pam] : 0, (int)m.rc.pu_len[pam + 1], (int)m.n_max, (int)m.mid_bound);
-              if (len < 0) out_flags |= BIN_FLAG_ROW;
-              else {
-                const uint32_t name_len = m.name_off[hh.contig + 1] - m.name_off[hh.contig];
-                out_bytes += m.rc.head_len + name_len + 1u + (uint32_t)len + m.rc.tail_len;
-#pragma unroll
-                for (int k = 0; k < SMALL_MAX; k++) if ((uint32_t)k == out_rows) out_row[k] = BinRow{rsrc, (uint32_t)len};
-                out_rows++;
-              }
-            }
+            for (int k = 0; k < SMALL_MAX; k++) if (k == curp) keep[k] = true;
           }
-          if (out_flags) { out_rows = 0; out_bytes = 0; out_acc = 0; }
         }
+        // ---- 5. the bin's kept hits in final order ----
+#pragma unroll
+        for (int p = 0; p < SMALL_MAX; p++) {
+          const unsigned long long okey = own_key(x.c, s_start[p]);
+          const bool mine = (uint32_t)p < nA && (int64_t)s_start[p] >= x.lo() && (int64_t)s_start[p] < x.hi() && okey >= a.own_lo && okey < a.own_hi;
+          if (mine && !done[p]) out_flags |= BIN_FLAG_HALO;
+          if (mine && keep[p]) {
+            uint32_t rsrc = 0;
+            HitRec hh{};
+#pragma unroll
+            for (int i = 0; i < SMALL_MAX; i++) if (s_arr[p] == i) { rsrc = acc_src[i]; hh = hr[i]; }
+            const int len = middle_length(m, a.raw + rsrc, hh);
+            if (len < 0) out_flags |= BIN_FLAG_ROW;
+            else {
+              out_bytes += row_length(m.rc, m.name_off, hh.contig, (uint32_t)len);
+#pragma unroll
+              for (int k = 0; k < SMALL_MAX; k++) if ((uint32_t)k == out_rows) out_row[k] = BinRow{rsrc, (uint32_t)len};
+              out_rows++;
+            }
+          }
+        }
+        if (out_flags) { out_rows = 0; out_bytes = 0; out_acc = 0; }
       }
     }
   }
@@ -596,6 +574,29 @@ struct RowsArgs {
   const uint32_t* complex_count;   // (statistics) bins that took a whole wave
 };
 
+// The post to the host (word layout: binned.hpp, BIN_BOX_*), by the 64 lanes of one wave once the bin kernels' sums are final: the lane's
+// eight counters, rows and accepted alignments summed over the chunks, the bytes and flags given, the three stamps; then the sequence word.
+// FLAGS_LATE: the flags are read here, by the posting lane (the counts kernel: every workgroup's are in by then), not given.
+template <bool FLAGS_LATE = false>
+__device__ __forceinline__ void bin_post(const BinArgs& a, const RowsArgs& o, unsigned long long bytes, uint32_t flags, const int lane) {
+  uint32_t rows_tot = 0, acc_tot = 0;
+  for (uint32_t ch = (uint32_t)lane; ch < o.n_chunks; ch += 64) { rows_tot += a.chunk_rows[ch]; acc_tot += a.chunk_acc[ch]; }
+  rows_tot = (uint32_t)wave_sum_u64(rows_tot); acc_tot = (uint32_t)wave_sum_u64(acc_tot);
+  if (lane == 0) {
+    for (int i = 0; i < 8; i++) o.box[BIN_BOX_COUNTERS + i] = __hip_atomic_load(o.counters + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    o.box[BIN_BOX_ROWS] = rows_tot; o.box[BIN_BOX_BYTES] = (uint32_t)bytes; o.box[BIN_BOX_BYTES + 1] = (uint32_t)(bytes >> 32);
+    o.box[BIN_BOX_FLAGS] = FLAGS_LATE ? __hip_atomic_load(a.flags, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : flags;
+    o.box[BIN_BOX_ACCEPTED] = acc_tot; o.box[BIN_BOX_COMPLEX] = *o.complex_count;
+    const unsigned long long now = (unsigned long long)wall_clock64();
+    for (int i = 0; i < 3; i++) {
+      const unsigned long long t = i < 2 ? a.stamps[i] : now;
+      o.box[BIN_BOX_STAMPS + 2 * i] = (uint32_t)t; o.box[BIN_BOX_STAMPS + 2 * i + 1] = (uint32_t)(t >> 32);
+    }
+    __threadfence_system();
+    __hip_atomic_store(o.box, o.seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+  }
+}
+
 // One wave per bin: where the bin's text starts = bytes of the chunks before its chunk + bytes of the bins before it in its chunk;
 // then row by row: the middle part in the wave's LDS line (build_middle), head | chromosome | middle | tail at the row's final place.
 // The first wave of the grid also posts the totals (final since bin_hits_kernel ended) to the host when it starts.
@@ -625,36 +626,14 @@ __global__ __launch_bounds__(64 * BIN_WAVES) void bin_rows_kernel(BinArgs a, Mid
   tot = wave_sum_u64(tot); before = wave_sum_u64(before);
   const bool to_host = tot <= o.host_cap;                             // (the same for every wave of the grid; the host decides by the posted bytes)
   const uint32_t flags = *a.flags | (!to_host && tot > o.text_cap ? BIN_FLAG_TEXT : 0u);
-  if (posts && it == 0) {
-    uint32_t rows_tot = 0, acc_tot = 0;
-    for (uint32_t ch = (uint32_t)lane; ch < o.n_chunks; ch += 64) { rows_tot += a.chunk_rows[ch]; acc_tot += a.chunk_acc[ch]; }
-    rows_tot = (uint32_t)wave_sum_u64(rows_tot); acc_tot = (uint32_t)wave_sum_u64(acc_tot);
-    if (lane == 0) {
-      for (int i = 0; i < 8; i++) o.box[BIN_BOX_COUNTERS + i] = __hip_atomic_load(o.counters + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      o.box[BIN_BOX_ROWS] = rows_tot; o.box[BIN_BOX_BYTES] = (uint32_t)tot; o.box[BIN_BOX_BYTES + 1] = (uint32_t)(tot >> 32);
-      o.box[BIN_BOX_FLAGS] = flags; o.box[BIN_BOX_ACCEPTED] = acc_tot; o.box[BIN_BOX_COMPLEX] = *o.complex_count;
-      const unsigned long long now = (unsigned long long)wall_clock64();
-      for (int i = 0; i < 3; i++) {
-        const unsigned long long t = i < 2 ? a.stamps[i] : now;
-        o.box[BIN_BOX_STAMPS + 2 * i] = (uint32_t)t; o.box[BIN_BOX_STAMPS + 2 * i + 1] = (uint32_t)(t >> 32);
-      }
-      __threadfence_system();
-      __hip_atomic_store(o.box, o.seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
-  }
+  if (posts && it == 0) bin_post(a, o, tot, flags, lane);
   if (flags != 0) return;
   if (n == 0) continue;
-  const uint8_t* head = reinterpret_cast<const uint8_t*>(m.blob) + o.rc.head_off;     // constant pieces straight from global memory (L2-resident)
-  const uint8_t* tail = reinterpret_cast<const uint8_t*>(m.blob) + o.rc.tail_off;
   unsigned long long at = before;
   for (uint32_t k = 0; k < n; k++) {
     const auto* row = uniform_ptr(a.rows) + ((size_t)rel * BIN_ROWS + k);
     const uint32_t ridx = row->raw, want = row->len;
-    const auto* rp = uniform_ptr(a.raw) + ridx;
-    RowIn rin;
-    const auto* ow = (const __attribute__((address_space(4))) uint32_t*)rp->ops;
-    rin.w0 = ow[0]; rin.w1 = ow[1]; rin.w2 = ow[2]; rin.w3 = ow[3]; rin.w4 = ow[4];
-    rin.n_ops = rp->n_ops; rin.pam = rp->pam; rin.offset = rp->offset; rin.pam_x = rp->pam_x;
+    const RowIn rin = load_row_in(a.raw + ridx);
     HitRec h;                                             // the same coordinates bin_hits_kernel derived (every lane computes them: uniform)
     {
       const HitRec hv = hit_record(a.raw + ridx, a.guides, a.win_base, a.win);
@@ -663,28 +642,10 @@ __global__ __launch_bounds__(64 * BIN_WAVES) void bin_rows_kernel(BinArgs a, Mid
       h.gend = __builtin_amdgcn_readfirstlane(hv.gend); h.score = __builtin_amdgcn_readfirstlane(hv.score);
       h.rh_end = __builtin_amdgcn_readfirstlane(hv.rh_end); h.minus = (uint32_t)__builtin_amdgcn_readfirstlane((int)hv.minus);
     }
-    const auto* gp = uniform_ptr(a.guides) + rp->guide;
-    RowGuide g;
-    g.L = gp->L; g.pam5 = gp->pam5; g.pam_len = rin.pam >= 0 ? gp->pam_len[rin.pam] : 0;
-    wave_lds_sync();                                      // the copy-out of the previous row is done with line[]
-    const int len = build_middle<true>(line, fwd, m, blob, rin, h, g, lane);
-    if (len < 0 || (uint32_t)len != want) {               // cannot happen: both kernels run the same arithmetic
-      if (lane == 0) __hip_atomic_fetch_or(o.box + BIN_BOX_LATE, BIN_FLAG_INTERNAL, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-      return;
-    }
-    wave_lds_sync();
-    const uint32_t nb = uniform_ptr(m.name_off)[h.contig], nl = uniform_ptr(m.name_off)[h.contig + 1] - nb;
-    const uint32_t s0 = o.rc.head_len, s1 = s0 + nl + 1, s2 = s1 + (uint32_t)len, total = s2 + o.rc.tail_len;
-    char* dst = (to_host ? o.host_text : o.text) + at;
-    for (uint32_t x = (uint32_t)lane; x < total; x += 64) {
-      uint8_t ch;
-      if (x < s0) ch = head[x];
-      else if (x < s1) ch = (x - s0 < nl) ? (uint8_t)o.names[nb + x - s0] : (uint8_t)'\t';
-      else if (x < s2) ch = line[x - s1];
-      else ch = tail[x - s2];
-      dst[x] = (char)ch;
-    }
-    at += total;
+    const RowGuide g = row_guide(a.guides + uniform_ptr(a.raw)[ridx].guide, rin.pam);
+    const int len = checked_middle(line, fwd, m, blob, rin, h, g, lane, want, o.box + BIN_BOX_LATE, BIN_FLAG_INTERNAL);
+    if (len < 0) return;
+    at += write_row((to_host ? o.host_text : o.text) + at, line, (uint32_t)len, h.contig, o.rc, blob, o.names, m.name_off, lane);
   }
   }
 }
@@ -715,32 +676,7 @@ __global__ __launch_bounds__(COUNTS_BLOCK) void bin_counts_kernel(BinArgs a, Cou
   if (!counts_flush(hist, co)) return;
   counts_publish(co);
   if (threadIdx.x >= 64) return;                            // the post: the first wave of the last workgroup
-  const int lane = (int)threadIdx.x;
-  uint32_t rows_tot = 0, acc_tot = 0;
-  for (uint32_t ch = (uint32_t)lane; ch < o.n_chunks; ch += 64) { rows_tot += a.chunk_rows[ch]; acc_tot += a.chunk_acc[ch]; }
-  rows_tot = (uint32_t)wave_sum_u64(rows_tot); acc_tot = (uint32_t)wave_sum_u64(acc_tot);
-  if (lane == 0) {
-    for (int i = 0; i < 8; i++) o.box[BIN_BOX_COUNTERS + i] = __hip_atomic_load(o.counters + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    o.box[BIN_BOX_ROWS] = rows_tot; o.box[BIN_BOX_BYTES] = 0u; o.box[BIN_BOX_BYTES + 1] = 0u;
-    o.box[BIN_BOX_FLAGS] = __hip_atomic_load(a.flags, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    o.box[BIN_BOX_ACCEPTED] = acc_tot; o.box[BIN_BOX_COMPLEX] = *o.complex_count;
-    const unsigned long long now = (unsigned long long)wall_clock64();
-    for (int i = 0; i < 3; i++) {
-      const unsigned long long t = i < 2 ? a.stamps[i] : now;
-      o.box[BIN_BOX_STAMPS + 2 * i] = (uint32_t)t; o.box[BIN_BOX_STAMPS + 2 * i + 1] = (uint32_t)(t >> 32);
-    }
-    __threadfence_system();
-    __hip_atomic_store(o.box, o.seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-  }
-}
-
-template <typename T>
-hipError_t grow_to(T** p, size_t& cap, size_t need) {
-  if (need <= cap) return hipSuccess;
-  (void)hipFree(*p); *p = nullptr; cap = 0;
-  hipError_t e = hipMalloc((void**)p, need * sizeof(T));
-  if (e == hipSuccess) cap = need;
-  return e;
+  bin_post<true>(a, o, 0ull, 0u, (int)threadIdx.x);      // no bytes
 }
 
 }  // namespace
@@ -805,16 +741,16 @@ hipError_t binned_prepare_host(BinnedWork** pw, uint32_t n_bins, void** clear, s
   BinnedWork& w = **pw;
   hipError_t e;
   const uint32_t n_chunks = (n_bins >> CHUNK_SHIFT) + 1;
-  TRY(grow_to(&w.bin_idx, w.bin_idx_cap, (size_t)n_bins * BIN_CAP));
-  TRY(grow_to(&w.rows, w.rows_cap, (size_t)n_bins * BIN_ROWS));
-  TRY(grow_to(&w.bin_rows, w.bin_rows_cap, (size_t)n_bins));
-  TRY(grow_to(&w.bin_bytes, w.bin_bytes_cap, (size_t)n_bins));
-  TRY(grow_to(&w.complex_list, w.complex_cap, (size_t)n_bins));
-  TRY(grow_to(&w.rows_list, w.rows_list_cap, (size_t)n_bins));
+  TRY(grow(&w.bin_idx, w.bin_idx_cap, (size_t)n_bins * BIN_CAP, false));
+  TRY(grow(&w.rows, w.rows_cap, (size_t)n_bins * BIN_ROWS, false));
+  TRY(grow(&w.bin_rows, w.bin_rows_cap, (size_t)n_bins, false));
+  TRY(grow(&w.bin_bytes, w.bin_bytes_cap, (size_t)n_bins, false));
+  TRY(grow(&w.complex_list, w.complex_cap, (size_t)n_bins, false));
+  TRY(grow(&w.rows_list, w.rows_list_cap, (size_t)n_bins, false));
   // the 64-bit sums first, then the 32-bit arrays; the whole block is a multiple of 16 bytes (MI355X_MICROARCH: memset sizes)
   const uint32_t n_supers = (n_bins >> SUPER_SHIFT) + 1;
   const size_t bytes = (((size_t)(n_chunks + n_supers) * 8 + (size_t)n_chunks * 4 * 2 + (size_t)n_bins * 4 + 12) + 15) & ~(size_t)15;
-  TRY(grow_to(&w.clear, w.clear_cap, bytes));
+  TRY(grow(&w.clear, w.clear_cap, bytes, false));
   w.chunk_bytes = reinterpret_cast<unsigned long long*>(w.clear);
   w.super_bytes = w.chunk_bytes + n_chunks;
   w.chunk_rows = reinterpret_cast<uint32_t*>(w.super_bytes + n_supers);
@@ -857,117 +793,116 @@ void binned_fill_align_args(const BinnedWork* w, const BinnedGeometry& geo, Alig
 
 const char* binned_text(const HitsWork* hits) { return hits ? hits->text : nullptr; }
 
-static hipError_t launch_rows(BinnedWork& w, HitsWork& hw, const BinArgs& ba, const MidArgs& ma, const uint32_t* d_counters, hipStream_t stream,
-                              Mailbox* post, hipEvent_t ev_start, hipEvent_t ev_done, char* host_dst = nullptr, unsigned long long host_dst_cap = 0) {
-  hipError_t e;
-  TRY(mailbox_open(*post));
-  RowsArgs ro{};
-  ro.rc = hw.rc; ro.names = hw.names; ro.text = hw.text; ro.text_cap = hw.text_cap; ro.host_text = w.host_text; ro.host_cap = w.host_text ? w.host_cap : 0;
-  if (host_dst) { ro.host_text = host_dst; ro.host_cap = host_dst_cap; }   // the caller's page-locked destination: the text's final place
-  ro.counters = d_counters; ro.box = post->dev; ro.seq = ++post->seq;
-  ro.n_chunks = w.n_chunks; ro.n_supers = w.n_supers; ro.complex_count = w.complex_count;
-  post->host[BIN_BOX_LATE] = 0;                              // raised by any wave while rows are written; read when the stream is done
-  const unsigned grid = std::min<uint32_t>(std::max<uint32_t>(w.n_bins, 1u), 16384u);      // strides over the list of bins with rows
-  hipExtLaunchKernelGGL(bin_rows_kernel, dim3(grid), dim3(64), 0, stream, ev_start, ev_done, 0, ba, ma, ro);
-  return hipGetLastError();
-}
-
-static void fill_args(BinnedWork& w, HitsWork& hw, const BinnedGeometry& geo, const HitsRef& ref, const RawAln* d_raw, const GuideDev* d_guides,
-                      const uint64_t* d_win_base, const int2* d_win, const BinnedParams& p, BinArgs& ba, MidArgs& ma) {
+// What the kernels of a call take: the bins' tables and sums (BinArgs), the row builder's inputs (MidArgs).  A null table would be a
+// wild read on the device, not an error code: refused here, for every entry point.
+static hipError_t call_args(const BinnedCall& c, BinArgs& ba, MidArgs& ma) {
+  if (!c.work || !c.hits || !*c.hits || !c.post) return hipErrorInvalidValue;
+  const BinnedWork& w = *c.work;
+  const HitsWork& hw = **c.hits;
+  const BinnedGeometry& geo = c.geo;
+  const BinnedParams& p = c.p;
   ba = BinArgs{};
-  ba.raw = d_raw; ba.bin_idx = w.bin_idx; ba.bin_count = w.bin_count; ba.bin_base = geo.d_bin_base; ba.bin_contig = geo.d_bin_contig; ba.n_contigs = geo.n_contigs; ba.bin_first = geo.bin_first;
-  ba.n_bins = geo.n_bins; ba.bin_shift = geo.bin_shift; ba.guides = d_guides; ba.win_base = d_win_base; ba.win = d_win;
+  ba.raw = c.d_raw; ba.bin_idx = w.bin_idx; ba.bin_count = w.bin_count; ba.bin_base = geo.d_bin_base; ba.bin_contig = geo.d_bin_contig; ba.n_contigs = geo.n_contigs; ba.bin_first = geo.bin_first;
+  ba.n_bins = geo.n_bins; ba.bin_shift = geo.bin_shift; ba.guides = c.d_guides; ba.win_base = c.d_win_base; ba.win = c.d_win;
   ba.W = p.window_size; ba.step = p.step; ba.max_total_diffs = p.max_total_diffs; ba.max_overlap = p.max_overlap;
   ba.own_lo = p.own_lo; ba.own_hi = p.own_hi;
   ba.rows = w.rows; ba.bin_rows = w.bin_rows; ba.bin_bytes = w.bin_bytes; ba.chunk_bytes = w.chunk_bytes; ba.super_bytes = w.super_bytes; ba.chunk_rows = w.chunk_rows;
   ba.chunk_acc = w.chunk_acc; ba.flags = w.flags; ba.rows_list = w.rows_list; ba.rows_count = w.rows_count; ba.stamps = w.stamps;
-  const uint32_t n_max = (uint32_t)std::min<int>(MID_COLS, std::max(1, p.max_ops));
+  const MidSize ms = mid_size(p.max_ops);
   ma = MidArgs{};
-  ma.ref = ref; ma.rc = hw.rc; ma.blob = hw.blob; ma.name_off = hw.name_off; ma.guides = d_guides;
-  ma.mid_bound = (6 * n_max + 128 + 3) & ~3u; ma.n_max = n_max; ma.blob_bytes = (uint32_t)hw.blob_bytes;
+  ma.ref = c.ref; ma.rc = hw.rc; ma.blob = hw.blob; ma.name_off = hw.name_off; ma.guides = c.d_guides;
+  ma.mid_bound = ms.mid_bound; ma.n_max = ms.n_max; ma.blob_bytes = (uint32_t)hw.blob_bytes;
+  if (!ba.raw || !ba.bin_idx || !ba.bin_count || !ba.bin_base || !ba.bin_contig || !ba.guides || !ba.win_base || !ba.win || !ba.rows || !ba.bin_rows ||
+      !ba.bin_bytes || !ba.chunk_bytes || !ba.super_bytes || !ba.chunk_rows || !ba.chunk_acc || !ba.flags || !ba.rows_list || !ba.rows_count || !ba.stamps || !ma.blob || !ma.name_off || !hw.names ||
+      !w.complex_list || !w.complex_count || w.n_bins < geo.n_bins)
+    return hipErrorInvalidValue;
+  return hipSuccess;
 }
 
-hipError_t binned_run(BinnedWork* pw, HitsWork** phw, const BinnedGeometry& geo, const HitsRef& ref, const RawAln* d_raw, const GuideDev* d_guides,
-                      const uint64_t* d_win_base, const int2* d_win, const BinnedParams& p, const uint32_t* d_counters, hipStream_t stream,
-                      Mailbox* post, hipEvent_t ev_hits_done, hipEvent_t ev_rows_start, hipEvent_t ev_rows_done, bool with_rows) {
-  if (!pw || !*phw || !(*phw)->prepared) return hipErrorInvalidValue;
-  BinnedWork& w = *pw;
-  HitsWork& hw = **phw;
-  hw.prepared = false;
+// The post's share of a rows or counts launch; the word for flags raised while rows are written is cleared (read when the stream is done).
+static hipError_t post_args(const BinnedCall& c, RowsArgs& ro) {
   hipError_t e;
+  TRY(mailbox_open(*c.post));
+  const BinnedWork& w = *c.work;
+  ro = RowsArgs{};
+  ro.counters = c.d_counters; ro.box = c.post->dev; ro.seq = ++c.post->seq;
+  ro.n_chunks = w.n_chunks; ro.n_supers = w.n_supers; ro.complex_count = w.complex_count;
+  c.post->host[BIN_BOX_LATE] = 0;
+  return hipSuccess;
+}
+
+static hipError_t launch_rows(const BinnedCall& c, const BinArgs& ba, const MidArgs& ma, hipEvent_t ev_start, hipEvent_t ev_done, char* host_dst = nullptr,
+                              unsigned long long host_dst_cap = 0) {
+  hipError_t e;
+  const BinnedWork& w = *c.work;
+  const HitsWork& hw = **c.hits;
+  if (!hw.text) return hipErrorInvalidValue;
+  RowsArgs ro;
+  TRY(post_args(c, ro));
+  ro.rc = hw.rc; ro.names = hw.names; ro.text = hw.text; ro.text_cap = hw.text_cap; ro.host_text = w.host_text; ro.host_cap = w.host_text ? w.host_cap : 0;
+  if (host_dst) { ro.host_text = host_dst; ro.host_cap = host_dst_cap; }   // the caller's page-locked destination: the text's final place
+  const unsigned grid = std::min<uint32_t>(std::max<uint32_t>(w.n_bins, 1u), 16384u);      // strides over the list of bins with rows
+  hipExtLaunchKernelGGL(bin_rows_kernel, dim3(grid), dim3(64), 0, c.stream, ev_start, ev_done, 0, ba, ma, ro);
+  return hipGetLastError();
+}
+
+hipError_t binned_run(const BinnedCall& c, hipEvent_t ev_hits_done, hipEvent_t ev_rows_start, hipEvent_t ev_rows_done, bool with_rows) {
+  hipError_t e;
+  BinArgs ba; MidArgs ma;
+  TRY(call_args(c, ba, ma));
+  BinnedWork& w = *c.work;
+  HitsWork& hw = **c.hits;
+  if (!hw.prepared) return hipErrorInvalidValue;
+  hw.prepared = false;
   {
     size_t first_guess = (size_t)32 << 20;                     // BIN_FLAG_TEXT asks for more
     if (const char* env = TUNE_GET("CALITAS_BINNED_TEXT_KB")) first_guess = (size_t)std::max(1, std::atoi(env)) << 10;   // tests: force the regrow path
     if (hw.text_cap < first_guess) TRY(grow(&hw.text, hw.text_cap, first_guess));
   }
-  BinArgs ba; MidArgs ma;
-  fill_args(w, hw, geo, ref, d_raw, d_guides, d_win_base, d_win, p, ba, ma);
-  // (a null table here would be a wild read on the device, not an error code: refuse on the host)
-  if (!ba.raw || !ba.bin_idx || !ba.bin_count || !ba.bin_base || !ba.bin_contig || !ba.guides || !ba.win_base || !ba.win || !ba.rows || !ba.bin_rows ||
-      !ba.bin_bytes || !ba.chunk_bytes || !ba.super_bytes || !ba.chunk_rows || !ba.chunk_acc || !ba.flags || !ba.rows_list || !ba.rows_count || !ba.stamps || !ma.blob || !ma.name_off || !hw.names ||
-      !hw.text || w.n_bins < geo.n_bins)
-    return hipErrorInvalidValue;
   SmallArgs sa{w.complex_list, w.complex_count, 0u};
   if (const char* env = TUNE_GET("CALITAS_BINNED_COMPLEX")) sa.force_complex = std::atoi(env) != 0;   // tests: the wave-per-bin kernel for every bin
-  if (!sa.complex_list || !sa.complex_count) return hipErrorInvalidValue;
   // (the listed bins inside the lane kernel -- its waves doing the bins their lanes left over, one launch less -- measured slower at
   // every size: 0.176 against 0.165 ms for an E. coli-sized call, 0.685 against 0.588 ms for an eighth of the hg38-sized genome: the
   // lanes of a wave that does a listed bin wait for it, and the listed bins of a wave run one after the other)
-  const dim3 sgrid((std::max<uint32_t>(geo.n_bins, 1u) + 63) / 64);
-  hipLaunchKernelGGL(bin_hits_small_kernel, sgrid, dim3(64), 0, stream, ba, ma, sa);
+  const dim3 sgrid((std::max<uint32_t>(c.geo.n_bins, 1u) + 63) / 64);
+  hipLaunchKernelGGL(bin_hits_small_kernel, sgrid, dim3(64), 0, c.stream, ba, ma, sa);
   TRY(hipGetLastError());
   // the listed bins: a fixed grid that strides over the list (its length is on the device)
-  const unsigned grid = std::min<uint32_t>(std::max<uint32_t>(geo.n_bins, 1u), 1024u);
-  hipExtLaunchKernelGGL(bin_hits_kernel, dim3(grid), dim3(64), 0, stream, nullptr, ev_hits_done, 0, ba, ma, (const uint32_t*)w.complex_list,
+  const unsigned grid = std::min<uint32_t>(std::max<uint32_t>(c.geo.n_bins, 1u), 1024u);
+  hipExtLaunchKernelGGL(bin_hits_kernel, dim3(grid), dim3(64), 0, c.stream, nullptr, ev_hits_done, 0, ba, ma, (const uint32_t*)w.complex_list,
                         (const uint32_t*)w.complex_count);
   TRY(hipGetLastError());
   if (!with_rows) return hipSuccess;                         // (the caller launches them itself: binned_rows)
-  return launch_rows(w, hw, ba, ma, d_counters, stream, post, ev_rows_start, ev_rows_done);
+  return launch_rows(c, ba, ma, ev_rows_start, ev_rows_done);
 }
 
-hipError_t binned_rows(BinnedWork* pw, HitsWork** phw, const BinnedGeometry& geo, const HitsRef& ref, const RawAln* d_raw, const GuideDev* d_guides,
-                       const uint64_t* d_win_base, const int2* d_win, const BinnedParams& p, const uint32_t* d_counters, hipStream_t stream,
-                       Mailbox* post, hipEvent_t ev_rows_done, char* host_dst, unsigned long long host_dst_cap) {
-  if (!pw || !*phw) return hipErrorInvalidValue;
+hipError_t binned_rows(const BinnedCall& c, hipEvent_t ev_rows_done, char* host_dst, unsigned long long host_dst_cap) {
   BinArgs ba; MidArgs ma;
-  fill_args(*pw, **phw, geo, ref, d_raw, d_guides, d_win_base, d_win, p, ba, ma);
-  return launch_rows(*pw, **phw, ba, ma, d_counters, stream, post, nullptr, ev_rows_done, host_dst, host_dst_cap);
+  hipError_t e = call_args(c, ba, ma);
+  return e == hipSuccess ? launch_rows(c, ba, ma, nullptr, ev_rows_done, host_dst, host_dst_cap) : e;
 }
 
-hipError_t binned_counts(BinnedWork* pw, HitsWork** phw, const BinnedGeometry& geo, const HitsRef& ref, const RawAln* d_raw, const GuideDev* d_guides,
-                         const uint64_t* d_win_base, const int2* d_win, const BinnedParams& p, const uint32_t* d_counters, hipStream_t stream,
-                         Mailbox* post, hipEvent_t ev_done, const CountsShape& shape) {
-  if (!pw || !*phw) return hipErrorInvalidValue;
-  BinnedWork& w = *pw;
-  HitsWork& hw = **phw;
+hipError_t binned_counts(const BinnedCall& c, hipEvent_t ev_done, const CountsShape& shape) {
   hipError_t e;
-  BinArgs ba; MidArgs ma;
-  fill_args(w, hw, geo, ref, d_raw, d_guides, d_win_base, d_win, p, ba, ma);
+  BinArgs ba; MidArgs ma; RowsArgs ro;
+  TRY(call_args(c, ba, ma));
   CountsOut co{};
-  TRY(counts_buffers(hw, shape, &co));
-  TRY(mailbox_open(*post));
-  RowsArgs ro{};
-  ro.counters = d_counters; ro.box = post->dev; ro.seq = ++post->seq;
-  ro.n_chunks = w.n_chunks; ro.n_supers = w.n_supers; ro.complex_count = w.complex_count;
-  post->host[BIN_BOX_LATE] = 0;
-  hipExtLaunchKernelGGL(bin_counts_kernel, dim3(counts_grid(geo.n_bins)), dim3(COUNTS_BLOCK), 0, stream, nullptr, ev_done, 0, ba, co, ro);
+  TRY(counts_buffers(**c.hits, shape, &co));
+  TRY(post_args(c, ro));
+  hipExtLaunchKernelGGL(bin_counts_kernel, dim3(counts_grid(c.geo.n_bins)), dim3(COUNTS_BLOCK), 0, c.stream, nullptr, ev_done, 0, ba, co, ro);
   return hipGetLastError();
 }
 
 const uint64_t* binned_counts_table(const HitsWork* hits) { return hits ? reinterpret_cast<const uint64_t*>(hits->cnt_host) : nullptr; }
 
-hipError_t binned_rerun_rows(BinnedWork* pw, HitsWork** phw, const BinnedGeometry& geo, const HitsRef& ref, const RawAln* d_raw, const GuideDev* d_guides,
-                             const uint64_t* d_win_base, const int2* d_win, const BinnedParams& p, const uint32_t* d_counters,
-                             uint64_t bytes, hipStream_t stream, Mailbox* post, hipEvent_t ev_rows_done) {
-  if (!pw || !*phw) return hipErrorInvalidValue;
-  BinnedWork& w = *pw;
-  HitsWork& hw = **phw;
+hipError_t binned_rerun_rows(const BinnedCall& c, uint64_t bytes, hipEvent_t ev_rows_done) {
   hipError_t e;
-  TRY(hipStreamSynchronize(stream));                           // nobody is writing the old buffer any more
-  TRY(grow(&hw.text, hw.text_cap, (size_t)bytes + (size_t)(bytes / 4)));
   BinArgs ba; MidArgs ma;
-  fill_args(w, hw, geo, ref, d_raw, d_guides, d_win_base, d_win, p, ba, ma);
-  return launch_rows(w, hw, ba, ma, d_counters, stream, post, nullptr, ev_rows_done);
+  TRY(call_args(c, ba, ma));
+  HitsWork& hw = **c.hits;
+  TRY(hipStreamSynchronize(c.stream));                         // nobody is writing the old buffer any more
+  TRY(grow(&hw.text, hw.text_cap, (size_t)bytes + (size_t)(bytes / 4)));
+  return launch_rows(c, ba, ma, nullptr, ev_rows_done);
 }
 
 #undef TRY

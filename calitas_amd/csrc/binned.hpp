@@ -70,33 +70,35 @@ struct BinnedParams {
   unsigned long long own_lo, own_hi;
 };
 
-// Queues the two kernels behind trace_kernel.  hits: the lane's HitsWork after hits_prepare / hits_set_names (constant row pieces, contig
-// names, the text buffer).  d_counters: the lane's eight counters (posted with the result).  The rows kernel posts rows, bytes and
+// One lane's call of the entry points below: built once, handed to each.  hits: the lane's HitsWork after hits_prepare / hits_set_names
+// (constant row pieces, contig names, the text buffer).  d_raw: the lane's raw alignments (trace_kernel's list).  d_counters: the lane's
+// eight counters (posted with the result).
+struct BinnedCall {
+  BinnedWork* work; HitsWork** hits;
+  BinnedGeometry geo; HitsRef ref;
+  const RawAln* d_raw; const GuideDev* d_guides; const uint64_t* d_win_base; const int2* d_win;
+  BinnedParams p;
+  const uint32_t* d_counters; hipStream_t stream; Mailbox* post;
+};
+
+// Queues the two kernels behind trace_kernel.  The rows kernel posts rows, bytes and
 // flags to `post` when it STARTS (they are final then); the text is complete when the stream is.  ev_*: optional timing events that
 // ride on the dispatches (each costs the kernel behind it ~5 us of its start: pass nullptr and take the times from the posted stamps).
-hipError_t binned_run(BinnedWork* work, HitsWork** hits, const BinnedGeometry& geo, const HitsRef& ref, const RawAln* d_raw, const GuideDev* d_guides,
-                      const uint64_t* d_win_base, const int2* d_win, const BinnedParams& p, const uint32_t* d_counters, hipStream_t stream,
-                      Mailbox* post, hipEvent_t ev_hits_done, hipEvent_t ev_rows_start, hipEvent_t ev_rows_done, bool with_rows = true);
+hipError_t binned_run(const BinnedCall& call, hipEvent_t ev_hits_done, hipEvent_t ev_rows_start, hipEvent_t ev_rows_done, bool with_rows = true);
 // The rows kernel by itself, behind a binned_run(..., with_rows = false): host_dst / host_dst_cap (may be null / 0) is page-locked memory
 // of the caller the device can address -- the place the text finally goes.  A text of up to host_dst_cap bytes is written there by the
 // kernel (46-49 GB/s for rows of ~520 bytes, tools/host_write_bench.hip: the copy engine's rate, without the copy's start-up and the
 // wait between the kernel and it); a longer one goes to the device buffer as usual.  The posted byte count tells which.
-hipError_t binned_rows(BinnedWork* work, HitsWork** hits, const BinnedGeometry& geo, const HitsRef& ref, const RawAln* d_raw, const GuideDev* d_guides,
-                       const uint64_t* d_win_base, const int2* d_win, const BinnedParams& p, const uint32_t* d_counters, hipStream_t stream,
-                       Mailbox* post, hipEvent_t ev_rows_done, char* host_dst, unsigned long long host_dst_cap);
+hipError_t binned_rows(const BinnedCall& call, hipEvent_t ev_rows_done, char* host_dst, unsigned long long host_dst_cap);
 // The table of calitas_search_counts instead of rows, behind a binned_run(..., with_rows = false): bin_counts_kernel counts the bins'
 // kept hits (hits_dev.hpp: one histogram per workgroup in LDS) and the workgroup that finishes last writes the table into page-locked
-// host memory and then posts what the rows kernel posts (counters, rows, flags, accepted alignments, stamps; no bytes) -- the lane still
-// makes one host round trip, and the table is complete when the post arrives: binned_counts_table(), `shape.cells()` words, valid until
-// the next counts call on this HitsWork.
-hipError_t binned_counts(BinnedWork* work, HitsWork** hits, const BinnedGeometry& geo, const HitsRef& ref, const RawAln* d_raw, const GuideDev* d_guides,
-                         const uint64_t* d_win_base, const int2* d_win, const BinnedParams& p, const uint32_t* d_counters, hipStream_t stream,
-                         Mailbox* post, hipEvent_t ev_done, const CountsShape& shape);
+// host memory and then posts what the rows kernel posts (counters, rows, flags, accepted alignments, stamps; no bytes -- one device
+// function, bin_post, writes both) -- the lane still makes one host round trip, and the table is complete when the post arrives:
+// binned_counts_table(), `shape.cells()` words, valid until the next counts call on this HitsWork.
+hipError_t binned_counts(const BinnedCall& call, hipEvent_t ev_done, const CountsShape& shape);
 const uint64_t* binned_counts_table(const HitsWork* hits);
 // After BIN_FLAG_TEXT: the text buffer grown to `bytes`, the rows kernel once more.
-hipError_t binned_rerun_rows(BinnedWork* work, HitsWork** hits, const BinnedGeometry& geo, const HitsRef& ref, const RawAln* d_raw, const GuideDev* d_guides,
-                             const uint64_t* d_win_base, const int2* d_win, const BinnedParams& p, const uint32_t* d_counters,
-                             uint64_t bytes, hipStream_t stream, Mailbox* post, hipEvent_t ev_rows_done);
+hipError_t binned_rerun_rows(const BinnedCall& call, uint64_t bytes, hipEvent_t ev_rows_done);
 // Where the text is: in the lane's page-locked host buffer when the posted byte count is <= binned_host_cap() (complete when the
 // stream is; no copy), else in the device buffer of `hits`.
 const char* binned_text(const HitsWork* hits);

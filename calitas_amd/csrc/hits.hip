@@ -17,6 +17,9 @@
 //                      one lane walks one cluster with the reference's loop (SR:661-671), stepping over the other strand's hits.
 //   4. len_kernel / rows_kernel: rows of the kept hits, already in final order (dropped hits have length 0): lengths, offsets, then
 //                      every row built at its final place.
+// What these kernels share with the per-bin ones (binned.hip) is in hits_dev.hpp: middle_length, row_length, load_row_in, row_guide,
+// checked_middle, write_row, own_key.  The post of the counts is post_counts / counts_from_box below.  hits_run's stages are the functions
+// of a HitsRun: size_buffers, order_and_walk, ext_rows_on_demand, then counts_tail or rows_tail.
 #include <hip/hip_runtime.h>
 #include <sched.h>
 
@@ -124,8 +127,8 @@ __device__ __forceinline__ void cluster_body(const uint32_t i, const int32_t* s_
   if (!head[i]) return;
   const uint32_t cs = s_cs[i];
   // HitsOwn: a walk that starts where hits may be missing must not decide an owned hit
-  const bool unsure = (((unsigned long long)(cs >> 2) << 32) | (uint32_t)s_start[i]) < own.safe;
-  auto owned = [&](uint32_t j) { const unsigned long long k = ((unsigned long long)(cs >> 2) << 32) | (uint32_t)s_start[j]; return k >= own.lo && k < own.hi; };
+  const bool unsure = own_key(cs >> 2, s_start[i]) < own.safe;
+  auto owned = [&](uint32_t j) { const unsigned long long k = own_key(cs >> 2, s_start[j]); return k >= own.lo && k < own.hi; };
   // next hit of this (contig, strand) group after position j, or n
   auto next = [&](uint32_t j) {
     for (j++; j < n; j++) {
@@ -223,8 +226,8 @@ __global__ void ext_place_kernel(const uint32_t* order, const uint32_t* midlen, 
 //   len_kernel   one lane per sorted position: the row's length from the alignment's op counts (middle_length: the arithmetic
 //                build_middle does with ballots, without fetching or writing anything) -- what the offsets' scan needs;
 //   rows_kernel  after the scan and the host's look at the totals: a wave per row builds the middle part in its LDS line and writes
-//                head | chromosome \t | middle | tail at the row's final place.  The two lengths are held against each other for every
-//                row (a mismatch raises HITS_FLAG_INTERNAL in the work's late word: two implementations of one arithmetic).
+//                head | chromosome \t | middle | tail at the row's final place (write_row).  The two lengths are held against each other for
+//                every row (checked_middle: a mismatch raises HITS_FLAG_INTERNAL in the work's late word: two implementations of one arithmetic).
 __global__ __launch_bounds__(256) void len_kernel(MidArgs a, uint32_t* midlen, uint64_t* lens, uint32_t* flags) {
   CALITAS_TAIL_PRIO();
   const uint32_t k = blockIdx.x * 256 + threadIdx.x;
@@ -239,19 +242,16 @@ __global__ __launch_bounds__(256) void len_kernel(MidArgs a, uint32_t* midlen, u
     } else {
       const HitRec h = a.hits[v];
       if (live && (a.own_lo != 0 || a.own_hi != ~0ull)) {   // HitsOwn: rows of the stretch only
-        const unsigned long long key = ((unsigned long long)(uint32_t)h.contig << 32) | (uint32_t)h.gstart;
+        const unsigned long long key = own_key((uint32_t)h.contig, h.gstart);
         live = key >= a.own_lo && key < a.own_hi;
       }
       int len = 0;
       if (live) {
-        const RawAln* rp = a.fin + v;
-        const GuideDev* gp = a.guides + rp->guide;
-        const int pam = rp->pam;
-        len = middle_length(rp, h, gp->L, pam >= 0 ? gp->pam_len[pam] : 0, (int)a.rc.pu_len[pam + 1], (int)a.n_max, (int)a.mid_bound);
+        len = middle_length(a, a.fin + v, h);
         if (len < 0) { atomicOr(flags, HITS_FLAG_ROW); len = 0; }
       }
       midlen[k] = (uint32_t)len;
-      lens[k] = live ? (uint64_t)(a.rc.head_len + (a.name_off[h.contig + 1] - a.name_off[h.contig]) + 1 + (uint32_t)len + a.rc.tail_len) : 0;
+      lens[k] = live ? (uint64_t)row_length(a.rc, a.name_off, h.contig, (uint32_t)len) : 0;
     }
   }
   // rows (and kept hits of the caller's own) of the call: one atomic per wave
@@ -287,8 +287,6 @@ __global__ __launch_bounds__(256) void rows_kernel(MidArgs a, OutArgs o, char* t
   // queued right behind the kernels that size the text, before the host has looked at their counts: nothing to do when the stage
   // declined, and nothing may be written when the text does not fit the buffer it was given
   if (o.counts[0] > o.text_cap || (uint32_t)o.counts[2] != 0u) return;
-  const uint8_t* head = blob + a.rc.head_off;
-  const uint8_t* tail = blob + a.rc.tail_off;
   const uint32_t k0 = (blockIdx.x * 4 + wave) * ROWS_PER_WAVE;
   for (int rr = 0; rr < ROWS_PER_WAVE; rr++) {
     const uint32_t k = k0 + (uint32_t)rr;
@@ -304,36 +302,29 @@ __global__ __launch_bounds__(256) void rows_kernel(MidArgs a, OutArgs o, char* t
       for (uint64_t b = (uint64_t)lane; b < nb; b += 64) dst[b] = o.ext_rows[b0 + b];
       continue;
     }
-    const auto* rp = uniform_ptr(a.fin) + v;
-    RowIn r;
-    const auto* ow = (const __attribute__((address_space(4))) uint32_t*)rp->ops;   // RawAln::ops sits at a 4-byte aligned offset
-    r.w0 = ow[0]; r.w1 = ow[1]; r.w2 = ow[2]; r.w3 = ow[3]; r.w4 = ow[4];
-    r.n_ops = rp->n_ops; r.pam = rp->pam; r.offset = rp->offset; r.pam_x = rp->pam_x;
+    const RowIn r = load_row_in(a.fin + v);
     const auto* hp = uniform_ptr(a.hits) + v;
     HitRec h;
     h.contig = hp->contig; h.start = hp->start; h.end = hp->end; h.gstart = hp->gstart; h.gend = hp->gend; h.score = hp->score;
     h.rh_end = hp->rh_end; h.minus = hp->minus;
-    const auto* gp = uniform_ptr(a.guides) + rp->guide;
-    RowGuide g;
-    g.L = gp->L; g.pam5 = gp->pam5; g.pam_len = r.pam >= 0 ? gp->pam_len[r.pam] : 0;
-    wave_lds_sync();                                      // the copy-out of the previous row is done with line[]
-    const int len = build_middle(line, fwd, a, blob, r, h, g, lane);
-    if (len < 0 || (uint32_t)len != want) {               // cannot happen: both kernels run the same arithmetic
-      if (lane == 0) __hip_atomic_fetch_or(o.late, HITS_FLAG_INTERNAL, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-      continue;
-    }
-    wave_lds_sync();
-    const uint32_t nb = uniform_ptr(a.name_off)[h.contig], nl = uniform_ptr(a.name_off)[h.contig + 1] - nb;
-    const uint32_t s0 = a.rc.head_len, s1 = s0 + nl + 1, s2 = s1 + (uint32_t)len, total = s2 + a.rc.tail_len;
-    for (uint32_t x = (uint32_t)lane; x < total; x += 64) {
-      uint8_t ch;
-      if (x < s0) ch = head[x];
-      else if (x < s1) ch = (x - s0 < nl) ? (uint8_t)o.names[nb + x - s0] : (uint8_t)'\t';
-      else if (x < s2) ch = line[x - s1];
-      else ch = tail[x - s2];
-      dst[x] = (char)ch;
-    }
+    const RowGuide g = row_guide(a.guides + uniform_ptr(a.fin)[v].guide, r.pam);
+    const int len = checked_middle(line, fwd, a, blob, r, h, g, lane, want, o.late, HITS_FLAG_INTERNAL);
+    if (len < 0) continue;
+    (void)write_row(dst, line, (uint32_t)len, h.contig, a.rc, blob, o.names, a.name_off, lane);
   }
+}
+
+// The post every call waits for: the three counts (d_counts; rows and flags come from other kernels' atomics) as six words into the host's
+// mailbox (mailbox.hpp), then the sequence word.  One thread, from the kernel that completes the counts -- a kernel of its own for the
+// post was one more launch on the path every call waits for.  counts_from_box is the host's side of it.
+__device__ __forceinline__ void post_counts(uint32_t* box, const uint64_t* counts, uint32_t seq) {
+  const uint32_t* src = reinterpret_cast<const uint32_t*>(counts);
+  for (int i = 0; i < 6; i++) box[1 + i] = __hip_atomic_load(src + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  __threadfence_system();
+  __hip_atomic_store(box, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+void counts_from_box(const Mailbox& box, uint64_t* counts) {
+  for (int k = 0; k < 3; k++) counts[k] = (uint64_t)box.host[1 + 2 * k] | ((uint64_t)box.host[2 + 2 * k] << 32);
 }
 
 // Counts mode: behind the walks, instead of len_kernel / rows_kernel.  One lane per sorted position k: keep[k] and order[k] lead to the
@@ -352,7 +343,7 @@ __global__ __launch_bounds__(COUNTS_BLOCK) void counts_kernel(MidArgs a, CountsO
     const uint32_t v = a.order[k];
     if (v >= a.n_dev) continue;                             // (a hit of the caller's own: not in a counts call)
     const HitRec h = a.hits[v];
-    const unsigned long long key = ((unsigned long long)(uint32_t)h.contig << 32) | (uint32_t)h.gstart;
+    const unsigned long long key = own_key((uint32_t)h.contig, h.gstart);
     if (key < a.own_lo || key >= a.own_hi) continue;
     const int cell = counts_cell(a.fin + v, h.minus, o.shape);
     if (cell < 0) { atomicOr(flags, HITS_FLAG_EXTENT); continue; }
@@ -365,24 +356,15 @@ __global__ __launch_bounds__(COUNTS_BLOCK) void counts_kernel(MidArgs a, CountsO
   if (threadIdx.x == 0 && s_rows) (void)__hip_atomic_fetch_add(a.n_rows, s_rows, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   if (!counts_flush(hist, o)) return;
   counts_publish(o);
-  if (threadIdx.x == 0) {
-    const uint32_t* src = reinterpret_cast<const uint32_t*>(counts);   // [0] bytes: none, [1] rows, [2] flags
-    for (int i = 0; i < 6; i++) box[1 + i] = __hip_atomic_load(src + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __threadfence_system();
-    __hip_atomic_store(box, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-  }
+  if (threadIdx.x == 0) post_counts(box, counts, seq);    // [0] bytes: none, [1] rows, [2] flags
 }
 
-// Length of the text = end of the last row; posted with the other two counts (rows, flags) to the host's mailbox (mailbox.hpp) by the
-// same thread -- a kernel of its own for the post was one more launch on the path every call waits for.
+// Length of the text = end of the last row; posted with the other two counts (rows, flags) by the same thread (post_counts).
 __global__ void total_kernel(const uint64_t* offs, const uint64_t* lens, uint32_t n, uint64_t* counts, uint32_t* box, uint32_t seq) {
   CALITAS_TAIL_PRIO();
   counts[0] = offs[n - 1] + lens[n - 1];
   __threadfence();
-  const uint32_t* src = reinterpret_cast<const uint32_t*>(counts);
-  for (int i = 0; i < 6; i++) box[1 + i] = __hip_atomic_load(src + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // rows and flags come from other kernels' atomics
-  __threadfence_system();
-  __hip_atomic_store(box, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+  post_counts(box, counts, seq);
 }
 
 // Row offsets, the length of the text and the post to the host for at most HITS_SMALL rows: one workgroup instead of the scan's two
@@ -405,10 +387,7 @@ __global__ __launch_bounds__(HITS_SMALL) void offs_small_kernel(const uint64_t* 
   if (i == 0) {
     counts[0] = s_sum[HITS_SMALL - 1];
     __threadfence();
-    const uint32_t* src = reinterpret_cast<const uint32_t*>(counts);
-    for (int k = 0; k < 6; k++) box[1 + k] = __hip_atomic_load(src + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __threadfence_system();
-    __hip_atomic_store(box, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+    post_counts(box, counts, seq);
   }
 }
 
@@ -484,207 +463,232 @@ hipError_t hits_prepare_host(HitsWork** pw, const RowStrings& st, HitsSetup* out
   return hipSuccess;
 }
 
-hipError_t hits_run(HitsWork** pw, const HitsRef& ref, const RawAln* d_final, uint32_t n_in, const GuideDev* d_guides,
-                    const uint64_t* d_win_base, const int2* d_win, const RowStrings& st, int max_overlap, int score_hi,
-                    int max_ops, uint32_t window_reach, hipStream_t stream, HitsResult* res, const HitsExt* ext, const HitsOwn* own,
-                    const CountsShape* counts) {
-  if (!*pw) *pw = new HitsWork();
-  HitsWork& w = **pw;
-  hipError_t e;
-  *res = HitsResult{};
-  const uint32_t n_ext = ext ? ext->n : 0;
-  if (counts && n_ext) return hipErrorInvalidValue;      // (a table of the reference's own hits)
-  if (ext && ext->kept) *ext->kept = 0;
-  if ((uint64_t)n_in + n_ext > 0xFFFFFFF0ull) { res->flags = HITS_FLAG_CLUSTER; return hipSuccess; }
-  const size_t n = (size_t)n_in + n_ext;
-  CountsOut co{};
-  if (counts) {
-    TRY(counts_buffers(w, *counts, &co));
-    if (n == 0) std::memset(co.host, 0, (size_t)co.cells * sizeof(unsigned long long));
-    res->counts = reinterpret_cast<const uint64_t*>(co.host);
-  }
-  if (n == 0) return hipSuccess;
-  if (n_ext) window_reach = 0;                         // the caller's hits have no window: the general stable sort
-  n_in = (uint32_t)n;                                  // every stage behind hit_kernel runs over both; n_dev is the device's share
-  const uint32_t n_dev = (uint32_t)(n - n_ext);
-  if (!w.prepared) TRY(hits_prepare(pw, st, stream));  // normally done at the start of the call
-  w.prepared = false;
-  const RowConstDev rc = w.rc;
-  const size_t blob_bytes = w.blob_bytes;
-  uint32_t* d_kept = (uint32_t*)(w.d_counts + 1);
-  uint32_t* d_flags = (uint32_t*)(w.d_counts + 2);
+namespace {
 
-  TRY(grow(&w.hits, w.hits_cap, n)); TRY(grow(&w.keys, w.keys_cap, n)); TRY(grow(&w.keys2, w.keys2_cap, n));
-  TRY(grow(&w.vals, w.vals_cap, n)); TRY(grow(&w.vals2, w.vals2_cap, n)); TRY(grow(&w.s_cs, w.cs_cap, n)); TRY(grow(&w.wks, w.wks_cap, n));
-  TRY(grow(&w.lens, w.lens_cap, n)); TRY(grow(&w.offs, w.offs_cap, n)); TRY(grow(&w.s_start, w.ss_cap, n));
-  TRY(grow(&w.s_end, w.se_cap, n)); TRY(grow(&w.s_score, w.sc_cap, n)); TRY(grow(&w.keep, w.keep_cap, n)); TRY(grow(&w.head, w.head_cap, n));
-  size_t t1 = 0, t3 = 0;
-  if (window_reach == 0) TRY(rocprim::radix_sort_pairs(nullptr, t1, w.keys, w.keys2, w.vals, w.vals2, n, 0, 64, stream));
-  TRY(rocprim::exclusive_scan(nullptr, t3, w.lens, w.offs, (uint64_t)0, n, rocprim::plus<uint64_t>(), stream));
-  {
+// One hits_run: the work, the call, and what its stages hand to each other.
+struct HitsRun {
+  HitsWork& w; const HitsRunCall& c; HitsResult* res;
+  size_t n;                             // what every stage behind hit_kernel runs over: the device's n_dev alignments and the caller's n_ext hits
+  uint32_t n_dev, n_ext, reach;         // reach: window_reach, 0 with hits of the caller's (they have no window: the general stable sort)
+  bool small, on_demand, ext_on_host;   // 1-3 and the offsets in one launch each | HitsExt::rows_for | HitsExtRows::fill_on_host
+  HitsOwn ho; CountsOut co;
+  uint32_t *d_kept, *d_flags;
+  dim3 grid;                            // one lane per alignment, 256 to a workgroup
+
+  HitsRun(HitsWork& work, const HitsRunCall& call, HitsResult* result, const CountsOut& table)
+      : w(work), c(call), res(result), n_ext(call.ext ? call.ext->n : 0), ext_on_host(false), ho(call.own ? *call.own : HitsOwn()), co(table) {
+    n = (size_t)c.n + n_ext; n_dev = c.n;
+    reach = n_ext ? 0u : c.window_reach;
+    small = n <= HITS_SMALL && reach != 0 && !c.own;
+    on_demand = n_ext && c.ext->rows_for;
+    d_kept = (uint32_t*)(w.d_counts + 1); d_flags = (uint32_t*)(w.d_counts + 2);
+    grid = dim3((unsigned)((n + 255) / 256));
+  }
+
+  // Scratch for n alignments, and rocPRIM's for the sort (crowded windows only) and the scan of the row lengths.
+  hipError_t size_buffers() {
+    hipError_t e;
+    TRY(grow(&w.hits, w.hits_cap, n)); TRY(grow(&w.keys, w.keys_cap, n)); TRY(grow(&w.keys2, w.keys2_cap, n));
+    TRY(grow(&w.vals, w.vals_cap, n)); TRY(grow(&w.vals2, w.vals2_cap, n)); TRY(grow(&w.s_cs, w.cs_cap, n)); TRY(grow(&w.wks, w.wks_cap, n));
+    TRY(grow(&w.lens, w.lens_cap, n)); TRY(grow(&w.offs, w.offs_cap, n)); TRY(grow(&w.s_start, w.ss_cap, n));
+    TRY(grow(&w.s_end, w.se_cap, n)); TRY(grow(&w.s_score, w.sc_cap, n)); TRY(grow(&w.keep, w.keep_cap, n)); TRY(grow(&w.head, w.head_cap, n));
+    size_t t1 = 0, t3 = 0;
+    if (reach == 0) TRY(rocprim::radix_sort_pairs(nullptr, t1, w.keys, w.keys2, w.vals, w.vals2, n, 0, 64, c.stream));
+    TRY(rocprim::exclusive_scan(nullptr, t3, w.lens, w.offs, (uint64_t)0, n, rocprim::plus<uint64_t>(), c.stream));
     const size_t need = std::max(t1, t3);
     if (need > w.temp_cap) { (void)hipFree(w.temp); w.temp = nullptr; w.temp_cap = 0; TRY(hipMalloc(&w.temp, need)); w.temp_cap = need; }
+    return hipSuccess;
   }
-  const dim3 block(256), grid((unsigned)((n + 255) / 256));
-  size_t ts;
-  bool ext_on_host = false;                            // HitsExtRows::fill_on_host
-  const bool on_demand = n_ext && ext->rows_for;       // the rows of the caller's hits once the walks have decided (hits.hpp)
-  if (on_demand && own) return hipErrorInvalidValue;
-  // the rows of the caller's hits (offsets, text) to the device: before anything runs when they came with the call, behind the walks on demand
-  auto upload_ext_rows = [&](const HitsExtRows& r) -> hipError_t {
+
+  // The rows of the caller's hits (offsets, text) to the device: before anything runs when they came with the call, behind the walks on demand.
+  hipError_t upload_ext_rows(const HitsExtRows& r) {
+    hipError_t e;
     if (!r.row_off || r.row_off[0] != 0) return hipErrorInvalidValue;
     const size_t row_bytes = (size_t)r.row_off[n_ext];
     TRY(grow(&w.ext_off, w.ext_off_cap, (size_t)n_ext + 1));
     TRY(grow(&w.ext_rows, w.ext_rows_cap, std::max<size_t>(1, row_bytes)));
-    TRY(hipMemcpyAsync(w.ext_off, r.row_off, ((size_t)n_ext + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, stream));
+    TRY(hipMemcpyAsync(w.ext_off, r.row_off, ((size_t)n_ext + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, c.stream));
     if (r.fill_on_host) { ext_on_host = true; return hipSuccess; }
-    if (row_bytes && r.rows) TRY(hipMemcpyAsync(w.ext_rows, r.rows, row_bytes, hipMemcpyHostToDevice, stream));
+    if (row_bytes && r.rows) TRY(hipMemcpyAsync(w.ext_rows, r.rows, row_bytes, hipMemcpyHostToDevice, c.stream));
     else if (row_bytes) {
       if (!r.n_seg || !r.seg || !r.seg_off || r.seg_off[0] != 0 || r.seg_off[r.n_seg] != row_bytes) return hipErrorInvalidValue;
       for (uint32_t sg = 0; sg < r.n_seg; sg++) {
         const uint64_t nb = r.seg_off[sg + 1] - r.seg_off[sg];
-        if (nb) TRY(hipMemcpyAsync(w.ext_rows + r.seg_off[sg], r.seg[sg], (size_t)nb, hipMemcpyHostToDevice, stream));
+        if (nb) TRY(hipMemcpyAsync(w.ext_rows + r.seg_off[sg], r.seg[sg], (size_t)nb, hipMemcpyHostToDevice, c.stream));
       }
     }
     return hipSuccess;
-  };
-  if (n_ext) {
-    TRY(grow(&w.ext_keys, w.ext_keys_cap, (size_t)n_ext));
-    TRY(hipMemcpyAsync(w.ext_keys, ext->keys, (size_t)n_ext * sizeof(HitsExtKey), hipMemcpyHostToDevice, stream));
-    if (!on_demand) {
-      HitsExtRows given;
-      given.row_off = ext->row_off; given.rows = ext->rows; given.n_seg = ext->n_seg; given.seg = ext->seg; given.seg_off = ext->seg_off;
-      TRY(upload_ext_rows(given));
+  }
+
+  // 1-3: coordinates, the final order, removeOverlaps (the caller's own hits go up first: keys, and the rows that came with the call).
+  hipError_t order_and_walk() {
+    hipError_t e;
+    hipStream_t stream = c.stream;
+    const uint32_t n_in = (uint32_t)n;
+    if (n_ext) {
+      TRY(grow(&w.ext_keys, w.ext_keys_cap, (size_t)n_ext));
+      TRY(hipMemcpyAsync(w.ext_keys, c.ext->keys, (size_t)n_ext * sizeof(HitsExtKey), hipMemcpyHostToDevice, stream));
+      if (!on_demand) {
+        TRY(upload_ext_rows(HitsExtRows{c.ext->row_off, c.ext->rows, c.ext->n_seg, c.ext->seg, c.ext->seg_off}));
+      }
     }
+    if (small) {          // in one launch
+      HitsSmallArgs sa{};
+      sa.fin = c.d_final; sa.guides = c.d_guides; sa.win_base = c.d_win_base; sa.win = c.d_win; sa.hits = w.hits; sa.keys = w.keys; sa.vals = w.vals;
+      sa.wks = w.wks; sa.order = w.vals2; sa.s_start = w.s_start; sa.s_end = w.s_end; sa.s_score = w.s_score; sa.s_cs = w.s_cs; sa.head = w.head;
+      sa.keep = w.keep; sa.flags = d_flags; sa.n = n_in; sa.reach = reach; sa.score_hi = c.score_hi; sa.max_overlap = c.max_overlap;
+      hipLaunchKernelGGL(hits_small_kernel, dim3(1), dim3(HITS_SMALL), 0, stream, sa);
+      return hipSuccess;
+    }
+    const dim3 block(256);
+    // 1: coordinates and the final order
+    if (n_dev) hipLaunchKernelGGL(hit_kernel, dim3((n_dev + 255) / 256), block, 0, stream, c.d_final, n_dev, c.d_guides, c.d_win_base, c.d_win, c.score_hi, w.hits, w.keys, w.vals, w.wks, d_flags);
+    if (n_ext) hipLaunchKernelGGL(ext_kernel, dim3((n_ext + 255) / 256), block, 0, stream, (const HitsExtKey*)w.ext_keys, n_ext, n_dev, c.ext->contig, c.score_hi, w.hits, w.keys, w.vals, d_flags);
+    if (reach) {          // the order by counting among the neighbouring windows (rank_kernel)
+      hipLaunchKernelGGL(rank_kernel, grid, block, 0, stream, (const uint64_t*)w.keys, (const uint32_t*)w.wks, n_in, reach, w.vals2);
+    } else {              // a window is too crowded for that: the general stable sort
+      size_t ts = w.temp_cap;
+      TRY(rocprim::radix_sort_pairs(w.temp, ts, w.keys, w.keys2, w.vals, w.vals2, n, 0, 64, stream));
+    }
+    // 2-3: removeOverlaps
+    hipLaunchKernelGGL(prep_kernel, grid, block, 0, stream, (const HitRec*)w.hits, (const uint32_t*)w.vals2, n_in, c.max_overlap, w.s_start, w.s_end,
+                       w.s_score, w.s_cs, w.head, w.keep);
+    hipLaunchKernelGGL(cluster_kernel, grid, block, 0, stream, (const int32_t*)w.s_start, (const int32_t*)w.s_end, (const int32_t*)w.s_score,
+                       (const uint32_t*)w.s_cs, (const uint8_t*)w.head, n_in, c.max_overlap, w.keep, d_flags, ho);
+    return hipSuccess;
   }
-  const bool small = n_in <= HITS_SMALL && window_reach != 0 && !own;
-  const HitsOwn ho = own ? *own : HitsOwn();
-  if (small) {          // 1-3 in one launch
-    HitsSmallArgs sa{};
-    sa.fin = d_final; sa.guides = d_guides; sa.win_base = d_win_base; sa.win = d_win; sa.hits = w.hits; sa.keys = w.keys; sa.vals = w.vals;
-    sa.wks = w.wks; sa.order = w.vals2; sa.s_start = w.s_start; sa.s_end = w.s_end; sa.s_score = w.s_score; sa.s_cs = w.s_cs; sa.head = w.head;
-    sa.keep = w.keep; sa.flags = d_flags; sa.n = n_in; sa.reach = window_reach; sa.score_hi = score_hi; sa.max_overlap = max_overlap;
-    hipLaunchKernelGGL(hits_small_kernel, dim3(1), dim3(HITS_SMALL), 0, stream, sa);
-  } else {
-  // 1: coordinates and the final order
-  if (n_dev) hipLaunchKernelGGL(hit_kernel, dim3((n_dev + 255) / 256), block, 0, stream, d_final, n_dev, d_guides, d_win_base, d_win, score_hi, w.hits, w.keys, w.vals, w.wks, d_flags);
-  if (n_ext) hipLaunchKernelGGL(ext_kernel, dim3((n_ext + 255) / 256), block, 0, stream, (const HitsExtKey*)w.ext_keys, n_ext, n_dev, ext->contig, score_hi, w.hits, w.keys, w.vals, d_flags);
-  if (window_reach) {   // the order by counting among the neighbouring windows (rank_kernel)
-    hipLaunchKernelGGL(rank_kernel, grid, block, 0, stream, (const uint64_t*)w.keys, (const uint32_t*)w.wks, n_in, window_reach, w.vals2);
-  } else {              // a window is too crowded for that: the general stable sort
-    ts = w.temp_cap;
-    TRY(rocprim::radix_sort_pairs(w.temp, ts, w.keys, w.keys2, w.vals, w.vals2, n, 0, 64, stream));
-  }
-  // 2-3: removeOverlaps
-  hipLaunchKernelGGL(prep_kernel, grid, block, 0, stream, (const HitRec*)w.hits, (const uint32_t*)w.vals2, n_in, max_overlap, w.s_start, w.s_end,
-                     w.s_score, w.s_cs, w.head, w.keep);
-  hipLaunchKernelGGL(cluster_kernel, grid, block, 0, stream, (const int32_t*)w.s_start, (const int32_t*)w.s_end, (const int32_t*)w.s_score,
-                     (const uint32_t*)w.s_cs, (const uint8_t*)w.head, n_in, max_overlap, w.keep, d_flags, ho);
-  }
-  if (on_demand) {
-    // the walks' verdicts on the caller's hits to the host, the rows of the kept ones back: the one place where this stage waits for the
-    // host in the middle (a contig's worth of a variant search: 80 000 entries, 8 000 rows, a millisecond of the caller's workers)
+
+  // HitsExt::rows_for: the walks' verdicts on the caller's hits to the host, the rows of the kept ones back: the one place where this stage
+  // waits for the host in the middle (a contig's worth of a variant search: 80 000 entries, 8 000 rows, a millisecond of the caller's workers).
+  hipError_t ext_rows_on_demand() {
+    hipError_t e;
     TRY(grow(&w.ext_keep, w.ext_keep_cap, (size_t)n_ext));
-    if ((size_t)n_ext > w.h_ext_keep_cap) {
-      if (w.h_ext_keep) (void)hipHostFree(w.h_ext_keep);
-      w.h_ext_keep = nullptr; w.h_ext_keep_cap = 0;
-      const size_t cap = (size_t)n_ext + (size_t)n_ext / 4 + 4096;
-      TRY(hipHostMalloc((void**)&w.h_ext_keep, cap, hipHostMallocDefault));
-      w.h_ext_keep_cap = cap;
-    }
-    hipLaunchKernelGGL(ext_keep_kernel, grid, block, 0, stream, (const uint32_t*)w.vals2, (const uint8_t*)w.keep, n_in, n_dev, w.ext_keep);
+    TRY(grow_pinned(&w.h_ext_keep, w.h_ext_keep_cap, (size_t)n_ext));
+    hipLaunchKernelGGL(ext_keep_kernel, grid, dim3(256), 0, c.stream, (const uint32_t*)w.vals2, (const uint8_t*)w.keep, (uint32_t)n, n_dev, w.ext_keep);
     TRY(hipGetLastError());
-    TRY(hipMemcpyAsync(w.h_ext_keep, w.ext_keep, (size_t)n_ext, hipMemcpyDeviceToHost, stream));
-    TRY(hipStreamSynchronize(stream));
+    TRY(hipMemcpyAsync(w.h_ext_keep, w.ext_keep, (size_t)n_ext, hipMemcpyDeviceToHost, c.stream));
+    TRY(hipStreamSynchronize(c.stream));
     HitsExtRows made;
-    if (ext->rows_for(w.h_ext_keep, &made) != 0) return hipErrorUnknown;
-    TRY(upload_ext_rows(made));
+    if (c.ext->rows_for(w.h_ext_keep, &made) != 0) return hipErrorUnknown;
+    return upload_ext_rows(made);
   }
-  if (counts) {
-    // 4, counts mode: the table of the kept hits instead of their rows -- one launch, and the post the host waits for comes from it
-    MidArgs ca{};
-    ca.fin = d_final; ca.hits = w.hits; ca.guides = d_guides; ca.keep = w.keep; ca.order = w.vals2; ca.n = n_in; ca.n_dev = n_dev;
-    ca.n_rows = d_kept; ca.own_lo = ho.lo; ca.own_hi = ho.hi;
+
+  MidArgs mid_args() const {   // what the counts tail and the rows tail both give their kernels
+    MidArgs a{};
+    a.fin = c.d_final; a.hits = w.hits; a.guides = c.d_guides; a.keep = w.keep; a.order = w.vals2; a.n = (uint32_t)n; a.n_dev = n_dev;
+    a.n_rows = d_kept; a.own_lo = ho.lo; a.own_hi = ho.hi;
+    return a;
+  }
+
+  // 4, counts mode: the table of the kept hits instead of their rows -- one launch, and the post the host waits for comes from it.
+  hipError_t counts_tail() {
+    hipError_t e;
     TRY(mailbox_open(w.mbox));
     w.mbox.seq++;
-    hipLaunchKernelGGL(counts_kernel, dim3(counts_grid(n)), dim3(COUNTS_BLOCK), 0, stream, ca, co, w.d_counts, d_flags, w.mbox.dev, w.mbox.seq);
+    hipLaunchKernelGGL(counts_kernel, dim3(counts_grid(n)), dim3(COUNTS_BLOCK), 0, c.stream, mid_args(), co, w.d_counts, d_flags, w.mbox.dev, w.mbox.seq);
     TRY(hipGetLastError());
-    TRY(mailbox_wait(w.mbox, stream));
-    for (int k = 0; k < 3; k++) w.h_counts[k] = (uint64_t)w.mbox.host[1 + 2 * k] | ((uint64_t)w.mbox.host[2 + 2 * k] << 32);
+    TRY(mailbox_wait(w.mbox, c.stream));
+    counts_from_box(w.mbox, w.h_counts);
     res->flags = (uint32_t)w.h_counts[2];
     res->n_rows = (uint32_t)w.h_counts[1];
     return hipSuccess;
   }
-  // 4: rows
+
+  // 4: rows -- lengths, offsets and the post, then every row at its final place; once more when the text did not fit the buffer.
   // (a row with more padded columns than a wave has lanes raises HITS_FLAG_ROW and the caller finishes on the host)
-  const uint32_t n_max = (uint32_t)std::min<int>(MID_COLS, std::max(1, max_ops));
-  const uint32_t mid_bound = (6 * n_max + 128 + 3) & ~3u;
-  const uint32_t mid_lds = 4 * (MID_LINE + MID_FWD) + (uint32_t)((blob_bytes + 15) & ~(size_t)15);   // four waves' line buffers | constant strings
-  if (mid_lds > 64 * 1024) {   // beyond the default dynamic LDS limit (absurdly long parameter strings): decline
-    TRY(hipStreamSynchronize(stream));
-    res->flags = HITS_FLAG_ROW;
-    return hipSuccess;
-  }
-  const size_t n_pad = (n + 63) / 64 * 64;
-  TRY(grow(&w.midlen, w.midlen_cap, n_pad));
-  if (!w.text) TRY(grow(&w.text, w.text_cap, std::min<size_t>((size_t)32 << 20, n * (size_t)(mid_bound + rc.head_len + rc.tail_len + 64))));   // (first call: a guess)
-  MidArgs ma{};
-  ma.ref = ref; ma.rc = rc; ma.blob = w.blob; ma.name_off = w.name_off; ma.fin = d_final; ma.hits = w.hits; ma.guides = d_guides;
-  ma.keep = w.keep; ma.order = w.vals2; ma.n = n_in; ma.n_rows = d_kept; ma.n_dev = n_dev; ma.ext_off = w.ext_off; ma.ext_kept = d_kept + 1; ma.own_lo = ho.lo; ma.own_hi = ho.hi; ma.mid_bound = mid_bound; ma.n_max = n_max; ma.blob_bytes = (uint32_t)blob_bytes;
-  hipLaunchKernelGGL(len_kernel, grid, block, 0, stream, ma, w.midlen, w.lens, d_flags);
-  TRY(mailbox_open(w.mbox));
-  w.mbox.seq++;
-  w.mbox.host[HITS_BOX_LATE] = 0;                          // raised by rows_kernel while rows are written; read when the stream is done (hits_late)
-  if (small) {
-    hipLaunchKernelGGL(offs_small_kernel, dim3(1), dim3(HITS_SMALL), 0, stream, (const uint64_t*)w.lens, n_in, w.offs, w.d_counts, w.mbox.dev, w.mbox.seq);
-  } else {
-    ts = w.temp_cap;
-    TRY(rocprim::exclusive_scan(w.temp, ts, w.lens, w.offs, (uint64_t)0, n, rocprim::plus<uint64_t>(), stream));
-    hipLaunchKernelGGL(total_kernel, dim3(1), dim3(1), 0, stream, (const uint64_t*)w.offs, (const uint64_t*)w.lens, n_in, w.d_counts, w.mbox.dev, w.mbox.seq);
-  }
-  TRY(hipGetLastError());
-  // The rows kernel goes out at once, into the buffer as it is (sized by the last call's text: a search is usually followed by one like
-  // it): the host's look at the counts -- a round trip of 20-30 us -- is then off the lane's critical path, as in the binned tail.  A
-  // text that does not fit makes the kernel return untouched; the buffer grows and the kernel runs again.
-  OutArgs oa{};
-  oa.names = w.names; oa.offs = w.offs; oa.midlen = w.midlen; oa.ext_rows = ext_on_host ? nullptr : w.ext_rows; oa.late = w.mbox.dev + HITS_BOX_LATE;
-  if (ext_on_host) {
-    TRY(grow(&w.ext_place, w.ext_place_cap, (size_t)n_ext));
-    if ((size_t)n_ext > w.h_ext_place_cap) {
-      if (w.h_ext_place) (void)hipHostFree(w.h_ext_place);
-      w.h_ext_place = nullptr; w.h_ext_place_cap = 0;
-      const size_t cap = (size_t)n_ext + (size_t)n_ext / 4 + 4096;
-      TRY(hipHostMalloc((void**)&w.h_ext_place, cap * sizeof(uint64_t), hipHostMallocDefault));
-      w.h_ext_place_cap = cap;
+  hipError_t rows_tail() {
+    hipError_t e;
+    hipStream_t stream = c.stream;
+    const uint32_t n_in = (uint32_t)n;
+    const MidSize ms = mid_size(c.max_ops);
+    const uint32_t mid_lds = 4 * (MID_LINE + MID_FWD) + (uint32_t)((w.blob_bytes + 15) & ~(size_t)15);   // four waves' line buffers | constant strings
+    if (mid_lds > 64 * 1024) {   // beyond the default dynamic LDS limit (absurdly long parameter strings): decline
+      TRY(hipStreamSynchronize(stream));
+      res->flags = HITS_FLAG_ROW;
+      return hipSuccess;
     }
-    hipLaunchKernelGGL(ext_place_kernel, grid, block, 0, stream, (const uint32_t*)w.vals2, (const uint32_t*)w.midlen, (const uint64_t*)w.offs, n_in, n_dev, w.ext_place);
+    TRY(grow(&w.midlen, w.midlen_cap, (n + 63) / 64 * 64));
+    if (!w.text) TRY(grow(&w.text, w.text_cap, std::min<size_t>((size_t)32 << 20, n * (size_t)(ms.mid_bound + w.rc.head_len + w.rc.tail_len + 64))));   // (first call: a guess)
+    MidArgs ma = mid_args();
+    ma.ref = c.ref; ma.rc = w.rc; ma.blob = w.blob; ma.name_off = w.name_off; ma.ext_off = w.ext_off; ma.ext_kept = d_kept + 1;
+    ma.mid_bound = ms.mid_bound; ma.n_max = ms.n_max; ma.blob_bytes = (uint32_t)w.blob_bytes;
+    hipLaunchKernelGGL(len_kernel, grid, dim3(256), 0, stream, ma, w.midlen, w.lens, d_flags);
+    TRY(mailbox_open(w.mbox));
+    w.mbox.seq++;
+    w.mbox.host[HITS_BOX_LATE] = 0;                          // raised by rows_kernel while rows are written; read when the stream is done (hits_late)
+    if (small) {
+      hipLaunchKernelGGL(offs_small_kernel, dim3(1), dim3(HITS_SMALL), 0, stream, (const uint64_t*)w.lens, n_in, w.offs, w.d_counts, w.mbox.dev, w.mbox.seq);
+    } else {
+      size_t ts = w.temp_cap;
+      TRY(rocprim::exclusive_scan(w.temp, ts, w.lens, w.offs, (uint64_t)0, n, rocprim::plus<uint64_t>(), stream));
+      hipLaunchKernelGGL(total_kernel, dim3(1), dim3(1), 0, stream, (const uint64_t*)w.offs, (const uint64_t*)w.lens, n_in, w.d_counts, w.mbox.dev, w.mbox.seq);
+    }
     TRY(hipGetLastError());
-    TRY(hipMemcpyAsync(w.h_ext_place, w.ext_place, (size_t)n_ext * sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
-  }
-  oa.counts = w.d_counts;
-  const unsigned rows_per_block = 4 * ROWS_PER_WAVE;
-  const dim3 rows_grid((n_in + rows_per_block - 1) / rows_per_block);
-  oa.text_cap = w.text_cap;
-  hipLaunchKernelGGL(rows_kernel, rows_grid, dim3(256), mid_lds, stream, ma, oa, w.text);
-  TRY(hipGetLastError());
-  TRY(mailbox_wait(w.mbox, stream));
-  for (int k = 0; k < 3; k++) w.h_counts[k] = (uint64_t)w.mbox.host[1 + 2 * k] | ((uint64_t)w.mbox.host[2 + 2 * k] << 32);
-  TRY(hipGetLastError());
-  res->flags = (uint32_t)w.h_counts[2];
-  if (res->flags) return hipSuccess;
-  res->n_rows = (uint32_t)w.h_counts[1];
-  if (ext && ext->kept) *ext->kept = (uint32_t)(w.h_counts[1] >> 32);
-  res->text_bytes = w.h_counts[0];
-  if (res->text_bytes > oa.text_cap) {                       // the kernel returned at once: a buffer of the right size (and some more), again
-    TRY(hipStreamSynchronize(stream));
-    TRY(grow(&w.text, w.text_cap, (size_t)res->text_bytes + (size_t)(res->text_bytes / 8) + 4096));
+    // The rows kernel goes out at once, into the buffer as it is (sized by the last call's text: a search is usually followed by one like
+    // it): the host's look at the counts -- a round trip of 20-30 us -- is then off the lane's critical path, as in the binned tail.  A
+    // text that does not fit makes the kernel return untouched; the buffer grows and the kernel runs again.
+    OutArgs oa{};
+    oa.names = w.names; oa.offs = w.offs; oa.midlen = w.midlen; oa.ext_rows = ext_on_host ? nullptr : w.ext_rows; oa.late = w.mbox.dev + HITS_BOX_LATE;
+    if (ext_on_host) {
+      TRY(grow(&w.ext_place, w.ext_place_cap, (size_t)n_ext));
+      TRY(grow_pinned(&w.h_ext_place, w.h_ext_place_cap, (size_t)n_ext));
+      hipLaunchKernelGGL(ext_place_kernel, grid, dim3(256), 0, stream, (const uint32_t*)w.vals2, (const uint32_t*)w.midlen, (const uint64_t*)w.offs, n_in, n_dev, w.ext_place);
+      TRY(hipGetLastError());
+      TRY(hipMemcpyAsync(w.h_ext_place, w.ext_place, (size_t)n_ext * sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
+    }
+    oa.counts = w.d_counts;
+    const dim3 rows_grid((n_in + 4 * ROWS_PER_WAVE - 1) / (4 * ROWS_PER_WAVE));
     oa.text_cap = w.text_cap;
     hipLaunchKernelGGL(rows_kernel, rows_grid, dim3(256), mid_lds, stream, ma, oa, w.text);
     TRY(hipGetLastError());
+    TRY(mailbox_wait(w.mbox, stream));
+    counts_from_box(w.mbox, w.h_counts);
+    TRY(hipGetLastError());
+    res->flags = (uint32_t)w.h_counts[2];
+    if (res->flags) return hipSuccess;
+    res->n_rows = (uint32_t)w.h_counts[1];
+    if (c.ext && c.ext->kept) *c.ext->kept = (uint32_t)(w.h_counts[1] >> 32);
+    res->text_bytes = w.h_counts[0];
+    if (res->text_bytes > oa.text_cap) {                       // the kernel returned at once: a buffer of the right size (and some more), again
+      TRY(hipStreamSynchronize(stream));
+      TRY(grow(&w.text, w.text_cap, (size_t)res->text_bytes + (size_t)(res->text_bytes / 8) + 4096));
+      oa.text_cap = w.text_cap;
+      hipLaunchKernelGGL(rows_kernel, rows_grid, dim3(256), mid_lds, stream, ma, oa, w.text);
+      TRY(hipGetLastError());
+    }
+    res->d_text = w.text;
+    res->ext_place = ext_on_host ? w.h_ext_place : nullptr;
+    return hipSuccess;
   }
-  res->d_text = w.text;
-  res->ext_place = ext_on_host ? w.h_ext_place : nullptr;
-  return hipSuccess;
+};
+
+}  // namespace
+
+hipError_t hits_run(HitsWork** pw, const HitsRunCall& c, HitsResult* res) {
+  if (!*pw) *pw = new HitsWork();
+  HitsWork& w = **pw;
+  hipError_t e;
+  *res = HitsResult{};
+  const uint32_t n_ext = c.ext ? c.ext->n : 0;
+  if (c.counts && n_ext) return hipErrorInvalidValue;    // (a table of the reference's own hits)
+  if (c.ext && c.ext->kept) *c.ext->kept = 0;
+  if ((uint64_t)c.n + n_ext > 0xFFFFFFF0ull) { res->flags = HITS_FLAG_CLUSTER; return hipSuccess; }
+  const size_t n = (size_t)c.n + n_ext;
+  CountsOut co{};
+  if (c.counts) {
+    TRY(counts_buffers(w, *c.counts, &co));
+    if (n == 0) std::memset(co.host, 0, (size_t)co.cells * sizeof(unsigned long long));
+    res->counts = reinterpret_cast<const uint64_t*>(co.host);
+  }
+  if (n == 0) return hipSuccess;
+  if (!w.prepared) TRY(hits_prepare(pw, *c.strings, c.stream));   // normally done at the start of the call
+  w.prepared = false;
+  HitsRun run(w, c, res, co);
+  TRY(run.size_buffers());
+  if (run.on_demand && c.own) return hipErrorInvalidValue;
+  TRY(run.order_and_walk());
+  if (run.on_demand) TRY(run.ext_rows_on_demand());
+  return c.counts ? run.counts_tail() : run.rows_tail();
 }
 
 #undef TRY

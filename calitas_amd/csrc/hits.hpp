@@ -134,10 +134,12 @@ struct HitsExtSource { std::function<int(int contig, const HitsExt** ext)> get; 
 // from a count among neighbouring windows), or 0 for the general sort (crowded windows).  On success the rows are at res->d_text in
 // final order.  counts: no rows -- counts_kernel takes the place of the row kernels behind the walks and res->counts is the table of the
 // kept (and owned) hits; still one host round trip.
-hipError_t hits_run(HitsWork** work, const HitsRef& ref, const RawAln* d_final, uint32_t n, const GuideDev* d_guides,
-                    const uint64_t* d_win_base, const int2* d_win, const RowStrings& strings, int max_overlap, int score_hi,
-                    int max_ops, uint32_t window_reach, hipStream_t stream, HitsResult* res, const HitsExt* ext = nullptr,
-                    const HitsOwn* own = nullptr, const CountsShape* counts = nullptr);
+struct HitsRunCall {
+  HitsRef ref; const RawAln* d_final; uint32_t n; const GuideDev* d_guides; const uint64_t* d_win_base; const int2* d_win;
+  const RowStrings* strings; int max_overlap, score_hi, max_ops; uint32_t window_reach; hipStream_t stream;
+  const HitsExt* ext = nullptr; const HitsOwn* own = nullptr; const CountsShape* counts = nullptr;   // optional
+};
+hipError_t hits_run(HitsWork** work, const HitsRunCall& call, HitsResult* res);
 // Flags raised while the rows of the last hits_run were being written (HITS_FLAG_INTERNAL); valid once the stream the rows kernel ran
 // on is done.
 uint32_t hits_late(const HitsWork* work);

@@ -1,5 +1,6 @@
 // hits_dev.hpp -- device code and scratch shared by hits.hip (the general removeOverlaps / sort / rows kernels) and binned.hip (the
-// same stages fused per reference bin): the hit record, its coordinates, and the wave-per-row builder of a hits.txt row's middle part.
+// same stages fused per reference bin): the hit record, its coordinates, the ownership key and ReferenceHit.sort's comparison, a row's
+// length, the wave-per-row builder of a hits.txt row's middle part and the copy-out of the finished row.
 // Private to those two translation units (everything sits in an anonymous namespace there).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -77,16 +78,21 @@ __device__ __forceinline__ void hit_body(const uint32_t i, const RawAln* fin, co
 
 constexpr int HIT_MAX_LEN = CALITAS_MAX_OPS;   // a hit covers at most this many reference bases (ReferenceHit.end - start + 1)
 
+// What HitsOwn / BinnedParams hold a hit against: (contig << 32 | coordinate_start), owned when it lies in [own_lo, own_hi).
+__device__ __forceinline__ unsigned long long own_key(uint32_t contig, int32_t gstart) { return ((unsigned long long)contig << 32) | (uint32_t)gstart; }
+
+// ReferenceHit.sort (RH:284) between two hits of one contig: does (gs, mi, sc) = (start, strand, score) come before hit h -- start and
+// strand ascending, score descending --, or is it the same key?  (The counting sorts of binned.hip; arrival order breaks the tie there.)
+struct SortCmp { bool less, same; };
+__device__ __forceinline__ SortCmp sort_cmp(int gs, uint32_t mi, int sc, int h_gs, uint32_t h_mi, int h_sc) {
+  return SortCmp{gs < h_gs || (gs == h_gs && (mi < h_mi || (mi == h_mi && sc > h_sc))), gs == h_gs && mi == h_mi && sc == h_sc};
+}
+
 // ---- rows ------------------------------------------------------------------------------------------------------------
-// A row is  head | chromosome \t | middle | tail  where head and tail are the same for every row of the call.
-//   mid_kernel: one *wave* per row builds the middle part: lane i owns padded column i of the alignment (op, query, target and
-//               alignment characters; the counts of GuideAlignment are popcounts of wave ballots), lane f owns field f's length and
-//               -- for the numeric fields -- its digits; a prefix sum over the 25 field lengths places every field in the wave's
-//               line buffer, which is copied to a fixed-stride staging buffer with coalesced dword stores.
-//   out_kernel: after the exclusive scan of the lengths, a wave assembles row after row at its final offset with
-//               coalesced byte stores (head / tail come from LDS).
-// (The first version ran one lane per row with its working arrays in a 560-byte LDS slot: 36 KB per single-wave workgroup, each of
-// which kept a four-wave workgroup of the next range's scan off its CU, and a 100 us chain of dependent LDS round trips -- DESIGN.md 4.4.)
+// A row is  head | chromosome \t | middle | tail  where head and tail are the same for every row of the call.  One *wave* per row:
+// build_middle lays the middle part out in the wave's LDS line (lane i owns padded column i of the alignment, lane f field f's length and
+// digits), write_row copies the four pieces to the row's final place with coalesced byte stores; middle_length is build_middle's
+// arithmetic for one lane, for the kernels that place the rows before they are built (DESIGN.md 4.4 has the history).
 
 __device__ __forceinline__ char comp_base(char c) {   // fgbio Sequences.complement on an upper-case base
   switch (c) {
@@ -323,14 +329,79 @@ __device__ __forceinline__ int build_middle(uint8_t* line, uint8_t* fwd, const M
   return total;
 }
 
+// The RowIn of an alignment and the RowGuide of its guide: scalar loads.
+__device__ __forceinline__ RowIn load_row_in(const RawAln* p) {
+  const auto* rp = uniform_ptr(p);
+  RowIn r;
+  const auto* ow = (const __attribute__((address_space(4))) uint32_t*)rp->ops;   // RawAln::ops sits at a 4-byte aligned offset
+  r.w0 = ow[0]; r.w1 = ow[1]; r.w2 = ow[2]; r.w3 = ow[3]; r.w4 = ow[4];
+  r.n_ops = rp->n_ops; r.pam = rp->pam; r.offset = rp->offset; r.pam_x = rp->pam_x;
+  return r;
+}
+__device__ __forceinline__ RowGuide row_guide(const GuideDev* p, int pam) {
+  const auto* gp = uniform_ptr(p);
+  return RowGuide{gp->L, gp->pam5, pam >= 0 ? gp->pam_len[pam] : 0};
+}
+
+// A row's middle part in the wave's line buffer, held against the length `want` its sizing kernel computed for it.  The two cannot
+// differ (both run the same arithmetic); if they do, `flag` is raised in the mailbox word `late` and the row must not be written: -1.
+__device__ __forceinline__ int checked_middle(uint8_t* line, uint8_t* fwd, const MidArgs& a, const uint8_t* blob, const RowIn& r, const HitRec& h,
+                                              const RowGuide& g, const int lane, uint32_t want, uint32_t* late, uint32_t flag) {
+  wave_lds_sync();                                        // the copy-out of the previous row is done with line[]
+  const int len = build_middle<true>(line, fwd, a, blob, r, h, g, lane);
+  if (len < 0 || (uint32_t)len != want) {
+    if (lane == 0) __hip_atomic_fetch_or(late, flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    return -1;
+  }
+  wave_lds_sync();
+  return len;
+}
+
+// head | chromosome \t | middle | tail at dst, by the 64 lanes of a wave: line[0..len) is the middle part, head and tail lie in `blob`.
+// Returns the row's length (row_length of the same row).
+__device__ __forceinline__ uint32_t write_row(char* dst, const uint8_t* line, uint32_t len, int32_t contig, const RowConstDev& rc, const uint8_t* blob,
+                                              const char* names, const uint32_t* name_off, const int lane) {
+  const uint8_t* head = blob + rc.head_off;
+  const uint8_t* tail = blob + rc.tail_off;
+  const uint32_t nb = uniform_ptr(name_off)[contig], nl = uniform_ptr(name_off)[contig + 1] - nb;
+  const uint32_t s0 = rc.head_len, s1 = s0 + nl + 1, s2 = s1 + len, total = s2 + rc.tail_len;
+  for (uint32_t x = (uint32_t)lane; x < total; x += 64) {
+    uint8_t ch;
+    if (x < s0) ch = head[x];
+    else if (x < s1) ch = (x - s0 < nl) ? (uint8_t)names[nb + x - s0] : (uint8_t)'\t';
+    else if (x < s2) ch = line[x - s1];
+    else ch = tail[x - s2];
+    dst[x] = (char)ch;
+  }
+  return total;
+}
+
+// Device scratch of at least `need` elements: a quarter more than asked for, or exactly that (slack = false: sized by the reference, not the call).
 template <typename T>
-hipError_t grow(T** p, size_t& cap, size_t need) {
+hipError_t grow(T** p, size_t& cap, size_t need, bool slack = true) {
   if (need <= cap) return hipSuccess;
   (void)hipFree(*p); *p = nullptr; cap = 0;
-  need += need / 4;
+  if (slack) need += need / 4;
   hipError_t e = hipMalloc((void**)p, need * sizeof(T));
   if (e == hipSuccess) cap = need;
   return e;
+}
+// The same in page-locked host memory.
+template <typename T>
+hipError_t grow_pinned(T** p, size_t& cap, size_t need) {
+  if (need <= cap) return hipSuccess;
+  if (*p) (void)hipHostFree(*p);
+  *p = nullptr; cap = 0; need += need / 4 + 4096;
+  hipError_t e = hipHostMalloc((void**)p, need * sizeof(T), hipHostMallocDefault);
+  if (e == hipSuccess) cap = need;
+  return e;
+}
+
+// MidArgs::n_max and MidArgs::mid_bound of a search whose alignments have at most max_ops padded columns.
+struct MidSize { uint32_t n_max, mid_bound; };
+inline MidSize mid_size(int max_ops) {
+  const uint32_t n_max = (uint32_t)std::min<int>(MID_COLS, std::max(1, max_ops));
+  return MidSize{n_max, (6 * n_max + 128 + 3) & ~3u};
 }
 
 
@@ -351,8 +422,10 @@ __device__ __forceinline__ HitKey hit_key(const OpCounts& oc, int pam, int offse
 
 // Length of the middle part of a row = what build_middle computes with ballots, for one lane: the field lengths of RH:210-254 from
 // the alignment's op counts (GA:99-115, 139-183) and the run-length encoding of its cigar.  -1: the row builder does not lay it out.
-__device__ __forceinline__ int middle_length(const RawAln* rp, const HitRec& h, int L, int pam_len, int pu_len, int n_max, int mid_bound) {
+__device__ __forceinline__ int middle_length(const MidArgs& a, const RawAln* rp, const HitRec& h) {
+  const GuideDev* gp = a.guides + rp->guide;
   const int ng = rp->n_ops, pam = rp->pam;
+  const int L = gp->L, pam_len = pam >= 0 ? gp->pam_len[pam] : 0, pu_len = (int)a.rc.pu_len[pam + 1], n_max = (int)a.n_max, mid_bound = (int)a.mid_bound;
   const int gap = pam >= 0 ? rp->offset : 0;
   const uint32_t pam_x = rp->pam_x;
   const int n = ng + gap + pam_len;
@@ -382,6 +455,11 @@ __device__ __forceinline__ int middle_length(const RawAln* rp, const HitRec& h, 
   const int total = MID_FIELDS + digits(h.gstart) + digits(h.gend) + 1 + utn + 10 + 10 + pu_len + digits(h.score) + digits(gmm) + digits(ggp) +
                     digits(gmm + ggp) + digits(pam_mm) + digits(edits) + 3 * n + 8 + 8 + cigar_len + digits(L) + digits(utn);
   return total > mid_bound ? -1 : total;
+}
+
+// The length of the whole row around a middle part of middle_len bytes -- what write_row returns for it.
+__device__ __forceinline__ uint32_t row_length(const RowConstDev& rc, const uint32_t* name_off, int32_t contig, uint32_t middle_len) {
+  return rc.head_len + (name_off[contig + 1] - name_off[contig]) + 1 + middle_len + rc.tail_len;
 }
 
 // ---- the off-target table (calitas_search_counts) ---------------------------------------------------------------------------------

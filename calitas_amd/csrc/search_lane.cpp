@@ -314,20 +314,18 @@ static int lane_rows_binned(calitas_ctx* lane, const SearchPlan& pl, bool prelau
   binned_fill_align_args(lane->binned, geo, aa);
   // (no events on these dispatches: each would hold back the kernel behind it by ~5 us; the kernels stamp the device's wall clock instead)
   HIP_TRY(lane, launch_align_trace(pl, aa, lane->stream, nullptr));
-  HIP_TRY(lane, binned_run(lane->binned, &lane->hits, geo, hr, lane->d_raw, lane->d_guides, own->d_win_base, own->d_win, bp, lane->d_counters, lane->stream,
-                           &lane->mbox, nullptr, nullptr, lane->ev[5], dest == nullptr && !pl.counts));
+  const BinnedCall bc{lane->binned, &lane->hits, geo, hr, lane->d_raw, lane->d_guides, own->d_win_base, own->d_win, bp, lane->d_counters, lane->stream, &lane->mbox};
+  HIP_TRY(lane, binned_run(bc, nullptr, nullptr, lane->ev[5], dest == nullptr && !pl.counts));
   char* host_dst = nullptr;
   uint64_t host_dst_cap = 0;
   if (pl.counts) {
     // the table instead of rows: bin_counts_kernel where the rows kernel would go, with the same post behind it
-    HIP_TRY(lane, binned_counts(lane->binned, &lane->hits, geo, hr, lane->d_raw, lane->d_guides, own->d_win_base, own->d_win, bp, lane->d_counters, lane->stream,
-                                &lane->mbox, lane->ev[5], pl.cshape));
+    HIP_TRY(lane, binned_counts(bc, lane->ev[5], pl.cshape));
   } else if (dest) {
     // the rows kernel goes out once the text's final place is known (the byte counts of the ranges before this one: their row kernels
     // have started by then) and writes there itself -- no copy behind it
     if (!dest->get(&host_dst, &host_dst_cap)) { host_dst = nullptr; host_dst_cap = 0; }
-    HIP_TRY(lane, binned_rows(lane->binned, &lane->hits, geo, hr, lane->d_raw, lane->d_guides, own->d_win_base, own->d_win, bp, lane->d_counters, lane->stream,
-                              &lane->mbox, lane->ev[5], host_dst, host_dst_cap));
+    HIP_TRY(lane, binned_rows(bc, lane->ev[5], host_dst, host_dst_cap));
   }
   lane->rows_ev0 = -1;                                       // (the row stage's time: binned_rows_ms)
   g_marks.mark("queued-binned");
@@ -359,8 +357,7 @@ static int lane_rows_binned(calitas_ctx* lane, const SearchPlan& pl, bool prelau
     if (sum != lane->mbox.host[BIN_BOX_ROWS]) return fail(lane, CALITAS_EHIP, "binned counts kernel: the table does not add up to the bins' kept hits (internal error)");
   }
   if (flags & BIN_FLAG_TEXT) {                               // the text buffer was a guess: grow it, the rows kernel once more
-    HIP_TRY(lane, binned_rerun_rows(lane->binned, &lane->hits, geo, hr, lane->d_raw, lane->d_guides, own->d_win_base, own->d_win, bp, lane->d_counters, bytes,
-                                    lane->stream, &lane->mbox, lane->ev[5]));
+    HIP_TRY(lane, binned_rerun_rows(bc, bytes, lane->ev[5]));
     HIP_TRY(lane, mailbox_wait(lane->mbox, lane->stream));
     flags = lane->mbox.host[BIN_BOX_FLAGS];
     if (flags) return fail(lane, CALITAS_EHIP, "binned rows kernel: flags " + std::to_string(flags) + " after the text buffer was grown (internal error)");
@@ -466,9 +463,12 @@ int lane_rows(calitas_ctx* lane, const SearchPlan& pl, bool prelaunched, const R
       }
       HIP_TRY(lane, hipEventRecord(lane->ev[4], lane->stream));
       lane->rows_ev0 = 4;
-      HIP_TRY(lane, hits_run(&lane->hits, hr, dev.d_final, dev.n_sel, lane->d_guides, own->d_win_base, own->d_win, rs, p.max_overlap, score_hi,
-                             widest_hit(pl, max_pam), dev.crowded ? 0u : (uint32_t)((p.window_size + pl.step - 1) / pl.step),
-                             lane->stream, &res, ext, own_general ? &ho : nullptr, pl.counts ? &pl.cshape : nullptr));
+      HitsRunCall hc{};
+      hc.ref = hr; hc.d_final = dev.d_final; hc.n = dev.n_sel; hc.d_guides = lane->d_guides; hc.d_win_base = own->d_win_base; hc.d_win = own->d_win;
+      hc.strings = &rs; hc.max_overlap = p.max_overlap; hc.score_hi = score_hi; hc.max_ops = widest_hit(pl, max_pam);
+      hc.window_reach = dev.crowded ? 0u : (uint32_t)((p.window_size + pl.step - 1) / pl.step); hc.stream = lane->stream;
+      hc.ext = ext; hc.own = own_general ? &ho : nullptr; hc.counts = pl.counts ? &pl.cshape : nullptr;
+      HIP_TRY(lane, hits_run(&lane->hits, hc, &res));
       HIP_TRY(lane, hipEventRecord(lane->ev[5], lane->stream));
       g_marks.mark("rows-queued");
       kernel_times(lane, lt.tm);          // while out_kernel runs

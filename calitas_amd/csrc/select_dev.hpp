@@ -25,16 +25,13 @@ __device__ __forceinline__ unsigned long long order_key(const Derived& d) {
          ((unsigned long long)(0xFFFFu - d.gaps) << 24) | ((unsigned long long)(0x7FFFFu - (d.ekey & 0x7FFFFu)) << 1) | 1ull;
 }
 
-// What the filter looks at, from one raw alignment.
-__device__ __forceinline__ Derived derive(const RawAln* rp, const GuideDev* guides, const uint64_t* win_base, const int2* win, uint32_t window_lo,
-                                          uint32_t windows_per_guide) {
-  const uint32_t contig = rp->contig, window_k = rp->window_k, guide = rp->guide;
+// What the filter looks at, from one raw alignment: its window is `w` (the window table's entry), widx in the caller's numbering.
+__device__ __forceinline__ Derived derive_in_window(const RawAln* rp, const GuideDev* guides, const int2 w, uint32_t widx) {
+  const uint32_t guide = rp->guide;
   const int pam = rp->pam, offset = rp->offset, n_ops = rp->n_ops, dir = rp->dir;
   const OpCounts oc = count_ops(load_ops_words(rp->ops), n_ops);
   int diffs = oc.non_eq, gaps = oc.gaps, pam_len = 0;
   if (pam >= 0) { pam_len = guides[guide].pam_len[pam]; diffs += offset + __popc((unsigned)rp->pam_x); gaps += offset; }
-  const uint64_t wi = win_base[contig] + window_k;
-  const int2 w = win[wi];
   const int start_s = (int)rp->t_start - 1, end_s = (int)rp->t_end_guide + offset + pam_len;
   Derived d;
   if (dir == 0) { d.start = w.x + start_s; d.end = w.x + end_s; }
@@ -43,8 +40,21 @@ __device__ __forceinline__ Derived derive(const RawAln* rp, const GuideDev* guid
   const uint32_t pam5 = guides[guide].pam5;
   const uint32_t list = pam5 ? (dir == 1 ? 0u : 1u) : (dir == 0 ? 0u : 1u);   // 0 = forward-strand list (SGA:316)
   d.ekey = (list << 19) | ((uint32_t)rp->t_end_guide << 6) | ((uint32_t)rp->pad << 4) | (uint32_t)(pam + 1);
-  d.widx = guide * windows_per_guide + ((uint32_t)wi - window_lo);
+  d.widx = widx;
   return d;
+}
+
+// select.hip: any contig's alignment; widx counts the windows of the call's range, guide by guide.
+__device__ __forceinline__ Derived derive(const RawAln* rp, const GuideDev* guides, const uint64_t* win_base, const int2* win, uint32_t window_lo,
+                                          uint32_t windows_per_guide) {
+  const uint64_t wi = win_base[rp->contig] + rp->window_k;
+  return derive_in_window(rp, guides, win[wi], rp->guide * windows_per_guide + ((uint32_t)wi - window_lo));
+}
+
+// binned.hip: the contig is the bin's and its windows start at wbase (no dependent load of win_base[contig]); widx = the table's index.
+__device__ __forceinline__ Derived derive_in_contig(const RawAln* rp, const GuideDev* guides, uint32_t wbase, const int2* win) {
+  const uint32_t wi = wbase + rp->window_k;
+  return derive_in_window(rp, guides, win[wi], wi);
 }
 
 // 64-bit wave maximum (all lanes get it)

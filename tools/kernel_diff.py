@@ -1,14 +1,16 @@
 #!/usr/bin/env python3
-"""Generated-code comparison of the stage units (scan_columns / align / trace / mailbox / setup .hip) against kernels.hip of an earlier
-revision, which they replaced: the check that a move or a refactor of device code left the compiler's output as it was.
+"""Generated-code comparison of the device units (the stage units scan_columns / align / trace / mailbox / setup .hip, which replaced
+kernels.hip, and select / hits / binned .hip) against an earlier revision: the check that a move or a refactor of device code left the
+compiler's output as it was.
 
   python tools/kernel_diff.py [--rev HEAD~1] [--show]
 
-1. `git archive REV calitas_amd/csrc` into a temporary directory; every .hip file of the list below that exists there (kernels.hip
+1. `git archive REV calitas_amd/csrc include` into a temporary directory; every .hip file of the list below that exists there (kernels.hip
    before the split) and every one of the working tree is compiled with
    `hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC --cuda-device-only -S` (the flags of the Makefile).
 2. Every function of the output (the kernels, and replay_word, which the compiler keeps out of line) is cut from its label to
-   .Lfunc_end; comments, directives and the function's index in the labels (.LBB<k>_<n>) are dropped.
+   .Lfunc_end; comments, directives and the function's index in the labels (.LBB<k>_<n>) are dropped.  rocPRIM's own kernels (the
+   sort and the scan hits.hip and select.hip instantiate: mangled names beginning _ZN7rocprim) are skipped.
 3. Per kernel: identical or not; VGPRs, SGPRs, LDS bytes and scratch of both; the instruction count of every innermost loop that
    shifts values down the lanes (`wave_shr:1`: the fill loops of the aligners), and whether those loops differ in more than the
    numbers of their registers.  --show prints the unified diff of a kernel that
@@ -24,7 +26,7 @@ import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join("calitas_amd", "csrc")
-UNITS = ["kernels.hip", "scan_columns.hip", "align.hip", "trace.hip", "mailbox.hip", "setup.hip"]
+UNITS = ["kernels.hip", "scan_columns.hip", "align.hip", "trace.hip", "mailbox.hip", "setup.hip", "select.hip", "hits.hip", "binned.hip"]
 
 
 def device_asm(csrc, out_dir):
@@ -47,7 +49,7 @@ def functions_of(asm):
     i = 0
     while i < len(lines):
         m = re.match(r"^(_Z\w+):", lines[i])
-        if not m:
+        if not m or m.group(1).startswith("_ZN7rocprim"):     # (rocPRIM's: hundreds of kernels, and variables that end in no .Lfunc_end)
             i += 1
             continue
         name, raw = m.group(1), []
@@ -100,7 +102,7 @@ def lane_shift_loops(raw):
 
 def short(name):
     try:
-        return subprocess.check_output(["c++filt", name], text=True).strip().split("(")[0].replace("calitas::", "").replace("void ", "")
+        return subprocess.check_output(["c++filt", name], text=True).strip().replace("(anonymous namespace)::", "").split("(")[0].replace("calitas::", "").replace("void ", "")
     except (OSError, subprocess.CalledProcessError):
         return name
 
@@ -113,7 +115,7 @@ def main():
     with tempfile.TemporaryDirectory() as d:
         os.makedirs(os.path.join(d, "old"))
         os.makedirs(os.path.join(d, "new"))
-        tar = subprocess.Popen(["git", "-C", ROOT, "archive", a.rev, CSRC], stdout=subprocess.PIPE)
+        tar = subprocess.Popen(["git", "-C", ROOT, "archive", a.rev, CSRC, "include"], stdout=subprocess.PIPE)
         subprocess.check_call(["tar", "-x", "-C", os.path.join(d, "old")], stdin=tar.stdout)
         if tar.wait() != 0:
             sys.exit("kernel_diff: git archive %s failed" % a.rev)
