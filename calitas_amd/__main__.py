@@ -1,11 +1,11 @@
-"""`python -m calitas_amd <Tool> [flags]` -- the reference's four tools (Main.scala; flags as in SearchReference.scala:452-470,
+"""`python -m calitas_amd <Tool> [flags]` -- FindGuides (this project's own: tools.find_guides_tool) and the reference's four tools (Main.scala; flags as in SearchReference.scala:452-470,
 AlignToReference.scala:34-51, PairwiseAlignSequences.scala:25-33, PrepareVcf.scala:32-36) on the MI355X path.
 `-t/--threads` is accepted and ignored: the GPU replaces the thread pool."""
 import argparse
 import sys
 
 from .aligner import Defaults, SearchReference
-from .tools import align_to_reference, pairwise_align_sequences
+from .tools import align_to_reference, find_guides_tool, pairwise_align_sequences
 from .variants import prepare_vcf
 
 
@@ -60,6 +60,23 @@ def main(argv=None):
     pas.add_argument("-O", "--max-overlap", type=int, default=Defaults.MaxOverlap)   # declared and unused by the reference as well
     _costs(pas)
 
+    fg = sub.add_parser("FindGuides", help="the guides a region offers: exact sites of an IUPAC pattern such as NNNNNNNNNNNNNNNNNNNNnrg")
+    fg.add_argument("-i", "--guide", required=True, help="the pattern: IUPAC protospacer in upper case, PAM in lower case at either end")
+    fg.add_argument("-x", "--auxiliary-pams", nargs="*", default=[])
+    fg.add_argument("-r", "--ref", required=True)
+    fg.add_argument("-c", "--chrom")
+    fg.add_argument("-s", "--start", type=int, default=0, help="0-based first base of the region")
+    fg.add_argument("-e", "--end", type=int, help="0-based end of the region, exclusive (default: the contig's end)")
+    fg.add_argument("-o", "--output")
+    fg.add_argument("--counts", action="store_true",
+                    help="search every distinct guide of the table (the flags below) and add hits, hits_mm0 .. hits_mmE per row")
+    fg.add_argument("-d", "--max-guide-diffs", type=int, default=Defaults.MaxGuideDiffs)
+    fg.add_argument("-p", "--max-pam-mismatches", type=int, default=Defaults.MaxPamMismatches)
+    fg.add_argument("-g", "--max-gaps-between-guide-and-pam", type=int, default=Defaults.MaxGapsBetweenGuideAndPam)
+    fg.add_argument("-D", "--max-total-diffs", type=int)
+    fg.add_argument("-O", "--max-overlap", type=int, default=Defaults.MaxOverlap)
+    _costs(fg)
+
     pv = sub.add_parser("PrepareVcf")
     pv.add_argument("-i", "--input", nargs="+", required=True)
     pv.add_argument("-o", "--output", required=True)
@@ -82,6 +99,15 @@ def main(argv=None):
                                   max_total_diffs=a.max_total_diffs, max_overlap=a.max_overlap,
                                   guide_mismatch_net_cost=a.guide_mismatch_net_cost, pam_mismatch_net_cost=a.pam_mismatch_net_cost,
                                   genome_gap_net_cost=a.genome_gap_net_cost, guide_gap_net_cost=a.guide_gap_net_cost, device=a.device)
+        if a.output is None:
+            sys.stdout.write(text)
+    elif a.tool == "FindGuides":
+        text = find_guides_tool(a.ref, a.guide, a.auxiliary_pams, chrom=a.chrom, start=a.start, end=a.end, output=a.output, counts=a.counts,
+                                device=a.device, max_guide_diffs=a.max_guide_diffs, max_pam_mismatches=a.max_pam_mismatches,
+                                max_gaps_between_guide_and_pam=a.max_gaps_between_guide_and_pam, max_total_diffs=a.max_total_diffs,
+                                max_overlap=a.max_overlap, guide_mismatch_net_cost=a.guide_mismatch_net_cost,
+                                pam_mismatch_net_cost=a.pam_mismatch_net_cost, genome_gap_net_cost=a.genome_gap_net_cost,
+                                guide_gap_net_cost=a.guide_gap_net_cost)
         if a.output is None:
             sys.stdout.write(text)
     elif a.tool == "PairwiseAlignSequences":

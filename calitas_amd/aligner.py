@@ -10,7 +10,7 @@ import ctypes
 import time
 
 from . import _lib
-from ._lib import AlnT, CalitasError, CountsT, GuideT, ParamsT, TimingT, lib
+from ._lib import AlnT, CalitasError, CountsT, GuideT, ParamsT, SiteT, TimingT, lib
 
 
 class Defaults:  # SequentialGuideAligner.scala:17-28
@@ -488,6 +488,51 @@ class Context:
         _lib.check(self._h, lib.calitas_hits_counts(self._h, ctypes.byref(g), ctypes.byref(params), arr, n, ctypes.byref(out)))
         return self._take_counts(out)
 
+    def _site_region(self, pattern, chrom, start, end):
+        if not isinstance(pattern, Guide):
+            pattern = Guide(pattern)
+        if chrom is None:
+            index = -1
+        elif isinstance(chrom, str):
+            if chrom not in self.contig_names:
+                raise ValueError("Unknown chromosome: %s" % chrom)
+            index = self.contig_names.index(chrom)
+        else:
+            index = int(chrom)
+        return pattern, index, int(start), 0 if end is None else int(end)
+
+    def find_sites(self, pattern, chrom=None, start=0, end=None, host=False):
+        """calitas_find_sites: every place of the region where a guide of the IUPAC `pattern` (a Guide or its `-i` string, e.g.
+        "NNNNNNNNNNNNNNNNNNNNnrg"; aux PAMs through Guide(..., aux)) can be cut out, as a numpy structured array with the fields of
+        calitas_site_t (SITE_DTYPE; strand as the byte b'+' / b'-'), sorted by contig, protospacer start, '+' before '-'.  chrom: a
+        name, an index or None (every contig); [start, end) in 0-based contig coordinates, end None: the contig's end.  host=True: the
+        host twin (calitas_find_sites_host), which also works on a host-only context."""
+        import numpy as np
+        pattern, index, start, end = self._site_region(pattern, chrom, start, end)
+        g = pattern.to_c()
+        out, n = ctypes.POINTER(SiteT)(), ctypes.c_uint64()
+        fn = lib.calitas_find_sites_host if host else lib.calitas_find_sites
+        _lib.check(self._h, fn(self._h, ctypes.byref(g), index, start, end, ctypes.byref(out), ctypes.byref(n)))
+        try:
+            if n.value == 0:
+                return np.zeros(0, dtype=SITE_DTYPE)
+            block = (ctypes.c_char * (n.value * ctypes.sizeof(SiteT))).from_address(ctypes.addressof(out.contents))
+            return np.frombuffer(block, dtype=SITE_DTYPE).copy()
+        finally:
+            lib.calitas_free(out)
+
+    def count_sites(self, pattern, chrom=None, start=0, end=None):
+        """calitas_count_sites: (total, per_contig_strand) -- the number of sites find_sites would list and a numpy uint64 array
+        [n_contigs][2] ('+' first) of them, from the kernel's first pass alone: no record is written or copied."""
+        import numpy as np
+        pattern, index, start, end = self._site_region(pattern, chrom, start, end)
+        g = pattern.to_c()
+        table = np.zeros((max(1, len(self.contig_names)), 2), dtype=np.uint64)
+        n = ctypes.c_uint64()
+        _lib.check(self._h, lib.calitas_count_sites(self._h, ctypes.byref(g), index, start, end,
+                                                    table.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), ctypes.byref(n)))
+        return n.value, table[:len(self.contig_names)]
+
     def timing(self):
         t = TimingT()
         _lib.check(self._h, lib.calitas_get_timing(self._h, ctypes.byref(t)))
@@ -627,6 +672,10 @@ class SearchReference:
             with open(self.output, "w") as f:
                 f.write(text)
 
+
+# calitas_site_t as a numpy record
+SITE_DTYPE = [("contig_index", "<i4"), ("protospacer_start", "<i4"), ("pam_start", "<i4"), ("strand", "S1"), ("pam_index", "i1"),
+              ("pam_length", "u1"), ("protospacer_length", "u1")]
 
 COUNTS_COLUMNS = ("guide_id", "strand", "guide_mm", "guide_gaps", "pam_mm", "hits")
 

@@ -27,6 +27,7 @@
 #include "post.hpp"
 #include "refpack.hpp"
 #include "ctx.hpp"
+#include "sites.hpp"
 
 static std::string g_create_error;
 
@@ -333,6 +334,7 @@ void calitas_destroy(calitas_ctx* c) {
     hits_destroy(c->hits);
     hits_destroy(c->hits_alt);
     binned_destroy(c->binned);
+    sites_destroy(c->sites);
     if (c->scan_done) (void)hipEventDestroy(c->scan_done);
     if (c->rows_ready) (void)hipEventDestroy(c->rows_ready);
     if (c->inputs_ready) (void)hipEventDestroy(c->inputs_ready);
@@ -733,6 +735,33 @@ int calitas_search_counts_batch(calitas_ctx* ctx, int32_t n_guides, const calita
   }
   if (rc) for (int i = 0; i < n_guides; i++) { calitas_free(out[i]); out[i] = nullptr; }
   return rc;
+}
+
+// Guide sites (sites_host.cpp): no reference counterpart.
+int calitas_find_sites(calitas_ctx* ctx, const calitas_guide_t* pattern, int32_t chrom_index, uint64_t start, uint64_t end,
+                       calitas_site_t** sites, uint64_t* n_sites) {
+  if (!ctx) return CALITAS_EINVAL;
+  if (!pattern || !n_sites) return fail(ctx, CALITAS_EINVAL, "NULL argument");
+  *n_sites = 0;
+  if (sites) *sites = nullptr;
+  return calitas_find_sites_impl(ctx, pattern, chrom_index, start, end, sites != nullptr, sites, nullptr, n_sites);
+}
+
+int calitas_count_sites(calitas_ctx* ctx, const calitas_guide_t* pattern, int32_t chrom_index, uint64_t start, uint64_t end,
+                        uint64_t* per_contig_strand, uint64_t* n_sites) {
+  if (!ctx) return CALITAS_EINVAL;
+  if (!pattern || !n_sites) return fail(ctx, CALITAS_EINVAL, "NULL argument");
+  *n_sites = 0;
+  return calitas_find_sites_impl(ctx, pattern, chrom_index, start, end, false, nullptr, per_contig_strand, n_sites);
+}
+
+int calitas_find_sites_host(const calitas_ctx* ctx, const calitas_guide_t* pattern, int32_t chrom_index, uint64_t start, uint64_t end,
+                            calitas_site_t** sites, uint64_t* n_sites) {
+  if (!ctx) return CALITAS_EINVAL;
+  if (!pattern || !n_sites) return fail(const_cast<calitas_ctx*>(ctx), CALITAS_EINVAL, "NULL argument");
+  *n_sites = 0;
+  if (sites) *sites = nullptr;
+  return calitas_find_sites_host_impl(ctx, pattern, chrom_index, start, end, sites, n_sites);
 }
 
 int calitas_scan_candidates(calitas_ctx* ctx, int32_t n_guides, const calitas_guide_t* guides, const calitas_params_t* params,

@@ -1,6 +1,7 @@
-// cli.cpp -- `calitas SearchReference ...` on the MI355X path: the flag surface of the reference tool
+// cli.cpp -- `calitas SearchReference ...` and `calitas FindGuides ...` on the MI355X path: for the first, the flag surface of the reference tool
 // (SearchReference.scala:452-470) over the C ABI of include/calitas_hip.h.  The Scala CLI stays the intended host in
 // production; this binary is the same host logic for boxes without a JVM.
+#include <algorithm>
 #include <cctype>
 #include <cstdio>
 #include <cstdlib>
@@ -18,7 +19,9 @@ static void usage() {
     "         [-b genome-gap-net-cost=-122] [-B guide-gap-net-cost=-121] [-c chrom] [-t threads (ignored)]\n"
     "         [-v variants.vcf[.gz]] [-V max-variants=16]\n"
     "         [--counts (the table guide_id strand guide_mm guide_gaps pam_mm hits instead of hits.txt)]\n"
-    "         [--device N]\n");
+    "         [--device N]\n"
+    "       calitas FindGuides -i PATTERNpam -r ref.fa [-x aux-pam ...] [-c chrom] [-s start=0] [-e end] [-o guides.tsv]\n"
+    "         [--device N (-1: the host twin, no GPU)]\n");
 }
 
 static std::string long_to_short(const std::string& a) {
@@ -32,7 +35,124 @@ static std::string long_to_short(const std::string& a) {
   return a;
 }
 
+// Guide.apply(sequence, auxPams): split by case (SequentialGuideAligner.scala:81-107)
+struct ParsedGuide {
+  std::string proto;
+  std::vector<std::string> pams;
+  std::vector<const char*> pam_ptrs;
+  int pam5 = 0;
+  size_t cli_length = 0;
+  calitas_guide_t c_guide() {
+    pam_ptrs.clear();
+    for (auto& s : pams) pam_ptrs.push_back(s.c_str());
+    calitas_guide_t g;
+    g.protospacer = proto.c_str(); g.n_pams = (int32_t)pams.size(); g.pams = pam_ptrs.empty() ? nullptr : pam_ptrs.data();
+    g.pam_is_5prime = pam5; g.cli_length = (int32_t)cli_length;
+    return g;
+  }
+};
+
+static int parse_guide(const std::string& guide, const std::vector<std::string>& aux, ParsedGuide& out) {
+  std::vector<std::string> parts;
+  for (size_t i = 0; i < guide.size();) {
+    bool lower = std::islower((unsigned char)guide[i]) != 0;
+    size_t j = i;
+    while (j < guide.size() && (std::islower((unsigned char)guide[j]) != 0) == lower) j++;
+    parts.push_back(guide.substr(i, j - i));
+    i = j;
+  }
+  if (parts.empty() || parts.size() > 2) { std::fprintf(stderr, "Invalid Guide sequence %s.\n", guide.c_str()); return 1; }
+  if (parts.size() == 1 && !std::isupper((unsigned char)parts[0][0])) { std::fprintf(stderr, "Guide sequence cannot be all lower case.\n"); return 1; }
+  if (!aux.empty() && parts.size() != 2) { std::fprintf(stderr, "Cannot provide auxiliary PAMs without providing a PAM in the guide sequence.\n"); return 1; }
+  for (auto& x : aux) for (char c : x) if (std::isupper((unsigned char)c)) { std::fprintf(stderr, "All PAMs must be lower case.\n"); return 1; }
+  if (parts.size() == 1) out.proto = parts[0];
+  else if (std::isupper((unsigned char)parts[0][0])) { out.proto = parts[0]; out.pams.push_back(parts[1]); }
+  else { out.proto = parts[1]; out.pams.push_back(parts[0]); out.pam5 = 1; }
+  for (auto& x : aux) out.pams.push_back(x);
+  out.cli_length = guide.size();
+  return 0;
+}
+
+// `calitas FindGuides`: the sites of an IUPAC pattern in a region as the guides a search takes -- the table of
+// `python -m calitas_amd FindGuides`, byte for byte (calitas_amd/tools.py guides_tsv).  No reference counterpart.
+static int find_guides_main(int argc, char** argv) {
+  std::string pattern, ref, output, chrom;
+  std::vector<std::string> aux;
+  uint64_t start = 0, end = 0;
+  int device = 0;
+  for (int i = 2; i < argc; i++) {
+    std::string a = argv[i], val;
+    size_t eq = a.find('=');
+    if (a.compare(0, 2, "--") == 0 && eq != std::string::npos) { val = a.substr(eq + 1); a = a.substr(0, eq); }
+    a = long_to_short(a);
+    auto next = [&]() -> std::string {
+      if (!val.empty()) return val;
+      if (i + 1 >= argc) { usage(); std::exit(2); }
+      return argv[++i];
+    };
+    if (a == "-i") pattern = next();
+    else if (a == "-r") ref = next();
+    else if (a == "-o") output = next();
+    else if (a == "-c") chrom = next();
+    else if (a == "-s" || a == "--start") start = std::strtoull(next().c_str(), nullptr, 10);
+    else if (a == "-e" || a == "--end") end = std::strtoull(next().c_str(), nullptr, 10);
+    else if (a == "-x") { aux.push_back(next()); while (i + 1 < argc && argv[i + 1][0] != '-') aux.push_back(argv[++i]); }
+    else if (a == "--device") device = std::atoi(next().c_str());
+    else { std::fprintf(stderr, "unknown argument %s\n", a.c_str()); usage(); return 2; }
+  }
+  if (pattern.empty() || ref.empty()) { usage(); return 2; }
+  ParsedGuide pg;
+  if (int rc = parse_guide(pattern, aux, pg)) return rc;
+  calitas_guide_t g = pg.c_guide();
+  calitas_ctx* ctx = nullptr;
+  if (calitas_create(device, &ctx) != CALITAS_OK) { std::fprintf(stderr, "calitas: %s\n", calitas_last_error(nullptr)); return 1; }
+  auto die = [&](const char* what) { std::fprintf(stderr, "calitas: %s: %s\n", what, calitas_last_error(ctx)); calitas_destroy(ctx); std::exit(1); };
+  if (calitas_set_reference_fasta(ctx, ref.c_str()) != CALITAS_OK) die("reading reference");
+  int32_t chrom_index = -1;
+  if (!chrom.empty()) {
+    int32_t n = 0; calitas_reference_info(ctx, &n, nullptr, nullptr);
+    for (int32_t i = 0; i < n; i++) { const char* nm; uint64_t len; calitas_contig_name(ctx, i, &nm, &len); if (chrom == nm) chrom_index = i; }
+    if (chrom_index < 0) { std::fprintf(stderr, "Unknown chromosome: %s\n", chrom.c_str()); calitas_destroy(ctx); return 1; }
+  }
+  calitas_site_t* sites = nullptr; uint64_t n_sites = 0;
+  const int rc = device < 0 ? calitas_find_sites_host(ctx, &g, chrom_index, start, end, &sites, &n_sites)
+                            : calitas_find_sites(ctx, &g, chrom_index, start, end, &sites, &n_sites);
+  if (rc != CALITAS_OK) die("finding sites");
+  FILE* f = output.empty() ? stdout : std::fopen(output.c_str(), "w");
+  if (!f) { std::fprintf(stderr, "cannot write %s\n", output.c_str()); calitas_free(sites); calitas_destroy(ctx); return 1; }
+  std::fprintf(f, "guide_id\tchromosome\tstart\tend\tstrand\tpam_index\tguide\tpam_sequence\n");
+  auto on_strand = [](std::string t, bool minus) {     // upper-case bases as fetched; '-': their reverse complement
+    if (!minus) return t;
+    std::string o(t.rbegin(), t.rend());
+    for (auto& c : o) c = c == 'A' ? 'T' : c == 'C' ? 'G' : c == 'G' ? 'C' : (c == 'T' || c == 'U') ? 'A' : c;
+    return o;
+  };
+  const int64_t L = (int64_t)pg.proto.size();
+  for (uint64_t i = 0; i < n_sites; i++) {
+    const calitas_site_t& s = sites[i];
+    const bool minus = s.strand == '-';
+    const char* name; uint64_t len;
+    calitas_contig_name(ctx, s.contig_index, &name, &len);
+    std::string proto((size_t)L, 'N'), pam((size_t)s.pam_length, 'N');
+    if (calitas_fetch_bases(ctx, s.contig_index, (uint64_t)s.protospacer_start, (uint32_t)L, &proto[0]) != CALITAS_OK) die("fetching bases");
+    if (s.pam_start >= 0 && calitas_fetch_bases(ctx, s.contig_index, (uint64_t)s.pam_start, s.pam_length, &pam[0]) != CALITAS_OK) die("fetching bases");
+    proto = on_strand(proto, minus); pam = on_strand(pam, minus);
+    for (auto& c : proto) if (c == 'U') c = 'T';          // an ACGT guide
+    const int64_t lo = s.pam_start < 0 ? s.protospacer_start : std::min<int64_t>(s.protospacer_start, s.pam_start);
+    const int64_t hi = s.pam_start < 0 ? s.protospacer_start + L : std::max<int64_t>(s.protospacer_start + L, (int64_t)s.pam_start + s.pam_length);
+    const std::string pat_pam = s.pam_index >= 0 ? pg.pams[(size_t)s.pam_index] : std::string();
+    const std::string guide = pg.pam5 ? pat_pam + proto : proto + pat_pam;
+    std::fprintf(f, "%s:%lld:%c\t%s\t%lld\t%lld\t%c\t%d\t%s\t%s\n", name, (long long)lo, (char)s.strand, name, (long long)lo, (long long)hi,
+                 (char)s.strand, (int)s.pam_index, guide.c_str(), pam.c_str());
+  }
+  if (f != stdout) std::fclose(f);
+  std::fprintf(stderr, "calitas: %llu guides\n", (unsigned long long)n_sites);
+  calitas_free(sites); calitas_destroy(ctx);
+  return 0;
+}
+
 int main(int argc, char** argv) {
+  if (argc >= 2 && std::strcmp(argv[1], "FindGuides") == 0) return find_guides_main(argc, argv);
   if (argc < 2 || std::strcmp(argv[1], "SearchReference") != 0) { usage(); return 2; }
   std::string guide, guide_id, ref, output, chrom, variants;
   std::vector<std::string> aux;
@@ -78,31 +198,9 @@ int main(int argc, char** argv) {
   if (guide.empty() || guide_id.empty() || ref.empty()) { usage(); return 2; }
   if (counts && !variants.empty()) { std::fprintf(stderr, "--counts covers the reference-genome branch only (no --variants)\n"); return 2; }
 
-  // Guide.apply(sequence, auxPams): split by case (SequentialGuideAligner.scala:81-107)
-  std::vector<std::string> parts;
-  for (size_t i = 0; i < guide.size();) {
-    bool lower = std::islower((unsigned char)guide[i]) != 0;
-    size_t j = i;
-    while (j < guide.size() && (std::islower((unsigned char)guide[j]) != 0) == lower) j++;
-    parts.push_back(guide.substr(i, j - i));
-    i = j;
-  }
-  if (parts.empty() || parts.size() > 2) { std::fprintf(stderr, "Invalid Guide sequence %s.\n", guide.c_str()); return 1; }
-  if (parts.size() == 1 && !std::isupper((unsigned char)parts[0][0])) { std::fprintf(stderr, "Guide sequence cannot be all lower case.\n"); return 1; }
-  if (!aux.empty() && parts.size() != 2) { std::fprintf(stderr, "Cannot provide auxiliary PAMs without providing a PAM in the guide sequence.\n"); return 1; }
-  for (auto& x : aux) for (char c : x) if (std::isupper((unsigned char)c)) { std::fprintf(stderr, "All PAMs must be lower case.\n"); return 1; }
-  std::string proto;
-  std::vector<std::string> pams;
-  int pam5 = 0;
-  if (parts.size() == 1) proto = parts[0];
-  else if (std::isupper((unsigned char)parts[0][0])) { proto = parts[0]; pams.push_back(parts[1]); }
-  else { proto = parts[1]; pams.push_back(parts[0]); pam5 = 1; }
-  for (auto& x : aux) pams.push_back(x);
-  std::vector<const char*> pam_ptrs;
-  for (auto& s : pams) pam_ptrs.push_back(s.c_str());
-  calitas_guide_t g;
-  g.protospacer = proto.c_str(); g.n_pams = (int32_t)pams.size(); g.pams = pam_ptrs.empty() ? nullptr : pam_ptrs.data();
-  g.pam_is_5prime = pam5; g.cli_length = (int32_t)guide.size();
+  ParsedGuide pg;
+  if (int rc = parse_guide(guide, aux, pg)) return rc;
+  calitas_guide_t g = pg.c_guide();
 
   calitas_ctx* ctx = nullptr;
   if (calitas_create(device, &ctx) != CALITAS_OK) { std::fprintf(stderr, "calitas: %s\n", calitas_last_error(nullptr)); return 1; }

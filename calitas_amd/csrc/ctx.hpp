@@ -21,6 +21,7 @@
 #include "dma.hpp"
 #include "mailbox.hpp"
 
+namespace calitas { struct SitesWork; }   // sites.hpp
 using namespace calitas;
 
 struct calitas_ctx {
@@ -66,6 +67,7 @@ struct calitas_ctx {
   std::vector<uint32_t> bin_base;   // the same on the host
   int bin_shift = 0;                // 0 = not built
   BinnedWork* binned = nullptr;     // lane
+  SitesWork* sites = nullptr;       // calitas_find_sites: device scratch kept between calls (sites_host.cpp)
   double align_ms_by_stamps = -1;   // lane: >= 0: align_kernel + trace_kernel of the current search ran without an event behind them (binned.hpp, BIN_BOX_STAMPS)
   int rows_ev0 = 4;                 // lane: ev[rows_ev0] .. ev[5] bracket the row stage of the last call
   bool binned_late_check = false;   // lane: the text being copied comes from the binned rows kernel (its late flags are checked after the copy's wait)

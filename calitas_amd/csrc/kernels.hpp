@@ -1,4 +1,4 @@
-// kernels.hpp -- launch interface of scan_columns.hip, scan_rows.hip, align.hip, trace.hip and setup.hip (device pointers only).
+// kernels.hpp -- launch interface of scan_columns.hip, scan_rows.hip, align.hip, trace.hip, setup.hip and sites.hip (device pointers only).
 #pragma once
 #include "mailbox.hpp"
 #include <hip/hip_runtime_api.h>
@@ -95,5 +95,53 @@ hipError_t launch_trace(const AlignArgs& a, uint32_t n_blocks, hipStream_t strea
 hipError_t launch_window_table(const Run* runs, int64_t n_runs, const ContigInfo* contigs, const uint64_t* win_base, int n_contigs,
                                uint64_t n_windows, int W, int step, int2* out, hipStream_t stream);
 hipError_t launch_dpp_selftest(int* out, hipStream_t stream);
+
+// sites.hip: exact IUPAC pattern scan (calitas_find_sites / calitas_count_sites).  One SitePattern per (PAM, strand): the letters the
+// FORWARD text must show around a protospacer that starts at base p -- for '-' the reverse complement of the strand-space pattern, so
+// both strands are matched on the same planes.  Offsets are relative to p: the footprint is [p + lo, p + hi), -16 <= lo <= 0 < hi <= 48.
+constexpr int SITE_MAX_FOOT = MAX_L + MAX_PAM_LEN;
+constexpr int SITES_BLOCK_WORDS = 256;   // 32-base words of a segment = lanes of a workgroup
+struct SitePattern {
+  int32_t lo, hi;
+  int32_t pam_off;                 // the PAM starts at p + pam_off (lo for a PAM on the left, the protospacer's length on the right)
+  int32_t pam_len;
+  uint32_t sets[8];                // four bits per offset -16 .. 47 (bit 4 (d + 16) on): the IUPAC set the forward base at p + d must be in,
+                                   // 15 for N and outside the footprint
+};
+struct SitePatterns {
+  int32_t n_pams;                  // >= 1: a PAM-less pattern has one entry with pam_len 0
+  int32_t pamless;
+  int32_t proto_len;
+  int32_t pad;
+  SitePattern p[MAX_PAMS][2];      // [PAM][strand: 0 '+', 1 '-']
+};
+struct SiteRecord {                // = calitas_site_t
+  int32_t contig, proto_start, pam_start;
+  int8_t strand, pam_index;
+  uint8_t pam_len, proto_len;
+};
+struct SitesArgs {
+  const uint2* planes;
+  const uint32_t* mask;
+  const TileInfo* tiles;
+  const ContigInfo* contigs;
+  const SitePatterns* pat;         // device memory
+  uint64_t n_words;                // 32-base words of the packed space
+  uint64_t w0;                     // first word of the launch, a multiple of SITES_BLOCK_WORDS
+  uint32_t n_segs;                 // segments of SITES_BLOCK_WORDS words from w0 on
+  uint32_t segs_per_wg;            // consecutive segments a workgroup takes
+  uint32_t tile_words;             // 32-base words per scan tile, a multiple of SITES_BLOCK_WORDS: a segment never spans two tiles
+  int32_t chrom_index;
+  uint64_t start, end;             // the region, in contig coordinates; end == 0: the contig's end
+  uint32_t* wg_count;              // pass 1: sites per segment
+  unsigned long long* totals;      // pass 1: sites per (contig, strand), zero at launch
+  const uint64_t* wg_offset;       // pass 2: exclusive scan of wg_count
+  SiteRecord* out;                 // pass 2
+  uint64_t out_capacity;
+};
+hipError_t launch_sites_count(const SitesArgs& a, hipStream_t stream);
+// wg_count[0 .. n) -> wg_offset[0 .. n], wg_offset[n] = the total
+hipError_t launch_sites_offsets(const uint32_t* wg_count, uint64_t* wg_offset, uint32_t n, hipStream_t stream);
+hipError_t launch_sites_write(const SitesArgs& a, hipStream_t stream);
 
 }  // namespace calitas

@@ -1,0 +1,286 @@
+// sites.hip -- exact IUPAC pattern scan of the packed reference: where can a guide be cut out (calitas_find_sites, gfx950).
+// No reference counterpart: the reference starts from a guide somebody already has.
+//
+// The match runs along the text, as scan_rows.hip does.  A lane owns one 32-base word of the two bit-planes (lo, hi: bit j = low / high
+// bit of base j's 2-bit code) and of the exception mask, and builds a MATCH VECTOR per (PAM, strand): bit j = a protospacer can start
+// at base 32 w + j.  A footprint reaches at most 16 bases to the left of its protospacer's first base and 48 to the right, so the lane
+// sees a chain of four words, w - 1 .. w + 2, staged once per segment of 256 words in LDS.
+//   * "the base at offset d from the start lies in the letter's IUPAC set" is a two-input boolean function of the planes moved down
+//     by d: two v_alignbit_b32 across the word boundary, then a selection among four all-ones / all-zeros masks, one per base of the
+//     letter's set, ANDed into the accumulator.  The pattern is 64 four-bit sets in scalar registers, one per offset; the offsets are
+//     unrolled, so every shift is an immediate.  N costs a scalar branch.
+//   * "no exception base in the footprint" is a run-length test on ~exc by doubling (runs of 1, 2, 4, .. ANDed with themselves moved
+//     down), six steps at most, once per footprint length.
+//   * '-' is the reverse-complemented pattern on the same forward planes (the host builds both, SitePattern): one pass over memory.
+//   * the region is a mask of start positions per lane; contig ends need nothing (padding is exception bases).
+// Output in order, without a sort and without a returning atomic: pass 1 stores one count per segment, a one-workgroup scan turns
+// the counts into offsets, pass 2 recomputes the vectors and every lane writes its records at offset + prefix (a DPP prefix sum per
+// wave, the waves' sums through LDS); the '+' and '-' record of one position are neighbours.
+#include <hip/hip_runtime.h>
+
+#include "common.hpp"
+#include "kernels.hpp"
+
+namespace calitas {
+
+namespace {
+
+typedef const __attribute__((address_space(4))) SitePatterns PatConst;   // scalar loads
+typedef const __attribute__((address_space(4))) SitePattern PatOne;
+
+// acc & "the base at chain position X lies in the set" for the 32 starts of the lane's word: the planes moved down by X across the word
+// boundary (X is a compile-time constant: the shift is an immediate, the word pair fixed), then a selection among four all-ones /
+// all-zeros masks, one per base of the set (A=1 C=2 G=4 T=8), as in scan_rows.hip's IUPAC part 1.  The set is wave-uniform.
+template <int X>
+CAL_DEV uint32_t and_letter(uint32_t acc, uint32_t set, const uint32_t (&c_lo)[4], const uint32_t (&c_hi)[4]) {
+  constexpr int Q = X >> 5, SH = X & 31;
+  const uint32_t lo = SH ? __builtin_amdgcn_alignbit(c_lo[Q + 1], c_lo[Q], SH) : c_lo[Q];
+  const uint32_t hi = SH ? __builtin_amdgcn_alignbit(c_hi[Q + 1], c_hi[Q], SH) : c_hi[Q];
+  const uint32_t ka = 0u - (set & 1u), kc = 0u - ((set >> 1) & 1u), kg = 0u - ((set >> 2) & 1u), kt = 0u - ((set >> 3) & 1u);
+  const uint32_t hi0 = (lo & kc) | (~lo & ka), hi1 = (lo & kt) | (~lo & kg);
+  return acc & ((hi & hi1) | (~hi & hi0));
+}
+
+// The eight letters of one word of SitePattern::sets (chain positions 16 + 8 I ..): N -- and everything outside the footprint -- is
+// skipped by a scalar branch, a whole word of them by one.
+template <int I>
+CAL_DEV uint32_t and_letters(uint32_t acc, uint32_t sets, const uint32_t (&c_lo)[4], const uint32_t (&c_hi)[4]) {
+  if (sets == 0xFFFFFFFFu) return acc;
+#define CALITAS_SITE_LETTER(J) \
+  if (((sets >> (4 * J)) & 15u) != 15u) acc = and_letter<16 + 8 * I + J>(acc, (sets >> (4 * J)) & 15u, c_lo, c_hi);
+  CALITAS_SITE_LETTER(0) CALITAS_SITE_LETTER(1) CALITAS_SITE_LETTER(2) CALITAS_SITE_LETTER(3)
+  CALITAS_SITE_LETTER(4) CALITAS_SITE_LETTER(5) CALITAS_SITE_LETTER(6) CALITAS_SITE_LETTER(7)
+#undef CALITAS_SITE_LETTER
+  return acc;
+}
+
+// bits j of a word whose first base is contig position base0 with pmin <= base0 + j <= pmax
+CAL_DEV uint32_t range_bits(int64_t base0, int64_t pmin, int64_t pmax) {
+  const int64_t a = pmin - base0, b = pmax - base0;
+  if (b < 0 || a > 31 || a > b) return 0u;
+  const uint32_t from = a > 0 ? (uint32_t)a : 0u, to = b < 31 ? (uint32_t)b : 31u;
+  return (0xFFFFFFFFu << from) & (0xFFFFFFFFu >> (31u - to));
+}
+
+// inclusive prefix sum over the wave: row_shr 1, 2, 4, 8 inside the rows of 16 lanes, then row 0's and rows 0-1's totals handed on
+CAL_DEV uint32_t wave_inclusive_sum(uint32_t v) {
+  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x111 /* row_shr:1 */, 0xf, 0xf, false);
+  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x112 /* row_shr:2 */, 0xf, 0xf, false);
+  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x114 /* row_shr:4 */, 0xf, 0xf, false);
+  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x118 /* row_shr:8 */, 0xf, 0xf, false);
+  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x142 /* row_bcast:15 */, 0xa, 0xf, false);
+  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x143 /* row_bcast:31 */, 0xc, 0xf, false);
+  return v;
+}
+
+struct LaneSites {
+  uint32_t plus, minus;        // match vectors: a site of that strand starts at base j
+  uint32_t kp[3], km[3];       // bit-planes of the matching PAM's index
+};
+
+// The match vectors of the lane's word.  c_*: the chain w - 1 .. w + 2; base0: contig position of the word's first base.
+CAL_DEV LaneSites match_word(PatConst* pat, uint32_t (&c_lo)[4], uint32_t (&c_hi)[4], const uint32_t (&c_ex)[4], int64_t base0,
+                             int64_t r_start, int64_t r_end) {
+  LaneSites s{0u, 0u, {0u, 0u, 0u}, {0u, 0u, 0u}};
+  const int n_pams = pat->n_pams;
+  int run_len = 0;
+  uint32_t run[4] = {0u, 0u, 0u, 0u};       // bit = a run of run_len clean bases starts here (chain positions; beyond the chain: none)
+  for (int k = 0; k < n_pams; k++) {
+    const int foot = pat->p[k][0].hi - pat->p[k][0].lo;
+    if (foot != run_len) {
+      run_len = foot;
+#pragma unroll
+      for (int i = 0; i < 4; i++) run[i] = ~c_ex[i];
+      int len = 1;
+      while (len < foot) {
+        const uint32_t by = (uint32_t)(2 * len <= foot ? len : foot - len);   // < 32; the last step's windows overlap
+        run[0] &= __builtin_amdgcn_alignbit(run[1], run[0], by);
+        run[1] &= __builtin_amdgcn_alignbit(run[2], run[1], by);
+        run[2] &= __builtin_amdgcn_alignbit(run[3], run[2], by);
+        run[3] &= run[3] >> by;
+        len += (int)by;
+      }
+    }
+#pragma unroll
+    for (int st = 0; st < 2; st++) {
+      PatOne* sp = &pat->p[k][st];
+      const int lo = sp->lo, hi = sp->hi;
+      // the moved planes are the same for every PAM and strand: left alone the compiler computes all 128 of them ahead of the loop
+      // and keeps them (300 VGPRs)
+#pragma unroll
+      for (int i = 0; i < 4; i++) asm volatile("" : "+v"(c_lo[i]), "+v"(c_hi[i]));
+      // starts whose footprint [p + lo, p + hi) lies in the region and is clean
+      uint32_t acc = range_bits(base0, r_start - lo, r_end - hi);
+      const uint32_t at = (uint32_t)(32 + lo);                                // 16 .. 32
+      acc &= at >= 32u ? run[1] : __builtin_amdgcn_alignbit(run[1], run[0], at);
+      acc = and_letters<0>(acc, sp->sets[0], c_lo, c_hi);  acc = and_letters<1>(acc, sp->sets[1], c_lo, c_hi);
+      acc = and_letters<2>(acc, sp->sets[2], c_lo, c_hi);  acc = and_letters<3>(acc, sp->sets[3], c_lo, c_hi);
+      acc = and_letters<4>(acc, sp->sets[4], c_lo, c_hi);  acc = and_letters<5>(acc, sp->sets[5], c_lo, c_hi);
+      acc = and_letters<6>(acc, sp->sets[6], c_lo, c_hi);  acc = and_letters<7>(acc, sp->sets[7], c_lo, c_hi);
+      uint32_t& found = st ? s.minus : s.plus;
+      uint32_t (&kb)[3] = st ? s.km : s.kp;
+      acc &= ~found;                                                          // the first PAM that matches wins
+      found |= acc;
+      if (k & 1) kb[0] |= acc;
+      if (k & 2) kb[1] |= acc;
+      if (k & 4) kb[2] |= acc;
+    }
+  }
+  return s;
+}
+
+// What a lane brings from memory for one segment: its own word, and for lanes 0-2 one of the three words around the segment.
+struct Fetched {
+  uint2 pl, halo_pl;
+  uint32_t ex, halo_ex;
+};
+
+// WRITE = false: pass 1 (counts); true: pass 2 (records).  A SEGMENT is SITES_BLOCK_WORDS consecutive words, all of one tile, one lane
+// per word; it is the unit of the counts and offsets.  A workgroup takes segs_per_wg consecutive segments, the next one's words on
+// their way from memory while it matches the current one's (a workgroup per segment is bound by the rate at which workgroups start).
+template <bool WRITE>
+__global__ __launch_bounds__(SITES_BLOCK_WORDS) void sites_kernel(SitesArgs a) {
+  __shared__ uint32_t s_lo[SITES_BLOCK_WORDS + 3], s_hi[SITES_BLOCK_WORDS + 3], s_ex[SITES_BLOCK_WORDS + 3];
+  __shared__ uint32_t s_wave[SITES_BLOCK_WORDS / 64];
+  const uint32_t tid = threadIdx.x, wave = tid >> 6, wl = tid & 63u;
+  const uint32_t seg0 = blockIdx.x * a.segs_per_wg, seg1 = min(seg0 + a.segs_per_wg, a.n_segs);
+  PatConst* pat = (PatConst*)a.pat;
+
+  // dead tile, padding, another contig: nothing to do (wave-uniform)
+  auto tile_of = [&](uint32_t seg) { return a.tiles[(a.w0 + (uint64_t)seg * SITES_BLOCK_WORDS) / a.tile_words]; };
+  auto live = [&](const TileInfo ti) {
+    return !(ti.flag == 2u || ti.contig == 0xFFFFFFFFu || (a.chrom_index >= 0 && ti.contig != (uint32_t)a.chrom_index));
+  };
+  // the words wb - 1 .. wb + 257 of a segment (wb >= one tile: the packed space starts with a tile of padding)
+  auto fetch = [&](uint32_t seg) {
+    Fetched f{make_uint2(0u, 0u), make_uint2(0u, 0u), 0xFFFFFFFFu, 0xFFFFFFFFu};
+    if (seg >= seg1 || !live(tile_of(seg))) return f;
+    const uint64_t wb = a.w0 + (uint64_t)seg * SITES_BLOCK_WORDS;
+    const uint64_t w = wb + tid, h = tid == 0 ? wb - 1 : wb + SITES_BLOCK_WORDS - 1 + tid;
+    if (w < a.n_words) { f.pl = a.planes[w]; f.ex = a.mask[w]; }
+    if (tid < 3u && h < a.n_words) { f.halo_pl = a.planes[h]; f.halo_ex = a.mask[h]; }
+    return f;
+  };
+
+  uint32_t t_contig = 0xFFFFFFFFu, t_plus = 0u, t_minus = 0u;     // lane 0: sites of the segments so far, per strand, of one contig
+  auto flush_totals = [&]() {
+    if (t_plus) (void)atomicAdd(&a.totals[2 * t_contig], (unsigned long long)t_plus);
+    if (t_minus) (void)atomicAdd(&a.totals[2 * t_contig + 1], (unsigned long long)t_minus);
+    t_plus = t_minus = 0u;
+  };
+
+  Fetched f = fetch(seg0);
+  for (uint32_t seg = seg0; seg < seg1; seg++) {
+    const TileInfo ti = tile_of(seg);
+    if (!live(ti)) {
+      if (!WRITE && tid == 0) a.wg_count[seg] = 0u;
+      f = fetch(seg + 1);
+      continue;
+    }
+    s_lo[tid + 1] = f.pl.x; s_hi[tid + 1] = f.pl.y; s_ex[tid + 1] = f.ex;
+    if (tid < 3u) {
+      const uint32_t i = tid == 0 ? 0u : SITES_BLOCK_WORDS + tid;
+      s_lo[i] = f.halo_pl.x; s_hi[i] = f.halo_pl.y; s_ex[i] = f.halo_ex;
+    }
+    __syncthreads();
+    uint32_t c_lo[4], c_hi[4], c_ex[4];
+#pragma unroll
+    for (int i = 0; i < 4; i++) { c_lo[i] = s_lo[tid + i]; c_hi[i] = s_hi[tid + i]; c_ex[i] = s_ex[tid + i]; }
+    f = fetch(seg + 1);
+
+    const uint64_t wb = a.w0 + (uint64_t)seg * SITES_BLOCK_WORDS;
+    const ContigInfo ci = a.contigs[ti.contig];
+    const int64_t r_start = (int64_t)(a.start < ci.len ? a.start : ci.len);
+    const int64_t r_end = (int64_t)((a.end == 0 || a.end > ci.len) ? ci.len : a.end);
+    const int64_t base0 = (int64_t)((wb + tid) * 32u) - (int64_t)ci.gbase;
+    const LaneSites s = match_word(pat, c_lo, c_hi, c_ex, base0, r_start, r_end);
+
+    const uint32_t n_plus = (uint32_t)__builtin_popcount(s.plus), n_minus = (uint32_t)__builtin_popcount(s.minus);
+    if (!WRITE) {
+      // '+' in the low half, '-' in the high half: a segment has at most 8192 of each
+      const uint32_t incl = wave_inclusive_sum(n_plus | (n_minus << 16));
+      if (wl == 63u) s_wave[wave] = incl;
+      __syncthreads();                                    // (also: every lane has its chain out of LDS before the next segment goes in)
+      if (tid == 0) {
+        const uint32_t t = s_wave[0] + s_wave[1] + s_wave[2] + s_wave[3];
+        a.wg_count[seg] = (t & 0xFFFFu) + (t >> 16);
+        if (ti.contig != t_contig) { flush_totals(); t_contig = ti.contig; }
+        t_plus += t & 0xFFFFu; t_minus += t >> 16;
+      }
+      continue;
+    }
+    const uint32_t mine = n_plus + n_minus;
+    const uint32_t incl = wave_inclusive_sum(mine);
+    if (wl == 63u) s_wave[wave] = incl;
+    __syncthreads();
+    uint64_t at = a.wg_offset[seg] + (incl - mine);
+    for (uint32_t v = 0; v < wave; v++) at += s_wave[v];
+    const int pamless = pat->pamless, proto_len = pat->proto_len;
+    uint32_t any = s.plus | s.minus;
+    while (any) {
+      const uint32_t j = (uint32_t)__builtin_ctz(any);
+      any &= any - 1u;
+      const int32_t p = (int32_t)(base0 + j);
+#pragma unroll
+      for (int st = 0; st < 2; st++) {
+        if (!(((st ? s.minus : s.plus) >> j) & 1u)) continue;
+        const uint32_t (&kb)[3] = st ? s.km : s.kp;
+        const uint32_t k = ((kb[0] >> j) & 1u) | (((kb[1] >> j) & 1u) << 1) | (((kb[2] >> j) & 1u) << 2);
+        const SitePattern* sp = &a.pat->p[k][st];                              // (per lane: an ordinary load)
+        const int pam_len = sp->pam_len;
+        SiteRecord r;
+        r.contig = (int32_t)ti.contig; r.proto_start = p; r.pam_start = pamless ? -1 : p + sp->pam_off;
+        r.strand = st ? '-' : '+'; r.pam_index = pamless ? (int8_t)-1 : (int8_t)k; r.pam_len = (uint8_t)pam_len; r.proto_len = (uint8_t)proto_len;
+        static_assert(sizeof(SiteRecord) == 16, "one 16-byte store per record");
+        if (at < a.out_capacity) *reinterpret_cast<uint4*>(&a.out[at]) = *reinterpret_cast<const uint4*>(&r);
+        at++;
+      }
+    }
+  }
+  if (!WRITE && tid == 0) flush_totals();
+}
+
+// Exclusive scan of the workgroups' counts by one workgroup: a stretch per thread, the stretches' sums scanned in LDS.
+constexpr int OFFSETS_THREADS = 1024;
+__global__ __launch_bounds__(OFFSETS_THREADS) void sites_offsets_kernel(const uint32_t* wg_count, uint64_t* wg_offset, uint32_t n) {
+  __shared__ uint64_t s_sum[OFFSETS_THREADS];
+  const uint32_t tid = threadIdx.x;
+  const uint32_t per = (n + OFFSETS_THREADS - 1) / OFFSETS_THREADS;
+  const uint64_t b = (uint64_t)tid * per, e = b + per < n ? b + per : n;
+  uint64_t sum = 0;
+  for (uint64_t i = b; i < e; i++) sum += wg_count[i];
+  s_sum[tid] = sum;
+  __syncthreads();
+  for (uint32_t d = 1; d < OFFSETS_THREADS; d <<= 1) {      // inclusive scan, Hillis-Steele
+    const uint64_t add = tid >= d ? s_sum[tid - d] : 0;
+    __syncthreads();
+    s_sum[tid] += add;
+    __syncthreads();
+  }
+  uint64_t run = s_sum[tid] - sum;
+  for (uint64_t i = b; i < e; i++) { wg_offset[i] = run; run += wg_count[i]; }
+  if (tid == OFFSETS_THREADS - 1) wg_offset[n] = s_sum[tid];
+}
+
+}  // namespace
+
+hipError_t launch_sites_count(const SitesArgs& a, hipStream_t stream) {
+  if (a.n_segs == 0) return hipSuccess;
+  const uint32_t n_blocks = (a.n_segs + a.segs_per_wg - 1) / a.segs_per_wg;
+  hipLaunchKernelGGL(sites_kernel<false>, dim3(n_blocks), dim3(SITES_BLOCK_WORDS), 0, stream, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_sites_offsets(const uint32_t* wg_count, uint64_t* wg_offset, uint32_t n, hipStream_t stream) {
+  hipLaunchKernelGGL(sites_offsets_kernel, dim3(1), dim3(OFFSETS_THREADS), 0, stream, wg_count, wg_offset, n);
+  return hipGetLastError();
+}
+
+hipError_t launch_sites_write(const SitesArgs& a, hipStream_t stream) {
+  if (a.n_segs == 0) return hipSuccess;
+  const uint32_t n_blocks = (a.n_segs + a.segs_per_wg - 1) / a.segs_per_wg;
+  hipLaunchKernelGGL(sites_kernel<true>, dim3(n_blocks), dim3(SITES_BLOCK_WORDS), 0, stream, a);
+  return hipGetLastError();
+}
+
+}  // namespace calitas

@@ -310,3 +310,112 @@ def align_to_reference(input_path, ref, output_path=None, window_size=None, max_
     finally:
         if own:
             ctx.close()
+
+
+# ---- FindGuides: the sites of an IUPAC pattern as guides a search takes (no reference counterpart) ----
+
+GUIDE_COLUMNS = ["guide_id", "chromosome", "start", "end", "strand", "pam_index", "guide", "pam_sequence"]
+_RC = str.maketrans("ACGTU", "TGCAA")
+
+
+class GuideSite:
+    """One site of Context.find_sites as a guide: `guide` is the `-i` string a search takes -- the protospacer as it reads on the site's
+    strand, upper case, with the PATTERN's matched PAM in lower case behind it (in front of it for a 5' PAM) -- and pam_sequence the
+    genomic PAM bases on that strand; [start, end) is the footprint (protospacer + PAM), 0-based half-open."""
+    __slots__ = ("chromosome", "start", "end", "strand", "pam_index", "guide", "pam_sequence", "protospacer_start")
+
+    def __init__(self, *v):
+        for k, x in zip(self.__slots__, v):
+            setattr(self, k, x)
+
+    @property
+    def guide_id(self):
+        return "%s:%d:%s" % (self.chromosome, self.start, self.strand)
+
+    def row(self):
+        return [self.guide_id, self.chromosome, self.start, self.end, self.strand, self.pam_index, self.guide, self.pam_sequence]
+
+
+def find_guides(ctx, pattern, chrom=None, start=0, end=None, host=False):
+    """Context.find_sites turned into guides: a list of GuideSite in the sites' order.  pattern: a Guide or its `-i` string."""
+    if not isinstance(pattern, Guide):
+        pattern = Guide(pattern)
+    sites = ctx.find_sites(pattern, chrom, start, end, host=host)
+    out = []
+    L = pattern.protospacer_length
+    bounds = {}
+    for s in sites:                                    # one fetch per contig: the stretch its footprints cover
+        c, ps, pm, pl = int(s["contig_index"]), int(s["protospacer_start"]), int(s["pam_start"]), int(s["pam_length"])
+        lo, hi = (ps, ps + L) if pm < 0 else (min(ps, pm), max(ps + L, pm + pl))
+        b = bounds.get(c)
+        bounds[c] = (lo, hi) if b is None else (min(b[0], lo), max(b[1], hi))
+    text = {c: (lo, ctx.fetch_bases(c, lo, hi - lo)) for c, (lo, hi) in bounds.items()}
+    for s in sites:
+        c, ps, pm, pl = int(s["contig_index"]), int(s["protospacer_start"]), int(s["pam_start"]), int(s["pam_length"])
+        minus = s["strand"] == b"-"
+        off, t = text[c]
+        proto = t[ps - off:ps - off + L]
+        pam_seq = t[pm - off:pm - off + pl] if pm >= 0 else ""
+        if minus:
+            proto, pam_seq = proto.translate(_RC)[::-1], pam_seq.translate(_RC)[::-1]
+        proto = proto.replace("U", "T")               # an ACGT guide
+        k = int(s["pam_index"])
+        pam = pattern.pams[k] if k >= 0 else ""
+        lo, hi = (ps, ps + L) if pm < 0 else (min(ps, pm), max(ps + L, pm + pl))
+        out.append(GuideSite(ctx.contig_names[c], lo, hi, "-" if minus else "+", k, (pam + proto) if pattern.pam_is_five_prime else (proto + pam),
+                             pam_seq, ps))
+    return out
+
+
+def guide_counts(ctx, guides, params, batch=64):
+    """Off-target tables of distinct `-i` strings: {string: table of Context.search_counts}, searched in batches (search_counts_batch
+    takes guides of one length, at most 64 at a time)."""
+    by_len = {}
+    for g in dict.fromkeys(guides):
+        by_len.setdefault(len(g), []).append(g)
+    tables = {}
+    for same in by_len.values():
+        for b in range(0, len(same), batch):
+            part = same[b:b + batch]
+            for g, t in zip(part, ctx.search_counts_batch([Guide(g) for g in part], params)):
+                tables[g] = t
+    return tables
+
+
+def guides_tsv(rows, tables=None):
+    """The FindGuides table: GUIDE_COLUMNS, one row per GuideSite; with tables (guide_counts) also hits -- the table's sum -- and
+    hits_mm0 .. hits_mmE, the hits per number of protospacer mismatches, summed over strands, gaps and PAM mismatches."""
+    header = list(GUIDE_COLUMNS)
+    n_mm = 0
+    if tables is not None:
+        n_mm = max([t.shape[1] for t in tables.values()], default=1)
+        header += ["hits"] + ["hits_mm%d" % m for m in range(n_mm)]
+    lines = ["\t".join(header)]
+    for r in rows:
+        f = [str(x) for x in r.row()]
+        if tables is not None:
+            t = tables[r.guide]
+            f += [str(int(t.sum()))] + [str(int(t[:, m].sum())) if m < t.shape[1] else "0" for m in range(n_mm)]
+        lines.append("\t".join(f))
+    return "\n".join(lines) + "\n"
+
+
+def find_guides_tool(ref, pattern, auxiliary_pams=(), chrom=None, start=0, end=None, output=None, counts=False, device=0, **search):
+    """`python -m calitas_amd FindGuides`: the guides of a region as a TSV (guides_tsv); counts=True: every distinct guide also goes
+    through the off-target search with the SearchReference flags in `search` (make_params names).  device -1: the host twin of the
+    enumeration (no GPU; not with counts).  Returns the text."""
+    if counts and device < 0:
+        raise ValueError("--counts searches on the GPU: it cannot run with --device -1")
+    pat = Guide(pattern, auxiliary_pams)
+    ctx = Context(device)
+    try:
+        ctx.set_reference_fasta(ref)
+        rows = find_guides(ctx, pat, chrom, start, end, host=device < 0)
+        tables = guide_counts(ctx, [r.guide for r in rows], make_params(**search)) if counts else None
+        text = guides_tsv(rows, tables)
+        if output is not None:
+            with open(output, "w") as f:
+                f.write(text)
+        return text
+    finally:
+        ctx.close()

@@ -269,6 +269,45 @@ int calitas_search_counts(calitas_ctx* ctx, const calitas_guide_t* guide, const 
 int calitas_search_counts_batch(calitas_ctx* ctx, int32_t n_guides, const calitas_guide_t* guides, const calitas_params_t* params,
                                 calitas_counts_t** out);
 
+/* Guide sites ---------------------------------------------------------------------------------------------------- */
+
+/* One place of the resident reference where a guide can be cut out: an exact match of an IUPAC pattern.  The pattern is a
+ * calitas_guide_t read as a pattern: protospacer of any IUPAC letters (NNNNNNNNNNNNNNNNNNNN is the usual case), 0..8 PAMs of any
+ * lengths, pam_is_5prime as in a guide, cli_length ignored.  In strand space PAM k's pattern is protospacer + pam_k (3' PAM),
+ * pam_k + protospacer (5' PAM) or the protospacer alone; a site is a (contig, strand, protospacer position) where some PAM's pattern
+ * matches the text read on that strand ('-': the reverse complement of the footprint), every base of the footprint being a plain
+ * A C G T (either case) or U and lying in the IUPAC set of its pattern letter.  pam_index is the first PAM that matches; there is
+ * one record per (contig, strand, protospacer start), never one per PAM.
+ * Not a `-d 0` search: a search lets an ambiguity code of the REFERENCE (an R in the FASTA) pair with a compatible guide base; a site
+ * never contains one (nor an N, nor padding), because a guide cut from it would not be an ACGT guide. */
+typedef struct {
+  int32_t contig_index;
+  int32_t protospacer_start;   /* leftmost base of the protospacer, forward coordinates, 0-based */
+  int32_t pam_start;           /* leftmost base of the matched PAM, forward coordinates; -1 for a PAM-less pattern */
+  int8_t strand;               /* '+' or '-' */
+  int8_t pam_index;            /* -1 for a PAM-less pattern */
+  uint8_t pam_length;
+  uint8_t protospacer_length;
+} calitas_site_t;
+
+/* All sites of `pattern` in a region, sorted by contig_index, protospacer_start, '+' before '-'; the same bytes from call to call.
+ * Region: chrom_index (< 0: every contig) and [start, end) in 0-based contig coordinates, end == 0 meaning the contig's end (with
+ * chrom_index < 0 the bounds apply to every contig, cut to its length); a site counts when its whole footprint -- protospacer plus
+ * the matching PAM -- lies inside, and a PAM whose footprint would leave the region does not match there.  A region that needs an
+ * absent contig fails with CALITAS_EINVAL, as a search does.  Runs on the device: one kernel matches 32 start positions per lane on the
+ * bit-planes the scan streams, in two passes (count, then write at scanned offsets: no sort).  sites == NULL: *n_sites only, after the
+ * first pass.  *sites is one block for calitas_free.  No reference counterpart. */
+int calitas_find_sites(calitas_ctx* ctx, const calitas_guide_t* pattern, int32_t chrom_index, uint64_t start, uint64_t end,
+                       calitas_site_t** sites, uint64_t* n_sites);
+/* The first pass alone: *n_sites and, when per_contig_strand is not NULL, the sites per contig and strand ([n_contigs][2], '+'
+ * first; contigs outside the region get 0).  No reference counterpart. */
+int calitas_count_sites(calitas_ctx* ctx, const calitas_guide_t* pattern, int32_t chrom_index, uint64_t start, uint64_t end,
+                        uint64_t* per_contig_strand, uint64_t* n_sites);
+/* The host twin of calitas_find_sites: the same records from a base-by-base walk over the packed reference of the context, which may
+ * be host-only (calitas_create(-1)) -- the second implementation the tests hold the kernel against.  No reference counterpart. */
+int calitas_find_sites_host(const calitas_ctx* ctx, const calitas_guide_t* pattern, int32_t chrom_index, uint64_t start, uint64_t end,
+                            calitas_site_t** sites, uint64_t* n_sites);
+
 /* SequentialGuideAligner.align on explicit (guide, target) pairs -- the per-task call of PairwiseAlignSequences
  * (PairwiseAlignSequences.scala:64 -> alignBest, SequentialGuideAligner.scala:333-345) and AlignToReference
  * (AlignToReference.scala:114-135 -> alignToRef / alignToRefBest, SequentialGuideAligner.scala:359-418).  Task t aligns
