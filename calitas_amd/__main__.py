@@ -4,7 +4,7 @@ AlignToReference.scala:34-51, PairwiseAlignSequences.scala:25-33, PrepareVcf.sca
 import argparse
 import sys
 
-from .aligner import Defaults, SearchReference
+from .aligner import Defaults, ScoreModel, SearchReference
 from .tools import align_to_reference, find_guides_tool, pairwise_align_sequences
 from .variants import prepare_vcf
 
@@ -39,6 +39,9 @@ def main(argv=None):
     sr.add_argument("-c", "--chrom")
     sr.add_argument("--counts", action="store_true",
                     help="write the off-target table (guide_id strand guide_mm guide_gaps pam_mm hits; non-zero cells) instead of hits.txt")
+    sr.add_argument("--scores", metavar="MODEL",
+                    help="write the specificity score under the model file (guide_id rows perfect offtarget_sum_q32 max_q32 specificity) "
+                         "instead of hits.txt; with --counts the table's TSV follows it behind an empty line")
     _costs(sr)
 
     a2r = sub.add_parser("AlignToReference")
@@ -70,6 +73,8 @@ def main(argv=None):
     fg.add_argument("-o", "--output")
     fg.add_argument("--counts", action="store_true",
                     help="search every distinct guide of the table (the flags below) and add hits, hits_mm0 .. hits_mmE per row")
+    fg.add_argument("--scores", metavar="MODEL",
+                    help="like --counts, and score every guide's hits under the model file: the columns perfect and specificity follow")
     fg.add_argument("-d", "--max-guide-diffs", type=int, default=Defaults.MaxGuideDiffs)
     fg.add_argument("-p", "--max-pam-mismatches", type=int, default=Defaults.MaxPamMismatches)
     fg.add_argument("-g", "--max-gaps-between-guide-and-pam", type=int, default=Defaults.MaxGapsBetweenGuideAndPam)
@@ -86,13 +91,15 @@ def main(argv=None):
 
     a = top.parse_args(argv)
     if a.tool == "SearchReference":
+        if a.scores is not None and a.variants is not None:
+            top.error("--scores covers the reference-genome branch only (no --variants)")
         SearchReference(guide=a.guide, guide_id=a.guide_id, ref=a.ref, output=a.output, auxiliary_pams=a.auxiliary_pams,
                         window_size=a.window_size, max_guide_diffs=a.max_guide_diffs, max_pam_mismatches=a.max_pam_mismatches,
                         max_gaps_between_guide_and_pam=a.max_gaps_between_guide_and_pam, max_total_diffs=a.max_total_diffs,
                         max_overlap=a.max_overlap, guide_mismatch_net_cost=a.guide_mismatch_net_cost,
                         pam_mismatch_net_cost=a.pam_mismatch_net_cost, genome_gap_net_cost=a.genome_gap_net_cost,
                         guide_gap_net_cost=a.guide_gap_net_cost, chrom=a.chrom, variants=a.variants, max_variants=a.max_variants,
-                        device=a.device).execute(counts=a.counts)
+                        device=a.device).execute(counts=a.counts, scores=ScoreModel.read(a.scores) if a.scores is not None else None)
     elif a.tool == "AlignToReference":
         text = align_to_reference(a.input, a.ref, a.output, window_size=a.window_size, max_guide_diffs=a.max_guide_diffs,
                                   max_pam_mismatches=a.max_pam_mismatches, max_gaps_between_guide_and_pam=a.max_gaps_between_guide_and_pam,
@@ -102,7 +109,7 @@ def main(argv=None):
         if a.output is None:
             sys.stdout.write(text)
     elif a.tool == "FindGuides":
-        text = find_guides_tool(a.ref, a.guide, a.auxiliary_pams, chrom=a.chrom, start=a.start, end=a.end, output=a.output, counts=a.counts,
+        text = find_guides_tool(a.ref, a.guide, a.auxiliary_pams, chrom=a.chrom, start=a.start, end=a.end, output=a.output, counts=a.counts, scores=a.scores,
                                 device=a.device, max_guide_diffs=a.max_guide_diffs, max_pam_mismatches=a.max_pam_mismatches,
                                 max_gaps_between_guide_and_pam=a.max_gaps_between_guide_and_pam, max_total_diffs=a.max_total_diffs,
                                 max_overlap=a.max_overlap, guide_mismatch_net_cost=a.guide_mismatch_net_cost,

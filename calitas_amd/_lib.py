@@ -66,12 +66,23 @@ class CountsT(ctypes.Structure):
                 ("counts", ctypes.POINTER(ctypes.c_uint64))]
 
 
+class ScoreModelT(ctypes.Structure):
+    _fields_ = [("protospacer_length", ctypes.c_int32), ("gap", ctypes.c_uint32), ("pam_mismatch", ctypes.c_uint32),
+                ("mismatch", ctypes.POINTER(ctypes.c_uint32))]
+
+
+class ScoresT(ctypes.Structure):
+    _fields_ = [("rows", ctypes.c_uint64), ("perfect", ctypes.c_uint64), ("sum_q32", ctypes.c_uint64), ("max_q32", ctypes.c_uint64),
+                ("table", CountsT)]
+
+
 # every symbol include/calitas_hip.h declares
 SYMBOLS = ["calitas_create", "calitas_destroy", "calitas_last_error", "calitas_free", "calitas_set_reference",
            "calitas_set_reference_fasta", "calitas_save_index", "calitas_load_index", "calitas_reference_info", "calitas_contig_name", "calitas_genome_build", "calitas_fetch_bases", "calitas_expand_rows",
            "calitas_window_table", "calitas_search", "calitas_search_hits", "calitas_search_hits_stream", "calitas_search_hits_into", "calitas_pin_host", "calitas_unpin_host", "calitas_alloc_host", "calitas_release_parked", "calitas_search_hits_batch", "calitas_get_timing", "calitas_scan_candidates", "calitas_scan_candidates_columnwise", "calitas_contig_packed_base", "calitas_reference_tiles", "calitas_window_filter", "calitas_hits_tsv", "calitas_hits_tsv_ext", "calitas_search_variants", "calitas_search_variants_into", "calitas_vcf_identifier", "calitas_vcf_records",
            "calitas_padded_strings", "calitas_align_windows", "calitas_padded_strings_target", "calitas_version", "calitas_switches", "calitas_reap_wait",
            "calitas_search_counts", "calitas_search_counts_batch", "calitas_hits_counts",
+           "calitas_search_scores", "calitas_search_scores_batch", "calitas_hits_scores",
            "calitas_find_sites", "calitas_count_sites", "calitas_find_sites_host"]
 
 if not os.path.exists(LIB_PATH):
@@ -136,6 +147,12 @@ lib.calitas_find_sites.argtypes = [ctypes.c_void_p, ctypes.POINTER(GuideT), ctyp
 lib.calitas_find_sites_host.argtypes = lib.calitas_find_sites.argtypes
 lib.calitas_count_sites.argtypes = [ctypes.c_void_p, ctypes.POINTER(GuideT), ctypes.c_int32, ctypes.c_uint64, ctypes.c_uint64,
                                     ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]
+lib.calitas_search_scores.argtypes = [ctypes.c_void_p, ctypes.POINTER(GuideT), ctypes.POINTER(ParamsT), ctypes.POINTER(ScoreModelT),
+                                      ctypes.POINTER(ctypes.POINTER(ScoresT))]
+lib.calitas_search_scores_batch.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.POINTER(GuideT), ctypes.POINTER(ParamsT),
+                                            ctypes.POINTER(ScoreModelT), ctypes.POINTER(ctypes.POINTER(ScoresT))]
+lib.calitas_hits_scores.argtypes = [ctypes.c_void_p, ctypes.POINTER(GuideT), ctypes.POINTER(ParamsT), ctypes.POINTER(ScoreModelT),
+                                    ctypes.POINTER(AlnT), ctypes.c_uint64, ctypes.POINTER(ctypes.POINTER(ScoresT))]
 lib.calitas_pin_host.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64]
 lib.calitas_unpin_host.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
 lib.calitas_genome_build.restype = ctypes.c_char_p

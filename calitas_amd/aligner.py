@@ -10,7 +10,7 @@ import ctypes
 import time
 
 from . import _lib
-from ._lib import AlnT, CalitasError, CountsT, GuideT, ParamsT, SiteT, TimingT, lib
+from ._lib import AlnT, CalitasError, CountsT, GuideT, ParamsT, ScoreModelT, ScoresT, SiteT, TimingT, lib
 
 
 class Defaults:  # SequentialGuideAligner.scala:17-28
@@ -533,6 +533,54 @@ class Context:
                                                     table.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), ctypes.byref(n)))
         return n.value, table[:len(self.contig_names)]
 
+    @staticmethod
+    def _take_scores(ptr):
+        """A calitas_scores_t block as a Scores object; the block is freed."""
+        import numpy as np
+        try:
+            c = ptr.contents
+            t = c.table
+            shape = (2, t.n_mm, t.n_gaps, t.n_pam)
+            n = 2 * t.n_mm * t.n_gaps * t.n_pam
+            table = np.ctypeslib.as_array(t.counts, shape=(n,)).astype(np.uint64).reshape(shape)   # (astype copies)
+            if int(table.sum()) != c.rows or t.rows != c.rows or c.perfect > c.rows:
+                raise CalitasError(_lib.EHIP, "the scores block does not add up to its rows")
+            return Scores(int(c.rows), int(c.perfect), int(c.sum_q32), int(c.max_q32), table)
+        finally:
+            lib.calitas_free(ptr)
+
+    def search_scores(self, guide, params, model):
+        """calitas_search_scores: search_counts plus the specificity score of the guide's hits under `model` (a ScoreModel of the
+        guide's protospacer length) -- a Scores object.  Equal to scores_of_rows of the hits.txt search_hits gives for the same guide
+        and params, window range included; no text is built or copied."""
+        g = guide.to_c()
+        m = model.to_c()
+        out = ctypes.POINTER(ScoresT)()
+        _lib.check(self._h, lib.calitas_search_scores(self._h, ctypes.byref(g), ctypes.byref(params), ctypes.byref(m), ctypes.byref(out)))
+        return self._take_scores(out)
+
+    def search_scores_batch(self, guides, params, model):
+        """calitas_search_scores_batch: a list of Scores, one per guide (all of one length: one model serves them), pipelined on the
+        device like search_counts_batch."""
+        n = len(guides)
+        keep = [g.to_c() for g in guides]
+        garr = (GuideT * n)(*keep)
+        m = model.to_c()
+        out = (ctypes.POINTER(ScoresT) * n)()
+        _lib.check(self._h, lib.calitas_search_scores_batch(self._h, n, garr, ctypes.byref(params), ctypes.byref(m), out))
+        return [self._take_scores(out[i]) for i in range(n)]
+
+    def hits_scores(self, guide, params, model, alignments):
+        """calitas_hits_scores: removeOverlaps on a guide's alignments (as search() returns them), then table and score -- the host
+        stage, usable on a host-only context."""
+        g = guide.to_c()
+        m = model.to_c()
+        n = len(alignments)
+        arr = (AlnT * max(1, n))(*[a.to_c() for a in alignments])
+        out = ctypes.POINTER(ScoresT)()
+        _lib.check(self._h, lib.calitas_hits_scores(self._h, ctypes.byref(g), ctypes.byref(params), ctypes.byref(m), arr, n, ctypes.byref(out)))
+        return self._take_scores(out)
+
     def timing(self):
         t = TimingT()
         _lib.check(self._h, lib.calitas_get_timing(self._h, ctypes.byref(t)))
@@ -662,9 +710,39 @@ class SearchReference:
             if own:
                 ctx.close()
 
-    def execute(self, counts=False):
-        """counts=True (`--counts`): the table as a TSV (counts_tsv) instead of hits.txt."""
-        text = counts_tsv(self.guide_id, self.counts()) if counts else self.run()[0]
+    def scores(self, model):
+        """The specificity score instead of hits.txt (Context.search_scores): a Scores object."""
+        if self.variants is not None:
+            raise ValueError("scores() covers the reference-genome branch only (no --variants)")
+        ctx = self.context
+        own = ctx is None
+        if own:
+            ctx = Context(self.device)
+            ctx.set_reference_fasta(self.ref)
+        try:
+            chrom_index = -1
+            if self.chrom is not None:
+                if self.chrom not in ctx.contig_names:
+                    raise ValueError("Unknown chromosome: %s" % self.chrom)
+                chrom_index = ctx.contig_names.index(self.chrom)
+            params = make_params(chrom_index=chrom_index, **self._kw)
+            t0 = time.perf_counter()
+            got = ctx.search_scores(self.query, params, model)
+            self.timing = ctx.timing()
+            self.wall_ms = (time.perf_counter() - t0) * 1e3
+            return got
+        finally:
+            if own:
+                ctx.close()
+
+    def execute(self, counts=False, scores=None):
+        """counts=True (`--counts`): the table as a TSV (counts_tsv) instead of hits.txt.  scores=ScoreModel (`--scores MODEL`): the
+        scores TSV (scores_tsv); with counts as well, the counts TSV of the same pass's table follows it behind an empty line."""
+        if scores is not None:
+            got = self.scores(scores)
+            text = scores_tsv(self.guide_id, got) + ("\n" + counts_tsv(self.guide_id, got.table) if counts else "")
+        else:
+            text = counts_tsv(self.guide_id, self.counts()) if counts else self.run()[0]
         if self.output is None:
             import sys
             sys.stdout.write(text)
@@ -717,6 +795,193 @@ def read_counts_tsv(path_or_text, shape):
         _, s, m, g, p, n = ln.split("\t")
         table[{"+": 0, "-": 1}[s], int(m), int(g), int(p)] += np.uint64(int(n))
     return table
+
+
+# ---- the specificity score (include/calitas_hip.h has the contract) ----
+
+SCORES_COLUMNS = ("guide_id", "rows", "perfect", "offtarget_sum_q32", "max_q32", "specificity")
+Q16_ONE = 65536
+_LETTER = {"A": 0, "C": 1, "G": 2, "T": 3}
+_MODEL_LETTERS = "ACGT"
+
+
+def _q16(x):
+    """A decimal of a model file in [0, 1] as Q16: floor(x * 65536 + 0.5) in double."""
+    import math
+    v = float(x)
+    if not 0.0 <= v <= 1.0:
+        raise ValueError("a factor of a score model lies in [0, 1], not %r" % (x,))
+    return int(math.floor(v * 65536.0 + 0.5))
+
+
+class ScoreModel:
+    """The weights of a specificity score for protospacers of L bases, all Q16 (65536 = 1.0, none above it): mismatch[L][5][5] by guide
+    position (0-based, the upper-case letters of the guide as written, left to right), guide letter and target letter (A 0, C 1, G 2,
+    T 3, anything else 4), one gap factor, one pam_mismatch factor.  The library ships no published table: read() loads any table of
+    this product form from a TSV with `#` comments and the lines
+
+        length<TAB>L
+        gap<TAB>x
+        pam_mismatch<TAB>x
+        mismatch<TAB>position (1-based, or *)<TAB>guide_base (A C G T, `other`, or *)<TAB>target_base (likewise)<TAB>x
+
+    where x is a decimal in [0, 1], entries not given are 1.0 and later lines override earlier ones."""
+
+    def __init__(self, L, mismatch, gap=Q16_ONE, pam_mismatch=Q16_ONE):
+        import numpy as np
+        self.L = int(L)
+        self.mismatch = np.ascontiguousarray(mismatch, dtype=np.uint32)
+        if self.mismatch.shape != (self.L, 5, 5):
+            raise ValueError("mismatch must have shape (L, 5, 5) = (%d, 5, 5), not %r" % (self.L, self.mismatch.shape))
+        self.gap, self.pam_mismatch = int(gap), int(pam_mismatch)
+
+    @classmethod
+    def uniform(cls, L, mismatch=Q16_ONE, gap=Q16_ONE, pam_mismatch=Q16_ONE):
+        """Every mismatch the same factor, whatever the position and the letters."""
+        import numpy as np
+        return cls(L, np.full((int(L), 5, 5), int(mismatch), dtype=np.uint32), gap, pam_mismatch)
+
+    def to_c(self):
+        m = ScoreModelT()
+        m.protospacer_length, m.gap, m.pam_mismatch = self.L, self.gap & 0xFFFFFFFF, self.pam_mismatch & 0xFFFFFFFF
+        m.mismatch = self.mismatch.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32))
+        m._keep = self.mismatch
+        return m
+
+    @classmethod
+    def read(cls, path):
+        import numpy as np
+        L, gap, pam, lines = None, Q16_ONE, Q16_ONE, []
+        with open(path) as f:
+            for ln in f:
+                ln = ln.split("#", 1)[0].strip()
+                if not ln:
+                    continue
+                fld = ln.split("\t")
+                if fld[0] == "length" and len(fld) == 2:
+                    L = int(fld[1])
+                elif fld[0] == "gap" and len(fld) == 2:
+                    gap = _q16(fld[1])
+                elif fld[0] == "pam_mismatch" and len(fld) == 2:
+                    pam = _q16(fld[1])
+                elif fld[0] == "mismatch" and len(fld) == 5:
+                    lines.append(fld[1:])
+                else:
+                    raise ValueError("%s: not a line of a score model: %r" % (path, ln))
+        if L is None or not 1 <= L <= 32:
+            raise ValueError("%s: a score model needs a `length` line with 1 <= L <= 32" % path)
+        mm = np.full((L, 5, 5), Q16_ONE, dtype=np.uint32)
+
+        def axis(word, n, names):
+            if word == "*":
+                return range(n)
+            if names is None:
+                k = int(word) - 1
+            else:
+                k = 4 if word.lower() == "other" else names.find(word.upper()) if len(word) == 1 else -1
+            if not 0 <= k < n:
+                raise ValueError("%s: %r is not a position / base of a score model" % (path, word))
+            return [k]
+        for pos, gb, tb, x in lines:
+            v = _q16(x)
+            for i in axis(pos, L, None):
+                for g in axis(gb, 5, _MODEL_LETTERS):
+                    for t in axis(tb, 5, _MODEL_LETTERS):
+                        mm[i, g, t] = v
+        return cls(L, mm, gap, pam)
+
+    def write(self, path):
+        """The model as a file read() gives back exactly: every factor as the shortest decimal that rounds to it."""
+        def dec(q):
+            for digits in range(1, 12):
+                t = "%.*f" % (digits, q / 65536.0)
+                if _q16(t) == q:
+                    return t
+            raise ValueError("factor %r is not a Q16 value in [0, 65536]" % (q,))
+        names = list(_MODEL_LETTERS) + ["other"]
+        with open(path, "w") as f:
+            f.write("# calitas score model: Q16 factors as decimals (x -> floor(x * 65536 + 0.5)); entries not given are 1.0\n")
+            f.write("length\t%d\ngap\t%s\npam_mismatch\t%s\n" % (self.L, dec(self.gap), dec(self.pam_mismatch)))
+            for i in range(self.L):
+                for g in range(5):
+                    for t in range(5):
+                        if int(self.mismatch[i, g, t]) != Q16_ONE:
+                            f.write("mismatch\t%d\t%s\t%s\t%s\n" % (i + 1, names[g], names[t], dec(int(self.mismatch[i, g, t]))))
+
+
+class Scores:
+    """What a guide's hits add up to under a ScoreModel: rows (all hits), perfect (hits with total_mm_plus_gaps == 0: counted, not
+    scored), sum_q32 and max_q32 (sum and maximum of the other hits' scores, 2^32 = 1.0) and the table of search_counts."""
+    __slots__ = ("rows", "perfect", "sum_q32", "max_q32", "table")
+
+    def __init__(self, rows, perfect, sum_q32, max_q32, table):
+        self.rows, self.perfect, self.sum_q32, self.max_q32, self.table = rows, perfect, sum_q32, max_q32, table
+
+    @property
+    def offtarget_sum(self):
+        return self.sum_q32 / 2.0 ** 32
+
+    @property
+    def specificity(self):
+        return 2.0 ** 32 / (2.0 ** 32 + self.sum_q32)
+
+    def __add__(self, o):
+        """Window ranges, contigs, ranks of one job: everything adds, max_q32 takes the maximum."""
+        return Scores(self.rows + o.rows, self.perfect + o.perfect, self.sum_q32 + o.sum_q32, max(self.max_q32, o.max_q32), self.table + o.table)
+
+    def __eq__(self, o):
+        import numpy as np
+        return (isinstance(o, Scores) and (self.rows, self.perfect, self.sum_q32, self.max_q32) == (o.rows, o.perfect, o.sum_q32, o.max_q32)
+                and self.table.shape == o.table.shape and bool(np.array_equal(self.table, o.table)))
+
+    __hash__ = None
+
+    def __repr__(self):
+        return "Scores(rows=%d, perfect=%d, sum_q32=%d, max_q32=%d)" % (self.rows, self.perfect, self.sum_q32, self.max_q32)
+
+
+def score_of_row(row, model):
+    """The contract on one hits.txt row (a read_hits dict), in plain Python integers: None for a perfect row, else its score."""
+    pg, pa, pt = row["padded_guide"], row["padded_alignment"], row["padded_target"]
+    n_upper = sum(1 for c in pg if "A" <= c <= "Z")
+    if n_upper != model.L:
+        raise ValueError("a row with %d upper-case guide letters cannot be scored by a model of length %d" % (n_upper, model.L))
+    if int(row["total_mm_plus_gaps"]) == 0:
+        return None
+    s, i = 1 << 32, 0
+    for g, a, t in zip(pg, pa, pt):
+        if not "A" <= g <= "Z":
+            continue
+        if a == ".":
+            s = (s * int(model.mismatch[i, _LETTER.get(g, 4), _LETTER.get(t, 4)])) >> 16
+        i += 1
+    for _ in range(int(row["guide_gaps"])):
+        s = (s * model.gap) >> 16
+    for _ in range(int(row["pam_mm"])):
+        s = (s * model.pam_mismatch) >> 16
+    return s
+
+
+def scores_of_rows(rows, model, shape=None):
+    """What search_scores returns, from hits.txt rows (read_hits output): the reference implementation of the contract.  shape: the
+    table's extents (as for counts_of_rows); without it the table is a 1-cell array holding the row count."""
+    import numpy as np
+    perfect, total, top = 0, 0, 0
+    for r in rows:
+        s = score_of_row(r, model)
+        if s is None:
+            perfect += 1
+        else:
+            total += s
+            top = max(top, s)
+    table = counts_of_rows(rows, shape) if shape is not None else np.array([len(rows)], dtype=np.uint64)
+    return Scores(len(rows), perfect, total, top, table)
+
+
+def scores_tsv(guide_id, scores):
+    """`SearchReference --scores MODEL`: header guide_id rows perfect offtarget_sum_q32 max_q32 specificity, then one line."""
+    return "\t".join(SCORES_COLUMNS) + "\n" + "%s\t%d\t%d\t%d\t%d\t%.6f\n" % (guide_id, scores.rows, scores.perfect, scores.sum_q32,
+                                                                               scores.max_q32, scores.specificity)
 
 
 def read_hits(path_or_text):

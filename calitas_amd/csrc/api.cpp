@@ -764,6 +764,71 @@ int calitas_find_sites_host(const calitas_ctx* ctx, const calitas_guide_t* patte
   return calitas_find_sites_host_impl(ctx, pattern, chrom_index, start, end, sites, n_sites);
 }
 
+// A guide's scores as the ABI hands them over: struct, table and cells in one block of the library's.
+static calitas_scores_t* scores_block(const CountsShape& shape, const uint64_t* table, uint64_t rows, const ScoreWords& w) {
+  const size_t cells = shape.cells();
+  calitas_scores_t* c = (calitas_scores_t*)out_alloc(sizeof(calitas_scores_t) + cells * sizeof(uint64_t));
+  if (!c) return nullptr;
+  c->rows = rows; c->perfect = w.perfect; c->sum_q32 = w.sum_q32; c->max_q32 = w.max_q32;
+  c->table.n_mm = shape.n_mm; c->table.n_gaps = shape.n_gaps; c->table.n_pam = shape.n_pam; c->table.rows = rows;
+  c->table.counts = reinterpret_cast<uint64_t*>(c + 1);
+  std::memcpy(c->table.counts, table, cells * sizeof(uint64_t));
+  return c;
+}
+
+// The guide and the model of a score call, validated against each other; "" or the reason for CALITAS_EINVAL.
+static std::string score_inputs(const calitas_guide_t& guide, const calitas_score_model_t* model, GuideHost& gh, ScoreModelHost& mh) {
+  std::string e = make_guide_host(guide, gh);
+  if (e.empty()) e = make_score_model(model, (int)gh.protospacer.size(), mh);
+  return e;
+}
+
+int calitas_search_scores(calitas_ctx* ctx, const calitas_guide_t* guide, const calitas_params_t* params, const calitas_score_model_t* model,
+                          calitas_scores_t** out) {
+  if (!ctx) return CALITAS_EINVAL;
+  if (!guide || !params || !model || !out) return fail(ctx, CALITAS_EINVAL, "NULL argument");
+  *out = nullptr;
+  GuideHost gh;
+  ScoreModelHost mh;
+  const std::string e = score_inputs(*guide, model, gh, mh);
+  if (!e.empty()) return fail(ctx, CALITAS_EINVAL, e);
+  CountsShape shape;
+  std::vector<uint64_t> table;
+  uint64_t rows = 0;
+  ScoreWords w;
+  const int rc = calitas_search_counts_impl(ctx, guide, params, &shape, &table, &rows, &mh, &w);
+  if (rc) return rc;
+  *out = scores_block(shape, table.data(), rows, w);
+  return *out ? CALITAS_OK : fail(ctx, CALITAS_EINVAL, "out of memory");
+}
+
+int calitas_search_scores_batch(calitas_ctx* ctx, int32_t n_guides, const calitas_guide_t* guides, const calitas_params_t* params,
+                                const calitas_score_model_t* model, calitas_scores_t** out) {
+  if (!ctx) return CALITAS_EINVAL;
+  if (n_guides <= 0 || !guides || !params || !model || !out) return fail(ctx, CALITAS_EINVAL, "bad argument");
+  for (int i = 0; i < n_guides; i++) out[i] = nullptr;
+  ScoreModelHost mh;
+  for (int i = 0; i < n_guides; i++) {                        // (all guides of a batch have one length: one model serves them)
+    GuideHost gh;
+    const std::string e = score_inputs(guides[i], model, gh, mh);
+    if (!e.empty()) return fail(ctx, CALITAS_EINVAL, e);
+  }
+  std::vector<std::vector<uint64_t>> tables((size_t)n_guides);
+  std::vector<uint64_t> rows((size_t)n_guides, 0);
+  std::vector<ScoreWords> words((size_t)n_guides);
+  int rc = calitas_search_hits_batch_impl(ctx, n_guides, guides, nullptr, params, nullptr, nullptr, nullptr, nullptr, rows.data(), &tables, &mh, &words);
+  for (int i = 0; i < n_guides && !rc; i++) {
+    GuideHost gh;
+    CountsShape shape;
+    std::string e = make_guide_host(guides[i], gh);
+    if (e.empty()) e = counts_shape(gh, *params, shape);
+    if (!e.empty() || tables[(size_t)i].size() != shape.cells()) rc = fail(ctx, CALITAS_EINVAL, e.empty() ? "a guide's table has another shape than its plan (internal error)" : e);
+    else if (!(out[i] = scores_block(shape, tables[(size_t)i].data(), rows[(size_t)i], words[(size_t)i]))) rc = fail(ctx, CALITAS_EINVAL, "out of memory");
+  }
+  if (rc) for (int i = 0; i < n_guides; i++) { calitas_free(out[i]); out[i] = nullptr; }
+  return rc;
+}
+
 int calitas_scan_candidates(calitas_ctx* ctx, int32_t n_guides, const calitas_guide_t* guides, const calitas_params_t* params,
                             uint32_t** records, uint64_t* n_records) {
   return calitas_scan_candidates_impl(ctx, n_guides, guides, params, records, n_records);
@@ -859,6 +924,28 @@ int calitas_hits_counts(const calitas_ctx* ctx, const calitas_guide_t* guide, co
   e = hits_counts(ctx->ref, gh, *params, alns, n_alns, shape.n_mm, shape.n_gaps, shape.n_pam, table.data(), &rows, ctx->pool);
   if (!e.empty()) return fail(c, CALITAS_EINVAL, e);
   *out = counts_block(shape, table.data(), rows);
+  return *out ? CALITAS_OK : fail(c, CALITAS_EINVAL, "out of memory");
+}
+
+int calitas_hits_scores(const calitas_ctx* ctx, const calitas_guide_t* guide, const calitas_params_t* params, const calitas_score_model_t* model,
+                        const calitas_aln_t* alns, uint64_t n_alns, calitas_scores_t** out) {
+  if (!ctx || !guide || !params || !model || !out || (n_alns && !alns)) return CALITAS_EINVAL;
+  calitas_ctx* c = const_cast<calitas_ctx*>(ctx);
+  *out = nullptr;
+  if (!ctx->has_ref) return fail(c, CALITAS_ESTATE, "calitas_set_reference has not been called");
+  GuideHost gh;
+  ScoreModelHost mh;
+  CountsShape shape;
+  std::string e = score_inputs(*guide, model, gh, mh);
+  if (e.empty()) e = counts_shape(gh, *params, shape);
+  if (!e.empty()) return fail(c, CALITAS_EINVAL, e);
+  std::vector<uint64_t> table(shape.cells(), 0);
+  uint64_t rows = 0;
+  ScoreWords w;
+  e = hits_scores(ctx->ref, gh, *params, mh, alns, n_alns, shape.n_mm, shape.n_gaps, shape.n_pam, table.data(), &rows, &w.perfect, &w.sum_q32, &w.max_q32,
+                  ctx->pool);
+  if (!e.empty()) return fail(c, CALITAS_EINVAL, e);
+  *out = scores_block(shape, table.data(), rows, w);
   return *out ? CALITAS_OK : fail(c, CALITAS_EINVAL, "out of memory");
 }
 

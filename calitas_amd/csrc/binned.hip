@@ -653,12 +653,16 @@ __global__ __launch_bounds__(64 * BIN_WAVES) void bin_rows_kernel(BinArgs a, Mid
 // Counts mode: the bins' kept hits (bin_hits_small_kernel / bin_hits_kernel listed the bins that have any, with their rows' alignments
 // in final order) counted into the call's table instead of being built as rows.  One lane per listed bin (a bin keeps 0-2 hits, at most
 // BIN_ROWS); the cell comes from the same arithmetic the row's length does (hits_dev.hpp: hit_key).  The workgroup that finishes last
-// brings the table to the host and posts what bin_rows_kernel posts when it starts.
-__global__ __launch_bounds__(COUNTS_BLOCK) void bin_counts_kernel(BinArgs a, CountsOut co, RowsArgs o) {
+// brings the table to the host and posts what bin_rows_kernel posts when it starts.  The body is a template over SCORE:
+// bin_counts_kernel is it without the score (what a counts call launches, unchanged), bin_scores_kernel with it.
+template <bool SCORE>
+__device__ __forceinline__ void bin_counts_body(const BinArgs& a, const CountsOut& co, const ScoreArgs& sa, const HitsRef& ref, const RowsArgs& o,
+                                                uint32_t* hist, ScoreLds* sl) {
   CALITAS_TAIL_PRIO();
-  __shared__ uint32_t hist[COUNTS_LDS_CELLS];
+  if (SCORE) score_begin(*sl, sa);
   counts_begin(hist, co);
   const uint32_t n_todo = *a.rows_count;
+  ScoreAcc acc;
   if (*a.flags == 0) {                                     // (a bin declined: the general kernels count this range)
     for (uint32_t it = blockIdx.x * COUNTS_BLOCK + threadIdx.x; it < n_todo; it += gridDim.x * COUNTS_BLOCK) {
       const uint32_t rel = a.rows_list[it];
@@ -670,13 +674,28 @@ __global__ __launch_bounds__(COUNTS_BLOCK) void bin_counts_kernel(BinArgs a, Cou
         const int cell = counts_cell(rp, plus ? 0u : 1u, co.shape);
         if (cell < 0) { atomicOr(a.flags, BIN_FLAG_EXTENT); continue; }
         counts_add(hist, co, cell);
+        if (SCORE) score_hit(*sl, sa, ref, rp, hit_record(rp, a.guides, a.win_base, a.win), a.guides + rp->guide, acc);
       }
     }
   }
+  if (SCORE) score_reduce(*sl, co, acc);
   if (!counts_flush(hist, co)) return;
+  if (SCORE) score_publish(co);
   counts_publish(co);
   if (threadIdx.x >= 64) return;                            // the post: the first wave of the last workgroup
   bin_post<true>(a, o, 0ull, 0u, (int)threadIdx.x);      // no bytes
+}
+
+__global__ __launch_bounds__(COUNTS_BLOCK) void bin_counts_kernel(BinArgs a, CountsOut co, RowsArgs o) {
+  __shared__ uint32_t hist[COUNTS_LDS_CELLS];
+  bin_counts_body<false>(a, co, ScoreArgs{}, HitsRef{}, o, hist, nullptr);
+}
+
+// Score mode: the same lanes over the same bins, and each kept hit's score into the four words behind the cells (hits_dev.hpp: score_hit).
+__global__ __launch_bounds__(COUNTS_BLOCK) void bin_scores_kernel(BinArgs a, CountsOut co, ScoreArgs sa, HitsRef ref, RowsArgs o) {
+  __shared__ uint32_t hist[COUNTS_LDS_CELLS];
+  __shared__ ScoreLds sl;
+  bin_counts_body<true>(a, co, sa, ref, o, hist, &sl);
 }
 
 }  // namespace
@@ -882,14 +901,17 @@ hipError_t binned_rows(const BinnedCall& c, hipEvent_t ev_rows_done, char* host_
   return e == hipSuccess ? launch_rows(c, ba, ma, nullptr, ev_rows_done, host_dst, host_dst_cap) : e;
 }
 
-hipError_t binned_counts(const BinnedCall& c, hipEvent_t ev_done, const CountsShape& shape) {
+hipError_t binned_counts(const BinnedCall& c, hipEvent_t ev_done, const CountsShape& shape, const ScoreCall* score) {
   hipError_t e;
   BinArgs ba; MidArgs ma; RowsArgs ro;
   TRY(call_args(c, ba, ma));
   CountsOut co{};
   TRY(counts_buffers(**c.hits, shape, &co));
+  ScoreArgs sa{};
+  if (score) TRY(score_model(**c.hits, *score, c.stream, &sa));
   TRY(post_args(c, ro));
-  hipExtLaunchKernelGGL(bin_counts_kernel, dim3(counts_grid(c.geo.n_bins)), dim3(COUNTS_BLOCK), 0, c.stream, nullptr, ev_done, 0, ba, co, ro);
+  if (score) hipExtLaunchKernelGGL(bin_scores_kernel, dim3(counts_grid(c.geo.n_bins)), dim3(COUNTS_BLOCK), 0, c.stream, nullptr, ev_done, 0, ba, co, sa, c.ref, ro);
+  else hipExtLaunchKernelGGL(bin_counts_kernel, dim3(counts_grid(c.geo.n_bins)), dim3(COUNTS_BLOCK), 0, c.stream, nullptr, ev_done, 0, ba, co, ro);
   return hipGetLastError();
 }
 

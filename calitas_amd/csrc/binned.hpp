@@ -95,7 +95,8 @@ hipError_t binned_rows(const BinnedCall& call, hipEvent_t ev_rows_done, char* ho
 // host memory and then posts what the rows kernel posts (counters, rows, flags, accepted alignments, stamps; no bytes -- one device
 // function, bin_post, writes both) -- the lane still makes one host round trip, and the table is complete when the post arrives:
 // binned_counts_table(), `shape.cells()` words, valid until the next counts call on this HitsWork.
-hipError_t binned_counts(const BinnedCall& call, hipEvent_t ev_done, const CountsShape& shape);
+// score: bin_scores_kernel in its place, and SCORE_WORDS more words behind the table's cells (hits.hpp).
+hipError_t binned_counts(const BinnedCall& call, hipEvent_t ev_done, const CountsShape& shape, const ScoreCall* score = nullptr);
 const uint64_t* binned_counts_table(const HitsWork* hits);
 // After BIN_FLAG_TEXT: the text buffer grown to `bytes`, the rows kernel once more.
 hipError_t binned_rerun_rows(const BinnedCall& call, uint64_t bytes, hipEvent_t ev_rows_done);

@@ -3,6 +3,7 @@
 // production; this binary is the same host logic for boxes without a JVM.
 #include <algorithm>
 #include <cctype>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -19,6 +20,8 @@ static void usage() {
     "         [-b genome-gap-net-cost=-122] [-B guide-gap-net-cost=-121] [-c chrom] [-t threads (ignored)]\n"
     "         [-v variants.vcf[.gz]] [-V max-variants=16]\n"
     "         [--counts (the table guide_id strand guide_mm guide_gaps pam_mm hits instead of hits.txt)]\n"
+    "         [--scores model.tsv (guide_id rows perfect offtarget_sum_q32 max_q32 specificity instead of hits.txt; with --counts the\n"
+    "          table follows behind an empty line)]\n"
     "         [--device N]\n"
     "       calitas FindGuides -i PATTERNpam -r ref.fa [-x aux-pam ...] [-c chrom] [-s start=0] [-e end] [-o guides.tsv]\n"
     "         [--device N (-1: the host twin, no GPU)]\n");
@@ -71,6 +74,66 @@ static int parse_guide(const std::string& guide, const std::vector<std::string>&
   for (auto& x : aux) out.pams.push_back(x);
   out.cli_length = guide.size();
   return 0;
+}
+
+// A score model file (calitas_amd/aligner.py, ScoreModel.read: the same lines, the same integers -- strtod and Python's float() are both
+// correctly rounded): `#` comments, length / gap / pam_mismatch / mismatch lines, `*` for every index, later lines override earlier ones.
+struct ScoreModelFile {
+  int L = 0;
+  uint32_t gap = 65536, pam = 65536;
+  std::vector<uint32_t> mm;
+};
+static bool read_score_model(const std::string& path, ScoreModelFile& out, std::string& err) {
+  FILE* f = std::fopen(path.c_str(), "r");
+  if (!f) { err = "cannot read " + path; return false; }
+  std::vector<std::vector<std::string>> lines;
+  char buf[1024];
+  auto q16 = [&](const std::string& x, uint32_t* v) {
+    char* end = nullptr;
+    const double d = std::strtod(x.c_str(), &end);
+    if (x.empty() || *end || !(d >= 0.0 && d <= 1.0)) { err = "a factor of a score model lies in [0, 1], not " + x; return false; }
+    *v = (uint32_t)std::floor(d * 65536.0 + 0.5);
+    return true;
+  };
+  bool ok = true;
+  while (ok && std::fgets(buf, sizeof buf, f)) {
+    std::string ln = buf;
+    const size_t hash = ln.find('#');
+    if (hash != std::string::npos) ln.erase(hash);
+    while (!ln.empty() && std::isspace((unsigned char)ln.back())) ln.pop_back();
+    size_t b = 0;
+    while (b < ln.size() && std::isspace((unsigned char)ln[b])) b++;
+    ln.erase(0, b);
+    if (ln.empty()) continue;
+    std::vector<std::string> fld;
+    for (size_t i = 0;;) { const size_t t = ln.find('\t', i); fld.push_back(ln.substr(i, t == std::string::npos ? t : t - i)); if (t == std::string::npos) break; i = t + 1; }
+    if (fld[0] == "length" && fld.size() == 2) out.L = std::atoi(fld[1].c_str());
+    else if (fld[0] == "gap" && fld.size() == 2) ok = q16(fld[1], &out.gap);
+    else if (fld[0] == "pam_mismatch" && fld.size() == 2) ok = q16(fld[1], &out.pam);
+    else if (fld[0] == "mismatch" && fld.size() == 5) lines.push_back(fld);
+    else { err = path + ": not a line of a score model: " + ln; ok = false; }
+  }
+  std::fclose(f);
+  if (!ok) return false;
+  if (out.L < 1 || out.L > 32) { err = path + ": a score model needs a `length` line with 1 <= L <= 32"; return false; }
+  out.mm.assign((size_t)out.L * 25, 65536u);
+  auto axis = [&](const std::string& w, int n, bool base, int* lo, int* hi) {
+    if (w == "*") { *lo = 0; *hi = n; return true; }
+    int k = -1;
+    if (!base) k = std::atoi(w.c_str()) - 1;
+    else if (w == "other" || w == "OTHER" || w == "Other") k = 4;
+    else if (w.size() == 1) { const char* at = std::strchr("ACGT", std::toupper((unsigned char)w[0])); k = at && *at ? (int)(at - "ACGT") : -1; }
+    if (k < 0 || k >= n) { err = path + ": " + w + " is not a position / base of a score model"; return false; }
+    *lo = k; *hi = k + 1;
+    return true;
+  };
+  for (auto& fld : lines) {
+    uint32_t v = 0;
+    int i0, i1, g0, g1, t0, t1;
+    if (!q16(fld[4], &v) || !axis(fld[1], out.L, false, &i0, &i1) || !axis(fld[2], 5, true, &g0, &g1) || !axis(fld[3], 5, true, &t0, &t1)) return false;
+    for (int i = i0; i < i1; i++) for (int g = g0; g < g1; g++) for (int t = t0; t < t1; t++) out.mm[(size_t)i * 25 + (size_t)g * 5 + (size_t)t] = v;
+  }
+  return true;
 }
 
 // `calitas FindGuides`: the sites of an IUPAC pattern in a region as the guides a search takes -- the table of
@@ -154,7 +217,7 @@ static int find_guides_main(int argc, char** argv) {
 int main(int argc, char** argv) {
   if (argc >= 2 && std::strcmp(argv[1], "FindGuides") == 0) return find_guides_main(argc, argv);
   if (argc < 2 || std::strcmp(argv[1], "SearchReference") != 0) { usage(); return 2; }
-  std::string guide, guide_id, ref, output, chrom, variants;
+  std::string guide, guide_id, ref, output, chrom, variants, scores;
   std::vector<std::string> aux;
   calitas_params_t p{};
   p.window_size = 1000; p.max_guide_diffs = 5; p.max_pam_mismatches = 1; p.max_gaps_between_guide_and_pam = 3; p.max_total_diffs = -1;
@@ -192,11 +255,18 @@ int main(int argc, char** argv) {
     else if (a == "-t") (void)next();
     else if (a == "--device") device = std::atoi(next().c_str());
     else if (a == "--counts") counts = true;
+    else if (a == "--scores") scores = next();
     else if (a == "-v") variants = next();
     else { std::fprintf(stderr, "unknown argument %s\n", a.c_str()); usage(); return 2; }
   }
   if (guide.empty() || guide_id.empty() || ref.empty()) { usage(); return 2; }
   if (counts && !variants.empty()) { std::fprintf(stderr, "--counts covers the reference-genome branch only (no --variants)\n"); return 2; }
+  if (!scores.empty() && !variants.empty()) { std::fprintf(stderr, "--scores covers the reference-genome branch only (no --variants)\n"); return 2; }
+  ScoreModelFile model;
+  if (!scores.empty()) {
+    std::string err;
+    if (!read_score_model(scores, model, err)) { std::fprintf(stderr, "calitas: %s\n", err.c_str()); return 2; }
+  }
 
   ParsedGuide pg;
   if (int rc = parse_guide(guide, aux, pg)) return rc;
@@ -220,9 +290,7 @@ int main(int argc, char** argv) {
   }
   FILE* f = output.empty() ? stdout : std::fopen(output.c_str(), "w");
   if (!f) { std::fprintf(stderr, "cannot write %s\n", output.c_str()); return 1; }
-  if (counts) {               // the off-target table instead of hits.txt: the non-zero cells in table order
-    calitas_counts_t* t = nullptr;
-    if (calitas_search_counts(ctx, &g, &p, &t) != CALITAS_OK) die("search");
+  auto write_counts = [&](const calitas_counts_t* t) {     // the non-zero cells in table order
     std::fprintf(f, "guide_id\tstrand\tguide_mm\tguide_gaps\tpam_mm\thits\n");
     uint64_t cell = 0;
     for (uint32_t s = 0; s < 2; s++)
@@ -230,6 +298,22 @@ int main(int argc, char** argv) {
         for (uint32_t gp = 0; gp < t->n_gaps; gp++)
           for (uint32_t pm = 0; pm < t->n_pam; pm++, cell++)
             if (t->counts[cell]) std::fprintf(f, "%s\t%c\t%u\t%u\t%u\t%llu\n", guide_id.c_str(), s ? '-' : '+', m, gp, pm, (unsigned long long)t->counts[cell]);
+  };
+  if (!scores.empty()) {      // the specificity score instead of hits.txt; with --counts the same pass's table behind an empty line
+    const calitas_score_model_t cm{model.L, model.gap, model.pam, model.mm.data()};
+    calitas_scores_t* sc = nullptr;
+    if (calitas_search_scores(ctx, &g, &p, &cm, &sc) != CALITAS_OK) die("search");
+    const double two32 = 4294967296.0;
+    std::fprintf(f, "guide_id\trows\tperfect\tofftarget_sum_q32\tmax_q32\tspecificity\n%s\t%llu\t%llu\t%llu\t%llu\t%.6f\n", guide_id.c_str(),
+                 (unsigned long long)sc->rows, (unsigned long long)sc->perfect, (unsigned long long)sc->sum_q32, (unsigned long long)sc->max_q32,
+                 two32 / (two32 + (double)sc->sum_q32));
+    if (counts) { std::fprintf(f, "\n"); write_counts(&sc->table); }
+    rows = sc->rows;
+    calitas_free(sc);
+  } else if (counts) {        // the off-target table instead of hits.txt
+    calitas_counts_t* t = nullptr;
+    if (calitas_search_counts(ctx, &g, &p, &t) != CALITAS_OK) die("search");
+    write_counts(t);
     rows = t->rows;
     calitas_free(t);
   } else if (variants.empty()) {     // straight to the file: a hits.txt of tens of gigabytes (PAM-less, many diffs) is never held in memory

@@ -137,7 +137,8 @@ int calitas_side_context(calitas_ctx* ctx, calitas_ctx** side, int which = 0);
 void calitas_reap_later(std::function<void()> job);
 int calitas_search_hits_batch_impl(calitas_ctx* ctx, int32_t n_guides, const calitas_guide_t* guides, const char* const* guide_ids,
                                    const calitas_params_t* params, const char* aligner_version, const char* time_stamp, char** tsv,
-                                   uint64_t* tsv_bytes, uint64_t* n_rows, std::vector<std::vector<uint64_t>>* tables = nullptr);
+                                   uint64_t* tsv_bytes, uint64_t* n_rows, std::vector<std::vector<uint64_t>>* tables = nullptr,
+                                   const ScoreModelHost* model = nullptr, std::vector<ScoreWords>* scores = nullptr);
 int calitas_scan_candidates_impl(calitas_ctx* ctx, int32_t n_guides, const calitas_guide_t* guides, const calitas_params_t* params,
                                  uint32_t** records, uint64_t* n_records, bool columnwise = false);
 void calitas_destroy_lanes(calitas_ctx* ctx);
@@ -149,7 +150,7 @@ std::string build_guide_dev(const GuideHost& gh, const calitas_params_t& p, cons
 // with (scan_max_edits: the most edits a protospacer alignment can have), not from max_guide_diffs alone.  Needs no device.
 std::string counts_shape(const GuideHost& gh, const calitas_params_t& p, CountsShape& shape);
 int calitas_search_counts_impl(calitas_ctx* ctx, const calitas_guide_t* guide, const calitas_params_t* params, CountsShape* shape,
-                               std::vector<uint64_t>* table, uint64_t* rows);
+                               std::vector<uint64_t>* table, uint64_t* rows, const ScoreModelHost* model = nullptr, ScoreWords* score = nullptr);
 int ensure_buffers(calitas_ctx* ctx, uint32_t rec_cap, uint32_t raw_cap, uint64_t slab_per_rec, uint32_t item_cap);
 
 // Host waits on the critical path poll instead of blocking: a call has four of them per lane and a blocking wait adds tens of

@@ -330,14 +330,18 @@ void counts_from_box(const Mailbox& box, uint64_t* counts) {
 // Counts mode: behind the walks, instead of len_kernel / rows_kernel.  One lane per sorted position k: keep[k] and order[k] lead to the
 // alignment fin[order[k]] and its record; a kept hit the call owns (HitsOwn, as len_kernel applies it) adds one to its cell of the
 // workgroup's histogram (hits_dev.hpp: counts_cell, CountsOut).  The workgroup that finishes last brings the table to the host and
-// posts what total_kernel posts for a text: no bytes, the rows it counted, the flags.
-__global__ __launch_bounds__(COUNTS_BLOCK) void counts_kernel(MidArgs a, CountsOut o, uint64_t* counts, uint32_t* flags, uint32_t* box, uint32_t seq) {
+// posts what total_kernel posts for a text: no bytes, the rows it counted, the flags.  The body is a template over SCORE: counts_kernel is
+// it without the score (the kernel a counts call launches, unchanged), scores_kernel with it.
+template <bool SCORE>
+__device__ __forceinline__ void counts_body(const MidArgs& a, const CountsOut& o, const ScoreArgs& sa, uint32_t* hist, ScoreLds* sl, uint64_t* counts,
+                                            uint32_t* flags, uint32_t* box, uint32_t seq) {
   CALITAS_TAIL_PRIO();
-  __shared__ uint32_t hist[COUNTS_LDS_CELLS];
   __shared__ uint32_t s_rows;
   if (threadIdx.x == 0) s_rows = 0;
+  if (SCORE) score_begin(*sl, sa);
   counts_begin(hist, o);
   uint32_t mine = 0;
+  ScoreAcc acc;
   for (uint32_t k = blockIdx.x * COUNTS_BLOCK + threadIdx.x; k < a.n; k += gridDim.x * COUNTS_BLOCK) {
     if (!a.keep[k]) continue;
     const uint32_t v = a.order[k];
@@ -348,15 +352,31 @@ __global__ __launch_bounds__(COUNTS_BLOCK) void counts_kernel(MidArgs a, CountsO
     const int cell = counts_cell(a.fin + v, h.minus, o.shape);
     if (cell < 0) { atomicOr(flags, HITS_FLAG_EXTENT); continue; }
     counts_add(hist, o, cell);
+    if (SCORE) score_hit(*sl, sa, a.ref, a.fin + v, h, a.guides + a.fin[v].guide, acc);
     mine++;
   }
   // rows of the call: one LDS add per lane that counted, one global add per workgroup
   if (mine) (void)__hip_atomic_fetch_add(&s_rows, mine, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
   __syncthreads();
   if (threadIdx.x == 0 && s_rows) (void)__hip_atomic_fetch_add(a.n_rows, s_rows, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  if (SCORE) score_reduce(*sl, o, acc);
   if (!counts_flush(hist, o)) return;
+  if (SCORE) score_publish(o);
   counts_publish(o);
   if (threadIdx.x == 0) post_counts(box, counts, seq);    // [0] bytes: none, [1] rows, [2] flags
+}
+
+__global__ __launch_bounds__(COUNTS_BLOCK) void counts_kernel(MidArgs a, CountsOut o, uint64_t* counts, uint32_t* flags, uint32_t* box, uint32_t seq) {
+  __shared__ uint32_t hist[COUNTS_LDS_CELLS];
+  counts_body<false>(a, o, ScoreArgs{}, hist, nullptr, counts, flags, box, seq);
+}
+
+// Score mode: the same lanes, the same cells, and each kept hit's score into the four words behind them (hits_dev.hpp: score_hit).
+__global__ __launch_bounds__(COUNTS_BLOCK) void scores_kernel(MidArgs a, CountsOut o, ScoreArgs sa, uint64_t* counts, uint32_t* flags, uint32_t* box,
+                                                              uint32_t seq) {
+  __shared__ uint32_t hist[COUNTS_LDS_CELLS];
+  __shared__ ScoreLds sl;
+  counts_body<true>(a, o, sa, hist, &sl, counts, flags, box, seq);
 }
 
 // Length of the text = end of the last row; posted with the other two counts (rows, flags) by the same thread (post_counts).
@@ -405,7 +425,7 @@ void hits_destroy(HitsWork* w) {
   if (w->h_ext_keep) (void)hipHostFree(w->h_ext_keep);
   if (w->h_ext_place) (void)hipHostFree(w->h_ext_place);
   if (w->h_counts) (void)hipHostFree(w->h_counts);
-  (void)hipFree(w->cnt_table);
+  (void)hipFree(w->cnt_table); (void)hipFree(w->score_dev);
   if (w->cnt_host) (void)hipHostFree(w->cnt_host);
   mailbox_close(w->mbox);
   delete w;
@@ -585,7 +605,15 @@ struct HitsRun {
     hipError_t e;
     TRY(mailbox_open(w.mbox));
     w.mbox.seq++;
-    hipLaunchKernelGGL(counts_kernel, dim3(counts_grid(n)), dim3(COUNTS_BLOCK), 0, c.stream, mid_args(), co, w.d_counts, d_flags, w.mbox.dev, w.mbox.seq);
+    if (c.score) {
+      ScoreArgs sa{};
+      TRY(score_model(w, *c.score, c.stream, &sa));
+      MidArgs ma = mid_args();
+      ma.ref = c.ref;
+      hipLaunchKernelGGL(scores_kernel, dim3(counts_grid(n)), dim3(COUNTS_BLOCK), 0, c.stream, ma, co, sa, w.d_counts, d_flags, w.mbox.dev, w.mbox.seq);
+    } else {
+      hipLaunchKernelGGL(counts_kernel, dim3(counts_grid(n)), dim3(COUNTS_BLOCK), 0, c.stream, mid_args(), co, w.d_counts, d_flags, w.mbox.dev, w.mbox.seq);
+    }
     TRY(hipGetLastError());
     TRY(mailbox_wait(w.mbox, c.stream));
     counts_from_box(w.mbox, w.h_counts);
@@ -670,14 +698,14 @@ hipError_t hits_run(HitsWork** pw, const HitsRunCall& c, HitsResult* res) {
   hipError_t e;
   *res = HitsResult{};
   const uint32_t n_ext = c.ext ? c.ext->n : 0;
-  if (c.counts && n_ext) return hipErrorInvalidValue;    // (a table of the reference's own hits)
+  if ((c.counts && n_ext) || (c.score && !c.counts)) return hipErrorInvalidValue;    // (a table of the reference's own hits)
   if (c.ext && c.ext->kept) *c.ext->kept = 0;
   if ((uint64_t)c.n + n_ext > 0xFFFFFFF0ull) { res->flags = HITS_FLAG_CLUSTER; return hipSuccess; }
   const size_t n = (size_t)c.n + n_ext;
   CountsOut co{};
   if (c.counts) {
     TRY(counts_buffers(w, *c.counts, &co));
-    if (n == 0) std::memset(co.host, 0, (size_t)co.cells * sizeof(unsigned long long));
+    if (n == 0) std::memset(co.host, 0, ((size_t)co.cells + SCORE_WORDS) * sizeof(unsigned long long));
     res->counts = reinterpret_cast<const uint64_t*>(co.host);
   }
   if (n == 0) return hipSuccess;

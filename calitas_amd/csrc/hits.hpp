@@ -32,11 +32,26 @@ struct CountsShape {
   uint32_t cells() const { return 2u * n_mm * n_gaps * n_pam; }
 };
 
+// Score mode (calitas_search_scores) = counts mode plus the specificity score of the kept hits (post.hpp: ScoreModelHost, score_columns).
+// What a tail is given: the model as the device holds it -- mismatch[MAX_L][5][5] zero-padded, gap, pam_mismatch; Q16 -- and the
+// letter index (A 0, C 1, G 2, T 3, anything else 4) of every protospacer position as written on the command line, 4 bits each.
+constexpr uint32_t SCORE_MODEL_WORDS = MAX_L * 25 + 2;
+constexpr uint32_t SCORE_WORDS = 4;                 // behind a table's cells: sum_q32, perfect, max_q32, the hits looked at
+struct ScoreCall {
+  const uint32_t* model;                            // host memory, SCORE_MODEL_WORDS words, valid during the call
+  uint64_t letters[2];                              // positions 0-15 / 16-31
+};
+// What a guide's kept hits add up to besides the table; across window ranges, contigs and lanes sum and perfect add, max takes the maximum.
+struct ScoreWords {
+  uint64_t sum_q32 = 0, perfect = 0, max_q32 = 0;
+  void add(const ScoreWords& o) { sum_q32 += o.sum_q32; perfect += o.perfect; if (o.max_q32 > max_q32) max_q32 = o.max_q32; }
+};
+
 struct HitsResult {
   uint32_t flags;        // != 0: the device path declined (see HITS_FLAG_*); nothing else is valid
   uint32_t n_rows;
   // counts mode: the table (CountsShape::cells() words, page-locked host memory of the work's, complete when hits_run returns and valid
-  // until the next hits_run on this work); n_rows is its sum, there is no text
+  // until the next hits_run on this work); n_rows is its sum, there is no text.  Score mode: SCORE_WORDS more words behind the cells
   const uint64_t* counts;
   uint64_t text_bytes;   // bytes of row text at d_text
   const char* d_text;
@@ -138,6 +153,7 @@ struct HitsRunCall {
   HitsRef ref; const RawAln* d_final; uint32_t n; const GuideDev* d_guides; const uint64_t* d_win_base; const int2* d_win;
   const RowStrings* strings; int max_overlap, score_hi, max_ops; uint32_t window_reach; hipStream_t stream;
   const HitsExt* ext = nullptr; const HitsOwn* own = nullptr; const CountsShape* counts = nullptr;   // optional
+  const ScoreCall* score = nullptr;                  // with counts: scores_kernel in counts_kernel's place
 };
 hipError_t hits_run(HitsWork** work, const HitsRunCall& call, HitsResult* res);
 // Flags raised while the rows of the last hits_run were being written (HITS_FLAG_INTERNAL); valid once the stream the rows kernel ran

@@ -7,7 +7,9 @@
 
 #include <algorithm>
 #include <cstddef>
+#include <cstring>
 #include <string>
+#include <vector>
 
 #include "../../include/calitas_hip.h"
 #include "common.hpp"
@@ -531,6 +533,99 @@ __device__ __forceinline__ void counts_publish(const CountsOut& o) {
   __syncthreads();
 }
 
+// ---- the specificity score (calitas_search_scores) --------------------------------------------------------------------------------
+// Score mode is counts mode plus, per kept hit and in the same lane, the product of the model's factors (calitas_hip.h has the
+// contract): scores_kernel and bin_scores_kernel are the counts kernels' bodies with SCORE set.  Each workgroup copies the model to LDS
+// once; a lane keeps a 64-bit sum, a count of perfect hits and a maximum; score_reduce brings them wave -> LDS -> one set of
+// non-returning device atomics per workgroup into the SCORE_WORDS words behind the table's cells, ahead of counts_flush, whose ticket
+// then covers them; the workgroup that finishes last publishes them with the table (score_publish, counts_publish).
+struct ScoreArgs {
+  const uint32_t* model;       // device memory, SCORE_MODEL_WORDS words (null in a counts kernel)
+  unsigned long long letters_lo, letters_hi;   // ScoreCall::letters
+};
+struct ScoreAcc { unsigned long long sum = 0, max = 0; uint32_t perfect = 0, hits = 0; };
+struct ScoreLds { uint32_t model[SCORE_MODEL_WORDS]; unsigned long long sum, max, perfect, hits; };
+
+__device__ __forceinline__ void score_begin(ScoreLds& s, const ScoreArgs& sa) {     // (counts_begin's barrier follows)
+  for (uint32_t i = threadIdx.x; i < SCORE_MODEL_WORDS; i += blockDim.x) s.model[i] = sa.model[i];
+  if (threadIdx.x == 0) { s.sum = 0; s.max = 0; s.perfect = 0; s.hits = 0; }
+}
+
+__device__ __forceinline__ uint32_t score_letter(char c) { return c == 'A' ? 0u : c == 'C' ? 1u : c == 'G' ? 2u : c == 'T' ? 3u : 4u; }
+
+// One kept hit.  The columns are walked in the order the row shows them -- ascending command-line position: aligner order for a 3' PAM,
+// traceback order (= aligner order reversed, what the row of a 5' PAM guide is) for a 5' PAM, where the PAM and the gap to it come first
+// among the target's bases.  An 'X' column at position i: the target letter is the one base_upper_dev gives for the forward strand,
+// complemented on the minus strand (as the row builder does) -- the packed code and the exception bit are loaded together, the runs are
+// looked at for an exception base only --, the guide letter is position i of the command line.
+__device__ __forceinline__ void score_hit(const ScoreLds& s, const ScoreArgs& sa, const HitsRef& ref, const RawAln* rp, const HitRec& h,
+                                          const GuideDev* gp, ScoreAcc& acc) {
+  const int ng = rp->n_ops, pam = rp->pam;
+  const OpsWords ow = load_ops_words(rp->ops);
+  const OpCounts oc = count_ops(ow, ng);
+  const HitKey k = hit_key(oc, pam, rp->offset, rp->pam_x);
+  const int gap = pam >= 0 ? rp->offset : 0;
+  acc.hits++;
+  if (oc.non_eq + gap + k.pam_mm == 0) { acc.perfect++; return; }      // total_mm_plus_gaps == 0 (GA:101): counted, not scored
+  const bool minus = h.minus != 0, pam5 = gp->pam5 != 0;
+  const ContigInfo ci = ref.contigs[h.contig];
+  unsigned long long v = 1ull << 32;
+  int i = 0, tj = pam5 ? gap + (pam >= 0 ? (int)gp->pam_len[pam] : 0) : 0;
+  for (int c = 0; c < ng; c++) {
+    const int op = ow.op(pam5 ? c : ng - 1 - c);
+    if (op == 1) {
+      const int64_t p = minus ? (int64_t)h.end - 1 - tj : (int64_t)h.start + tj;
+      uint32_t t = 4u;                                                 // beyond the contig: 'N' (RH:262-264)
+      if (p >= 0 && p < (int64_t)ci.len) {
+        const uint64_t g = ci.gbase + (uint64_t)p;
+        const uint32_t cw = ref.codes[g >> 4], mw = ref.mask[g >> 5];
+        const uint32_t code = (cw >> ((g & 15) * 2)) & 3u;
+        t = minus ? 3u - code : code;
+        if ((mw >> (g & 31)) & 1u) { const char b = base_upper_dev(ref, g); t = score_letter(minus ? comp_base(b) : b); }
+      }
+      const unsigned long long lw = i < 16 ? sa.letters_lo : sa.letters_hi;
+      const uint32_t gl = (uint32_t)(lw >> ((i & 15) * 4)) & 7u;
+      v = (v * s.model[(uint32_t)(i & (MAX_L - 1)) * 25u + min(gl, 4u) * 5u + t]) >> 16;
+    }
+    i += op != 3; tj += op != 2;
+  }
+  for (int r = 0; r < k.guide_gaps; r++) v = (v * s.model[MAX_L * 25]) >> 16;
+  for (int r = 0; r < k.pam_mm; r++) v = (v * s.model[MAX_L * 25 + 1]) >> 16;
+  acc.sum += v; acc.max = max(acc.max, v);
+}
+
+// The lanes' sums into the workgroup's, the workgroup's into the words behind the table's cells.  Every thread of the workgroup calls it.
+__device__ __forceinline__ void score_reduce(ScoreLds& s, const CountsOut& o, ScoreAcc acc) {
+  unsigned long long pk = ((unsigned long long)acc.perfect << 32) | acc.hits;      // (a lane sees fewer than 2^32 hits)
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    acc.sum += __shfl_xor(acc.sum, off); pk += __shfl_xor(pk, off);
+    acc.max = max(acc.max, (unsigned long long)__shfl_xor(acc.max, off));
+  }
+  if ((threadIdx.x & 63u) == 0 && (uint32_t)pk != 0u) {                             // (a wave sees fewer than 2^32 hits, too)
+    (void)__hip_atomic_fetch_add(&s.sum, acc.sum, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    (void)__hip_atomic_fetch_add(&s.perfect, pk >> 32, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    (void)__hip_atomic_fetch_add(&s.hits, pk & 0xFFFFFFFFull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    (void)__hip_atomic_fetch_max(&s.max, acc.max, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+  }
+  __syncthreads();
+  if (threadIdx.x == 0 && s.hits) {
+    unsigned long long* w = o.table + o.cells;
+    (void)__hip_atomic_fetch_add(w + 0, s.sum, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    (void)__hip_atomic_fetch_add(w + 1, s.perfect, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    (void)__hip_atomic_fetch_max(w + 2, s.max, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    (void)__hip_atomic_fetch_add(w + 3, s.hits, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+}
+
+// The last workgroup, ahead of counts_publish (whose fence and barrier then cover these stores): the words to the host, and cleared.
+__device__ __forceinline__ void score_publish(const CountsOut& o) {
+  if (threadIdx.x < SCORE_WORDS) {
+    o.host[o.cells + threadIdx.x] = __hip_atomic_load(o.table + o.cells + threadIdx.x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_store(o.table + o.cells + threadIdx.x, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+}
+
 // Workgroups of a counts kernel over `items` items (each strides over them).
 static inline unsigned counts_grid(size_t items) { return (unsigned)std::min<size_t>(std::max<size_t>((items + COUNTS_BLOCK - 1) / COUNTS_BLOCK, 1), 128); }
 
@@ -559,6 +654,8 @@ struct HitsWork {
   // counts mode (CountsOut): the call's table on the device with its ticket word behind it, and the table's page-locked copy
   unsigned long long* cnt_table = nullptr; size_t cnt_cap = 0;
   unsigned long long* cnt_host = nullptr; size_t cnt_host_cap = 0;
+  // score mode: this context's device copy of the model, brought up again only when its bytes change (score_model)
+  uint32_t* score_dev = nullptr; std::vector<uint32_t> score_host;
   Mailbox mbox;                   // carries d_counts to the host (mailbox.hpp)
   RowConstDev rc{};               // set by hits_prepare
   size_t blob_bytes = 0;
@@ -566,10 +663,11 @@ struct HitsWork {
   bool prepared = false;
 };
 
-// The buffers of a call's table in the work (zero on the device: the kernels leave them so).
+// The buffers of a call's table in the work (zero on the device: the kernels leave them so), with room for a score call's SCORE_WORDS
+// behind the cells.
 inline hipError_t counts_buffers(HitsWork& w, const CountsShape& shape, CountsOut* out) {
-  const size_t cells = shape.cells();
-  if (cells == 0) return hipErrorInvalidValue;
+  const size_t cells = (size_t)shape.cells() + SCORE_WORDS;
+  if (cells == SCORE_WORDS) return hipErrorInvalidValue;
   if (cells + 2 > w.cnt_cap) {
     (void)hipFree(w.cnt_table); w.cnt_table = nullptr; w.cnt_cap = 0;
     const size_t cap = ((cells + 2) + 1) & ~(size_t)1;     // (a multiple of 16 bytes)
@@ -587,8 +685,24 @@ inline hipError_t counts_buffers(HitsWork& w, const CountsShape& shape, CountsOu
     if (e != hipSuccess) return e;
     w.cnt_host_cap = cells;
   }
-  out->shape = shape; out->cells = (uint32_t)cells; out->table = w.cnt_table; out->tickets = reinterpret_cast<uint32_t*>(w.cnt_table + w.cnt_cap - 1);
+  out->shape = shape; out->cells = shape.cells(); out->table = w.cnt_table; out->tickets = reinterpret_cast<uint32_t*>(w.cnt_table + w.cnt_cap - 1);
   out->host = w.cnt_host;
+  return hipSuccess;
+}
+
+// The model of a score call on the device: the work's copy, uploaded on `stream` when its bytes differ from the last call's.
+inline hipError_t score_model(HitsWork& w, const ScoreCall& sc, hipStream_t stream, ScoreArgs* out) {
+  hipError_t e;
+  if (!w.score_dev && (e = hipMalloc((void**)&w.score_dev, SCORE_MODEL_WORDS * sizeof(uint32_t))) != hipSuccess) return e;
+  if (w.score_host.size() != SCORE_MODEL_WORDS || std::memcmp(w.score_host.data(), sc.model, SCORE_MODEL_WORDS * sizeof(uint32_t)) != 0) {
+    if ((e = hipStreamSynchronize(stream)) != hipSuccess) return e;      // (a copy of the old bytes may still be reading them)
+    w.score_host.assign(sc.model, sc.model + SCORE_MODEL_WORDS);
+    if ((e = hipMemcpyAsync(w.score_dev, w.score_host.data(), SCORE_MODEL_WORDS * sizeof(uint32_t), hipMemcpyHostToDevice, stream)) != hipSuccess) {
+      w.score_host.clear();
+      return e;
+    }
+  }
+  out->model = w.score_dev; out->letters_lo = sc.letters[0]; out->letters_hi = sc.letters[1];
   return hipSuccess;
 }
 

@@ -754,22 +754,59 @@ char* hits_tsv(const PackedRef& ref, const GuideHost& g, const std::string& guid
   return out;
 }
 
-std::string hits_counts(const PackedRef& ref, const GuideHost& g, const calitas_params_t& p, const calitas_aln_t* alns, uint64_t n, uint32_t n_mm,
-                        uint32_t n_gaps, uint32_t n_pam, uint64_t* table, uint64_t* n_rows, WorkerPool* pool) {
+std::string make_score_model(const calitas_score_model_t* m, int guide_len, ScoreModelHost& out) {
+  if (!m || !m->mismatch) return "the score model has no mismatch table";
+  if (m->protospacer_length != guide_len)
+    return "the score model is for protospacers of " + std::to_string(m->protospacer_length) + " bases, the guide has " + std::to_string(guide_len);
+  if (guide_len < 1 || guide_len > MAX_L) return "the score model's length is out of range";
+  if (m->gap > 65536u || m->pam_mismatch > 65536u) return "a factor of the score model is above 65536 (1.0)";
+  out.L = guide_len;
+  out.words.assign((size_t)MAX_L * 25 + 2, 0u);
+  for (int i = 0; i < guide_len * 25; i++) {
+    if (m->mismatch[i] > 65536u) return "a factor of the score model is above 65536 (1.0)";
+    out.words[(size_t)i] = m->mismatch[i];
+  }
+  out.words[(size_t)MAX_L * 25] = m->gap;
+  out.words[(size_t)MAX_L * 25 + 1] = m->pam_mismatch;
+  return "";
+}
+
+bool score_columns(const ScoreModelHost& m, const char* pg, const char* pa, const char* pt, int len, int guide_gaps, int pam_mm, uint64_t* score) {
+  uint64_t s = 1ull << 32;
+  int i = 0;
+  for (int c = 0; c < len; c++) {
+    if (pg[c] < 'A' || pg[c] > 'Z') continue;
+    if (i >= m.L) return false;
+    if (pa[c] == '.') s = (s * m.mismatch(i, (int)score_letter_index(pg[c]), (int)score_letter_index(pt[c]))) >> 16;
+    i++;
+  }
+  for (int r = 0; r < guide_gaps; r++) s = (s * m.gap()) >> 16;
+  for (int r = 0; r < pam_mm; r++) s = (s * m.pam_mismatch()) >> 16;
+  *score = s;
+  return true;
+}
+
+// What hits_counts and hits_scores share: the kept hits, each one's padded columns (the target's only for a score) and its cell.
+static std::string count_kept(const PackedRef& ref, const GuideHost& g, const calitas_params_t& p, const ScoreModelHost* model, const calitas_aln_t* alns,
+                              uint64_t n, uint32_t n_mm, uint32_t n_gaps, uint32_t n_pam, uint64_t* table, uint64_t* n_rows, uint64_t* perfect,
+                              uint64_t* sum_q32, uint64_t* max_q32, WorkerPool* pool) {
   WorkerPool serial(1);
   if (!pool) pool = &serial;
   const std::vector<Lite> keepers = kept_hits(ref, p, alns, n, pool, nullptr, 0);
   for (const Lite& k : keepers) {
     const calitas_aln_t& a = alns[k.idx];
     const std::string q = g.query_for(a.pam_index);
-    char pg[CALITAS_MAX_OPS + 1], pa[CALITAS_MAX_OPS + 1];
+    char pg[CALITAS_MAX_OPS + 1], pa[CALITAS_MAX_OPS + 1], pt[CALITAS_MAX_OPS + 1];
     const int len = a.n_ops;
+    if (len < 0 || len > CALITAS_MAX_OPS) return "an alignment has more columns than CALITAS_MAX_OPS";
     size_t qi = 0;
+    int edits = 0;
     for (int i = 0; i < len; i++) {                        // the padded guide and alignment strings, as write_row lays them out (SGA:511)
       const bool has_q = a.ops[i] != 'D';
       if (has_q && qi >= q.size()) return "an alignment has more guide columns than its guide has bases";
       pg[i] = has_q ? q[qi++] : '-';
       pa[i] = a.ops[i] == '=' ? '|' : a.ops[i] == 'X' ? '.' : '~';
+      edits += a.ops[i] != '=';
     }
     const int gmm = ga_count_raw(pg, pa, len, false, false, true, false);    // guide_mm GA:103
     const int ggp = ga_count_raw(pg, pa, len, false, false, false, true);    // guide_gaps GA:104
@@ -779,9 +816,34 @@ std::string hits_counts(const PackedRef& ref, const GuideHost& g, const calitas_
              " lies outside the table's extents (" + std::to_string(n_mm) + " x " + std::to_string(n_gaps) + " x " + std::to_string(n_pam) + ")";
     const uint32_t s = a.strand == '-' ? 1u : 0u;
     table[((s * n_mm + (uint32_t)gmm) * n_gaps + (uint32_t)ggp) * n_pam + (uint32_t)pmm]++;
+    if (!model) continue;
+    if (edits == 0) { ++*perfect; continue; }              // total_mm_plus_gaps GA:101
+    const std::string t = target_bases(ref, a.contig_index, a.start_offset, a.end_offset, a.strand == '-');
+    size_t ti = 0;
+    for (int i = 0; i < len; i++) {                        // the padded target (SGA:511)
+      const bool has_t = a.ops[i] != 'I';
+      if (has_t && ti >= t.size()) return "an alignment has more target columns than its span has bases";
+      pt[i] = has_t ? t[ti++] : '-';
+    }
+    uint64_t v = 0;
+    if (!score_columns(*model, pg, pa, pt, len, ggp, pmm, &v)) return "an alignment has more protospacer columns than the score model has positions";
+    *sum_q32 += v;
+    if (v > *max_q32) *max_q32 = v;
   }
   if (n_rows) *n_rows = keepers.size();
   return "";
+}
+
+std::string hits_counts(const PackedRef& ref, const GuideHost& g, const calitas_params_t& p, const calitas_aln_t* alns, uint64_t n, uint32_t n_mm,
+                        uint32_t n_gaps, uint32_t n_pam, uint64_t* table, uint64_t* n_rows, WorkerPool* pool) {
+  return count_kept(ref, g, p, nullptr, alns, n, n_mm, n_gaps, n_pam, table, n_rows, nullptr, nullptr, nullptr, pool);
+}
+
+std::string hits_scores(const PackedRef& ref, const GuideHost& g, const calitas_params_t& p, const ScoreModelHost& model, const calitas_aln_t* alns,
+                        uint64_t n, uint32_t n_mm, uint32_t n_gaps, uint32_t n_pam, uint64_t* table, uint64_t* n_rows, uint64_t* perfect,
+                        uint64_t* sum_q32, uint64_t* max_q32, WorkerPool* pool) {
+  *perfect = 0; *sum_q32 = 0; *max_q32 = 0;
+  return count_kept(ref, g, p, &model, alns, n, n_mm, n_gaps, n_pam, table, n_rows, perfect, sum_q32, max_q32, pool);
 }
 
 }  // namespace calitas

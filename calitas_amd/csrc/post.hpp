@@ -87,4 +87,29 @@ char* hits_tsv(const PackedRef& ref, const GuideHost& g, const std::string& guid
 std::string hits_counts(const PackedRef& ref, const GuideHost& g, const calitas_params_t& p, const calitas_aln_t* alns, uint64_t n, uint32_t n_mm,
                         uint32_t n_gaps, uint32_t n_pam, uint64_t* table, uint64_t* n_rows, WorkerPool* pool = nullptr);
 
+// ---- the specificity score (calitas_search_scores; include/calitas_hip.h has the contract) -----------------------------------------
+// A validated calitas_score_model_t.  words: the model as the device holds it -- mismatch[32][5][5] zero-padded behind position L,
+// then gap and pam_mismatch (hits.hpp: SCORE_MODEL_WORDS) --, so equal models have equal bytes.
+struct ScoreModelHost {
+  int L = 0;
+  std::vector<uint32_t> words;
+  uint32_t mismatch(int i, int g, int t) const { return words[(size_t)i * 25 + (size_t)g * 5 + (size_t)t]; }
+  uint32_t gap() const { return words[32 * 25]; }
+  uint32_t pam_mismatch() const { return words[32 * 25 + 1]; }
+};
+// "" or why the model is refused for a guide with a protospacer of guide_len bases.
+std::string make_score_model(const calitas_score_model_t* m, int guide_len, ScoreModelHost& out);
+// Letter index of the contract: A 0, C 1, G 2, T 3, anything else 4.
+inline uint32_t score_letter_index(char c) { return c == 'A' ? 0u : c == 'C' ? 1u : c == 'G' ? 2u : c == 'T' ? 3u : 4u; }
+// The score of one hit from its padded columns in guide orientation (the hits.txt columns padded_guide, padded_alignment, padded_target
+// and guide_gaps, pam_mm): the contract's loop, 64-bit with a truncation at every step.  false: the row has more upper-case guide
+// letters than the model has positions.
+bool score_columns(const ScoreModelHost& m, const char* pg, const char* pa, const char* pt, int len, int guide_gaps, int pam_mm, uint64_t* score);
+
+// hits_counts plus the score: the kept hits counted into table[] as there, and those with an edit scored from their ops (guide
+// orientation) and the packed reference's bases; a kept hit without one is counted in *perfect.
+std::string hits_scores(const PackedRef& ref, const GuideHost& g, const calitas_params_t& p, const ScoreModelHost& model, const calitas_aln_t* alns,
+                        uint64_t n, uint32_t n_mm, uint32_t n_gaps, uint32_t n_pam, uint64_t* table, uint64_t* n_rows, uint64_t* perfect,
+                        uint64_t* sum_q32, uint64_t* max_q32, WorkerPool* pool = nullptr);
+
 }  // namespace calitas

@@ -65,7 +65,9 @@ static calitas_timing_t batch_timing(const std::vector<calitas_timing_t>& tms) {
 // guide g's tail runs.  Each guide's text goes to its own pinned buffer.
 int calitas_search_hits_batch_impl(calitas_ctx* ctx, int32_t n_guides, const calitas_guide_t* guides, const char* const* guide_ids,
                                   const calitas_params_t* params, const char* aligner_version, const char* time_stamp, char** tsv,
-                                  uint64_t* tsv_bytes, uint64_t* n_rows, std::vector<std::vector<uint64_t>>* tables) {
+                                  uint64_t* tsv_bytes, uint64_t* n_rows, std::vector<std::vector<uint64_t>>* tables, const ScoreModelHost* model,
+                                  std::vector<ScoreWords>* scores) {
+  // model, scores (calitas_search_scores_batch): with tables, the tails run in score mode and (*scores)[i] receives guides[i]'s words
   // tables (calitas_search_counts_batch): every guide's tail runs in counts mode and `finish` takes its table -- no text is built, copied
   // or expanded, tsv is not touched; (*tables)[i] and n_rows[i] receive what calitas_search_counts returns for guides[i]
   const bool counting = tables != nullptr;
@@ -76,7 +78,7 @@ int calitas_search_hits_batch_impl(calitas_ctx* ctx, int32_t n_guides, const cal
     if (counting) {
       CountsShape shape;
       uint64_t rows = 0;
-      const int rc = calitas_search_counts_impl(ctx, &guides[i], params, &shape, &(*tables)[(size_t)i], &rows);
+      const int rc = calitas_search_counts_impl(ctx, &guides[i], params, &shape, &(*tables)[(size_t)i], &rows, model, scores ? &(*scores)[(size_t)i] : nullptr);
       if (!rc && n_rows) n_rows[i] = rows;
       return rc;
     }
@@ -102,7 +104,7 @@ int calitas_search_hits_batch_impl(calitas_ctx* ctx, int32_t n_guides, const cal
   std::vector<char> owned_ok((size_t)n_guides, 1);
   int rc = plan_batch(ctx, n_guides, guides, params, n_lanes, plans, owned_ok);
   if (rc) return rc;
-  if (counting) for (auto& q : plans) q.counts = true;
+  if (counting) for (auto& q : plans) { q.counts = true; q.model = model; }
   const PackedRef& ref = ctx->ref;
   std::mutex scan_mu, copy_mu;
   const bool device_rows = !TUNE_GET("CALITAS_HOST_HITS");
@@ -145,6 +147,7 @@ int calitas_search_hits_batch_impl(calitas_ctx* ctx, int32_t n_guides, const cal
     if (counting) {                                            // the table is on the host already: nothing to bring in
       if (lt.counts.size() != plans[g].cshape.cells()) return fail(lane, CALITAS_EHIP, "a guide's tail returned no counts table (internal error)");
       (*tables)[(size_t)g] = std::move(lt.counts);
+      if (scores) (*scores)[(size_t)g] = lt.score;
       if (n_rows) n_rows[g] = lt.rows;
       tms[g] = lt.tm; tms[g].hit_rows = lt.rows; tms[g].hits_bytes = 0;
       return CALITAS_OK;

@@ -125,7 +125,7 @@ static int search_hits_owned(calitas_ctx* ctx, const HitsCall& call, HitsOut& ou
     // the stretch on the per-bin kernels, cut into lanes like any other call (search_hits_attempt): everything it returns is final
     const uint64_t range[2] = {(uint64_t)params->first_window, (uint64_t)params->n_windows};
     bool declined = false;
-    const HitsCall all{call.guide, call.guide_id, &whole, call.aligner_version, call.time_stamp, call.user_dst, call.user_cap, nullptr, nullptr, nullptr, call.counts};
+    const HitsCall all{call.guide, call.guide_id, &whole, call.aligner_version, call.time_stamp, call.user_dst, call.user_cap, nullptr, nullptr, nullptr, call.counts, call.model};
     rc = search_hits_attempt(ctx, all, out, range, &declined);
     if (rc || !declined) return rc;
     HIP_TRY(ctx, calitas_spin_sync(ctx->stream));
@@ -146,22 +146,36 @@ static int search_hits_owned(calitas_ctx* ctx, const HitsCall& call, HitsOut& ou
   calitas_timing_t tm{};
   // counts mode on this (rare, slow) path: the kept rows are counted by their columns strand (6), guide_mm (16), guide_gaps (17) and
   // pam_mm (19) of RH:99-132 -- the text calls of the touched contigs decide the rows either way
+  // score mode: the row's score besides, from its columns total_mm_plus_gaps (20), padded_guide (21), padded_alignment (22) and
+  // padded_target (23) -- the contract as written (calitas_hip.h)
   std::vector<uint64_t> table(call.counts ? pl.cshape.cells() : 0, 0);
+  ScoreWords score;
   auto count_row = [&](const char* q, const char* row_end) -> bool {
     const char* f = q;
     uint32_t minus = 0;
-    long v[3] = {0, 0, 0};
-    for (int k = 0; k < 20 && f < row_end; k++) {
+    long v[4] = {0, 0, 0, 0};
+    const char* col[3] = {nullptr, nullptr, nullptr};
+    size_t col_len[3] = {0, 0, 0};
+    for (int k = 0; k < 24 && f < row_end; k++) {
+      const char* tab = (const char*)std::memchr(f, '\t', (size_t)(row_end - f));
       if (k == 6) minus = *f == '-' ? 1u : 0u;
       if (k == 16) v[0] = std::strtol(f, nullptr, 10);
       if (k == 17) v[1] = std::strtol(f, nullptr, 10);
       if (k == 19) v[2] = std::strtol(f, nullptr, 10);
-      const char* tab = (const char*)std::memchr(f, '\t', (size_t)(row_end - f));
+      if (k == 20) v[3] = std::strtol(f, nullptr, 10);
+      if (k >= 21) { col[k - 21] = f; col_len[k - 21] = (size_t)((tab ? tab : row_end) - f); }
       f = tab ? tab + 1 : row_end;
     }
     const CountsShape& cs = pl.cshape;
     if (v[0] < 0 || v[1] < 0 || v[2] < 0 || (uint32_t)v[0] >= cs.n_mm || (uint32_t)v[1] >= cs.n_gaps || (uint32_t)v[2] >= cs.n_pam) return false;
     table[((minus * cs.n_mm + (uint32_t)v[0]) * cs.n_gaps + (uint32_t)v[1]) * cs.n_pam + (uint32_t)v[2]]++;
+    if (!call.model) return true;
+    if (v[3] == 0) { score.perfect++; return true; }
+    uint64_t one = 0;
+    if (!col[2] || col_len[0] != col_len[1] || col_len[0] != col_len[2] ||
+        !score_columns(*call.model, col[0], col[1], col[2], (int)col_len[0], (int)v[1], (int)v[2], &one)) return false;
+    ScoreWords w; w.sum_q32 = one; w.max_q32 = one;
+    score.add(w);
     return true;
   };
   for (size_t c = 0; c < ref.contigs.size(); c++) {
@@ -185,7 +199,7 @@ static int search_hits_owned(calitas_ctx* ctx, const HitsCall& call, HitsOut& ou
       const uint64_t key = ((uint64_t)c << 32) | pos;
       if (key >= own_lo && key < own_hi) {
         if (!call.counts) body.append(q, (size_t)(row_end - q));
-        else if (!count_row(q, row_end)) { calitas_free(t); return fail(ctx, CALITAS_EHIP, "a hit lies outside the extents of the counts table (internal error)"); }
+        else if (!count_row(q, row_end)) { calitas_free(t); return fail(ctx, CALITAS_EHIP, "a hit lies outside the extents of the counts table, or its row cannot be scored (internal error)"); }
         rows++;
       }
       q = row_end;
@@ -196,7 +210,7 @@ static int search_hits_owned(calitas_ctx* ctx, const HitsCall& call, HitsOut& ou
   if (call.counts) {
     tm.hit_rows = rows; tm.hits_bytes = 0; tm.lanes = 1;
     ctx->timing = tm;
-    out.counts = std::move(table); out.shape = pl.cshape; out.rows = rows;
+    out.counts = std::move(table); out.shape = pl.cshape; out.rows = rows; out.score = score;
     return CALITAS_OK;
   }
   const size_t total = hlen + body.size();
@@ -638,6 +652,7 @@ int search_hits_attempt(calitas_ctx* ctx, const HitsCall& call, HitsOut& out, co
   int rc = plan_search(ctx, 1, call.guide, call.params, pl);
   if (rc) return rc;
   pl.counts = call.counts;
+  pl.model = call.counts ? call.model : nullptr;
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   rc = ensure_bin_base(ctx, pl, ctx->stream);                // (built once per reference and window size)
   if (rc) return rc;
@@ -688,6 +703,7 @@ int search_hits_attempt(calitas_ctx* ctx, const HitsCall& call, HitsOut& out, co
     for (auto& lt : a.parts) {
       if (lt.counts.size() != out.counts.size()) return fail(ctx, CALITAS_EHIP, "a lane returned no counts table (internal error)");
       add_counts(out.counts, lt.counts);
+      out.score.add(lt.score);
       out.rows += lt.rows;
       add_lane_timing(tm, lt.tm);
     }
@@ -750,12 +766,14 @@ int calitas_search_hits_impl(calitas_ctx* ctx, const calitas_guide_t* guide, con
 
 // calitas_search_counts: the ways of calitas_search_hits (one pass in lanes, a window range, one pass per contig) with HitsCall::counts set.
 int calitas_search_counts_impl(calitas_ctx* ctx, const calitas_guide_t* guide, const calitas_params_t* params, CountsShape* shape,
-                               std::vector<uint64_t>* table, uint64_t* rows) {
+                               std::vector<uint64_t>* table, uint64_t* rows, const ScoreModelHost* model, ScoreWords* score) {
+  // (model: calitas_search_scores -- the same ways in score mode, *score receives what the rows' scores add up to)
   g_marks.start();
   struct Dump { ~Dump() { g_marks.mark("return"); g_marks.dump(); } } dump_at_exit;
   static const std::string no_id;
   HitsCall call{guide, no_id, params, "-", "-"};             // (no row carries them: nothing to format)
   call.counts = true;
+  call.model = model;
   HitsOut out;
   bool one_pass = false;
   const int rc = params && (params->first_window != 0 || params->n_windows != 0)
@@ -763,6 +781,7 @@ int calitas_search_counts_impl(calitas_ctx* ctx, const calitas_guide_t* guide, c
   if (rc) return rc;
   if (out.counts.size() != out.shape.cells() || out.counts.empty()) return fail(ctx, CALITAS_EHIP, "the search returned no counts table (internal error)");
   *shape = out.shape; *table = std::move(out.counts); *rows = out.rows;
+  if (score) *score = out.score;
   return CALITAS_OK;
 }
 

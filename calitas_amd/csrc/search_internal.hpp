@@ -72,6 +72,8 @@ struct SearchPlan {
   // always planned (counts_shape: from the guide and the params alone); `counts` is set by the entry point
   bool counts = false;
   CountsShape cshape;
+  // calitas_search_scores: counts mode with the score of every kept hit besides (set with `counts`; the model outlives the call)
+  const ScoreModelHost* model = nullptr;
   bool general_tail = false;          // the caller brings hits of its own into the row stage (HitsExt): the general kernels take them, the bins do not
 };
 
@@ -98,6 +100,7 @@ struct LaneText {
   const HitsExt* ext = nullptr;        // the caller's hits whose rows the caller writes into the text itself (HitsExtRows::fill_on_host) ...
   const uint64_t* ext_place = nullptr; // ... and where (HitsResult::ext_place)
   std::vector<uint64_t> counts;        // counts mode (SearchPlan::counts): the lane's table, SearchPlan::cshape.cells() words; no text, bytes = 0
+  ScoreWords score;                    // score mode (SearchPlan::model): what the lane's kept hits add up to
   calitas_timing_t tm{};
 };
 
@@ -121,6 +124,7 @@ struct HitsCall {
   void* sink_user = nullptr;
   const HitsExtSource* ext_source = nullptr;   // ... and hits of the caller's own are brought into every contig's row stage
   bool counts = false;                      // calitas_search_counts: no text at all, HitsOut::counts receives the table of the rows
+  const ScoreModelHost* model = nullptr;    // calitas_search_scores: with counts, HitsOut::score receives the rows' scores
 };
 // ... and what it gets back (tsv stays NULL where the text went to a sink).
 struct HitsOut {
@@ -128,6 +132,7 @@ struct HitsOut {
   uint64_t bytes = 0, rows = 0;
   std::vector<uint64_t> counts;             // HitsCall::counts: the table, shape.cells() words
   CountsShape shape;
+  ScoreWords score;                         // HitsCall::model
   void store(char** t, uint64_t* b, uint64_t* r) const { if (t) *t = tsv; if (b) *b = bytes; if (r) *r = rows; }
 };
 
@@ -178,6 +183,12 @@ void release_scratch(calitas_ctx* ctx);
 int search_hits_attempt(calitas_ctx* ctx, const HitsCall& call, HitsOut& out, const uint64_t* owned = nullptr, bool* owned_declined = nullptr);
 int search_hits_sequential(calitas_ctx* ctx, const HitsCall& call, HitsOut& out);
 int search_counts_sequential(calitas_ctx* ctx, const HitsCall& call, HitsOut& out);
+// What the tails take of a plan's model (hits.hpp: ScoreCall): its words and the letter indices of the guide's positions.
+inline ScoreCall score_call(const ScoreModelHost& m, const GuideHost& gh) {
+  ScoreCall sc{m.words.data(), {0, 0}};
+  for (size_t i = 0; i < gh.protospacer.size() && i < 32; i++) sc.letters[i >> 4] |= (uint64_t)score_letter_index(gh.protospacer[i]) << ((i & 15) * 4);
+  return sc;
+}
 // b += a, element by element (tables of one shape: of ranges, contigs, lanes)
 inline void add_counts(std::vector<uint64_t>& b, const std::vector<uint64_t>& a) {
   if (b.size() < a.size()) b.resize(a.size(), 0);

@@ -320,7 +320,8 @@ static int lane_rows_binned(calitas_ctx* lane, const SearchPlan& pl, bool prelau
   uint64_t host_dst_cap = 0;
   if (pl.counts) {
     // the table instead of rows: bin_counts_kernel where the rows kernel would go, with the same post behind it
-    HIP_TRY(lane, binned_counts(bc, lane->ev[5], pl.cshape));
+    const ScoreCall sc = pl.model ? score_call(*pl.model, pl.gh[0]) : ScoreCall{};
+    HIP_TRY(lane, binned_counts(bc, lane->ev[5], pl.cshape, pl.model ? &sc : nullptr));
   } else if (dest) {
     // the rows kernel goes out once the text's final place is known (the byte counts of the ranges before this one: their row kernels
     // have started by then) and writes there itself -- no copy behind it
@@ -355,6 +356,11 @@ static int lane_rows_binned(calitas_ctx* lane, const SearchPlan& pl, bool prelau
     uint64_t sum = 0;
     for (uint64_t v : lt.counts) sum += v;
     if (sum != lane->mbox.host[BIN_BOX_ROWS]) return fail(lane, CALITAS_EHIP, "binned counts kernel: the table does not add up to the bins' kept hits (internal error)");
+    if (pl.model) {                                          // ... and so did the four words behind its cells
+      const uint64_t* w = table + pl.cshape.cells();
+      lt.score = ScoreWords{w[0], w[1], w[2]};
+      if (w[3] != sum) return fail(lane, CALITAS_EHIP, "binned scores kernel: the hits it scored are not the hits it counted (internal error)");
+    }
   }
   if (flags & BIN_FLAG_TEXT) {                               // the text buffer was a guess: grow it, the rows kernel once more
     HIP_TRY(lane, binned_rerun_rows(bc, bytes, lane->ev[5]));
@@ -468,6 +474,8 @@ int lane_rows(calitas_ctx* lane, const SearchPlan& pl, bool prelaunched, const R
       hc.strings = &rs; hc.max_overlap = p.max_overlap; hc.score_hi = score_hi; hc.max_ops = widest_hit(pl, max_pam);
       hc.window_reach = dev.crowded ? 0u : (uint32_t)((p.window_size + pl.step - 1) / pl.step); hc.stream = lane->stream;
       hc.ext = ext; hc.own = own_general ? &ho : nullptr; hc.counts = pl.counts ? &pl.cshape : nullptr;
+      const ScoreCall sc = pl.model ? score_call(*pl.model, pl.gh[0]) : ScoreCall{};
+      hc.score = pl.counts && pl.model ? &sc : nullptr;
       HIP_TRY(lane, hits_run(&lane->hits, hc, &res));
       HIP_TRY(lane, hipEventRecord(lane->ev[5], lane->stream));
       g_marks.mark("rows-queued");
@@ -478,6 +486,11 @@ int lane_rows(calitas_ctx* lane, const SearchPlan& pl, bool prelaunched, const R
         uint64_t sum = 0;
         for (uint64_t v : lt.counts) sum += v;
         if (sum != res.n_rows) return fail(lane, CALITAS_EHIP, "counts kernel: the table does not add up to the kept hits (internal error)");
+        if (pl.model) {
+          const uint64_t* w = res.counts + pl.cshape.cells();
+          lt.score = ScoreWords{w[0], w[1], w[2]};
+          if (w[3] != sum) return fail(lane, CALITAS_EHIP, "scores kernel: the hits it scored are not the hits it counted (internal error)");
+        }
         lt.rows = res.n_rows;
         if (own_general) lt.tm.owned_general_lanes = 1;
         return CALITAS_OK;
@@ -504,7 +517,9 @@ int lane_rows(calitas_ctx* lane, const SearchPlan& pl, bool prelaunched, const R
   uint64_t rows = 0;
   if (pl.counts) {                                           // the host stage of calitas_hits_counts
     lt.counts.assign(pl.cshape.cells(), 0);
-    const std::string e = hits_counts(ref, gh, p, alns, n_alns, pl.cshape.n_mm, pl.cshape.n_gaps, pl.cshape.n_pam, lt.counts.data(), &rows, own->pool);
+    const std::string e = pl.model ? hits_scores(ref, gh, p, *pl.model, alns, n_alns, pl.cshape.n_mm, pl.cshape.n_gaps, pl.cshape.n_pam, lt.counts.data(), &rows,
+                                                 &lt.score.perfect, &lt.score.sum_q32, &lt.score.max_q32, own->pool)
+                                   : hits_counts(ref, gh, p, alns, n_alns, pl.cshape.n_mm, pl.cshape.n_gaps, pl.cshape.n_pam, lt.counts.data(), &rows, own->pool);
     calitas_free(alns);
     if (!e.empty()) return fail(lane, CALITAS_EHIP, e);
     lt.on_host = true;

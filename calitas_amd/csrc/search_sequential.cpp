@@ -335,6 +335,7 @@ int search_counts_sequential(calitas_ctx* ctx, const HitsCall& call, HitsOut& ou
   int rc = plan_search(ctx, 1, call.guide, call.params, pl);
   if (rc) return rc;
   pl.counts = true;
+  pl.model = call.model;
   std::string version, stamp;
   calitas_default_version_and_stamp(call.aligner_version, call.time_stamp, version, stamp);
   const RowStrings rs = make_row_strings(ctx->ref, pl.gh[0], call.guide_id, pl.p, version, stamp);
@@ -353,6 +354,7 @@ int search_counts_sequential(calitas_ctx* ctx, const HitsCall& call, HitsOut& ou
     if (rc) return rc;
     if (lt.counts.size() != out.counts.size()) return fail(ctx, CALITAS_EHIP, "a contig pass returned no counts table (internal error)");
     add_counts(out.counts, lt.counts);
+    out.score.add(lt.score);
     out.rows += lt.rows;
     add_lane_timing(tm, lt.tm);
   }

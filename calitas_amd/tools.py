@@ -382,37 +382,62 @@ def guide_counts(ctx, guides, params, batch=64):
     return tables
 
 
-def guides_tsv(rows, tables=None):
+def guide_scores(ctx, guides, params, model, batch=64):
+    """guide_counts in score mode: {string: Scores of Context.search_scores} through search_scores_batch (the model's length is the
+    guides' length)."""
+    got = {}
+    same = list(dict.fromkeys(guides))
+    for b in range(0, len(same), batch):
+        part = same[b:b + batch]
+        for g, s in zip(part, ctx.search_scores_batch([Guide(g) for g in part], params, model)):
+            got[g] = s
+    return got
+
+
+def guides_tsv(rows, tables=None, scores=None):
     """The FindGuides table: GUIDE_COLUMNS, one row per GuideSite; with tables (guide_counts) also hits -- the table's sum -- and
-    hits_mm0 .. hits_mmE, the hits per number of protospacer mismatches, summed over strands, gaps and PAM mismatches."""
+    hits_mm0 .. hits_mmE, the hits per number of protospacer mismatches, summed over strands, gaps and PAM mismatches; with scores
+    (guide_scores) those columns come from the same pass's tables and perfect and specificity (%.6f) follow them."""
     header = list(GUIDE_COLUMNS)
     n_mm = 0
+    if scores is not None:
+        tables = {g: s.table for g, s in scores.items()}
     if tables is not None:
         n_mm = max([t.shape[1] for t in tables.values()], default=1)
         header += ["hits"] + ["hits_mm%d" % m for m in range(n_mm)]
+    if scores is not None:
+        header += ["perfect", "specificity"]
     lines = ["\t".join(header)]
     for r in rows:
         f = [str(x) for x in r.row()]
         if tables is not None:
             t = tables[r.guide]
             f += [str(int(t.sum()))] + [str(int(t[:, m].sum())) if m < t.shape[1] else "0" for m in range(n_mm)]
+        if scores is not None:
+            f += [str(scores[r.guide].perfect), "%.6f" % scores[r.guide].specificity]
         lines.append("\t".join(f))
     return "\n".join(lines) + "\n"
 
 
-def find_guides_tool(ref, pattern, auxiliary_pams=(), chrom=None, start=0, end=None, output=None, counts=False, device=0, **search):
+def find_guides_tool(ref, pattern, auxiliary_pams=(), chrom=None, start=0, end=None, output=None, counts=False, device=0, scores=None,
+                     **search):
     """`python -m calitas_amd FindGuides`: the guides of a region as a TSV (guides_tsv); counts=True: every distinct guide also goes
-    through the off-target search with the SearchReference flags in `search` (make_params names).  device -1: the host twin of the
-    enumeration (no GPU; not with counts).  Returns the text."""
-    if counts and device < 0:
-        raise ValueError("--counts searches on the GPU: it cannot run with --device -1")
+    through the off-target search with the SearchReference flags in `search` (make_params names); scores=ScoreModel (or its file):
+    through search_scores_batch instead, which adds perfect and specificity.  device -1: the host twin of the enumeration (no GPU; not
+    with counts or scores).  Returns the text."""
+    if (counts or scores is not None) and device < 0:
+        raise ValueError("--counts and --scores search on the GPU: they cannot run with --device -1")
+    if isinstance(scores, str):
+        from .aligner import ScoreModel
+        scores = ScoreModel.read(scores)
     pat = Guide(pattern, auxiliary_pams)
     ctx = Context(device)
     try:
         ctx.set_reference_fasta(ref)
         rows = find_guides(ctx, pat, chrom, start, end, host=device < 0)
-        tables = guide_counts(ctx, [r.guide for r in rows], make_params(**search)) if counts else None
-        text = guides_tsv(rows, tables)
+        tables = guide_counts(ctx, [r.guide for r in rows], make_params(**search)) if counts and scores is None else None
+        scored = guide_scores(ctx, [r.guide for r in rows], make_params(**search), scores) if scores is not None else None
+        text = guides_tsv(rows, tables, scored)
         if output is not None:
             with open(output, "w") as f:
                 f.write(text)

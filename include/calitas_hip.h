@@ -308,6 +308,49 @@ int calitas_count_sites(calitas_ctx* ctx, const calitas_guide_t* pattern, int32_
 int calitas_find_sites_host(const calitas_ctx* ctx, const calitas_guide_t* pattern, int32_t chrom_index, uint64_t start, uint64_t end,
                             calitas_site_t** sites, uint64_t* n_sites);
 
+/* The specificity score of a guide: one number per off-target hit, summed per guide.  No reference counterpart.
+ * A model for protospacers of L bases holds Q16 factors (65536 = 1.0, none above it): mismatch[L][5][5] indexed by guide position,
+ * guide letter and target letter, one gap factor and one pam_mismatch factor.  Guide positions are 0-based and count the upper-case
+ * letters of the guide as written on the command line, left to right; the letter index is A 0, C 1, G 2, T 3, anything else 4 (U, N
+ * and the IUPAC codes alike), for both letters.  The score of one hit is defined on its hits.txt row:
+ *     s = 1 << 32
+ *     for each column, left to right, whose padded_guide letter is upper case (i = its index among them):
+ *         if padded_alignment is '.':  s = (s * mismatch[i][idx(padded_guide)][idx(padded_target)]) >> 16
+ *     repeat guide_gaps times:  s = (s * gap) >> 16
+ *     repeat pam_mm times:      s = (s * pam_mismatch) >> 16
+ * in 64-bit unsigned arithmetic, truncating at every step: the order is part of the contract, and every implementation (the device
+ * kernels, the host stage, a reader of the text) gives the same integers.  A hit with total_mm_plus_gaps == 0 is perfect (the guide's
+ * own site and its exact copies): counted, not scored.  The library ships no published weight table, only the mechanism. */
+typedef struct {
+  int32_t protospacer_length;  /* L: must be the guide's */
+  uint32_t gap;
+  uint32_t pam_mismatch;
+  const uint32_t* mismatch;    /* [L][5][5] */
+} calitas_score_model_t;
+
+/* What a guide's hits add up to.  Across window ranges, contigs and ranks of one job rows, perfect, sum_q32 and the table add and
+ * max_q32 takes the maximum; specificity = 2^32 / (2^32 + sum_q32), in double on the host.  The struct, table.counts included, is one
+ * block: one calitas_free. */
+typedef struct {
+  uint64_t rows;               /* all hits == n_rows of calitas_search_hits */
+  uint64_t perfect;            /* hits with total_mm_plus_gaps == 0 */
+  uint64_t sum_q32;            /* the sum of s over the other hits */
+  uint64_t max_q32;            /* the largest such s, 0 when there is none */
+  calitas_counts_t table;      /* the table of calitas_search_counts, from the same pass */
+} calitas_scores_t;
+
+/* calitas_search_counts plus the score.  No reference counterpart.  Behind removeOverlaps one lane per kept hit reads the hit's
+ * mismatch columns, fetches the reference base under each, looks the pair up in the model and the sums are reduced per workgroup; a
+ * few words cross PCIe.  Accepts whatever calitas_search_counts accepts (the whole reference, chrom_index, a window range).
+ * CALITAS_EINVAL for a model of another length than the guide's protospacer, a factor above 65536 or a NULL table.  Where a device
+ * stage declines, the host stage of calitas_hits_scores finishes the call. */
+int calitas_search_scores(calitas_ctx* ctx, const calitas_guide_t* guide, const calitas_params_t* params, const calitas_score_model_t* model,
+                          calitas_scores_t** out);
+/* ... for a batch of guides.  No reference counterpart.  It follows the rules of calitas_search_counts_batch: all guides have one length, so
+ * one model serves them; out[i] receives the block of guides[i], each freed with calitas_free. */
+int calitas_search_scores_batch(calitas_ctx* ctx, int32_t n_guides, const calitas_guide_t* guides, const calitas_params_t* params,
+                                const calitas_score_model_t* model, calitas_scores_t** out);
+
 /* SequentialGuideAligner.align on explicit (guide, target) pairs -- the per-task call of PairwiseAlignSequences
  * (PairwiseAlignSequences.scala:64 -> alignBest, SequentialGuideAligner.scala:333-345) and AlignToReference
  * (AlignToReference.scala:114-135 -> alignToRef / alignToRefBest, SequentialGuideAligner.scala:359-418).  Task t aligns
@@ -342,6 +385,12 @@ int calitas_hits_tsv(const calitas_ctx* ctx, const calitas_guide_t* guide, const
  * calitas_search_counts falls back to; works on a host-only context). */
 int calitas_hits_counts(const calitas_ctx* ctx, const calitas_guide_t* guide, const calitas_params_t* params, const calitas_aln_t* alns,
                         uint64_t n_alns, calitas_counts_t** out);
+
+/* The twin of calitas_hits_counts for the score.  No reference counterpart.  It runs removeOverlaps on the alignments of one guide, then the kept
+ * hits counted and scored from their ops (guide orientation) and the bases of the packed reference -- the host stage
+ * calitas_search_scores falls back to; works on a host-only context. */
+int calitas_hits_scores(const calitas_ctx* ctx, const calitas_guide_t* guide, const calitas_params_t* params, const calitas_score_model_t* model,
+                        const calitas_aln_t* alns, uint64_t n_alns, calitas_scores_t** out);
 
 /* A hit row built by the caller -- the variant branch of SearchReference.execute (SearchReference.scala:570-630) builds its
  * ReferenceHits from variant windows on the host.  calitas_hits_tsv_ext lets such hits take part in removeOverlaps (grouped by
