@@ -17,6 +17,16 @@ PATTERNS = {
     "fixed_nrg": (FIXED, ["nrg"], False),
     "n20_nngrrt_nrg": (N20, ["nngrrt", "nrg"], False),
     "max48": ("NNNNNNNNRNNNNNNNNNNNNNNNYNNNNNNN", ["nnnnnnnnnnnnnngg"], False),
+    # eight PAMs: all three bit-planes of the winning PAM's index; the footprint goes 27, 24, 27, 26, 24, 26, 23, 24, so the run-length
+    # mask is rebuilt before every PAM but the first, in both directions
+    "eight_pams": (N20, ["nnagaaw", "ngcg", "nnngatt", "nngrrt", "ngaa", "nnnrrt", "nrg", "nrrh"], False),
+    # the same on the 5' side, with a 16-nt PAM (lo = -16) and a 1-nt PAM among them
+    "five_prime_eight": (N20, ["tttv", "tycv", "ttnnnnnnnnnnnnnv", "ctn", "nngrrtnn", "gn", "gnnnnnc", "a"], True),
+    "five16_L32": ("NNNNNNNNRNNNNNNNNNNNNNNNYNNNNNNN", ["ttnnnnnnnnnnnnnv"], True),     # lo = -16 and a footprint of 48
+    # footprints at the corners of the run-length doubling: 1 (no step), 33 (last step by 1), 47 (last step by 15)
+    "one_letter": ("A", [], False),
+    "foot33": ("N" * 30, ["ngg"], False),
+    "foot47": ("N" * 31, ["nnnnnnnnnnnnnngg"], False),
 }
 
 
@@ -33,6 +43,12 @@ def revcomp(s):
 def brute_sites(contigs, proto, pams, five, chrom=None, start=0, end=None):
     """[(contig_index, protospacer_start, pam_start, strand, pam_index, pam_length, protospacer_length)] in the output's order."""
     out, L = [], len(proto)
+    clean = set("ACGTUacgtu")
+    # per PAM: the letters to hold the text against, as (offset, set); an N holds for every base of a clean footprint
+    letters = []
+    for pam in pams or [""]:
+        want = ((pam + proto) if five else (proto + pam)).upper()
+        letters.append([(i, IUPAC[c]) for i, c in enumerate(want) if c != "N"])
     for ci, seq in enumerate(contigs):
         if chrom is not None and ci != chrom:
             continue
@@ -49,13 +65,12 @@ def brute_sites(contigs, proto, pams, five, chrom=None, start=0, end=None):
                     if lo < r0 or hi > r1:
                         continue
                     foot = seq[lo:hi]
-                    if any(ch not in "ACGTUacgtu" for ch in foot):
+                    if not clean.issuperset(foot):
                         continue
                     text = foot.upper().replace("U", "T")
                     if strand == "-":
                         text = revcomp(text)
-                    want = ((pam + proto) if five else (proto + pam)).upper()
-                    if all(text[i] in IUPAC[want[i]] for i in range(len(want))):
+                    if all(text[i] in allowed for i, allowed in letters[k]):
                         pam_start = -1 if not pams else (p - pl if pam_left else p + L)
                         out.append((ci, p, pam_start, strand, k if pams else -1, pl, L))
                         break
@@ -66,6 +81,19 @@ def as_tuples(sites):
     """A find_sites array in brute_sites' form."""
     return [(int(s["contig_index"]), int(s["protospacer_start"]), int(s["pam_start"]), s["strand"].decode(), int(s["pam_index"]),
              int(s["pam_length"]), int(s["protospacer_length"])) for s in sites]
+
+
+def as_records(sites, dtype):
+    """brute_sites' tuples as a find_sites array (for a comparison of bytes, where as_tuples of the records would take seconds)."""
+    import numpy as np
+    out = np.zeros(len(sites), dtype=dtype)
+    if sites:
+        cols = list(zip(*sites))
+        for field, col in zip(("contig_index", "protospacer_start", "pam_start", None, "pam_index", "pam_length", "protospacer_length"), cols):
+            if field:
+                out[field] = np.array(col)
+        out["strand"] = np.array([s.encode() for s in cols[3]], dtype="S1")
+    return out
 
 
 def _rand(rng, n):
@@ -108,6 +136,17 @@ def host_genome(seed=7):
     _put(d, 64 - 10, site)                              # straddles a 32-base word boundary
     _put(d, 600, "N" * 200)
     return ["chrA", "chrB", "c26", "c12", "chrD"], ["".join(x) for x in (a, b, c26, c12, d)]
+
+
+def many_contigs(seed, n):
+    """n contigs of random bases, every ninth 2500 to 20000 bases long (one to three segments of 8192 bases with sites in them; every
+    other one of these at most 5000, to keep the brute force quick), the others 90 to 250: with one scan tile per contig, a launch of
+    about 16 n segments most of which count nothing.
+    Returns (names, strings)."""
+    rng = random.Random(seed)
+    seqs = [_rand(rng, (rng.randrange(2500, 20001) if i % 18 == 4 else rng.randrange(2500, 5001)) if i % 9 == 4 else rng.randrange(90, 251))
+            for i in range(n)]
+    return ["m%d" % i for i in range(n)], seqs
 
 
 def gpu_genome(seed, tile, chunk):

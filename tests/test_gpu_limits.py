@@ -16,6 +16,25 @@ the CPU oracle, every column -- and one step past each limit, which must be refu
 | align_pk_kernel: 4 big (L + 2) < 30000 | pack16-edge-29920 / pack16-beyond-30008        | (the other kernel, same rows)       |
 | E != d (scan budget from the costs)    | costs-E3d-L20, costs-E3d-L28                   |                                     |
 | mixed L / PAM side in one pass         | test_mixed_guides_in_one_pass                  | another CLI length: refused         |
+
+The limits of the counts, score and site kernels are held by tests of their own modules:
+
+| limit                                  | at the limit                                   | one past it                         |
+|----------------------------------------|------------------------------------------------|-------------------------------------|
+| counts table <= 4096 cells in LDS      | test_gpu_table_limits: cells-4096              | cells-4224, cells-4524-sparse,      |
+| (COUNTS_LDS_CELLS)                     |                                                | cells-9702-dense (the largest table |
+|                                        |                                                | a search asks for): added directly  |
+| device table zero between calls        | test_the_device_table_is_left_clean            |                                     |
+| 128 x 256 lanes of a counts kernel     | test_more_items_than_one_stride (> 65 536      |                                     |
+|                                        | items: a second and a third stride)            |                                     |
+| score factors 0 .. 65536 (17 bits)     | test_factors_of_zero_and_one                   | (ScoreModel takes none above)       |
+| 8 PAMs of a site pattern               | test_gpu_sites: eight_pams, five_prime_eight,  | (the ABI takes 8 at most)           |
+|                                        | test_every_pam_index_wins_on_both_strands      |                                     |
+| 5' PAM <= 16 nt (lo = -16)             | five_prime_eight, five16_L32                   | refusal "17-nt PAM" above           |
+| footprint 1 .. 48 bases                | one_letter (1), foot33, foot47, max48,         |                                     |
+|                                        | five16_L32 (48)                                |                                     |
+| 1024 threads of sites_offsets_kernel   | test_many_segments_through_the_offsets_scan    |                                     |
+|                                        | (two and three counts per thread)              |                                     |
 """
 import re
 

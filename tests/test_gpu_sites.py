@@ -97,6 +97,86 @@ def test_device_equals_host_twin_equals_brute_force(C, name, chunk, monkeypatch)
         ctx.close()
 
 
+@pytest.mark.parametrize("name", ["eight_pams", "five_prime_eight"])
+def test_every_pam_index_wins_on_both_strands(C, name, monkeypatch):
+    """Eight PAMs: each of the indices 0 to 7 -- every combination of the three bit-planes sites_kernel keeps the winner in -- is the
+    first matching PAM somewhere on both strands (by the brute force), and the device's records carry index and PAM length there."""
+    monkeypatch.delenv("CALITAS_SITES_SEGS", raising=False)
+    proto, pams, five = R.PATTERNS[name]
+    want = _want(None, name)
+    classes = {}
+    for w in want:
+        classes[(w[3], w[4])] = classes.get((w[3], w[4]), 0) + 1
+    print(name, "sites", len(want), "smallest class", min(classes.values()))
+    assert len(pams) == 8 and set(classes) == {(s, k) for s in "+-" for k in range(8)}
+    ctx = _context(C, None, monkeypatch)
+    try:
+        got = ctx.find_sites(_pattern(C, name))
+        assert R.as_tuples(got) == want
+        seen = {}
+        for s in got:
+            key = (s["strand"].decode(), int(s["pam_index"]))
+            seen[key] = seen.get(key, 0) + 1
+            assert int(s["pam_length"]) == len(pams[key[1]])
+        assert seen == classes
+    finally:
+        ctx.close()
+
+
+def _launch_segments(C, ctx, seqs):
+    """Segments of 256 words (8192 bases) a call over every contig launches, as calitas_find_sites_impl works them out: from the first
+    contig's first word, rounded down to a segment, to the last contig's last word."""
+    import ctypes
+    g = ctypes.c_uint64()
+    base = []
+    for i in (0, len(seqs) - 1):
+        C._lib.check(ctx._h, C._lib.lib.calitas_contig_packed_base(ctx._h, i, ctypes.byref(g)))
+        base.append(g.value)
+    w0, w1 = base[0] // 32, (base[1] + len(seqs[-1]) + 31) // 32
+    w0 -= w0 % 256
+    return (w1 - w0 + 255) // 256
+
+
+@pytest.mark.parametrize("n_contigs, per", [(70, 2), (140, 3)])
+def test_many_segments_through_the_offsets_scan(C, monkeypatch, n_contigs, per):
+    """More segments than sites_offsets_kernel has threads: with a tile per contig (lane chunk 512: 16 segments a tile) 70 contigs are
+    more than 1024 segments, two counts per thread, and 140 more than 2048, three per thread -- stretches that straddle tiles, the
+    clamp at n and threads whose stretch lies wholly past n.  Listing and counts against the brute force and the host twin, for one PAM,
+    eight PAMs and the dense pattern (every segment of a contig counts), and once with 16 segments per workgroup."""
+    monkeypatch.setenv("CALITAS_CHUNK", "512")
+    monkeypatch.delenv("CALITAS_SITES_SEGS", raising=False)
+    names, seqs = R.many_contigs(500 + n_contigs, n_contigs)
+    ctx = C.Context(0)
+    try:
+        ctx.set_reference(names, [s.encode() for s in seqs])
+        census = ctx.tile_census()
+        n_segs = _launch_segments(C, ctx, seqs)
+        print(n_contigs, "contigs", sum(len(s) for s in seqs), "bases", census["tiles"], "tiles", n_segs, "segments, per", -(-n_segs // 1024))
+        assert census["tile_bases"] == 512 * 256
+        assert 1024 * (per - 1) < n_segs <= 1024 * per
+        for pat, spec in (("n20_nrg", R.PATTERNS["n20_nrg"]), ("eight_pams", R.PATTERNS["eight_pams"]), ("NNNNn", ("NNNN", ["n"], False))):
+            want = R.brute_sites(seqs, *spec)
+            G = _pattern(C, pat) if pat in R.PATTERNS else C.Guide(pat)
+            got = ctx.find_sites(G)
+            print(pat, "sites", len(want))
+            assert len(want) > 1000 and len({w[0] for w in want}) == n_contigs
+            # neighbouring segments that both count something: a thread's stretch with more than one non-zero count
+            assert {w[0] for w in want if w[1] < 8192} & {w[0] for w in want if 8192 <= w[1] < 16384}
+            assert len(got) == len(want) and got.tobytes() == R.as_records(want, got.dtype).tobytes(), pat
+            assert got.tobytes() == ctx.find_sites(G, host=True).tobytes(), pat
+            hist = np.zeros((n_contigs, 2), dtype=np.uint64)
+            for w in want:
+                hist[w[0], int(w[3] == "-")] += 1
+            n, table = ctx.count_sites(G)
+            assert n == len(want) and np.array_equal(table, hist), pat
+            if pat == "eight_pams":
+                monkeypatch.setenv("CALITAS_SITES_SEGS", "16")
+                assert ctx.find_sites(G).tobytes() == got.tobytes()
+                monkeypatch.delenv("CALITAS_SITES_SEGS")
+    finally:
+        ctx.close()
+
+
 @pytest.mark.parametrize("segs", [None, "3", "16"])
 def test_dense_output_across_many_workgroups(C, monkeypatch, segs):
     """NNNN + n: every clean position is a site on both strands -- more than 1e5 records from two contigs, whose offsets run across
