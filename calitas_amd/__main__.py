@@ -42,6 +42,9 @@ def main(argv=None):
     sr.add_argument("--scores", metavar="MODEL",
                     help="write the specificity score under the model file (guide_id rows perfect offtarget_sum_q32 max_q32 specificity) "
                          "instead of hits.txt; with --counts the table's TSV follows it behind an empty line")
+    sr.add_argument("--top", metavar="K", type=int,
+                    help="with --scores: the K (1 .. 256) highest-scoring imperfect hits of the same pass behind the scores and an empty line "
+                         "(guide_id rank chromosome coordinate_start coordinate_end strand guide_mm guide_gaps pam_mm score_q32 score)")
     _costs(sr)
 
     a2r = sub.add_parser("AlignToReference")
@@ -93,13 +96,17 @@ def main(argv=None):
     if a.tool == "SearchReference":
         if a.scores is not None and a.variants is not None:
             top.error("--scores covers the reference-genome branch only (no --variants)")
+        if a.top is not None and a.scores is None:
+            top.error("--top K requires --scores MODEL")
+        if a.top is not None and not 1 <= a.top <= 256:
+            top.error("--top K: K is 1 .. 256")
         SearchReference(guide=a.guide, guide_id=a.guide_id, ref=a.ref, output=a.output, auxiliary_pams=a.auxiliary_pams,
                         window_size=a.window_size, max_guide_diffs=a.max_guide_diffs, max_pam_mismatches=a.max_pam_mismatches,
                         max_gaps_between_guide_and_pam=a.max_gaps_between_guide_and_pam, max_total_diffs=a.max_total_diffs,
                         max_overlap=a.max_overlap, guide_mismatch_net_cost=a.guide_mismatch_net_cost,
                         pam_mismatch_net_cost=a.pam_mismatch_net_cost, genome_gap_net_cost=a.genome_gap_net_cost,
                         guide_gap_net_cost=a.guide_gap_net_cost, chrom=a.chrom, variants=a.variants, max_variants=a.max_variants,
-                        device=a.device).execute(counts=a.counts, scores=ScoreModel.read(a.scores) if a.scores is not None else None)
+                        device=a.device).execute(counts=a.counts, scores=ScoreModel.read(a.scores) if a.scores is not None else None, top=a.top)
     elif a.tool == "AlignToReference":
         text = align_to_reference(a.input, a.ref, a.output, window_size=a.window_size, max_guide_diffs=a.max_guide_diffs,
                                   max_pam_mismatches=a.max_pam_mismatches, max_gaps_between_guide_and_pam=a.max_gaps_between_guide_and_pam,

@@ -76,6 +76,19 @@ class ScoresT(ctypes.Structure):
                 ("table", CountsT)]
 
 
+class TopHitT(ctypes.Structure):
+    _fields_ = [("score_q32", ctypes.c_uint64), ("contig_index", ctypes.c_int32), ("coordinate_start", ctypes.c_int32),
+                ("coordinate_end", ctypes.c_int32), ("strand", ctypes.c_int8), ("guide_mm", ctypes.c_uint8), ("guide_gaps", ctypes.c_uint8),
+                ("pam_mm", ctypes.c_uint8)]
+
+
+class TopT(ctypes.Structure):
+    _fields_ = [("scores", ScoresT), ("k", ctypes.c_uint32), ("n", ctypes.c_uint32), ("hits", ctypes.POINTER(TopHitT))]
+
+
+TOP_MAX = 256
+assert ctypes.sizeof(TopHitT) == 24
+
 # every symbol include/calitas_hip.h declares
 SYMBOLS = ["calitas_create", "calitas_destroy", "calitas_last_error", "calitas_free", "calitas_set_reference",
            "calitas_set_reference_fasta", "calitas_save_index", "calitas_load_index", "calitas_reference_info", "calitas_contig_name", "calitas_genome_build", "calitas_fetch_bases", "calitas_expand_rows",
@@ -83,6 +96,7 @@ SYMBOLS = ["calitas_create", "calitas_destroy", "calitas_last_error", "calitas_f
            "calitas_padded_strings", "calitas_align_windows", "calitas_padded_strings_target", "calitas_version", "calitas_switches", "calitas_reap_wait",
            "calitas_search_counts", "calitas_search_counts_batch", "calitas_hits_counts",
            "calitas_search_scores", "calitas_search_scores_batch", "calitas_hits_scores",
+           "calitas_search_top", "calitas_search_top_batch", "calitas_hits_top",
            "calitas_find_sites", "calitas_count_sites", "calitas_find_sites_host"]
 
 if not os.path.exists(LIB_PATH):
@@ -153,6 +167,12 @@ lib.calitas_search_scores_batch.argtypes = [ctypes.c_void_p, ctypes.c_int32, cty
                                             ctypes.POINTER(ScoreModelT), ctypes.POINTER(ctypes.POINTER(ScoresT))]
 lib.calitas_hits_scores.argtypes = [ctypes.c_void_p, ctypes.POINTER(GuideT), ctypes.POINTER(ParamsT), ctypes.POINTER(ScoreModelT),
                                     ctypes.POINTER(AlnT), ctypes.c_uint64, ctypes.POINTER(ctypes.POINTER(ScoresT))]
+lib.calitas_search_top.argtypes = [ctypes.c_void_p, ctypes.POINTER(GuideT), ctypes.POINTER(ParamsT), ctypes.POINTER(ScoreModelT), ctypes.c_uint32,
+                                   ctypes.POINTER(ctypes.POINTER(TopT))]
+lib.calitas_search_top_batch.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.POINTER(GuideT), ctypes.POINTER(ParamsT),
+                                         ctypes.POINTER(ScoreModelT), ctypes.c_uint32, ctypes.POINTER(ctypes.POINTER(TopT))]
+lib.calitas_hits_top.argtypes = [ctypes.c_void_p, ctypes.POINTER(GuideT), ctypes.POINTER(ParamsT), ctypes.POINTER(ScoreModelT), ctypes.c_uint32,
+                                 ctypes.POINTER(AlnT), ctypes.c_uint64, ctypes.POINTER(ctypes.POINTER(TopT))]
 lib.calitas_pin_host.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64]
 lib.calitas_unpin_host.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
 lib.calitas_genome_build.restype = ctypes.c_char_p

@@ -5,12 +5,13 @@ Names, argument meaning and error behaviour follow
   calitas/src/main/scala/com/editasmedicine/aligner/SearchReference.scala (SearchReference flags, execute)
 so the parity tests read like the reference's own tests.  All alignment work happens in libcalitas_hip.so.
 """
+import collections
 import contextlib
 import ctypes
 import time
 
 from . import _lib
-from ._lib import AlnT, CalitasError, CountsT, GuideT, ParamsT, ScoreModelT, ScoresT, SiteT, TimingT, lib
+from ._lib import AlnT, CalitasError, CountsT, GuideT, ParamsT, ScoreModelT, ScoresT, SiteT, TimingT, TopT, lib
 
 
 class Defaults:  # SequentialGuideAligner.scala:17-28
@@ -534,20 +535,70 @@ class Context:
         return n.value, table[:len(self.contig_names)]
 
     @staticmethod
+    def _scores_of(c):
+        """A calitas_scores_t as a Scores object (the table is copied)."""
+        import numpy as np
+        t = c.table
+        shape = (2, t.n_mm, t.n_gaps, t.n_pam)
+        n = 2 * t.n_mm * t.n_gaps * t.n_pam
+        table = np.ctypeslib.as_array(t.counts, shape=(n,)).astype(np.uint64).reshape(shape)   # (astype copies)
+        if int(table.sum()) != c.rows or t.rows != c.rows or c.perfect > c.rows:
+            raise CalitasError(_lib.EHIP, "the scores block does not add up to its rows")
+        return Scores(int(c.rows), int(c.perfect), int(c.sum_q32), int(c.max_q32), table)
+
+    @staticmethod
     def _take_scores(ptr):
         """A calitas_scores_t block as a Scores object; the block is freed."""
-        import numpy as np
         try:
-            c = ptr.contents
-            t = c.table
-            shape = (2, t.n_mm, t.n_gaps, t.n_pam)
-            n = 2 * t.n_mm * t.n_gaps * t.n_pam
-            table = np.ctypeslib.as_array(t.counts, shape=(n,)).astype(np.uint64).reshape(shape)   # (astype copies)
-            if int(table.sum()) != c.rows or t.rows != c.rows or c.perfect > c.rows:
-                raise CalitasError(_lib.EHIP, "the scores block does not add up to its rows")
-            return Scores(int(c.rows), int(c.perfect), int(c.sum_q32), int(c.max_q32), table)
+            return Context._scores_of(ptr.contents)
         finally:
             lib.calitas_free(ptr)
+
+    def _take_top(self, ptr):
+        """A calitas_top_t block as a Top object; the block is freed."""
+        try:
+            t = ptr.contents
+            scores = self._scores_of(t.scores)
+            if t.n != min(t.k, scores.rows - scores.perfect):
+                raise CalitasError(_lib.EHIP, "the top block does not hold min(k, imperfect rows) records")
+            import numpy as np
+            names = self.contig_names
+            # (one copy and one tolist(): a ctypes field access per value cost 0.5 ms per 256 records, a quarter of an hg38-sized call)
+            rec = np.frombuffer(ctypes.string_at(t.hits, 24 * t.n), dtype=TOP_DTYPE).tolist() if t.n else []
+            hits = [TopHit(s, names[c], a, b, st.decode(), mm, gp, pm) for s, c, a, b, st, mm, gp, pm in rec]
+            return Top(scores, int(t.k), hits)
+        finally:
+            lib.calitas_free(ptr)
+
+    def search_top(self, guide, params, model, k):
+        """calitas_search_top: search_scores plus the k (1 .. 256) highest-scoring imperfect hits -- a Top object.  Equal to top_of_rows
+        of the hits.txt search_hits gives for the same guide and params, window range included; no text is built or copied."""
+        g = guide.to_c()
+        m = model.to_c()
+        out = ctypes.POINTER(TopT)()
+        _lib.check(self._h, lib.calitas_search_top(self._h, ctypes.byref(g), ctypes.byref(params), ctypes.byref(m), _top_k(k), ctypes.byref(out)))
+        return self._take_top(out)
+
+    def search_top_batch(self, guides, params, model, k):
+        """calitas_search_top_batch: a list of Top, one per guide (all of one length: one model serves them), pipelined on the device
+        like search_scores_batch."""
+        n = len(guides)
+        keep = [g.to_c() for g in guides]
+        garr = (GuideT * n)(*keep)
+        m = model.to_c()
+        out = (ctypes.POINTER(TopT) * n)()
+        _lib.check(self._h, lib.calitas_search_top_batch(self._h, n, garr, ctypes.byref(params), ctypes.byref(m), _top_k(k), out))
+        return [self._take_top(out[i]) for i in range(n)]
+
+    def hits_top(self, guide, params, model, k, alignments):
+        """calitas_hits_top: hits_scores plus the list -- the host stage, usable on a host-only context."""
+        g = guide.to_c()
+        m = model.to_c()
+        n = len(alignments)
+        arr = (AlnT * max(1, n))(*[a.to_c() for a in alignments])
+        out = ctypes.POINTER(TopT)()
+        _lib.check(self._h, lib.calitas_hits_top(self._h, ctypes.byref(g), ctypes.byref(params), ctypes.byref(m), _top_k(k), arr, n, ctypes.byref(out)))
+        return self._take_top(out)
 
     def search_scores(self, guide, params, model):
         """calitas_search_scores: search_counts plus the specificity score of the guide's hits under `model` (a ScoreModel of the
@@ -710,10 +761,11 @@ class SearchReference:
             if own:
                 ctx.close()
 
-    def scores(self, model):
-        """The specificity score instead of hits.txt (Context.search_scores): a Scores object."""
+    def _score_pass(self, call):
+        """What scores() and top() share: the context (this object's, or one of its own with the reference loaded), the params of the
+        flags and the timing around call(ctx, params)."""
         if self.variants is not None:
-            raise ValueError("scores() covers the reference-genome branch only (no --variants)")
+            raise ValueError("scores() and top() cover the reference-genome branch only (no --variants)")
         ctx = self.context
         own = ctx is None
         if own:
@@ -727,7 +779,7 @@ class SearchReference:
                 chrom_index = ctx.contig_names.index(self.chrom)
             params = make_params(chrom_index=chrom_index, **self._kw)
             t0 = time.perf_counter()
-            got = ctx.search_scores(self.query, params, model)
+            got = call(ctx, params)
             self.timing = ctx.timing()
             self.wall_ms = (time.perf_counter() - t0) * 1e3
             return got
@@ -735,12 +787,25 @@ class SearchReference:
             if own:
                 ctx.close()
 
-    def execute(self, counts=False, scores=None):
+    def scores(self, model):
+        """The specificity score instead of hits.txt (Context.search_scores): a Scores object."""
+        return self._score_pass(lambda ctx, params: ctx.search_scores(self.query, params, model))
+
+    def top(self, model, k):
+        """The scores and the k highest-scoring imperfect hits (Context.search_top): a Top object."""
+        return self._score_pass(lambda ctx, params: ctx.search_top(self.query, params, model, k))
+
+    def execute(self, counts=False, scores=None, top=None):
         """counts=True (`--counts`): the table as a TSV (counts_tsv) instead of hits.txt.  scores=ScoreModel (`--scores MODEL`): the
-        scores TSV (scores_tsv); with counts as well, the counts TSV of the same pass's table follows it behind an empty line."""
+        scores TSV (scores_tsv); top=K with it (`--top K`): the top TSV (top_tsv) of the same pass behind an empty line; with counts as
+        well, the counts TSV of the same pass's table follows behind an empty line."""
+        if top is not None and scores is None:
+            raise ValueError("--top K requires --scores MODEL")
         if scores is not None:
-            got = self.scores(scores)
-            text = scores_tsv(self.guide_id, got) + ("\n" + counts_tsv(self.guide_id, got.table) if counts else "")
+            got = self.scores(scores) if top is None else self.top(scores, top)
+            sc = got if top is None else got.scores
+            text = (scores_tsv(self.guide_id, sc) + ("\n" + top_tsv(self.guide_id, got) if top is not None else "")
+                    + ("\n" + counts_tsv(self.guide_id, sc.table) if counts else ""))
         else:
             text = counts_tsv(self.guide_id, self.counts()) if counts else self.run()[0]
         if self.output is None:
@@ -976,6 +1041,79 @@ def scores_of_rows(rows, model, shape=None):
             top = max(top, s)
     table = counts_of_rows(rows, shape) if shape is not None else np.array([len(rows)], dtype=np.uint64)
     return Scores(len(rows), perfect, total, top, table)
+
+
+# calitas_top_hit_t as a numpy record
+TOP_DTYPE = [("score_q32", "<u8"), ("contig_index", "<i4"), ("coordinate_start", "<i4"), ("coordinate_end", "<i4"), ("strand", "S1"),
+             ("guide_mm", "u1"), ("guide_gaps", "u1"), ("pam_mm", "u1")]
+
+TOP_COLUMNS = ("guide_id", "rank", "chromosome", "coordinate_start", "coordinate_end", "strand", "guide_mm", "guide_gaps", "pam_mm", "score_q32",
+               "score")
+
+# A record of a top list: calitas_top_hit_t with the chromosome's name in the place of contig_index.
+TopHit = collections.namedtuple("TopHit", ("score_q32", "chromosome", "coordinate_start", "coordinate_end", "strand", "guide_mm",
+                                           "guide_gaps", "pam_mm"))
+
+
+def _top_k(k):
+    if not isinstance(k, int) or isinstance(k, bool) or k < 0 or k >= 1 << 32:
+        raise ValueError("k of a top call is an integer (1 .. %d)" % _lib.TOP_MAX)
+    return k
+
+
+class Top:
+    """What a top call returns: `scores` (the Scores of the same pass), `k` as asked and `hits`, the min(k, rows - perfect)
+    highest-scoring imperfect hits as TopHit records, best first; among equal scores the hit whose row comes earlier in hits.txt."""
+    __slots__ = ("scores", "k", "hits")
+
+    def __init__(self, scores, k, hits):
+        self.scores, self.k, self.hits = scores, k, list(hits)
+
+    def merge(self, *others):
+        """Consecutive pieces of one job (window ranges, contigs, ranks) IN THEIR ORDER: the scores add, the lists merge stably by
+        score (a piece's records stay in order and come before a later piece's equal scores), cut at k."""
+        scores, hits = self.scores, list(self.hits)
+        for o in others:
+            if o.k != self.k:
+                raise ValueError("top lists of different k do not merge")
+            scores = scores + o.scores
+            hits = hits + list(o.hits)
+        hits.sort(key=lambda h: -h.score_q32)               # (stable: the tie rule)
+        return Top(scores, self.k, hits[:self.k])
+
+    def __eq__(self, o):
+        return isinstance(o, Top) and self.k == o.k and self.hits == o.hits and self.scores == o.scores
+
+    __hash__ = None
+
+    def __repr__(self):
+        return "Top(k=%d, n=%d, %r)" % (self.k, len(self.hits), self.scores)
+
+
+def top_of_rows(rows, model, k, shape=None):
+    """What search_top returns, from hits.txt rows (read_hits output) in the text's order: the reference implementation of the
+    contract -- score_of_row per row, perfect rows dropped, a stable sort by descending score.  shape: as for scores_of_rows."""
+    if not 1 <= k <= _lib.TOP_MAX:
+        raise ValueError("k of a top call is 1 .. %d" % _lib.TOP_MAX)
+    hits = []
+    for r in rows:
+        s = score_of_row(r, model)
+        if s is None:
+            continue
+        hits.append(TopHit(s, r["chromosome"], int(r["coordinate_start"]), int(r["coordinate_end"]), r["strand"], int(r["guide_mm"]),
+                           int(r["guide_gaps"]), int(r["pam_mm"])))
+    hits.sort(key=lambda h: -h.score_q32)
+    return Top(scores_of_rows(rows, model, shape), k, hits[:k])
+
+
+def top_tsv(guide_id, top):
+    """`SearchReference --scores MODEL --top K`: header guide_id rank chromosome coordinate_start coordinate_end strand guide_mm
+    guide_gaps pam_mm score_q32 score, then one line per record; rank is 1-based, score = score_q32 / 2^32."""
+    lines = ["\t".join(TOP_COLUMNS)]
+    for i, h in enumerate(top.hits):
+        lines.append("%s\t%d\t%s\t%d\t%d\t%s\t%d\t%d\t%d\t%d\t%.6f" % (guide_id, i + 1, h.chromosome, h.coordinate_start, h.coordinate_end, h.strand,
+                                                                         h.guide_mm, h.guide_gaps, h.pam_mm, h.score_q32, h.score_q32 / 2.0 ** 32))
+    return "\n".join(lines) + "\n"
 
 
 def scores_tsv(guide_id, scores):

@@ -829,6 +829,76 @@ int calitas_search_scores_batch(calitas_ctx* ctx, int32_t n_guides, const calita
   return rc;
 }
 
+// A guide's top list as the ABI hands it over: struct, table cells and records in one block of the library's.
+static calitas_top_t* top_block(const CountsShape& shape, const uint64_t* table, uint64_t rows, const ScoreWords& w, uint32_t k) {
+  const size_t cells = shape.cells(), n = std::min<size_t>(w.top.hits.size(), k);
+  calitas_top_t* t = (calitas_top_t*)out_alloc(sizeof(calitas_top_t) + cells * sizeof(uint64_t) + n * sizeof(calitas_top_hit_t));
+  if (!t) return nullptr;
+  calitas_scores_t* c = &t->scores;
+  c->rows = rows; c->perfect = w.perfect; c->sum_q32 = w.sum_q32; c->max_q32 = w.max_q32;
+  c->table.n_mm = shape.n_mm; c->table.n_gaps = shape.n_gaps; c->table.n_pam = shape.n_pam; c->table.rows = rows;
+  c->table.counts = reinterpret_cast<uint64_t*>(t + 1);
+  std::memcpy(c->table.counts, table, cells * sizeof(uint64_t));
+  t->k = k; t->n = (uint32_t)n;
+  t->hits = reinterpret_cast<calitas_top_hit_t*>(c->table.counts + cells);
+  if (n) std::memcpy(t->hits, w.top.hits.data(), n * sizeof(calitas_top_hit_t));
+  return t;
+}
+static const char* const kBadTopK = "k of a top call must be 1 .. CALITAS_TOP_MAX (256)";
+
+int calitas_search_top(calitas_ctx* ctx, const calitas_guide_t* guide, const calitas_params_t* params, const calitas_score_model_t* model,
+                       uint32_t k, calitas_top_t** out) {
+  if (!ctx) return CALITAS_EINVAL;
+  if (!guide || !params || !model || !out) return fail(ctx, CALITAS_EINVAL, "NULL argument");
+  *out = nullptr;
+  if (k == 0 || k > CALITAS_TOP_MAX) return fail(ctx, CALITAS_EINVAL, kBadTopK);
+  GuideHost gh;
+  ScoreModelHost mh;
+  const std::string e = score_inputs(*guide, model, gh, mh);
+  if (!e.empty()) return fail(ctx, CALITAS_EINVAL, e);
+  mh.top_k = k;
+  CountsShape shape;
+  std::vector<uint64_t> table;
+  uint64_t rows = 0;
+  ScoreWords w;
+  const int rc = calitas_search_counts_impl(ctx, guide, params, &shape, &table, &rows, &mh, &w);
+  if (rc) return rc;
+  if (w.top.hits.size() != std::min<uint64_t>(k, rows - w.perfect)) return fail(ctx, CALITAS_EHIP, "the list of a top call does not have min(k, imperfect rows) records (internal error)");
+  *out = top_block(shape, table.data(), rows, w, k);
+  return *out ? CALITAS_OK : fail(ctx, CALITAS_EINVAL, "out of memory");
+}
+
+int calitas_search_top_batch(calitas_ctx* ctx, int32_t n_guides, const calitas_guide_t* guides, const calitas_params_t* params,
+                             const calitas_score_model_t* model, uint32_t k, calitas_top_t** out) {
+  if (!ctx) return CALITAS_EINVAL;
+  if (n_guides <= 0 || !guides || !params || !model || !out) return fail(ctx, CALITAS_EINVAL, "bad argument");
+  for (int i = 0; i < n_guides; i++) out[i] = nullptr;
+  if (k == 0 || k > CALITAS_TOP_MAX) return fail(ctx, CALITAS_EINVAL, kBadTopK);
+  ScoreModelHost mh;
+  for (int i = 0; i < n_guides; i++) {                        // (all guides of a batch have one length: one model serves them)
+    GuideHost gh;
+    const std::string e = score_inputs(guides[i], model, gh, mh);
+    if (!e.empty()) return fail(ctx, CALITAS_EINVAL, e);
+  }
+  mh.top_k = k;
+  std::vector<std::vector<uint64_t>> tables((size_t)n_guides);
+  std::vector<uint64_t> rows((size_t)n_guides, 0);
+  std::vector<ScoreWords> words((size_t)n_guides);
+  int rc = calitas_search_hits_batch_impl(ctx, n_guides, guides, nullptr, params, nullptr, nullptr, nullptr, nullptr, rows.data(), &tables, &mh, &words);
+  for (int i = 0; i < n_guides && !rc; i++) {
+    GuideHost gh;
+    CountsShape shape;
+    const ScoreWords& w = words[(size_t)i];
+    std::string e = make_guide_host(guides[i], gh);
+    if (e.empty()) e = counts_shape(gh, *params, shape);
+    if (!e.empty() || tables[(size_t)i].size() != shape.cells()) rc = fail(ctx, CALITAS_EINVAL, e.empty() ? "a guide's table has another shape than its plan (internal error)" : e);
+    else if (w.top.hits.size() != std::min<uint64_t>(k, rows[(size_t)i] - w.perfect)) rc = fail(ctx, CALITAS_EHIP, "the list of a top call does not have min(k, imperfect rows) records (internal error)");
+    else if (!(out[i] = top_block(shape, tables[(size_t)i].data(), rows[(size_t)i], w, k))) rc = fail(ctx, CALITAS_EINVAL, "out of memory");
+  }
+  if (rc) for (int i = 0; i < n_guides; i++) { calitas_free(out[i]); out[i] = nullptr; }
+  return rc;
+}
+
 int calitas_scan_candidates(calitas_ctx* ctx, int32_t n_guides, const calitas_guide_t* guides, const calitas_params_t* params,
                             uint32_t** records, uint64_t* n_records) {
   return calitas_scan_candidates_impl(ctx, n_guides, guides, params, records, n_records);
@@ -946,6 +1016,30 @@ int calitas_hits_scores(const calitas_ctx* ctx, const calitas_guide_t* guide, co
                   ctx->pool);
   if (!e.empty()) return fail(c, CALITAS_EINVAL, e);
   *out = scores_block(shape, table.data(), rows, w);
+  return *out ? CALITAS_OK : fail(c, CALITAS_EINVAL, "out of memory");
+}
+
+int calitas_hits_top(const calitas_ctx* ctx, const calitas_guide_t* guide, const calitas_params_t* params, const calitas_score_model_t* model,
+                     uint32_t k, const calitas_aln_t* alns, uint64_t n_alns, calitas_top_t** out) {
+  if (!ctx || !guide || !params || !model || !out || (n_alns && !alns)) return CALITAS_EINVAL;
+  calitas_ctx* c = const_cast<calitas_ctx*>(ctx);
+  *out = nullptr;
+  if (!ctx->has_ref) return fail(c, CALITAS_ESTATE, "calitas_set_reference has not been called");
+  if (k == 0 || k > CALITAS_TOP_MAX) return fail(c, CALITAS_EINVAL, kBadTopK);
+  GuideHost gh;
+  ScoreModelHost mh;
+  CountsShape shape;
+  std::string e = score_inputs(*guide, model, gh, mh);
+  if (e.empty()) e = counts_shape(gh, *params, shape);
+  if (!e.empty()) return fail(c, CALITAS_EINVAL, e);
+  std::vector<uint64_t> table(shape.cells(), 0);
+  uint64_t rows = 0;
+  ScoreWords w;
+  w.top.k = k;
+  e = hits_top(ctx->ref, gh, *params, mh, alns, n_alns, shape.n_mm, shape.n_gaps, shape.n_pam, table.data(), &rows, &w.perfect, &w.sum_q32, &w.max_q32,
+               &w.top, ctx->pool);
+  if (!e.empty()) return fail(c, CALITAS_EINVAL, e);
+  *out = top_block(shape, table.data(), rows, w, k);
   return *out ? CALITAS_OK : fail(c, CALITAS_EINVAL, "out of memory");
 }
 

@@ -653,16 +653,20 @@ __global__ __launch_bounds__(64 * BIN_WAVES) void bin_rows_kernel(BinArgs a, Mid
 // Counts mode: the bins' kept hits (bin_hits_small_kernel / bin_hits_kernel listed the bins that have any, with their rows' alignments
 // in final order) counted into the call's table instead of being built as rows.  One lane per listed bin (a bin keeps 0-2 hits, at most
 // BIN_ROWS); the cell comes from the same arithmetic the row's length does (hits_dev.hpp: hit_key).  The workgroup that finishes last
-// brings the table to the host and posts what bin_rows_kernel posts when it starts.  The body is a template over SCORE:
-// bin_counts_kernel is it without the score (what a counts call launches, unchanged), bin_scores_kernel with it.
-template <bool SCORE>
-__device__ __forceinline__ void bin_counts_body(const BinArgs& a, const CountsOut& co, const ScoreArgs& sa, const HitsRef& ref, const RowsArgs& o,
-                                                uint32_t* hist, ScoreLds* sl) {
+// brings the table to the host and posts what bin_rows_kernel posts when it starts.  The body is a template over a mode:
+// bin_counts_kernel is it without the score (what a counts call launches, unchanged), bin_scores_kernel with it, bin_top_kernel with
+// the score and the list.
+template <int MODE>
+__device__ __forceinline__ void bin_counts_body(const BinArgs& a, const CountsOut& co, const ScoreArgs& sa, const TopArgs& ta, const HitsRef& ref,
+                                                const RowsArgs& o, uint32_t* hist, ScoreLds* sl, TopLds* tl) {
+  constexpr bool SCORE = MODE != MODE_COUNTS, TOP = MODE == MODE_TOP;
   CALITAS_TAIL_PRIO();
   if (SCORE) score_begin(*sl, sa);
+  if (TOP) top_begin(*tl);
   counts_begin(hist, co);
   const uint32_t n_todo = *a.rows_count;
   ScoreAcc acc;
+  if (!TOP) {
   if (*a.flags == 0) {                                     // (a bin declined: the general kernels count this range)
     for (uint32_t it = blockIdx.x * COUNTS_BLOCK + threadIdx.x; it < n_todo; it += gridDim.x * COUNTS_BLOCK) {
       const uint32_t rel = a.rows_list[it];
@@ -678,9 +682,60 @@ __device__ __forceinline__ void bin_counts_body(const BinArgs& a, const CountsOu
       }
     }
   }
+  } else {
+    // A trip is one slot of one listed bin per lane.  top_offer is a workgroup barrier, so both trip counts are the same in every lane
+    // of the workgroup: the outer one is a function of the list's length and the grid, the inner one the most rows any bin of this
+    // trip has in the workgroup (wave, then LDS: tl->most); lanes past the end of the list, and bins with fewer rows, offer key 0.  (The loop
+    // above keeps its per-lane trip counts: the kernels of a counts and a scores call are what they were.)
+    const uint32_t first = blockIdx.x * COUNTS_BLOCK + threadIdx.x, stride = gridDim.x * COUNTS_BLOCK;
+    // (the flags word can change while this kernel runs -- BIN_FLAG_EXTENT below --, so one thread reads it for the workgroup)
+    __syncthreads();
+    if (threadIdx.x == 0) tl->most = *a.flags;
+    __syncthreads();
+    const uint32_t trips = tl->most == 0 ? (n_todo + stride - 1) / stride : 0u;   // (a bin declined: the general kernels do this range)
+    for (uint32_t t = 0; t < trips; t++) {
+      const unsigned long long it = (unsigned long long)first + (unsigned long long)t * stride;
+      const uint32_t rel = it < n_todo ? a.rows_list[it] : 0u;
+      const uint32_t n = it < n_todo ? min(a.bin_rows[rel], BIN_ROWS) : 0u;
+      uint32_t most = n;
+      for (int off = 32; off > 0; off >>= 1) most = max(most, (uint32_t)__shfl_xor((int)most, off));
+      __syncthreads();                                     // (the trip before has read tl->most)
+      if (threadIdx.x == 0) tl->most = 0;
+      __syncthreads();
+      if ((threadIdx.x & 63u) == 0) (void)__hip_atomic_fetch_max(&tl->most, most, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+      __syncthreads();
+      most = tl->most;
+      for (uint32_t k = 0; k < most; k++) {
+        unsigned long long tk = 0;
+        if (k < n) {
+          const RawAln* rp = a.raw + a.rows[(size_t)rel * BIN_ROWS + k].raw;
+          const uint32_t pam5 = a.guides[rp->guide].pam5;
+          const bool plus = pam5 ? (rp->dir == 1) : (rp->dir == 0);      // as hit_record
+          const int cell = counts_cell(rp, plus ? 0u : 1u, co.shape);
+          if (cell < 0) atomicOr(a.flags, BIN_FLAG_EXTENT);
+          else {
+            counts_add(hist, co, cell);
+            const unsigned long long s = score_hit(*sl, sa, ref, rp, hit_record(rp, a.guides, a.win_base, a.win), a.guides + rp->guide, acc);
+            if (s != SCORE_PERFECT) tk = top_key(s, rel * BIN_ROWS + k);
+          }
+        }
+        top_offer(*tl, ta.k, tk);
+      }
+    }
+    top_store(*tl, ta);
+  }
   if (SCORE) score_reduce(*sl, co, acc);
   if (!counts_flush(hist, co)) return;
   if (SCORE) score_publish(co);
+  if (TOP) {                                                // the winners: key -> bin and slot -> the alignment, its record as the rows kernel derives it
+    const uint32_t m = top_fold(*tl, ta);
+    if (threadIdx.x == 0) co.host[co.cells + SCORE_WORDS] = m;
+    if (threadIdx.x < m) {
+      const unsigned long long key = tl->key[threadIdx.x];
+      const RawAln* rp = a.raw + a.rows[top_rank(key)].raw;
+      top_record(co, threadIdx.x, key, rp, hit_record(rp, a.guides, a.win_base, a.win));
+    }
+  }
   counts_publish(co);
   if (threadIdx.x >= 64) return;                            // the post: the first wave of the last workgroup
   bin_post<true>(a, o, 0ull, 0u, (int)threadIdx.x);      // no bytes
@@ -688,14 +743,24 @@ __device__ __forceinline__ void bin_counts_body(const BinArgs& a, const CountsOu
 
 __global__ __launch_bounds__(COUNTS_BLOCK) void bin_counts_kernel(BinArgs a, CountsOut co, RowsArgs o) {
   __shared__ uint32_t hist[COUNTS_LDS_CELLS];
-  bin_counts_body<false>(a, co, ScoreArgs{}, HitsRef{}, o, hist, nullptr);
+  bin_counts_body<MODE_COUNTS>(a, co, ScoreArgs{}, TopArgs{}, HitsRef{}, o, hist, nullptr, nullptr);
 }
 
 // Score mode: the same lanes over the same bins, and each kept hit's score into the four words behind the cells (hits_dev.hpp: score_hit).
 __global__ __launch_bounds__(COUNTS_BLOCK) void bin_scores_kernel(BinArgs a, CountsOut co, ScoreArgs sa, HitsRef ref, RowsArgs o) {
   __shared__ uint32_t hist[COUNTS_LDS_CELLS];
   __shared__ ScoreLds sl;
-  bin_counts_body<true>(a, co, sa, ref, o, hist, &sl);
+  bin_counts_body<MODE_SCORES>(a, co, sa, TopArgs{}, ref, o, hist, &sl, nullptr);
+}
+
+// Top mode: score mode, and the k best imperfect hits' records behind the score words (hits_dev.hpp: the top list).  The rank of a hit
+// is rel * BIN_ROWS + slot: the rows kernel writes the bins' texts in ascending rel (a bin's text starts where the bins before it
+// end) and a bin's rows in ascending slot, so that number grows with the row's place in the text.
+__global__ __launch_bounds__(COUNTS_BLOCK) void bin_top_kernel(BinArgs a, CountsOut co, ScoreArgs sa, TopArgs ta, HitsRef ref, RowsArgs o) {
+  __shared__ uint32_t hist[COUNTS_LDS_CELLS];
+  __shared__ ScoreLds sl;
+  __shared__ TopLds tl;
+  bin_counts_body<MODE_TOP>(a, co, sa, ta, ref, o, hist, &sl, &tl);
 }
 
 }  // namespace
@@ -910,7 +975,12 @@ hipError_t binned_counts(const BinnedCall& c, hipEvent_t ev_done, const CountsSh
   ScoreArgs sa{};
   if (score) TRY(score_model(**c.hits, *score, c.stream, &sa));
   TRY(post_args(c, ro));
-  if (score) hipExtLaunchKernelGGL(bin_scores_kernel, dim3(counts_grid(c.geo.n_bins)), dim3(COUNTS_BLOCK), 0, c.stream, nullptr, ev_done, 0, ba, co, sa, c.ref, ro);
+  if (score && score->top_k) {
+    if ((uint64_t)c.geo.n_bins * BIN_ROWS > TOP_RANK_MAX) return hipErrorInvalidValue;      // (binned_possible keeps such a call off the bins)
+    TopArgs ta{};
+    TRY(top_buffers(**c.hits, score->top_k, &ta));
+    hipExtLaunchKernelGGL(bin_top_kernel, dim3(counts_grid(c.geo.n_bins)), dim3(COUNTS_BLOCK), 0, c.stream, nullptr, ev_done, 0, ba, co, sa, ta, c.ref, ro);
+  } else if (score) hipExtLaunchKernelGGL(bin_scores_kernel, dim3(counts_grid(c.geo.n_bins)), dim3(COUNTS_BLOCK), 0, c.stream, nullptr, ev_done, 0, ba, co, sa, c.ref, ro);
   else hipExtLaunchKernelGGL(bin_counts_kernel, dim3(counts_grid(c.geo.n_bins)), dim3(COUNTS_BLOCK), 0, c.stream, nullptr, ev_done, 0, ba, co, ro);
   return hipGetLastError();
 }

@@ -20,6 +20,7 @@ static void usage() {
     "         [-b genome-gap-net-cost=-122] [-B guide-gap-net-cost=-121] [-c chrom] [-t threads (ignored)]\n"
     "         [-v variants.vcf[.gz]] [-V max-variants=16]\n"
     "         [--counts (the table guide_id strand guide_mm guide_gaps pam_mm hits instead of hits.txt)]\n"
+    "         [--top K (with --scores: the K highest-scoring imperfect hits behind the scores and an empty line)]\n"
     "         [--scores model.tsv (guide_id rows perfect offtarget_sum_q32 max_q32 specificity instead of hits.txt; with --counts the\n"
     "          table follows behind an empty line)]\n"
     "         [--device N]\n"
@@ -225,6 +226,7 @@ int main(int argc, char** argv) {
   p.guide_gap_net_cost = -121; p.chrom_index = -1; p.eqx_by_score = 0; p.max_variants = 16;
   int device = 0;
   bool counts = false;
+  int top_k = -1;              // --top K: with --scores, the K highest-scoring imperfect hits behind the scores
   for (int i = 2; i < argc; i++) {
     std::string a = argv[i], val;
     size_t eq = a.find('=');
@@ -256,12 +258,15 @@ int main(int argc, char** argv) {
     else if (a == "--device") device = std::atoi(next().c_str());
     else if (a == "--counts") counts = true;
     else if (a == "--scores") scores = next();
+    else if (a == "--top") top_k = std::atoi(next().c_str());
     else if (a == "-v") variants = next();
     else { std::fprintf(stderr, "unknown argument %s\n", a.c_str()); usage(); return 2; }
   }
   if (guide.empty() || guide_id.empty() || ref.empty()) { usage(); return 2; }
   if (counts && !variants.empty()) { std::fprintf(stderr, "--counts covers the reference-genome branch only (no --variants)\n"); return 2; }
   if (!scores.empty() && !variants.empty()) { std::fprintf(stderr, "--scores covers the reference-genome branch only (no --variants)\n"); return 2; }
+  if (top_k != -1 && scores.empty()) { std::fprintf(stderr, "--top K requires --scores MODEL\n"); return 2; }
+  if (top_k != -1 && (top_k < 1 || top_k > CALITAS_TOP_MAX)) { std::fprintf(stderr, "--top K: K is 1 .. %d\n", CALITAS_TOP_MAX); return 2; }
   ScoreModelFile model;
   if (!scores.empty()) {
     std::string err;
@@ -302,14 +307,28 @@ int main(int argc, char** argv) {
   if (!scores.empty()) {      // the specificity score instead of hits.txt; with --counts the same pass's table behind an empty line
     const calitas_score_model_t cm{model.L, model.gap, model.pam, model.mm.data()};
     calitas_scores_t* sc = nullptr;
-    if (calitas_search_scores(ctx, &g, &p, &cm, &sc) != CALITAS_OK) die("search");
+    calitas_top_t* tp = nullptr;                            // --top K: the same pass with the list; its scores are the scores
+    if (top_k > 0) {
+      if (calitas_search_top(ctx, &g, &p, &cm, (uint32_t)top_k, &tp) != CALITAS_OK) die("search");
+      sc = &tp->scores;
+    } else if (calitas_search_scores(ctx, &g, &p, &cm, &sc) != CALITAS_OK) die("search");
     const double two32 = 4294967296.0;
     std::fprintf(f, "guide_id\trows\tperfect\tofftarget_sum_q32\tmax_q32\tspecificity\n%s\t%llu\t%llu\t%llu\t%llu\t%.6f\n", guide_id.c_str(),
                  (unsigned long long)sc->rows, (unsigned long long)sc->perfect, (unsigned long long)sc->sum_q32, (unsigned long long)sc->max_q32,
                  two32 / (two32 + (double)sc->sum_q32));
+    if (tp) {
+      std::fprintf(f, "\nguide_id\trank\tchromosome\tcoordinate_start\tcoordinate_end\tstrand\tguide_mm\tguide_gaps\tpam_mm\tscore_q32\tscore\n");
+      for (uint32_t i = 0; i < tp->n; i++) {
+        const calitas_top_hit_t& h = tp->hits[i];
+        const char* nm = ""; uint64_t len = 0;
+        calitas_contig_name(ctx, h.contig_index, &nm, &len);
+        std::fprintf(f, "%s\t%u\t%s\t%d\t%d\t%c\t%u\t%u\t%u\t%llu\t%.6f\n", guide_id.c_str(), i + 1, nm, h.coordinate_start, h.coordinate_end, (char)h.strand,
+                     (unsigned)h.guide_mm, (unsigned)h.guide_gaps, (unsigned)h.pam_mm, (unsigned long long)h.score_q32, (double)h.score_q32 / two32);
+      }
+    }
     if (counts) { std::fprintf(f, "\n"); write_counts(&sc->table); }
     rows = sc->rows;
-    calitas_free(sc);
+    calitas_free(tp ? (void*)tp : (void*)sc);
   } else if (counts) {        // the off-target table instead of hits.txt
     calitas_counts_t* t = nullptr;
     if (calitas_search_counts(ctx, &g, &p, &t) != CALITAS_OK) die("search");

@@ -330,30 +330,61 @@ void counts_from_box(const Mailbox& box, uint64_t* counts) {
 // Counts mode: behind the walks, instead of len_kernel / rows_kernel.  One lane per sorted position k: keep[k] and order[k] lead to the
 // alignment fin[order[k]] and its record; a kept hit the call owns (HitsOwn, as len_kernel applies it) adds one to its cell of the
 // workgroup's histogram (hits_dev.hpp: counts_cell, CountsOut).  The workgroup that finishes last brings the table to the host and
-// posts what total_kernel posts for a text: no bytes, the rows it counted, the flags.  The body is a template over SCORE: counts_kernel is
-// it without the score (the kernel a counts call launches, unchanged), scores_kernel with it.
-template <bool SCORE>
-__device__ __forceinline__ void counts_body(const MidArgs& a, const CountsOut& o, const ScoreArgs& sa, uint32_t* hist, ScoreLds* sl, uint64_t* counts,
-                                            uint32_t* flags, uint32_t* box, uint32_t seq) {
+// posts what total_kernel posts for a text: no bytes, the rows it counted, the flags.  The body is a template over a mode: counts_kernel is
+// it without the score (the kernel a counts call launches, unchanged), scores_kernel with it, top_kernel with the score and the list.
+template <int MODE>
+__device__ __forceinline__ void counts_body(const MidArgs& a, const CountsOut& o, const ScoreArgs& sa, const TopArgs& ta, uint32_t* hist, ScoreLds* sl,
+                                            TopLds* tl, uint64_t* counts, uint32_t* flags, uint32_t* box, uint32_t seq) {
+  constexpr bool SCORE = MODE != MODE_COUNTS, TOP = MODE == MODE_TOP;
   CALITAS_TAIL_PRIO();
   __shared__ uint32_t s_rows;
   if (threadIdx.x == 0) s_rows = 0;
   if (SCORE) score_begin(*sl, sa);
+  if (TOP) top_begin(*tl);
   counts_begin(hist, o);
   uint32_t mine = 0;
   ScoreAcc acc;
-  for (uint32_t k = blockIdx.x * COUNTS_BLOCK + threadIdx.x; k < a.n; k += gridDim.x * COUNTS_BLOCK) {
-    if (!a.keep[k]) continue;
-    const uint32_t v = a.order[k];
-    if (v >= a.n_dev) continue;                             // (a hit of the caller's own: not in a counts call)
-    const HitRec h = a.hits[v];
-    const unsigned long long key = own_key((uint32_t)h.contig, h.gstart);
-    if (key < a.own_lo || key >= a.own_hi) continue;
-    const int cell = counts_cell(a.fin + v, h.minus, o.shape);
-    if (cell < 0) { atomicOr(flags, HITS_FLAG_EXTENT); continue; }
-    counts_add(hist, o, cell);
-    if (SCORE) score_hit(*sl, sa, a.ref, a.fin + v, h, a.guides + a.fin[v].guide, acc);
-    mine++;
+  if (!TOP) {
+    for (uint32_t k = blockIdx.x * COUNTS_BLOCK + threadIdx.x; k < a.n; k += gridDim.x * COUNTS_BLOCK) {
+      if (!a.keep[k]) continue;
+      const uint32_t v = a.order[k];
+      if (v >= a.n_dev) continue;                             // (a hit of the caller's own: not in a counts call)
+      const HitRec h = a.hits[v];
+      const unsigned long long key = own_key((uint32_t)h.contig, h.gstart);
+      if (key < a.own_lo || key >= a.own_hi) continue;
+      const int cell = counts_cell(a.fin + v, h.minus, o.shape);
+      if (cell < 0) { atomicOr(flags, HITS_FLAG_EXTENT); continue; }
+      counts_add(hist, o, cell);
+      if (SCORE) score_hit(*sl, sa, a.ref, a.fin + v, h, a.guides + a.fin[v].guide, acc);
+      mine++;
+    }
+  } else {
+    // The same stride with a trip count every lane of the grid shares: top_offer is a workgroup barrier, so no lane leaves the loop
+    // early or skips a trip -- a lane past the end, or whose position has no hit to list, offers key 0.  (The loop above keeps its
+    // per-lane `continue`s: the kernels of a counts and a scores call are what they were.)
+    const uint32_t first = blockIdx.x * COUNTS_BLOCK + threadIdx.x, stride = gridDim.x * COUNTS_BLOCK;
+    const uint32_t trips = (a.n + stride - 1) / stride;     // (a.n <= TOP_RANK_MAX: no overflow)
+    for (uint32_t it = 0; it < trips; it++) {
+      const unsigned long long k = (unsigned long long)first + (unsigned long long)it * stride;
+      unsigned long long tk = 0;
+      uint32_t v = 0;
+      bool live = k < a.n && a.keep[k] != 0;
+      if (live) { v = a.order[k]; live = v < a.n_dev; }
+      if (live) {
+        const HitRec h = a.hits[v];
+        const unsigned long long key = own_key((uint32_t)h.contig, h.gstart);
+        const int cell = key >= a.own_lo && key < a.own_hi ? counts_cell(a.fin + v, h.minus, o.shape) : -2;
+        if (cell == -1) atomicOr(flags, HITS_FLAG_EXTENT);
+        if (cell >= 0) {
+          counts_add(hist, o, cell);
+          const unsigned long long s = score_hit(*sl, sa, a.ref, a.fin + v, h, a.guides + a.fin[v].guide, acc);
+          mine++;
+          if (s != SCORE_PERFECT) tk = top_key(s, (uint32_t)k);
+        }
+      }
+      top_offer(*tl, ta.k, tk);
+    }
+    top_store(*tl, ta);
   }
   // rows of the call: one LDS add per lane that counted, one global add per workgroup
   if (mine) (void)__hip_atomic_fetch_add(&s_rows, mine, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -362,13 +393,22 @@ __device__ __forceinline__ void counts_body(const MidArgs& a, const CountsOut& o
   if (SCORE) score_reduce(*sl, o, acc);
   if (!counts_flush(hist, o)) return;
   if (SCORE) score_publish(o);
+  if (TOP) {                                                // the winners: key -> sorted position -> the hit and its alignment
+    const uint32_t m = top_fold(*tl, ta);
+    if (threadIdx.x == 0) o.host[o.cells + SCORE_WORDS] = m;
+    if (threadIdx.x < m) {
+      const unsigned long long key = tl->key[threadIdx.x];
+      const uint32_t v = a.order[top_rank(key)];
+      top_record(o, threadIdx.x, key, a.fin + v, a.hits[v]);
+    }
+  }
   counts_publish(o);
   if (threadIdx.x == 0) post_counts(box, counts, seq);    // [0] bytes: none, [1] rows, [2] flags
 }
 
 __global__ __launch_bounds__(COUNTS_BLOCK) void counts_kernel(MidArgs a, CountsOut o, uint64_t* counts, uint32_t* flags, uint32_t* box, uint32_t seq) {
   __shared__ uint32_t hist[COUNTS_LDS_CELLS];
-  counts_body<false>(a, o, ScoreArgs{}, hist, nullptr, counts, flags, box, seq);
+  counts_body<MODE_COUNTS>(a, o, ScoreArgs{}, TopArgs{}, hist, nullptr, nullptr, counts, flags, box, seq);
 }
 
 // Score mode: the same lanes, the same cells, and each kept hit's score into the four words behind them (hits_dev.hpp: score_hit).
@@ -376,7 +416,17 @@ __global__ __launch_bounds__(COUNTS_BLOCK) void scores_kernel(MidArgs a, CountsO
                                                               uint32_t seq) {
   __shared__ uint32_t hist[COUNTS_LDS_CELLS];
   __shared__ ScoreLds sl;
-  counts_body<true>(a, o, sa, hist, &sl, counts, flags, box, seq);
+  counts_body<MODE_SCORES>(a, o, sa, TopArgs{}, hist, &sl, nullptr, counts, flags, box, seq);
+}
+
+// Top mode: score mode, and the k best imperfect hits' records behind the score words (hits_dev.hpp: the top list).  The rank of a hit
+// is its sorted position k: the rows of the text are the kept positions in ascending k.
+__global__ __launch_bounds__(COUNTS_BLOCK) void top_kernel(MidArgs a, CountsOut o, ScoreArgs sa, TopArgs ta, uint64_t* counts, uint32_t* flags, uint32_t* box,
+                                                           uint32_t seq) {
+  __shared__ uint32_t hist[COUNTS_LDS_CELLS];
+  __shared__ ScoreLds sl;
+  __shared__ TopLds tl;
+  counts_body<MODE_TOP>(a, o, sa, ta, hist, &sl, &tl, counts, flags, box, seq);
 }
 
 // Length of the text = end of the last row; posted with the other two counts (rows, flags) by the same thread (post_counts).
@@ -425,7 +475,7 @@ void hits_destroy(HitsWork* w) {
   if (w->h_ext_keep) (void)hipHostFree(w->h_ext_keep);
   if (w->h_ext_place) (void)hipHostFree(w->h_ext_place);
   if (w->h_counts) (void)hipHostFree(w->h_counts);
-  (void)hipFree(w->cnt_table); (void)hipFree(w->score_dev);
+  (void)hipFree(w->cnt_table); (void)hipFree(w->score_dev); (void)hipFree(w->top_lists); (void)hipFree(w->top_n);
   if (w->cnt_host) (void)hipHostFree(w->cnt_host);
   mailbox_close(w->mbox);
   delete w;
@@ -610,6 +660,11 @@ struct HitsRun {
       TRY(score_model(w, *c.score, c.stream, &sa));
       MidArgs ma = mid_args();
       ma.ref = c.ref;
+      if (c.score->top_k) {
+        TopArgs ta{};
+        TRY(top_buffers(w, c.score->top_k, &ta));
+        hipLaunchKernelGGL(top_kernel, dim3(counts_grid(n)), dim3(COUNTS_BLOCK), 0, c.stream, ma, co, sa, ta, w.d_counts, d_flags, w.mbox.dev, w.mbox.seq);
+      } else
       hipLaunchKernelGGL(scores_kernel, dim3(counts_grid(n)), dim3(COUNTS_BLOCK), 0, c.stream, ma, co, sa, w.d_counts, d_flags, w.mbox.dev, w.mbox.seq);
     } else {
       hipLaunchKernelGGL(counts_kernel, dim3(counts_grid(n)), dim3(COUNTS_BLOCK), 0, c.stream, mid_args(), co, w.d_counts, d_flags, w.mbox.dev, w.mbox.seq);
@@ -702,10 +757,11 @@ hipError_t hits_run(HitsWork** pw, const HitsRunCall& c, HitsResult* res) {
   if (c.ext && c.ext->kept) *c.ext->kept = 0;
   if ((uint64_t)c.n + n_ext > 0xFFFFFFF0ull) { res->flags = HITS_FLAG_CLUSTER; return hipSuccess; }
   const size_t n = (size_t)c.n + n_ext;
+  if (c.score && c.score->top_k && n > TOP_RANK_MAX) { res->flags = HITS_FLAG_CLUSTER; return hipSuccess; }   // (more ranks than a key holds: the host stage)
   CountsOut co{};
   if (c.counts) {
     TRY(counts_buffers(w, *c.counts, &co));
-    if (n == 0) std::memset(co.host, 0, ((size_t)co.cells + SCORE_WORDS) * sizeof(unsigned long long));
+    if (n == 0) std::memset(co.host, 0, ((size_t)co.cells + SCORE_WORDS + 1) * sizeof(unsigned long long));   // (+ 1: a top call's number of records)
     res->counts = reinterpret_cast<const uint64_t*>(co.host);
   }
   if (n == 0) return hipSuccess;

@@ -5,6 +5,7 @@
 #include <hip/hip_runtime_api.h>
 #include <hip/hip_vector_types.h>
 
+#include <cstring>
 #include <functional>
 #include <string>
 #include <vector>
@@ -40,12 +41,26 @@ constexpr uint32_t SCORE_WORDS = 4;                 // behind a table's cells: s
 struct ScoreCall {
   const uint32_t* model;                            // host memory, SCORE_MODEL_WORDS words, valid during the call
   uint64_t letters[2];                              // positions 0-15 / 16-31
+  uint32_t top_k = 0;                               // calitas_search_top: top_kernel / bin_top_kernel in the scores kernels' place
 };
 // What a guide's kept hits add up to besides the table; across window ranges, contigs and lanes sum and perfect add, max takes the maximum.
+// top: the list of a top call (post.hpp, TopList) -- `o` is the piece that follows this one in the text, so add() is called in that order.
 struct ScoreWords {
   uint64_t sum_q32 = 0, perfect = 0, max_q32 = 0;
-  void add(const ScoreWords& o) { sum_q32 += o.sum_q32; perfect += o.perfect; if (o.max_q32 > max_q32) max_q32 = o.max_q32; }
+  TopList top;
+  void add(const ScoreWords& o) { sum_q32 += o.sum_q32; perfect += o.perfect; if (o.max_q32 > max_q32) max_q32 = o.max_q32; top.merge(o.top); }
 };
+// What a top call's kernels leave behind the SCORE_WORDS in the work's page-locked block: the number of records, then three words per
+// record in the layout of calitas_top_hit_t.
+constexpr uint32_t TOP_WORDS = 1 + 3 * CALITAS_TOP_MAX;
+inline TopList top_from_words(const uint64_t* w, uint32_t k) {
+  TopList t;
+  t.k = k;
+  const size_t n = (size_t)std::min<uint64_t>(w[0], k);
+  t.hits.resize(n);
+  if (n) std::memcpy(t.hits.data(), w + 1, n * sizeof(calitas_top_hit_t));
+  return t;
+}
 
 struct HitsResult {
   uint32_t flags;        // != 0: the device path declined (see HITS_FLAG_*); nothing else is valid

@@ -557,16 +557,17 @@ __device__ __forceinline__ uint32_t score_letter(char c) { return c == 'A' ? 0u 
 // traceback order (= aligner order reversed, what the row of a 5' PAM guide is) for a 5' PAM, where the PAM and the gap to it come first
 // among the target's bases.  An 'X' column at position i: the target letter is the one base_upper_dev gives for the forward strand,
 // complemented on the minus strand (as the row builder does) -- the packed code and the exception bit are loaded together, the runs are
-// looked at for an exception base only --, the guide letter is position i of the command line.
-__device__ __forceinline__ void score_hit(const ScoreLds& s, const ScoreArgs& sa, const HitsRef& ref, const RawAln* rp, const HitRec& h,
-                                          const GuideDev* gp, ScoreAcc& acc) {
+// looked at for an exception base only --, the guide letter is position i of the command line.  Returns the score (top mode keeps it).
+constexpr unsigned long long SCORE_PERFECT = ~0ull;   // what score_hit returns for a perfect hit (a score is at most 2^32)
+__device__ __forceinline__ unsigned long long score_hit(const ScoreLds& s, const ScoreArgs& sa, const HitsRef& ref, const RawAln* rp, const HitRec& h,
+                                                        const GuideDev* gp, ScoreAcc& acc) {
   const int ng = rp->n_ops, pam = rp->pam;
   const OpsWords ow = load_ops_words(rp->ops);
   const OpCounts oc = count_ops(ow, ng);
   const HitKey k = hit_key(oc, pam, rp->offset, rp->pam_x);
   const int gap = pam >= 0 ? rp->offset : 0;
   acc.hits++;
-  if (oc.non_eq + gap + k.pam_mm == 0) { acc.perfect++; return; }      // total_mm_plus_gaps == 0 (GA:101): counted, not scored
+  if (oc.non_eq + gap + k.pam_mm == 0) { acc.perfect++; return SCORE_PERFECT; }   // total_mm_plus_gaps == 0 (GA:101): counted, not scored
   const bool minus = h.minus != 0, pam5 = gp->pam5 != 0;
   const ContigInfo ci = ref.contigs[h.contig];
   unsigned long long v = 1ull << 32;
@@ -592,6 +593,7 @@ __device__ __forceinline__ void score_hit(const ScoreLds& s, const ScoreArgs& sa
   for (int r = 0; r < k.guide_gaps; r++) v = (v * s.model[MAX_L * 25]) >> 16;
   for (int r = 0; r < k.pam_mm; r++) v = (v * s.model[MAX_L * 25 + 1]) >> 16;
   acc.sum += v; acc.max = max(acc.max, v);
+  return v;
 }
 
 // The lanes' sums into the workgroup's, the workgroup's into the words behind the table's cells.  Every thread of the workgroup calls it.
@@ -626,6 +628,119 @@ __device__ __forceinline__ void score_publish(const CountsOut& o) {
   }
 }
 
+// ---- the top list (calitas_search_top) --------------------------------------------------------------------------------------------
+// Top mode is score mode plus an exact selection of the k best imperfect hits: top_kernel and bin_top_kernel are the
+// counts kernels' bodies in a third mode.  A hit is one comparable word, key = score << 31 | (0x7FFFFFFF - rank), where rank is the
+// hit's place in the text order of the call (below TOP_RANK_MAX, so no key is 0 and no two are equal; larger is better): the k largest
+// keys ARE the list, whatever order they are met in.  A workgroup keeps TOP_CAP keys and a threshold in LDS; a lane appends a key above
+// the threshold through an LDS counter; before a trip that could overflow the buffer the workgroup sorts it (bitonic), keeps the best
+// k and raises the threshold to the k-th.  At its end a workgroup stores its at most k keys and their number into its slot of the
+// work's lists, ahead of counts_flush, whose ticket then covers them; the workgroup that finishes last runs all slots through the same
+// buffer and writes the winners' records behind the score words in the work's page-locked block.  Every workgroup stores its number
+// in every call and the last one reads the slots of this grid only, so the slots need no clearing between calls.
+constexpr uint32_t TOP_CAP = 2 * CALITAS_TOP_MAX;
+constexpr uint32_t TOP_LISTS = 128;                      // the most workgroups counts_grid gives
+constexpr uint32_t TOP_RANK_MAX = 0x7FFFFFFEu;           // ranks are 0 .. TOP_RANK_MAX: a call with more declines
+static_assert(TOP_CAP == 2 * COUNTS_BLOCK && CALITAS_TOP_MAX <= COUNTS_BLOCK, "a thread per pair of the sort; a trip appends at most COUNTS_BLOCK keys");
+
+// The three modes of the counts kernels' bodies (counts_body in hits.hip, bin_counts_body in binned.hip).
+constexpr int MODE_COUNTS = 0, MODE_SCORES = 1, MODE_TOP = 2;
+
+struct TopArgs {
+  uint32_t k;
+  unsigned long long* lists;   // device memory, TOP_LISTS x CALITAS_TOP_MAX keys
+  uint32_t* list_n;            // TOP_LISTS numbers of keys
+};
+struct TopLds { unsigned long long key[TOP_CAP]; unsigned long long thr, floor; uint32_t n, most; uint32_t list_n[TOP_LISTS]; };   // most: bin_top_kernel, the most rows of a bin of a trip
+
+__device__ __forceinline__ unsigned long long top_key(unsigned long long score, uint32_t rank) { return (score << 31) | (0x7FFFFFFFu - rank); }
+
+__device__ __forceinline__ void top_begin(TopLds& t) {            // (counts_begin's barrier follows)
+  if (threadIdx.x == 0) { t.n = 0; t.thr = 0; }
+}
+
+// The buffer sorted, best first, and cut at k: returns what is left (t.n).  Every thread of the workgroup calls it, behind a barrier
+// that follows the last append.
+__device__ __forceinline__ uint32_t top_compact(TopLds& t, uint32_t k) {
+  const uint32_t n = t.n, tid = threadIdx.x;
+  for (uint32_t i = tid; i < TOP_CAP; i += COUNTS_BLOCK) if (i >= n) t.key[i] = 0;
+  __syncthreads();
+  for (uint32_t size = 2; size <= TOP_CAP; size <<= 1)
+    for (uint32_t stride = size >> 1; stride > 0; stride >>= 1) {
+      const uint32_t lo = ((tid & ~(stride - 1)) << 1) | (tid & (stride - 1)), hi = lo | stride;
+      const unsigned long long x = t.key[lo], y = t.key[hi];
+      if ((lo & size) == 0 ? x < y : x > y) { t.key[lo] = y; t.key[hi] = x; }
+      __syncthreads();
+    }
+  const uint32_t m = min(n, k);
+  if (tid == 0) { t.n = m; if (n > k) t.thr = t.key[k - 1]; }
+  __syncthreads();
+  return m;
+}
+
+// One trip of every thread of the workgroup (key 0: this lane has none): room for a trip's appends is made first -- the decision is
+// taken on a value read between two barriers, so it is the same in every thread --, then the keys above the threshold are appended.
+__device__ __forceinline__ void top_offer(TopLds& t, uint32_t k, unsigned long long key) {
+  __syncthreads();                                        // the appends of the trip before are in
+  const uint32_t n = t.n;
+  __syncthreads();                                        // ... and everybody has read their number
+  if (n > TOP_CAP - COUNTS_BLOCK) (void)top_compact(t, k);
+  if (key > t.thr) t.key[__hip_atomic_fetch_add(&t.n, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)] = key;
+}
+
+// The end of a workgroup's hits: its best k keys into its slot.  Every thread calls it.
+__device__ __forceinline__ void top_store(TopLds& t, const TopArgs& ta) {
+  __syncthreads();
+  const uint32_t m = top_compact(t, ta.k);
+  if (threadIdx.x < m) __hip_atomic_store(ta.lists + (size_t)blockIdx.x * CALITAS_TOP_MAX + threadIdx.x, t.key[threadIdx.x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  if (threadIdx.x == 0) __hip_atomic_store(ta.list_n + blockIdx.x, m, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// The last workgroup (counts_flush said so): the slots of the grid's workgroups through the buffer, COUNTS_BLOCK / k slots to a trip;
+// returns the number of winners, which are t.key[0 .. ), best first.  Every thread calls it.
+__device__ __forceinline__ uint32_t top_fold(TopLds& t, const TopArgs& ta) {
+  const uint32_t tid = threadIdx.x, lists = min(gridDim.x, TOP_LISTS);
+  __syncthreads();                                        // (top_store's readers of key[] are done)
+  if (tid == 0) { t.n = 0; t.thr = 0; t.floor = ~0ull; }
+  if (tid < lists) t.list_n[tid] = min(__hip_atomic_load(ta.list_n + tid, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), ta.k);
+  __syncthreads();
+  // A floor under the k-th key before any slot is read whole: with c = ceil(k / slots), the c-th key of every slot -- where every slot
+  // has one -- makes slots * c >= k keys at or above the smallest of them, so nothing below that can be among the k best: the fold of
+  // 128 slots of 256 keys then appends a few hundred keys instead of compacting on most of its 128 trips.
+  const uint32_t c = (ta.k + lists - 1) / lists;
+  if (tid < lists) {
+    const unsigned long long f = t.list_n[tid] >= c ? __hip_atomic_load(ta.lists + (size_t)tid * CALITAS_TOP_MAX + (c - 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0ull;
+    (void)__hip_atomic_fetch_min(&t.floor, f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+  }
+  __syncthreads();
+  if (tid == 0 && t.floor != 0) t.thr = t.floor - 1;      // (a key equal to the floor passes top_offer's `>`)
+  const uint32_t per = COUNTS_BLOCK / ta.k, sub = tid / ta.k, e = tid - sub * ta.k;
+  auto load = [&](uint32_t l0) -> unsigned long long {
+    const uint32_t l = l0 + sub;
+    if (sub >= per || l >= lists || e >= t.list_n[l]) return 0ull;
+    return __hip_atomic_load(ta.lists + (size_t)l * CALITAS_TOP_MAX + e, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  };
+  unsigned long long key = load(0);
+  for (uint32_t l0 = 0; l0 < lists; l0 += per) {
+    const unsigned long long next = l0 + per < lists ? load(l0 + per) : 0ull;   // (in flight across this trip's barriers)
+    top_offer(t, ta.k, key);
+    key = next;
+  }
+  __syncthreads();
+  return top_compact(t, ta.k);
+}
+
+// A winner's record into the work's page-locked block, behind the score words: three words in the layout of calitas_top_hit_t.
+__device__ __forceinline__ void top_record(const CountsOut& o, uint32_t i, unsigned long long key, const RawAln* rp, const HitRec& h) {
+  const HitKey hk = hit_key(count_ops(load_ops_words(rp->ops), rp->n_ops), rp->pam, rp->offset, rp->pam_x);
+  unsigned long long* w = o.host + o.cells + SCORE_WORDS + 1 + 3 * (size_t)i;
+  w[0] = key >> 31;
+  w[1] = (unsigned long long)(uint32_t)h.contig | ((unsigned long long)(uint32_t)h.gstart << 32);
+  w[2] = (unsigned long long)(uint32_t)h.gend | ((unsigned long long)(h.minus ? '-' : '+') << 32) | ((unsigned long long)(hk.guide_mm & 255) << 40) |
+         ((unsigned long long)(hk.guide_gaps & 255) << 48) | ((unsigned long long)(hk.pam_mm & 255) << 56);
+}
+__device__ __forceinline__ uint32_t top_rank(unsigned long long key) { return 0x7FFFFFFFu - (uint32_t)(key & 0x7FFFFFFFull); }
+
 // Workgroups of a counts kernel over `items` items (each strides over them).
 static inline unsigned counts_grid(size_t items) { return (unsigned)std::min<size_t>(std::max<size_t>((items + COUNTS_BLOCK - 1) / COUNTS_BLOCK, 1), 128); }
 
@@ -656,6 +771,8 @@ struct HitsWork {
   unsigned long long* cnt_host = nullptr; size_t cnt_host_cap = 0;
   // score mode: this context's device copy of the model, brought up again only when its bytes change (score_model)
   uint32_t* score_dev = nullptr; std::vector<uint32_t> score_host;
+  // top mode (TopArgs): the workgroups' slots and their numbers of keys
+  unsigned long long* top_lists = nullptr; uint32_t* top_n = nullptr;
   Mailbox mbox;                   // carries d_counts to the host (mailbox.hpp)
   RowConstDev rc{};               // set by hits_prepare
   size_t blob_bytes = 0;
@@ -664,7 +781,7 @@ struct HitsWork {
 };
 
 // The buffers of a call's table in the work (zero on the device: the kernels leave them so), with room for a score call's SCORE_WORDS
-// behind the cells.
+// behind the cells -- and in the page-locked copy for a top call's TOP_WORDS behind those.
 inline hipError_t counts_buffers(HitsWork& w, const CountsShape& shape, CountsOut* out) {
   const size_t cells = (size_t)shape.cells() + SCORE_WORDS;
   if (cells == SCORE_WORDS) return hipErrorInvalidValue;
@@ -681,12 +798,21 @@ inline hipError_t counts_buffers(HitsWork& w, const CountsShape& shape, CountsOu
   if (cells > w.cnt_host_cap) {
     if (w.cnt_host) (void)hipHostFree(w.cnt_host);
     w.cnt_host = nullptr; w.cnt_host_cap = 0;
-    hipError_t e = hipHostMalloc((void**)&w.cnt_host, cells * sizeof(unsigned long long), hipHostMallocDefault);
+    hipError_t e = hipHostMalloc((void**)&w.cnt_host, (cells + TOP_WORDS) * sizeof(unsigned long long), hipHostMallocDefault);
     if (e != hipSuccess) return e;
     w.cnt_host_cap = cells;
   }
   out->shape = shape; out->cells = shape.cells(); out->table = w.cnt_table; out->tickets = reinterpret_cast<uint32_t*>(w.cnt_table + w.cnt_cap - 1);
   out->host = w.cnt_host;
+  return hipSuccess;
+}
+
+// The slots of a top call in the work.
+inline hipError_t top_buffers(HitsWork& w, uint32_t k, TopArgs* out) {
+  hipError_t e;
+  if (!w.top_lists && (e = hipMalloc((void**)&w.top_lists, (size_t)TOP_LISTS * CALITAS_TOP_MAX * sizeof(unsigned long long))) != hipSuccess) return e;
+  if (!w.top_n && (e = hipMalloc((void**)&w.top_n, TOP_LISTS * sizeof(uint32_t))) != hipSuccess) return e;
+  out->k = k; out->lists = w.top_lists; out->list_n = w.top_n;
   return hipSuccess;
 }
 

@@ -789,7 +789,7 @@ bool score_columns(const ScoreModelHost& m, const char* pg, const char* pa, cons
 // What hits_counts and hits_scores share: the kept hits, each one's padded columns (the target's only for a score) and its cell.
 static std::string count_kept(const PackedRef& ref, const GuideHost& g, const calitas_params_t& p, const ScoreModelHost* model, const calitas_aln_t* alns,
                               uint64_t n, uint32_t n_mm, uint32_t n_gaps, uint32_t n_pam, uint64_t* table, uint64_t* n_rows, uint64_t* perfect,
-                              uint64_t* sum_q32, uint64_t* max_q32, WorkerPool* pool) {
+                              uint64_t* sum_q32, uint64_t* max_q32, WorkerPool* pool, TopList* top = nullptr) {
   WorkerPool serial(1);
   if (!pool) pool = &serial;
   const std::vector<Lite> keepers = kept_hits(ref, p, alns, n, pool, nullptr, 0);
@@ -829,6 +829,8 @@ static std::string count_kept(const PackedRef& ref, const GuideHost& g, const ca
     if (!score_columns(*model, pg, pa, pt, len, ggp, pmm, &v)) return "an alignment has more protospacer columns than the score model has positions";
     *sum_q32 += v;
     if (v > *max_q32) *max_q32 = v;
+    if (top)                                               // (the keepers come in the text's order: push keeps it among equal scores)
+      top->push(calitas_top_hit_t{v, a.contig_index, a.guide_start_offset, a.guide_end_offset, (int8_t)a.strand, (uint8_t)gmm, (uint8_t)ggp, (uint8_t)pmm});
   }
   if (n_rows) *n_rows = keepers.size();
   return "";
@@ -844,6 +846,14 @@ std::string hits_scores(const PackedRef& ref, const GuideHost& g, const calitas_
                         uint64_t* sum_q32, uint64_t* max_q32, WorkerPool* pool) {
   *perfect = 0; *sum_q32 = 0; *max_q32 = 0;
   return count_kept(ref, g, p, &model, alns, n, n_mm, n_gaps, n_pam, table, n_rows, perfect, sum_q32, max_q32, pool);
+}
+
+std::string hits_top(const PackedRef& ref, const GuideHost& g, const calitas_params_t& p, const ScoreModelHost& model, const calitas_aln_t* alns,
+                     uint64_t n, uint32_t n_mm, uint32_t n_gaps, uint32_t n_pam, uint64_t* table, uint64_t* n_rows, uint64_t* perfect,
+                     uint64_t* sum_q32, uint64_t* max_q32, TopList* top, WorkerPool* pool) {
+  *perfect = 0; *sum_q32 = 0; *max_q32 = 0;
+  top->hits.clear();
+  return count_kept(ref, g, p, &model, alns, n, n_mm, n_gaps, n_pam, table, n_rows, perfect, sum_q32, max_q32, pool, top);
 }
 
 }  // namespace calitas

@@ -1,6 +1,8 @@
 // post.hpp -- host-side stages above the kernels: raw alignment -> GuideAlignment record, the per-window filter,
 // removeOverlaps / sort / hits.txt rows.
 #pragma once
+#include <algorithm>
+#include <cstddef>
 #include <memory>
 #include <string>
 #include <vector>
@@ -93,6 +95,7 @@ std::string hits_counts(const PackedRef& ref, const GuideHost& g, const calitas_
 struct ScoreModelHost {
   int L = 0;
   std::vector<uint32_t> words;
+  uint32_t top_k = 0;                 // calitas_search_top: the k of the list the call keeps besides the sums (0: a scores call)
   uint32_t mismatch(int i, int g, int t) const { return words[(size_t)i * 25 + (size_t)g * 5 + (size_t)t]; }
   uint32_t gap() const { return words[32 * 25]; }
   uint32_t pam_mismatch() const { return words[32 * 25 + 1]; }
@@ -106,10 +109,42 @@ inline uint32_t score_letter_index(char c) { return c == 'A' ? 0u : c == 'C' ? 1
 // letters than the model has positions.
 bool score_columns(const ScoreModelHost& m, const char* pg, const char* pa, const char* pt, int len, int guide_gaps, int pam_mm, uint64_t* score);
 
+// The k highest-scoring imperfect hits of a piece of a job (calitas_hip.h, calitas_top_t: score descending, the text's order among
+// equal scores), best first.  merge: the piece that follows this one in the text -- a stable merge by score, this piece's records
+// first among equals, cut at k; that is the top of the two pieces' concatenated text.
+struct TopList {
+  uint32_t k = 0;
+  std::vector<calitas_top_hit_t> hits;
+  void merge(const TopList& later) {
+    if (later.k > k) k = later.k;
+    if (later.hits.empty() && hits.size() <= k) return;      // (nothing to merge in: the text fallback adds plain score words per row)
+    std::vector<calitas_top_hit_t> out;
+    out.reserve(std::min<size_t>(k, hits.size() + later.hits.size()));
+    size_t i = 0, j = 0;
+    while (out.size() < k && (i < hits.size() || j < later.hits.size())) {
+      if (j == later.hits.size() || (i < hits.size() && hits[i].score_q32 >= later.hits[j].score_q32)) out.push_back(hits[i++]);
+      else out.push_back(later.hits[j++]);
+    }
+    hits.swap(out);
+  }
+  // one more hit behind those seen so far (the host stages walk the kept hits in the text's order)
+  void push(const calitas_top_hit_t& h) {
+    if (hits.size() == k && (k == 0 || hits.back().score_q32 >= h.score_q32)) return;
+    size_t at = hits.size();
+    while (at > 0 && hits[at - 1].score_q32 < h.score_q32) at--;
+    hits.insert(hits.begin() + (std::ptrdiff_t)at, h);
+    if (hits.size() > k) hits.pop_back();
+  }
+};
+
 // hits_counts plus the score: the kept hits counted into table[] as there, and those with an edit scored from their ops (guide
 // orientation) and the packed reference's bases; a kept hit without one is counted in *perfect.
 std::string hits_scores(const PackedRef& ref, const GuideHost& g, const calitas_params_t& p, const ScoreModelHost& model, const calitas_aln_t* alns,
                         uint64_t n, uint32_t n_mm, uint32_t n_gaps, uint32_t n_pam, uint64_t* table, uint64_t* n_rows, uint64_t* perfect,
                         uint64_t* sum_q32, uint64_t* max_q32, WorkerPool* pool = nullptr);
+// hits_scores plus the list: top->k is what the caller asks for, top->hits receives the records.
+std::string hits_top(const PackedRef& ref, const GuideHost& g, const calitas_params_t& p, const ScoreModelHost& model, const calitas_aln_t* alns,
+                     uint64_t n, uint32_t n_mm, uint32_t n_gaps, uint32_t n_pam, uint64_t* table, uint64_t* n_rows, uint64_t* perfect,
+                     uint64_t* sum_q32, uint64_t* max_q32, TopList* top, WorkerPool* pool = nullptr);
 
 }  // namespace calitas

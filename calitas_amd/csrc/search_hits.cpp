@@ -149,15 +149,18 @@ static int search_hits_owned(calitas_ctx* ctx, const HitsCall& call, HitsOut& ou
   // score mode: the row's score besides, from its columns total_mm_plus_gaps (20), padded_guide (21), padded_alignment (22) and
   // padded_target (23) -- the contract as written (calitas_hip.h)
   std::vector<uint64_t> table(call.counts ? pl.cshape.cells() : 0, 0);
+  // top mode: the row's record besides, from coordinate_start (4), coordinate_end (5) and the columns above; the rows pass in the text's order
   ScoreWords score;
-  auto count_row = [&](const char* q, const char* row_end) -> bool {
+  score.top.k = call.model ? call.model->top_k : 0;
+  auto count_row = [&](const char* q, const char* row_end, int32_t contig) -> bool {
     const char* f = q;
     uint32_t minus = 0;
-    long v[4] = {0, 0, 0, 0};
+    long v[4] = {0, 0, 0, 0}, coord[2] = {0, 0};
     const char* col[3] = {nullptr, nullptr, nullptr};
     size_t col_len[3] = {0, 0, 0};
     for (int k = 0; k < 24 && f < row_end; k++) {
       const char* tab = (const char*)std::memchr(f, '\t', (size_t)(row_end - f));
+      if (k == 4 || k == 5) coord[k - 4] = std::strtol(f, nullptr, 10);
       if (k == 6) minus = *f == '-' ? 1u : 0u;
       if (k == 16) v[0] = std::strtol(f, nullptr, 10);
       if (k == 17) v[1] = std::strtol(f, nullptr, 10);
@@ -176,6 +179,8 @@ static int search_hits_owned(calitas_ctx* ctx, const HitsCall& call, HitsOut& ou
         !score_columns(*call.model, col[0], col[1], col[2], (int)col_len[0], (int)v[1], (int)v[2], &one)) return false;
     ScoreWords w; w.sum_q32 = one; w.max_q32 = one;
     score.add(w);
+    if (score.top.k)
+      score.top.push(calitas_top_hit_t{one, contig, (int32_t)coord[0], (int32_t)coord[1], (int8_t)(minus ? '-' : '+'), (uint8_t)v[0], (uint8_t)v[1], (uint8_t)v[2]});
     return true;
   };
   for (size_t c = 0; c < ref.contigs.size(); c++) {
@@ -199,7 +204,7 @@ static int search_hits_owned(calitas_ctx* ctx, const HitsCall& call, HitsOut& ou
       const uint64_t key = ((uint64_t)c << 32) | pos;
       if (key >= own_lo && key < own_hi) {
         if (!call.counts) body.append(q, (size_t)(row_end - q));
-        else if (!count_row(q, row_end)) { calitas_free(t); return fail(ctx, CALITAS_EHIP, "a hit lies outside the extents of the counts table, or its row cannot be scored (internal error)"); }
+        else if (!count_row(q, row_end, (int32_t)c)) { calitas_free(t); return fail(ctx, CALITAS_EHIP, "a hit lies outside the extents of the counts table, or its row cannot be scored (internal error)"); }
         rows++;
       }
       q = row_end;

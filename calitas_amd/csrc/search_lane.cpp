@@ -211,6 +211,7 @@ bool binned_possible(calitas_ctx* lane, const SearchPlan& pl) {
   }
   if (!want) return false;
   if (pl.p.max_overlap < 1 || own->ref.contigs.size() >= (1u << 18) - 1) return false;
+  if (pl.model && pl.model->top_k && (uint64_t)pl.n_bins * BIN_ROWS > 0x7FFFFFFEull) return false;   // (a top call: more ranks than a key holds)
   return true;
 }
 
@@ -358,7 +359,8 @@ static int lane_rows_binned(calitas_ctx* lane, const SearchPlan& pl, bool prelau
     if (sum != lane->mbox.host[BIN_BOX_ROWS]) return fail(lane, CALITAS_EHIP, "binned counts kernel: the table does not add up to the bins' kept hits (internal error)");
     if (pl.model) {                                          // ... and so did the four words behind its cells
       const uint64_t* w = table + pl.cshape.cells();
-      lt.score = ScoreWords{w[0], w[1], w[2]};
+      lt.score = ScoreWords{w[0], w[1], w[2], TopList()};
+      if (pl.model->top_k) lt.score.top = top_from_words(w + SCORE_WORDS, pl.model->top_k);
       if (w[3] != sum) return fail(lane, CALITAS_EHIP, "binned scores kernel: the hits it scored are not the hits it counted (internal error)");
     }
   }
@@ -488,7 +490,8 @@ int lane_rows(calitas_ctx* lane, const SearchPlan& pl, bool prelaunched, const R
         if (sum != res.n_rows) return fail(lane, CALITAS_EHIP, "counts kernel: the table does not add up to the kept hits (internal error)");
         if (pl.model) {
           const uint64_t* w = res.counts + pl.cshape.cells();
-          lt.score = ScoreWords{w[0], w[1], w[2]};
+          lt.score = ScoreWords{w[0], w[1], w[2], TopList()};
+          if (pl.model->top_k) lt.score.top = top_from_words(w + SCORE_WORDS, pl.model->top_k);
           if (w[3] != sum) return fail(lane, CALITAS_EHIP, "scores kernel: the hits it scored are not the hits it counted (internal error)");
         }
         lt.rows = res.n_rows;
@@ -517,8 +520,9 @@ int lane_rows(calitas_ctx* lane, const SearchPlan& pl, bool prelaunched, const R
   uint64_t rows = 0;
   if (pl.counts) {                                           // the host stage of calitas_hits_counts
     lt.counts.assign(pl.cshape.cells(), 0);
-    const std::string e = pl.model ? hits_scores(ref, gh, p, *pl.model, alns, n_alns, pl.cshape.n_mm, pl.cshape.n_gaps, pl.cshape.n_pam, lt.counts.data(), &rows,
-                                                 &lt.score.perfect, &lt.score.sum_q32, &lt.score.max_q32, own->pool)
+    lt.score.top.k = pl.model ? pl.model->top_k : 0;
+    const std::string e = pl.model ? hits_top(ref, gh, p, *pl.model, alns, n_alns, pl.cshape.n_mm, pl.cshape.n_gaps, pl.cshape.n_pam, lt.counts.data(), &rows,
+                                              &lt.score.perfect, &lt.score.sum_q32, &lt.score.max_q32, &lt.score.top, own->pool)
                                    : hits_counts(ref, gh, p, alns, n_alns, pl.cshape.n_mm, pl.cshape.n_gaps, pl.cshape.n_pam, lt.counts.data(), &rows, own->pool);
     calitas_free(alns);
     if (!e.empty()) return fail(lane, CALITAS_EHIP, e);

@@ -351,6 +351,43 @@ int calitas_search_scores(calitas_ctx* ctx, const calitas_guide_t* guide, const 
 int calitas_search_scores_batch(calitas_ctx* ctx, int32_t n_guides, const calitas_guide_t* guides, const calitas_params_t* params,
                                 const calitas_score_model_t* model, calitas_scores_t** out);
 
+/* The K highest-scoring imperfect hits of a guide, from the pass that scores them.  No reference counterpart.
+ * The candidates are the kept hits that are not perfect (total_mm_plus_gaps != 0); they are ordered by score_q32 descending, and among
+ * equal scores the hit whose row comes earlier in the hits.txt of the same call comes first.  That is a total order: the n records are
+ * the same bytes from call to call and on every path (per-bin kernels, general kernels, host stage).  For consecutive pieces of one
+ * job (window ranges, contigs, ranks in order) the top of the whole is the first k of a stable merge of the pieces' lists by score,
+ * pieces in their order -- the texts of the pieces concatenate. */
+#define CALITAS_TOP_MAX 256
+typedef struct {
+  uint64_t score_q32;          /* the row's score under the model (calitas_score_model_t contract): 1 .. 2^32, or 0 where a factor is 0 */
+  int32_t contig_index;
+  int32_t coordinate_start;    /* the integers of the row's coordinate_start / coordinate_end columns */
+  int32_t coordinate_end;
+  int8_t strand;               /* '+' or '-' */
+  uint8_t guide_mm, guide_gaps, pam_mm;   /* the row's columns of these names */
+} calitas_top_hit_t;
+#ifdef __cplusplus
+static_assert(sizeof(calitas_top_hit_t) == 24, "calitas_top_hit_t is 24 bytes");
+#else
+_Static_assert(sizeof(calitas_top_hit_t) == 24, "calitas_top_hit_t is 24 bytes");
+#endif
+typedef struct {
+  calitas_scores_t scores;     /* exactly what calitas_search_scores returns for the same arguments */
+  uint32_t k;                  /* as asked */
+  uint32_t n;                  /* records returned = min(k, scores.rows - scores.perfect) */
+  calitas_top_hit_t* hits;     /* n records, best first */
+} calitas_top_t;               /* one block: one calitas_free */
+
+/* calitas_search_scores plus the list.  CALITAS_EINVAL for k == 0, k > CALITAS_TOP_MAX and everything calitas_search_scores refuses;
+ * accepts whatever it accepts (the whole reference, chrom_index, a window range, ownership applied as there).  The selection runs in
+ * the lanes that score the hits (top_kernel / bin_top_kernel); at most k records of 24 bytes cross PCIe besides the scores.  Where a
+ * device stage declines, the host stage of calitas_hits_top finishes the call. */
+int calitas_search_top(calitas_ctx* ctx, const calitas_guide_t* guide, const calitas_params_t* params, const calitas_score_model_t* model,
+                       uint32_t k, calitas_top_t** out);
+/* ... for a batch of guides, with the rules of calitas_search_scores_batch.  No reference counterpart. */
+int calitas_search_top_batch(calitas_ctx* ctx, int32_t n_guides, const calitas_guide_t* guides, const calitas_params_t* params,
+                             const calitas_score_model_t* model, uint32_t k, calitas_top_t** out);
+
 /* SequentialGuideAligner.align on explicit (guide, target) pairs -- the per-task call of PairwiseAlignSequences
  * (PairwiseAlignSequences.scala:64 -> alignBest, SequentialGuideAligner.scala:333-345) and AlignToReference
  * (AlignToReference.scala:114-135 -> alignToRef / alignToRefBest, SequentialGuideAligner.scala:359-418).  Task t aligns
@@ -391,6 +428,11 @@ int calitas_hits_counts(const calitas_ctx* ctx, const calitas_guide_t* guide, co
  * calitas_search_scores falls back to; works on a host-only context. */
 int calitas_hits_scores(const calitas_ctx* ctx, const calitas_guide_t* guide, const calitas_params_t* params, const calitas_score_model_t* model,
                         const calitas_aln_t* alns, uint64_t n_alns, calitas_scores_t** out);
+
+/* The twin of calitas_hits_scores for the list.  No reference counterpart.  It is calitas_hits_scores plus the k highest-scoring imperfect
+ * kept hits in the order of the calitas_top_t contract -- the host stage calitas_search_top falls back to; works on a host-only context. */
+int calitas_hits_top(const calitas_ctx* ctx, const calitas_guide_t* guide, const calitas_params_t* params, const calitas_score_model_t* model,
+                     uint32_t k, const calitas_aln_t* alns, uint64_t n_alns, calitas_top_t** out);
 
 /* A hit row built by the caller -- the variant branch of SearchReference.execute (SearchReference.scala:570-630) builds its
  * ReferenceHits from variant windows on the host.  calitas_hits_tsv_ext lets such hits take part in removeOverlaps (grouped by
