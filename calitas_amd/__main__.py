@@ -45,6 +45,12 @@ def main(argv=None):
     sr.add_argument("--top", metavar="K", type=int,
                     help="with --scores: the K (1 .. 256) highest-scoring imperfect hits of the same pass behind the scores and an empty line "
                          "(guide_id rank chromosome coordinate_start coordinate_end strand guide_mm guide_gaps pam_mm score_q32 score)")
+    sr.add_argument("--regions", metavar="FILE.bed",
+                    help="with --scores: the scores split by the classes of a four-column BED file (chromosome start end class; the classes take "
+                         "priority in order of first appearance, at most 7) behind the scores and an empty line "
+                         "(guide_id class rows perfect offtarget_sum_q32 max_q32 specificity); the --top lines gain a last column class")
+    sr.add_argument("--top-classes", metavar="NAME,...",
+                    help="with --regions and --top: list only hits of these classes (elsewhere: outside every interval)")
     _costs(sr)
 
     a2r = sub.add_parser("AlignToReference")
@@ -100,13 +106,20 @@ def main(argv=None):
             top.error("--top K requires --scores MODEL")
         if a.top is not None and not 1 <= a.top <= 256:
             top.error("--top K: K is 1 .. 256")
+        if a.regions is not None and a.scores is None:
+            top.error("--regions FILE.bed requires --scores MODEL")
+        if a.regions is not None and a.variants is not None:
+            top.error("--regions covers the reference-genome branch only (no --variants)")
+        if a.top_classes is not None and (a.regions is None or a.top is None):
+            top.error("--top-classes requires --regions and --top")
         SearchReference(guide=a.guide, guide_id=a.guide_id, ref=a.ref, output=a.output, auxiliary_pams=a.auxiliary_pams,
                         window_size=a.window_size, max_guide_diffs=a.max_guide_diffs, max_pam_mismatches=a.max_pam_mismatches,
                         max_gaps_between_guide_and_pam=a.max_gaps_between_guide_and_pam, max_total_diffs=a.max_total_diffs,
                         max_overlap=a.max_overlap, guide_mismatch_net_cost=a.guide_mismatch_net_cost,
                         pam_mismatch_net_cost=a.pam_mismatch_net_cost, genome_gap_net_cost=a.genome_gap_net_cost,
                         guide_gap_net_cost=a.guide_gap_net_cost, chrom=a.chrom, variants=a.variants, max_variants=a.max_variants,
-                        device=a.device).execute(counts=a.counts, scores=ScoreModel.read(a.scores) if a.scores is not None else None, top=a.top)
+                        device=a.device).execute(counts=a.counts, scores=ScoreModel.read(a.scores) if a.scores is not None else None, top=a.top,
+                                                   regions=a.regions, top_classes=a.top_classes)
     elif a.tool == "AlignToReference":
         text = align_to_reference(a.input, a.ref, a.output, window_size=a.window_size, max_guide_diffs=a.max_guide_diffs,
                                   max_pam_mismatches=a.max_pam_mismatches, max_gaps_between_guide_and_pam=a.max_gaps_between_guide_and_pam,

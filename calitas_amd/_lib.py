@@ -86,7 +86,17 @@ class TopT(ctypes.Structure):
     _fields_ = [("scores", ScoresT), ("k", ctypes.c_uint32), ("n", ctypes.c_uint32), ("hits", ctypes.POINTER(TopHitT))]
 
 
+class RegionT(ctypes.Structure):
+    _fields_ = [("contig_index", ctypes.c_int32), ("start", ctypes.c_int32), ("end", ctypes.c_int32), ("cls", ctypes.c_uint32)]
+
+
+class RegionsT(ctypes.Structure):
+    _fields_ = [("top", TopT), ("hit_class", ctypes.POINTER(ctypes.c_uint8)), ("n_classes", ctypes.c_uint32), ("list_mask", ctypes.c_uint32),
+                ("by_class", ctypes.POINTER(ScoresT))]
+
+
 TOP_MAX = 256
+REGION_CLASSES_MAX = 8
 assert ctypes.sizeof(TopHitT) == 24
 
 # every symbol include/calitas_hip.h declares
@@ -97,6 +107,7 @@ SYMBOLS = ["calitas_create", "calitas_destroy", "calitas_last_error", "calitas_f
            "calitas_search_counts", "calitas_search_counts_batch", "calitas_hits_counts",
            "calitas_search_scores", "calitas_search_scores_batch", "calitas_hits_scores",
            "calitas_search_top", "calitas_search_top_batch", "calitas_hits_top",
+           "calitas_set_regions", "calitas_search_regions", "calitas_search_regions_batch", "calitas_hits_regions", "calitas_region_class",
            "calitas_find_sites", "calitas_count_sites", "calitas_find_sites_host"]
 
 if not os.path.exists(LIB_PATH):
@@ -173,6 +184,14 @@ lib.calitas_search_top_batch.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes
                                          ctypes.POINTER(ScoreModelT), ctypes.c_uint32, ctypes.POINTER(ctypes.POINTER(TopT))]
 lib.calitas_hits_top.argtypes = [ctypes.c_void_p, ctypes.POINTER(GuideT), ctypes.POINTER(ParamsT), ctypes.POINTER(ScoreModelT), ctypes.c_uint32,
                                  ctypes.POINTER(AlnT), ctypes.c_uint64, ctypes.POINTER(ctypes.POINTER(TopT))]
+lib.calitas_set_regions.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(RegionT), ctypes.c_uint32]
+lib.calitas_search_regions.argtypes = [ctypes.c_void_p, ctypes.POINTER(GuideT), ctypes.POINTER(ParamsT), ctypes.POINTER(ScoreModelT), ctypes.c_uint32,
+                                       ctypes.c_uint32, ctypes.POINTER(ctypes.POINTER(RegionsT))]
+lib.calitas_search_regions_batch.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.POINTER(GuideT), ctypes.POINTER(ParamsT),
+                                             ctypes.POINTER(ScoreModelT), ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(ctypes.POINTER(RegionsT))]
+lib.calitas_hits_regions.argtypes = [ctypes.c_void_p, ctypes.POINTER(GuideT), ctypes.POINTER(ParamsT), ctypes.POINTER(ScoreModelT), ctypes.c_uint32,
+                                     ctypes.c_uint32, ctypes.POINTER(AlnT), ctypes.c_uint64, ctypes.POINTER(ctypes.POINTER(RegionsT))]
+lib.calitas_region_class.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_int64]
 lib.calitas_pin_host.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64]
 lib.calitas_unpin_host.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
 lib.calitas_genome_build.restype = ctypes.c_char_p

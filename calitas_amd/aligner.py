@@ -11,7 +11,7 @@ import ctypes
 import time
 
 from . import _lib
-from ._lib import AlnT, CalitasError, CountsT, GuideT, ParamsT, ScoreModelT, ScoresT, SiteT, TimingT, TopT, lib
+from ._lib import AlnT, CalitasError, CountsT, GuideT, ParamsT, RegionsT, RegionT, ScoreModelT, ScoresT, SiteT, TimingT, TopT, lib
 
 
 class Defaults:  # SequentialGuideAligner.scala:17-28
@@ -159,6 +159,7 @@ class Context:
         self.device = device
         self.contig_names = []
         self.contig_lengths = []
+        self.regions = None                  # the Regions of the last set_regions (their class names label what the calls return)
 
     def close(self):
         if self._h:
@@ -175,6 +176,7 @@ class Context:
         n = ctypes.c_int32()
         _lib.check(self._h, lib.calitas_reference_info(self._h, ctypes.byref(n), None, None))
         self.contig_names, self.contig_lengths = [], []
+        self.regions = None                  # (a new reference drops the set)
         for i in range(n.value):
             nm, ln = ctypes.c_char_p(), ctypes.c_uint64()
             _lib.check(self._h, lib.calitas_contig_name(self._h, i, ctypes.byref(nm), ctypes.byref(ln)))
@@ -600,6 +602,75 @@ class Context:
         _lib.check(self._h, lib.calitas_hits_top(self._h, ctypes.byref(g), ctypes.byref(params), ctypes.byref(m), _top_k(k), arr, n, ctypes.byref(out)))
         return self._take_top(out)
 
+    def set_regions(self, regions):
+        """calitas_set_regions: a Regions object (None or an empty one clears the set).  The set is flattened and brought to the device
+        here, once; set_reference* and load_index drop it.  Works on a host-only context."""
+        self.regions = None
+        if regions is None or not regions.intervals:
+            _lib.check(self._h, lib.calitas_set_regions(self._h, 0, None, 0))
+            return
+        index = {nm: i for i, nm in enumerate(self.contig_names)}
+        for chrom, _, _, _ in regions.intervals:
+            if chrom not in index:
+                raise ValueError("Unknown chromosome: %s" % chrom)
+        n = len(regions.intervals)
+        arr = (RegionT * n)(*[RegionT(index[chrom], a, b, c) for chrom, a, b, c in regions.intervals])
+        _lib.check(self._h, lib.calitas_set_regions(self._h, n, arr, len(regions.classes)))
+        self.regions = regions
+
+    def region_class(self, chrom, start, end):
+        """(test hook) The class the library's flattened set gives the extent [start, end) of a chromosome."""
+        return lib.calitas_region_class(self._h, self.contig_names.index(chrom), start, end)
+
+    def _take_regions(self, ptr):
+        """A calitas_regions_t block as a RegionScores object; the block is freed."""
+        try:
+            r = ptr.contents
+            t = r.top
+            scores = self._scores_of(t.scores)
+            import numpy as np
+            names = self.contig_names
+            rec = np.frombuffer(ctypes.string_at(t.hits, 24 * t.n), dtype=TOP_DTYPE).tolist() if t.n else []
+            hits = [TopHit(s, names[c], a, b, st.decode(), mm, gp, pm) for s, c, a, b, st, mm, gp, pm in rec]
+            hit_class = list(ctypes.string_at(r.hit_class, t.n)) if t.n else []
+            by_class = [self._scores_of(r.by_class[c]) for c in range(r.n_classes)]
+            classes = list(self.regions.classes) if getattr(self, "regions", None) is not None else ["class%d" % c for c in range(r.n_classes)]
+            return RegionScores(Top(scores, int(t.k), hits), classes, by_class, hit_class)
+        finally:
+            lib.calitas_free(ptr)
+
+    def search_regions(self, guide, params, model, k, list_mask=None):
+        """calitas_search_regions: search_top split by the context's regions -- a RegionScores object.  k is 0 .. 256 (0: no list);
+        list_mask: bit c set = hits of class c may be listed (None: every class).  Equal to regions_of_rows of the hits.txt
+        search_hits gives for the same guide and params, window range included; no text is built or copied."""
+        g = guide.to_c()
+        m = model.to_c()
+        out = ctypes.POINTER(RegionsT)()
+        _lib.check(self._h, lib.calitas_search_regions(self._h, ctypes.byref(g), ctypes.byref(params), ctypes.byref(m), _top_k(k), _mask(list_mask),
+                                                       ctypes.byref(out)))
+        return self._take_regions(out)
+
+    def search_regions_batch(self, guides, params, model, k, list_mask=None):
+        """calitas_search_regions_batch: a list of RegionScores, one per guide (all of one length), pipelined like search_top_batch."""
+        n = len(guides)
+        keep = [g.to_c() for g in guides]
+        garr = (GuideT * n)(*keep)
+        m = model.to_c()
+        out = (ctypes.POINTER(RegionsT) * n)()
+        _lib.check(self._h, lib.calitas_search_regions_batch(self._h, n, garr, ctypes.byref(params), ctypes.byref(m), _top_k(k), _mask(list_mask), out))
+        return [self._take_regions(out[i]) for i in range(n)]
+
+    def hits_regions(self, guide, params, model, k, alignments, list_mask=None):
+        """calitas_hits_regions: hits_top split by the context's regions -- the host stage, usable on a host-only context."""
+        g = guide.to_c()
+        m = model.to_c()
+        n = len(alignments)
+        arr = (AlnT * max(1, n))(*[a.to_c() for a in alignments])
+        out = ctypes.POINTER(RegionsT)()
+        _lib.check(self._h, lib.calitas_hits_regions(self._h, ctypes.byref(g), ctypes.byref(params), ctypes.byref(m), _top_k(k), _mask(list_mask), arr, n,
+                                                     ctypes.byref(out)))
+        return self._take_regions(out)
+
     def search_scores(self, guide, params, model):
         """calitas_search_scores: search_counts plus the specificity score of the guide's hits under `model` (a ScoreModel of the
         guide's protospacer length) -- a Scores object.  Equal to scores_of_rows of the hits.txt search_hits gives for the same guide
@@ -795,13 +866,35 @@ class SearchReference:
         """The scores and the k highest-scoring imperfect hits (Context.search_top): a Top object."""
         return self._score_pass(lambda ctx, params: ctx.search_top(self.query, params, model, k))
 
-    def execute(self, counts=False, scores=None, top=None):
+    def regions(self, model, regions, k=0, top_classes=None):
+        """The scores, split by the classes of a Regions object or a BED file, and the k best imperfect hits of the classes named in
+        top_classes (None: all) (Context.search_regions): a RegionScores object."""
+        def call(ctx, params):
+            reg = regions if isinstance(regions, Regions) else Regions.read_bed(regions, dict(zip(ctx.contig_names, ctx.contig_lengths)))
+            ctx.set_regions(reg)
+            return ctx.search_regions(self.query, params, model, k, None if top_classes is None else reg.mask_of(top_classes))
+        return self._score_pass(call)
+
+    def execute(self, counts=False, scores=None, top=None, regions=None, top_classes=None):
         """counts=True (`--counts`): the table as a TSV (counts_tsv) instead of hits.txt.  scores=ScoreModel (`--scores MODEL`): the
         scores TSV (scores_tsv); top=K with it (`--top K`): the top TSV (top_tsv) of the same pass behind an empty line; with counts as
-        well, the counts TSV of the same pass's table follows behind an empty line."""
+        well, the counts TSV of the same pass's table follows behind an empty line.  regions=FILE.bed with scores (`--regions`): the
+        classes' TSV (regions_tsv) behind the scores and an empty line, and the top TSV gains a last column `class`; top_classes
+        (`--top-classes name,...`): the classes whose hits may be listed."""
         if top is not None and scores is None:
             raise ValueError("--top K requires --scores MODEL")
-        if scores is not None:
+        if regions is not None and scores is None:
+            raise ValueError("--regions FILE.bed requires --scores MODEL")
+        if regions is not None and self.variants is not None:
+            raise ValueError("--regions covers the reference-genome branch only (no --variants)")
+        if top_classes is not None and (regions is None or top is None):
+            raise ValueError("--top-classes requires --regions and --top")
+        if regions is not None:
+            got = self.regions(scores, regions, top or 0, top_classes)
+            text = (scores_tsv(self.guide_id, got.top.scores) + "\n" + regions_tsv(self.guide_id, got)
+                    + ("\n" + top_tsv(self.guide_id, got.top, [got.classes[c] for c in got.hit_class]) if top is not None else "")
+                    + ("\n" + counts_tsv(self.guide_id, got.top.scores.table) if counts else ""))
+        elif scores is not None:
             got = self.scores(scores) if top is None else self.top(scores, top)
             sc = got if top is None else got.scores
             text = (scores_tsv(self.guide_id, sc) + ("\n" + top_tsv(self.guide_id, got) if top is not None else "")
@@ -1106,13 +1199,176 @@ def top_of_rows(rows, model, k, shape=None):
     return Top(scores_of_rows(rows, model, shape), k, hits[:k])
 
 
-def top_tsv(guide_id, top):
+def top_tsv(guide_id, top, class_names=None):
     """`SearchReference --scores MODEL --top K`: header guide_id rank chromosome coordinate_start coordinate_end strand guide_mm
-    guide_gaps pam_mm score_q32 score, then one line per record; rank is 1-based, score = score_q32 / 2^32."""
-    lines = ["\t".join(TOP_COLUMNS)]
+    guide_gaps pam_mm score_q32 score, then one line per record; rank is 1-based, score = score_q32 / 2^32.  class_names (with
+    `--regions`): one name per record, a last column `class`."""
+    lines = ["\t".join(TOP_COLUMNS + (("class",) if class_names is not None else ()))]
     for i, h in enumerate(top.hits):
         lines.append("%s\t%d\t%s\t%d\t%d\t%s\t%d\t%d\t%d\t%d\t%.6f" % (guide_id, i + 1, h.chromosome, h.coordinate_start, h.coordinate_end, h.strand,
-                                                                         h.guide_mm, h.guide_gaps, h.pam_mm, h.score_q32, h.score_q32 / 2.0 ** 32))
+                                                                         h.guide_mm, h.guide_gaps, h.pam_mm, h.score_q32, h.score_q32 / 2.0 ** 32)
+                     + ("\t" + class_names[i] if class_names is not None else ""))
+    return "\n".join(lines) + "\n"
+
+
+REGION_COLUMNS = ("guide_id", "class", "rows", "perfect", "offtarget_sum_q32", "max_q32", "specificity")
+
+
+def _mask(list_mask):
+    if list_mask is None:
+        return 0xFFFFFFFF
+    if not isinstance(list_mask, int) or isinstance(list_mask, bool) or list_mask < 0 or list_mask >= 1 << 32:
+        raise ValueError("list_mask of a regions call is an integer of 32 bits")
+    return list_mask
+
+
+class Regions:
+    """A set of annotated intervals: (chromosome, start, end, class_name) tuples, [start, end) 0-based and half-open like BED, in any
+    order, overlapping or nested.  The class names take priority in order of first appearance -- classes[0] is "elsewhere" (no
+    interval), classes[1] wins over classes[2] where both cover a hit -- and at most 7 are allowed.  intervals: the tuples with the
+    class's index in the place of its name."""
+    ELSEWHERE = "elsewhere"
+
+    def __init__(self, intervals=(), classes=None):
+        self.classes = [self.ELSEWHERE] + [c for c in (classes or [])]
+        if len(set(self.classes)) != len(self.classes):
+            raise ValueError("class names repeat, or one is the reserved name %r" % self.ELSEWHERE)
+        self.intervals = []
+        for chrom, start, end, name in intervals:
+            if name == self.ELSEWHERE:
+                raise ValueError("the class name %r is reserved for hits outside every interval" % self.ELSEWHERE)
+            if name not in self.classes:
+                self.classes.append(name)
+            start, end = int(start), int(end)
+            if not 0 <= start < end:
+                raise ValueError("interval %s:%d-%d: start >= end (or negative)" % (chrom, start, end))
+            self.intervals.append((chrom, start, end, self.classes.index(name)))
+        if len(self.classes) > _lib.REGION_CLASSES_MAX:
+            raise ValueError("%d class names: at most %d are allowed" % (len(self.classes) - 1, _lib.REGION_CLASSES_MAX - 1))
+        if self.intervals and len(self.classes) < 2:
+            raise ValueError("no class")
+
+    def mask_of(self, names):
+        """The list_mask of these class names (an iterable, or a comma-separated string); "elsewhere" is class 0."""
+        if isinstance(names, str):
+            names = [n for n in names.split(",") if n]
+        mask = 0
+        for n in names:
+            if n not in self.classes:
+                raise ValueError("unknown class %r (the set has %s)" % (n, ", ".join(self.classes)))
+            mask |= 1 << self.classes.index(n)
+        return mask
+
+    @classmethod
+    def read_bed(cls, path, contigs=None):
+        """Four columns: chromosome, start, end, class name (further columns are ignored); lines starting with #, track or browser and
+        empty lines are skipped.  contigs (name -> length, e.g. of a Context): intervals on a chromosome it lacks are skipped and
+        counted on stderr, an interval past its contig's end is an error."""
+        import sys
+        rows, skipped = [], 0
+        with open(path) as f:
+            for no, line in enumerate(f, 1):
+                line = line.rstrip("\r\n")
+                if not line.strip() or line.startswith("#") or line.startswith("track") or line.startswith("browser"):
+                    continue
+                p = line.split("\t") if "\t" in line else line.split()
+                if len(p) < 4:
+                    raise ValueError("%s:%d: a regions file has four columns (chromosome, start, end, class)" % (path, no))
+                try:
+                    a, b = int(p[1]), int(p[2])
+                except ValueError:
+                    raise ValueError("%s:%d: start and end are integers" % (path, no))
+                if contigs is not None and p[0] in contigs and b > contigs[p[0]]:
+                    raise ValueError("%s:%d: the interval ends beyond %s (%d bases)" % (path, no, p[0], contigs[p[0]]))
+                rows.append((p[0], a, b, p[3]))
+        out = cls(rows)                         # (a class keeps its priority even when all its intervals are skipped)
+        if contigs is not None:
+            kept = [iv for iv in out.intervals if iv[0] in contigs]
+            skipped = len(out.intervals) - len(kept)
+            out.intervals = kept
+        if skipped:
+            sys.stderr.write("%d intervals on chromosomes the reference does not have were skipped\n" % skipped)
+        return out
+
+
+class RegionScores:
+    """What a regions call returns: `top` (a Top: its scores are the totals, its hits the best k among the classes of the mask),
+    `classes` (the names, class 0 = "elsewhere" first), `by_class` (a Scores per class; they add up to top.scores) and `hit_class`
+    (the class index of every record of top.hits)."""
+    __slots__ = ("top", "classes", "by_class", "hit_class")
+
+    def __init__(self, top, classes, by_class, hit_class):
+        self.top, self.classes, self.by_class, self.hit_class = top, list(classes), list(by_class), [int(c) for c in hit_class]
+
+    def merge(self, *others):
+        """Consecutive pieces of one job IN THEIR ORDER: by_class adds like Scores, the lists merge like Top's, and a record's class
+        travels with it."""
+        scores, by_class = self.top.scores, list(self.by_class)
+        pairs = list(zip(self.top.hits, self.hit_class))
+        for o in others:
+            if o.top.k != self.top.k or o.classes != self.classes:
+                raise ValueError("pieces of different k or classes do not merge")
+            scores = scores + o.top.scores
+            by_class = [a + b for a, b in zip(by_class, o.by_class)]
+            pairs += list(zip(o.top.hits, o.hit_class))
+        pairs.sort(key=lambda p: -p[0].score_q32)            # (stable: the tie rule)
+        pairs = pairs[:self.top.k]
+        return RegionScores(Top(scores, self.top.k, [p[0] for p in pairs]), self.classes, by_class, [p[1] for p in pairs])
+
+    def __eq__(self, o):
+        return (isinstance(o, RegionScores) and self.top == o.top and self.classes == o.classes and self.by_class == o.by_class
+                and self.hit_class == o.hit_class)
+
+    __hash__ = None
+
+    def __repr__(self):
+        return "RegionScores(%r, %s, hit_class=%r)" % (self.top, ", ".join("%s: %r" % (n, s) for n, s in zip(self.classes, self.by_class)), self.hit_class)
+
+
+def class_of_row(row, regions, by_chromosome=None):
+    """The contract on one hits.txt row: the smallest class index among the raw intervals of the row's chromosome with
+    start < coordinate_end and end > coordinate_start; 0 when there is none or the extent is empty.  A plain scan of every interval
+    (by_chromosome: the same intervals as lists per chromosome, so that many rows do not each pass over the other chromosomes')."""
+    chrom, a, b = row["chromosome"], int(row["coordinate_start"]), int(row["coordinate_end"])
+    best = 0
+    if a < b:
+        for c, s, e, k in (regions.intervals if by_chromosome is None else by_chromosome.get(chrom, ())):
+            if c == chrom and s < b and e > a and (best == 0 or k < best):
+                best = k
+    return best
+
+
+def regions_of_rows(rows, model, regions, k, list_mask=None, shape=None):
+    """What search_regions returns, from hits.txt rows (read_hits output) in the text's order: the contract in plain Python --
+    class_of_row and score_of_row per row, the rows of a class summed by scores_of_rows, and a stable sort by descending score of
+    the imperfect rows whose class is in list_mask.  It shares nothing with the library's flattened form."""
+    if not 0 <= k <= _lib.TOP_MAX:
+        raise ValueError("k of a regions call is 0 .. %d" % _lib.TOP_MAX)
+    mask = _mask(list_mask)
+    n = len(regions.classes)
+    by_chromosome = {}
+    for iv in regions.intervals:
+        by_chromosome.setdefault(iv[0], []).append(iv)
+    cls = [class_of_row(r, regions, by_chromosome) for r in rows]
+    by_class = [scores_of_rows([r for r, c in zip(rows, cls) if c == i], model, shape) for i in range(n)]
+    hits = []
+    for r, c in zip(rows, cls):
+        s = score_of_row(r, model)
+        if s is None or not (mask >> c) & 1:
+            continue
+        hits.append((TopHit(s, r["chromosome"], int(r["coordinate_start"]), int(r["coordinate_end"]), r["strand"], int(r["guide_mm"]),
+                            int(r["guide_gaps"]), int(r["pam_mm"])), c))
+    hits.sort(key=lambda h: -h[0].score_q32)
+    hits = hits[:k]
+    return RegionScores(Top(scores_of_rows(rows, model, shape), k, [h[0] for h in hits]), regions.classes, by_class, [h[1] for h in hits])
+
+
+def regions_tsv(guide_id, got):
+    """`SearchReference --scores MODEL --regions FILE.bed`: header guide_id class rows perfect offtarget_sum_q32 max_q32 specificity,
+    then one line per class in class order ("elsewhere" first)."""
+    lines = ["\t".join(REGION_COLUMNS)]
+    for name, s in zip(got.classes, got.by_class):
+        lines.append("%s\t%s\t%d\t%d\t%d\t%d\t%.6f" % (guide_id, name, s.rows, s.perfect, s.sum_q32, s.max_q32, s.specificity))
     return "\n".join(lines) + "\n"
 
 

@@ -242,8 +242,16 @@ int calitas_fail(calitas_ctx* ctx, int code, const std::string& msg) {
 }
 static int fail(calitas_ctx* ctx, int code, const std::string& msg) { return calitas_fail(ctx, code, msg); }
 
+// The device copy of the regions' tables (calitas_set_regions); the caller has made sure nothing on the device still reads them.
+static void free_regions_device(calitas_ctx* c) {
+  if (c->device < 0) return;
+  (void)hipFree(c->d_region_seg); (void)hipFree(c->d_region_coarse); (void)hipFree(c->d_region_contig);
+  c->d_region_seg = nullptr; c->d_region_coarse = nullptr; c->d_region_contig = nullptr;
+}
+
 static void free_reference_device(calitas_ctx* c) {
   if (c->device < 0) return;
+  free_regions_device(c);
   (void)hipFree(c->d_codes); (void)hipFree(c->d_planes); (void)hipFree(c->d_mask); (void)hipFree(c->d_runs); (void)hipFree(c->d_contigs); (void)hipFree(c->d_tiles); (void)hipFree(c->d_tile_list); (void)hipFree(c->d_win_base); (void)hipFree(c->d_win);
   c->d_win_base = nullptr; c->d_win = nullptr; c->win_cap = 0; c->win_W = c->win_step = 0;
   (void)hipFree(c->d_bin_base); c->d_bin_base = nullptr; (void)hipFree(c->d_bin_contig); c->d_bin_contig = nullptr; c->bin_shift = 0; c->bin_base.clear(); c->bin_decl_pams = -1;
@@ -387,6 +395,7 @@ static int upload_reference(calitas_ctx* ctx) {
   ctx->ref_serial++;
   ctx->seq_pams = -1; ctx->fit_pams = -1;   // what did (not) fit the old reference may (not) fit this one
   ctx->has_ref = false;
+  ctx->regions.clear();                     // (the intervals were given in the old reference's coordinates; free_reference_device drops their device copy)
   if (ctx->device >= 0) {
     const int rc = upload_reference_device(ctx);
     if (rc) {
@@ -398,6 +407,39 @@ static int upload_reference(calitas_ctx* ctx) {
   }
   ctx->has_ref = true;
   return CALITAS_OK;
+}
+
+int calitas_set_regions(calitas_ctx* ctx, uint64_t n, const calitas_region_t* iv, uint32_t n_classes) {
+  if (!ctx) return CALITAS_EINVAL;
+  if (!ctx->has_ref) return fail(ctx, CALITAS_ESTATE, "calitas_set_reference has not been called");
+  std::vector<uint64_t> lens(ctx->ref.contigs.size());
+  for (size_t c = 0; c < lens.size(); c++) lens[c] = ctx->ref.contigs[c].len;
+  RegionsHost flat;
+  const std::string e = regions_flatten(lens, [&](size_t c) { return ctx->ref.is_absent(c); }, iv, n, n_classes, flat);
+  if (!e.empty()) return fail(ctx, CALITAS_EINVAL, e);
+  if (ctx->device >= 0) {
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, hipDeviceSynchronize());   // (nothing of the old set may be freed under a kernel that reads it)
+    free_regions_device(ctx);
+  }
+  ctx->regions.clear();
+  if (flat.empty()) return CALITAS_OK;
+  if (ctx->device >= 0) {
+    HIP_TRY(ctx, hipMalloc((void**)&ctx->d_region_seg, flat.seg.size() * sizeof(RegionSeg)));
+    HIP_TRY(ctx, hipMalloc((void**)&ctx->d_region_coarse, flat.coarse.size() * sizeof(uint32_t)));
+    HIP_TRY(ctx, hipMalloc((void**)&ctx->d_region_contig, flat.contig.size() * sizeof(uint32_t)));
+    HIP_TRY(ctx, hipMemcpy(ctx->d_region_seg, flat.seg.data(), flat.seg.size() * sizeof(RegionSeg), hipMemcpyHostToDevice));
+    HIP_TRY(ctx, hipMemcpy(ctx->d_region_coarse, flat.coarse.data(), flat.coarse.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    HIP_TRY(ctx, hipMemcpy(ctx->d_region_contig, flat.contig.data(), flat.contig.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    HIP_TRY(ctx, hipDeviceSynchronize());   // the searches run on non-blocking streams, which nothing orders against these copies
+  }
+  ctx->regions = std::move(flat);
+  return CALITAS_OK;
+}
+
+int calitas_region_class(const calitas_ctx* ctx, int32_t contig_index, int64_t start, int64_t end) {
+  if (!ctx || !ctx->has_ref || ctx->regions.empty() || contig_index < 0 || (size_t)contig_index >= ctx->ref.contigs.size()) return -1;
+  return (int)region_class(ctx->regions.view(), (uint32_t)contig_index, start, end, ctx->ref.contigs[(size_t)contig_index].len);
 }
 
 int calitas_set_reference(calitas_ctx* ctx, int32_t n_contigs, const char* const* names, const uint64_t* lengths,
@@ -899,6 +941,110 @@ int calitas_search_top_batch(calitas_ctx* ctx, int32_t n_guides, const calitas_g
   return rc;
 }
 
+// A guide's regions result as the ABI hands it over: struct, by_class entries, the cells of the totals and of every class, the records
+// and their class bytes in one block of the library's.
+static calitas_regions_t* regions_block(const CountsShape& shape, const uint64_t* table, uint64_t rows, const ScoreWords& w, uint32_t k, uint32_t list_mask,
+                                        uint32_t n_classes) {
+  const size_t cells = shape.cells(), n = std::min<size_t>(w.top.hits.size(), k);
+  const size_t bytes = sizeof(calitas_regions_t) + n_classes * sizeof(calitas_scores_t) + (1 + (size_t)n_classes) * cells * sizeof(uint64_t) +
+                       n * sizeof(calitas_top_hit_t) + n;
+  calitas_regions_t* r = (calitas_regions_t*)out_alloc(bytes);
+  if (!r) return nullptr;
+  r->by_class = reinterpret_cast<calitas_scores_t*>(r + 1);
+  uint64_t* cell_mem = reinterpret_cast<uint64_t*>(r->by_class + n_classes);
+  auto fill = [&](calitas_scores_t* c, uint64_t c_rows, uint64_t perfect, uint64_t sum, uint64_t max, const uint64_t* src) {
+    c->rows = c_rows; c->perfect = perfect; c->sum_q32 = sum; c->max_q32 = max;
+    c->table.n_mm = shape.n_mm; c->table.n_gaps = shape.n_gaps; c->table.n_pam = shape.n_pam; c->table.rows = c_rows;
+    c->table.counts = cell_mem;
+    if (src) std::memcpy(cell_mem, src, cells * sizeof(uint64_t)); else std::memset(cell_mem, 0, cells * sizeof(uint64_t));
+    cell_mem += cells;
+  };
+  fill(&r->top.scores, rows, w.perfect, w.sum_q32, w.max_q32, table);
+  const bool have = w.reg.n_classes == n_classes;             // (a call without any hit leaves no words: every class is empty)
+  for (uint32_t c = 0; c < n_classes; c++) {
+    const uint64_t* cw = have ? w.reg.words.data() + (size_t)c * REGION_WORDS : nullptr;
+    fill(&r->by_class[c], cw ? cw[3] : 0, cw ? cw[1] : 0, cw ? cw[0] : 0, cw ? cw[2] : 0, have ? w.reg.tables.data() + (size_t)c * cells : nullptr);
+  }
+  r->top.k = k; r->top.n = (uint32_t)n;
+  r->top.hits = reinterpret_cast<calitas_top_hit_t*>(cell_mem);
+  if (n) std::memcpy(r->top.hits, w.top.hits.data(), n * sizeof(calitas_top_hit_t));
+  r->hit_class = reinterpret_cast<uint8_t*>(r->top.hits + n);
+  if (n) std::memcpy(r->hit_class, w.top.cls.data(), n);
+  r->n_classes = n_classes; r->list_mask = list_mask;
+  return r;
+}
+// What every regions entry point checks first, and what it gives the model.  Returns an error text or "".
+static std::string regions_inputs(const calitas_ctx* ctx, uint32_t k, uint32_t list_mask, ScoreModelHost& mh) {
+  if (ctx->regions.empty()) return "the context has no regions (calitas_set_regions)";
+  if (k > CALITAS_TOP_MAX) return "k of a regions call must be 0 .. CALITAS_TOP_MAX (256)";
+  if (k > 0 && (list_mask & ((1u << ctx->regions.n_classes) - 1u)) == 0) return "list_mask of a regions call has no bit below n_classes";
+  mh.top_k = k;
+  mh.regions = &ctx->regions;
+  mh.list_mask = list_mask & ((1u << ctx->regions.n_classes) - 1u);
+  mh.regions_dev = RegionsView{ctx->d_region_seg, ctx->d_region_coarse, ctx->d_region_contig, ctx->regions.n_classes};
+  return "";
+}
+// What a regions call's words must satisfy before they are handed over (internal errors otherwise): the list as long as it can be at
+// most, a class byte per record, and the classes' rows adding up to the call's.
+static bool regions_words_ok(const ScoreWords& w, uint64_t rows, uint32_t k) {
+  if (w.top.hits.size() > std::min<uint64_t>(k, rows - w.perfect) || w.top.cls.size() != w.top.hits.size()) return false;
+  if (w.reg.n_classes == 0) return rows == 0;
+  uint64_t sum = 0;
+  for (uint32_t c = 0; c < w.reg.n_classes; c++) sum += w.reg.words[(size_t)c * REGION_WORDS + 3];
+  return sum == rows;
+}
+
+int calitas_search_regions(calitas_ctx* ctx, const calitas_guide_t* guide, const calitas_params_t* params, const calitas_score_model_t* model,
+                           uint32_t k, uint32_t list_mask, calitas_regions_t** out) {
+  if (!ctx) return CALITAS_EINVAL;
+  if (!guide || !params || !model || !out) return fail(ctx, CALITAS_EINVAL, "NULL argument");
+  *out = nullptr;
+  GuideHost gh;
+  ScoreModelHost mh;
+  std::string e = score_inputs(*guide, model, gh, mh);
+  if (e.empty()) e = regions_inputs(ctx, k, list_mask, mh);
+  if (!e.empty()) return fail(ctx, CALITAS_EINVAL, e);
+  CountsShape shape;
+  std::vector<uint64_t> table;
+  uint64_t rows = 0;
+  ScoreWords w;
+  const int rc = calitas_search_counts_impl(ctx, guide, params, &shape, &table, &rows, &mh, &w);
+  if (rc) return rc;
+  if (!regions_words_ok(w, rows, k)) return fail(ctx, CALITAS_EHIP, "the words of a regions call do not add up to its rows (internal error)");
+  *out = regions_block(shape, table.data(), rows, w, k, list_mask, ctx->regions.n_classes);
+  return *out ? CALITAS_OK : fail(ctx, CALITAS_EINVAL, "out of memory");
+}
+
+int calitas_search_regions_batch(calitas_ctx* ctx, int32_t n_guides, const calitas_guide_t* guides, const calitas_params_t* params,
+                                 const calitas_score_model_t* model, uint32_t k, uint32_t list_mask, calitas_regions_t** out) {
+  if (!ctx) return CALITAS_EINVAL;
+  if (n_guides <= 0 || !guides || !params || !model || !out) return fail(ctx, CALITAS_EINVAL, "bad argument");
+  for (int i = 0; i < n_guides; i++) out[i] = nullptr;
+  ScoreModelHost mh;
+  for (int i = 0; i < n_guides; i++) {                        // (all guides of a batch have one length: one model serves them)
+    GuideHost gh;
+    const std::string e = score_inputs(guides[i], model, gh, mh);
+    if (!e.empty()) return fail(ctx, CALITAS_EINVAL, e);
+  }
+  { const std::string e = regions_inputs(ctx, k, list_mask, mh); if (!e.empty()) return fail(ctx, CALITAS_EINVAL, e); }
+  std::vector<std::vector<uint64_t>> tables((size_t)n_guides);
+  std::vector<uint64_t> rows((size_t)n_guides, 0);
+  std::vector<ScoreWords> words((size_t)n_guides);
+  int rc = calitas_search_hits_batch_impl(ctx, n_guides, guides, nullptr, params, nullptr, nullptr, nullptr, nullptr, rows.data(), &tables, &mh, &words);
+  for (int i = 0; i < n_guides && !rc; i++) {
+    GuideHost gh;
+    CountsShape shape;
+    const ScoreWords& w = words[(size_t)i];
+    std::string e = make_guide_host(guides[i], gh);
+    if (e.empty()) e = counts_shape(gh, *params, shape);
+    if (!e.empty() || tables[(size_t)i].size() != shape.cells()) rc = fail(ctx, CALITAS_EINVAL, e.empty() ? "a guide's table has another shape than its plan (internal error)" : e);
+    else if (!regions_words_ok(w, rows[(size_t)i], k)) rc = fail(ctx, CALITAS_EHIP, "the words of a regions call do not add up to its rows (internal error)");
+    else if (!(out[i] = regions_block(shape, tables[(size_t)i].data(), rows[(size_t)i], w, k, list_mask, ctx->regions.n_classes))) rc = fail(ctx, CALITAS_EINVAL, "out of memory");
+  }
+  if (rc) for (int i = 0; i < n_guides; i++) { calitas_free(out[i]); out[i] = nullptr; }
+  return rc;
+}
+
 int calitas_scan_candidates(calitas_ctx* ctx, int32_t n_guides, const calitas_guide_t* guides, const calitas_params_t* params,
                             uint32_t** records, uint64_t* n_records) {
   return calitas_scan_candidates_impl(ctx, n_guides, guides, params, records, n_records);
@@ -1040,6 +1186,30 @@ int calitas_hits_top(const calitas_ctx* ctx, const calitas_guide_t* guide, const
                &w.top, ctx->pool);
   if (!e.empty()) return fail(c, CALITAS_EINVAL, e);
   *out = top_block(shape, table.data(), rows, w, k);
+  return *out ? CALITAS_OK : fail(c, CALITAS_EINVAL, "out of memory");
+}
+
+int calitas_hits_regions(const calitas_ctx* ctx, const calitas_guide_t* guide, const calitas_params_t* params, const calitas_score_model_t* model,
+                         uint32_t k, uint32_t list_mask, const calitas_aln_t* alns, uint64_t n_alns, calitas_regions_t** out) {
+  if (!ctx || !guide || !params || !model || !out || (n_alns && !alns)) return CALITAS_EINVAL;
+  calitas_ctx* c = const_cast<calitas_ctx*>(ctx);
+  *out = nullptr;
+  if (!ctx->has_ref) return fail(c, CALITAS_ESTATE, "calitas_set_reference has not been called");
+  GuideHost gh;
+  ScoreModelHost mh;
+  CountsShape shape;
+  std::string e = score_inputs(*guide, model, gh, mh);
+  if (e.empty()) e = regions_inputs(ctx, k, list_mask, mh);
+  if (e.empty()) e = counts_shape(gh, *params, shape);
+  if (!e.empty()) return fail(c, CALITAS_EINVAL, e);
+  std::vector<uint64_t> table(shape.cells(), 0);
+  uint64_t rows = 0;
+  ScoreWords w;
+  w.top.k = k;
+  e = hits_regions(ctx->ref, gh, *params, mh, alns, n_alns, shape.n_mm, shape.n_gaps, shape.n_pam, table.data(), &rows, &w.perfect, &w.sum_q32, &w.max_q32,
+                   &w.top, &w.reg, ctx->pool);
+  if (!e.empty()) return fail(c, CALITAS_EINVAL, e);
+  *out = regions_block(shape, table.data(), rows, w, k, list_mask, ctx->regions.n_classes);
   return *out ? CALITAS_OK : fail(c, CALITAS_EINVAL, "out of memory");
 }
 

@@ -655,14 +655,15 @@ __global__ __launch_bounds__(64 * BIN_WAVES) void bin_rows_kernel(BinArgs a, Mid
 // BIN_ROWS); the cell comes from the same arithmetic the row's length does (hits_dev.hpp: hit_key).  The workgroup that finishes last
 // brings the table to the host and posts what bin_rows_kernel posts when it starts.  The body is a template over a mode:
 // bin_counts_kernel is it without the score (what a counts call launches, unchanged), bin_scores_kernel with it, bin_top_kernel with
-// the score and the list.
+// the score and the list, bin_regions_kernel with a class per hit besides (hits_dev.hpp: the regions).
 template <int MODE>
-__device__ __forceinline__ void bin_counts_body(const BinArgs& a, const CountsOut& co, const ScoreArgs& sa, const TopArgs& ta, const HitsRef& ref,
-                                                const RowsArgs& o, uint32_t* hist, ScoreLds* sl, TopLds* tl) {
-  constexpr bool SCORE = MODE != MODE_COUNTS, TOP = MODE == MODE_TOP;
+__device__ __forceinline__ void bin_counts_body(const BinArgs& a, const CountsOut& co, const ScoreArgs& sa, const TopArgs& ta, const RegionArgs& ra,
+                                                const HitsRef& ref, const RowsArgs& o, uint32_t* hist, ScoreLds* sl, TopLds* tl, RegionLds* rl) {
+  constexpr bool SCORE = MODE != MODE_COUNTS, TOP = MODE == MODE_TOP || MODE == MODE_REGIONS, REG = MODE == MODE_REGIONS;
   CALITAS_TAIL_PRIO();
   if (SCORE) score_begin(*sl, sa);
   if (TOP) top_begin(*tl);
+  if (REG) region_begin(*rl);
   counts_begin(hist, co);
   const uint32_t n_todo = *a.rows_count;
   ScoreAcc acc;
@@ -713,27 +714,37 @@ __device__ __forceinline__ void bin_counts_body(const BinArgs& a, const CountsOu
           const bool plus = pam5 ? (rp->dir == 1) : (rp->dir == 0);      // as hit_record
           const int cell = counts_cell(rp, plus ? 0u : 1u, co.shape);
           if (cell < 0) atomicOr(a.flags, BIN_FLAG_EXTENT);
-          else {
+          else if (REG) {
+            const HitRec h = hit_record(rp, a.guides, a.win_base, a.win);
+            const uint32_t cls = region_of_hit(ra, ref, h);
+            counts_add(hist, co, (int)(cls * ra.base_cells) + cell);
+            const unsigned long long s = score_hit(*sl, sa, ref, rp, h, a.guides + rp->guide, acc);
+            region_hit(*rl, cls, s);
+            if (s != SCORE_PERFECT && ((ra.list_mask >> cls) & 1u)) tk = top_key(s, rel * BIN_ROWS + k);
+          } else {
             counts_add(hist, co, cell);
             const unsigned long long s = score_hit(*sl, sa, ref, rp, hit_record(rp, a.guides, a.win_base, a.win), a.guides + rp->guide, acc);
             if (s != SCORE_PERFECT) tk = top_key(s, rel * BIN_ROWS + k);
           }
         }
-        top_offer(*tl, ta.k, tk);
+        if (!REG || ta.k) top_offer(*tl, ta.k, tk);
       }
     }
-    top_store(*tl, ta);
+    if (!REG || ta.k) top_store(*tl, ta);
   }
   if (SCORE) score_reduce(*sl, co, acc);
+  if (REG) region_reduce(*rl, co, ra.rv.n_classes);
   if (!counts_flush(hist, co)) return;
   if (SCORE) score_publish(co);
+  if (REG) region_publish(co, ra.rv.n_classes);
   if (TOP) {                                                // the winners: key -> bin and slot -> the alignment, its record as the rows kernel derives it
-    const uint32_t m = top_fold(*tl, ta);
+    const uint32_t m = !REG || ta.k ? top_fold(*tl, ta) : 0u;
     if (threadIdx.x == 0) co.host[co.cells + SCORE_WORDS] = m;
     if (threadIdx.x < m) {
       const unsigned long long key = tl->key[threadIdx.x];
       const RawAln* rp = a.raw + a.rows[top_rank(key)].raw;
       top_record(co, threadIdx.x, key, rp, hit_record(rp, a.guides, a.win_base, a.win));
+      if (REG) region_record(co, threadIdx.x, region_of_hit(ra, ref, hit_record(rp, a.guides, a.win_base, a.win)));
     }
   }
   counts_publish(co);
@@ -743,14 +754,14 @@ __device__ __forceinline__ void bin_counts_body(const BinArgs& a, const CountsOu
 
 __global__ __launch_bounds__(COUNTS_BLOCK) void bin_counts_kernel(BinArgs a, CountsOut co, RowsArgs o) {
   __shared__ uint32_t hist[COUNTS_LDS_CELLS];
-  bin_counts_body<MODE_COUNTS>(a, co, ScoreArgs{}, TopArgs{}, HitsRef{}, o, hist, nullptr, nullptr);
+  bin_counts_body<MODE_COUNTS>(a, co, ScoreArgs{}, TopArgs{}, RegionArgs{}, HitsRef{}, o, hist, nullptr, nullptr, nullptr);
 }
 
 // Score mode: the same lanes over the same bins, and each kept hit's score into the four words behind the cells (hits_dev.hpp: score_hit).
 __global__ __launch_bounds__(COUNTS_BLOCK) void bin_scores_kernel(BinArgs a, CountsOut co, ScoreArgs sa, HitsRef ref, RowsArgs o) {
   __shared__ uint32_t hist[COUNTS_LDS_CELLS];
   __shared__ ScoreLds sl;
-  bin_counts_body<MODE_SCORES>(a, co, sa, TopArgs{}, ref, o, hist, &sl, nullptr);
+  bin_counts_body<MODE_SCORES>(a, co, sa, TopArgs{}, RegionArgs{}, ref, o, hist, &sl, nullptr, nullptr);
 }
 
 // Top mode: score mode, and the k best imperfect hits' records behind the score words (hits_dev.hpp: the top list).  The rank of a hit
@@ -760,7 +771,16 @@ __global__ __launch_bounds__(COUNTS_BLOCK) void bin_top_kernel(BinArgs a, Counts
   __shared__ uint32_t hist[COUNTS_LDS_CELLS];
   __shared__ ScoreLds sl;
   __shared__ TopLds tl;
-  bin_counts_body<MODE_TOP>(a, co, sa, ta, ref, o, hist, &sl, &tl);
+  bin_counts_body<MODE_TOP>(a, co, sa, ta, RegionArgs{}, ref, o, hist, &sl, &tl, nullptr);
+}
+
+// Regions mode: top mode, every kept hit classed by the context's regions (hits_dev.hpp: the regions).
+__global__ __launch_bounds__(COUNTS_BLOCK) void bin_regions_kernel(BinArgs a, CountsOut co, ScoreArgs sa, TopArgs ta, RegionArgs ra, HitsRef ref, RowsArgs o) {
+  __shared__ uint32_t hist[COUNTS_LDS_CELLS];
+  __shared__ ScoreLds sl;
+  __shared__ TopLds tl;
+  __shared__ RegionLds rl;
+  bin_counts_body<MODE_REGIONS>(a, co, sa, ta, ra, ref, o, hist, &sl, &tl, &rl);
 }
 
 }  // namespace
@@ -971,11 +991,17 @@ hipError_t binned_counts(const BinnedCall& c, hipEvent_t ev_done, const CountsSh
   BinArgs ba; MidArgs ma; RowsArgs ro;
   TRY(call_args(c, ba, ma));
   CountsOut co{};
-  TRY(counts_buffers(**c.hits, shape, &co));
+  TRY(counts_buffers(**c.hits, shape, &co, score ? score->regions.n_classes : 0u));
   ScoreArgs sa{};
   if (score) TRY(score_model(**c.hits, *score, c.stream, &sa));
   TRY(post_args(c, ro));
-  if (score && score->top_k) {
+  if (score && score->regions.n_classes) {
+    if ((uint64_t)c.geo.n_bins * BIN_ROWS > TOP_RANK_MAX) return hipErrorInvalidValue;      // (binned_possible keeps such a call off the bins)
+    TopArgs ta{};
+    TRY(top_buffers(**c.hits, score->top_k, &ta));
+    const RegionArgs ra{score->regions, shape.cells(), score->list_mask};
+    hipExtLaunchKernelGGL(bin_regions_kernel, dim3(counts_grid(c.geo.n_bins)), dim3(COUNTS_BLOCK), 0, c.stream, nullptr, ev_done, 0, ba, co, sa, ta, ra, c.ref, ro);
+  } else if (score && score->top_k) {
     if ((uint64_t)c.geo.n_bins * BIN_ROWS > TOP_RANK_MAX) return hipErrorInvalidValue;      // (binned_possible keeps such a call off the bins)
     TopArgs ta{};
     TRY(top_buffers(**c.hits, score->top_k, &ta));

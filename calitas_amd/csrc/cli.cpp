@@ -21,6 +21,8 @@ static void usage() {
     "         [-v variants.vcf[.gz]] [-V max-variants=16]\n"
     "         [--counts (the table guide_id strand guide_mm guide_gaps pam_mm hits instead of hits.txt)]\n"
     "         [--top K (with --scores: the K highest-scoring imperfect hits behind the scores and an empty line)]\n"
+    "         [--regions FILE.bed (with --scores: the scores per class of the four-column BED file behind the scores and an empty line;\n"
+    "          the --top lines gain a last column class)] [--top-classes name,... (list only hits of these classes)]\n"
     "         [--scores model.tsv (guide_id rows perfect offtarget_sum_q32 max_q32 specificity instead of hits.txt; with --counts the\n"
     "          table follows behind an empty line)]\n"
     "         [--device N]\n"
@@ -139,6 +141,75 @@ static bool read_score_model(const std::string& path, ScoreModelFile& out, std::
 
 // `calitas FindGuides`: the sites of an IUPAC pattern in a region as the guides a search takes -- the table of
 // `python -m calitas_amd FindGuides`, byte for byte (calitas_amd/tools.py guides_tsv).  No reference counterpart.
+// --regions FILE.bed: four columns (chromosome, start, end, class name; more are ignored); lines that start with #, track or browser
+// and empty lines are skipped.  The class names take priority in order of first appearance (class 0 is "elsewhere", at most 7 names);
+// an interval on a chromosome the reference lacks is skipped and counted on stderr, one past its contig's end is an error.
+static bool set_regions_from_bed(calitas_ctx* ctx, const std::string& path, std::vector<std::string>& classes, std::string& err) {
+  FILE* f = std::fopen(path.c_str(), "r");
+  if (!f) { err = "cannot open " + path; return false; }
+  std::string text;
+  char buf[65536];
+  size_t got;
+  while ((got = std::fread(buf, 1, sizeof buf, f)) > 0) text.append(buf, got);
+  std::fclose(f);
+  int32_t n_contigs = 0;
+  calitas_reference_info(ctx, &n_contigs, nullptr, nullptr);
+  std::vector<std::string> names((size_t)n_contigs);
+  std::vector<uint64_t> lens((size_t)n_contigs);
+  for (int32_t c = 0; c < n_contigs; c++) { const char* nm = ""; calitas_contig_name(ctx, c, &nm, &lens[(size_t)c]); names[(size_t)c] = nm; }
+  classes.assign(1, "elsewhere");
+  std::vector<calitas_region_t> iv;
+  size_t skipped = 0, line_no = 0;
+  for (size_t at = 0; at < text.size();) {
+    size_t nl = text.find('\n', at);
+    if (nl == std::string::npos) nl = text.size();
+    std::string line = text.substr(at, nl - at);
+    at = nl + 1; line_no++;
+    while (!line.empty() && (line.back() == '\r' || line.back() == '\n')) line.pop_back();
+    if (line.find_first_not_of(" \t\r\f\v") == std::string::npos || line[0] == '#' || line.rfind("track", 0) == 0 || line.rfind("browser", 0) == 0) continue;
+    const std::string where = path + ":" + std::to_string(line_no) + ": ";
+    std::vector<std::string> col;
+    if (line.find('\t') != std::string::npos) {
+      for (size_t a = 0;;) { const size_t t = line.find('\t', a); col.push_back(line.substr(a, t == std::string::npos ? t : t - a)); if (t == std::string::npos) break; a = t + 1; }
+    } else {
+      for (size_t a = 0; (a = line.find_first_not_of(" \f\v", a)) != std::string::npos;) { const size_t t = line.find_first_of(" \f\v", a); col.push_back(line.substr(a, t == std::string::npos ? t : t - a)); if (t == std::string::npos) break; a = t; }
+    }
+    if (col.size() < 4) { err = where + "a regions file has four columns (chromosome, start, end, class)"; return false; }
+    char *e1 = nullptr, *e2 = nullptr;
+    const long long a = std::strtoll(col[1].c_str(), &e1, 10), b = std::strtoll(col[2].c_str(), &e2, 10);
+    if (col[1].empty() || col[2].empty() || *e1 || *e2) { err = where + "start and end are integers"; return false; }
+    if (col[3] == "elsewhere") { err = where + "the class name elsewhere is reserved for hits outside every interval"; return false; }
+    size_t cls = std::find(classes.begin(), classes.end(), col[3]) - classes.begin();
+    if (cls == classes.size()) classes.push_back(col[3]);
+    if (classes.size() > CALITAS_REGION_CLASSES_MAX) { err = where + "more than 7 class names"; return false; }
+    if (a < 0 || a >= b) { err = where + "start >= end (or negative)"; return false; }
+    const size_t c = std::find(names.begin(), names.end(), col[0]) - names.begin();
+    if (c == names.size()) { skipped++; continue; }
+    if ((uint64_t)b > lens[c]) { err = where + "the interval ends beyond " + col[0]; return false; }
+    iv.push_back(calitas_region_t{(int32_t)c, (int32_t)a, (int32_t)b, (uint32_t)cls});
+  }
+  if (skipped) std::fprintf(stderr, "%zu intervals on chromosomes the reference does not have were skipped\n", skipped);
+  if (classes.size() < 2) { err = path + ": no interval"; return false; }
+  if (calitas_set_regions(ctx, iv.size(), iv.data(), (uint32_t)classes.size()) != CALITAS_OK) { err = std::string("regions: ") + calitas_last_error(ctx); return false; }
+  if (iv.empty()) { err = path + ": no interval lies on a chromosome of the reference"; return false; }
+  return true;
+}
+// --top-classes name,...: the list_mask of those classes.
+static bool class_mask(const std::vector<std::string>& classes, const std::string& names, uint32_t& mask, std::string& err) {
+  mask = 0;
+  for (size_t a = 0; a <= names.size();) {
+    size_t t = names.find(',', a);
+    if (t == std::string::npos) t = names.size();
+    const std::string nm = names.substr(a, t - a);
+    a = t + 1;
+    if (nm.empty()) continue;
+    const size_t c = std::find(classes.begin(), classes.end(), nm) - classes.begin();
+    if (c == classes.size()) { err = "unknown class " + nm; return false; }
+    mask |= 1u << c;
+  }
+  return true;
+}
+
 static int find_guides_main(int argc, char** argv) {
   std::string pattern, ref, output, chrom;
   std::vector<std::string> aux;
@@ -227,6 +298,8 @@ int main(int argc, char** argv) {
   int device = 0;
   bool counts = false;
   int top_k = -1;              // --top K: with --scores, the K highest-scoring imperfect hits behind the scores
+  std::string regions_path, top_classes;   // --regions FILE.bed [--top-classes name,...]: with --scores, the same split by the file's classes
+  bool have_top_classes = false;
   for (int i = 2; i < argc; i++) {
     std::string a = argv[i], val;
     size_t eq = a.find('=');
@@ -259,6 +332,8 @@ int main(int argc, char** argv) {
     else if (a == "--counts") counts = true;
     else if (a == "--scores") scores = next();
     else if (a == "--top") top_k = std::atoi(next().c_str());
+    else if (a == "--regions") regions_path = next();
+    else if (a == "--top-classes") { top_classes = next(); have_top_classes = true; }
     else if (a == "-v") variants = next();
     else { std::fprintf(stderr, "unknown argument %s\n", a.c_str()); usage(); return 2; }
   }
@@ -267,6 +342,9 @@ int main(int argc, char** argv) {
   if (!scores.empty() && !variants.empty()) { std::fprintf(stderr, "--scores covers the reference-genome branch only (no --variants)\n"); return 2; }
   if (top_k != -1 && scores.empty()) { std::fprintf(stderr, "--top K requires --scores MODEL\n"); return 2; }
   if (top_k != -1 && (top_k < 1 || top_k > CALITAS_TOP_MAX)) { std::fprintf(stderr, "--top K: K is 1 .. %d\n", CALITAS_TOP_MAX); return 2; }
+  if (!regions_path.empty() && scores.empty()) { std::fprintf(stderr, "--regions FILE.bed requires --scores MODEL\n"); return 2; }
+  if (!regions_path.empty() && !variants.empty()) { std::fprintf(stderr, "--regions covers the reference-genome branch only (no --variants)\n"); return 2; }
+  if (have_top_classes && (regions_path.empty() || top_k == -1)) { std::fprintf(stderr, "--top-classes requires --regions and --top\n"); return 2; }
   ScoreModelFile model;
   if (!scores.empty()) {
     std::string err;
@@ -308,7 +386,17 @@ int main(int argc, char** argv) {
     const calitas_score_model_t cm{model.L, model.gap, model.pam, model.mm.data()};
     calitas_scores_t* sc = nullptr;
     calitas_top_t* tp = nullptr;                            // --top K: the same pass with the list; its scores are the scores
-    if (top_k > 0) {
+    calitas_regions_t* rg = nullptr;                        // --regions: the same pass split by the file's classes; its top is the top
+    std::vector<std::string> classes;
+    if (!regions_path.empty()) {
+      std::string err;
+      uint32_t mask = 0xFFFFFFFFu;
+      if (!set_regions_from_bed(ctx, regions_path, classes, err) ||
+          (have_top_classes && !class_mask(classes, top_classes, mask, err))) { std::fprintf(stderr, "%s\n", err.c_str()); return 2; }
+      if (calitas_search_regions(ctx, &g, &p, &cm, top_k > 0 ? (uint32_t)top_k : 0u, mask, &rg) != CALITAS_OK) die("search");
+      sc = &rg->top.scores;
+      if (top_k > 0) tp = &rg->top;
+    } else if (top_k > 0) {
       if (calitas_search_top(ctx, &g, &p, &cm, (uint32_t)top_k, &tp) != CALITAS_OK) die("search");
       sc = &tp->scores;
     } else if (calitas_search_scores(ctx, &g, &p, &cm, &sc) != CALITAS_OK) die("search");
@@ -316,19 +404,29 @@ int main(int argc, char** argv) {
     std::fprintf(f, "guide_id\trows\tperfect\tofftarget_sum_q32\tmax_q32\tspecificity\n%s\t%llu\t%llu\t%llu\t%llu\t%.6f\n", guide_id.c_str(),
                  (unsigned long long)sc->rows, (unsigned long long)sc->perfect, (unsigned long long)sc->sum_q32, (unsigned long long)sc->max_q32,
                  two32 / (two32 + (double)sc->sum_q32));
+    if (rg) {
+      std::fprintf(f, "\nguide_id\tclass\trows\tperfect\tofftarget_sum_q32\tmax_q32\tspecificity\n");
+      for (uint32_t c = 0; c < rg->n_classes; c++) {
+        const calitas_scores_t& s = rg->by_class[c];
+        std::fprintf(f, "%s\t%s\t%llu\t%llu\t%llu\t%llu\t%.6f\n", guide_id.c_str(), classes[c].c_str(), (unsigned long long)s.rows,
+                     (unsigned long long)s.perfect, (unsigned long long)s.sum_q32, (unsigned long long)s.max_q32, two32 / (two32 + (double)s.sum_q32));
+      }
+    }
     if (tp) {
-      std::fprintf(f, "\nguide_id\trank\tchromosome\tcoordinate_start\tcoordinate_end\tstrand\tguide_mm\tguide_gaps\tpam_mm\tscore_q32\tscore\n");
+      std::fprintf(f, "\nguide_id\trank\tchromosome\tcoordinate_start\tcoordinate_end\tstrand\tguide_mm\tguide_gaps\tpam_mm\tscore_q32\tscore%s\n", rg ? "\tclass" : "");
       for (uint32_t i = 0; i < tp->n; i++) {
         const calitas_top_hit_t& h = tp->hits[i];
         const char* nm = ""; uint64_t len = 0;
         calitas_contig_name(ctx, h.contig_index, &nm, &len);
-        std::fprintf(f, "%s\t%u\t%s\t%d\t%d\t%c\t%u\t%u\t%u\t%llu\t%.6f\n", guide_id.c_str(), i + 1, nm, h.coordinate_start, h.coordinate_end, (char)h.strand,
+        std::fprintf(f, "%s\t%u\t%s\t%d\t%d\t%c\t%u\t%u\t%u\t%llu\t%.6f", guide_id.c_str(), i + 1, nm, h.coordinate_start, h.coordinate_end, (char)h.strand,
                      (unsigned)h.guide_mm, (unsigned)h.guide_gaps, (unsigned)h.pam_mm, (unsigned long long)h.score_q32, (double)h.score_q32 / two32);
+        if (rg) std::fprintf(f, "\t%s", classes[rg->hit_class[i]].c_str());
+        std::fprintf(f, "\n");
       }
     }
     if (counts) { std::fprintf(f, "\n"); write_counts(&sc->table); }
     rows = sc->rows;
-    calitas_free(tp ? (void*)tp : (void*)sc);
+    calitas_free(rg ? (void*)rg : tp ? (void*)tp : (void*)sc);
   } else if (counts) {        // the off-target table instead of hits.txt
     calitas_counts_t* t = nullptr;
     if (calitas_search_counts(ctx, &g, &p, &t) != CALITAS_OK) die("search");

@@ -15,6 +15,7 @@
 #include "parallel.hpp"
 #include "post.hpp"
 #include "refpack.hpp"
+#include "regions.hpp"
 #include "select.hpp"
 #include "hits.hpp"
 #include "binned.hpp"
@@ -67,6 +68,10 @@ struct calitas_ctx {
   std::vector<uint32_t> bin_base;   // the same on the host
   int bin_shift = 0;                // 0 = not built
   BinnedWork* binned = nullptr;     // lane
+  // calitas_set_regions (owner): the set, flattened (regions.hpp), and its device copy -- brought up once per set, not per call
+  RegionsHost regions;
+  RegionSeg* d_region_seg = nullptr;
+  uint32_t *d_region_coarse = nullptr, *d_region_contig = nullptr;
   SitesWork* sites = nullptr;       // calitas_find_sites: device scratch kept between calls (sites_host.cpp)
   double align_ms_by_stamps = -1;   // lane: >= 0: align_kernel + trace_kernel of the current search ran without an event behind them (binned.hpp, BIN_BOX_STAMPS)
   int rows_ev0 = 4;                 // lane: ev[rows_ev0] .. ev[5] bracket the row stage of the last call

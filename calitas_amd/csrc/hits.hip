@@ -331,16 +331,19 @@ void counts_from_box(const Mailbox& box, uint64_t* counts) {
 // alignment fin[order[k]] and its record; a kept hit the call owns (HitsOwn, as len_kernel applies it) adds one to its cell of the
 // workgroup's histogram (hits_dev.hpp: counts_cell, CountsOut).  The workgroup that finishes last brings the table to the host and
 // posts what total_kernel posts for a text: no bytes, the rows it counted, the flags.  The body is a template over a mode: counts_kernel is
-// it without the score (the kernel a counts call launches, unchanged), scores_kernel with it, top_kernel with the score and the list.
+// it without the score (the kernel a counts call launches, unchanged), scores_kernel with it, top_kernel with the score and the list,
+// regions_kernel with a class per hit besides (hits_dev.hpp: the regions).
 template <int MODE>
-__device__ __forceinline__ void counts_body(const MidArgs& a, const CountsOut& o, const ScoreArgs& sa, const TopArgs& ta, uint32_t* hist, ScoreLds* sl,
-                                            TopLds* tl, uint64_t* counts, uint32_t* flags, uint32_t* box, uint32_t seq) {
-  constexpr bool SCORE = MODE != MODE_COUNTS, TOP = MODE == MODE_TOP;
+__device__ __forceinline__ void counts_body(const MidArgs& a, const CountsOut& o, const ScoreArgs& sa, const TopArgs& ta, const RegionArgs& ra,
+                                            uint32_t* hist, ScoreLds* sl, TopLds* tl, RegionLds* rl, uint64_t* counts, uint32_t* flags, uint32_t* box,
+                                            uint32_t seq) {
+  constexpr bool SCORE = MODE != MODE_COUNTS, TOP = MODE == MODE_TOP || MODE == MODE_REGIONS, REG = MODE == MODE_REGIONS;
   CALITAS_TAIL_PRIO();
   __shared__ uint32_t s_rows;
   if (threadIdx.x == 0) s_rows = 0;
   if (SCORE) score_begin(*sl, sa);
   if (TOP) top_begin(*tl);
+  if (REG) region_begin(*rl);
   counts_begin(hist, o);
   uint32_t mine = 0;
   ScoreAcc acc;
@@ -376,30 +379,35 @@ __device__ __forceinline__ void counts_body(const MidArgs& a, const CountsOut& o
         const int cell = key >= a.own_lo && key < a.own_hi ? counts_cell(a.fin + v, h.minus, o.shape) : -2;
         if (cell == -1) atomicOr(flags, HITS_FLAG_EXTENT);
         if (cell >= 0) {
-          counts_add(hist, o, cell);
+          const uint32_t cls = REG ? region_of_hit(ra, a.ref, h) : 0u;
+          counts_add(hist, o, REG ? (int)(cls * ra.base_cells) + cell : cell);
           const unsigned long long s = score_hit(*sl, sa, a.ref, a.fin + v, h, a.guides + a.fin[v].guide, acc);
           mine++;
-          if (s != SCORE_PERFECT) tk = top_key(s, (uint32_t)k);
+          if (REG) region_hit(*rl, cls, s);
+          if (s != SCORE_PERFECT && (!REG || ((ra.list_mask >> cls) & 1u))) tk = top_key(s, (uint32_t)k);
         }
       }
-      top_offer(*tl, ta.k, tk);
+      if (!REG || ta.k) top_offer(*tl, ta.k, tk);
     }
-    top_store(*tl, ta);
+    if (!REG || ta.k) top_store(*tl, ta);
   }
   // rows of the call: one LDS add per lane that counted, one global add per workgroup
   if (mine) (void)__hip_atomic_fetch_add(&s_rows, mine, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
   __syncthreads();
   if (threadIdx.x == 0 && s_rows) (void)__hip_atomic_fetch_add(a.n_rows, s_rows, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   if (SCORE) score_reduce(*sl, o, acc);
+  if (REG) region_reduce(*rl, o, ra.rv.n_classes);
   if (!counts_flush(hist, o)) return;
   if (SCORE) score_publish(o);
+  if (REG) region_publish(o, ra.rv.n_classes);
   if (TOP) {                                                // the winners: key -> sorted position -> the hit and its alignment
-    const uint32_t m = top_fold(*tl, ta);
+    const uint32_t m = !REG || ta.k ? top_fold(*tl, ta) : 0u;
     if (threadIdx.x == 0) o.host[o.cells + SCORE_WORDS] = m;
     if (threadIdx.x < m) {
       const unsigned long long key = tl->key[threadIdx.x];
       const uint32_t v = a.order[top_rank(key)];
       top_record(o, threadIdx.x, key, a.fin + v, a.hits[v]);
+      if (REG) region_record(o, threadIdx.x, region_of_hit(ra, a.ref, a.hits[v]));
     }
   }
   counts_publish(o);
@@ -408,7 +416,7 @@ __device__ __forceinline__ void counts_body(const MidArgs& a, const CountsOut& o
 
 __global__ __launch_bounds__(COUNTS_BLOCK) void counts_kernel(MidArgs a, CountsOut o, uint64_t* counts, uint32_t* flags, uint32_t* box, uint32_t seq) {
   __shared__ uint32_t hist[COUNTS_LDS_CELLS];
-  counts_body<MODE_COUNTS>(a, o, ScoreArgs{}, TopArgs{}, hist, nullptr, nullptr, counts, flags, box, seq);
+  counts_body<MODE_COUNTS>(a, o, ScoreArgs{}, TopArgs{}, RegionArgs{}, hist, nullptr, nullptr, nullptr, counts, flags, box, seq);
 }
 
 // Score mode: the same lanes, the same cells, and each kept hit's score into the four words behind them (hits_dev.hpp: score_hit).
@@ -416,7 +424,7 @@ __global__ __launch_bounds__(COUNTS_BLOCK) void scores_kernel(MidArgs a, CountsO
                                                               uint32_t seq) {
   __shared__ uint32_t hist[COUNTS_LDS_CELLS];
   __shared__ ScoreLds sl;
-  counts_body<MODE_SCORES>(a, o, sa, TopArgs{}, hist, &sl, nullptr, counts, flags, box, seq);
+  counts_body<MODE_SCORES>(a, o, sa, TopArgs{}, RegionArgs{}, hist, &sl, nullptr, nullptr, counts, flags, box, seq);
 }
 
 // Top mode: score mode, and the k best imperfect hits' records behind the score words (hits_dev.hpp: the top list).  The rank of a hit
@@ -426,7 +434,18 @@ __global__ __launch_bounds__(COUNTS_BLOCK) void top_kernel(MidArgs a, CountsOut 
   __shared__ uint32_t hist[COUNTS_LDS_CELLS];
   __shared__ ScoreLds sl;
   __shared__ TopLds tl;
-  counts_body<MODE_TOP>(a, o, sa, ta, hist, &sl, &tl, counts, flags, box, seq);
+  counts_body<MODE_TOP>(a, o, sa, ta, RegionArgs{}, hist, &sl, &tl, nullptr, counts, flags, box, seq);
+}
+
+// Regions mode: top mode, every kept hit classed by the context's regions -- the cells, and REGION_WORDS sums, per class, and only
+// hits of the classes in list_mask in the list, with a class byte per record.
+__global__ __launch_bounds__(COUNTS_BLOCK) void regions_kernel(MidArgs a, CountsOut o, ScoreArgs sa, TopArgs ta, RegionArgs ra, uint64_t* counts, uint32_t* flags,
+                                                               uint32_t* box, uint32_t seq) {
+  __shared__ uint32_t hist[COUNTS_LDS_CELLS];
+  __shared__ ScoreLds sl;
+  __shared__ TopLds tl;
+  __shared__ RegionLds rl;
+  counts_body<MODE_REGIONS>(a, o, sa, ta, ra, hist, &sl, &tl, &rl, counts, flags, box, seq);
 }
 
 // Length of the text = end of the last row; posted with the other two counts (rows, flags) by the same thread (post_counts).
@@ -660,7 +679,12 @@ struct HitsRun {
       TRY(score_model(w, *c.score, c.stream, &sa));
       MidArgs ma = mid_args();
       ma.ref = c.ref;
-      if (c.score->top_k) {
+      if (c.score->regions.n_classes) {
+        TopArgs ta{};
+        TRY(top_buffers(w, c.score->top_k, &ta));
+        const RegionArgs ra{c.score->regions, c.counts->cells(), c.score->list_mask};
+        hipLaunchKernelGGL(regions_kernel, dim3(counts_grid(n)), dim3(COUNTS_BLOCK), 0, c.stream, ma, co, sa, ta, ra, w.d_counts, d_flags, w.mbox.dev, w.mbox.seq);
+      } else if (c.score->top_k) {
         TopArgs ta{};
         TRY(top_buffers(w, c.score->top_k, &ta));
         hipLaunchKernelGGL(top_kernel, dim3(counts_grid(n)), dim3(COUNTS_BLOCK), 0, c.stream, ma, co, sa, ta, w.d_counts, d_flags, w.mbox.dev, w.mbox.seq);
@@ -757,11 +781,15 @@ hipError_t hits_run(HitsWork** pw, const HitsRunCall& c, HitsResult* res) {
   if (c.ext && c.ext->kept) *c.ext->kept = 0;
   if ((uint64_t)c.n + n_ext > 0xFFFFFFF0ull) { res->flags = HITS_FLAG_CLUSTER; return hipSuccess; }
   const size_t n = (size_t)c.n + n_ext;
-  if (c.score && c.score->top_k && n > TOP_RANK_MAX) { res->flags = HITS_FLAG_CLUSTER; return hipSuccess; }   // (more ranks than a key holds: the host stage)
+  if (c.score && (c.score->top_k || c.score->regions.n_classes) && n > TOP_RANK_MAX) { res->flags = HITS_FLAG_CLUSTER; return hipSuccess; }   // (more ranks than a key holds: the host stage)
   CountsOut co{};
   if (c.counts) {
-    TRY(counts_buffers(w, *c.counts, &co));
-    if (n == 0) std::memset(co.host, 0, ((size_t)co.cells + SCORE_WORDS + 1) * sizeof(unsigned long long));   // (+ 1: a top call's number of records)
+    const uint32_t n_classes = c.score ? c.score->regions.n_classes : 0u;
+    TRY(counts_buffers(w, *c.counts, &co, n_classes));
+    if (n == 0) {
+      std::memset(co.host, 0, ((size_t)co.cells + SCORE_WORDS + 1) * sizeof(unsigned long long));   // (+ 1: a top call's number of records)
+      if (n_classes) std::memset(co.host + co.cells + SCORE_WORDS + TOP_WORDS, 0, REGION_CLASS_WORDS * sizeof(unsigned long long));
+    }
     res->counts = reinterpret_cast<const uint64_t*>(co.host);
   }
   if (n == 0) return hipSuccess;

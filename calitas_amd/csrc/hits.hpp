@@ -42,24 +42,54 @@ struct ScoreCall {
   const uint32_t* model;                            // host memory, SCORE_MODEL_WORDS words, valid during the call
   uint64_t letters[2];                              // positions 0-15 / 16-31
   uint32_t top_k = 0;                               // calitas_search_top: top_kernel / bin_top_kernel in the scores kernels' place
+  // calitas_search_regions: regions_kernel / bin_regions_kernel in their place (top_k may be 0: no list) -- the owner's device tables
+  RegionsView regions{};
+  uint32_t list_mask = ~0u;
 };
 // What a guide's kept hits add up to besides the table; across window ranges, contigs and lanes sum and perfect add, max takes the maximum.
 // top: the list of a top call (post.hpp, TopList) -- `o` is the piece that follows this one in the text, so add() is called in that order.
 struct ScoreWords {
   uint64_t sum_q32 = 0, perfect = 0, max_q32 = 0;
   TopList top;
-  void add(const ScoreWords& o) { sum_q32 += o.sum_q32; perfect += o.perfect; if (o.max_q32 > max_q32) max_q32 = o.max_q32; top.merge(o.top); }
+  RegionWords reg;                                  // a regions call: the same per class, and the classes' tables (regions.hpp)
+  void add(const ScoreWords& o) { sum_q32 += o.sum_q32; perfect += o.perfect; if (o.max_q32 > max_q32) max_q32 = o.max_q32; top.merge(o.top); reg.add(o.reg); }
 };
 // What a top call's kernels leave behind the SCORE_WORDS in the work's page-locked block: the number of records, then three words per
 // record in the layout of calitas_top_hit_t.
 constexpr uint32_t TOP_WORDS = 1 + 3 * CALITAS_TOP_MAX;
-inline TopList top_from_words(const uint64_t* w, uint32_t k) {
+inline TopList top_from_words(const uint64_t* w, uint32_t k, const uint8_t* cls = nullptr) {
   TopList t;
   t.k = k;
   const size_t n = (size_t)std::min<uint64_t>(w[0], k);
   t.hits.resize(n);
   if (n) std::memcpy(t.hits.data(), w + 1, n * sizeof(calitas_top_hit_t));
+  t.cls.assign(n, 0);
+  if (n && cls) std::memcpy(t.cls.data(), cls, n);
   return t;
+}
+// What a regions call's kernels leave in the work's page-locked block.  The cells come first, class-major (n_classes tables of
+// CountsShape::cells() words), then the SCORE_WORDS of the totals and the TOP_WORDS as in a top call, then REGION_WORDS words per
+// class (the last one: the hits of that class looked at) for CALITAS_REGION_CLASSES_MAX classes, then one class byte per record.
+constexpr uint32_t REGION_CLASS_WORDS = CALITAS_REGION_CLASSES_MAX * REGION_WORDS;
+constexpr uint32_t REGION_HOST_WORDS = REGION_CLASS_WORDS + CALITAS_TOP_MAX / 8;
+static_assert(REGION_WORDS == SCORE_WORDS, "a class's words are laid out like the totals'");
+// The lane's share of a regions call from that block: the classes' tables and words into `score`, the list with its class bytes, and
+// the classes' tables summed into `total` (the table every counts call returns).  False when a class's rows are not its table's sum.
+inline bool regions_from_words(const uint64_t* host, uint32_t cells, uint32_t n_classes, uint32_t k, std::vector<uint64_t>& total, ScoreWords& score) {
+  const uint64_t* w = host + (size_t)cells * n_classes;
+  const uint64_t* cw = w + SCORE_WORDS + TOP_WORDS;
+  score = ScoreWords{w[0], w[1], w[2], TopList(), RegionWords()};
+  score.reg.n_classes = n_classes;
+  score.reg.tables.assign(host, host + (size_t)cells * n_classes);
+  score.reg.words.assign(cw, cw + (size_t)n_classes * REGION_WORDS);
+  total.assign(cells, 0);
+  for (uint32_t c = 0; c < n_classes; c++) {
+    uint64_t sum = 0;
+    for (uint32_t i = 0; i < cells; i++) { const uint64_t v = host[(size_t)c * cells + i]; total[i] += v; sum += v; }
+    if (sum != cw[(size_t)c * REGION_WORDS + 3]) return false;
+  }
+  score.top = top_from_words(w + SCORE_WORDS, k, reinterpret_cast<const uint8_t*>(cw + REGION_CLASS_WORDS));
+  return true;
 }
 
 struct HitsResult {

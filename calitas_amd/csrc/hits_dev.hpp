@@ -643,8 +643,8 @@ constexpr uint32_t TOP_LISTS = 128;                      // the most workgroups 
 constexpr uint32_t TOP_RANK_MAX = 0x7FFFFFFEu;           // ranks are 0 .. TOP_RANK_MAX: a call with more declines
 static_assert(TOP_CAP == 2 * COUNTS_BLOCK && CALITAS_TOP_MAX <= COUNTS_BLOCK, "a thread per pair of the sort; a trip appends at most COUNTS_BLOCK keys");
 
-// The three modes of the counts kernels' bodies (counts_body in hits.hip, bin_counts_body in binned.hip).
-constexpr int MODE_COUNTS = 0, MODE_SCORES = 1, MODE_TOP = 2;
+// The four modes of the counts kernels' bodies (counts_body in hits.hip, bin_counts_body in binned.hip).
+constexpr int MODE_COUNTS = 0, MODE_SCORES = 1, MODE_TOP = 2, MODE_REGIONS = 3;
 
 struct TopArgs {
   uint32_t k;
@@ -741,6 +741,65 @@ __device__ __forceinline__ void top_record(const CountsOut& o, uint32_t i, unsig
 }
 __device__ __forceinline__ uint32_t top_rank(unsigned long long key) { return 0x7FFFFFFFu - (uint32_t)(key & 0x7FFFFFFFull); }
 
+// ---- the regions (calitas_search_regions) ------------------------------------------------------------------------------------------
+// Regions mode is top mode with a class per kept hit (regions.hpp: region_class on the record's coordinate_start / coordinate_end):
+// regions_kernel and bin_regions_kernel are the counts kernels' bodies in a fourth mode.  The table gets a leading class dimension --
+// CountsOut::cells is n_classes x the shape's cells, so counts_begin / counts_add / counts_flush / counts_publish do for it what they
+// do for any table: in LDS up to COUNTS_LDS_CELLS, by direct adds beyond.  The totals take the path they take in score mode (a lane's
+// registers, score_reduce); per class, every hit adds to REGION_WORDS 64-bit words in LDS -- no array indexed by the class in a
+// lane's registers --, which region_reduce flushes behind the SCORE_WORDS of the device table ahead of counts_flush and the last
+// workgroup publishes and clears (region_publish).  A hit offers its key to the selection only when its class is in list_mask; k = 0
+// (uniform) skips the selection.  The last workgroup writes a class byte per record behind the classes' words.
+struct RegionArgs {
+  RegionsView rv;
+  uint32_t base_cells;         // the shape's cells: a hit's cell is cls * base_cells + counts_cell
+  uint32_t list_mask;
+};
+struct RegionLds { unsigned long long w[CALITAS_REGION_CLASSES_MAX * REGION_WORDS]; };
+
+__device__ __forceinline__ void region_begin(RegionLds& r) {      // (counts_begin's barrier follows)
+  if (threadIdx.x < CALITAS_REGION_CLASSES_MAX * REGION_WORDS) r.w[threadIdx.x] = 0;
+}
+__device__ __forceinline__ uint32_t region_of_hit(const RegionArgs& ra, const HitsRef& ref, const HitRec& h) {
+  return min(region_class(ra.rv, (uint32_t)h.contig, h.gstart, h.gend, ref.contigs[h.contig].len), ra.rv.n_classes - 1u);
+}
+// One kept hit of class cls with score s (SCORE_PERFECT: a perfect one).
+__device__ __forceinline__ void region_hit(RegionLds& r, uint32_t cls, unsigned long long s) {
+  unsigned long long* w = r.w + cls * REGION_WORDS;
+  (void)__hip_atomic_fetch_add(w + 3, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+  if (s == SCORE_PERFECT) (void)__hip_atomic_fetch_add(w + 1, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+  else {
+    (void)__hip_atomic_fetch_add(w + 0, s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    (void)__hip_atomic_fetch_max(w + 2, s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+  }
+}
+// The workgroup's words into the device table's, behind the totals' SCORE_WORDS.  Every thread calls it, ahead of counts_flush.
+__device__ __forceinline__ void region_reduce(RegionLds& r, const CountsOut& o, uint32_t n_classes) {
+  __syncthreads();
+  if (threadIdx.x < n_classes * REGION_WORDS) {
+    const unsigned long long v = r.w[threadIdx.x];
+    unsigned long long* w = o.table + o.cells + SCORE_WORDS + threadIdx.x;
+    if (v) {
+      if ((threadIdx.x & 3u) == 2u) (void)__hip_atomic_fetch_max(w, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      else (void)__hip_atomic_fetch_add(w, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+  }
+}
+// The last workgroup, ahead of counts_publish: the classes' words to the host (behind the top list's words), and cleared.
+__device__ __forceinline__ void region_publish(const CountsOut& o, uint32_t n_classes) {
+  if (threadIdx.x < CALITAS_REGION_CLASSES_MAX * REGION_WORDS) {
+    unsigned long long v = 0;
+    if (threadIdx.x < n_classes * REGION_WORDS) {
+      v = __hip_atomic_load(o.table + o.cells + SCORE_WORDS + threadIdx.x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      __hip_atomic_store(o.table + o.cells + SCORE_WORDS + threadIdx.x, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    o.host[o.cells + SCORE_WORDS + TOP_WORDS + threadIdx.x] = v;
+  }
+}
+__device__ __forceinline__ void region_record(const CountsOut& o, uint32_t i, uint32_t cls) {
+  reinterpret_cast<uint8_t*>(o.host + o.cells + SCORE_WORDS + TOP_WORDS + REGION_CLASS_WORDS)[i] = (uint8_t)cls;
+}
+
 // Workgroups of a counts kernel over `items` items (each strides over them).
 static inline unsigned counts_grid(size_t items) { return (unsigned)std::min<size_t>(std::max<size_t>((items + COUNTS_BLOCK - 1) / COUNTS_BLOCK, 1), 128); }
 
@@ -781,10 +840,13 @@ struct HitsWork {
 };
 
 // The buffers of a call's table in the work (zero on the device: the kernels leave them so), with room for a score call's SCORE_WORDS
-// behind the cells -- and in the page-locked copy for a top call's TOP_WORDS behind those.
-inline hipError_t counts_buffers(HitsWork& w, const CountsShape& shape, CountsOut* out) {
-  const size_t cells = (size_t)shape.cells() + SCORE_WORDS;
-  if (cells == SCORE_WORDS) return hipErrorInvalidValue;
+// behind the cells -- and in the page-locked copy for a top call's TOP_WORDS behind those.  n_classes != 0: a regions call, whose
+// table has that many times the cells, and REGION_WORDS per class behind the SCORE_WORDS (in the page-locked copy: REGION_HOST_WORDS
+// behind the TOP_WORDS).
+inline hipError_t counts_buffers(HitsWork& w, const CountsShape& shape, CountsOut* out, uint32_t n_classes = 0) {
+  const size_t table_cells = (size_t)shape.cells() * std::max(n_classes, 1u);
+  const size_t cells = table_cells + SCORE_WORDS + (size_t)n_classes * REGION_WORDS;
+  if (table_cells == 0 || table_cells > 0x7FFFFFFFull) return hipErrorInvalidValue;
   if (cells + 2 > w.cnt_cap) {
     (void)hipFree(w.cnt_table); w.cnt_table = nullptr; w.cnt_cap = 0;
     const size_t cap = ((cells + 2) + 1) & ~(size_t)1;     // (a multiple of 16 bytes)
@@ -798,11 +860,11 @@ inline hipError_t counts_buffers(HitsWork& w, const CountsShape& shape, CountsOu
   if (cells > w.cnt_host_cap) {
     if (w.cnt_host) (void)hipHostFree(w.cnt_host);
     w.cnt_host = nullptr; w.cnt_host_cap = 0;
-    hipError_t e = hipHostMalloc((void**)&w.cnt_host, (cells + TOP_WORDS) * sizeof(unsigned long long), hipHostMallocDefault);
+    hipError_t e = hipHostMalloc((void**)&w.cnt_host, (cells + TOP_WORDS + REGION_HOST_WORDS) * sizeof(unsigned long long), hipHostMallocDefault);
     if (e != hipSuccess) return e;
     w.cnt_host_cap = cells;
   }
-  out->shape = shape; out->cells = shape.cells(); out->table = w.cnt_table; out->tickets = reinterpret_cast<uint32_t*>(w.cnt_table + w.cnt_cap - 1);
+  out->shape = shape; out->cells = (uint32_t)table_cells; out->table = w.cnt_table; out->tickets = reinterpret_cast<uint32_t*>(w.cnt_table + w.cnt_cap - 1);
   out->host = w.cnt_host;
   return hipSuccess;
 }

@@ -789,10 +789,12 @@ bool score_columns(const ScoreModelHost& m, const char* pg, const char* pa, cons
 // What hits_counts and hits_scores share: the kept hits, each one's padded columns (the target's only for a score) and its cell.
 static std::string count_kept(const PackedRef& ref, const GuideHost& g, const calitas_params_t& p, const ScoreModelHost* model, const calitas_aln_t* alns,
                               uint64_t n, uint32_t n_mm, uint32_t n_gaps, uint32_t n_pam, uint64_t* table, uint64_t* n_rows, uint64_t* perfect,
-                              uint64_t* sum_q32, uint64_t* max_q32, WorkerPool* pool, TopList* top = nullptr) {
+                              uint64_t* sum_q32, uint64_t* max_q32, WorkerPool* pool, TopList* top = nullptr, RegionWords* reg = nullptr) {
   WorkerPool serial(1);
   if (!pool) pool = &serial;
   const std::vector<Lite> keepers = kept_hits(ref, p, alns, n, pool, nullptr, 0);
+  const size_t cells = (size_t)2 * n_mm * n_gaps * n_pam;
+  if (reg) reg->init(model->regions->n_classes, cells);
   for (const Lite& k : keepers) {
     const calitas_aln_t& a = alns[k.idx];
     const std::string q = g.query_for(a.pam_index);
@@ -815,9 +817,13 @@ static std::string count_kept(const PackedRef& ref, const GuideHost& g, const ca
       return "a hit with guide_mm " + std::to_string(gmm) + ", guide_gaps " + std::to_string(ggp) + ", pam_mm " + std::to_string(pmm) +
              " lies outside the table's extents (" + std::to_string(n_mm) + " x " + std::to_string(n_gaps) + " x " + std::to_string(n_pam) + ")";
     const uint32_t s = a.strand == '-' ? 1u : 0u;
-    table[((s * n_mm + (uint32_t)gmm) * n_gaps + (uint32_t)ggp) * n_pam + (uint32_t)pmm]++;
+    const size_t cell = ((s * n_mm + (uint32_t)gmm) * n_gaps + (uint32_t)ggp) * n_pam + (uint32_t)pmm;
+    table[cell]++;
     if (!model) continue;
-    if (edits == 0) { ++*perfect; continue; }              // total_mm_plus_gaps GA:101
+    // a regions call: the class of the record's extent (the row's coordinate_start / coordinate_end columns)
+    const uint32_t cls = reg ? region_class(model->regions->view(), (uint32_t)a.contig_index, a.guide_start_offset, a.guide_end_offset,
+                                            ref.contigs[(size_t)a.contig_index].len) : 0u;
+    if (edits == 0) { ++*perfect; if (reg) reg->count(cls, cells, cell, true, 0); continue; }              // total_mm_plus_gaps GA:101
     const std::string t = target_bases(ref, a.contig_index, a.start_offset, a.end_offset, a.strand == '-');
     size_t ti = 0;
     for (int i = 0; i < len; i++) {                        // the padded target (SGA:511)
@@ -829,8 +835,9 @@ static std::string count_kept(const PackedRef& ref, const GuideHost& g, const ca
     if (!score_columns(*model, pg, pa, pt, len, ggp, pmm, &v)) return "an alignment has more protospacer columns than the score model has positions";
     *sum_q32 += v;
     if (v > *max_q32) *max_q32 = v;
-    if (top)                                               // (the keepers come in the text's order: push keeps it among equal scores)
-      top->push(calitas_top_hit_t{v, a.contig_index, a.guide_start_offset, a.guide_end_offset, (int8_t)a.strand, (uint8_t)gmm, (uint8_t)ggp, (uint8_t)pmm});
+    if (reg) reg->count(cls, cells, cell, false, v);
+    if (top && (!reg || ((model->list_mask >> cls) & 1u)))   // (the keepers come in the text's order: push keeps it among equal scores)
+      top->push(calitas_top_hit_t{v, a.contig_index, a.guide_start_offset, a.guide_end_offset, (int8_t)a.strand, (uint8_t)gmm, (uint8_t)ggp, (uint8_t)pmm}, (uint8_t)cls);
   }
   if (n_rows) *n_rows = keepers.size();
   return "";
@@ -852,8 +859,17 @@ std::string hits_top(const PackedRef& ref, const GuideHost& g, const calitas_par
                      uint64_t n, uint32_t n_mm, uint32_t n_gaps, uint32_t n_pam, uint64_t* table, uint64_t* n_rows, uint64_t* perfect,
                      uint64_t* sum_q32, uint64_t* max_q32, TopList* top, WorkerPool* pool) {
   *perfect = 0; *sum_q32 = 0; *max_q32 = 0;
-  top->hits.clear();
+  top->hits.clear(); top->cls.clear();
   return count_kept(ref, g, p, &model, alns, n, n_mm, n_gaps, n_pam, table, n_rows, perfect, sum_q32, max_q32, pool, top);
+}
+
+std::string hits_regions(const PackedRef& ref, const GuideHost& g, const calitas_params_t& p, const ScoreModelHost& model, const calitas_aln_t* alns,
+                         uint64_t n, uint32_t n_mm, uint32_t n_gaps, uint32_t n_pam, uint64_t* table, uint64_t* n_rows, uint64_t* perfect,
+                         uint64_t* sum_q32, uint64_t* max_q32, TopList* top, RegionWords* reg, WorkerPool* pool) {
+  if (!model.regions || model.regions->empty()) return "the context has no regions (calitas_set_regions)";
+  *perfect = 0; *sum_q32 = 0; *max_q32 = 0;
+  top->hits.clear(); top->cls.clear();
+  return count_kept(ref, g, p, &model, alns, n, n_mm, n_gaps, n_pam, table, n_rows, perfect, sum_q32, max_q32, pool, top, reg);
 }
 
 }  // namespace calitas

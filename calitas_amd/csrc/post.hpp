@@ -11,6 +11,7 @@
 #include "common.hpp"
 #include "parallel.hpp"
 #include "refpack.hpp"
+#include "regions.hpp"
 
 namespace calitas {
 
@@ -96,6 +97,11 @@ struct ScoreModelHost {
   int L = 0;
   std::vector<uint32_t> words;
   uint32_t top_k = 0;                 // calitas_search_top: the k of the list the call keeps besides the sums (0: a scores call)
+  // calitas_search_regions: the context's set (it outlives the call) -- the call classes every kept hit, keeps the sums per class
+  // besides, and lists only hits whose class has its bit in list_mask (top_k may be 0 here: no list)
+  const RegionsHost* regions = nullptr;
+  uint32_t list_mask = ~0u;
+  RegionsView regions_dev{};          // ... and the owner's device copy of its tables (null on a host-only context)
   uint32_t mismatch(int i, int g, int t) const { return words[(size_t)i * 25 + (size_t)g * 5 + (size_t)t]; }
   uint32_t gap() const { return words[32 * 25]; }
   uint32_t pam_mismatch() const { return words[32 * 25 + 1]; }
@@ -112,28 +118,32 @@ bool score_columns(const ScoreModelHost& m, const char* pg, const char* pa, cons
 // The k highest-scoring imperfect hits of a piece of a job (calitas_hip.h, calitas_top_t: score descending, the text's order among
 // equal scores), best first.  merge: the piece that follows this one in the text -- a stable merge by score, this piece's records
 // first among equals, cut at k; that is the top of the two pieces' concatenated text.
+// cls: one byte per record, the record's class in a regions call (calitas_regions_t::hit_class; 0 elsewhere) -- it travels with it.
 struct TopList {
   uint32_t k = 0;
   std::vector<calitas_top_hit_t> hits;
+  std::vector<uint8_t> cls;
   void merge(const TopList& later) {
     if (later.k > k) k = later.k;
     if (later.hits.empty() && hits.size() <= k) return;      // (nothing to merge in: the text fallback adds plain score words per row)
     std::vector<calitas_top_hit_t> out;
+    std::vector<uint8_t> out_cls;
     out.reserve(std::min<size_t>(k, hits.size() + later.hits.size()));
     size_t i = 0, j = 0;
     while (out.size() < k && (i < hits.size() || j < later.hits.size())) {
-      if (j == later.hits.size() || (i < hits.size() && hits[i].score_q32 >= later.hits[j].score_q32)) out.push_back(hits[i++]);
-      else out.push_back(later.hits[j++]);
+      if (j == later.hits.size() || (i < hits.size() && hits[i].score_q32 >= later.hits[j].score_q32)) { out.push_back(hits[i]); out_cls.push_back(cls[i++]); }
+      else { out.push_back(later.hits[j]); out_cls.push_back(later.cls[j++]); }
     }
-    hits.swap(out);
+    hits.swap(out); cls.swap(out_cls);
   }
   // one more hit behind those seen so far (the host stages walk the kept hits in the text's order)
-  void push(const calitas_top_hit_t& h) {
+  void push(const calitas_top_hit_t& h, uint8_t c = 0) {
     if (hits.size() == k && (k == 0 || hits.back().score_q32 >= h.score_q32)) return;
     size_t at = hits.size();
     while (at > 0 && hits[at - 1].score_q32 < h.score_q32) at--;
     hits.insert(hits.begin() + (std::ptrdiff_t)at, h);
-    if (hits.size() > k) hits.pop_back();
+    cls.insert(cls.begin() + (std::ptrdiff_t)at, c);
+    if (hits.size() > k) { hits.pop_back(); cls.pop_back(); }
   }
 };
 
@@ -146,5 +156,10 @@ std::string hits_scores(const PackedRef& ref, const GuideHost& g, const calitas_
 std::string hits_top(const PackedRef& ref, const GuideHost& g, const calitas_params_t& p, const ScoreModelHost& model, const calitas_aln_t* alns,
                      uint64_t n, uint32_t n_mm, uint32_t n_gaps, uint32_t n_pam, uint64_t* table, uint64_t* n_rows, uint64_t* perfect,
                      uint64_t* sum_q32, uint64_t* max_q32, TopList* top, WorkerPool* pool = nullptr);
+// hits_top of a regions call (model.regions set): every kept hit classed from its record's coordinates, the sums and tables per class
+// into *reg besides the totals, and only hits whose class is in model.list_mask offered to the list.
+std::string hits_regions(const PackedRef& ref, const GuideHost& g, const calitas_params_t& p, const ScoreModelHost& model, const calitas_aln_t* alns,
+                         uint64_t n, uint32_t n_mm, uint32_t n_gaps, uint32_t n_pam, uint64_t* table, uint64_t* n_rows, uint64_t* perfect,
+                         uint64_t* sum_q32, uint64_t* max_q32, TopList* top, RegionWords* reg, WorkerPool* pool = nullptr);
 
 }  // namespace calitas

@@ -152,6 +152,9 @@ static int search_hits_owned(calitas_ctx* ctx, const HitsCall& call, HitsOut& ou
   // top mode: the row's record besides, from coordinate_start (4), coordinate_end (5) and the columns above; the rows pass in the text's order
   ScoreWords score;
   score.top.k = call.model ? call.model->top_k : 0;
+  // regions mode: the row's class besides, from the same two columns (regions.hpp: region_class)
+  const RegionsHost* regions = call.model ? call.model->regions : nullptr;
+  if (regions) score.reg.init(regions->n_classes, pl.cshape.cells());
   auto count_row = [&](const char* q, const char* row_end, int32_t contig) -> bool {
     const char* f = q;
     uint32_t minus = 0;
@@ -171,16 +174,19 @@ static int search_hits_owned(calitas_ctx* ctx, const HitsCall& call, HitsOut& ou
     }
     const CountsShape& cs = pl.cshape;
     if (v[0] < 0 || v[1] < 0 || v[2] < 0 || (uint32_t)v[0] >= cs.n_mm || (uint32_t)v[1] >= cs.n_gaps || (uint32_t)v[2] >= cs.n_pam) return false;
-    table[((minus * cs.n_mm + (uint32_t)v[0]) * cs.n_gaps + (uint32_t)v[1]) * cs.n_pam + (uint32_t)v[2]]++;
+    const size_t cell = ((minus * cs.n_mm + (uint32_t)v[0]) * cs.n_gaps + (uint32_t)v[1]) * cs.n_pam + (uint32_t)v[2];
+    table[cell]++;
     if (!call.model) return true;
-    if (v[3] == 0) { score.perfect++; return true; }
+    const uint32_t cls = regions ? region_class(regions->view(), (uint32_t)contig, coord[0], coord[1], ref.contigs[(size_t)contig].len) : 0u;
+    if (v[3] == 0) { score.perfect++; if (regions) score.reg.count(cls, cs.cells(), cell, true, 0); return true; }
     uint64_t one = 0;
     if (!col[2] || col_len[0] != col_len[1] || col_len[0] != col_len[2] ||
         !score_columns(*call.model, col[0], col[1], col[2], (int)col_len[0], (int)v[1], (int)v[2], &one)) return false;
     ScoreWords w; w.sum_q32 = one; w.max_q32 = one;
     score.add(w);
-    if (score.top.k)
-      score.top.push(calitas_top_hit_t{one, contig, (int32_t)coord[0], (int32_t)coord[1], (int8_t)(minus ? '-' : '+'), (uint8_t)v[0], (uint8_t)v[1], (uint8_t)v[2]});
+    if (regions) score.reg.count(cls, cs.cells(), cell, false, one);
+    if (score.top.k && (!regions || ((call.model->list_mask >> cls) & 1u)))
+      score.top.push(calitas_top_hit_t{one, contig, (int32_t)coord[0], (int32_t)coord[1], (int8_t)(minus ? '-' : '+'), (uint8_t)v[0], (uint8_t)v[1], (uint8_t)v[2]}, (uint8_t)cls);
     return true;
   };
   for (size_t c = 0; c < ref.contigs.size(); c++) {

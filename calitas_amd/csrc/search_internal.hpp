@@ -185,7 +185,7 @@ int search_hits_sequential(calitas_ctx* ctx, const HitsCall& call, HitsOut& out)
 int search_counts_sequential(calitas_ctx* ctx, const HitsCall& call, HitsOut& out);
 // What the tails take of a plan's model (hits.hpp: ScoreCall): its words and the letter indices of the guide's positions.
 inline ScoreCall score_call(const ScoreModelHost& m, const GuideHost& gh) {
-  ScoreCall sc{m.words.data(), {0, 0}, m.top_k};
+  ScoreCall sc{m.words.data(), {0, 0}, m.top_k, m.regions ? m.regions_dev : RegionsView{}, m.list_mask};
   for (size_t i = 0; i < gh.protospacer.size() && i < 32; i++) sc.letters[i >> 4] |= (uint64_t)score_letter_index(gh.protospacer[i]) << ((i & 15) * 4);
   return sc;
 }

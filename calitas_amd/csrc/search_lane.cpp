@@ -211,7 +211,7 @@ bool binned_possible(calitas_ctx* lane, const SearchPlan& pl) {
   }
   if (!want) return false;
   if (pl.p.max_overlap < 1 || own->ref.contigs.size() >= (1u << 18) - 1) return false;
-  if (pl.model && pl.model->top_k && (uint64_t)pl.n_bins * BIN_ROWS > 0x7FFFFFFEull) return false;   // (a top call: more ranks than a key holds)
+  if (pl.model && (pl.model->top_k || pl.model->regions) && (uint64_t)pl.n_bins * BIN_ROWS > 0x7FFFFFFEull) return false;   // (a top call: more ranks than a key holds)
   return true;
 }
 
@@ -353,13 +353,21 @@ static int lane_rows_binned(calitas_ctx* lane, const SearchPlan& pl, bool prelau
   uint64_t bytes = (uint64_t)lane->mbox.host[BIN_BOX_BYTES] | ((uint64_t)lane->mbox.host[BIN_BOX_BYTES + 1] << 32);
   if (pl.counts) {                                           // the table arrived ahead of the post
     const uint64_t* table = binned_counts_table(lane->hits);
-    lt.counts.assign(table, table + pl.cshape.cells());
+    const bool regions = pl.model && pl.model->regions;
+    const uint32_t n_classes = regions ? pl.model->regions->n_classes : 1u;
+    ScoreWords rw;                                           // a regions call: the classes' tables, folded into the one every call returns
+    if (!regions) lt.counts.assign(table, table + pl.cshape.cells());
+    else if (!regions_from_words(table, pl.cshape.cells(), n_classes, pl.model->top_k, lt.counts, rw))
+      return fail(lane, CALITAS_EHIP, "binned regions kernel: a class's table does not add up to its hits (internal error)");
     uint64_t sum = 0;
     for (uint64_t v : lt.counts) sum += v;
     if (sum != lane->mbox.host[BIN_BOX_ROWS]) return fail(lane, CALITAS_EHIP, "binned counts kernel: the table does not add up to the bins' kept hits (internal error)");
-    if (pl.model) {                                          // ... and so did the four words behind its cells
+    if (regions) {
+      lt.score = rw;
+      if (table[(size_t)pl.cshape.cells() * n_classes + 3] != sum) return fail(lane, CALITAS_EHIP, "binned regions kernel: the hits it scored are not the hits it counted (internal error)");
+    } else if (pl.model) {                                   // ... and so did the four words behind its cells
       const uint64_t* w = table + pl.cshape.cells();
-      lt.score = ScoreWords{w[0], w[1], w[2], TopList()};
+      lt.score = ScoreWords{w[0], w[1], w[2], TopList(), RegionWords()};
       if (pl.model->top_k) lt.score.top = top_from_words(w + SCORE_WORDS, pl.model->top_k);
       if (w[3] != sum) return fail(lane, CALITAS_EHIP, "binned scores kernel: the hits it scored are not the hits it counted (internal error)");
     }
@@ -484,13 +492,21 @@ int lane_rows(calitas_ctx* lane, const SearchPlan& pl, bool prelaunched, const R
       kernel_times(lane, lt.tm);          // while out_kernel runs
       if (pl.counts && (res.flags & HITS_FLAG_EXTENT)) return fail(lane, CALITAS_EHIP, "a hit lies outside the extents of the counts table (internal error)");
       if (res.flags == 0 && pl.counts) {
-        lt.counts.assign(res.counts, res.counts + pl.cshape.cells());
+        const bool regions = pl.model && pl.model->regions;
+        const uint32_t n_classes = regions ? pl.model->regions->n_classes : 1u;
+        ScoreWords rw;
+        if (!regions) lt.counts.assign(res.counts, res.counts + pl.cshape.cells());
+        else if (!regions_from_words(res.counts, pl.cshape.cells(), n_classes, pl.model->top_k, lt.counts, rw))
+          return fail(lane, CALITAS_EHIP, "regions kernel: a class's table does not add up to its hits (internal error)");
         uint64_t sum = 0;
         for (uint64_t v : lt.counts) sum += v;
         if (sum != res.n_rows) return fail(lane, CALITAS_EHIP, "counts kernel: the table does not add up to the kept hits (internal error)");
-        if (pl.model) {
+        if (regions) {
+          lt.score = rw;
+          if (res.counts[(size_t)pl.cshape.cells() * n_classes + 3] != sum) return fail(lane, CALITAS_EHIP, "regions kernel: the hits it scored are not the hits it counted (internal error)");
+        } else if (pl.model) {
           const uint64_t* w = res.counts + pl.cshape.cells();
-          lt.score = ScoreWords{w[0], w[1], w[2], TopList()};
+          lt.score = ScoreWords{w[0], w[1], w[2], TopList(), RegionWords()};
           if (pl.model->top_k) lt.score.top = top_from_words(w + SCORE_WORDS, pl.model->top_k);
           if (w[3] != sum) return fail(lane, CALITAS_EHIP, "scores kernel: the hits it scored are not the hits it counted (internal error)");
         }
@@ -521,7 +537,10 @@ int lane_rows(calitas_ctx* lane, const SearchPlan& pl, bool prelaunched, const R
   if (pl.counts) {                                           // the host stage of calitas_hits_counts
     lt.counts.assign(pl.cshape.cells(), 0);
     lt.score.top.k = pl.model ? pl.model->top_k : 0;
-    const std::string e = pl.model ? hits_top(ref, gh, p, *pl.model, alns, n_alns, pl.cshape.n_mm, pl.cshape.n_gaps, pl.cshape.n_pam, lt.counts.data(), &rows,
+    const std::string e = pl.model && pl.model->regions
+                              ? hits_regions(ref, gh, p, *pl.model, alns, n_alns, pl.cshape.n_mm, pl.cshape.n_gaps, pl.cshape.n_pam, lt.counts.data(), &rows,
+                                             &lt.score.perfect, &lt.score.sum_q32, &lt.score.max_q32, &lt.score.top, &lt.score.reg, own->pool)
+                          : pl.model ? hits_top(ref, gh, p, *pl.model, alns, n_alns, pl.cshape.n_mm, pl.cshape.n_gaps, pl.cshape.n_pam, lt.counts.data(), &rows,
                                               &lt.score.perfect, &lt.score.sum_q32, &lt.score.max_q32, &lt.score.top, own->pool)
                                    : hits_counts(ref, gh, p, alns, n_alns, pl.cshape.n_mm, pl.cshape.n_gaps, pl.cshape.n_pam, lt.counts.data(), &rows, own->pool);
     calitas_free(alns);

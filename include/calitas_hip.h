@@ -388,6 +388,47 @@ int calitas_search_top(calitas_ctx* ctx, const calitas_guide_t* guide, const cal
 int calitas_search_top_batch(calitas_ctx* ctx, int32_t n_guides, const calitas_guide_t* guides, const calitas_params_t* params,
                              const calitas_score_model_t* model, uint32_t k, calitas_top_t** out);
 
+/* A guide's scores and top list split by annotated regions.  No reference counterpart.
+ * calitas_set_regions gives the context a set of intervals, each with a class 1 .. n_classes - 1 (2 <= n_classes <=
+ * CALITAS_REGION_CLASSES_MAX); [start, end) is 0-based and half-open in the contig's coordinates, like BED.  Intervals come in any
+ * order and may overlap or nest.  n == 0 clears the set; calitas_set_reference* and calitas_load_index clear it too.  Works on a
+ * host-only context.  CALITAS_EINVAL for a bad contig index, start >= end, an end beyond the contig, an interval on an absent contig
+ * and a class out of range.  The set is flattened once here and brought to the device once, not per call.
+ *
+ * The class of a hit is defined on its hits.txt row: the hit occupies [coordinate_start, coordinate_end) of its chromosome (the
+ * protospacer, as those two columns give it; half-open), and its class is the smallest cls among the intervals of that contig with
+ * start < coordinate_end && end > coordinate_start -- 0 ("elsewhere") when there is none or the extent is empty.  Every hit has
+ * exactly one class. */
+#define CALITAS_REGION_CLASSES_MAX 8
+typedef struct {
+  int32_t contig_index;
+  int32_t start, end;
+  uint32_t cls;
+} calitas_region_t;
+int calitas_set_regions(calitas_ctx* ctx, uint64_t n, const calitas_region_t* iv, uint32_t n_classes);
+
+typedef struct {
+  calitas_top_t top;           /* top.scores: exactly what calitas_search_scores returns for the same arguments; top.hits: the
+                                  n = min(k, candidates) best imperfect hits whose class has its bit set in list_mask, in the order
+                                  of the calitas_top_t contract (score descending, then the earlier row) */
+  uint8_t* hit_class;          /* top.n bytes: the class of every record */
+  uint32_t n_classes;
+  uint32_t list_mask;          /* as asked */
+  calitas_scores_t* by_class;  /* n_classes entries: rows, perfect, sum_q32, max_q32 and an own counts table, of the hits of that class */
+} calitas_regions_t;           /* one block: one calitas_free */
+
+/* calitas_search_top split by the context's regions, with the rules of calitas_search_top (the whole reference, chrom_index, a
+ * window range with ownership).  k is 0 .. CALITAS_TOP_MAX; k == 0 means no list.  With k > 0 a list_mask without a bit below
+ * n_classes is CALITAS_EINVAL; higher bits are ignored.  CALITAS_EINVAL when the context has no regions and for everything
+ * calitas_search_top refuses.  Invariants: the by_class entries sum, field by field and cell by cell, to top.scores (max_q32 is their
+ * maximum); with every bit set in list_mask, top equals calitas_search_top's result.  Across consecutive pieces of a job by_class
+ * adds (max_q32 takes the maximum) and the lists merge stably as calitas_top_t's do; hit_class travels with its records.  The class
+ * lookup and the selection run in the lanes that score the hits (regions_kernel / bin_regions_kernel). */
+int calitas_search_regions(calitas_ctx* ctx, const calitas_guide_t* guide, const calitas_params_t* params, const calitas_score_model_t* model,
+                           uint32_t k, uint32_t list_mask, calitas_regions_t** out);
+int calitas_search_regions_batch(calitas_ctx* ctx, int32_t n_guides, const calitas_guide_t* guides, const calitas_params_t* params,
+                                 const calitas_score_model_t* model, uint32_t k, uint32_t list_mask, calitas_regions_t** out);
+
 /* SequentialGuideAligner.align on explicit (guide, target) pairs -- the per-task call of PairwiseAlignSequences
  * (PairwiseAlignSequences.scala:64 -> alignBest, SequentialGuideAligner.scala:333-345) and AlignToReference
  * (AlignToReference.scala:114-135 -> alignToRef / alignToRefBest, SequentialGuideAligner.scala:359-418).  Task t aligns
@@ -433,6 +474,13 @@ int calitas_hits_scores(const calitas_ctx* ctx, const calitas_guide_t* guide, co
  * kept hits in the order of the calitas_top_t contract -- the host stage calitas_search_top falls back to; works on a host-only context. */
 int calitas_hits_top(const calitas_ctx* ctx, const calitas_guide_t* guide, const calitas_params_t* params, const calitas_score_model_t* model,
                      uint32_t k, const calitas_aln_t* alns, uint64_t n_alns, calitas_top_t** out);
+
+/* The twin of calitas_hits_top for calitas_search_regions -- the host stage it falls back to (CALITAS_HOST_HITS=1, -O 0, a declined
+ * device stage); works on a host-only context.  No reference counterpart. */
+int calitas_hits_regions(const calitas_ctx* ctx, const calitas_guide_t* guide, const calitas_params_t* params, const calitas_score_model_t* model,
+                         uint32_t k, uint32_t list_mask, const calitas_aln_t* alns, uint64_t n_alns, calitas_regions_t** out);
+/* (test hook) The class the context's flattened regions give the extent [start, end) of a contig, or -1 without regions / for a bad contig. */
+int calitas_region_class(const calitas_ctx* ctx, int32_t contig_index, int64_t start, int64_t end);
 
 /* A hit row built by the caller -- the variant branch of SearchReference.execute (SearchReference.scala:570-630) builds its
  * ReferenceHits from variant windows on the host.  calitas_hits_tsv_ext lets such hits take part in removeOverlaps (grouped by
