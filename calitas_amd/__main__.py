@@ -84,6 +84,11 @@ def main(argv=None):
                     help="search every distinct guide of the table (the flags below) and add hits, hits_mm0 .. hits_mmE per row")
     fg.add_argument("--scores", metavar="MODEL",
                     help="like --counts, and score every guide's hits under the model file: the columns perfect and specificity follow")
+    fg.add_argument("--gc-min", metavar="PCT", type=int, help="keep guides whose protospacer has at least PCT percent G + C (0 .. 100)")
+    fg.add_argument("--gc-max", metavar="PCT", type=int, help="... and at most PCT percent")
+    fg.add_argument("--max-run", metavar="SPEC", help="the longest run of one base a protospacer may hold: N, or T=3,G=4 (unnamed bases unlimited)")
+    fg.add_argument("--avoid", metavar="MOTIF", action="append", default=[],
+                    help="drop guides whose protospacer holds this IUPAC motif or its reverse complement (repeatable; 8 motifs in all)")
     fg.add_argument("-d", "--max-guide-diffs", type=int, default=Defaults.MaxGuideDiffs)
     fg.add_argument("-p", "--max-pam-mismatches", type=int, default=Defaults.MaxPamMismatches)
     fg.add_argument("-g", "--max-gaps-between-guide-and-pam", type=int, default=Defaults.MaxGapsBetweenGuideAndPam)
@@ -130,7 +135,7 @@ def main(argv=None):
             sys.stdout.write(text)
     elif a.tool == "FindGuides":
         text = find_guides_tool(a.ref, a.guide, a.auxiliary_pams, chrom=a.chrom, start=a.start, end=a.end, output=a.output, counts=a.counts, scores=a.scores,
-                                device=a.device, max_guide_diffs=a.max_guide_diffs, max_pam_mismatches=a.max_pam_mismatches,
+                                device=a.device, gc_min=a.gc_min, gc_max=a.gc_max, max_run=a.max_run, avoid=a.avoid, max_guide_diffs=a.max_guide_diffs, max_pam_mismatches=a.max_pam_mismatches,
                                 max_gaps_between_guide_and_pam=a.max_gaps_between_guide_and_pam, max_total_diffs=a.max_total_diffs,
                                 max_overlap=a.max_overlap, guide_mismatch_net_cost=a.guide_mismatch_net_cost,
                                 pam_mismatch_net_cost=a.pam_mismatch_net_cost, genome_gap_net_cost=a.genome_gap_net_cost,

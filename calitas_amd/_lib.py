@@ -86,6 +86,11 @@ class TopT(ctypes.Structure):
     _fields_ = [("scores", ScoresT), ("k", ctypes.c_uint32), ("n", ctypes.c_uint32), ("hits", ctypes.POINTER(TopHitT))]
 
 
+class SiteFilterT(ctypes.Structure):
+    _fields_ = [("gc_min", ctypes.c_uint8), ("gc_max", ctypes.c_uint8), ("max_run", ctypes.c_uint8 * 4), ("n_motifs", ctypes.c_uint8),
+                ("reserved", ctypes.c_uint8), ("motifs", (ctypes.c_char * 16) * 8)]
+
+
 class RegionT(ctypes.Structure):
     _fields_ = [("contig_index", ctypes.c_int32), ("start", ctypes.c_int32), ("end", ctypes.c_int32), ("cls", ctypes.c_uint32)]
 
@@ -108,7 +113,8 @@ SYMBOLS = ["calitas_create", "calitas_destroy", "calitas_last_error", "calitas_f
            "calitas_search_scores", "calitas_search_scores_batch", "calitas_hits_scores",
            "calitas_search_top", "calitas_search_top_batch", "calitas_hits_top",
            "calitas_set_regions", "calitas_search_regions", "calitas_search_regions_batch", "calitas_hits_regions", "calitas_region_class",
-           "calitas_find_sites", "calitas_count_sites", "calitas_find_sites_host"]
+           "calitas_find_sites", "calitas_count_sites", "calitas_find_sites_host",
+           "calitas_find_sites_filtered", "calitas_count_sites_filtered", "calitas_find_sites_filtered_host"]
 
 if not os.path.exists(LIB_PATH):
     raise ImportError("%s is missing: build it with `make -C calitas_amd/csrc` (hipcc, gfx950). "
@@ -172,6 +178,11 @@ lib.calitas_find_sites.argtypes = [ctypes.c_void_p, ctypes.POINTER(GuideT), ctyp
 lib.calitas_find_sites_host.argtypes = lib.calitas_find_sites.argtypes
 lib.calitas_count_sites.argtypes = [ctypes.c_void_p, ctypes.POINTER(GuideT), ctypes.c_int32, ctypes.c_uint64, ctypes.c_uint64,
                                     ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]
+lib.calitas_find_sites_filtered.argtypes = [ctypes.c_void_p, ctypes.POINTER(GuideT), ctypes.POINTER(SiteFilterT), ctypes.c_int32, ctypes.c_uint64,
+                                            ctypes.c_uint64, ctypes.POINTER(ctypes.POINTER(SiteT)), ctypes.POINTER(ctypes.c_uint64)]
+lib.calitas_find_sites_filtered_host.argtypes = lib.calitas_find_sites_filtered.argtypes
+lib.calitas_count_sites_filtered.argtypes = [ctypes.c_void_p, ctypes.POINTER(GuideT), ctypes.POINTER(SiteFilterT), ctypes.c_int32, ctypes.c_uint64,
+                                             ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]
 lib.calitas_search_scores.argtypes = [ctypes.c_void_p, ctypes.POINTER(GuideT), ctypes.POINTER(ParamsT), ctypes.POINTER(ScoreModelT),
                                       ctypes.POINTER(ctypes.POINTER(ScoresT))]
 lib.calitas_search_scores_batch.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.POINTER(GuideT), ctypes.POINTER(ParamsT),

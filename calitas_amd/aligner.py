@@ -11,7 +11,7 @@ import ctypes
 import time
 
 from . import _lib
-from ._lib import AlnT, CalitasError, CountsT, GuideT, ParamsT, RegionsT, RegionT, ScoreModelT, ScoresT, SiteT, TimingT, TopT, lib
+from ._lib import AlnT, CalitasError, CountsT, GuideT, ParamsT, RegionsT, RegionT, ScoreModelT, ScoresT, SiteFilterT, SiteT, TimingT, TopT, lib
 
 
 class Defaults:  # SequentialGuideAligner.scala:17-28
@@ -504,18 +504,25 @@ class Context:
             index = int(chrom)
         return pattern, index, int(start), 0 if end is None else int(end)
 
-    def find_sites(self, pattern, chrom=None, start=0, end=None, host=False):
+    def find_sites(self, pattern, chrom=None, start=0, end=None, host=False, filter=None):
         """calitas_find_sites: every place of the region where a guide of the IUPAC `pattern` (a Guide or its `-i` string, e.g.
         "NNNNNNNNNNNNNNNNNNNNnrg"; aux PAMs through Guide(..., aux)) can be cut out, as a numpy structured array with the fields of
         calitas_site_t (SITE_DTYPE; strand as the byte b'+' / b'-'), sorted by contig, protospacer start, '+' before '-'.  chrom: a
         name, an index or None (every contig); [start, end) in 0-based contig coordinates, end None: the contig's end.  host=True: the
-        host twin (calitas_find_sites_host), which also works on a host-only context."""
+        host twin (calitas_find_sites_host), which also works on a host-only context.  filter: a SiteFilter -- only the sites whose
+        protospacer passes it (calitas_find_sites_filtered, on the device inside the same kernel); None: the unfiltered entry points."""
         import numpy as np
         pattern, index, start, end = self._site_region(pattern, chrom, start, end)
         g = pattern.to_c()
         out, n = ctypes.POINTER(SiteT)(), ctypes.c_uint64()
-        fn = lib.calitas_find_sites_host if host else lib.calitas_find_sites
-        _lib.check(self._h, fn(self._h, ctypes.byref(g), index, start, end, ctypes.byref(out), ctypes.byref(n)))
+        if filter is None:
+            fn = lib.calitas_find_sites_host if host else lib.calitas_find_sites
+            rc = fn(self._h, ctypes.byref(g), index, start, end, ctypes.byref(out), ctypes.byref(n))
+        else:
+            f = filter.to_c()
+            fn = lib.calitas_find_sites_filtered_host if host else lib.calitas_find_sites_filtered
+            rc = fn(self._h, ctypes.byref(g), ctypes.byref(f), index, start, end, ctypes.byref(out), ctypes.byref(n))
+        _lib.check(self._h, rc)
         try:
             if n.value == 0:
                 return np.zeros(0, dtype=SITE_DTYPE)
@@ -524,16 +531,22 @@ class Context:
         finally:
             lib.calitas_free(out)
 
-    def count_sites(self, pattern, chrom=None, start=0, end=None):
+    def count_sites(self, pattern, chrom=None, start=0, end=None, filter=None):
         """calitas_count_sites: (total, per_contig_strand) -- the number of sites find_sites would list and a numpy uint64 array
-        [n_contigs][2] ('+' first) of them, from the kernel's first pass alone: no record is written or copied."""
+        [n_contigs][2] ('+' first) of them, from the kernel's first pass alone: no record is written or copied.  filter: as in
+        find_sites (calitas_count_sites_filtered)."""
         import numpy as np
         pattern, index, start, end = self._site_region(pattern, chrom, start, end)
         g = pattern.to_c()
         table = np.zeros((max(1, len(self.contig_names)), 2), dtype=np.uint64)
         n = ctypes.c_uint64()
-        _lib.check(self._h, lib.calitas_count_sites(self._h, ctypes.byref(g), index, start, end,
-                                                    table.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), ctypes.byref(n)))
+        cells = table.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64))
+        if filter is None:
+            rc = lib.calitas_count_sites(self._h, ctypes.byref(g), index, start, end, cells, ctypes.byref(n))
+        else:
+            f = filter.to_c()
+            rc = lib.calitas_count_sites_filtered(self._h, ctypes.byref(g), ctypes.byref(f), index, start, end, cells, ctypes.byref(n))
+        _lib.check(self._h, rc)
         return n.value, table[:len(self.contig_names)]
 
     @staticmethod
@@ -912,6 +925,65 @@ class SearchReference:
 # calitas_site_t as a numpy record
 SITE_DTYPE = [("contig_index", "<i4"), ("protospacer_start", "<i4"), ("pam_start", "<i4"), ("strand", "S1"), ("pam_index", "i1"),
               ("pam_length", "u1"), ("protospacer_length", "u1")]
+
+_IUPAC_COMPLEMENT = str.maketrans("ACGTUMRWSYKVHDBN", "TGCAAKYWSRMBDHVN")
+
+
+def iupac_revcomp(motif):
+    """The reverse complement of an IUPAC string, upper case."""
+    return motif.upper().translate(_IUPAC_COMPLEMENT)[::-1]
+
+
+class SiteFilter:
+    """calitas_site_filter_t: which sites of a pattern are guides worth ordering, decided on the protospacer as it reads on the site's
+    strand.  gc_min / gc_max: bounds on the NUMBER of G and C (SiteFilter.percent turns percentages into them; a gc_max above the
+    length means the length); max_run: the longest run allowed, an int for all four bases, or a dict by base / a 4-sequence in ACGT order
+    (0: no limit); avoid: IUPAC motifs (at most 8, 1 .. 16 letters) none of which may occur -- in the orientation given: add
+    iupac_revcomp(m) to avoid both."""
+
+    def __init__(self, gc_min=0, gc_max=255, max_run=0, avoid=()):
+        self.gc_min, self.gc_max = int(gc_min), int(gc_max)
+        if isinstance(max_run, dict):
+            unknown = set(k.upper() for k in max_run) - set("ACGT")
+            if unknown:
+                raise ValueError("max_run: not a base: %s" % ", ".join(sorted(unknown)))
+            upper = {k.upper(): v for k, v in max_run.items()}
+            self.max_run = tuple(int(upper.get(b, 0)) for b in "ACGT")
+        elif isinstance(max_run, int):
+            self.max_run = (max_run,) * 4
+        else:
+            self.max_run = tuple(int(x) for x in max_run)
+            if len(self.max_run) != 4:
+                raise ValueError("max_run: four limits, for A C G T")
+        self.avoid = (avoid,) if isinstance(avoid, str) else tuple(avoid)
+        for v in (self.gc_min, self.gc_max) + self.max_run:
+            if not 0 <= v <= 255:
+                raise ValueError("a site filter's numbers are 0 .. 255")
+
+    @staticmethod
+    def percent(L, lo, hi):
+        """(gc_min, gc_max) for a protospacer of L bases whose G + C share lies in [lo, hi] percent (integers): ceil(lo L / 100),
+        floor(hi L / 100)."""
+        return -((-int(lo) * L) // 100), (int(hi) * L) // 100
+
+    def to_c(self):
+        f = SiteFilterT()                                  # (zeroed)
+        f.gc_min, f.gc_max = self.gc_min, self.gc_max
+        for i, r in enumerate(self.max_run):
+            f.max_run[i] = r
+        if len(self.avoid) > 8:
+            raise ValueError("a site filter takes at most 8 motifs, not %d" % len(self.avoid))
+        f.n_motifs = len(self.avoid)
+        for i, m in enumerate(self.avoid):
+            raw = m.encode()
+            if len(raw) > 16 or b"\0" in raw:
+                raise ValueError("a motif of a site filter has at most 16 letters: %s" % m)
+            f.motifs[i].value = raw                        # (the library checks the letters)
+        return f
+
+    def __repr__(self):
+        return "SiteFilter(gc_min=%d, gc_max=%d, max_run=%r, avoid=%r)" % (self.gc_min, self.gc_max, self.max_run, self.avoid)
+
 
 COUNTS_COLUMNS = ("guide_id", "strand", "guide_mm", "guide_gaps", "pam_mm", "hits")
 

@@ -779,31 +779,46 @@ int calitas_search_counts_batch(calitas_ctx* ctx, int32_t n_guides, const calita
   return rc;
 }
 
-// Guide sites (sites_host.cpp): no reference counterpart.
-int calitas_find_sites(calitas_ctx* ctx, const calitas_guide_t* pattern, int32_t chrom_index, uint64_t start, uint64_t end,
-                       calitas_site_t** sites, uint64_t* n_sites) {
+// Guide sites (sites_host.cpp): no reference counterpart.  The unfiltered calls are the filtered ones without a filter.
+int calitas_find_sites_filtered(calitas_ctx* ctx, const calitas_guide_t* pattern, const calitas_site_filter_t* filter, int32_t chrom_index,
+                                uint64_t start, uint64_t end, calitas_site_t** sites, uint64_t* n_sites) {
   if (!ctx) return CALITAS_EINVAL;
   if (!pattern || !n_sites) return fail(ctx, CALITAS_EINVAL, "NULL argument");
   *n_sites = 0;
   if (sites) *sites = nullptr;
-  return calitas_find_sites_impl(ctx, pattern, chrom_index, start, end, sites != nullptr, sites, nullptr, n_sites);
+  return calitas_find_sites_impl(ctx, pattern, filter, chrom_index, start, end, sites != nullptr, sites, nullptr, n_sites);
 }
 
-int calitas_count_sites(calitas_ctx* ctx, const calitas_guide_t* pattern, int32_t chrom_index, uint64_t start, uint64_t end,
-                        uint64_t* per_contig_strand, uint64_t* n_sites) {
+int calitas_count_sites_filtered(calitas_ctx* ctx, const calitas_guide_t* pattern, const calitas_site_filter_t* filter, int32_t chrom_index,
+                                 uint64_t start, uint64_t end, uint64_t* per_contig_strand, uint64_t* n_sites) {
   if (!ctx) return CALITAS_EINVAL;
   if (!pattern || !n_sites) return fail(ctx, CALITAS_EINVAL, "NULL argument");
   *n_sites = 0;
-  return calitas_find_sites_impl(ctx, pattern, chrom_index, start, end, false, nullptr, per_contig_strand, n_sites);
+  return calitas_find_sites_impl(ctx, pattern, filter, chrom_index, start, end, false, nullptr, per_contig_strand, n_sites);
 }
 
-int calitas_find_sites_host(const calitas_ctx* ctx, const calitas_guide_t* pattern, int32_t chrom_index, uint64_t start, uint64_t end,
-                            calitas_site_t** sites, uint64_t* n_sites) {
+int calitas_find_sites_filtered_host(const calitas_ctx* ctx, const calitas_guide_t* pattern, const calitas_site_filter_t* filter,
+                                     int32_t chrom_index, uint64_t start, uint64_t end, calitas_site_t** sites, uint64_t* n_sites) {
   if (!ctx) return CALITAS_EINVAL;
   if (!pattern || !n_sites) return fail(const_cast<calitas_ctx*>(ctx), CALITAS_EINVAL, "NULL argument");
   *n_sites = 0;
   if (sites) *sites = nullptr;
-  return calitas_find_sites_host_impl(ctx, pattern, chrom_index, start, end, sites, n_sites);
+  return calitas_find_sites_host_impl(ctx, pattern, filter, chrom_index, start, end, sites, n_sites);
+}
+
+int calitas_find_sites(calitas_ctx* ctx, const calitas_guide_t* pattern, int32_t chrom_index, uint64_t start, uint64_t end,
+                       calitas_site_t** sites, uint64_t* n_sites) {
+  return calitas_find_sites_filtered(ctx, pattern, nullptr, chrom_index, start, end, sites, n_sites);
+}
+
+int calitas_count_sites(calitas_ctx* ctx, const calitas_guide_t* pattern, int32_t chrom_index, uint64_t start, uint64_t end,
+                        uint64_t* per_contig_strand, uint64_t* n_sites) {
+  return calitas_count_sites_filtered(ctx, pattern, nullptr, chrom_index, start, end, per_contig_strand, n_sites);
+}
+
+int calitas_find_sites_host(const calitas_ctx* ctx, const calitas_guide_t* pattern, int32_t chrom_index, uint64_t start, uint64_t end,
+                            calitas_site_t** sites, uint64_t* n_sites) {
+  return calitas_find_sites_filtered_host(ctx, pattern, nullptr, chrom_index, start, end, sites, n_sites);
 }
 
 // A guide's scores as the ABI hands them over: struct, table and cells in one block of the library's.

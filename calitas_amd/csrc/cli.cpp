@@ -27,6 +27,8 @@ static void usage() {
     "          table follows behind an empty line)]\n"
     "         [--device N]\n"
     "       calitas FindGuides -i PATTERNpam -r ref.fa [-x aux-pam ...] [-c chrom] [-s start=0] [-e end] [-o guides.tsv]\n"
+    "         [--gc-min PCT] [--gc-max PCT (G + C of the protospacer, percent)] [--max-run N | T=3,G=4 (longest run of a base)]\n"
+    "         [--avoid MOTIF ... (IUPAC; with its reverse complement, 8 motifs in all)]\n"
     "         [--device N (-1: the host twin, no GPU)]\n");
 }
 
@@ -210,11 +212,57 @@ static bool class_mask(const std::vector<std::string>& classes, const std::strin
   return true;
 }
 
+// --gc-min / --gc-max / --max-run / --avoid as a calitas_site_filter_t for a protospacer of L bases (calitas_amd/tools.py
+// site_filter_of_flags: the same numbers, the same motifs in the same order).
+static bool site_filter_of_flags(int L, int gc_lo, int gc_hi, bool limited, const std::string& max_run, const std::vector<std::string>& avoid, calitas_site_filter_t& f,
+                                 std::string& err) {
+  std::memset(&f, 0, sizeof f);
+  if (gc_lo < 0 || gc_lo > 100 || gc_hi < 0 || gc_hi > 100) { err = "--gc-min and --gc-max are percentages, 0 .. 100"; return false; }
+  f.gc_min = (uint8_t)((gc_lo * L + 99) / 100);
+  f.gc_max = (uint8_t)(gc_hi * L / 100);
+  for (size_t a = 0; limited && a <= max_run.size();) {
+    size_t t = max_run.find(',', a);
+    if (t == std::string::npos) t = max_run.size();
+    std::string part = max_run.substr(a, t - a);
+    a = t + 1;
+    while (!part.empty() && part.front() == ' ') part.erase(0, 1);
+    while (!part.empty() && part.back() == ' ') part.pop_back();
+    const size_t eq = part.rfind('=');
+    const std::string n = eq == std::string::npos ? part : part.substr(eq + 1);
+    const char* at = eq == 1 ? std::strchr("ACGT", std::toupper((unsigned char)part[0])) : nullptr;
+    const size_t nz = n.find_first_not_of('0');               // (leading zeros are digits, as int() has it)
+    if (n.empty() || n.find_first_not_of("0123456789") != std::string::npos || (nz != std::string::npos && n.size() - nz > 3) || std::atoi(n.c_str()) > 255 ||
+        (eq != std::string::npos && !(at && *at))) { err = "--max-run takes N or BASE=N,... (A C G T; 0 .. 255), not " + max_run; return false; }
+    if (eq == std::string::npos) for (int b = 0; b < 4; b++) f.max_run[b] = (uint8_t)std::atoi(n.c_str());
+    else f.max_run[at - "ACGT"] = (uint8_t)std::atoi(n.c_str());
+  }
+  std::vector<std::string> motifs;
+  for (const std::string& m : avoid) {
+    std::string up = m, rc;
+    for (auto& c : up) c = (char)std::toupper((unsigned char)c);
+    for (size_t i = up.size(); i-- > 0;) {
+      const char* from = "ACGTUMRWSYKVHDBN";
+      const char* to = "TGCAAKYWSRMBDHVN";
+      const char* p = std::strchr(from, up[i]);
+      rc += (p && *p) ? to[p - from] : up[i];
+    }
+    for (const std::string& x : {up, rc}) if (std::find(motifs.begin(), motifs.end(), x) == motifs.end()) motifs.push_back(x);
+  }
+  if (motifs.size() > 8) { err = "--avoid: more than 8 motifs once the reverse complements are added"; return false; }
+  f.n_motifs = (uint8_t)motifs.size();
+  for (size_t i = 0; i < motifs.size(); i++) {
+    if (motifs[i].size() > 16) { err = "a motif of a site filter has at most 16 letters: " + motifs[i]; return false; }
+    std::memcpy(f.motifs[i], motifs[i].data(), motifs[i].size());
+  }
+  return true;
+}
+
 static int find_guides_main(int argc, char** argv) {
-  std::string pattern, ref, output, chrom;
-  std::vector<std::string> aux;
+  std::string pattern, ref, output, chrom, max_run;
+  std::vector<std::string> aux, avoid;
   uint64_t start = 0, end = 0;
-  int device = 0;
+  int device = 0, gc_lo = 0, gc_hi = 100;
+  bool filtered = false, limited = false;
   for (int i = 2; i < argc; i++) {
     std::string a = argv[i], val;
     size_t eq = a.find('=');
@@ -233,12 +281,23 @@ static int find_guides_main(int argc, char** argv) {
     else if (a == "-e" || a == "--end") end = std::strtoull(next().c_str(), nullptr, 10);
     else if (a == "-x") { aux.push_back(next()); while (i + 1 < argc && argv[i + 1][0] != '-') aux.push_back(argv[++i]); }
     else if (a == "--device") device = std::atoi(next().c_str());
+    else if (a == "--gc-min") { gc_lo = std::atoi(next().c_str()); filtered = true; }
+    else if (a == "--gc-max") { gc_hi = std::atoi(next().c_str()); filtered = true; }
+    else if (a == "--max-run") { max_run = next(); filtered = limited = true; }
+    else if (a == "--avoid") { avoid.push_back(next()); filtered = true; }
     else { std::fprintf(stderr, "unknown argument %s\n", a.c_str()); usage(); return 2; }
   }
   if (pattern.empty() || ref.empty()) { usage(); return 2; }
   ParsedGuide pg;
   if (int rc = parse_guide(pattern, aux, pg)) return rc;
   calitas_guide_t g = pg.c_guide();
+  calitas_site_filter_t filter;
+  std::string filter_err;
+  if (filtered && !site_filter_of_flags((int)pg.proto.size(), gc_lo, gc_hi, limited, max_run, avoid, filter, filter_err)) {
+    std::fprintf(stderr, "calitas: %s\n", filter_err.c_str());
+    return 2;
+  }
+  const calitas_site_filter_t* keep = filtered ? &filter : nullptr;
   calitas_ctx* ctx = nullptr;
   if (calitas_create(device, &ctx) != CALITAS_OK) { std::fprintf(stderr, "calitas: %s\n", calitas_last_error(nullptr)); return 1; }
   auto die = [&](const char* what) { std::fprintf(stderr, "calitas: %s: %s\n", what, calitas_last_error(ctx)); calitas_destroy(ctx); std::exit(1); };
@@ -250,8 +309,8 @@ static int find_guides_main(int argc, char** argv) {
     if (chrom_index < 0) { std::fprintf(stderr, "Unknown chromosome: %s\n", chrom.c_str()); calitas_destroy(ctx); return 1; }
   }
   calitas_site_t* sites = nullptr; uint64_t n_sites = 0;
-  const int rc = device < 0 ? calitas_find_sites_host(ctx, &g, chrom_index, start, end, &sites, &n_sites)
-                            : calitas_find_sites(ctx, &g, chrom_index, start, end, &sites, &n_sites);
+  const int rc = device < 0 ? calitas_find_sites_filtered_host(ctx, &g, keep, chrom_index, start, end, &sites, &n_sites)
+                            : calitas_find_sites_filtered(ctx, &g, keep, chrom_index, start, end, &sites, &n_sites);
   if (rc != CALITAS_OK) die("finding sites");
   FILE* f = output.empty() ? stdout : std::fopen(output.c_str(), "w");
   if (!f) { std::fprintf(stderr, "cannot write %s\n", output.c_str()); calitas_free(sites); calitas_destroy(ctx); return 1; }

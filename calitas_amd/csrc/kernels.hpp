@@ -115,6 +115,24 @@ struct SitePatterns {
   int32_t pad;
   SitePattern p[MAX_PAMS][2];      // [PAM][strand: 0 '+', 1 '-']
 };
+// A site filter as the kernel reads it (calitas_site_filter_t after validation): everything about the protospacer as the
+// FORWARD text shows it, so that '-' needs no second set of planes -- a run limit sits at the complement's code, a motif is reverse
+// complemented.  It lives behind the patterns in one device block (SiteTables), which keeps SitesArgs what it is without a filter.
+struct SiteFilterDev {
+  int32_t gc_min, gc_max;          // bounds on the G + C count that can bind; 0 and >= proto_len otherwise
+  int32_t max_run[2][4];           // [strand][forward base code A C G T]: longest run allowed, 0: no limit (or one no protospacer can exceed)
+  int32_t n_motifs;                // distinct strings the forward text must not show: a motif on '+', its reverse complement on '-' --
+  int32_t pad;                     // one entry where the two coincide (a palindrome; a motif passed in both orientations), 16 at most
+  struct Motif {
+    int32_t len;                   // 1 .. 16, <= proto_len
+    uint32_t strands;              // bit 0: rejects on '+', bit 1: on '-'
+    uint32_t sets[2];              // four bits per offset 0 .. 15 from the occurrence's leftmost forward base, 15 for N and beyond len
+  } motif[16];
+};
+struct SiteTables {
+  SitePatterns pat;
+  SiteFilterDev filter;            // read by the FILTER instantiations only
+};
 struct SiteRecord {                // = calitas_site_t
   int32_t contig, proto_start, pam_start;
   int8_t strand, pam_index;
@@ -125,7 +143,7 @@ struct SitesArgs {
   const uint32_t* mask;
   const TileInfo* tiles;
   const ContigInfo* contigs;
-  const SitePatterns* pat;         // device memory
+  const SitePatterns* pat;         // device memory: the head of a SiteTables
   uint64_t n_words;                // 32-base words of the packed space
   uint64_t w0;                     // first word of the launch, a multiple of SITES_BLOCK_WORDS
   uint32_t n_segs;                 // segments of SITES_BLOCK_WORDS words from w0 on
@@ -139,9 +157,10 @@ struct SitesArgs {
   SiteRecord* out;                 // pass 2
   uint64_t out_capacity;
 };
-hipError_t launch_sites_count(const SitesArgs& a, hipStream_t stream);
+// filtered: a.pat's SiteTables holds a filter, and the match vectors are ANDed with it in both passes
+hipError_t launch_sites_count(const SitesArgs& a, bool filtered, hipStream_t stream);
 // wg_count[0 .. n) -> wg_offset[0 .. n], wg_offset[n] = the total
 hipError_t launch_sites_offsets(const uint32_t* wg_count, uint64_t* wg_offset, uint32_t n, hipStream_t stream);
-hipError_t launch_sites_write(const SitesArgs& a, hipStream_t stream);
+hipError_t launch_sites_write(const SitesArgs& a, bool filtered, hipStream_t stream);
 
 }  // namespace calitas

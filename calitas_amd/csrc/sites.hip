@@ -16,6 +16,8 @@
 // Output in order, without a sort and without a returning atomic: pass 1 stores one count per segment, a one-workgroup scan turns
 // the counts into offsets, pass 2 recomputes the vectors and every lane writes its records at offset + prefix (a DPP prefix sum per
 // wave, the waves' sums through LDS); the '+' and '-' record of one position are neighbours.
+// FILTER (calitas_find_sites_filtered): a keep vector per strand from the same registers -- G + C count, base runs and motifs of the
+// protospacer, chain positions 32 + j .. 32 + j + L - 1 -- ANDed into the match vectors in both passes (site_keep).
 #include <hip/hip_runtime.h>
 
 #include "common.hpp"
@@ -73,12 +75,163 @@ CAL_DEV uint32_t wave_inclusive_sum(uint32_t v) {
   return v;
 }
 
+typedef const __attribute__((address_space(4))) SiteFilterDev FilterConst;
+typedef const __attribute__((address_space(4))) SiteTables TablesConst;
+
+// ---- the site filter: keep vectors for the 32 starts of the lane's word from chain words 1 - 3 ----
+// A vector over chain positions 32 .. 95 is a pair (word 1, word 2).  Zeros come in at position 96: what a window reads from there is
+// wrong, and no protospacer that starts in word 1 reaches it (32 + 31 + L - 1 <= 94).
+
+// bit j: some / every bit of [j, j + n) is set (1 <= n <= 32, wave-uniform), by doubling; the last step's windows overlap
+template <bool ALL>
+CAL_DEV void window(uint32_t (&v)[2], int n) {
+  int len = 1;
+  while (len < n) {
+    const uint32_t by = (uint32_t)(2 * len <= n ? len : n - len);
+    const uint32_t m0 = __builtin_amdgcn_alignbit(v[1], v[0], by), m1 = v[1] >> by;
+    if (ALL) { v[0] &= m0; v[1] &= m1; } else { v[0] |= m0; v[1] |= m1; }
+    len += (int)by;
+  }
+}
+
+CAL_DEV uint32_t maj(uint32_t a, uint32_t b, uint32_t c) { return (a & b) | (c & (a ^ b)); }
+
+// Starts whose L bases hold between gc_min and gc_max G or C (the same on both strands).  The count is a bit-sliced number per start,
+// plane i = bit i: the counts over windows of 1, 2, 4, .. bases by adding a number to itself moved down, and the pieces that make L
+// added up as they come by.  Planes that cannot be set yet are constants the compiler drops.
+CAL_DEV uint32_t keep_gc(const uint32_t (&c_lo)[4], const uint32_t (&c_hi)[4], int L, int gc_min, int gc_max) {
+  uint32_t pw[6][2] = {{c_lo[1] ^ c_hi[1], c_lo[2] ^ c_hi[2]}, {0u, 0u}, {0u, 0u}, {0u, 0u}, {0u, 0u}, {0u, 0u}};   // C = 01, G = 10
+  uint32_t sum[6] = {0u, 0u, 0u, 0u, 0u, 0u};
+  uint32_t done = 0;                                           // bases in sum
+#pragma unroll
+  for (int k = 0; k < 6; k++) {
+    if (L & (1 << k)) {                                        // sum += the windows of 2^k that start `done` further on
+      uint32_t c = 0u;
+#pragma unroll
+      for (int i = 0; i < 6; i++) {
+        const uint32_t b = __builtin_amdgcn_alignbit(pw[i][1], pw[i][0], done), a = sum[i];
+        sum[i] = a ^ b ^ c;
+        c = maj(a, b, c);
+      }
+      done += 1u << k;
+    }
+    if ((L >> (k + 1)) == 0) break;
+    uint32_t c0 = 0u, c1 = 0u;
+#pragma unroll
+    for (int i = 0; i < 6; i++) {
+      const uint32_t a0 = pw[i][0], a1 = pw[i][1];
+      const uint32_t b0 = __builtin_amdgcn_alignbit(a1, a0, 1u << k), b1 = a1 >> (1u << k);
+      pw[i][0] = a0 ^ b0 ^ c0;  c0 = maj(a0, b0, c0);
+      pw[i][1] = a1 ^ b1 ^ c1;  c1 = maj(a1, b1, c1);
+    }
+  }
+  // sum >= gc_min and sum <= gc_max, from the low plane up: a plane decides unless it equals the bound's bit
+  uint32_t keep = 0xFFFFFFFFu;
+  if (gc_min > 0) {
+    uint32_t ge = 0xFFFFFFFFu;
+#pragma unroll
+    for (int i = 0; i < 6; i++) ge = ((gc_min >> i) & 1) ? (sum[i] & ge) : (sum[i] | ge);
+    keep &= ge;
+  }
+  if (gc_max < L) {
+    uint32_t le = 0xFFFFFFFFu;
+#pragma unroll
+    for (int i = 0; i < 6; i++) le = ((gc_max >> i) & 1) ? (~sum[i] | le) : (~sum[i] & le);
+    keep &= le;
+  }
+  return keep;
+}
+
+// Chain positions 32 .. 95 at which a run of R + 1 of the forward base `code` starts
+CAL_DEV void run_starts(int code, const uint32_t (&c_lo)[4], const uint32_t (&c_hi)[4], int R, uint32_t (&v)[2]) {
+#pragma unroll
+  for (int i = 0; i < 2; i++) v[i] = ((code & 1) ? c_lo[1 + i] : ~c_lo[1 + i]) & ((code & 2) ? c_hi[1 + i] : ~c_hi[1 + i]);
+  window<true>(v, R + 1);
+}
+
+// Starts whose L bases hold a run longer than its base's limit (lim: by forward base code, 0 for none): a run of R + 1 starts somewhere
+// in [j, j + L - R).  Bases with the same limit share that window.
+CAL_DEV uint32_t long_runs(FilterConst* f, int st, const uint32_t (&c_lo)[4], const uint32_t (&c_hi)[4], int L) {
+  const int lim[4] = {f->max_run[st][0], f->max_run[st][1], f->max_run[st][2], f->max_run[st][3]};
+  uint32_t bad = 0u, done = 0u;
+#pragma unroll
+  for (int code = 0; code < 4; code++) {
+    const int R = lim[code];
+    if (R <= 0 || ((done >> code) & 1u)) continue;
+    uint32_t v[2];
+    run_starts(code, c_lo, c_hi, R, v);
+#pragma unroll
+    for (int other = code + 1; other < 4; other++) {
+      if (lim[other] != R) continue;
+      uint32_t w[2];
+      run_starts(other, c_lo, c_hi, R, w);
+      v[0] |= w[0]; v[1] |= w[1];
+      done |= 1u << other;
+    }
+    window<false>(v, L - R);
+    bad |= v[0];
+  }
+  return bad;
+}
+
+// Starts whose L bases hold the motif: an occurrence starts somewhere in [j, j + L - len].  The occurrence vector is and_letter over the
+// letters, for the starts in chain words 1 and 2.
+CAL_DEV uint32_t has_motif(const uint32_t (&sets)[2], int len, uint32_t (&c_lo)[4], uint32_t (&c_hi)[4], int L) {
+#pragma unroll
+  for (int i = 0; i < 4; i++) asm volatile("" : "+v"(c_lo[i]), "+v"(c_hi[i]));     // (as in match_word: no moved plane kept across motifs)
+  uint32_t v[2] = {0xFFFFFFFFu, 0xFFFFFFFFu};
+#define CALITAS_MOTIF_LETTER(J) \
+  if (((sets[J >> 3] >> (4 * (J & 7))) & 15u) != 15u) { \
+    v[0] = and_letter<32 + J>(v[0], (sets[J >> 3] >> (4 * (J & 7))) & 15u, c_lo, c_hi); \
+    v[1] = and_letter<64 + J>(v[1], (sets[J >> 3] >> (4 * (J & 7))) & 15u, c_lo, c_hi); \
+  }
+  CALITAS_MOTIF_LETTER(0) CALITAS_MOTIF_LETTER(1) CALITAS_MOTIF_LETTER(2) CALITAS_MOTIF_LETTER(3)
+  CALITAS_MOTIF_LETTER(4) CALITAS_MOTIF_LETTER(5) CALITAS_MOTIF_LETTER(6) CALITAS_MOTIF_LETTER(7)
+  if (sets[1] != 0xFFFFFFFFu) {
+    CALITAS_MOTIF_LETTER(8) CALITAS_MOTIF_LETTER(9) CALITAS_MOTIF_LETTER(10) CALITAS_MOTIF_LETTER(11)
+    CALITAS_MOTIF_LETTER(12) CALITAS_MOTIF_LETTER(13) CALITAS_MOTIF_LETTER(14) CALITAS_MOTIF_LETTER(15)
+  }
+#undef CALITAS_MOTIF_LETTER
+  window<false>(v, L - len + 1);
+  return v[0];
+}
+
+// The filter's verdict on the protospacers that start in the lane's word, per strand.  Every parameter is wave-uniform and comes
+// through the scalar path; a test that is not set costs a scalar branch.  Where the footprint holds an exception base the match vector is
+// clear already, so the planes' content there does not matter.
+CAL_DEV void site_keep(FilterConst* f, int L, uint32_t (&c_lo)[4], uint32_t (&c_hi)[4], uint32_t& plus, uint32_t& minus) {
+  const int gc_min = f->gc_min, gc_max = f->gc_max;
+  if (gc_min > 0 || gc_max < L) {
+    const uint32_t keep = keep_gc(c_lo, c_hi, L, gc_min, gc_max);
+    plus &= keep; minus &= keep;
+  }
+  bool limited = false, same = true;                           // (the same limits by forward base on both strands: A = T and C = G)
+#pragma unroll
+  for (int code = 0; code < 4; code++) {
+    limited = limited || f->max_run[0][code] > 0 || f->max_run[1][code] > 0;
+    same = same && f->max_run[0][code] == f->max_run[1][code];
+  }
+  if (limited) {
+    const uint32_t bad = long_runs(f, 0, c_lo, c_hi, L);
+    plus &= ~bad;
+    minus &= ~(same ? bad : long_runs(f, 1, c_lo, c_hi, L));
+  }
+  const int n_motifs = f->n_motifs;
+  for (int m = 0; m < n_motifs; m++) {
+    const uint32_t sets[2] = {f->motif[m].sets[0], f->motif[m].sets[1]}, strands = f->motif[m].strands;
+    const uint32_t bad = has_motif(sets, f->motif[m].len, c_lo, c_hi, L);
+    if (strands & 1u) plus &= ~bad;
+    if (strands & 2u) minus &= ~bad;
+  }
+}
+
 struct LaneSites {
   uint32_t plus, minus;        // match vectors: a site of that strand starts at base j
   uint32_t kp[3], km[3];       // bit-planes of the matching PAM's index
 };
 
 // The match vectors of the lane's word.  c_*: the chain w - 1 .. w + 2; base0: contig position of the word's first base.
+template <bool FILTER>
 CAL_DEV LaneSites match_word(PatConst* pat, uint32_t (&c_lo)[4], uint32_t (&c_hi)[4], const uint32_t (&c_ex)[4], int64_t base0,
                              int64_t r_start, int64_t r_end) {
   LaneSites s{0u, 0u, {0u, 0u, 0u}, {0u, 0u, 0u}};
@@ -126,6 +279,8 @@ CAL_DEV LaneSites match_word(PatConst* pat, uint32_t (&c_lo)[4], uint32_t (&c_hi
       if (k & 4) kb[2] |= acc;
     }
   }
+  // (the filter sees the protospacer alone, so it commutes with the PAMs' priority; kp / km are read at surviving bits only)
+  if constexpr (FILTER) site_keep(&((TablesConst*)pat)->filter, pat->proto_len, c_lo, c_hi, s.plus, s.minus);
   return s;
 }
 
@@ -135,10 +290,10 @@ struct Fetched {
   uint32_t ex, halo_ex;
 };
 
-// WRITE = false: pass 1 (counts); true: pass 2 (records).  A SEGMENT is SITES_BLOCK_WORDS consecutive words, all of one tile, one lane
+// WRITE = false: pass 1 (counts); true: pass 2 (records).  FILTER: a.pat heads a SiteTables whose filter applies.  A SEGMENT is SITES_BLOCK_WORDS consecutive words, all of one tile, one lane
 // per word; it is the unit of the counts and offsets.  A workgroup takes segs_per_wg consecutive segments, the next one's words on
 // their way from memory while it matches the current one's (a workgroup per segment is bound by the rate at which workgroups start).
-template <bool WRITE>
+template <bool WRITE, bool FILTER>
 __global__ __launch_bounds__(SITES_BLOCK_WORDS) void sites_kernel(SitesArgs a) {
   __shared__ uint32_t s_lo[SITES_BLOCK_WORDS + 3], s_hi[SITES_BLOCK_WORDS + 3], s_ex[SITES_BLOCK_WORDS + 3];
   __shared__ uint32_t s_wave[SITES_BLOCK_WORDS / 64];
@@ -193,7 +348,7 @@ __global__ __launch_bounds__(SITES_BLOCK_WORDS) void sites_kernel(SitesArgs a) {
     const int64_t r_start = (int64_t)(a.start < ci.len ? a.start : ci.len);
     const int64_t r_end = (int64_t)((a.end == 0 || a.end > ci.len) ? ci.len : a.end);
     const int64_t base0 = (int64_t)((wb + tid) * 32u) - (int64_t)ci.gbase;
-    const LaneSites s = match_word(pat, c_lo, c_hi, c_ex, base0, r_start, r_end);
+    const LaneSites s = match_word<FILTER>(pat, c_lo, c_hi, c_ex, base0, r_start, r_end);
 
     const uint32_t n_plus = (uint32_t)__builtin_popcount(s.plus), n_minus = (uint32_t)__builtin_popcount(s.minus);
     if (!WRITE) {
@@ -264,10 +419,11 @@ __global__ __launch_bounds__(OFFSETS_THREADS) void sites_offsets_kernel(const ui
 
 }  // namespace
 
-hipError_t launch_sites_count(const SitesArgs& a, hipStream_t stream) {
+hipError_t launch_sites_count(const SitesArgs& a, bool filtered, hipStream_t stream) {
   if (a.n_segs == 0) return hipSuccess;
   const uint32_t n_blocks = (a.n_segs + a.segs_per_wg - 1) / a.segs_per_wg;
-  hipLaunchKernelGGL(sites_kernel<false>, dim3(n_blocks), dim3(SITES_BLOCK_WORDS), 0, stream, a);
+  if (filtered) hipLaunchKernelGGL((sites_kernel<false, true>), dim3(n_blocks), dim3(SITES_BLOCK_WORDS), 0, stream, a);
+  else hipLaunchKernelGGL((sites_kernel<false, false>), dim3(n_blocks), dim3(SITES_BLOCK_WORDS), 0, stream, a);
   return hipGetLastError();
 }
 
@@ -276,10 +432,11 @@ hipError_t launch_sites_offsets(const uint32_t* wg_count, uint64_t* wg_offset, u
   return hipGetLastError();
 }
 
-hipError_t launch_sites_write(const SitesArgs& a, hipStream_t stream) {
+hipError_t launch_sites_write(const SitesArgs& a, bool filtered, hipStream_t stream) {
   if (a.n_segs == 0) return hipSuccess;
   const uint32_t n_blocks = (a.n_segs + a.segs_per_wg - 1) / a.segs_per_wg;
-  hipLaunchKernelGGL(sites_kernel<true>, dim3(n_blocks), dim3(SITES_BLOCK_WORDS), 0, stream, a);
+  if (filtered) hipLaunchKernelGGL((sites_kernel<true, true>), dim3(n_blocks), dim3(SITES_BLOCK_WORDS), 0, stream, a);
+  else hipLaunchKernelGGL((sites_kernel<true, false>), dim3(n_blocks), dim3(SITES_BLOCK_WORDS), 0, stream, a);
   return hipGetLastError();
 }
 

@@ -9,19 +9,28 @@ namespace calitas {
 
 // The per-(PAM, strand) patterns of a guide read as a pattern; returns an error text or "".
 std::string make_site_patterns(const GuideHost& gh, SitePatterns& out);
+// A site filter checked against a protospacer of L bases and turned into what the kernel reads; returns an error text that names the
+// field, or "".
+std::string make_site_filter(const calitas_site_filter_t& f, int L, SiteFilterDev& out);
+// Base by base: does the protospacer of L bases at [protospacer_start, protospacer_start + L) of the contig, read on the strand
+// (0 '+', 1 '-': the reverse complement), upper case and a U as T, pass the filter?  The protospacer alone: the verdict is the same for
+// every PAM that matches there.  Every base must be a plain one (any site's is).
+bool site_passes(const PackedRef& ref, int contig, int64_t protospacer_start, int L, int strand, const calitas_site_filter_t& filter);
 inline uint64_t region_end(uint64_t len, uint64_t end) { return (end == 0 || end > len) ? len : end; }
 // Base by base: the sites of one contig whose protospacer starts in [p_lo, p_hi), region [r_start, r_end), in output order, appended.
 // kernel_has != nullptr: none but those whose footprint holds a U, and appended to *kernel_has the record sites_kernel -- to which a U
 // is an exception base -- has at such a position instead (a later, shorter PAM's whose own footprint is clean), if it has one.
-void host_sites(const PackedRef& ref, const SitePatterns& pat, int contig, int64_t p_lo, int64_t p_hi, int64_t r_start, int64_t r_end,
-                std::vector<calitas_site_t>& out, std::vector<calitas_site_t>* kernel_has);
+// filter != nullptr: none but the sites that pass it, in `out` and in *kernel_has alike (the kernel filters what it writes).
+void host_sites(const PackedRef& ref, const SitePatterns& pat, const calitas_site_filter_t* filter, int contig, int64_t p_lo, int64_t p_hi,
+                int64_t r_start, int64_t r_end, std::vector<calitas_site_t>& out, std::vector<calitas_site_t>* kernel_has);
 struct SitesWork;                 // device scratch of a context, kept between calls
 void sites_destroy(SitesWork* w);
 
 }  // namespace calitas
 
-int calitas_find_sites_host_impl(const calitas_ctx* ctx, const calitas_guide_t* pattern, int32_t chrom_index, uint64_t start, uint64_t end,
-                                 calitas_site_t** sites, uint64_t* n_sites);
+// filter == nullptr: every site
+int calitas_find_sites_host_impl(const calitas_ctx* ctx, const calitas_guide_t* pattern, const calitas_site_filter_t* filter, int32_t chrom_index,
+                                 uint64_t start, uint64_t end, calitas_site_t** sites, uint64_t* n_sites);
 // listing: both passes and the records; otherwise the first pass alone
-int calitas_find_sites_impl(calitas_ctx* ctx, const calitas_guide_t* pattern, int32_t chrom_index, uint64_t start, uint64_t end, bool listing,
-                            calitas_site_t** sites, uint64_t* per_contig_strand, uint64_t* n_sites);
+int calitas_find_sites_impl(calitas_ctx* ctx, const calitas_guide_t* pattern, const calitas_site_filter_t* filter, int32_t chrom_index, uint64_t start,
+                            uint64_t end, bool listing, calitas_site_t** sites, uint64_t* per_contig_strand, uint64_t* n_sites);

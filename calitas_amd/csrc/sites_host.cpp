@@ -1,5 +1,6 @@
-// sites_host.cpp -- calitas_find_sites / calitas_count_sites / calitas_find_sites_host: the pattern both implementations share, the host
-// twin (a base-by-base walk over the packed reference) and the driver of sites.hip's two passes.  No reference counterpart.
+// sites_host.cpp -- calitas_find_sites / calitas_count_sites / calitas_find_sites_host and their _filtered forms: the pattern and the
+// filter both implementations share, the host twin (a base-by-base walk over the packed reference) and the driver of sites.hip's two
+// passes.  No reference counterpart.
 #include "sites.hpp"
 #include "tuning.hpp"
 
@@ -55,6 +56,79 @@ inline int plain_code(const PackedRef& ref, uint64_t g, bool* u) {
 
 }  // namespace
 
+std::string make_site_filter(const calitas_site_filter_t& f, int L, SiteFilterDev& out) {
+  std::memset(&out, 0, sizeof(out));
+  const int gc_max = std::min<int>(f.gc_max, L);
+  if ((int)f.gc_min > gc_max) return "site filter: gc_min exceeds gc_max (or the protospacer's length)";
+  if (f.reserved != 0) return "site filter: reserved must be 0";
+  if (f.n_motifs > 8) return "site filter: n_motifs exceeds 8";
+  out.gc_min = f.gc_min; out.gc_max = gc_max;
+  for (int b = 0; b < 4; b++) {
+    const int r = f.max_run[b] < L ? f.max_run[b] : 0;         // a run of L or more does not fit: no limit
+    out.max_run[0][b] = r;                                     // '+': the forward base is the guide's
+    out.max_run[1][3 - b] = r;                                 // '-': its complement's
+  }
+  out.n_motifs = 0;
+  for (int m = 0; m < (int)f.n_motifs; m++) {
+    const std::string at = "site filter: motifs[" + std::to_string(m) + "]";
+    std::string text;
+    for (int i = 0; i < 16 && f.motifs[m][i]; i++) text += f.motifs[m][i];
+    if (text.empty()) return at + " is empty";
+    if ((int)text.size() > L) return at + " is longer than the protospacer";
+    bool all_n = true;
+    for (char ch : text) {
+      const int set = iupac_mask((unsigned char)ch);
+      if (set == 0) return at + " has a non-IUPAC character: " + ch;
+      all_n = all_n && set == 15;
+    }
+    if (all_n) return at + " is made of N only";
+    const std::string shown[2] = {text, revcomp_str(text)};   // what the forward text shows of an occurrence, left to right
+    for (int st = 0; st < 2; st++) {
+      uint32_t sets[2] = {0xFFFFFFFFu, 0xFFFFFFFFu};
+      for (int i = 0; i < (int)text.size(); i++) {
+        const uint32_t set = (uint32_t)iupac_mask((unsigned char)shown[st][(size_t)i]);
+        sets[i >> 3] &= ~((15u ^ set) << (4 * (i & 7)));
+      }
+      int e = 0;                                               // the same string from another motif or strand: one entry
+      while (e < out.n_motifs && !(out.motif[e].len == (int32_t)text.size() && out.motif[e].sets[0] == sets[0] && out.motif[e].sets[1] == sets[1])) e++;
+      if (e == out.n_motifs) {
+        out.n_motifs++;
+        out.motif[e].len = (int32_t)text.size(); out.motif[e].strands = 0; out.motif[e].sets[0] = sets[0]; out.motif[e].sets[1] = sets[1];
+      }
+      out.motif[e].strands |= 1u << st;
+    }
+  }
+  return "";
+}
+
+bool site_passes(const PackedRef& ref, int contig, int64_t protospacer_start, int L, int strand, const calitas_site_filter_t& f) {
+  const uint64_t g0 = ref.contigs[(size_t)contig].gbase + (uint64_t)protospacer_start;
+  int code[MAX_L];                                             // the guide's bases, 5' to 3'
+  for (int i = 0; i < L; i++) {
+    bool u = false;
+    const int c = plain_code(ref, g0 + (uint64_t)(strand ? L - 1 - i : i), &u);
+    code[i] = strand ? 3 - c : c;
+  }
+  int gc = 0;
+  for (int i = 0; i < L; i++) gc += code[i] == 1 || code[i] == 2;
+  if (gc < (int)f.gc_min || gc > std::min<int>(f.gc_max, L)) return false;
+  for (int i = 0, run = 0; i < L; i++) {
+    run = (i > 0 && code[i] == code[i - 1]) ? run + 1 : 1;
+    const int limit = f.max_run[code[i]];
+    if (limit > 0 && run > limit) return false;
+  }
+  for (int m = 0; m < (int)f.n_motifs; m++) {
+    int len = 0;
+    while (len < 16 && f.motifs[m][len]) len++;
+    for (int at = 0; at + len <= L; at++) {
+      bool hit = true;
+      for (int i = 0; i < len && hit; i++) hit = ((iupac_mask((unsigned char)f.motifs[m][i]) >> code[at + i]) & 1) != 0;
+      if (hit) return false;
+    }
+  }
+  return true;
+}
+
 namespace {
 
 // The first PAM whose pattern matches at protospacer start p on strand st with its footprint inside [r_start, r_end), or -1.
@@ -86,14 +160,16 @@ calitas_site_t site_record(const SitePatterns& pat, int contig, int64_t p, int s
 
 }  // namespace
 
-void host_sites(const PackedRef& ref, const SitePatterns& pat, int contig, int64_t p_lo, int64_t p_hi, int64_t r_start, int64_t r_end,
-                std::vector<calitas_site_t>& out, std::vector<calitas_site_t>* kernel_has) {
+void host_sites(const PackedRef& ref, const SitePatterns& pat, const calitas_site_filter_t* filter, int contig, int64_t p_lo, int64_t p_hi,
+                int64_t r_start, int64_t r_end, std::vector<calitas_site_t>& out, std::vector<calitas_site_t>* kernel_has) {
   const uint64_t gbase = ref.contigs[(size_t)contig].gbase;
   for (int64_t p = std::max(p_lo, r_start); p < std::min(p_hi, r_end); p++) {
     for (int st = 0; st < 2; st++) {
       bool u = false, unused = false;
       const int k = first_pam(ref, pat, gbase, p, st, r_start, r_end, true, &u);
       if (k < 0) continue;
+      // the protospacer decides, whichever PAM matched: what holds for this record holds for the kernel's at the same place
+      if (filter && !site_passes(ref, contig, p, pat.proto_len, st, *filter)) continue;
       if (!kernel_has) { out.push_back(site_record(pat, contig, p, st, k)); continue; }
       // A match without a U: no earlier PAM matches even with U as T, so the kernel has this very record.  With one: the kernel has
       // either nothing here or a LATER PAM whose own footprint is clean (PAMs differ in length) -- that record has to go.
@@ -106,7 +182,7 @@ void host_sites(const PackedRef& ref, const SitePatterns& pat, int contig, int64
 }
 
 struct SitesWork {
-  SitePatterns* d_pat = nullptr;
+  SiteTables* d_pat = nullptr;       // the patterns and, behind them, the filter of the call in flight
   uint32_t* d_count = nullptr;
   uint64_t* d_off = nullptr;
   size_t blocks_cap = 0;
@@ -130,16 +206,20 @@ void sites_destroy(SitesWork* w) {
 namespace {
 
 struct SiteCall {
-  SitePatterns pat;
+  SiteTables tab;                    // the patterns; the filter as the kernel reads it
+  const calitas_site_filter_t* filter = nullptr;
   int c_first = 0, c_last = 0;       // contigs [c_first, c_last]
 };
 
-// arguments every entry point shares: the pattern, the contigs, the region
-int plan_sites(calitas_ctx* c, const calitas_guide_t* pattern, int32_t chrom_index, uint64_t start, uint64_t end, SiteCall& call) {
+// arguments every entry point shares: the pattern, the filter, the contigs, the region
+int plan_sites(calitas_ctx* c, const calitas_guide_t* pattern, const calitas_site_filter_t* filter, int32_t chrom_index, uint64_t start, uint64_t end,
+               SiteCall& call) {
   if (!c->has_ref) return calitas_fail(c, CALITAS_ESTATE, "calitas_set_reference has not been called");
   GuideHost gh;
   std::string e = make_guide_host(*pattern, gh);
-  if (e.empty()) e = make_site_patterns(gh, call.pat);
+  if (e.empty()) e = make_site_patterns(gh, call.tab.pat);
+  call.filter = filter;
+  if (e.empty() && filter) e = make_site_filter(*filter, call.tab.pat.proto_len, call.tab.filter);
   if (!e.empty()) return calitas_fail(c, CALITAS_EINVAL, e);
   const PackedRef& ref = c->ref;
   const int nc = (int)ref.contigs.size();
@@ -182,22 +262,23 @@ void sites_with_u(calitas_ctx* c, const SiteCall& call, uint64_t start, uint64_t
     const int64_t x0 = (int64_t)(r.start - ci.gbase);
     int64_t p_lo = x0 - SITE_MAX_FOOT, p_hi = x0 + (int64_t)r.len + MAX_PAM_LEN;
     if (done_contig == contig && p_lo < done_to) p_lo = done_to;
-    host_sites(ref, call.pat, contig, p_lo, p_hi, (int64_t)std::min<uint64_t>(start, ci.len), (int64_t)region_end(ci.len, end), with_u, &kernel_has);
+    host_sites(ref, call.tab.pat, call.filter, contig, p_lo, p_hi, (int64_t)std::min<uint64_t>(start, ci.len), (int64_t)region_end(ci.len, end), with_u,
+               &kernel_has);
     done_contig = contig; done_to = std::max(p_hi, p_lo);
   }
 }
 
 }  // namespace
 
-int calitas_find_sites_host_impl(const calitas_ctx* ctx, const calitas_guide_t* pattern, int32_t chrom_index, uint64_t start, uint64_t end,
-                                 calitas_site_t** sites, uint64_t* n_sites) {
+int calitas_find_sites_host_impl(const calitas_ctx* ctx, const calitas_guide_t* pattern, const calitas_site_filter_t* filter, int32_t chrom_index,
+                                 uint64_t start, uint64_t end, calitas_site_t** sites, uint64_t* n_sites) {
   calitas_ctx* c = const_cast<calitas_ctx*>(ctx);
   SiteCall call;
-  if (int rc = plan_sites(c, pattern, chrom_index, start, end, call)) return rc;
+  if (int rc = plan_sites(c, pattern, filter, chrom_index, start, end, call)) return rc;
   std::vector<calitas_site_t> found;
   for (int i = call.c_first; i <= call.c_last; i++) {
     const uint64_t len = ctx->ref.contigs[(size_t)i].len;
-    host_sites(ctx->ref, call.pat, i, 0, (int64_t)len, (int64_t)std::min(start, len), (int64_t)region_end(len, end), found, nullptr);
+    host_sites(ctx->ref, call.tab.pat, filter, i, 0, (int64_t)len, (int64_t)std::min(start, len), (int64_t)region_end(len, end), found, nullptr);
   }
   *n_sites = found.size();
   if (!sites) return CALITAS_OK;
@@ -207,11 +288,12 @@ int calitas_find_sites_host_impl(const calitas_ctx* ctx, const calitas_guide_t* 
   return CALITAS_OK;
 }
 
-int calitas_find_sites_impl(calitas_ctx* ctx, const calitas_guide_t* pattern, int32_t chrom_index, uint64_t start, uint64_t end,
-                            bool listing, calitas_site_t** sites, uint64_t* per_contig_strand, uint64_t* n_sites) {
+int calitas_find_sites_impl(calitas_ctx* ctx, const calitas_guide_t* pattern, const calitas_site_filter_t* filter, int32_t chrom_index, uint64_t start,
+                            uint64_t end, bool listing, calitas_site_t** sites, uint64_t* per_contig_strand, uint64_t* n_sites) {
   if (ctx->device < 0) return calitas_fail(ctx, CALITAS_ENODEV, "host-only context: calitas_find_sites needs a GPU (there is no CPU fallback; calitas_find_sites_host is the host twin)");
   SiteCall call;
-  if (int rc = plan_sites(ctx, pattern, chrom_index, start, end, call)) return rc;
+  if (int rc = plan_sites(ctx, pattern, filter, chrom_index, start, end, call)) return rc;
+  static_assert(offsetof(SiteTables, pat) == 0, "SitesArgs::pat heads the block");
   static_assert(sizeof(SiteRecord) == sizeof(calitas_site_t) && offsetof(SiteRecord, contig) == offsetof(calitas_site_t, contig_index) &&
                 offsetof(SiteRecord, proto_start) == offsetof(calitas_site_t, protospacer_start) &&
                 offsetof(SiteRecord, pam_start) == offsetof(calitas_site_t, pam_start) && offsetof(SiteRecord, strand) == offsetof(calitas_site_t, strand) &&
@@ -250,17 +332,17 @@ int calitas_find_sites_impl(calitas_ctx* ctx, const calitas_guide_t* pattern, in
     HIP_TRY(ctx, hipMalloc((void**)&w->d_totals, 2 * nc * sizeof(unsigned long long)));
     w->totals_cap = 2 * nc;
   }
-  if (!w->d_pat) HIP_TRY(ctx, hipMalloc((void**)&w->d_pat, sizeof(SitePatterns)));
+  if (!w->d_pat) HIP_TRY(ctx, hipMalloc((void**)&w->d_pat, sizeof(SiteTables)));
 
   SitesArgs a{};
-  a.planes = ctx->d_planes; a.mask = ctx->d_mask; a.tiles = ctx->d_tiles; a.contigs = ctx->d_contigs; a.pat = w->d_pat;
+  a.planes = ctx->d_planes; a.mask = ctx->d_mask; a.tiles = ctx->d_tiles; a.contigs = ctx->d_contigs; a.pat = &w->d_pat->pat;
   a.n_words = ref.total_packed / 32; a.w0 = w0; a.n_segs = n_blocks; a.segs_per_wg = segs_per_wg; a.tile_words = (uint32_t)(ref.tile / 32); a.chrom_index = chrom_index;
   a.start = start; a.end = end; a.wg_count = w->d_count; a.totals = w->d_totals; a.wg_offset = w->d_off; a.out = nullptr; a.out_capacity = 0;
 
   std::vector<uint64_t> totals(2 * nc + 1, 0);
-  HIP_TRY(ctx, hipMemcpyAsync(w->d_pat, &call.pat, sizeof(SitePatterns), hipMemcpyHostToDevice, ctx->stream));
+  HIP_TRY(ctx, hipMemcpyAsync(w->d_pat, &call.tab, filter ? sizeof(SiteTables) : sizeof(SitePatterns), hipMemcpyHostToDevice, ctx->stream));   // (no filter: the patterns alone, as ever)
   HIP_TRY(ctx, hipMemsetAsync(w->d_totals, 0, 2 * nc * sizeof(unsigned long long), ctx->stream));
-  HIP_TRY(ctx, launch_sites_count(a, ctx->stream));
+  HIP_TRY(ctx, launch_sites_count(a, filter != nullptr, ctx->stream));
   if (listing) {
     HIP_TRY(ctx, launch_sites_offsets(w->d_count, w->d_off, n_blocks, ctx->stream));
     HIP_TRY(ctx, hipMemcpyAsync(&totals[2 * nc], w->d_off + n_blocks, sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
@@ -291,7 +373,7 @@ int calitas_find_sites_impl(calitas_ctx* ctx, const calitas_guide_t* pattern, in
         w->out_cap = n_dev;
       }
       a.out = w->d_out; a.out_capacity = n_dev;
-      if ((e = launch_sites_write(a, ctx->stream)) != hipSuccess ||
+      if ((e = launch_sites_write(a, filter != nullptr, ctx->stream)) != hipSuccess ||
           (e = hipMemcpyAsync(block, w->d_out, n_dev * sizeof(SiteRecord), hipMemcpyDeviceToHost, ctx->stream)) != hipSuccess ||
           (e = hipStreamSynchronize(ctx->stream)) != hipSuccess)
         rc = calitas_fail(ctx, CALITAS_EHIP, std::string("calitas_find_sites: ") + hipGetErrorString(e));

@@ -308,6 +308,37 @@ int calitas_count_sites(calitas_ctx* ctx, const calitas_guide_t* pattern, int32_
 int calitas_find_sites_host(const calitas_ctx* ctx, const calitas_guide_t* pattern, int32_t chrom_index, uint64_t start, uint64_t end,
                             calitas_site_t** sites, uint64_t* n_sites);
 
+/* A site filter: which of a pattern's sites are guides worth ordering.  It applies to the PROTOSPACER of a site as it reads on the site's
+ * strand (upper case, U as T, L = its length) and to nothing else -- not the PAM, not the flanks -- so the verdict does not depend on
+ * which PAM matched.  A site is kept when all of these hold:
+ *   GC      gc_min <= (number of G and C among the L bases) <= gc_max; a gc_max above L means L.
+ *   runs    for each base b of A C G T with max_run[b] > 0 the protospacer holds no run of b longer than max_run[b].  Only bases inside
+ *           the protospacer count: a run that goes on into the PAM or the flank is cut at the protospacer's edge.  A limit >= L is legal
+ *           and rejects nothing.
+ *   motifs  none of the n_motifs IUPAC motifs matches anywhere entirely inside the protospacer: each is 1 .. 16 letters, at most L, read in
+ *           the guide's orientation; a guide base matches a letter when it lies in the letter's IUPAC set.  No reverse complement is
+ *           added: pass both orientations to avoid both.
+ * CALITAS_EINVAL, with a message that names the field: gc_min > min(gc_max, L); n_motifs > 8; a motif that is empty, longer than L, made
+ * of N only or holds a non-IUPAC letter; reserved != 0.  A filter that rejects every site returns none. */
+typedef struct {
+  uint8_t gc_min, gc_max;     /* counts of G + C among the protospacer's bases, inclusive; {0, 255}: no bound */
+  uint8_t max_run[4];         /* A C G T as the guide reads; 0: no limit */
+  uint8_t n_motifs;           /* 0..8 */
+  uint8_t reserved;           /* 0 */
+  char motifs[8][16];         /* IUPAC letters, either case, NUL-padded */
+} calitas_site_filter_t;
+
+/* calitas_find_sites, calitas_count_sites and calitas_find_sites_host with a filter: the records of the unfiltered listing that pass, in
+ * its order and with its pam_index, and the counts of those alone; every other argument as there.  filter == NULL is the unfiltered
+ * call.  On the device the filter is part of the kernel's match (bit-parallel over the planes it holds already): nothing is listed and
+ * dropped.  No reference counterpart. */
+int calitas_find_sites_filtered(calitas_ctx* ctx, const calitas_guide_t* pattern, const calitas_site_filter_t* filter, int32_t chrom_index,
+                                uint64_t start, uint64_t end, calitas_site_t** sites, uint64_t* n_sites);
+int calitas_count_sites_filtered(calitas_ctx* ctx, const calitas_guide_t* pattern, const calitas_site_filter_t* filter, int32_t chrom_index,
+                                 uint64_t start, uint64_t end, uint64_t* per_contig_strand, uint64_t* n_sites);
+int calitas_find_sites_filtered_host(const calitas_ctx* ctx, const calitas_guide_t* pattern, const calitas_site_filter_t* filter,
+                                     int32_t chrom_index, uint64_t start, uint64_t end, calitas_site_t** sites, uint64_t* n_sites);
+
 /* The specificity score of a guide: one number per off-target hit, summed per guide.  No reference counterpart.
  * A model for protospacers of L bases holds Q16 factors (65536 = 1.0, none above it): mismatch[L][5][5] indexed by guide position,
  * guide letter and target letter, one gap factor and one pam_mismatch factor.  Guide positions are 0-based and count the upper-case
