@@ -1,7 +1,9 @@
 """The referee of the site-filter tests (test_site_filters_host.py, test_gpu_site_filters.py): plain Python on strings that shares no
 code with the library.  It takes sites_ref.brute_sites' tuples and the contig strings, cuts each protospacer out, takes an explicit
 reverse complement for '-', counts G and C, searches `b * (r + 1) in proto` and holds motifs letter by letter against sites_ref.IUPAC.
-filter_genome() is a contig of less than 12 kb with the cases the contract names planted for N20 + nrg on both strands."""
+filter_genome() is a contig of less than 12 kb with the cases the contract names planted for N20 + nrg on both strands.
+sweep_genome(), features(), check_sweep() and sweep_sets() serve the parameter sweep: "N" * L for L = 1 .. 32, every bound at which a
+verdict can change, the expected listing as a mask over the unfiltered one."""
 import random
 
 import sites_ref as R
@@ -213,3 +215,285 @@ def check_planted(seqs, planted, sites):
     every = [name for name, seen in offsets.items() if len(seen) > 2]
     assert len(every) >= 12 and all(len(offsets[name]) == 32 for name in every), {n: len(offsets[n]) for n in every}
     assert any(p < 8192 < p + L20 - 1 for _, _, p, _, _ in planted)
+
+
+# ---- the parameter sweep: every protospacer length and every bound at which a verdict can change ----
+# The patterns are PAM-less ("N" * L): every position with room is a site on both strands, so every bit offset and every word boundary
+# of the kernel's 32-base words is covered without planting.  A filter's expected listing is plain[mask]: a boolean mask over the
+# unfiltered listing, from per-site features (G + C count, longest run per base) that string operations give once per length.
+
+SWEEP_LENGTHS = tuple(range(1, 33))
+PAM_LENGTHS = (1, 2, 3, 7, 8, 15, 16, 17, 31, 32)
+PAM_PATTERNS = {"nrg": (["nrg"], False), "tttv": (["tttv"], True)}
+TUPLE_LENGTHS = (5, 20, 32)                # the lengths that get every max_run tuple of {0, 1, 2, L - 1}^4
+SWEEP_KINDS = ("gc", "runs", "motifs", "together", "with_pam")
+SEGMENT_EDGE = 8192                        # a segment boundary of the kernel for the first contig (as in check_planted)
+
+# 16 letters; not a palindrome, and no prefix of two letters or more is its own reverse complement (check_motif_strings)
+M16 = "GACTTGCAAGCTGTCA"
+_TWO = {"A": "R", "C": "Y", "G": "K", "T": "W"}            # a two-base code that contains the letter
+IUPAC_LENGTHS = (3, 8, 9, 16)
+# every third letter a two-base code, letter 12 an N (which takes the place of that third letter's code)
+M16_IUPAC = "".join("N" if i == 11 else _TWO[c] if i % 3 == 2 else c for i, c in enumerate(M16))
+# eight motifs, none a palindrome, no two each other's reverse complement: with both orientations the sixteen entries the device holds
+EIGHT = ("CGTCTC", "GAAGAC", "GGTCTC", "CACCTGC", "ARYBA", "TTTTV", "GACNNNNNNNNR", "SWNNNNKNNA")
+_IUPAC_COMP = {"A": "T", "C": "G", "G": "C", "T": "A", "M": "K", "R": "Y", "W": "W", "S": "S", "Y": "R", "K": "M", "V": "B", "H": "D",
+               "D": "H", "B": "V", "N": "N"}
+
+
+def iupac_revcomp(motif):
+    return "".join(_IUPAC_COMP[c] for c in reversed(motif))
+
+
+def check_motif_strings():
+    assert len(M16) == 16 and set(M16) <= set("ACGT") and M16 != R.revcomp(M16)
+    assert all(M16[:n] != R.revcomp(M16[:n]) for n in range(2, 17))
+    assert len(M16_IUPAC) == 16 and M16_IUPAC[11] == "N" and sum(c in "RYKW" for c in M16_IUPAC) == 4
+    assert all(a in R.IUPAC[b] for a, b in zip(M16, M16_IUPAC))
+    both = [m for m in EIGHT] + [iupac_revcomp(m) for m in EIGHT]
+    assert len(EIGHT) == 8 and len(set(both)) == 16, both
+
+
+def _ramps(rng):
+    """A window sliding across these takes every G + C count from 0 to its length."""
+    return "AT" * 20 + "GC" * 20 + "TA" * 20 + R._rand(rng, 32)
+
+
+def _separator(b, r):
+    """33 bases alternating two of the three bases that are not b; which two goes round with r."""
+    other = "ACGT".replace(b, "")
+    return ((other[r % 3] + other[(r + 1) % 3]) * 17)[:33]
+
+
+def sweep_genome(seed=32):
+    """(names, strings): one contig of plain ACGT.  In this order: 64 random bases; the GC ramps; the run ladder -- for each base b and
+    each r = 1 .. 32 a separator without b and without a repeat, then b * r, and a closing separator per base; 600 random bases; random
+    filler up to base 8152; the ramps once more, so that GC windows of every length lie across base 8192 (SEGMENT_EDGE); 200 random bases
+    with M16 planted once per strand."""
+    rng = random.Random(seed)
+    parts = [R._rand(rng, 64), _ramps(rng)]
+    for b in "ACGT":
+        for r in range(1, 33):
+            parts.append(_separator(b, r) + b * r)
+        parts.append(_separator(b, 33))
+    parts.append(R._rand(rng, 600))
+    designed = sum(len(p) for p in parts)
+    assert designed == 7284, designed
+    parts.append(R._rand(rng, SEGMENT_EDGE - 40 - designed))
+    parts.append(_ramps(rng))
+    tail = list(R._rand(rng, 200))
+    R._put(tail, 40, M16)
+    R._put(tail, 120, R.revcomp(M16))
+    parts.append("".join(tail))
+    seq = "".join(parts)
+    assert set(seq) == set("ACGT") and seq[SEGMENT_EDGE - 40:SEGMENT_EDGE + 40] == "AT" * 20 + "GC" * 20 and len(seq) < 10000
+    return ["chrS"], [seq]
+
+
+class Features:
+    """Per brute_sites tuple, in the listing's order: minus (the strand), gc (G + C of the protospacer as the guide reads) and run
+    (the longest run of A, C, G, T in it), numpy arrays; protos: the protospacers themselves."""
+
+    def __init__(self, protos, minus, gc, run):
+        self.protos, self.minus, self.gc, self.run = protos, minus, gc, run
+
+
+def _longest(proto, b):
+    r = 0
+    while b * (r + 1) in proto:
+        r += 1
+    return r
+
+
+def features(sites, contigs):
+    import numpy as np
+    protos = [protospacer(s, contigs) for s in sites]
+    return Features(protos, np.array([s[3] == "-" for s in sites], dtype=bool),
+                    np.array([p.count("G") + p.count("C") for p in protos], dtype=np.int64),
+                    np.array([[_longest(p, b) for b in "ACGT"] for p in protos], dtype=np.int64).reshape(len(protos), 4))
+
+
+def mask_of(feat, L, gc_min=0, gc_max=255, max_run=(0, 0, 0, 0), avoid=(), motif_mask=None):
+    """passes() over a whole listing: the GC bounds and the run limits from the features, each motif's verdicts through
+    motif_mask(motif) (passes() itself, protospacer by protospacer, kept per motif)."""
+    keep = (feat.gc >= gc_min) & (feat.gc <= min(gc_max, L))
+    for i, r in enumerate(max_run):
+        if r > 0:
+            keep &= feat.run[:, i] <= r
+    for motif in avoid:
+        keep &= motif_mask(motif)
+    return keep
+
+
+def occurrences(proto, motif):
+    """The offsets at which the IUPAC motif occurs in the protospacer."""
+    return [at for at in range(len(proto) - len(motif) + 1) if all(proto[at + i] in R.IUPAC[motif[i]] for i in range(len(motif)))]
+
+
+def motifs_of(L):
+    """The single-motif cases of a length: M16's prefixes of 1 .. 16 letters that fit, and its IUPAC version's of IUPAC_LENGTHS."""
+    return [M16[:n] for n in range(1, min(16, L) + 1)] + [M16_IUPAC[:n] for n in IUPAC_LENGTHS if n <= L]
+
+
+_occurrences = {}
+
+
+def _occurs(seq, motif):
+    """Per strand, per forward position q with room: passes() rejects the stretch seq[q:q + len(motif)] as that strand's guide reads it."""
+    if motif not in _occurrences:
+        n = len(motif)
+        stretches = [seq[q:q + n] for q in range(len(seq) - n + 1)]
+        _occurrences[motif] = ([not passes(t, avoid=(motif,)) for t in stretches], [not passes(R.revcomp(t), avoid=(motif,)) for t in stretches])
+    return _occurrences[motif]
+
+
+class Listing:
+    """The unfiltered listing of one pattern by the referee: brute_sites' tuples, their features, and the motif verdicts asked for so far."""
+
+    def __init__(self, contigs, L, pams=(), five=False):
+        self.L, self.pams, self.five = L, list(pams), five
+        self.pattern = ("".join(pams[:1]) + "N" * L) if five else ("N" * L + "".join(pams[:1]))
+        self.sites = R.brute_sites(contigs, "N" * L, self.pams, five)
+        self.features = features(self.sites, contigs)
+        self.contig = contigs[0]
+        self._motifs = {}
+        self.checked = False
+
+    def motif_mask(self, motif):
+        """passes(protospacer, avoid=(motif,)) per site.  passes() rejects a protospacer when one of its windows of the motif's length
+        is an occurrence, and a window is a stretch of the contig that protospacers of every length share: passes() judges every such
+        stretch once per strand (_occurs), a site is rejected when a stretch inside its protospacer was, and passes() on the whole
+        protospacer confirms the rejected sites (a seeded 1024 of them where there are more) and a seeded sample of the kept ones."""
+        import numpy as np
+        if motif not in self._motifs:
+            n, L = len(motif), self.L
+            first = np.array([s[1] for s in self.sites], dtype=np.int64)
+            keep = np.ones(len(self.sites), dtype=bool)
+            for minus, occurs in enumerate(_occurs(self.contig, motif)):
+                before = np.concatenate(([0], np.cumsum(occurs)))                 # occurrences that start in front of a position
+                here = self.features.minus == bool(minus)
+                keep[here] = before[first[here] + L - n + 1] == before[first[here]]
+            protos = self.features.protos
+            sample = random.Random(len(motif) * 64 + L).sample(range(len(protos)), min(64, len(protos)))
+            rejected = np.flatnonzero(~keep).tolist()
+            if len(rejected) > 1024:                                              # (a one- or two-letter motif rejects nearly everything)
+                rejected = random.Random(L).sample(rejected, 1024)
+            for i in set(rejected) | set(sample):
+                assert passes(protos[i], avoid=(motif,)) == bool(keep[i]), (L, motif, self.sites[i])
+            self._motifs[motif] = keep
+        return self._motifs[motif]
+
+    def mask(self, **flt):
+        return mask_of(self.features, self.L, motif_mask=self.motif_mask, **flt)
+
+
+_listings = {}
+
+
+def listing(L, pam=None):
+    """The Listing of "N" * L (pam None), "N" * L + "nrg" or "tttv" + "N" * L on sweep_genome(), made once per session."""
+    if "genome" not in _listings:
+        _listings["genome"] = sweep_genome()
+    if (L, pam) not in _listings:
+        _listings[(L, pam)] = Listing(_listings["genome"][1], L, *(PAM_PATTERNS[pam] if pam else ()))
+    return _listings[(L, pam)]
+
+
+def checked_listing(L, pam=None):
+    """listing(), with check_sweep asserted on it when it is first asked for (the PAM-less ones: every position is a site there)."""
+    ls = listing(L, pam)
+    if pam is None and not ls.checked:
+        check_sweep(ls.features, L, ls.motif_mask)
+        ls.checked = True
+    return ls
+
+
+def check_sweep(feat, L, motif_mask=None):
+    """What sweep_genome() is there for, on the referee alone: per strand, every G + C count 0 .. L and, per base, every longest run
+    0 .. L occurs among the protospacers of length L, so every bound keeps something and rejects something; the features are passes()'
+    own verdicts at a few bounds; GC windows of every count's neighbourhood lie across SEGMENT_EDGE.  With motif_mask (a Listing's):
+    every single-motif case keeps and rejects a protospacer per strand, and for motifs of eight letters and more one rejected
+    protospacer has its only occurrence at offset 0 and one at offset L - len, the two ends of the occurrence window."""
+    import numpy as np
+    assert len(feat.protos) == len(feat.gc) == len(feat.run) == len(feat.minus) > 0 and all(len(p) == L for p in feat.protos[:50])
+    for minus in (False, True):
+        here = feat.minus == minus
+        assert set(feat.gc[here].tolist()) == set(range(L + 1)), (L, minus, "gc", sorted(set(range(L + 1)) - set(feat.gc[here].tolist())))
+        for i, b in enumerate("ACGT"):
+            seen = set(feat.run[here, i].tolist())
+            assert seen == set(range(L + 1)), (L, minus, b, sorted(set(range(L + 1)) - seen))
+    for flt in (dict(gc_min=(L + 1) // 2), dict(gc_max=L // 2), dict(max_run=(1, 0, 2, 0)), dict(max_run=(0, L - 1, 0, 1)), dict(max_run=(L, 200, 1, 255))):
+        assert mask_of(feat, L, **flt).tolist() == [passes(p, **flt) for p in feat.protos], (L, flt)
+    if motif_mask is None:
+        return
+    for motif in motifs_of(L):
+        keep = motif_mask(motif)
+        n = len(motif)
+        for minus in (False, True):
+            here = feat.minus == minus
+            assert 0 < int(keep[here].sum()) < int(here.sum()), (L, motif, minus)
+        if n >= 8:
+            where = [occurrences(feat.protos[i], motif) for i in np.flatnonzero(~keep)]
+            assert all(where), (L, motif)
+            assert [0] in where and [L - n] in where, (L, motif)
+
+
+# The parameter sets: lists of keyword arguments of passes() / mask_of() and of calitas_amd.SiteFilter alike, in an order in which an
+# open filter follows a closed one and a closed one an open one (nothing may stick between calls).
+
+def gc_sets(L, bounds=None):
+    g = sorted(set(range(L + 1)) if bounds is None else {b for b in bounds if 0 <= b <= L})
+    return ([dict(gc_min=x) for x in g if x >= 1] + [dict(gc_min=0, gc_max=255)] + [dict(gc_max=x) for x in g if x < L] +
+            [dict(gc_min=0, gc_max=L)] + [dict(gc_min=x, gc_max=x) for x in g])
+
+
+def run_sets(L, bounds=None, tuples=None):
+    r = sorted(set(range(1, L)) if bounds is None else {b for b in bounds if 1 <= b < L})
+    out = []
+    for i, everything in enumerate((L, 200, 255, None)):
+        if everything is not None:
+            out.append(dict(max_run=(everything,) * 4))                       # no limit: the plain listing
+        out += [dict(max_run=tuple(x if j == i else 0 for j in range(4))) for x in r]                     # base i alone
+    out += [dict(max_run=(x,) * 4) for x in r]
+    if L in TUPLE_LENGTHS if tuples is None else tuples:
+        values = (0, 1, 2, L - 1)
+        out += [dict(max_run=(a, b, c, d)) for a in values for b in values for c in values for d in values]
+    return out
+
+
+def motif_sets(L):
+    out = [dict(avoid=(m,)) for m in motifs_of(L)]
+    if L in (20, 32):
+        out.append(dict(avoid=EIGHT))
+    return out
+
+
+def together_sets(L):
+    rng = random.Random(1000 + L)
+    out = []
+    for _ in range(20):
+        lo = rng.randrange(L + 1)
+        hi = rng.choice(list(range(lo, L + 1)) + [255])
+        out.append(dict(gc_min=lo, gc_max=hi, max_run=tuple(rng.randrange(L + 1) for _ in range(4)),
+                        avoid=tuple(rng.sample(motifs_of(L), min(rng.choice((1, 2)), len(motifs_of(L)))))))
+    return out
+
+
+def sweep_sets(kind):
+    """[(L, pam or None, filter)] of a kind of SWEEP_KINDS."""
+    if kind == "with_pam":
+        out = []
+        for L in PAM_LENGTHS:
+            bounds = (0, 1, L // 2, L - 1, L)
+            for pam in PAM_PATTERNS:
+                out += [(L, pam, flt) for flt in gc_sets(L, bounds) + run_sets(L, bounds, tuples=False)]
+        return out
+    make = {"gc": gc_sets, "runs": run_sets, "motifs": motif_sets, "together": together_sets}[kind]
+    return [(L, None, flt) for L in SWEEP_LENGTHS for flt in make(L)]
+
+
+def first_difference(got, want):
+    """Where two listings part, for an assertion's message."""
+    n = min(len(got), len(want))
+    at = next((i for i in range(n) if got[i] != want[i]), n)
+    return "record %d of %d / %d: got %s, want %s" % (at, len(got), len(want), got[at] if at < len(got) else None, want[at] if at < len(want) else None)

@@ -1,7 +1,8 @@
 """GPU tests of the site filters (sites.hip's FILTER instantiations): the device against its host twin and against the referee of
 site_filter_ref.py, as record bytes and as counts per contig and strand, on the planted genome and on the seam genomes of
 test_gpu_sites.py (whose brute force is shared, not repeated); regions, an absent contig, the unfiltered call around a filtered one,
-find_guides with a filter in front of the search, and FindGuides --counts with the flags."""
+find_guides with a filter in front of the search, FindGuides --counts with the flags, and the parameter sweep of
+site_filter_ref.sweep_sets (every protospacer length, every bound) against the referee's masks."""
 import os
 import subprocess
 import sys
@@ -240,3 +241,50 @@ def test_find_guides_tool_counts_with_the_flags(C, tmp_path):
     by_id = {f[0]: f for f in every[1:]}
     assert all(f == by_id[f[0]] for f in kept[1:])
     assert [ln.split("\t") for ln in open(out["py"]).read().splitlines()] == [f[:8] for f in kept]
+
+
+# ---- the parameter sweep (site_filter_ref.sweep_sets): every protospacer length, every bound at which a verdict can change ----
+# The host twin is held against the same masks in test_site_filters_host.py and is not called again here.
+
+SWEEP_PARTS = [(kind, half) for kind in F.SWEEP_KINDS if kind != "with_pam" for half in ((1, 16), (17, 32))] + [("with_pam", (1, 32))]
+
+
+@pytest.fixture(scope="module")
+def sweep_referee():
+    """The referee's listings of every sweep pattern, check_sweep asserted on each length: made before anything of the library runs."""
+    F.check_motif_strings()
+    return {(L, pam): F.checked_listing(L, pam) for L, pam in [(L, None) for L in F.SWEEP_LENGTHS] + [(L, pam) for L in F.PAM_LENGTHS for pam in F.PAM_PATTERNS]}
+
+
+@pytest.mark.parametrize("kind,half", SWEEP_PARTS, ids=["%s-%d-%d" % (k, h[0], h[1]) for k, h in SWEEP_PARTS])
+def test_sweep_device(C, sweep_referee, kind, half, monkeypatch):
+    """Per parameter set: the device listing == plain[mask] as bytes, count_sites gives len(plain[mask]), and its table per strand the
+    mask's counts per strand."""
+    monkeypatch.delenv("CALITAS_CHUNK", raising=False)
+    monkeypatch.delenv("CALITAS_SITES_SEGS", raising=False)
+    names, seqs = F.sweep_genome()
+    sets = [s for s in F.sweep_sets(kind) if half[0] <= s[0] <= half[1]]
+    ctx = C.Context(0)
+    try:
+        ctx.set_reference(names, [s.encode() for s in seqs])
+        plains, each_way = {}, 0
+        for L, pam, flt in sets:
+            ls = sweep_referee[(L, pam)]
+            if (L, pam) not in plains:
+                got = ctx.find_sites(ls.pattern)
+                plains[(L, pam)] = R.as_records(ls.sites, got.dtype)
+                assert got.tobytes() == plains[(L, pam)].tobytes(), (L, pam, F.first_difference(got.tolist(), plains[(L, pam)].tolist()))
+            plain = plains[(L, pam)]
+            mask = ls.mask(**flt)
+            want = plain[mask]
+            keep = C.SiteFilter(**flt)
+            got = ctx.find_sites(ls.pattern, filter=keep)
+            assert got.tobytes() == want.tobytes(), (L, pam, flt, F.first_difference(got.tolist(), want.tolist()))
+            n, table = ctx.count_sites(ls.pattern, filter=keep)
+            minus = int((mask & ls.features.minus).sum())
+            assert n == len(want) and table.tolist() == [[len(want) - minus, minus]], (L, pam, flt, n, table.tolist(), len(want), minus)
+            each_way += 0 < len(want) < len(plain)
+        print(kind, half, "sets", len(sets), "that keep and reject", each_way)
+        assert each_way > len(sets) // 2
+    finally:
+        ctx.close()

@@ -1,7 +1,8 @@
 """CPU tests of the site filters (calitas_find_sites_filtered_host on a host-only context): the host twin against the referee of
 site_filter_ref.py as record bytes, the planted cases, the open filter, validation, SiteFilter.percent, and both FindGuides tools with
---device -1 and the filter flags.  No GPU."""
+--device -1 and the filter flags; the parameter sweep of site_filter_ref.sweep_sets (every length, every bound).  No GPU."""
 import os
+import random
 import subprocess
 import sys
 
@@ -278,3 +279,63 @@ def test_both_tools_with_the_filter_flags_on_the_host_twin(C, contexts, tmp_path
         bad = subprocess.run(tool + ["FindGuides", "-r", fa, "-i", N20, "--device", "-1"] + sum([["--avoid", m] for m in ("AAC", "AAG", "AAT", "ACC", "ACG")], []),
                              env=env, cwd=ROOT, capture_output=True)
         assert bad.returncode != 0
+
+
+# ---- the parameter sweep (site_filter_ref.sweep_sets): every protospacer length, every bound at which a verdict can change ----
+
+@pytest.fixture(scope="module")
+def sweep_ctx(C):
+    names, seqs = F.sweep_genome()
+    ctx = C.Context(-1)
+    ctx.set_reference(names, [s.encode() for s in seqs])
+    yield ctx
+    ctx.close()
+
+
+_sweep_plain = {}
+
+
+def _sweep_plain_listing(C, ctx, L, pam):
+    """The referee's unfiltered listing of a sweep pattern as records, held against the host twin's as bytes when first asked for."""
+    if (L, pam) not in _sweep_plain:
+        ls = F.listing(L, pam)
+        got = ctx.find_sites(ls.pattern, host=True)
+        plain = R.as_records(ls.sites, got.dtype)
+        assert got.tobytes() == plain.tobytes(), (L, pam, F.first_difference(got.tolist(), plain.tolist()))
+        _sweep_plain[(L, pam)] = plain
+    return _sweep_plain[(L, pam)]
+
+
+def test_sweep_genome_is_on_target():
+    """check_sweep on the referee alone, for every length."""
+    F.check_motif_strings()
+    for L in F.SWEEP_LENGTHS:
+        ls = F.checked_listing(L)
+        some = random.Random(L).sample(range(len(ls.sites)), 1500)                 # (the combined masks are passes()' verdicts)
+        for flt in F.motif_sets(L)[-1:] + F.together_sets(L)[:2]:
+            mask = ls.mask(**flt)
+            assert all(bool(mask[i]) == F.passes(ls.features.protos[i], **flt) for i in some), (L, flt)
+    for L in (20, 32):
+        for minus in (False, True):
+            here = F.listing(L).features.minus == minus
+            assert 0 < int(F.listing(L).mask(avoid=F.EIGHT)[here].sum()) < int(here.sum())
+    for L in F.PAM_LENGTHS:
+        for pam in F.PAM_PATTERNS:
+            ls = F.listing(L, pam)
+            assert 50 < len(ls.sites) < len(F.listing(L).sites) // 2 and 0 < int(ls.features.minus.sum()) < len(ls.sites)
+
+
+@pytest.mark.parametrize("kind", F.SWEEP_KINDS)
+def test_sweep_host_twin(C, sweep_ctx, kind):
+    """find_sites(host=True, filter=...) == plain[mask] as bytes for every parameter set of the kind."""
+    each_way = 0
+    for L, pam, flt in F.sweep_sets(kind):
+        ls = F.checked_listing(L, pam)
+        plain = _sweep_plain_listing(C, sweep_ctx, L, pam)
+        mask = ls.mask(**flt)
+        want = plain[mask]
+        got = sweep_ctx.find_sites(ls.pattern, host=True, filter=C.SiteFilter(**flt))
+        assert got.tobytes() == want.tobytes(), (L, pam, flt, F.first_difference(got.tolist(), want.tolist()))
+        each_way += 0 < len(want) < len(plain)
+    print(kind, "sets", len(F.sweep_sets(kind)), "that keep and reject", each_way)
+    assert each_way > len(F.sweep_sets(kind)) // 2
