@@ -89,6 +89,12 @@ def main(argv=None):
     fg.add_argument("--max-run", metavar="SPEC", help="the longest run of one base a protospacer may hold: N, or T=3,G=4 (unnamed bases unlimited)")
     fg.add_argument("--avoid", metavar="MOTIF", action="append", default=[],
                     help="drop guides whose protospacer holds this IUPAC motif or its reverse complement (repeatable; 8 motifs in all)")
+    fg.add_argument("--copies", action="store_true",
+                    help="add copies: the sites of the pattern in the whole reference with this row's protospacer, the row's own among them")
+    fg.add_argument("--seed-copies", metavar="K", type=int,
+                    help="add seed_copies: the same for the PAM-proximal K bases of the protospacer (1 .. its length)")
+    fg.add_argument("--max-copies", metavar="N", type=int, help="drop guides with more than N copies (N >= 1; implies --copies)")
+    fg.add_argument("--max-seed-copies", metavar="N", type=int, help="drop guides with more than N seed copies (needs --seed-copies)")
     fg.add_argument("-d", "--max-guide-diffs", type=int, default=Defaults.MaxGuideDiffs)
     fg.add_argument("-p", "--max-pam-mismatches", type=int, default=Defaults.MaxPamMismatches)
     fg.add_argument("-g", "--max-gaps-between-guide-and-pam", type=int, default=Defaults.MaxGapsBetweenGuideAndPam)
@@ -135,7 +141,8 @@ def main(argv=None):
             sys.stdout.write(text)
     elif a.tool == "FindGuides":
         text = find_guides_tool(a.ref, a.guide, a.auxiliary_pams, chrom=a.chrom, start=a.start, end=a.end, output=a.output, counts=a.counts, scores=a.scores,
-                                device=a.device, gc_min=a.gc_min, gc_max=a.gc_max, max_run=a.max_run, avoid=a.avoid, max_guide_diffs=a.max_guide_diffs, max_pam_mismatches=a.max_pam_mismatches,
+                                device=a.device, gc_min=a.gc_min, gc_max=a.gc_max, max_run=a.max_run, avoid=a.avoid, copies=a.copies,
+                                seed_copies=a.seed_copies, max_copies=a.max_copies, max_seed_copies=a.max_seed_copies, max_guide_diffs=a.max_guide_diffs, max_pam_mismatches=a.max_pam_mismatches,
                                 max_gaps_between_guide_and_pam=a.max_gaps_between_guide_and_pam, max_total_diffs=a.max_total_diffs,
                                 max_overlap=a.max_overlap, guide_mismatch_net_cost=a.guide_mismatch_net_cost,
                                 pam_mismatch_net_cost=a.pam_mismatch_net_cost, genome_gap_net_cost=a.genome_gap_net_cost,

@@ -549,6 +549,30 @@ class Context:
         _lib.check(self._h, rc)
         return n.value, table[:len(self.contig_names)]
 
+    def count_copies(self, pattern, queries, key_length=None, chrom=None, start=0, end=None, host=False):
+        """calitas_count_copies: per query the number of sites of `pattern` (as count_sites counts them, unfiltered) whose KEY equals it,
+        a numpy uint64 array in the queries' order.  The key of a site is its protospacer as the guide reads it -- GuideSite.guide
+        without the PAM -- cut to its PAM-proximal key_length bases: the last ones for a 3' PAM or none, the first for a 5' PAM;
+        None: the whole protospacer.  queries: strings of that one length, A C G T in either case (U as T); a list or any iterable.
+        A guide cut from the reference counts itself.  host=True: the host twin (calitas_count_copies_host), also on a host-only
+        context."""
+        import numpy as np
+        pattern, index, start, end = self._site_region(pattern, chrom, start, end)
+        queries = [q.decode() if isinstance(q, bytes) else str(q) for q in queries]
+        K = pattern.protospacer_length if key_length is None else int(key_length)
+        for i, q in enumerate(queries):
+            if len(q) != K:
+                raise ValueError("queries[%d] has %d letters, the key has %d" % (i, len(q), K))
+        g = pattern.to_c()
+        out = np.zeros(max(1, len(queries)), dtype=np.uint64)
+        # (latin-1 keeps one byte per letter whatever the letter: the library names a bad one by its query's index)
+        text = "".join(queries).encode("latin-1", "replace")
+        fn = lib.calitas_count_copies_host if host else lib.calitas_count_copies
+        rc = fn(self._h, ctypes.byref(g), 0 if key_length is None else K, index, start, end, text, len(queries),
+                out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)))
+        _lib.check(self._h, rc)
+        return out[:len(queries)]
+
     @staticmethod
     def _scores_of(c):
         """A calitas_scores_t as a Scores object (the table is copied)."""

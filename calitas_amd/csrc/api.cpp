@@ -821,6 +821,20 @@ int calitas_find_sites_host(const calitas_ctx* ctx, const calitas_guide_t* patte
   return calitas_find_sites_filtered_host(ctx, pattern, nullptr, chrom_index, start, end, sites, n_sites);
 }
 
+int calitas_count_copies(calitas_ctx* ctx, const calitas_guide_t* pattern, int32_t key_length, int32_t chrom_index, uint64_t start, uint64_t end,
+                         const char* queries, uint64_t n_queries, uint64_t* copies) {
+  if (!ctx) return CALITAS_EINVAL;
+  if (!pattern || (n_queries && (!queries || !copies))) return fail(ctx, CALITAS_EINVAL, "NULL argument");
+  return calitas_count_copies_impl(ctx, pattern, key_length, chrom_index, start, end, queries, n_queries, copies);
+}
+
+int calitas_count_copies_host(const calitas_ctx* ctx, const calitas_guide_t* pattern, int32_t key_length, int32_t chrom_index, uint64_t start,
+                              uint64_t end, const char* queries, uint64_t n_queries, uint64_t* copies) {
+  if (!ctx) return CALITAS_EINVAL;
+  if (!pattern || (n_queries && (!queries || !copies))) return fail(const_cast<calitas_ctx*>(ctx), CALITAS_EINVAL, "NULL argument");
+  return calitas_count_copies_host_impl(ctx, pattern, key_length, chrom_index, start, end, queries, n_queries, copies);
+}
+
 // A guide's scores as the ABI hands them over: struct, table and cells in one block of the library's.
 static calitas_scores_t* scores_block(const CountsShape& shape, const uint64_t* table, uint64_t rows, const ScoreWords& w) {
   const size_t cells = shape.cells();

@@ -29,6 +29,9 @@ static void usage() {
     "       calitas FindGuides -i PATTERNpam -r ref.fa [-x aux-pam ...] [-c chrom] [-s start=0] [-e end] [-o guides.tsv]\n"
     "         [--gc-min PCT] [--gc-max PCT (G + C of the protospacer, percent)] [--max-run N | T=3,G=4 (longest run of a base)]\n"
     "         [--avoid MOTIF ... (IUPAC; with its reverse complement, 8 motifs in all)]\n"
+    "         [--copies (the column copies: sites of the pattern in the whole reference with the row's protospacer, its own among them)]\n"
+    "         [--seed-copies K (the column seed_copies: the same for the PAM-proximal K bases)]\n"
+    "         [--max-copies N (drop rows with more; implies --copies)] [--max-seed-copies N (needs --seed-copies)]\n"
     "         [--device N (-1: the host twin, no GPU)]\n");
 }
 
@@ -262,7 +265,9 @@ static int find_guides_main(int argc, char** argv) {
   std::vector<std::string> aux, avoid;
   uint64_t start = 0, end = 0;
   int device = 0, gc_lo = 0, gc_hi = 100;
-  bool filtered = false, limited = false;
+  bool filtered = false, limited = false, copies = false;
+  long long seed_k = 0, max_copies = 0, max_seed_copies = 0;      // 0: the flag is not given
+  bool have_seed = false, have_max = false, have_max_seed = false;
   for (int i = 2; i < argc; i++) {
     std::string a = argv[i], val;
     size_t eq = a.find('=');
@@ -285,6 +290,10 @@ static int find_guides_main(int argc, char** argv) {
     else if (a == "--gc-max") { gc_hi = std::atoi(next().c_str()); filtered = true; }
     else if (a == "--max-run") { max_run = next(); filtered = limited = true; }
     else if (a == "--avoid") { avoid.push_back(next()); filtered = true; }
+    else if (a == "--copies") copies = true;
+    else if (a == "--seed-copies") { seed_k = std::atoll(next().c_str()); have_seed = true; }
+    else if (a == "--max-copies") { max_copies = std::atoll(next().c_str()); have_max = copies = true; }
+    else if (a == "--max-seed-copies") { max_seed_copies = std::atoll(next().c_str()); have_max_seed = true; }
     else { std::fprintf(stderr, "unknown argument %s\n", a.c_str()); usage(); return 2; }
   }
   if (pattern.empty() || ref.empty()) { usage(); return 2; }
@@ -298,6 +307,10 @@ static int find_guides_main(int argc, char** argv) {
     return 2;
   }
   const calitas_site_filter_t* keep = filtered ? &filter : nullptr;
+  if (have_seed && (seed_k < 1 || seed_k > (long long)pg.proto.size())) { std::fprintf(stderr, "calitas: --seed-copies K: K is 1 .. %zu, the protospacer's length\n", pg.proto.size()); return 2; }
+  if (have_max && max_copies < 1) { std::fprintf(stderr, "calitas: --max-copies N: N is at least 1 (a guide counts itself)\n"); return 2; }
+  if (have_max_seed && !have_seed) { std::fprintf(stderr, "calitas: --max-seed-copies requires --seed-copies K\n"); return 2; }
+  if (have_max_seed && max_seed_copies < 1) { std::fprintf(stderr, "calitas: --max-seed-copies N: N is at least 1 (a guide counts itself)\n"); return 2; }
   calitas_ctx* ctx = nullptr;
   if (calitas_create(device, &ctx) != CALITAS_OK) { std::fprintf(stderr, "calitas: %s\n", calitas_last_error(nullptr)); return 1; }
   auto die = [&](const char* what) { std::fprintf(stderr, "calitas: %s: %s\n", what, calitas_last_error(ctx)); calitas_destroy(ctx); std::exit(1); };
@@ -314,7 +327,7 @@ static int find_guides_main(int argc, char** argv) {
   if (rc != CALITAS_OK) die("finding sites");
   FILE* f = output.empty() ? stdout : std::fopen(output.c_str(), "w");
   if (!f) { std::fprintf(stderr, "cannot write %s\n", output.c_str()); calitas_free(sites); calitas_destroy(ctx); return 1; }
-  std::fprintf(f, "guide_id\tchromosome\tstart\tend\tstrand\tpam_index\tguide\tpam_sequence\n");
+  std::fprintf(f, "guide_id\tchromosome\tstart\tend\tstrand\tpam_index\tguide\tpam_sequence%s%s\n", copies ? "\tcopies" : "", have_seed ? "\tseed_copies" : "");
   auto on_strand = [](std::string t, bool minus) {     // upper-case bases as fetched; '-': their reverse complement
     if (!minus) return t;
     std::string o(t.rbegin(), t.rend());
@@ -322,25 +335,54 @@ static int find_guides_main(int argc, char** argv) {
     return o;
   };
   const int64_t L = (int64_t)pg.proto.size();
+  // the rows' protospacers, or their PAM-proximal K bases, counted over the whole reference (tools.py guide_copies)
+  std::vector<std::string> protos((size_t)n_sites), pam_seqs((size_t)n_sites);
   for (uint64_t i = 0; i < n_sites; i++) {
     const calitas_site_t& s = sites[i];
-    const bool minus = s.strand == '-';
-    const char* name; uint64_t len;
-    calitas_contig_name(ctx, s.contig_index, &name, &len);
     std::string proto((size_t)L, 'N'), pam((size_t)s.pam_length, 'N');
     if (calitas_fetch_bases(ctx, s.contig_index, (uint64_t)s.protospacer_start, (uint32_t)L, &proto[0]) != CALITAS_OK) die("fetching bases");
     if (s.pam_start >= 0 && calitas_fetch_bases(ctx, s.contig_index, (uint64_t)s.pam_start, s.pam_length, &pam[0]) != CALITAS_OK) die("fetching bases");
-    proto = on_strand(proto, minus); pam = on_strand(pam, minus);
+    proto = on_strand(proto, s.strand == '-'); pam_seqs[(size_t)i] = on_strand(pam, s.strand == '-');
     for (auto& c : proto) if (c == 'U') c = 'T';          // an ACGT guide
+    protos[(size_t)i] = proto;
+  }
+  const bool five = pg.pam5 && !pg.pams.empty();
+  auto count = [&](int64_t K, std::vector<uint64_t>& out) {
+    std::string keys;
+    for (const std::string& p : protos) keys += five ? p.substr(0, (size_t)K) : p.substr((size_t)(L - K));
+    out.assign((size_t)n_sites + 1, 0);
+    const uint64_t most = 1ull << 24;                     // what one call takes; the queries are independent: a call's worth at a time
+    for (uint64_t at = 0; at < n_sites; at += most) {
+      const uint64_t n = std::min(most, n_sites - at);
+      const int rc2 = device < 0 ? calitas_count_copies_host(ctx, &g, (int32_t)K, -1, 0, 0, keys.data() + at * (uint64_t)K, n, out.data() + at)
+                                 : calitas_count_copies(ctx, &g, (int32_t)K, -1, 0, 0, keys.data() + at * (uint64_t)K, n, out.data() + at);
+      if (rc2 != CALITAS_OK) die("counting copies");
+    }
+  };
+  std::vector<uint64_t> n_copies, n_seed;
+  if (copies) count(L, n_copies);
+  if (have_seed) count(seed_k, n_seed);
+  uint64_t n_rows = 0;
+  for (uint64_t i = 0; i < n_sites; i++) {
+    if (have_max && n_copies[(size_t)i] > (uint64_t)max_copies) continue;
+    if (have_max_seed && n_seed[(size_t)i] > (uint64_t)max_seed_copies) continue;
+    n_rows++;
+    const calitas_site_t& s = sites[i];
+    const char* name; uint64_t len;
+    calitas_contig_name(ctx, s.contig_index, &name, &len);
+    const std::string &proto = protos[(size_t)i], &pam = pam_seqs[(size_t)i];
     const int64_t lo = s.pam_start < 0 ? s.protospacer_start : std::min<int64_t>(s.protospacer_start, s.pam_start);
     const int64_t hi = s.pam_start < 0 ? s.protospacer_start + L : std::max<int64_t>(s.protospacer_start + L, (int64_t)s.pam_start + s.pam_length);
     const std::string pat_pam = s.pam_index >= 0 ? pg.pams[(size_t)s.pam_index] : std::string();
     const std::string guide = pg.pam5 ? pat_pam + proto : proto + pat_pam;
-    std::fprintf(f, "%s:%lld:%c\t%s\t%lld\t%lld\t%c\t%d\t%s\t%s\n", name, (long long)lo, (char)s.strand, name, (long long)lo, (long long)hi,
+    std::fprintf(f, "%s:%lld:%c\t%s\t%lld\t%lld\t%c\t%d\t%s\t%s", name, (long long)lo, (char)s.strand, name, (long long)lo, (long long)hi,
                  (char)s.strand, (int)s.pam_index, guide.c_str(), pam.c_str());
+    if (copies) std::fprintf(f, "\t%llu", (unsigned long long)n_copies[(size_t)i]);
+    if (have_seed) std::fprintf(f, "\t%llu", (unsigned long long)n_seed[(size_t)i]);
+    std::fprintf(f, "\n");
   }
   if (f != stdout) std::fclose(f);
-  std::fprintf(stderr, "calitas: %llu guides\n", (unsigned long long)n_sites);
+  std::fprintf(stderr, "calitas: %llu guides\n", (unsigned long long)n_rows);
   calitas_free(sites); calitas_destroy(ctx);
   return 0;
 }

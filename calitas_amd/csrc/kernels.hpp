@@ -156,11 +156,37 @@ struct SitesArgs {
   const uint64_t* wg_offset;       // pass 2: exclusive scan of wg_count
   SiteRecord* out;                 // pass 2
   uint64_t out_capacity;
+  // copies_kernel only (calitas_count_copies): the table of the caller's distinct query keys
+  const uint64_t* keys;            // open addressing, table_mask + 1 slots (a power of two, at most half of them taken), COPIES_EMPTY: free
+  const uint32_t* key_index;       // per taken slot: the key's index among the distinct keys
+  unsigned long long* key_counts;  // per distinct key: its sites, zero at launch; [n_keys]: the call's error flag
+  uint32_t table_mask, table_shift;   // a key's first slot is (key * COPIES_HASH) >> table_shift
+  uint32_t n_keys;
+  uint32_t ones_index;             // the index of the key COPIES_EMPTY itself (all T at K = 32), COPIES_NONE when it is no query
+  int32_t key_len;                 // K, 1 .. proto_len
+  int32_t key_first;               // 1: the guide's first K bases (a 5' PAM), 0: its last K
 };
 // filtered: a.pat's SiteTables holds a filter, and the match vectors are ANDed with it in both passes
 hipError_t launch_sites_count(const SitesArgs& a, bool filtered, hipStream_t stream);
 // wg_count[0 .. n) -> wg_offset[0 .. n], wg_offset[n] = the total
 hipError_t launch_sites_offsets(const uint32_t* wg_count, uint64_t* wg_offset, uint32_t n, hipStream_t stream);
 hipError_t launch_sites_write(const SitesArgs& a, bool filtered, hipStream_t stream);
+
+// The KEY of a site (calitas_count_copies): the PAM-proximal K bases of its protospacer as the guide reads them, bit i of the low word
+// = low bit of base i's code (A 0, C 1, G 2, T 3), bit i of the high word = its high bit, base 0 the 5' one.  w_lo, w_hi: the planes of
+// the protospacer's L FORWARD bases from its leftmost one (bits above L - 1: anything); minus: the guide is their reverse complement --
+// the planes' bits in reverse order and complemented; first: the guide's first K bases (5' PAM) instead of its last K.  The host encodes
+// a query with L = K on '+': one function for both sides.  At K = 32 a key takes every value of 64 bits.
+CAL_HD inline uint64_t copies_key(uint32_t w_lo, uint32_t w_hi, int L, int K, bool minus, bool first) {
+  if (minus) { w_lo = __builtin_bitreverse32(~w_lo) >> (32 - L); w_hi = __builtin_bitreverse32(~w_hi) >> (32 - L); }
+  const uint32_t by = first ? 0u : (uint32_t)(L - K), m = 0xFFFFFFFFu >> (32 - K);
+  return (uint64_t)((w_lo >> by) & m) | ((uint64_t)((w_hi >> by) & m) << 32);
+}
+constexpr uint64_t COPIES_EMPTY = ~0ull;                    // a free slot; as a key (T x 32) it is kept outside the table (ones_index)
+constexpr uint64_t COPIES_HASH = 0x9E3779B97F4A7C15ull;     // multiplicative hash: the product's top bits
+constexpr uint32_t COPIES_NONE = 0xFFFFFFFFu;
+constexpr uint32_t COPIES_MIN_SLOTS = 16;
+// one pass of the unfiltered match; every site's key looked up, a hit adds 1 to its key's counter
+hipError_t launch_sites_copies(const SitesArgs& a, hipStream_t stream);
 
 }  // namespace calitas

@@ -16,6 +16,9 @@
 // Output in order, without a sort and without a returning atomic: pass 1 stores one count per segment, a one-workgroup scan turns
 // the counts into offsets, pass 2 recomputes the vectors and every lane writes its records at offset + prefix (a DPP prefix sum per
 // wave, the waves' sums through LDS); the '+' and '-' record of one position are neighbours.
+// COPIES (calitas_count_copies): the copies kernel, sites_kernel<false, false, true>, is the first pass's match with another ending -- instead of being counted, every site of the
+// lane's word gives its KEY (copies_key: the PAM-proximal K bases as the guide reads, from the chain registers), which is looked up in the
+// caller's table of query keys; a hit adds 1 to that key's counter (count_keys).
 // FILTER (calitas_find_sites_filtered): a keep vector per strand from the same registers -- G + C count, base runs and motifs of the
 // protospacer, chain positions 32 + j .. 32 + j + L - 1 -- ANDed into the match vectors in both passes (site_keep).
 #include <hip/hip_runtime.h>
@@ -290,10 +293,43 @@ struct Fetched {
   uint32_t ex, halo_ex;
 };
 
-// WRITE = false: pass 1 (counts); true: pass 2 (records).  FILTER: a.pat heads a SiteTables whose filter applies.  A SEGMENT is SITES_BLOCK_WORDS consecutive words, all of one tile, one lane
+// The keys of the sites that start in the lane's word (chain word 1), looked up one after the other: a site per turn of the loop, '+'
+// before '-'.  The protospacer's L <= 32 forward bases from bit j of word 1 on are one v_alignbit_b32 per plane.  The table is open
+// addressing with linear probing from the multiplicative hash's slot; at most half of its slots are taken, so a probe ends at the key
+// or at a free slot -- and at table_mask + 1 steps whatever the table holds: a probe that runs off that bound sets the call's error flag
+// and gives up (the host reports an internal error), it never spins.  A hit adds 1 to the key's counter with a non-returning atomic;
+// adds of a wave to one counter are not combined first (what was tried and what it gave).
+CAL_DEV void count_keys(const SitesArgs& a, const LaneSites& s, const uint32_t (&c_lo)[4], const uint32_t (&c_hi)[4], int L) {
+  const int K = a.key_len;
+  const bool first = a.key_first != 0;
+  const uint32_t mask = a.table_mask, shift = a.table_shift;
+  uint32_t left_p = s.plus, left_m = s.minus;
+  while (left_p | left_m) {
+    const bool minus = left_p == 0u;
+    const uint32_t j = (uint32_t)__builtin_ctz(minus ? left_m : left_p);
+    if (minus) left_m &= left_m - 1u; else left_p &= left_p - 1u;
+    const uint64_t key = copies_key(__builtin_amdgcn_alignbit(c_lo[2], c_lo[1], j), __builtin_amdgcn_alignbit(c_hi[2], c_hi[1], j), L, K, minus, first);
+    uint32_t idx = COPIES_NONE;
+    if (key == COPIES_EMPTY) {
+      idx = a.ones_index;
+    } else {
+      uint32_t slot = (uint32_t)((key * COPIES_HASH) >> shift), step = 0;
+      for (; step <= mask; step++) {
+        const uint64_t k = a.keys[slot];
+        if (k == key) { idx = a.key_index[slot]; break; }
+        if (k == COPIES_EMPTY) break;
+        slot = (slot + 1u) & mask;
+      }
+      if (step > mask) a.key_counts[a.n_keys] = 1ull;       // no free slot in the whole table: the error flag
+    }
+    if (idx != COPIES_NONE) (void)atomicAdd(&a.key_counts[idx], 1ull);
+  }
+}
+
+// WRITE = false: pass 1 (counts); true: pass 2 (records).  COPIES (with neither): the match of pass 1, the sites' keys counted.  FILTER: a.pat heads a SiteTables whose filter applies.  A SEGMENT is SITES_BLOCK_WORDS consecutive words, all of one tile, one lane
 // per word; it is the unit of the counts and offsets.  A workgroup takes segs_per_wg consecutive segments, the next one's words on
 // their way from memory while it matches the current one's (a workgroup per segment is bound by the rate at which workgroups start).
-template <bool WRITE, bool FILTER>
+template <bool WRITE, bool FILTER, bool COPIES = false>
 __global__ __launch_bounds__(SITES_BLOCK_WORDS) void sites_kernel(SitesArgs a) {
   __shared__ uint32_t s_lo[SITES_BLOCK_WORDS + 3], s_hi[SITES_BLOCK_WORDS + 3], s_ex[SITES_BLOCK_WORDS + 3];
   __shared__ uint32_t s_wave[SITES_BLOCK_WORDS / 64];
@@ -328,7 +364,7 @@ __global__ __launch_bounds__(SITES_BLOCK_WORDS) void sites_kernel(SitesArgs a) {
   for (uint32_t seg = seg0; seg < seg1; seg++) {
     const TileInfo ti = tile_of(seg);
     if (!live(ti)) {
-      if (!WRITE && tid == 0) a.wg_count[seg] = 0u;
+      if (!WRITE && !COPIES && tid == 0) a.wg_count[seg] = 0u;
       f = fetch(seg + 1);
       continue;
     }
@@ -349,6 +385,11 @@ __global__ __launch_bounds__(SITES_BLOCK_WORDS) void sites_kernel(SitesArgs a) {
     const int64_t r_end = (int64_t)((a.end == 0 || a.end > ci.len) ? ci.len : a.end);
     const int64_t base0 = (int64_t)((wb + tid) * 32u) - (int64_t)ci.gbase;
     const LaneSites s = match_word<FILTER>(pat, c_lo, c_hi, c_ex, base0, r_start, r_end);
+    if constexpr (COPIES) {
+      count_keys(a, s, c_lo, c_hi, pat->proto_len);
+      __syncthreads();                                      // (every lane has its chain out of LDS before the next segment goes in)
+      continue;
+    }
 
     const uint32_t n_plus = (uint32_t)__builtin_popcount(s.plus), n_minus = (uint32_t)__builtin_popcount(s.minus);
     if (!WRITE) {
@@ -392,7 +433,7 @@ __global__ __launch_bounds__(SITES_BLOCK_WORDS) void sites_kernel(SitesArgs a) {
       }
     }
   }
-  if (!WRITE && tid == 0) flush_totals();
+  if (!WRITE && !COPIES && tid == 0) flush_totals();
 }
 
 // Exclusive scan of the workgroups' counts by one workgroup: a stretch per thread, the stretches' sums scanned in LDS.
@@ -437,6 +478,13 @@ hipError_t launch_sites_write(const SitesArgs& a, bool filtered, hipStream_t str
   const uint32_t n_blocks = (a.n_segs + a.segs_per_wg - 1) / a.segs_per_wg;
   if (filtered) hipLaunchKernelGGL((sites_kernel<true, true>), dim3(n_blocks), dim3(SITES_BLOCK_WORDS), 0, stream, a);
   else hipLaunchKernelGGL((sites_kernel<true, false>), dim3(n_blocks), dim3(SITES_BLOCK_WORDS), 0, stream, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_sites_copies(const SitesArgs& a, hipStream_t stream) {
+  if (a.n_segs == 0) return hipSuccess;
+  const uint32_t n_blocks = (a.n_segs + a.segs_per_wg - 1) / a.segs_per_wg;
+  hipLaunchKernelGGL((sites_kernel<false, false, true>), dim3(n_blocks), dim3(SITES_BLOCK_WORDS), 0, stream, a);
   return hipGetLastError();
 }
 

@@ -34,3 +34,8 @@ int calitas_find_sites_host_impl(const calitas_ctx* ctx, const calitas_guide_t* 
 // listing: both passes and the records; otherwise the first pass alone
 int calitas_find_sites_impl(calitas_ctx* ctx, const calitas_guide_t* pattern, const calitas_site_filter_t* filter, int32_t chrom_index, uint64_t start,
                             uint64_t end, bool listing, calitas_site_t** sites, uint64_t* per_contig_strand, uint64_t* n_sites);
+// copies[i]: the sites of the unfiltered count whose key -- the PAM-proximal key_length bases of the protospacer (0: all of it) -- is query i
+int calitas_count_copies_host_impl(const calitas_ctx* ctx, const calitas_guide_t* pattern, int32_t key_length, int32_t chrom_index, uint64_t start,
+                                   uint64_t end, const char* queries, uint64_t n_queries, uint64_t* copies);
+int calitas_count_copies_impl(calitas_ctx* ctx, const calitas_guide_t* pattern, int32_t key_length, int32_t chrom_index, uint64_t start, uint64_t end,
+                              const char* queries, uint64_t n_queries, uint64_t* copies);

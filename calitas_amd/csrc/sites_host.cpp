@@ -1,6 +1,7 @@
 // sites_host.cpp -- calitas_find_sites / calitas_count_sites / calitas_find_sites_host and their _filtered forms: the pattern and the
 // filter both implementations share, the host twin (a base-by-base walk over the packed reference) and the driver of sites.hip's two
-// passes.  No reference counterpart.
+// passes.  calitas_count_copies / calitas_count_copies_host: the query keys and their table, the host twin and the driver of the copies
+// kernel.  No reference counterpart.
 #include "sites.hpp"
 #include "tuning.hpp"
 
@@ -8,6 +9,7 @@
 #include <cstddef>
 #include <cstdlib>
 #include <cstring>
+#include <unordered_map>
 
 namespace calitas {
 
@@ -190,6 +192,12 @@ struct SitesWork {
   size_t totals_cap = 0;
   SiteRecord* d_out = nullptr;
   size_t out_cap = 0;
+  // calitas_count_copies: the table of query keys (slots) and the distinct keys' counters (+ 1: the error flag)
+  uint64_t* d_keys = nullptr;
+  uint32_t* d_key_index = nullptr;
+  size_t slots_cap = 0;
+  unsigned long long* d_key_counts = nullptr;
+  size_t key_counts_cap = 0;
   // the U / u runs of the resident reference (a U is a plain base to a site and an exception base to the kernels)
   uint64_t u_serial = ~0ull;
   std::vector<Run> u_runs;
@@ -198,6 +206,7 @@ struct SitesWork {
 void sites_destroy(SitesWork* w) {
   if (!w) return;
   (void)hipFree(w->d_pat); (void)hipFree(w->d_count); (void)hipFree(w->d_off); (void)hipFree(w->d_totals); (void)hipFree(w->d_out);
+  (void)hipFree(w->d_keys); (void)hipFree(w->d_key_index); (void)hipFree(w->d_key_counts);
   delete w;
 }
 
@@ -209,6 +218,7 @@ struct SiteCall {
   SiteTables tab;                    // the patterns; the filter as the kernel reads it
   const calitas_site_filter_t* filter = nullptr;
   int c_first = 0, c_last = 0;       // contigs [c_first, c_last]
+  bool pam5 = false;                 // the pattern has PAMs and they stand in front of the protospacer
 };
 
 // arguments every entry point shares: the pattern, the filter, the contigs, the region
@@ -219,6 +229,7 @@ int plan_sites(calitas_ctx* c, const calitas_guide_t* pattern, const calitas_sit
   std::string e = make_guide_host(*pattern, gh);
   if (e.empty()) e = make_site_patterns(gh, call.tab.pat);
   call.filter = filter;
+  call.pam5 = gh.pam5 && !gh.pams.empty();
   if (e.empty() && filter) e = make_site_filter(*filter, call.tab.pat.proto_len, call.tab.filter);
   if (!e.empty()) return calitas_fail(c, CALITAS_EINVAL, e);
   const PackedRef& ref = c->ref;
@@ -268,6 +279,28 @@ void sites_with_u(calitas_ctx* c, const SiteCall& call, uint64_t start, uint64_t
   }
 }
 
+// The launch of a region: the words it touches, from a workgroup boundary on (contigs start on tile boundaries, tiles are whole
+// workgroups), and the arguments every kernel of sites.hip shares.
+int site_launch(calitas_ctx* ctx, const SiteCall& call, int32_t chrom_index, uint64_t start, uint64_t end, SitesWork* w, SitesArgs& a) {
+  const PackedRef& ref = ctx->ref;
+  const ContigInfo& cf = ref.contigs[(size_t)call.c_first];
+  const ContigInfo& cl = ref.contigs[(size_t)call.c_last];
+  uint64_t w0 = (cf.gbase + (chrom_index < 0 ? 0 : std::min(start, cf.len))) / 32, w1 = (cl.gbase + (chrom_index < 0 ? cl.len : region_end(cl.len, end)) + 31) / 32;
+  w0 -= w0 % SITES_BLOCK_WORDS;
+  const uint64_t blocks64 = w1 > w0 ? (w1 - w0 + SITES_BLOCK_WORDS - 1) / SITES_BLOCK_WORDS : 0;
+  if (blocks64 > 0x7FFFFFFFull) return calitas_fail(ctx, CALITAS_EINVAL, "the region is too large for one launch");
+  const uint32_t n_blocks = (uint32_t)blocks64;
+  // enough workgroups to fill the chip for a small region, few enough for a genome that their launch rate does not bind (DESIGN 4.9)
+  uint32_t segs_per_wg = std::min<uint32_t>(16u, std::max<uint32_t>(1u, n_blocks / 2048u));
+  if (const char* e = TUNE_GET("CALITAS_SITES_SEGS")) { const int v = std::atoi(e); if (v >= 1 && v <= 16) segs_per_wg = (uint32_t)v; }
+  if (!w->d_pat) HIP_TRY(ctx, hipMalloc((void**)&w->d_pat, sizeof(SiteTables)));
+  a = SitesArgs{};
+  a.planes = ctx->d_planes; a.mask = ctx->d_mask; a.tiles = ctx->d_tiles; a.contigs = ctx->d_contigs; a.pat = &w->d_pat->pat;
+  a.n_words = ref.total_packed / 32; a.w0 = w0; a.n_segs = n_blocks; a.segs_per_wg = segs_per_wg; a.tile_words = (uint32_t)(ref.tile / 32); a.chrom_index = chrom_index;
+  a.start = start; a.end = end;
+  return CALITAS_OK;
+}
+
 }  // namespace
 
 int calitas_find_sites_host_impl(const calitas_ctx* ctx, const calitas_guide_t* pattern, const calitas_site_filter_t* filter, int32_t chrom_index,
@@ -309,17 +342,9 @@ int calitas_find_sites_impl(calitas_ctx* ctx, const calitas_guide_t* pattern, co
   if (!ctx->sites) ctx->sites = new SitesWork();
   SitesWork* w = ctx->sites;
 
-  // the words the region touches, from a workgroup boundary on (contigs start on tile boundaries, tiles are whole workgroups)
-  const ContigInfo& cf = ref.contigs[(size_t)call.c_first];
-  const ContigInfo& cl = ref.contigs[(size_t)call.c_last];
-  uint64_t w0 = (cf.gbase + (chrom_index < 0 ? 0 : std::min(start, cf.len))) / 32, w1 = (cl.gbase + (chrom_index < 0 ? cl.len : region_end(cl.len, end)) + 31) / 32;
-  w0 -= w0 % SITES_BLOCK_WORDS;
-  const uint64_t blocks64 = w1 > w0 ? (w1 - w0 + SITES_BLOCK_WORDS - 1) / SITES_BLOCK_WORDS : 0;
-  if (blocks64 > 0x7FFFFFFFull) return calitas_fail(ctx, CALITAS_EINVAL, "the region is too large for one launch");
-  const uint32_t n_blocks = (uint32_t)blocks64;
-  // enough workgroups to fill the chip for a small region, few enough for a genome that their launch rate does not bind (DESIGN 4.9)
-  uint32_t segs_per_wg = std::min<uint32_t>(16u, std::max<uint32_t>(1u, n_blocks / 2048u));
-  if (const char* e = TUNE_GET("CALITAS_SITES_SEGS")) { const int v = std::atoi(e); if (v >= 1 && v <= 16) segs_per_wg = (uint32_t)v; }
+  SitesArgs a{};
+  if (int rc = site_launch(ctx, call, chrom_index, start, end, w, a)) return rc;
+  const uint32_t n_blocks = a.n_segs;
 
   if (w->blocks_cap < (size_t)n_blocks + 1) {
     (void)hipFree(w->d_count); (void)hipFree(w->d_off); w->d_count = nullptr; w->d_off = nullptr; w->blocks_cap = 0;
@@ -332,12 +357,7 @@ int calitas_find_sites_impl(calitas_ctx* ctx, const calitas_guide_t* pattern, co
     HIP_TRY(ctx, hipMalloc((void**)&w->d_totals, 2 * nc * sizeof(unsigned long long)));
     w->totals_cap = 2 * nc;
   }
-  if (!w->d_pat) HIP_TRY(ctx, hipMalloc((void**)&w->d_pat, sizeof(SiteTables)));
-
-  SitesArgs a{};
-  a.planes = ctx->d_planes; a.mask = ctx->d_mask; a.tiles = ctx->d_tiles; a.contigs = ctx->d_contigs; a.pat = &w->d_pat->pat;
-  a.n_words = ref.total_packed / 32; a.w0 = w0; a.n_segs = n_blocks; a.segs_per_wg = segs_per_wg; a.tile_words = (uint32_t)(ref.tile / 32); a.chrom_index = chrom_index;
-  a.start = start; a.end = end; a.wg_count = w->d_count; a.totals = w->d_totals; a.wg_offset = w->d_off; a.out = nullptr; a.out_capacity = 0;
+  a.wg_count = w->d_count; a.totals = w->d_totals; a.wg_offset = w->d_off; a.out = nullptr; a.out_capacity = 0;
 
   std::vector<uint64_t> totals(2 * nc + 1, 0);
   HIP_TRY(ctx, hipMemcpyAsync(w->d_pat, &call.tab, filter ? sizeof(SiteTables) : sizeof(SitePatterns), hipMemcpyHostToDevice, ctx->stream));   // (no filter: the patterns alone, as ever)
@@ -393,5 +413,155 @@ int calitas_find_sites_impl(calitas_ctx* ctx, const calitas_guide_t* pattern, co
     std::sort(block, block + *n_sites, site_less);
   }
   *sites = block;
+  return CALITAS_OK;
+}
+
+// ---- calitas_count_copies: how often a guide's protospacer, or its PAM-proximal seed, stands next to a PAM ----
+
+namespace {
+
+constexpr uint64_t COPIES_MAX_QUERIES = 1ull << 24;
+
+struct CopiesCall {
+  SiteCall site;
+  int L = 0, K = 0;
+  std::vector<uint64_t> keys;                        // the distinct query keys, in the order of their first query
+  std::vector<uint32_t> of_query;                    // per query: its key's index in `keys`
+  std::unordered_map<uint64_t, uint32_t> index;      // key -> index in `keys`
+};
+
+// The arguments both implementations share, checked in this order: the pattern and the region (plan_sites), key_length, the number of
+// queries, their letters.
+int plan_copies(calitas_ctx* c, const calitas_guide_t* pattern, int32_t key_length, int32_t chrom_index, uint64_t start, uint64_t end, const char* queries,
+                uint64_t n_queries, CopiesCall& call) {
+  if (int rc = plan_sites(c, pattern, nullptr, chrom_index, start, end, call.site)) return rc;
+  call.L = call.site.tab.pat.proto_len;
+  if (key_length < 0 || key_length > call.L)
+    return calitas_fail(c, CALITAS_EINVAL, "key_length is " + std::to_string(key_length) + ": it is 1 .. the protospacer's length (" + std::to_string(call.L) + "), or 0 for that length");
+  call.K = key_length == 0 ? call.L : key_length;
+  if (n_queries > COPIES_MAX_QUERIES) return calitas_fail(c, CALITAS_EINVAL, "n_queries exceeds 16777216 (2^24): count the queries in pieces");
+  const size_t K = (size_t)call.K;
+  call.of_query.resize((size_t)n_queries);
+  call.index.reserve((size_t)n_queries);
+  for (uint64_t q = 0; q < n_queries; q++) {
+    uint32_t lo = 0, hi = 0;
+    for (size_t i = 0; i < K; i++) {
+      const unsigned char ch = (unsigned char)queries[q * K + i];
+      const int set = iupac_mask(ch);
+      if (set != 1 && set != 2 && set != 4 && set != 8)
+        return calitas_fail(c, CALITAS_EINVAL, "queries[" + std::to_string(q) + "] holds a letter outside ACGTUacgtu at position " + std::to_string(i));
+      const uint32_t code = set == 1 ? 0u : set == 2 ? 1u : set == 4 ? 2u : 3u;
+      lo |= (code & 1u) << i; hi |= (code >> 1) << i;
+    }
+    const uint64_t key = copies_key(lo, hi, call.K, call.K, false, false);     // a guide of K bases on '+', all of it
+    const auto at = call.index.emplace(key, (uint32_t)call.keys.size());
+    if (at.second) call.keys.push_back(key);
+    call.of_query[(size_t)q] = at.first->second;
+  }
+  return CALITAS_OK;
+}
+
+// the key of the site whose protospacer starts at p of the contig at gbase, base by base (a U is a T)
+uint64_t key_at(const PackedRef& ref, uint64_t gbase, int64_t p, const CopiesCall& call, bool minus) {
+  uint32_t lo = 0, hi = 0;
+  for (int i = 0; i < call.L; i++) {
+    bool u = false;
+    const uint32_t code = (uint32_t)plain_code(ref, gbase + (uint64_t)(p + i), &u);
+    lo |= (code & 1u) << i; hi |= (code >> 1) << i;
+  }
+  return copies_key(lo, hi, call.L, call.K, minus, call.site.pam5);
+}
+
+// counts[key's index] += by for every record whose key is a query's
+void add_sites(const PackedRef& ref, const CopiesCall& call, const std::vector<calitas_site_t>& sites, uint64_t by, std::vector<uint64_t>& counts) {
+  for (const calitas_site_t& s : sites) {
+    const auto at = call.index.find(key_at(ref, ref.contigs[(size_t)s.contig_index].gbase, s.protospacer_start, call, s.strand == '-'));
+    if (at != call.index.end()) counts[at->second] += by;
+  }
+}
+
+}  // namespace
+
+int calitas_count_copies_host_impl(const calitas_ctx* ctx, const calitas_guide_t* pattern, int32_t key_length, int32_t chrom_index, uint64_t start,
+                                   uint64_t end, const char* queries, uint64_t n_queries, uint64_t* copies) {
+  calitas_ctx* c = const_cast<calitas_ctx*>(ctx);
+  CopiesCall call;
+  if (int rc = plan_copies(c, pattern, key_length, chrom_index, start, end, queries, n_queries, call)) return rc;
+  std::vector<uint64_t> counts(call.keys.size(), 0);
+  std::vector<calitas_site_t> found;
+  for (int i = call.site.c_first; i <= call.site.c_last && !call.keys.empty(); i++) {
+    const uint64_t len = ctx->ref.contigs[(size_t)i].len;
+    found.clear();
+    host_sites(ctx->ref, call.site.tab.pat, nullptr, i, 0, (int64_t)len, (int64_t)std::min(start, len), (int64_t)region_end(len, end), found, nullptr);
+    add_sites(ctx->ref, call, found, 1, counts);
+  }
+  for (uint64_t q = 0; q < n_queries; q++) copies[q] = counts[call.of_query[(size_t)q]];
+  return CALITAS_OK;
+}
+
+int calitas_count_copies_impl(calitas_ctx* ctx, const calitas_guide_t* pattern, int32_t key_length, int32_t chrom_index, uint64_t start, uint64_t end,
+                              const char* queries, uint64_t n_queries, uint64_t* copies) {
+  if (ctx->device < 0) return calitas_fail(ctx, CALITAS_ENODEV, "host-only context: calitas_count_copies needs a GPU (there is no CPU fallback; calitas_count_copies_host is the host twin)");
+  CopiesCall call;
+  if (int rc = plan_copies(ctx, pattern, key_length, chrom_index, start, end, queries, n_queries, call)) return rc;
+  const PackedRef& ref = ctx->ref;
+  const size_t n_keys = call.keys.size();
+  if (n_keys == 0 || ref.contigs.empty()) {         // nothing to look up, or nothing to scan
+    for (uint64_t q = 0; q < n_queries; q++) copies[q] = 0;
+    return CALITAS_OK;
+  }
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  if (!ctx->sites) ctx->sites = new SitesWork();
+  SitesWork* w = ctx->sites;
+  SitesArgs a{};
+  if (int rc = site_launch(ctx, call.site, chrom_index, start, end, w, a)) return rc;
+
+  // the table: a power of two of slots, at most half of them taken; linear probing from the multiplicative hash's slot.  The key that
+  // looks like a free slot (COPIES_EMPTY: T x 32, possible at K = 32 only) stays outside, the kernel knows its index.
+  uint32_t log2_slots = 4;
+  static_assert(COPIES_MIN_SLOTS == 16, "log2_slots starts at the minimum");
+  while (((size_t)1 << log2_slots) < 2 * n_keys) log2_slots++;
+  const size_t slots = (size_t)1 << log2_slots;
+  std::vector<uint64_t> table(slots, COPIES_EMPTY);
+  std::vector<uint32_t> table_index(slots, COPIES_NONE);
+  a.ones_index = COPIES_NONE;
+  for (size_t k = 0; k < n_keys; k++) {
+    const uint64_t key = call.keys[k];
+    if (key == COPIES_EMPTY) { a.ones_index = (uint32_t)k; continue; }
+    size_t slot = (size_t)((key * COPIES_HASH) >> (64 - log2_slots));
+    while (table[slot] != COPIES_EMPTY) slot = (slot + 1) & (slots - 1);
+    table[slot] = key; table_index[slot] = (uint32_t)k;
+  }
+  if (w->slots_cap < slots) {
+    (void)hipFree(w->d_keys); (void)hipFree(w->d_key_index); w->d_keys = nullptr; w->d_key_index = nullptr; w->slots_cap = 0;
+    HIP_TRY(ctx, hipMalloc((void**)&w->d_keys, slots * sizeof(uint64_t)));
+    HIP_TRY(ctx, hipMalloc((void**)&w->d_key_index, slots * sizeof(uint32_t)));
+    w->slots_cap = slots;
+  }
+  if (w->key_counts_cap < n_keys + 1) {
+    (void)hipFree(w->d_key_counts); w->d_key_counts = nullptr; w->key_counts_cap = 0;
+    HIP_TRY(ctx, hipMalloc((void**)&w->d_key_counts, (n_keys + 1) * sizeof(unsigned long long)));
+    w->key_counts_cap = n_keys + 1;
+  }
+  a.keys = w->d_keys; a.key_index = w->d_key_index; a.key_counts = w->d_key_counts;
+  a.table_mask = (uint32_t)(slots - 1); a.table_shift = 64 - log2_slots; a.n_keys = (uint32_t)n_keys;
+  a.key_len = call.K; a.key_first = call.site.pam5 ? 1 : 0;
+
+  std::vector<uint64_t> counts(n_keys + 1, 0);
+  HIP_TRY(ctx, hipMemcpyAsync(w->d_pat, &call.site.tab, sizeof(SitePatterns), hipMemcpyHostToDevice, ctx->stream));
+  HIP_TRY(ctx, hipMemcpyAsync(w->d_keys, table.data(), slots * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
+  HIP_TRY(ctx, hipMemcpyAsync(w->d_key_index, table_index.data(), slots * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+  HIP_TRY(ctx, hipMemsetAsync(w->d_key_counts, 0, (n_keys + 1) * sizeof(unsigned long long), ctx->stream));
+  HIP_TRY(ctx, launch_sites_copies(a, ctx->stream));
+  HIP_TRY(ctx, hipMemcpyAsync(counts.data(), w->d_key_counts, (n_keys + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  if (counts[n_keys] != 0) return calitas_fail(ctx, CALITAS_EHIP, "calitas_count_copies: a probe of the key table found neither its key nor a free slot (internal error)");
+
+  // a U is a T to a site and an exception base to the kernel: the sites it did not see in, the records it saw in their place out
+  std::vector<calitas_site_t> with_u, kernel_has;
+  sites_with_u(ctx, call.site, start, end, with_u, kernel_has);
+  add_sites(ref, call, with_u, 1, counts);
+  add_sites(ref, call, kernel_has, ~0ull, counts);          // (- 1)
+  for (uint64_t q = 0; q < n_queries; q++) copies[q] = counts[call.of_query[(size_t)q]];
   return CALITAS_OK;
 }

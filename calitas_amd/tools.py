@@ -395,11 +395,40 @@ def guide_scores(ctx, guides, params, model, batch=64):
     return got
 
 
-def guides_tsv(rows, tables=None, scores=None):
+COPIES_MAX_QUERIES = 1 << 24                 # what one calitas_count_copies call takes
+
+
+def guide_copies(ctx, pattern, rows, key_length=None, host=False):
+    """Context.count_copies for the GuideSites of find_guides: per row the number of sites of `pattern` in the WHOLE resident reference
+    -- whatever region the rows were listed in -- whose protospacer (key_length None) or PAM-proximal key_length bases equal the
+    row's, the row's own site among them.  A list of ints aligned with rows."""
+    if not isinstance(pattern, Guide):
+        pattern = Guide(pattern)
+    L = pattern.protospacer_length
+    K = L if key_length is None else int(key_length)
+    if not 1 <= K <= L:
+        raise ValueError("the key length is 1 .. %d (the protospacer's length), not %d" % (L, K))
+    five = pattern.pam_is_five_prime and bool(pattern.pams)
+    keys = []
+    for r in rows:
+        proto = r.guide[len(r.guide) - L:] if five else r.guide[:L]
+        keys.append(proto[:K] if five else proto[L - K:])
+    out = []
+    for at in range(0, len(keys), COPIES_MAX_QUERIES):           # the queries are independent: a call's worth at a time
+        out += [int(x) for x in ctx.count_copies(pattern, keys[at:at + COPIES_MAX_QUERIES], key_length=K, host=host)]
+    return out
+
+
+def guides_tsv(rows, tables=None, scores=None, copies=None, seed_copies=None):
     """The FindGuides table: GUIDE_COLUMNS, one row per GuideSite; with tables (guide_counts) also hits -- the table's sum -- and
     hits_mm0 .. hits_mmE, the hits per number of protospacer mismatches, summed over strands, gaps and PAM mismatches; with scores
-    (guide_scores) those columns come from the same pass's tables and perfect and specificity (%.6f) follow them."""
+    (guide_scores) those columns come from the same pass's tables and perfect and specificity (%.6f) follow them.  copies,
+    seed_copies: lists aligned with rows (guide_copies) -- the columns of those names, directly behind pam_sequence."""
     header = list(GUIDE_COLUMNS)
+    if copies is not None:
+        header.append("copies")
+    if seed_copies is not None:
+        header.append("seed_copies")
     n_mm = 0
     if scores is not None:
         tables = {g: s.table for g, s in scores.items()}
@@ -409,8 +438,12 @@ def guides_tsv(rows, tables=None, scores=None):
     if scores is not None:
         header += ["perfect", "specificity"]
     lines = ["\t".join(header)]
-    for r in rows:
+    for i, r in enumerate(rows):
         f = [str(x) for x in r.row()]
+        if copies is not None:
+            f.append(str(int(copies[i])))
+        if seed_copies is not None:
+            f.append(str(int(seed_copies[i])))
         if tables is not None:
             t = tables[r.guide]
             f += [str(int(t.sum()))] + [str(int(t[:, m].sum())) if m < t.shape[1] else "0" for m in range(n_mm)]
@@ -451,12 +484,16 @@ def site_filter_of_flags(L, gc_min=None, gc_max=None, max_run=None, avoid=()):
 
 
 def find_guides_tool(ref, pattern, auxiliary_pams=(), chrom=None, start=0, end=None, output=None, counts=False, device=0, scores=None,
-                     gc_min=None, gc_max=None, max_run=None, avoid=(), **search):
+                     gc_min=None, gc_max=None, max_run=None, avoid=(), copies=False, seed_copies=None, max_copies=None, max_seed_copies=None,
+                     **search):
     """`python -m calitas_amd FindGuides`: the guides of a region as a TSV (guides_tsv); counts=True: every distinct guide also goes
     through the off-target search with the SearchReference flags in `search` (make_params names); scores=ScoreModel (or its file):
     through search_scores_batch instead, which adds perfect and specificity.  gc_min, gc_max, max_run, avoid: the site filter's flags
     (site_filter_of_flags) -- fewer rows, the same columns and guide_ids, and only the kept guides are searched.  device -1: the host
-    twin of the enumeration (no GPU; not with counts or scores).  Returns the text."""
+    twin of the enumeration (no GPU; not with counts or scores).  copies=True: the column copies (guide_copies over the whole
+    reference); seed_copies=K: the column seed_copies, the same for the PAM-proximal K bases; max_copies=N (implies copies) and
+    max_seed_copies=N (needs seed_copies) drop the rows with more than N before anything is searched, the kept rows keep their
+    guide_ids.  These four work with device -1 through the host twin.  Returns the text."""
     if (counts or scores is not None) and device < 0:
         raise ValueError("--counts and --scores search on the GPU: they cannot run with --device -1")
     if isinstance(scores, str):
@@ -464,13 +501,28 @@ def find_guides_tool(ref, pattern, auxiliary_pams=(), chrom=None, start=0, end=N
         scores = ScoreModel.read(scores)
     pat = Guide(pattern, auxiliary_pams)
     keep = site_filter_of_flags(pat.protospacer_length, gc_min, gc_max, max_run, avoid)
+    if seed_copies is not None and not 1 <= int(seed_copies) <= pat.protospacer_length:
+        raise ValueError("--seed-copies K: K is 1 .. %d, the protospacer's length" % pat.protospacer_length)
+    if max_copies is not None and int(max_copies) < 1:
+        raise ValueError("--max-copies N: N is at least 1 (a guide counts itself)")
+    if max_seed_copies is not None and seed_copies is None:
+        raise ValueError("--max-seed-copies requires --seed-copies K")
+    if max_seed_copies is not None and int(max_seed_copies) < 1:
+        raise ValueError("--max-seed-copies N: N is at least 1 (a guide counts itself)")
     ctx = Context(device)
     try:
         ctx.set_reference_fasta(ref)
         rows = find_guides(ctx, pat, chrom, start, end, host=device < 0, filter=keep)
+        n_copies = guide_copies(ctx, pat, rows, host=device < 0) if copies or max_copies is not None else None
+        n_seed = guide_copies(ctx, pat, rows, key_length=int(seed_copies), host=device < 0) if seed_copies is not None else None
+        kept = [i for i in range(len(rows)) if (max_copies is None or n_copies[i] <= int(max_copies)) and
+                (max_seed_copies is None or n_seed[i] <= int(max_seed_copies))]
+        rows = [rows[i] for i in kept]
+        n_copies = None if n_copies is None else [n_copies[i] for i in kept]
+        n_seed = None if n_seed is None else [n_seed[i] for i in kept]
         tables = guide_counts(ctx, [r.guide for r in rows], make_params(**search)) if counts and scores is None else None
         scored = guide_scores(ctx, [r.guide for r in rows], make_params(**search), scores) if scores is not None else None
-        text = guides_tsv(rows, tables, scored)
+        text = guides_tsv(rows, tables, scored, copies=n_copies, seed_copies=n_seed)
         if output is not None:
             with open(output, "w") as f:
                 f.write(text)

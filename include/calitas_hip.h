@@ -339,6 +339,27 @@ int calitas_count_sites_filtered(calitas_ctx* ctx, const calitas_guide_t* patter
 int calitas_find_sites_filtered_host(const calitas_ctx* ctx, const calitas_guide_t* pattern, const calitas_site_filter_t* filter,
                                      int32_t chrom_index, uint64_t start, uint64_t end, calitas_site_t** sites, uint64_t* n_sites);
 
+/* Copies: how often a guide's protospacer -- or its PAM-proximal seed -- stands next to a PAM of the pattern, exactly.  The KEY of a site
+ * is its protospacer as the guide reads it on the site's strand (upper case, U as T, L bases: what a guide cut from the site is made
+ * of), cut to its PAM-proximal K bases: the last K for a 3' PAM and for a PAM-less pattern, the first K for a 5' PAM; K = L is the
+ * whole protospacer.  The PAM is no part of the key: copies next to different PAMs of the pattern count alike.
+ * copies[i] is the number of sites the unfiltered calitas_count_sites(pattern, chrom_index, start, end) counts whose key equals query i
+ * -- the region rules, absent contigs, one site per (contig, strand, protospacer start) and a U in the footprint as there -- so a guide
+ * cut from the resident reference has at least 1, itself.  queries: n_queries * K letters A C G T in either case (U as T), one query
+ * after the other without terminators; key_length: K, 0 meaning L.  Duplicated queries each get the full count; a query no site carries
+ * gets 0, one the pattern's own protospacer letters exclude among them; n_queries == 0 is legal.  Counts are 64-bit integers added in
+ * any order: every path gives the same numbers, and the counts of disjoint contig sets add up element by element.
+ * CALITAS_EINVAL, with a message that names the field or the query's index: key_length < 0 or > L; n_queries above 16777216 (2^24; the
+ * queries are independent: count them in pieces); a query letter outside ACGTUacgtu; and what calitas_count_sites refuses.
+ * Runs on the device: one pass of calitas_count_sites' match, every site's key looked up in a hash table of the distinct queries, one
+ * copy-back of their counters.  CALITAS_ENODEV on a host-only context.  No reference counterpart. */
+int calitas_count_copies(calitas_ctx* ctx, const calitas_guide_t* pattern, int32_t key_length, int32_t chrom_index, uint64_t start, uint64_t end,
+                         const char* queries, uint64_t n_queries, uint64_t* copies);
+/* The host twin of calitas_count_copies: the same numbers from a base-by-base walk over the packed reference of the context, which may
+ * be host-only -- the second implementation the tests hold the kernel against.  No reference counterpart. */
+int calitas_count_copies_host(const calitas_ctx* ctx, const calitas_guide_t* pattern, int32_t key_length, int32_t chrom_index, uint64_t start,
+                              uint64_t end, const char* queries, uint64_t n_queries, uint64_t* copies);
+
 /* The specificity score of a guide: one number per off-target hit, summed per guide.  No reference counterpart.
  * A model for protospacers of L bases holds Q16 factors (65536 = 1.0, none above it): mismatch[L][5][5] indexed by guide position,
  * guide letter and target letter, one gap factor and one pam_mismatch factor.  Guide positions are 0-based and count the upper-case
