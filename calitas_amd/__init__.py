@@ -3,5 +3,5 @@ from .aligner import (Alignment, CalitasError, Context, Defaults, Guide, Regions
                       counts_of_rows, counts_tsv, make_params, read_counts_tsv, read_hits, score_of_row, scores_of_rows, scores_tsv,
                       class_of_row, iupac_revcomp, regions_of_rows, regions_tsv, top_of_rows, top_tsv, window_filter)
 from .tools import (GuideAlignment, GuideSite, SequentialGuideAligner, align_to_reference, find_guides, find_guides_tool,  # noqa: F401,E402
-                    guide_copies, guide_counts, guide_scores, guides_tsv, pairwise_align_sequences, read_fasta, site_filter_of_flags)
+                    guide_copies, guide_counts, guide_near, guide_scores, guides_tsv, pairwise_align_sequences, read_fasta, site_filter_of_flags)
 from .variants import prepare_vcf, read_vcf  # noqa: F401,E402

@@ -573,6 +573,30 @@ class Context:
         _lib.check(self._h, rc)
         return out[:len(queries)]
 
+    def count_near(self, pattern, queries, max_mismatches, key_length=None, chrom=None, start=0, end=None, host=False):
+        """calitas_count_near: per query the number of sites of `pattern` (as count_sites counts them, unfiltered) whose key differs from
+        it at exactly d positions, d = 0 .. M = max_mismatches (0 .. 3): a numpy uint64 array of shape (len(queries), M + 1) in the
+        queries' order.  Key, key_length and queries as in count_copies, whose result is column 0; the key has at least M + 1 bases.  A
+        Hamming count over the key next to a PAM that matches the pattern: no gaps, no PAM mismatches.  host=True: the host twin
+        (calitas_count_near_host; sites x queries comparisons), also on a host-only context."""
+        import numpy as np
+        pattern, index, start, end = self._site_region(pattern, chrom, start, end)
+        queries = [q.decode() if isinstance(q, bytes) else str(q) for q in queries]
+        K = pattern.protospacer_length if key_length is None else int(key_length)
+        M = int(max_mismatches)
+        for i, q in enumerate(queries):
+            if len(q) != K:
+                raise ValueError("queries[%d] has %d letters, the key has %d" % (i, len(q), K))
+        g = pattern.to_c()
+        row = min(max(M, 0), 3) + 1                   # (an M outside 0 .. 3 is the library's to refuse)
+        out = np.zeros((max(1, len(queries)), row), dtype=np.uint64)
+        text = "".join(queries).encode("latin-1", "replace")
+        fn = lib.calitas_count_near_host if host else lib.calitas_count_near
+        rc = fn(self._h, ctypes.byref(g), 0 if key_length is None else K, M, index, start, end, text, len(queries),
+                out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)))
+        _lib.check(self._h, rc)
+        return out[:len(queries)]
+
     @staticmethod
     def _scores_of(c):
         """A calitas_scores_t as a Scores object (the table is copied)."""

@@ -835,6 +835,20 @@ int calitas_count_copies_host(const calitas_ctx* ctx, const calitas_guide_t* pat
   return calitas_count_copies_host_impl(ctx, pattern, key_length, chrom_index, start, end, queries, n_queries, copies);
 }
 
+int calitas_count_near(calitas_ctx* ctx, const calitas_guide_t* pattern, int32_t key_length, int32_t max_mismatches, int32_t chrom_index, uint64_t start,
+                       uint64_t end, const char* queries, uint64_t n_queries, uint64_t* near) {
+  if (!ctx) return CALITAS_EINVAL;
+  if (!pattern || (n_queries && (!queries || !near))) return fail(ctx, CALITAS_EINVAL, "NULL argument");
+  return calitas_count_near_impl(ctx, pattern, key_length, max_mismatches, chrom_index, start, end, queries, n_queries, near);
+}
+
+int calitas_count_near_host(const calitas_ctx* ctx, const calitas_guide_t* pattern, int32_t key_length, int32_t max_mismatches, int32_t chrom_index,
+                            uint64_t start, uint64_t end, const char* queries, uint64_t n_queries, uint64_t* near) {
+  if (!ctx) return CALITAS_EINVAL;
+  if (!pattern || (n_queries && (!queries || !near))) return fail(const_cast<calitas_ctx*>(ctx), CALITAS_EINVAL, "NULL argument");
+  return calitas_count_near_host_impl(ctx, pattern, key_length, max_mismatches, chrom_index, start, end, queries, n_queries, near);
+}
+
 // A guide's scores as the ABI hands them over: struct, table and cells in one block of the library's.
 static calitas_scores_t* scores_block(const CountsShape& shape, const uint64_t* table, uint64_t rows, const ScoreWords& w) {
   const size_t cells = shape.cells();

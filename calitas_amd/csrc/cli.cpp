@@ -32,6 +32,8 @@ static void usage() {
     "         [--copies (the column copies: sites of the pattern in the whole reference with the row's protospacer, its own among them)]\n"
     "         [--seed-copies K (the column seed_copies: the same for the PAM-proximal K bases)]\n"
     "         [--max-copies N (drop rows with more; implies --copies)] [--max-seed-copies N (needs --seed-copies)]\n"
+    "         [--near-copies M (0 .. 3: the columns copies_mm0 .. copies_mmM, the sites whose protospacer differs at exactly that many positions)]\n"
+    "         [--max-near-copies N (drop rows whose copies_mm columns sum to more; needs --near-copies)]\n"
     "         [--device N (-1: the host twin, no GPU)]\n");
 }
 
@@ -268,6 +270,8 @@ static int find_guides_main(int argc, char** argv) {
   bool filtered = false, limited = false, copies = false;
   long long seed_k = 0, max_copies = 0, max_seed_copies = 0;      // 0: the flag is not given
   bool have_seed = false, have_max = false, have_max_seed = false;
+  long long near_m = 0, max_near = 0;
+  bool have_near = false, have_max_near = false;
   for (int i = 2; i < argc; i++) {
     std::string a = argv[i], val;
     size_t eq = a.find('=');
@@ -294,6 +298,8 @@ static int find_guides_main(int argc, char** argv) {
     else if (a == "--seed-copies") { seed_k = std::atoll(next().c_str()); have_seed = true; }
     else if (a == "--max-copies") { max_copies = std::atoll(next().c_str()); have_max = copies = true; }
     else if (a == "--max-seed-copies") { max_seed_copies = std::atoll(next().c_str()); have_max_seed = true; }
+    else if (a == "--near-copies") { near_m = std::atoll(next().c_str()); have_near = true; }
+    else if (a == "--max-near-copies") { max_near = std::atoll(next().c_str()); have_max_near = true; }
     else { std::fprintf(stderr, "unknown argument %s\n", a.c_str()); usage(); return 2; }
   }
   if (pattern.empty() || ref.empty()) { usage(); return 2; }
@@ -311,6 +317,10 @@ static int find_guides_main(int argc, char** argv) {
   if (have_max && max_copies < 1) { std::fprintf(stderr, "calitas: --max-copies N: N is at least 1 (a guide counts itself)\n"); return 2; }
   if (have_max_seed && !have_seed) { std::fprintf(stderr, "calitas: --max-seed-copies requires --seed-copies K\n"); return 2; }
   if (have_max_seed && max_seed_copies < 1) { std::fprintf(stderr, "calitas: --max-seed-copies N: N is at least 1 (a guide counts itself)\n"); return 2; }
+  if (have_near && (near_m < 0 || near_m > CALITAS_NEAR_MAX_MISMATCHES)) { std::fprintf(stderr, "calitas: --near-copies M: M is 0 .. %d\n", CALITAS_NEAR_MAX_MISMATCHES); return 2; }
+  if (have_near && (long long)pg.proto.size() < near_m + 1) { std::fprintf(stderr, "calitas: --near-copies M: the protospacer has fewer than M + 1 bases\n"); return 2; }
+  if (have_max_near && !have_near) { std::fprintf(stderr, "calitas: --max-near-copies requires --near-copies M\n"); return 2; }
+  if (have_max_near && max_near < 1) { std::fprintf(stderr, "calitas: --max-near-copies N: N is at least 1 (a guide counts itself)\n"); return 2; }
   calitas_ctx* ctx = nullptr;
   if (calitas_create(device, &ctx) != CALITAS_OK) { std::fprintf(stderr, "calitas: %s\n", calitas_last_error(nullptr)); return 1; }
   auto die = [&](const char* what) { std::fprintf(stderr, "calitas: %s: %s\n", what, calitas_last_error(ctx)); calitas_destroy(ctx); std::exit(1); };
@@ -327,7 +337,9 @@ static int find_guides_main(int argc, char** argv) {
   if (rc != CALITAS_OK) die("finding sites");
   FILE* f = output.empty() ? stdout : std::fopen(output.c_str(), "w");
   if (!f) { std::fprintf(stderr, "cannot write %s\n", output.c_str()); calitas_free(sites); calitas_destroy(ctx); return 1; }
-  std::fprintf(f, "guide_id\tchromosome\tstart\tend\tstrand\tpam_index\tguide\tpam_sequence%s%s\n", copies ? "\tcopies" : "", have_seed ? "\tseed_copies" : "");
+  std::fprintf(f, "guide_id\tchromosome\tstart\tend\tstrand\tpam_index\tguide\tpam_sequence%s%s", copies ? "\tcopies" : "", have_seed ? "\tseed_copies" : "");
+  for (long long d = 0; have_near && d <= near_m; d++) std::fprintf(f, "\tcopies_mm%lld", d);
+  std::fprintf(f, "\n");
   auto on_strand = [](std::string t, bool minus) {     // upper-case bases as fetched; '-': their reverse complement
     if (!minus) return t;
     std::string o(t.rbegin(), t.rend());
@@ -362,8 +374,28 @@ static int find_guides_main(int argc, char** argv) {
   std::vector<uint64_t> n_copies, n_seed;
   if (copies) count(L, n_copies);
   if (have_seed) count(seed_k, n_seed);
+  // the whole protospacers within near_m substitutions (tools.py guide_near): rows of near_m + 1 counts
+  const size_t near_row = (size_t)near_m + 1;
+  std::vector<uint64_t> n_near;
+  if (have_near) {
+    std::string keys;
+    for (const std::string& p : protos) keys += p;
+    n_near.assign(((size_t)n_sites + 1) * near_row, 0);
+    const uint64_t most = 1ull << 24;
+    for (uint64_t at = 0; at < n_sites; at += most) {
+      const uint64_t n = std::min(most, n_sites - at);
+      const int rc2 = device < 0 ? calitas_count_near_host(ctx, &g, (int32_t)L, (int32_t)near_m, -1, 0, 0, keys.data() + at * (uint64_t)L, n, n_near.data() + at * near_row)
+                                 : calitas_count_near(ctx, &g, (int32_t)L, (int32_t)near_m, -1, 0, 0, keys.data() + at * (uint64_t)L, n, n_near.data() + at * near_row);
+      if (rc2 != CALITAS_OK) die("counting near copies");
+    }
+  }
   uint64_t n_rows = 0;
   for (uint64_t i = 0; i < n_sites; i++) {
+    if (have_max_near) {
+      uint64_t sum = 0;
+      for (size_t d = 0; d < near_row; d++) sum += n_near[(size_t)i * near_row + d];
+      if (sum > (uint64_t)max_near) continue;
+    }
     if (have_max && n_copies[(size_t)i] > (uint64_t)max_copies) continue;
     if (have_max_seed && n_seed[(size_t)i] > (uint64_t)max_seed_copies) continue;
     n_rows++;
@@ -379,6 +411,7 @@ static int find_guides_main(int argc, char** argv) {
                  (char)s.strand, (int)s.pam_index, guide.c_str(), pam.c_str());
     if (copies) std::fprintf(f, "\t%llu", (unsigned long long)n_copies[(size_t)i]);
     if (have_seed) std::fprintf(f, "\t%llu", (unsigned long long)n_seed[(size_t)i]);
+    for (size_t d = 0; have_near && d < near_row; d++) std::fprintf(f, "\t%llu", (unsigned long long)n_near[(size_t)i * near_row + d]);
     std::fprintf(f, "\n");
   }
   if (f != stdout) std::fclose(f);

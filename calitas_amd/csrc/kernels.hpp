@@ -157,10 +157,25 @@ struct SitesArgs {
   SiteRecord* out;                 // pass 2
   uint64_t out_capacity;
   // copies_kernel only (calitas_count_copies): the table of the caller's distinct query keys
-  const uint64_t* keys;            // open addressing, table_mask + 1 slots (a power of two, at most half of them taken), COPIES_EMPTY: free
-  const uint32_t* key_index;       // per taken slot: the key's index among the distinct keys
+  // (the near kernel's tables take the places of the copies table's: the two kernels never run in one launch, and the argument block
+  // every sites_kernel is launched with stays the size it was)
+  union {
+    const uint64_t* keys;          // open addressing, table_mask + 1 slots (a power of two, at most half of them taken), COPIES_EMPTY: free
+    const uint32_t* near_offsets;  // near kernel: near_m + 1 bucket tables of 4^near_w + 1 offsets each, one behind the other: the members of
+  };                               // piece p's bucket b are near_members[o[b] .. o[b + 1]), o = near_offsets + p (4^near_w + 1)
+  union {
+    const uint32_t* key_index;     // per taken slot: the key's index among the distinct keys
+    const uint4* near_members;     // near kernel: {the key's low plane, its high plane, its index among the distinct keys, 0}: every key
+  };                               // once per piece
   unsigned long long* key_counts;  // per distinct key: its sites, zero at launch; [n_keys]: the call's error flag
-  uint32_t table_mask, table_shift;   // a key's first slot is (key * COPIES_HASH) >> table_shift
+                                   // near kernel: n_keys rows of near_m + 1 counters, zero at launch, and no flag
+  union {
+    struct { uint32_t table_mask, table_shift; };   // a key's first slot is (key * COPIES_HASH) >> table_shift
+    struct {                       // near kernel (calitas_count_near; it reads n_keys, key_len and key_first as well)
+      int32_t near_m;              // M, 0 .. NEAR_MAX_M
+      int32_t near_w;              // bases per piece, 1 .. NEAR_MAX_W: piece p is the key's positions [p w, (p + 1) w)
+    };
+  };
   uint32_t n_keys;
   uint32_t ones_index;             // the index of the key COPIES_EMPTY itself (all T at K = 32), COPIES_NONE when it is no query
   int32_t key_len;                 // K, 1 .. proto_len
@@ -188,5 +203,21 @@ constexpr uint32_t COPIES_NONE = 0xFFFFFFFFu;
 constexpr uint32_t COPIES_MIN_SLOTS = 16;
 // one pass of the unfiltered match; every site's key looked up, a hit adds 1 to its key's counter
 hipError_t launch_sites_copies(const SitesArgs& a, hipStream_t stream);
+
+// calitas_count_near: the query keys within M substitutions of a site's key.  The key's K positions are cut into M + 1 disjoint PIECES of
+// w = min(K / (M + 1), NEAR_MAX_W) bases from position 0 on (what is left over belongs to no piece): M substitutions leave one piece
+// as it was, so every query within M of a site stands in the bucket one of the site's pieces names -- a bucket per value of a piece's
+// 2 w bits, addressed directly.
+constexpr int NEAR_MAX_M = 3;
+constexpr int NEAR_MAX_W = 8;                               // 4^8 + 1 = 65 537 offsets per piece
+CAL_HD inline int near_piece_width(int K, int M) { const int w = K / (M + 1); return w < NEAR_MAX_W ? w : NEAR_MAX_W; }
+// the bucket of a key's piece: the piece's w bits of the low plane, above them those of the high plane
+CAL_HD inline uint32_t near_bucket(uint32_t k_lo, uint32_t k_hi, int p, int w) {
+  const uint32_t m = (1u << w) - 1u;
+  return ((k_lo >> (p * w)) & m) | (((k_hi >> (p * w)) & m) << w);
+}
+// one pass of the unfiltered match; every site's key held against the members of its M + 1 buckets, a query at distance d <= M adds 1
+// to its counter d
+hipError_t launch_sites_near(const SitesArgs& a, hipStream_t stream);
 
 }  // namespace calitas

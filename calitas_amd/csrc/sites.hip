@@ -16,9 +16,11 @@
 // Output in order, without a sort and without a returning atomic: pass 1 stores one count per segment, a one-workgroup scan turns
 // the counts into offsets, pass 2 recomputes the vectors and every lane writes its records at offset + prefix (a DPP prefix sum per
 // wave, the waves' sums through LDS); the '+' and '-' record of one position are neighbours.
-// COPIES (calitas_count_copies): the copies kernel, sites_kernel<false, false, true>, is the first pass's match with another ending -- instead of being counted, every site of the
+// COPIES (calitas_count_copies): the copies kernel, sites_kernel<false, false, KEYS_EXACT>, is the first pass's match with another ending -- instead of being counted, every site of the
 // lane's word gives its KEY (copies_key: the PAM-proximal K bases as the guide reads, from the chain registers), which is looked up in the
 // caller's table of query keys; a hit adds 1 to that key's counter (count_keys).
+// NEAR (calitas_count_near): the near kernel, sites_kernel<false, false, KEYS_NEAR>, is the same match with a third ending -- the key is
+// held against the query keys that share one of its M + 1 pieces, and a query at Hamming distance d <= M gets 1 in its counter d (near_keys).
 // FILTER (calitas_find_sites_filtered): a keep vector per strand from the same registers -- G + C count, base runs and motifs of the
 // protospacer, chain positions 32 + j .. 32 + j + L - 1 -- ANDed into the match vectors in both passes (site_keep).
 #include <hip/hip_runtime.h>
@@ -326,10 +328,56 @@ CAL_DEV void count_keys(const SitesArgs& a, const LaneSites& s, const uint32_t (
   }
 }
 
-// WRITE = false: pass 1 (counts); true: pass 2 (records).  COPIES (with neither): the match of pass 1, the sites' keys counted.  FILTER: a.pat heads a SiteTables whose filter applies.  A SEGMENT is SITES_BLOCK_WORDS consecutive words, all of one tile, one lane
+// The keys of the sites that start in the lane's word, held against the queries within M substitutions: a site per turn of the loop as
+// in count_keys.  A query within M of the key equals it in one of the M + 1 pieces at least (kernels.hpp), so it is a member of one of
+// the M + 1 buckets the key's pieces name: their offsets are loaded together, then each bucket is walked, a 16-byte member per turn.
+// m = the positions at which key and member differ (either plane), d their number.  A member at d <= M counts in the FIRST piece in
+// which it equals the key -- in piece p only if every piece before p holds a difference -- so a (site, query) pair counts once however
+// many pieces agree.  M, w and the pieces' masks are wave-uniform; both loops end at offsets the host wrote, nothing can spin.
+CAL_DEV void near_keys(const SitesArgs& a, const LaneSites& s, const uint32_t (&c_lo)[4], const uint32_t (&c_hi)[4], int L) {
+  const int K = a.key_len, M = a.near_m, w = a.near_w;
+  const bool first = a.key_first != 0;
+  const uint32_t per_table = (1u << (2 * w)) + 1u, piece = (1u << w) - 1u, row = (uint32_t)M + 1u;
+  uint32_t left_p = s.plus, left_m = s.minus;
+  while (left_p | left_m) {
+    const bool minus = left_p == 0u;
+    const uint32_t j = (uint32_t)__builtin_ctz(minus ? left_m : left_p);
+    if (minus) left_m &= left_m - 1u; else left_p &= left_p - 1u;
+    const uint64_t key = copies_key(__builtin_amdgcn_alignbit(c_lo[2], c_lo[1], j), __builtin_amdgcn_alignbit(c_hi[2], c_hi[1], j), L, K, minus, first);
+    const uint32_t k_lo = (uint32_t)key, k_hi = (uint32_t)(key >> 32);
+    uint32_t from[NEAR_MAX_M + 1], to[NEAR_MAX_M + 1];
+#pragma unroll
+    for (int p = 0; p <= NEAR_MAX_M; p++) {
+      from[p] = to[p] = 0u;
+      if (p > M) continue;
+      const uint32_t b = __builtin_amdgcn_ubfe(k_lo, (uint32_t)(p * w), (uint32_t)w) | (__builtin_amdgcn_ubfe(k_hi, (uint32_t)(p * w), (uint32_t)w) << w);
+      const uint32_t* o = a.near_offsets + (uint32_t)p * per_table + b;
+      from[p] = o[0]; to[p] = o[1];
+    }
+#pragma unroll
+    for (int p = 0; p <= NEAR_MAX_M; p++) {
+      if (p > M) break;
+      for (uint32_t i = from[p]; i < to[p]; i++) {
+        uint4 q = a.near_members[i];
+        // (one 16-byte load: left alone the compiler fetches the planes first and the index in a second, dependent load once the member counts)
+        asm volatile("" : "+v"(q.x), "+v"(q.y), "+v"(q.z), "+v"(q.w));
+        const uint32_t m = (k_lo ^ q.x) | (k_hi ^ q.y);
+        const uint32_t d = (uint32_t)__builtin_popcount(m);
+        bool counts = d <= (uint32_t)M;
+#pragma unroll
+        for (int e = 0; e < NEAR_MAX_M; e++)
+          if (e < p) counts = counts && (m & (piece << (e * w))) != 0u;
+        if (counts) (void)atomicAdd(&a.key_counts[q.z * row + d], 1ull);
+      }
+    }
+  }
+}
+
+// WRITE = false: pass 1 (counts); true: pass 2 (records).  KEYS (with neither): the match of pass 1 with the sites' keys looked up, KEYS_EXACT in the copies table (count_keys), KEYS_NEAR in the near buckets (near_keys).  FILTER: a.pat heads a SiteTables whose filter applies.  A SEGMENT is SITES_BLOCK_WORDS consecutive words, all of one tile, one lane
 // per word; it is the unit of the counts and offsets.  A workgroup takes segs_per_wg consecutive segments, the next one's words on
 // their way from memory while it matches the current one's (a workgroup per segment is bound by the rate at which workgroups start).
-template <bool WRITE, bool FILTER, bool COPIES = false>
+constexpr int KEYS_NONE = 0, KEYS_EXACT = 1, KEYS_NEAR = 2;
+template <bool WRITE, bool FILTER, int KEYS = KEYS_NONE>
 __global__ __launch_bounds__(SITES_BLOCK_WORDS) void sites_kernel(SitesArgs a) {
   __shared__ uint32_t s_lo[SITES_BLOCK_WORDS + 3], s_hi[SITES_BLOCK_WORDS + 3], s_ex[SITES_BLOCK_WORDS + 3];
   __shared__ uint32_t s_wave[SITES_BLOCK_WORDS / 64];
@@ -364,7 +412,7 @@ __global__ __launch_bounds__(SITES_BLOCK_WORDS) void sites_kernel(SitesArgs a) {
   for (uint32_t seg = seg0; seg < seg1; seg++) {
     const TileInfo ti = tile_of(seg);
     if (!live(ti)) {
-      if (!WRITE && !COPIES && tid == 0) a.wg_count[seg] = 0u;
+      if (!WRITE && KEYS == KEYS_NONE && tid == 0) a.wg_count[seg] = 0u;
       f = fetch(seg + 1);
       continue;
     }
@@ -385,8 +433,9 @@ __global__ __launch_bounds__(SITES_BLOCK_WORDS) void sites_kernel(SitesArgs a) {
     const int64_t r_end = (int64_t)((a.end == 0 || a.end > ci.len) ? ci.len : a.end);
     const int64_t base0 = (int64_t)((wb + tid) * 32u) - (int64_t)ci.gbase;
     const LaneSites s = match_word<FILTER>(pat, c_lo, c_hi, c_ex, base0, r_start, r_end);
-    if constexpr (COPIES) {
-      count_keys(a, s, c_lo, c_hi, pat->proto_len);
+    if constexpr (KEYS != KEYS_NONE) {
+      if constexpr (KEYS == KEYS_NEAR) near_keys(a, s, c_lo, c_hi, pat->proto_len);
+      else count_keys(a, s, c_lo, c_hi, pat->proto_len);
       __syncthreads();                                      // (every lane has its chain out of LDS before the next segment goes in)
       continue;
     }
@@ -433,7 +482,7 @@ __global__ __launch_bounds__(SITES_BLOCK_WORDS) void sites_kernel(SitesArgs a) {
       }
     }
   }
-  if (!WRITE && !COPIES && tid == 0) flush_totals();
+  if (!WRITE && KEYS == KEYS_NONE && tid == 0) flush_totals();
 }
 
 // Exclusive scan of the workgroups' counts by one workgroup: a stretch per thread, the stretches' sums scanned in LDS.
@@ -484,7 +533,14 @@ hipError_t launch_sites_write(const SitesArgs& a, bool filtered, hipStream_t str
 hipError_t launch_sites_copies(const SitesArgs& a, hipStream_t stream) {
   if (a.n_segs == 0) return hipSuccess;
   const uint32_t n_blocks = (a.n_segs + a.segs_per_wg - 1) / a.segs_per_wg;
-  hipLaunchKernelGGL((sites_kernel<false, false, true>), dim3(n_blocks), dim3(SITES_BLOCK_WORDS), 0, stream, a);
+  hipLaunchKernelGGL((sites_kernel<false, false, KEYS_EXACT>), dim3(n_blocks), dim3(SITES_BLOCK_WORDS), 0, stream, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_sites_near(const SitesArgs& a, hipStream_t stream) {
+  if (a.n_segs == 0) return hipSuccess;
+  const uint32_t n_blocks = (a.n_segs + a.segs_per_wg - 1) / a.segs_per_wg;
+  hipLaunchKernelGGL((sites_kernel<false, false, KEYS_NEAR>), dim3(n_blocks), dim3(SITES_BLOCK_WORDS), 0, stream, a);
   return hipGetLastError();
 }
 

@@ -39,3 +39,8 @@ int calitas_count_copies_host_impl(const calitas_ctx* ctx, const calitas_guide_t
                                    uint64_t end, const char* queries, uint64_t n_queries, uint64_t* copies);
 int calitas_count_copies_impl(calitas_ctx* ctx, const calitas_guide_t* pattern, int32_t key_length, int32_t chrom_index, uint64_t start, uint64_t end,
                               const char* queries, uint64_t n_queries, uint64_t* copies);
+// near[i (M + 1) + d]: the sites of the unfiltered count whose key differs from query i at exactly d of its positions, d = 0 .. M = max_mismatches
+int calitas_count_near_host_impl(const calitas_ctx* ctx, const calitas_guide_t* pattern, int32_t key_length, int32_t max_mismatches, int32_t chrom_index,
+                                 uint64_t start, uint64_t end, const char* queries, uint64_t n_queries, uint64_t* near);
+int calitas_count_near_impl(calitas_ctx* ctx, const calitas_guide_t* pattern, int32_t key_length, int32_t max_mismatches, int32_t chrom_index, uint64_t start,
+                            uint64_t end, const char* queries, uint64_t n_queries, uint64_t* near);

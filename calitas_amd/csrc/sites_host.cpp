@@ -1,7 +1,8 @@
 // sites_host.cpp -- calitas_find_sites / calitas_count_sites / calitas_find_sites_host and their _filtered forms: the pattern and the
 // filter both implementations share, the host twin (a base-by-base walk over the packed reference) and the driver of sites.hip's two
 // passes.  calitas_count_copies / calitas_count_copies_host: the query keys and their table, the host twin and the driver of the copies
-// kernel.  No reference counterpart.
+// kernel.  calitas_count_near / calitas_count_near_host: the pieces' bucket tables, the host twin (plain Hamming distances, no buckets) and
+// the driver of the near kernel.  No reference counterpart.
 #include "sites.hpp"
 #include "tuning.hpp"
 
@@ -198,6 +199,11 @@ struct SitesWork {
   size_t slots_cap = 0;
   unsigned long long* d_key_counts = nullptr;
   size_t key_counts_cap = 0;
+  // calitas_count_near: the pieces' bucket tables and member lists (its counters are d_key_counts)
+  uint32_t* d_near_offsets = nullptr;
+  size_t near_offsets_cap = 0;
+  uint4* d_near_members = nullptr;
+  size_t near_members_cap = 0;
   // the U / u runs of the resident reference (a U is a plain base to a site and an exception base to the kernels)
   uint64_t u_serial = ~0ull;
   std::vector<Run> u_runs;
@@ -207,6 +213,7 @@ void sites_destroy(SitesWork* w) {
   if (!w) return;
   (void)hipFree(w->d_pat); (void)hipFree(w->d_count); (void)hipFree(w->d_off); (void)hipFree(w->d_totals); (void)hipFree(w->d_out);
   (void)hipFree(w->d_keys); (void)hipFree(w->d_key_index); (void)hipFree(w->d_key_counts);
+  (void)hipFree(w->d_near_offsets); (void)hipFree(w->d_near_members);
   delete w;
 }
 
@@ -563,5 +570,140 @@ int calitas_count_copies_impl(calitas_ctx* ctx, const calitas_guide_t* pattern, 
   add_sites(ref, call, with_u, 1, counts);
   add_sites(ref, call, kernel_has, ~0ull, counts);          // (- 1)
   for (uint64_t q = 0; q < n_queries; q++) copies[q] = counts[call.of_query[(size_t)q]];
+  return CALITAS_OK;
+}
+
+// ---- calitas_count_near: how often a guide's protospacer, or its seed, stands next to a PAM with up to M substitutions ----
+
+namespace {
+
+struct NearCall {
+  CopiesCall copies;                                 // the pattern, the region, K and the distinct query keys (plan_copies)
+  int M = 0;
+};
+
+// checked in this order: max_mismatches, what calitas_count_copies checks, K >= M + 1
+int plan_near(calitas_ctx* c, const calitas_guide_t* pattern, int32_t key_length, int32_t max_mismatches, int32_t chrom_index, uint64_t start, uint64_t end,
+              const char* queries, uint64_t n_queries, NearCall& call) {
+  static_assert(NEAR_MAX_M == CALITAS_NEAR_MAX_MISMATCHES, "the kernel unrolls what the contract allows");
+  if (max_mismatches < 0 || max_mismatches > NEAR_MAX_M)
+    return calitas_fail(c, CALITAS_EINVAL, "max_mismatches is " + std::to_string(max_mismatches) + ": it is 0 .. " + std::to_string(NEAR_MAX_M));
+  call.M = max_mismatches;
+  if (int rc = plan_copies(c, pattern, key_length, chrom_index, start, end, queries, n_queries, call.copies)) return rc;
+  if (call.copies.K < call.M + 1)
+    return calitas_fail(c, CALITAS_EINVAL, "key_length: a key of " + std::to_string(call.copies.K) + " bases is shorter than max_mismatches + 1 (" + std::to_string(call.M + 1) + ")");
+  return CALITAS_OK;
+}
+
+// the number of positions at which two keys differ: a position differs where either plane does
+inline int key_distance(uint64_t a, uint64_t b) {
+  const uint64_t x = a ^ b;
+  return __builtin_popcount((uint32_t)x | (uint32_t)(x >> 32));
+}
+
+// counts[index (M + 1) + d] += by for every record and every distinct query at distance d <= M of the record's key, query by query
+void add_near_sites(const PackedRef& ref, const NearCall& call, const std::vector<calitas_site_t>& sites, uint64_t by, std::vector<uint64_t>& counts) {
+  const size_t row = (size_t)call.M + 1;
+  for (const calitas_site_t& s : sites) {
+    const uint64_t key = key_at(ref, ref.contigs[(size_t)s.contig_index].gbase, s.protospacer_start, call.copies, s.strand == '-');
+    for (size_t k = 0; k < call.copies.keys.size(); k++) {
+      const int d = key_distance(key, call.copies.keys[k]);
+      if (d <= call.M) counts[k * row + (size_t)d] += by;
+    }
+  }
+}
+
+void near_rows(const NearCall& call, const std::vector<uint64_t>& counts, uint64_t n_queries, uint64_t* near) {
+  const size_t row = (size_t)call.M + 1;
+  for (uint64_t q = 0; q < n_queries; q++)
+    for (size_t d = 0; d < row; d++) near[q * row + d] = counts[(size_t)call.copies.of_query[(size_t)q] * row + d];
+}
+
+}  // namespace
+
+int calitas_count_near_host_impl(const calitas_ctx* ctx, const calitas_guide_t* pattern, int32_t key_length, int32_t max_mismatches, int32_t chrom_index,
+                                 uint64_t start, uint64_t end, const char* queries, uint64_t n_queries, uint64_t* near) {
+  calitas_ctx* c = const_cast<calitas_ctx*>(ctx);
+  NearCall call;
+  if (int rc = plan_near(c, pattern, key_length, max_mismatches, chrom_index, start, end, queries, n_queries, call)) return rc;
+  std::vector<uint64_t> counts(call.copies.keys.size() * ((size_t)call.M + 1), 0);
+  std::vector<calitas_site_t> found;
+  for (int i = call.copies.site.c_first; i <= call.copies.site.c_last && !call.copies.keys.empty(); i++) {
+    const uint64_t len = ctx->ref.contigs[(size_t)i].len;
+    found.clear();
+    host_sites(ctx->ref, call.copies.site.tab.pat, nullptr, i, 0, (int64_t)len, (int64_t)std::min(start, len), (int64_t)region_end(len, end), found, nullptr);
+    add_near_sites(ctx->ref, call, found, 1, counts);
+  }
+  near_rows(call, counts, n_queries, near);
+  return CALITAS_OK;
+}
+
+int calitas_count_near_impl(calitas_ctx* ctx, const calitas_guide_t* pattern, int32_t key_length, int32_t max_mismatches, int32_t chrom_index, uint64_t start,
+                            uint64_t end, const char* queries, uint64_t n_queries, uint64_t* near) {
+  if (ctx->device < 0) return calitas_fail(ctx, CALITAS_ENODEV, "host-only context: calitas_count_near needs a GPU (there is no CPU fallback; calitas_count_near_host is the host twin)");
+  NearCall call;
+  if (int rc = plan_near(ctx, pattern, key_length, max_mismatches, chrom_index, start, end, queries, n_queries, call)) return rc;
+  const PackedRef& ref = ctx->ref;
+  const std::vector<uint64_t>& keys = call.copies.keys;
+  const size_t n_keys = keys.size(), row = (size_t)call.M + 1;
+  if (n_keys == 0 || ref.contigs.empty()) {         // nothing to look up, or nothing to scan
+    for (uint64_t i = 0; i < n_queries * row; i++) near[i] = 0;
+    return CALITAS_OK;
+  }
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  if (!ctx->sites) ctx->sites = new SitesWork();
+  SitesWork* w = ctx->sites;
+  SitesArgs a{};
+  if (int rc = site_launch(ctx, call.copies.site, chrom_index, start, end, w, a)) return rc;
+
+  // per piece a bucket table in CSR form -- the offsets of piece p count from p n_keys on, so they address the one member array --
+  // and every key as a member of its bucket: a counting sort by bucket
+  const int pw = near_piece_width(call.copies.K, call.M);
+  const size_t per_table = ((size_t)1 << (2 * pw)) + 1, n_offsets = row * per_table, n_members = row * n_keys;
+  std::vector<uint32_t> offsets(n_offsets, 0);
+  std::vector<uint4> members(n_members);
+  for (size_t p = 0; p < row; p++) {
+    uint32_t* o = offsets.data() + p * per_table;
+    for (size_t k = 0; k < n_keys; k++) o[near_bucket((uint32_t)keys[k], (uint32_t)(keys[k] >> 32), (int)p, pw) + 1]++;
+    o[0] = (uint32_t)(p * n_keys);
+    for (size_t b = 1; b < per_table; b++) o[b] += o[b - 1];
+    std::vector<uint32_t> at(o, o + per_table - 1);
+    for (size_t k = 0; k < n_keys; k++)
+      members[at[near_bucket((uint32_t)keys[k], (uint32_t)(keys[k] >> 32), (int)p, pw)]++] = make_uint4((uint32_t)keys[k], (uint32_t)(keys[k] >> 32), (uint32_t)k, 0u);
+  }
+  if (w->near_offsets_cap < n_offsets) {
+    (void)hipFree(w->d_near_offsets); w->d_near_offsets = nullptr; w->near_offsets_cap = 0;
+    HIP_TRY(ctx, hipMalloc((void**)&w->d_near_offsets, n_offsets * sizeof(uint32_t)));
+    w->near_offsets_cap = n_offsets;
+  }
+  if (w->near_members_cap < n_members) {
+    (void)hipFree(w->d_near_members); w->d_near_members = nullptr; w->near_members_cap = 0;
+    if (hipMalloc((void**)&w->d_near_members, n_members * sizeof(uint4)) != hipSuccess) { (void)hipGetLastError(); return calitas_fail(ctx, CALITAS_ENOMEM, "the query keys do not fit the device: count the queries in pieces"); }
+    w->near_members_cap = n_members;
+  }
+  if (w->key_counts_cap < n_members) {
+    (void)hipFree(w->d_key_counts); w->d_key_counts = nullptr; w->key_counts_cap = 0;
+    HIP_TRY(ctx, hipMalloc((void**)&w->d_key_counts, n_members * sizeof(unsigned long long)));
+    w->key_counts_cap = n_members;
+  }
+  a.near_offsets = w->d_near_offsets; a.near_members = w->d_near_members; a.key_counts = w->d_key_counts;
+  a.near_m = call.M; a.near_w = pw; a.n_keys = (uint32_t)n_keys;
+  a.key_len = call.copies.K; a.key_first = call.copies.site.pam5 ? 1 : 0;
+
+  std::vector<uint64_t> counts(n_members, 0);
+  HIP_TRY(ctx, hipMemcpyAsync(w->d_pat, &call.copies.site.tab, sizeof(SitePatterns), hipMemcpyHostToDevice, ctx->stream));
+  HIP_TRY(ctx, hipMemcpyAsync(w->d_near_offsets, offsets.data(), n_offsets * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+  HIP_TRY(ctx, hipMemcpyAsync(w->d_near_members, members.data(), n_members * sizeof(uint4), hipMemcpyHostToDevice, ctx->stream));
+  HIP_TRY(ctx, hipMemsetAsync(w->d_key_counts, 0, n_members * sizeof(unsigned long long), ctx->stream));
+  HIP_TRY(ctx, launch_sites_near(a, ctx->stream));
+  HIP_TRY(ctx, hipMemcpyAsync(counts.data(), w->d_key_counts, n_members * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+
+  // a U is a T to a site and an exception base to the kernel: the sites it did not see in, the records it saw in their place out
+  std::vector<calitas_site_t> with_u, kernel_has;
+  sites_with_u(ctx, call.copies.site, start, end, with_u, kernel_has);
+  add_near_sites(ref, call, with_u, 1, counts);
+  add_near_sites(ref, call, kernel_has, ~0ull, counts);     // (- 1)
+  near_rows(call, counts, n_queries, near);
   return CALITAS_OK;
 }

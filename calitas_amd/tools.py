@@ -419,16 +419,41 @@ def guide_copies(ctx, pattern, rows, key_length=None, host=False):
     return out
 
 
-def guides_tsv(rows, tables=None, scores=None, copies=None, seed_copies=None):
+def guide_near(ctx, pattern, rows, max_mismatches, key_length=None, host=False):
+    """Context.count_near for the GuideSites of find_guides: per row the numbers of sites of `pattern` in the WHOLE resident reference
+    whose protospacer (key_length None) or PAM-proximal key_length bases differ from the row's at exactly 0 .. max_mismatches
+    positions, the row's own site in column 0.  A list of lists of ints aligned with rows."""
+    if not isinstance(pattern, Guide):
+        pattern = Guide(pattern)
+    L = pattern.protospacer_length
+    K = L if key_length is None else int(key_length)
+    if not 1 <= K <= L:
+        raise ValueError("the key length is 1 .. %d (the protospacer's length), not %d" % (L, K))
+    five = pattern.pam_is_five_prime and bool(pattern.pams)
+    keys = []
+    for r in rows:
+        proto = r.guide[len(r.guide) - L:] if five else r.guide[:L]
+        keys.append(proto[:K] if five else proto[L - K:])
+    out = []
+    for at in range(0, len(keys), COPIES_MAX_QUERIES):           # the queries are independent: a call's worth at a time
+        out += [[int(x) for x in row] for row in ctx.count_near(pattern, keys[at:at + COPIES_MAX_QUERIES], max_mismatches, key_length=K, host=host)]
+    return out
+
+
+def guides_tsv(rows, tables=None, scores=None, copies=None, seed_copies=None, near=None):
     """The FindGuides table: GUIDE_COLUMNS, one row per GuideSite; with tables (guide_counts) also hits -- the table's sum -- and
     hits_mm0 .. hits_mmE, the hits per number of protospacer mismatches, summed over strands, gaps and PAM mismatches; with scores
     (guide_scores) those columns come from the same pass's tables and perfect and specificity (%.6f) follow them.  copies,
-    seed_copies: lists aligned with rows (guide_copies) -- the columns of those names, directly behind pam_sequence."""
+    seed_copies: lists aligned with rows (guide_copies) -- the columns of those names, directly behind pam_sequence.  near: a list of
+    rows of M + 1 counts aligned with rows (guide_near), or an array of that shape -- the columns copies_mm0 .. copies_mmM behind those."""
     header = list(GUIDE_COLUMNS)
     if copies is not None:
         header.append("copies")
     if seed_copies is not None:
         header.append("seed_copies")
+    if near is not None:
+        # (an array of shape (n, M + 1) names its columns without a row; a list of rows needs one)
+        header += ["copies_mm%d" % d for d in range(near.shape[1] if hasattr(near, "shape") else len(near[0]) if len(near) else 0)]
     n_mm = 0
     if scores is not None:
         tables = {g: s.table for g, s in scores.items()}
@@ -444,6 +469,8 @@ def guides_tsv(rows, tables=None, scores=None, copies=None, seed_copies=None):
             f.append(str(int(copies[i])))
         if seed_copies is not None:
             f.append(str(int(seed_copies[i])))
+        if near is not None:
+            f += [str(int(x)) for x in near[i]]
         if tables is not None:
             t = tables[r.guide]
             f += [str(int(t.sum()))] + [str(int(t[:, m].sum())) if m < t.shape[1] else "0" for m in range(n_mm)]
@@ -485,7 +512,7 @@ def site_filter_of_flags(L, gc_min=None, gc_max=None, max_run=None, avoid=()):
 
 def find_guides_tool(ref, pattern, auxiliary_pams=(), chrom=None, start=0, end=None, output=None, counts=False, device=0, scores=None,
                      gc_min=None, gc_max=None, max_run=None, avoid=(), copies=False, seed_copies=None, max_copies=None, max_seed_copies=None,
-                     **search):
+                     near_copies=None, max_near_copies=None, **search):
     """`python -m calitas_amd FindGuides`: the guides of a region as a TSV (guides_tsv); counts=True: every distinct guide also goes
     through the off-target search with the SearchReference flags in `search` (make_params names); scores=ScoreModel (or its file):
     through search_scores_batch instead, which adds perfect and specificity.  gc_min, gc_max, max_run, avoid: the site filter's flags
@@ -493,7 +520,9 @@ def find_guides_tool(ref, pattern, auxiliary_pams=(), chrom=None, start=0, end=N
     twin of the enumeration (no GPU; not with counts or scores).  copies=True: the column copies (guide_copies over the whole
     reference); seed_copies=K: the column seed_copies, the same for the PAM-proximal K bases; max_copies=N (implies copies) and
     max_seed_copies=N (needs seed_copies) drop the rows with more than N before anything is searched, the kept rows keep their
-    guide_ids.  These four work with device -1 through the host twin.  Returns the text."""
+    guide_ids.  near_copies=M (0 .. 3): the columns copies_mm0 .. copies_mmM (guide_near over the whole reference, the whole
+    protospacer); max_near_copies=N (N >= 1, needs near_copies) drops the rows whose columns sum to more than N, likewise before
+    anything is searched.  These six work with device -1 through the host twin.  Returns the text."""
     if (counts or scores is not None) and device < 0:
         raise ValueError("--counts and --scores search on the GPU: they cannot run with --device -1")
     if isinstance(scores, str):
@@ -509,20 +538,33 @@ def find_guides_tool(ref, pattern, auxiliary_pams=(), chrom=None, start=0, end=N
         raise ValueError("--max-seed-copies requires --seed-copies K")
     if max_seed_copies is not None and int(max_seed_copies) < 1:
         raise ValueError("--max-seed-copies N: N is at least 1 (a guide counts itself)")
+    if near_copies is not None and not 0 <= int(near_copies) <= 3:
+        raise ValueError("--near-copies M: M is 0 .. 3")
+    if near_copies is not None and pat.protospacer_length < int(near_copies) + 1:
+        raise ValueError("--near-copies M: the protospacer has fewer than M + 1 bases")
+    if max_near_copies is not None and near_copies is None:
+        raise ValueError("--max-near-copies requires --near-copies M")
+    if max_near_copies is not None and int(max_near_copies) < 1:
+        raise ValueError("--max-near-copies N: N is at least 1 (a guide counts itself)")
     ctx = Context(device)
     try:
         ctx.set_reference_fasta(ref)
         rows = find_guides(ctx, pat, chrom, start, end, host=device < 0, filter=keep)
         n_copies = guide_copies(ctx, pat, rows, host=device < 0) if copies or max_copies is not None else None
         n_seed = guide_copies(ctx, pat, rows, key_length=int(seed_copies), host=device < 0) if seed_copies is not None else None
+        n_near = guide_near(ctx, pat, rows, int(near_copies), host=device < 0) if near_copies is not None else None
         kept = [i for i in range(len(rows)) if (max_copies is None or n_copies[i] <= int(max_copies)) and
-                (max_seed_copies is None or n_seed[i] <= int(max_seed_copies))]
+                (max_seed_copies is None or n_seed[i] <= int(max_seed_copies)) and
+                (max_near_copies is None or sum(n_near[i]) <= int(max_near_copies))]
         rows = [rows[i] for i in kept]
         n_copies = None if n_copies is None else [n_copies[i] for i in kept]
         n_seed = None if n_seed is None else [n_seed[i] for i in kept]
+        if n_near is not None:
+            import numpy as np
+            n_near = np.array([n_near[i] for i in kept], dtype=np.uint64).reshape(len(kept), int(near_copies) + 1)
         tables = guide_counts(ctx, [r.guide for r in rows], make_params(**search)) if counts and scores is None else None
         scored = guide_scores(ctx, [r.guide for r in rows], make_params(**search), scores) if scores is not None else None
-        text = guides_tsv(rows, tables, scored, copies=n_copies, seed_copies=n_seed)
+        text = guides_tsv(rows, tables, scored, copies=n_copies, seed_copies=n_seed, near=n_near)
         if output is not None:
             with open(output, "w") as f:
                 f.write(text)

@@ -360,6 +360,32 @@ int calitas_count_copies(calitas_ctx* ctx, const calitas_guide_t* pattern, int32
 int calitas_count_copies_host(const calitas_ctx* ctx, const calitas_guide_t* pattern, int32_t key_length, int32_t chrom_index, uint64_t start,
                               uint64_t end, const char* queries, uint64_t n_queries, uint64_t* copies);
 
+/* Near copies: how often a guide's protospacer -- or its seed -- stands next to a PAM of the pattern with up to M = max_mismatches
+ * substitutions, 0 <= M <= CALITAS_NEAR_MAX_MISMATCHES.  Key, K, key_length (0 = L), the queries' letters, the region rules, absent contigs,
+ * one site per (contig, strand, protospacer start) and a U in the footprint are exactly those of calitas_count_copies, and the sites
+ * are those the unfiltered calitas_count_sites(pattern, chrom_index, start, end) counts.  K >= M + 1.
+ * near has n_queries * (M + 1) entries: near[i * (M + 1) + d] is the number of sites whose key differs from query i at exactly d of
+ * its K positions, d = 0 .. M -- a Hamming count over the key.  The PAM is no part of the key: any PAM of the pattern qualifies a site,
+ * and it has to match the pattern as it does for calitas_find_sites (no PAM mismatches).  There are no gaps, and overlapping sites
+ * are not merged (no removeOverlaps): this is not calitas_search's gapped alignment, which remains the tool for that question.
+ * What holds: column 0 (d = 0) equals calitas_count_copies of the same arguments; duplicated queries each get the full row; a site
+ * counts for every query it is near, so two queries one substitution apart see each other's sites in column 1; the counts of disjoint
+ * contig sets add up element by element; counts are 64-bit integers added in any order, so every path returns the same numbers.
+ * CALITAS_EINVAL, with a message that names the field or the query's index: max_mismatches outside 0 .. 3; key_length (K) below
+ * max_mismatches + 1; and what calitas_count_copies refuses, its limit of 16777216 (2^24) queries among them.
+ * Runs on the device: one pass of calitas_count_sites' match; the key is cut into M + 1 pieces, of which M substitutions leave one
+ * untouched, and every site's key is held against the distinct queries that share a piece with it (a directly addressed bucket table
+ * per piece, no hash table); one copy-back of the counters.  CALITAS_ENOMEM when the tables do not fit the device.  CALITAS_ENODEV on a
+ * host-only context.  No reference counterpart. */
+#define CALITAS_NEAR_MAX_MISMATCHES 3
+int calitas_count_near(calitas_ctx* ctx, const calitas_guide_t* pattern, int32_t key_length, int32_t max_mismatches, int32_t chrom_index,
+                       uint64_t start, uint64_t end, const char* queries, uint64_t n_queries, uint64_t* near);
+/* The host twin of calitas_count_near: the same numbers from a base-by-base walk over the packed reference of the context, which may be
+ * host-only, every site's key compared with every distinct query by plain Hamming distance (no buckets) -- the second implementation
+ * the tests hold the kernel against; its cost is sites x distinct queries.  No reference counterpart. */
+int calitas_count_near_host(const calitas_ctx* ctx, const calitas_guide_t* pattern, int32_t key_length, int32_t max_mismatches, int32_t chrom_index,
+                            uint64_t start, uint64_t end, const char* queries, uint64_t n_queries, uint64_t* near);
+
 /* The specificity score of a guide: one number per off-target hit, summed per guide.  No reference counterpart.
  * A model for protospacers of L bases holds Q16 factors (65536 = 1.0, none above it): mismatch[L][5][5] indexed by guide position,
  * guide letter and target letter, one gap factor and one pam_mismatch factor.  Guide positions are 0-based and count the upper-case
