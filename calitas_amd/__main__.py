@@ -98,6 +98,8 @@ def main(argv=None):
     fg.add_argument("--near-copies", metavar="M", type=int,
                     help="add copies_mm0 .. copies_mmM: the sites of the pattern in the whole reference whose protospacer differs from this row's at exactly that many positions (M is 0 .. 3)")
     fg.add_argument("--max-near-copies", metavar="N", type=int, help="drop guides whose copies_mm columns sum to more than N (N >= 1; needs --near-copies)")
+    fg.add_argument("--near-scores", metavar="MODEL",
+                    help="with --near-copies M: score every row's near copies under the model file in the same pass and add near_sum_q32, near_max_q32, near_specificity")
     fg.add_argument("-d", "--max-guide-diffs", type=int, default=Defaults.MaxGuideDiffs)
     fg.add_argument("-p", "--max-pam-mismatches", type=int, default=Defaults.MaxPamMismatches)
     fg.add_argument("-g", "--max-gaps-between-guide-and-pam", type=int, default=Defaults.MaxGapsBetweenGuideAndPam)
@@ -145,7 +147,7 @@ def main(argv=None):
     elif a.tool == "FindGuides":
         text = find_guides_tool(a.ref, a.guide, a.auxiliary_pams, chrom=a.chrom, start=a.start, end=a.end, output=a.output, counts=a.counts, scores=a.scores,
                                 device=a.device, gc_min=a.gc_min, gc_max=a.gc_max, max_run=a.max_run, avoid=a.avoid, copies=a.copies,
-                                seed_copies=a.seed_copies, max_copies=a.max_copies, max_seed_copies=a.max_seed_copies, near_copies=a.near_copies, max_near_copies=a.max_near_copies, max_guide_diffs=a.max_guide_diffs, max_pam_mismatches=a.max_pam_mismatches,
+                                seed_copies=a.seed_copies, max_copies=a.max_copies, max_seed_copies=a.max_seed_copies, near_copies=a.near_copies, max_near_copies=a.max_near_copies, near_scores=a.near_scores, max_guide_diffs=a.max_guide_diffs, max_pam_mismatches=a.max_pam_mismatches,
                                 max_gaps_between_guide_and_pam=a.max_gaps_between_guide_and_pam, max_total_diffs=a.max_total_diffs,
                                 max_overlap=a.max_overlap, guide_mismatch_net_cost=a.guide_mismatch_net_cost,
                                 pam_mismatch_net_cost=a.pam_mismatch_net_cost, genome_gap_net_cost=a.genome_gap_net_cost,

@@ -115,7 +115,8 @@ SYMBOLS = ["calitas_create", "calitas_destroy", "calitas_last_error", "calitas_f
            "calitas_set_regions", "calitas_search_regions", "calitas_search_regions_batch", "calitas_hits_regions", "calitas_region_class",
            "calitas_find_sites", "calitas_count_sites", "calitas_find_sites_host",
            "calitas_find_sites_filtered", "calitas_count_sites_filtered", "calitas_find_sites_filtered_host",
-           "calitas_count_copies", "calitas_count_copies_host", "calitas_count_near", "calitas_count_near_host"]
+           "calitas_count_copies", "calitas_count_copies_host", "calitas_count_near", "calitas_count_near_host",
+           "calitas_score_near", "calitas_score_near_host"]
 
 if not os.path.exists(LIB_PATH):
     raise ImportError("%s is missing: build it with `make -C calitas_amd/csrc` (hipcc, gfx950). "
@@ -190,6 +191,10 @@ lib.calitas_count_copies_host.argtypes = lib.calitas_count_copies.argtypes
 lib.calitas_count_near.argtypes = [ctypes.c_void_p, ctypes.POINTER(GuideT), ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_uint64, ctypes.c_uint64,
                                    ctypes.c_char_p, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)]
 lib.calitas_count_near_host.argtypes = lib.calitas_count_near.argtypes
+# (scores: calitas_near_score_t[n], two uint64 each -- passed as the words of a (n, 2) array)
+lib.calitas_score_near.argtypes = [ctypes.c_void_p, ctypes.POINTER(GuideT), ctypes.c_int32, ctypes.POINTER(ScoreModelT), ctypes.c_int32, ctypes.c_uint64,
+                                   ctypes.c_uint64, ctypes.c_char_p, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]
+lib.calitas_score_near_host.argtypes = lib.calitas_score_near.argtypes
 lib.calitas_search_scores.argtypes = [ctypes.c_void_p, ctypes.POINTER(GuideT), ctypes.POINTER(ParamsT), ctypes.POINTER(ScoreModelT),
                                       ctypes.POINTER(ctypes.POINTER(ScoresT))]
 lib.calitas_search_scores_batch.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.POINTER(GuideT), ctypes.POINTER(ParamsT),

@@ -597,6 +597,31 @@ class Context:
         _lib.check(self._h, rc)
         return out[:len(queries)]
 
+    def score_near(self, pattern, queries, max_mismatches, model, chrom=None, start=0, end=None, host=False):
+        """calitas_score_near: count_near over the whole protospacer, and per query the sum and the maximum of its near copies' scores
+        under `model` (a ScoreModel of the protospacer's length; near_score is the contract on one pair) -- a NearScores.  Sites at
+        d = 0 are counted, not scored.  host=True: the host twin (calitas_score_near_host), also on a host-only context."""
+        import numpy as np
+        pattern, index, start, end = self._site_region(pattern, chrom, start, end)
+        queries = [q.decode() if isinstance(q, bytes) else str(q) for q in queries]
+        L = pattern.protospacer_length
+        M = int(max_mismatches)
+        for i, q in enumerate(queries):
+            if len(q) != L:
+                raise ValueError("queries[%d] has %d letters, the key has %d" % (i, len(q), L))
+        g = pattern.to_c()
+        m = model.to_c() if model is not None else None
+        row = min(max(M, 0), 3) + 1                   # (an M outside 0 .. 3 is the library's to refuse)
+        near = np.zeros((max(1, len(queries)), row), dtype=np.uint64)
+        words = np.zeros((max(1, len(queries)), 2), dtype=np.uint64)
+        text = "".join(queries).encode("latin-1", "replace")
+        fn = lib.calitas_score_near_host if host else lib.calitas_score_near
+        rc = fn(self._h, ctypes.byref(g), M, ctypes.byref(m) if m is not None else None, index, start, end, text, len(queries),
+                near.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), words.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)))
+        _lib.check(self._h, rc)
+        n = len(queries)
+        return NearScores(near[:n], words[:n, 0].copy(), words[:n, 1].copy())
+
     @staticmethod
     def _scores_of(c):
         """A calitas_scores_t as a Scores object (the table is copied)."""
@@ -1238,6 +1263,60 @@ def score_of_row(row, model):
     for _ in range(int(row["pam_mm"])):
         s = (s * model.pam_mismatch) >> 16
     return s
+
+
+def near_score(query, target, model):
+    """The contract of calitas_score_near on one (query, site key) pair, in plain Python integers: two strings of model.L letters
+    A C G T in either case, a U as a T; None at distance 0, else the factors of the differing positions multiplied into 2^32 in
+    ascending guide position, truncated by 16 bits at every step."""
+    q, t = query.upper().replace("U", "T"), target.upper().replace("U", "T")
+    if len(q) != model.L or len(t) != model.L:
+        raise ValueError("a pair of %d and %d letters cannot be scored by a model of length %d" % (len(q), len(t), model.L))
+    if q == t:
+        return None
+    s = 1 << 32
+    for i, (g, x) in enumerate(zip(q, t)):
+        if g != x:
+            s = (s * int(model.mismatch[i, _LETTER[g], _LETTER[x]])) >> 16
+    return s
+
+
+class NearScores:
+    """What Context.score_near returns for n queries: near (uint64, shape (n, M + 1): count_near's table over the whole protospacer),
+    sum_q32 and max_q32 (uint64, shape (n,): sum and maximum of the scores of the sites at d = 1 .. M, 2^32 = 1.0) and specificity
+    = 2^32 / (2^32 + sum_q32) as float64."""
+    __slots__ = ("near", "sum_q32", "max_q32")
+
+    def __init__(self, near, sum_q32, max_q32):
+        self.near, self.sum_q32, self.max_q32 = near, sum_q32, max_q32
+
+    @property
+    def specificity(self):
+        import numpy as np
+        return 2.0 ** 32 / (2.0 ** 32 + self.sum_q32.astype(np.float64))
+
+    def merge(self, *others):
+        """The same queries over disjoint contig sets: counts and sums add, the maxima take the maximum."""
+        import numpy as np
+        near, total, top = self.near.copy(), self.sum_q32.copy(), self.max_q32.copy()
+        for o in others:
+            if o.near.shape != near.shape:
+                raise ValueError("near scores of different queries or max_mismatches do not merge")
+            near, total, top = near + o.near, total + o.sum_q32, np.maximum(top, o.max_q32)
+        return NearScores(near, total, top)
+
+    def __add__(self, o):
+        return self.merge(o)
+
+    def __eq__(self, o):
+        import numpy as np
+        return (isinstance(o, NearScores) and self.near.shape == o.near.shape and bool(np.array_equal(self.near, o.near)) and
+                bool(np.array_equal(self.sum_q32, o.sum_q32)) and bool(np.array_equal(self.max_q32, o.max_q32)))
+
+    __hash__ = None
+
+    def __repr__(self):
+        return "NearScores(n=%d, M=%d)" % (self.near.shape[0], self.near.shape[1] - 1)
 
 
 def scores_of_rows(rows, model, shape=None):

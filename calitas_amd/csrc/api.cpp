@@ -849,6 +849,22 @@ int calitas_count_near_host(const calitas_ctx* ctx, const calitas_guide_t* patte
   return calitas_count_near_host_impl(ctx, pattern, key_length, max_mismatches, chrom_index, start, end, queries, n_queries, near);
 }
 
+// (the model is the implementation's to check: it comes after everything calitas_count_near refuses)
+int calitas_score_near(calitas_ctx* ctx, const calitas_guide_t* pattern, int32_t max_mismatches, const calitas_score_model_t* model, int32_t chrom_index,
+                       uint64_t start, uint64_t end, const char* queries, uint64_t n_queries, uint64_t* near, calitas_near_score_t* scores) {
+  if (!ctx) return CALITAS_EINVAL;
+  if (!pattern || (n_queries && (!queries || !near || !scores))) return fail(ctx, CALITAS_EINVAL, "NULL argument");
+  return calitas_score_near_impl(ctx, pattern, max_mismatches, model, chrom_index, start, end, queries, n_queries, near, scores);
+}
+
+int calitas_score_near_host(const calitas_ctx* ctx, const calitas_guide_t* pattern, int32_t max_mismatches, const calitas_score_model_t* model,
+                            int32_t chrom_index, uint64_t start, uint64_t end, const char* queries, uint64_t n_queries, uint64_t* near,
+                            calitas_near_score_t* scores) {
+  if (!ctx) return CALITAS_EINVAL;
+  if (!pattern || (n_queries && (!queries || !near || !scores))) return fail(const_cast<calitas_ctx*>(ctx), CALITAS_EINVAL, "NULL argument");
+  return calitas_score_near_host_impl(ctx, pattern, max_mismatches, model, chrom_index, start, end, queries, n_queries, near, scores);
+}
+
 // A guide's scores as the ABI hands them over: struct, table and cells in one block of the library's.
 static calitas_scores_t* scores_block(const CountsShape& shape, const uint64_t* table, uint64_t rows, const ScoreWords& w) {
   const size_t cells = shape.cells();

@@ -34,6 +34,7 @@ static void usage() {
     "         [--max-copies N (drop rows with more; implies --copies)] [--max-seed-copies N (needs --seed-copies)]\n"
     "         [--near-copies M (0 .. 3: the columns copies_mm0 .. copies_mmM, the sites whose protospacer differs at exactly that many positions)]\n"
     "         [--max-near-copies N (drop rows whose copies_mm columns sum to more; needs --near-copies)]\n"
+    "         [--near-scores model.tsv (with --near-copies: near_sum_q32 near_max_q32 near_specificity, the near copies' scores from the same pass)]\n"
     "         [--device N (-1: the host twin, no GPU)]\n");
 }
 
@@ -272,6 +273,7 @@ static int find_guides_main(int argc, char** argv) {
   bool have_seed = false, have_max = false, have_max_seed = false;
   long long near_m = 0, max_near = 0;
   bool have_near = false, have_max_near = false;
+  std::string near_scores;     // --near-scores MODEL.tsv
   for (int i = 2; i < argc; i++) {
     std::string a = argv[i], val;
     size_t eq = a.find('=');
@@ -300,6 +302,7 @@ static int find_guides_main(int argc, char** argv) {
     else if (a == "--max-seed-copies") { max_seed_copies = std::atoll(next().c_str()); have_max_seed = true; }
     else if (a == "--near-copies") { near_m = std::atoll(next().c_str()); have_near = true; }
     else if (a == "--max-near-copies") { max_near = std::atoll(next().c_str()); have_max_near = true; }
+    else if (a == "--near-scores") near_scores = next();
     else { std::fprintf(stderr, "unknown argument %s\n", a.c_str()); usage(); return 2; }
   }
   if (pattern.empty() || ref.empty()) { usage(); return 2; }
@@ -321,6 +324,17 @@ static int find_guides_main(int argc, char** argv) {
   if (have_near && (long long)pg.proto.size() < near_m + 1) { std::fprintf(stderr, "calitas: --near-copies M: the protospacer has fewer than M + 1 bases\n"); return 2; }
   if (have_max_near && !have_near) { std::fprintf(stderr, "calitas: --max-near-copies requires --near-copies M\n"); return 2; }
   if (have_max_near && max_near < 1) { std::fprintf(stderr, "calitas: --max-near-copies N: N is at least 1 (a guide counts itself)\n"); return 2; }
+  const bool have_near_scores = !near_scores.empty();
+  if (have_near_scores && !have_near) { std::fprintf(stderr, "calitas: --near-scores requires --near-copies M\n"); return 2; }
+  ScoreModelFile near_model;
+  if (have_near_scores) {
+    std::string err;
+    if (!read_score_model(near_scores, near_model, err)) { std::fprintf(stderr, "calitas: %s\n", err.c_str()); return 2; }
+    if (near_model.L != (int)pg.proto.size()) {
+      std::fprintf(stderr, "calitas: --near-scores: the model is for protospacers of %d bases, the pattern's has %zu\n", near_model.L, pg.proto.size());
+      return 2;
+    }
+  }
   calitas_ctx* ctx = nullptr;
   if (calitas_create(device, &ctx) != CALITAS_OK) { std::fprintf(stderr, "calitas: %s\n", calitas_last_error(nullptr)); return 1; }
   auto die = [&](const char* what) { std::fprintf(stderr, "calitas: %s: %s\n", what, calitas_last_error(ctx)); calitas_destroy(ctx); std::exit(1); };
@@ -339,6 +353,7 @@ static int find_guides_main(int argc, char** argv) {
   if (!f) { std::fprintf(stderr, "cannot write %s\n", output.c_str()); calitas_free(sites); calitas_destroy(ctx); return 1; }
   std::fprintf(f, "guide_id\tchromosome\tstart\tend\tstrand\tpam_index\tguide\tpam_sequence%s%s", copies ? "\tcopies" : "", have_seed ? "\tseed_copies" : "");
   for (long long d = 0; have_near && d <= near_m; d++) std::fprintf(f, "\tcopies_mm%lld", d);
+  if (have_near_scores) std::fprintf(f, "\tnear_sum_q32\tnear_max_q32\tnear_specificity");
   std::fprintf(f, "\n");
   auto on_strand = [](std::string t, bool minus) {     // upper-case bases as fetched; '-': their reverse complement
     if (!minus) return t;
@@ -374,10 +389,26 @@ static int find_guides_main(int argc, char** argv) {
   std::vector<uint64_t> n_copies, n_seed;
   if (copies) count(L, n_copies);
   if (have_seed) count(seed_k, n_seed);
-  // the whole protospacers within near_m substitutions (tools.py guide_near): rows of near_m + 1 counts
+  // the whole protospacers within near_m substitutions (tools.py guide_near): rows of near_m + 1 counts; with --near-scores the one
+  // scored pass gives them and the sums (tools.py guide_near_scores)
   const size_t near_row = (size_t)near_m + 1;
   std::vector<uint64_t> n_near;
-  if (have_near) {
+  std::vector<calitas_near_score_t> near_sc;
+  if (have_near_scores) {
+    std::string keys;
+    for (const std::string& p : protos) keys += p;
+    n_near.assign(((size_t)n_sites + 1) * near_row, 0);
+    near_sc.assign((size_t)n_sites + 1, calitas_near_score_t{0, 0});
+    calitas_score_model_t m;
+    m.protospacer_length = near_model.L; m.gap = near_model.gap; m.pam_mismatch = near_model.pam; m.mismatch = near_model.mm.data();
+    const uint64_t most = 1ull << 24;
+    for (uint64_t at = 0; at < n_sites; at += most) {
+      const uint64_t n = std::min(most, n_sites - at);
+      const int rc2 = device < 0 ? calitas_score_near_host(ctx, &g, (int32_t)near_m, &m, -1, 0, 0, keys.data() + at * (uint64_t)L, n, n_near.data() + at * near_row, near_sc.data() + at)
+                                 : calitas_score_near(ctx, &g, (int32_t)near_m, &m, -1, 0, 0, keys.data() + at * (uint64_t)L, n, n_near.data() + at * near_row, near_sc.data() + at);
+      if (rc2 != CALITAS_OK) die("scoring near copies");
+    }
+  } else if (have_near) {
     std::string keys;
     for (const std::string& p : protos) keys += p;
     n_near.assign(((size_t)n_sites + 1) * near_row, 0);
@@ -412,6 +443,9 @@ static int find_guides_main(int argc, char** argv) {
     if (copies) std::fprintf(f, "\t%llu", (unsigned long long)n_copies[(size_t)i]);
     if (have_seed) std::fprintf(f, "\t%llu", (unsigned long long)n_seed[(size_t)i]);
     for (size_t d = 0; have_near && d < near_row; d++) std::fprintf(f, "\t%llu", (unsigned long long)n_near[(size_t)i * near_row + d]);
+    if (have_near_scores)
+      std::fprintf(f, "\t%llu\t%llu\t%.6f", (unsigned long long)near_sc[(size_t)i].sum_q32, (unsigned long long)near_sc[(size_t)i].max_q32,
+                   4294967296.0 / (4294967296.0 + (double)near_sc[(size_t)i].sum_q32));
     std::fprintf(f, "\n");
   }
   if (f != stdout) std::fclose(f);

@@ -169,6 +169,7 @@ struct SitesArgs {
   };                               // once per piece
   unsigned long long* key_counts;  // per distinct key: its sites, zero at launch; [n_keys]: the call's error flag
                                    // near kernel: n_keys rows of near_m + 1 counters, zero at launch, and no flag
+                                   // (near_m + 3 with the score: calitas_score_near, below)
   union {
     struct { uint32_t table_mask, table_shift; };   // a key's first slot is (key * COPIES_HASH) >> table_shift
     struct {                       // near kernel (calitas_count_near; it reads n_keys, key_len and key_first as well)
@@ -219,5 +220,17 @@ CAL_HD inline uint32_t near_bucket(uint32_t k_lo, uint32_t k_hi, int p, int w) {
 // one pass of the unfiltered match; every site's key held against the members of its M + 1 buckets, a query at distance d <= M adds 1
 // to its counter d
 hipError_t launch_sites_near(const SitesArgs& a, hipStream_t stream);
+
+// calitas_score_near: the near kernel with K = L and the score of every pair that counts at d >= 1.  Both letters of a scored position
+// are plain bases, so only the 4 x 4 block of the model's mismatch[i] can be read: the host packs it as [MAX_L][4][4] words
+// (near_model_index; positions beyond L hold 0) and lays it behind the offsets in the near_offsets allocation (near_model_offset),
+// which needs no field of SitesArgs.  key_counts: n_keys rows of near_m + 3 words -- near_m + 1 counts, the sum, the maximum -- zero
+// at launch.
+constexpr uint32_t NEAR_MODEL_WORDS = 32 * 16;              // 2 KB
+static_assert(MAX_L == 32, "a row of the packed model per guide position");
+CAL_HD inline uint32_t near_model_index(uint32_t position, uint32_t query_letter, uint32_t site_letter) { return position * 16u + query_letter * 4u + site_letter; }
+CAL_HD inline size_t near_model_offset(int M, int w) { return (size_t)(M + 1) * (((size_t)1 << (2 * w)) + 1); }
+hipError_t launch_sites_near_score(const SitesArgs& a, hipStream_t stream);
+static_assert(sizeof(SitesArgs) == 176, "a longer argument block costs every sites_kernel launch (DESIGN 4.15)");
 
 }  // namespace calitas

@@ -21,6 +21,8 @@
 // caller's table of query keys; a hit adds 1 to that key's counter (count_keys).
 // NEAR (calitas_count_near): the near kernel, sites_kernel<false, false, KEYS_NEAR>, is the same match with a third ending -- the key is
 // held against the query keys that share one of its M + 1 pieces, and a query at Hamming distance d <= M gets 1 in its counter d (near_keys).
+// NEAR SCORE (calitas_score_near): sites_kernel<false, false, KEYS_NEAR_SCORE>, the near kernel's ending with the pair's score besides --
+// a product of Q16 factors of a model table kept in LDS -- added into a sum and a maximum per query behind its counts.
 // FILTER (calitas_find_sites_filtered): a keep vector per strand from the same registers -- G + C count, base runs and motifs of the
 // protospacer, chain positions 32 + j .. 32 + j + L - 1 -- ANDed into the match vectors in both passes (site_keep).
 #include <hip/hip_runtime.h>
@@ -334,10 +336,15 @@ CAL_DEV void count_keys(const SitesArgs& a, const LaneSites& s, const uint32_t (
 // m = the positions at which key and member differ (either plane), d their number.  A member at d <= M counts in the FIRST piece in
 // which it equals the key -- in piece p only if every piece before p holds a difference -- so a (site, query) pair counts once however
 // many pieces agree.  M, w and the pieces' masks are wave-uniform; both loops end at offsets the host wrote, nothing can spin.
-CAL_DEV void near_keys(const SitesArgs& a, const LaneSites& s, const uint32_t (&c_lo)[4], const uint32_t (&c_hi)[4], int L) {
+// SCORE (calitas_score_near; K = L, so bit j of the key is guide position j): a member that counts at d >= 1 also gets the pair's score
+// under the model -- the set bits of m in ascending order, three at most, each one factor of `model` (near_model_index: position, the
+// query's letter, the site's letter; both letters from the four planes) multiplied into s = 2^32 with a truncation by 16 bits -- and
+// the key's row of M + 3 counters takes the count, s into the sum and s into the maximum.
+template <bool SCORE>
+CAL_DEV void near_keys(const SitesArgs& a, const LaneSites& s, const uint32_t (&c_lo)[4], const uint32_t (&c_hi)[4], int L, const uint32_t* model) {
   const int K = a.key_len, M = a.near_m, w = a.near_w;
   const bool first = a.key_first != 0;
-  const uint32_t per_table = (1u << (2 * w)) + 1u, piece = (1u << w) - 1u, row = (uint32_t)M + 1u;
+  const uint32_t per_table = (1u << (2 * w)) + 1u, piece = (1u << w) - 1u, row = (uint32_t)M + (SCORE ? 3u : 1u);
   uint32_t left_p = s.plus, left_m = s.minus;
   while (left_p | left_m) {
     const bool minus = left_p == 0u;
@@ -367,7 +374,26 @@ CAL_DEV void near_keys(const SitesArgs& a, const LaneSites& s, const uint32_t (&
 #pragma unroll
         for (int e = 0; e < NEAR_MAX_M; e++)
           if (e < p) counts = counts && (m & (piece << (e * w))) != 0u;
-        if (counts) (void)atomicAdd(&a.key_counts[q.z * row + d], 1ull);
+        if constexpr (!SCORE) {
+          if (counts) (void)atomicAdd(&a.key_counts[q.z * row + d], 1ull);
+        } else if (counts) {
+          unsigned long long* out = a.key_counts + (uint64_t)q.z * row;
+          (void)atomicAdd(&out[d], 1ull);
+          if (d != 0u) {
+            uint64_t sc = 1ull << 32;
+            uint32_t left = m;
+#pragma unroll
+            for (int e = 0; e < NEAR_MAX_M; e++) {
+              if (left == 0u) break;
+              const uint32_t j = (uint32_t)__builtin_ctz(left);
+              left &= left - 1u;
+              const uint32_t g = ((q.x >> j) & 1u) | (((q.y >> j) & 1u) << 1), t = ((k_lo >> j) & 1u) | (((k_hi >> j) & 1u) << 1);
+              sc = (sc * model[near_model_index(j, g, t)]) >> 16;           // (s <= 2^32, a factor <= 2^16: the product has 48 bits)
+            }
+            (void)atomicAdd(&out[M + 1], (unsigned long long)sc);
+            (void)atomicMax(&out[M + 2], (unsigned long long)sc);
+          }
+        }
       }
     }
   }
@@ -376,7 +402,14 @@ CAL_DEV void near_keys(const SitesArgs& a, const LaneSites& s, const uint32_t (&
 // WRITE = false: pass 1 (counts); true: pass 2 (records).  KEYS (with neither): the match of pass 1 with the sites' keys looked up, KEYS_EXACT in the copies table (count_keys), KEYS_NEAR in the near buckets (near_keys).  FILTER: a.pat heads a SiteTables whose filter applies.  A SEGMENT is SITES_BLOCK_WORDS consecutive words, all of one tile, one lane
 // per word; it is the unit of the counts and offsets.  A workgroup takes segs_per_wg consecutive segments, the next one's words on
 // their way from memory while it matches the current one's (a workgroup per segment is bound by the rate at which workgroups start).
-constexpr int KEYS_NONE = 0, KEYS_EXACT = 1, KEYS_NEAR = 2;
+// KEYS_NEAR_SCORE: near_keys with the score; the model's packed table stands behind the near kernel's offsets in device memory and is
+// copied to LDS once per workgroup, ahead of the first segment.
+constexpr int KEYS_NONE = 0, KEYS_EXACT = 1, KEYS_NEAR = 2, KEYS_NEAR_SCORE = 3;
+// (a function's own LDS: it belongs to the one instantiation that calls this)
+CAL_DEV uint32_t* near_model_lds() {
+  __shared__ uint32_t s_model[NEAR_MODEL_WORDS];
+  return s_model;
+}
 template <bool WRITE, bool FILTER, int KEYS = KEYS_NONE>
 __global__ __launch_bounds__(SITES_BLOCK_WORDS) void sites_kernel(SitesArgs a) {
   __shared__ uint32_t s_lo[SITES_BLOCK_WORDS + 3], s_hi[SITES_BLOCK_WORDS + 3], s_ex[SITES_BLOCK_WORDS + 3];
@@ -384,6 +417,15 @@ __global__ __launch_bounds__(SITES_BLOCK_WORDS) void sites_kernel(SitesArgs a) {
   const uint32_t tid = threadIdx.x, wave = tid >> 6, wl = tid & 63u;
   const uint32_t seg0 = blockIdx.x * a.segs_per_wg, seg1 = min(seg0 + a.segs_per_wg, a.n_segs);
   PatConst* pat = (PatConst*)a.pat;
+  uint32_t* s_model = nullptr;
+  if constexpr (KEYS == KEYS_NEAR_SCORE) {
+    static_assert(NEAR_MODEL_WORDS == 2 * SITES_BLOCK_WORDS, "two words per lane fill the table");
+    s_model = near_model_lds();
+    const uint32_t* g_model = a.near_offsets + near_model_offset(a.near_m, a.near_w);
+    s_model[tid] = g_model[tid];
+    s_model[tid + SITES_BLOCK_WORDS] = g_model[tid + SITES_BLOCK_WORDS];
+    __syncthreads();
+  }
 
   // dead tile, padding, another contig: nothing to do (wave-uniform)
   auto tile_of = [&](uint32_t seg) { return a.tiles[(a.w0 + (uint64_t)seg * SITES_BLOCK_WORDS) / a.tile_words]; };
@@ -434,7 +476,8 @@ __global__ __launch_bounds__(SITES_BLOCK_WORDS) void sites_kernel(SitesArgs a) {
     const int64_t base0 = (int64_t)((wb + tid) * 32u) - (int64_t)ci.gbase;
     const LaneSites s = match_word<FILTER>(pat, c_lo, c_hi, c_ex, base0, r_start, r_end);
     if constexpr (KEYS != KEYS_NONE) {
-      if constexpr (KEYS == KEYS_NEAR) near_keys(a, s, c_lo, c_hi, pat->proto_len);
+      if constexpr (KEYS == KEYS_NEAR_SCORE) near_keys<true>(a, s, c_lo, c_hi, pat->proto_len, s_model);
+      else if constexpr (KEYS == KEYS_NEAR) near_keys<false>(a, s, c_lo, c_hi, pat->proto_len, nullptr);
       else count_keys(a, s, c_lo, c_hi, pat->proto_len);
       __syncthreads();                                      // (every lane has its chain out of LDS before the next segment goes in)
       continue;
@@ -541,6 +584,13 @@ hipError_t launch_sites_near(const SitesArgs& a, hipStream_t stream) {
   if (a.n_segs == 0) return hipSuccess;
   const uint32_t n_blocks = (a.n_segs + a.segs_per_wg - 1) / a.segs_per_wg;
   hipLaunchKernelGGL((sites_kernel<false, false, KEYS_NEAR>), dim3(n_blocks), dim3(SITES_BLOCK_WORDS), 0, stream, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_sites_near_score(const SitesArgs& a, hipStream_t stream) {
+  if (a.n_segs == 0) return hipSuccess;
+  const uint32_t n_blocks = (a.n_segs + a.segs_per_wg - 1) / a.segs_per_wg;
+  hipLaunchKernelGGL((sites_kernel<false, false, KEYS_NEAR_SCORE>), dim3(n_blocks), dim3(SITES_BLOCK_WORDS), 0, stream, a);
   return hipGetLastError();
 }
 

@@ -44,3 +44,9 @@ int calitas_count_near_host_impl(const calitas_ctx* ctx, const calitas_guide_t* 
                                  uint64_t start, uint64_t end, const char* queries, uint64_t n_queries, uint64_t* near);
 int calitas_count_near_impl(calitas_ctx* ctx, const calitas_guide_t* pattern, int32_t key_length, int32_t max_mismatches, int32_t chrom_index, uint64_t start,
                             uint64_t end, const char* queries, uint64_t n_queries, uint64_t* near);
+// near: as calitas_count_near with the whole protospacer as the key; scores[i]: sum and maximum of the model's scores of query i's sites at d = 1 .. M
+int calitas_score_near_host_impl(const calitas_ctx* ctx, const calitas_guide_t* pattern, int32_t max_mismatches, const calitas_score_model_t* model,
+                                 int32_t chrom_index, uint64_t start, uint64_t end, const char* queries, uint64_t n_queries, uint64_t* near,
+                                 calitas_near_score_t* scores);
+int calitas_score_near_impl(calitas_ctx* ctx, const calitas_guide_t* pattern, int32_t max_mismatches, const calitas_score_model_t* model, int32_t chrom_index,
+                            uint64_t start, uint64_t end, const char* queries, uint64_t n_queries, uint64_t* near, calitas_near_score_t* scores);

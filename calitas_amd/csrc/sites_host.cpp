@@ -2,7 +2,9 @@
 // filter both implementations share, the host twin (a base-by-base walk over the packed reference) and the driver of sites.hip's two
 // passes.  calitas_count_copies / calitas_count_copies_host: the query keys and their table, the host twin and the driver of the copies
 // kernel.  calitas_count_near / calitas_count_near_host: the pieces' bucket tables, the host twin (plain Hamming distances, no buckets) and
-// the driver of the near kernel.  No reference counterpart.
+// the driver of the near kernel.  calitas_score_near / calitas_score_near_host: the same driver with the model's packed table behind the
+// offsets and rows of M + 3 counters, the host twin (the score letter by letter from the caller's table) and the correction of sums and
+// maxima around a U.  No reference counterpart.
 #include "sites.hpp"
 #include "tuning.hpp"
 
@@ -638,18 +640,14 @@ int calitas_count_near_host_impl(const calitas_ctx* ctx, const calitas_guide_t* 
   return CALITAS_OK;
 }
 
-int calitas_count_near_impl(calitas_ctx* ctx, const calitas_guide_t* pattern, int32_t key_length, int32_t max_mismatches, int32_t chrom_index, uint64_t start,
-                            uint64_t end, const char* queries, uint64_t n_queries, uint64_t* near) {
-  if (ctx->device < 0) return calitas_fail(ctx, CALITAS_ENODEV, "host-only context: calitas_count_near needs a GPU (there is no CPU fallback; calitas_count_near_host is the host twin)");
-  NearCall call;
-  if (int rc = plan_near(ctx, pattern, key_length, max_mismatches, chrom_index, start, end, queries, n_queries, call)) return rc;
-  const PackedRef& ref = ctx->ref;
+namespace {
+
+// The near kernel's launch for a planned call: the pieces' bucket tables, the members, the counters zeroed, one pass, one copy-back.
+// model == nullptr: calitas_count_near, counts of n_keys rows of M + 1 words.  Otherwise NEAR_MODEL_WORDS words, the packed table of
+// calitas_score_near: it rides behind the offsets, and the rows have M + 3 words (the counts, the sum, the maximum).
+int run_near(calitas_ctx* ctx, const NearCall& call, int32_t chrom_index, uint64_t start, uint64_t end, const uint32_t* model, std::vector<uint64_t>& counts) {
   const std::vector<uint64_t>& keys = call.copies.keys;
-  const size_t n_keys = keys.size(), row = (size_t)call.M + 1;
-  if (n_keys == 0 || ref.contigs.empty()) {         // nothing to look up, or nothing to scan
-    for (uint64_t i = 0; i < n_queries * row; i++) near[i] = 0;
-    return CALITAS_OK;
-  }
+  const size_t n_keys = keys.size(), row = (size_t)call.M + 1, n_counters = n_keys * (row + (model ? 2 : 0));
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   if (!ctx->sites) ctx->sites = new SitesWork();
   SitesWork* w = ctx->sites;
@@ -660,7 +658,7 @@ int calitas_count_near_impl(calitas_ctx* ctx, const calitas_guide_t* pattern, in
   // and every key as a member of its bucket: a counting sort by bucket
   const int pw = near_piece_width(call.copies.K, call.M);
   const size_t per_table = ((size_t)1 << (2 * pw)) + 1, n_offsets = row * per_table, n_members = row * n_keys;
-  std::vector<uint32_t> offsets(n_offsets, 0);
+  std::vector<uint32_t> offsets(n_offsets + (model ? NEAR_MODEL_WORDS : 0), 0);
   std::vector<uint4> members(n_members);
   for (size_t p = 0; p < row; p++) {
     uint32_t* o = offsets.data() + p * per_table;
@@ -671,33 +669,55 @@ int calitas_count_near_impl(calitas_ctx* ctx, const calitas_guide_t* pattern, in
     for (size_t k = 0; k < n_keys; k++)
       members[at[near_bucket((uint32_t)keys[k], (uint32_t)(keys[k] >> 32), (int)p, pw)]++] = make_uint4((uint32_t)keys[k], (uint32_t)(keys[k] >> 32), (uint32_t)k, 0u);
   }
-  if (w->near_offsets_cap < n_offsets) {
+  if (model) {
+    if (near_model_offset(call.M, pw) != n_offsets) return calitas_fail(ctx, CALITAS_EHIP, "the score table does not stand where the kernel reads it (internal error)");
+    std::memcpy(offsets.data() + n_offsets, model, NEAR_MODEL_WORDS * sizeof(uint32_t));
+  }
+  if (w->near_offsets_cap < offsets.size()) {
     (void)hipFree(w->d_near_offsets); w->d_near_offsets = nullptr; w->near_offsets_cap = 0;
-    HIP_TRY(ctx, hipMalloc((void**)&w->d_near_offsets, n_offsets * sizeof(uint32_t)));
-    w->near_offsets_cap = n_offsets;
+    HIP_TRY(ctx, hipMalloc((void**)&w->d_near_offsets, offsets.size() * sizeof(uint32_t)));
+    w->near_offsets_cap = offsets.size();
   }
   if (w->near_members_cap < n_members) {
     (void)hipFree(w->d_near_members); w->d_near_members = nullptr; w->near_members_cap = 0;
     if (hipMalloc((void**)&w->d_near_members, n_members * sizeof(uint4)) != hipSuccess) { (void)hipGetLastError(); return calitas_fail(ctx, CALITAS_ENOMEM, "the query keys do not fit the device: count the queries in pieces"); }
     w->near_members_cap = n_members;
   }
-  if (w->key_counts_cap < n_members) {
+  if (w->key_counts_cap < n_counters) {
     (void)hipFree(w->d_key_counts); w->d_key_counts = nullptr; w->key_counts_cap = 0;
-    HIP_TRY(ctx, hipMalloc((void**)&w->d_key_counts, n_members * sizeof(unsigned long long)));
-    w->key_counts_cap = n_members;
+    HIP_TRY(ctx, hipMalloc((void**)&w->d_key_counts, n_counters * sizeof(unsigned long long)));
+    w->key_counts_cap = n_counters;
   }
   a.near_offsets = w->d_near_offsets; a.near_members = w->d_near_members; a.key_counts = w->d_key_counts;
   a.near_m = call.M; a.near_w = pw; a.n_keys = (uint32_t)n_keys;
   a.key_len = call.copies.K; a.key_first = call.copies.site.pam5 ? 1 : 0;
 
-  std::vector<uint64_t> counts(n_members, 0);
+  counts.assign(n_counters, 0);
   HIP_TRY(ctx, hipMemcpyAsync(w->d_pat, &call.copies.site.tab, sizeof(SitePatterns), hipMemcpyHostToDevice, ctx->stream));
-  HIP_TRY(ctx, hipMemcpyAsync(w->d_near_offsets, offsets.data(), n_offsets * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+  HIP_TRY(ctx, hipMemcpyAsync(w->d_near_offsets, offsets.data(), offsets.size() * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
   HIP_TRY(ctx, hipMemcpyAsync(w->d_near_members, members.data(), n_members * sizeof(uint4), hipMemcpyHostToDevice, ctx->stream));
-  HIP_TRY(ctx, hipMemsetAsync(w->d_key_counts, 0, n_members * sizeof(unsigned long long), ctx->stream));
-  HIP_TRY(ctx, launch_sites_near(a, ctx->stream));
-  HIP_TRY(ctx, hipMemcpyAsync(counts.data(), w->d_key_counts, n_members * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipMemsetAsync(w->d_key_counts, 0, n_counters * sizeof(unsigned long long), ctx->stream));
+  HIP_TRY(ctx, model ? launch_sites_near_score(a, ctx->stream) : launch_sites_near(a, ctx->stream));
+  HIP_TRY(ctx, hipMemcpyAsync(counts.data(), w->d_key_counts, n_counters * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  return CALITAS_OK;
+}
+
+}  // namespace
+
+int calitas_count_near_impl(calitas_ctx* ctx, const calitas_guide_t* pattern, int32_t key_length, int32_t max_mismatches, int32_t chrom_index, uint64_t start,
+                            uint64_t end, const char* queries, uint64_t n_queries, uint64_t* near) {
+  if (ctx->device < 0) return calitas_fail(ctx, CALITAS_ENODEV, "host-only context: calitas_count_near needs a GPU (there is no CPU fallback; calitas_count_near_host is the host twin)");
+  NearCall call;
+  if (int rc = plan_near(ctx, pattern, key_length, max_mismatches, chrom_index, start, end, queries, n_queries, call)) return rc;
+  const PackedRef& ref = ctx->ref;
+  const size_t row = (size_t)call.M + 1;
+  if (call.copies.keys.empty() || ref.contigs.empty()) {         // nothing to look up, or nothing to scan
+    for (uint64_t i = 0; i < n_queries * row; i++) near[i] = 0;
+    return CALITAS_OK;
+  }
+  std::vector<uint64_t> counts;
+  if (int rc = run_near(ctx, call, chrom_index, start, end, nullptr, counts)) return rc;
 
   // a U is a T to a site and an exception base to the kernel: the sites it did not see in, the records it saw in their place out
   std::vector<calitas_site_t> with_u, kernel_has;
@@ -705,5 +725,128 @@ int calitas_count_near_impl(calitas_ctx* ctx, const calitas_guide_t* pattern, in
   add_near_sites(ref, call, with_u, 1, counts);
   add_near_sites(ref, call, kernel_has, ~0ull, counts);     // (- 1)
   near_rows(call, counts, n_queries, near);
+  return CALITAS_OK;
+}
+
+// ---- calitas_score_near: the near copies of the whole protospacer, and what they add up to under a score model ----
+
+namespace {
+
+struct NearScoreCall {
+  NearCall near;                                     // K = L
+  const uint32_t* mismatch = nullptr;                // the caller's [L][5][5]
+};
+
+// checked in this order: what calitas_count_near checks (the key is the whole protospacer), then the model as calitas_search_scores
+// checks it -- of which this call reads the mismatch table alone
+int plan_near_score(calitas_ctx* c, const calitas_guide_t* pattern, int32_t max_mismatches, const calitas_score_model_t* model, int32_t chrom_index,
+                    uint64_t start, uint64_t end, const char* queries, uint64_t n_queries, NearScoreCall& call) {
+  if (int rc = plan_near(c, pattern, 0, max_mismatches, chrom_index, start, end, queries, n_queries, call.near)) return rc;
+  const int L = call.near.copies.L;
+  if (!model || !model->mismatch) return calitas_fail(c, CALITAS_EINVAL, "the score model has no mismatch table");
+  if (model->protospacer_length != L)
+    return calitas_fail(c, CALITAS_EINVAL, "the score model is for protospacers of " + std::to_string(model->protospacer_length) + " bases, the guide has " + std::to_string(L));
+  for (int i = 0; i < L * 25; i++)
+    if (model->mismatch[i] > 65536u) return calitas_fail(c, CALITAS_EINVAL, "a factor of the score model is above 65536 (1.0)");
+  call.mismatch = model->mismatch;
+  return CALITAS_OK;
+}
+
+// The contract's loop on two keys of L positions, letter by letter from the planes: the factors of the differing positions in
+// ascending order, each read from the caller's table as it stands (never from the kernel's packed one).
+uint64_t near_pair_score(const uint32_t* mismatch, int L, uint64_t query, uint64_t site) {
+  uint64_t s = 1ull << 32;
+  for (int i = 0; i < L; i++) {
+    const uint32_t g = (uint32_t)((query >> i) & 1u) | ((uint32_t)((query >> (32 + i)) & 1u) << 1);
+    const uint32_t t = (uint32_t)((site >> i) & 1u) | ((uint32_t)((site >> (32 + i)) & 1u) << 1);
+    if (g != t) s = (s * mismatch[(size_t)i * 25 + g * 5 + t]) >> 16;
+  }
+  return s;
+}
+
+// rows[k]: M + 1 counts, the sum, the maximum.  Every record against every distinct query: the count by `by` (1 or - 1), and at
+// d >= 1 the pair's score into the sum by the same sign; into the maximum only when the record comes in.
+void add_near_scores(const PackedRef& ref, const NearScoreCall& call, const std::vector<calitas_site_t>& sites, bool in, std::vector<uint64_t>& rows) {
+  const NearCall& nc = call.near;
+  const size_t M = (size_t)nc.M, row = M + 3;
+  for (const calitas_site_t& s : sites) {
+    const uint64_t key = key_at(ref, ref.contigs[(size_t)s.contig_index].gbase, s.protospacer_start, nc.copies, s.strand == '-');
+    for (size_t k = 0; k < nc.copies.keys.size(); k++) {
+      const int d = key_distance(key, nc.copies.keys[k]);
+      if (d > nc.M) continue;
+      uint64_t* r = &rows[k * row];
+      r[d] += in ? 1 : ~0ull;
+      if (d == 0) continue;
+      const uint64_t sc = near_pair_score(call.mismatch, nc.copies.L, nc.copies.keys[k], key);
+      if (in) { r[M + 1] += sc; r[M + 2] = std::max(r[M + 2], sc); }
+      else r[M + 1] -= sc;
+    }
+  }
+}
+
+void near_score_rows(const NearScoreCall& call, const std::vector<uint64_t>& rows, uint64_t n_queries, uint64_t* near, calitas_near_score_t* scores) {
+  const size_t M = (size_t)call.near.M, row = M + 3;
+  for (uint64_t q = 0; q < n_queries; q++) {
+    const uint64_t* r = rows.empty() ? nullptr : &rows[(size_t)call.near.copies.of_query[(size_t)q] * row];
+    for (size_t d = 0; d <= M; d++) near[q * (M + 1) + d] = r ? r[d] : 0;
+    scores[q].sum_q32 = r ? r[M + 1] : 0;
+    scores[q].max_q32 = r ? r[M + 2] : 0;
+  }
+}
+
+}  // namespace
+
+int calitas_score_near_host_impl(const calitas_ctx* ctx, const calitas_guide_t* pattern, int32_t max_mismatches, const calitas_score_model_t* model,
+                                 int32_t chrom_index, uint64_t start, uint64_t end, const char* queries, uint64_t n_queries, uint64_t* near,
+                                 calitas_near_score_t* scores) {
+  calitas_ctx* c = const_cast<calitas_ctx*>(ctx);
+  NearScoreCall call;
+  if (int rc = plan_near_score(c, pattern, max_mismatches, model, chrom_index, start, end, queries, n_queries, call)) return rc;
+  const CopiesCall& cc = call.near.copies;
+  std::vector<uint64_t> rows(cc.keys.size() * ((size_t)call.near.M + 3), 0);
+  std::vector<calitas_site_t> found;
+  for (int i = cc.site.c_first; i <= cc.site.c_last && !cc.keys.empty(); i++) {
+    const uint64_t len = ctx->ref.contigs[(size_t)i].len;
+    found.clear();
+    host_sites(ctx->ref, cc.site.tab.pat, nullptr, i, 0, (int64_t)len, (int64_t)std::min(start, len), (int64_t)region_end(len, end), found, nullptr);
+    add_near_scores(ctx->ref, call, found, true, rows);
+  }
+  near_score_rows(call, rows, n_queries, near, scores);
+  return CALITAS_OK;
+}
+
+int calitas_score_near_impl(calitas_ctx* ctx, const calitas_guide_t* pattern, int32_t max_mismatches, const calitas_score_model_t* model, int32_t chrom_index,
+                            uint64_t start, uint64_t end, const char* queries, uint64_t n_queries, uint64_t* near, calitas_near_score_t* scores) {
+  if (ctx->device < 0) return calitas_fail(ctx, CALITAS_ENODEV, "host-only context: calitas_score_near needs a GPU (there is no CPU fallback; calitas_score_near_host is the host twin)");
+  NearScoreCall call;
+  if (int rc = plan_near_score(ctx, pattern, max_mismatches, model, chrom_index, start, end, queries, n_queries, call)) return rc;
+  const PackedRef& ref = ctx->ref;
+  std::vector<uint64_t> rows;
+  if (call.near.copies.keys.empty() || ref.contigs.empty()) {    // nothing to look up, or nothing to scan
+    near_score_rows(call, rows, n_queries, near, scores);
+    return CALITAS_OK;
+  }
+  // the 4 x 4 block of plain bases of every position, as the kernel indexes it
+  std::vector<uint32_t> packed(NEAR_MODEL_WORDS, 0u);
+  for (uint32_t i = 0; i < (uint32_t)call.near.copies.L; i++)
+    for (uint32_t g = 0; g < 4; g++)
+      for (uint32_t t = 0; t < 4; t++) packed[near_model_index(i, g, t)] = call.mismatch[(size_t)i * 25 + g * 5 + t];
+  if (int rc = run_near(ctx, call.near, chrom_index, start, end, packed.data(), rows)) return rc;
+
+  // a U is a T to a site and an exception base to the kernel: the sites it did not see in, the records it saw in their place out.
+  // Counts and sums are corrected both ways.  A maximum cannot be taken back, and need not be: host_sites pushes a kernel_has record
+  // only at the (contig, strand, protospacer start) of the with_u record it has just pushed, so the two have one key and the same
+  // scores -- what the kernel's record put into a maximum, the true site puts there as well.  That pairing is checked here.
+  std::vector<calitas_site_t> with_u, kernel_has;
+  sites_with_u(ctx, call.near.copies.site, start, end, with_u, kernel_has);
+  size_t at = 0;
+  for (const calitas_site_t& s : kernel_has) {                   // (both lists are in output order)
+    while (at < with_u.size() && site_less(with_u[at], s)) at++;
+    if (at == with_u.size() || site_less(s, with_u[at]))
+      return calitas_fail(ctx, CALITAS_EHIP, "calitas_score_near: a record the kernel has beside a U stands where no site with a U does (internal error)");
+  }
+  add_near_scores(ref, call, with_u, true, rows);
+  add_near_scores(ref, call, kernel_has, false, rows);
+  near_score_rows(call, rows, n_queries, near, scores);
   return CALITAS_OK;
 }

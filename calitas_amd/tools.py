@@ -440,12 +440,33 @@ def guide_near(ctx, pattern, rows, max_mismatches, key_length=None, host=False):
     return out
 
 
-def guides_tsv(rows, tables=None, scores=None, copies=None, seed_copies=None, near=None):
+def guide_near_scores(ctx, pattern, rows, max_mismatches, model, host=False):
+    """Context.score_near for the GuideSites of find_guides: per row the near copies of its protospacer in the WHOLE resident
+    reference -- guide_near's table -- and the sum and maximum of their scores under `model`, from one pass.  A NearScores aligned
+    with rows."""
+    import numpy as np
+    from .aligner import NearScores
+    if not isinstance(pattern, Guide):
+        pattern = Guide(pattern)
+    L = pattern.protospacer_length
+    five = pattern.pam_is_five_prime and bool(pattern.pams)
+    keys = [r.guide[len(r.guide) - L:] if five else r.guide[:L] for r in rows]
+    M = int(max_mismatches)
+    parts = [ctx.score_near(pattern, keys[at:at + COPIES_MAX_QUERIES], M, model, host=host)
+             for at in range(0, len(keys), COPIES_MAX_QUERIES)]  # the queries are independent: a call's worth at a time
+    if not parts:
+        return ctx.score_near(pattern, [], M, model, host=host)
+    return NearScores(np.concatenate([p.near for p in parts]), np.concatenate([p.sum_q32 for p in parts]), np.concatenate([p.max_q32 for p in parts]))
+
+
+def guides_tsv(rows, tables=None, scores=None, copies=None, seed_copies=None, near=None, near_scores=None):
     """The FindGuides table: GUIDE_COLUMNS, one row per GuideSite; with tables (guide_counts) also hits -- the table's sum -- and
     hits_mm0 .. hits_mmE, the hits per number of protospacer mismatches, summed over strands, gaps and PAM mismatches; with scores
     (guide_scores) those columns come from the same pass's tables and perfect and specificity (%.6f) follow them.  copies,
     seed_copies: lists aligned with rows (guide_copies) -- the columns of those names, directly behind pam_sequence.  near: a list of
-    rows of M + 1 counts aligned with rows (guide_near), or an array of that shape -- the columns copies_mm0 .. copies_mmM behind those."""
+    rows of M + 1 counts aligned with rows (guide_near), or an array of that shape -- the columns copies_mm0 .. copies_mmM behind those.
+    near_scores: a NearScores aligned with rows (guide_near_scores) -- near_sum_q32, near_max_q32 and near_specificity (%.6f) directly
+    behind copies_mmM."""
     header = list(GUIDE_COLUMNS)
     if copies is not None:
         header.append("copies")
@@ -454,6 +475,9 @@ def guides_tsv(rows, tables=None, scores=None, copies=None, seed_copies=None, ne
     if near is not None:
         # (an array of shape (n, M + 1) names its columns without a row; a list of rows needs one)
         header += ["copies_mm%d" % d for d in range(near.shape[1] if hasattr(near, "shape") else len(near[0]) if len(near) else 0)]
+    if near_scores is not None:
+        header += ["near_sum_q32", "near_max_q32", "near_specificity"]
+        near_spec = near_scores.specificity
     n_mm = 0
     if scores is not None:
         tables = {g: s.table for g, s in scores.items()}
@@ -471,6 +495,8 @@ def guides_tsv(rows, tables=None, scores=None, copies=None, seed_copies=None, ne
             f.append(str(int(seed_copies[i])))
         if near is not None:
             f += [str(int(x)) for x in near[i]]
+        if near_scores is not None:
+            f += [str(int(near_scores.sum_q32[i])), str(int(near_scores.max_q32[i])), "%.6f" % near_spec[i]]
         if tables is not None:
             t = tables[r.guide]
             f += [str(int(t.sum()))] + [str(int(t[:, m].sum())) if m < t.shape[1] else "0" for m in range(n_mm)]
@@ -512,7 +538,7 @@ def site_filter_of_flags(L, gc_min=None, gc_max=None, max_run=None, avoid=()):
 
 def find_guides_tool(ref, pattern, auxiliary_pams=(), chrom=None, start=0, end=None, output=None, counts=False, device=0, scores=None,
                      gc_min=None, gc_max=None, max_run=None, avoid=(), copies=False, seed_copies=None, max_copies=None, max_seed_copies=None,
-                     near_copies=None, max_near_copies=None, **search):
+                     near_copies=None, max_near_copies=None, near_scores=None, **search):
     """`python -m calitas_amd FindGuides`: the guides of a region as a TSV (guides_tsv); counts=True: every distinct guide also goes
     through the off-target search with the SearchReference flags in `search` (make_params names); scores=ScoreModel (or its file):
     through search_scores_batch instead, which adds perfect and specificity.  gc_min, gc_max, max_run, avoid: the site filter's flags
@@ -522,7 +548,9 @@ def find_guides_tool(ref, pattern, auxiliary_pams=(), chrom=None, start=0, end=N
     max_seed_copies=N (needs seed_copies) drop the rows with more than N before anything is searched, the kept rows keep their
     guide_ids.  near_copies=M (0 .. 3): the columns copies_mm0 .. copies_mmM (guide_near over the whole reference, the whole
     protospacer); max_near_copies=N (N >= 1, needs near_copies) drops the rows whose columns sum to more than N, likewise before
-    anything is searched.  These six work with device -1 through the host twin.  Returns the text."""
+    anything is searched.  near_scores=ScoreModel (or its file; needs near_copies, the model's length is the protospacer's): the
+    columns near_sum_q32, near_max_q32 and near_specificity, from the one guide_near_scores pass that then gives the copies_mm columns
+    as well.  These seven work with device -1 through the host twin.  Returns the text."""
     if (counts or scores is not None) and device < 0:
         raise ValueError("--counts and --scores search on the GPU: they cannot run with --device -1")
     if isinstance(scores, str):
@@ -546,13 +574,24 @@ def find_guides_tool(ref, pattern, auxiliary_pams=(), chrom=None, start=0, end=N
         raise ValueError("--max-near-copies requires --near-copies M")
     if max_near_copies is not None and int(max_near_copies) < 1:
         raise ValueError("--max-near-copies N: N is at least 1 (a guide counts itself)")
+    if near_scores is not None and near_copies is None:
+        raise ValueError("--near-scores requires --near-copies M")
+    if isinstance(near_scores, str):
+        from .aligner import ScoreModel
+        near_scores = ScoreModel.read(near_scores)
+    if near_scores is not None and near_scores.L != pat.protospacer_length:
+        raise ValueError("--near-scores: the model is for protospacers of %d bases, the pattern's has %d" % (near_scores.L, pat.protospacer_length))
     ctx = Context(device)
     try:
         ctx.set_reference_fasta(ref)
         rows = find_guides(ctx, pat, chrom, start, end, host=device < 0, filter=keep)
         n_copies = guide_copies(ctx, pat, rows, host=device < 0) if copies or max_copies is not None else None
         n_seed = guide_copies(ctx, pat, rows, key_length=int(seed_copies), host=device < 0) if seed_copies is not None else None
-        n_near = guide_near(ctx, pat, rows, int(near_copies), host=device < 0) if near_copies is not None else None
+        scored_near = guide_near_scores(ctx, pat, rows, int(near_copies), near_scores, host=device < 0) if near_scores is not None else None
+        if scored_near is not None:
+            n_near = [[int(x) for x in row] for row in scored_near.near]
+        else:
+            n_near = guide_near(ctx, pat, rows, int(near_copies), host=device < 0) if near_copies is not None else None
         kept = [i for i in range(len(rows)) if (max_copies is None or n_copies[i] <= int(max_copies)) and
                 (max_seed_copies is None or n_seed[i] <= int(max_seed_copies)) and
                 (max_near_copies is None or sum(n_near[i]) <= int(max_near_copies))]
@@ -562,9 +601,12 @@ def find_guides_tool(ref, pattern, auxiliary_pams=(), chrom=None, start=0, end=N
         if n_near is not None:
             import numpy as np
             n_near = np.array([n_near[i] for i in kept], dtype=np.uint64).reshape(len(kept), int(near_copies) + 1)
+        if scored_near is not None:
+            from .aligner import NearScores
+            scored_near = NearScores(n_near, scored_near.sum_q32[kept], scored_near.max_q32[kept])
         tables = guide_counts(ctx, [r.guide for r in rows], make_params(**search)) if counts and scores is None else None
         scored = guide_scores(ctx, [r.guide for r in rows], make_params(**search), scores) if scores is not None else None
-        text = guides_tsv(rows, tables, scored, copies=n_copies, seed_copies=n_seed, near=n_near)
+        text = guides_tsv(rows, tables, scored, copies=n_copies, seed_copies=n_seed, near=n_near, near_scores=scored_near)
         if output is not None:
             with open(output, "w") as f:
                 f.write(text)

@@ -429,6 +429,41 @@ int calitas_search_scores(calitas_ctx* ctx, const calitas_guide_t* guide, const 
 int calitas_search_scores_batch(calitas_ctx* ctx, int32_t n_guides, const calitas_guide_t* guides, const calitas_params_t* params,
                                 const calitas_score_model_t* model, calitas_scores_t** out);
 
+/* Near copies with the score: calitas_count_near over the whole protospacer, and per query what its near copies add up to under a
+ * model -- for all guides of a table in the one genome pass.  No reference counterpart.
+ * Sites, region rules, absent contigs, one site per (contig, strand, protospacer start), a U in the footprint, the queries' letters and
+ * the limit of 2^24 queries are those of calitas_count_near.  The key is always the whole protospacer (K = L; there is no key_length:
+ * a score over a seed has no meaning in the model), so queries holds n_queries * L letters.  near receives exactly what
+ * calitas_count_near(pattern, 0, M, ...) returns, n_queries * (M + 1) counts from the same pass.
+ * The score of one (site, query) pair at d >= 1:
+ *     s = 1 << 32
+ *     for each position i at which the two differ, in ascending guide position:
+ *         s = (s * mismatch[i][idx(query letter)][idx(site letter)]) >> 16
+ * in 64-bit unsigned arithmetic, truncating at every step; i is 0-based in the guide as written on the command line.  That is the
+ * contract of calitas_score_model_t on a substitution-only row without a PAM mismatch: model->gap and model->pam_mismatch are not used.
+ * Both letters are plain bases, indices 0 .. 3, and a U in a query is a T (index 3) as in every copies call -- the ONE difference from
+ * the search's contract, which reads a U guide letter as index 4.
+ * scores[i].sum_q32 is the sum of s over query i's sites at d = 1 .. M, scores[i].max_q32 the largest such s, 0 when there is none.
+ * Sites at d = 0 are counted in near[i * (M + 1)] and not scored (the perfect hits of calitas_scores_t).  A factor of 0 gives s = 0:
+ * the pair is counted, adds nothing to the sum and leaves the maximum as it is.  Duplicated queries each get the full result; over
+ * disjoint contig sets counts and sums add and the maxima take the maximum; every path returns the same integers.  A sum wraps only
+ * past 2^32 scored sites of one query (each s is at most 2^32).
+ * CALITAS_EINVAL, with a message that names the field: what calitas_count_near refuses, in its order (the protospacer has at least
+ * M + 1 bases); then a NULL model or table, model->protospacer_length != L and a mismatch factor above 65536, with the messages of
+ * calitas_search_scores.  n_queries == 0 is legal.
+ * Runs on the device: the near kernel's pass; a member that counts at d >= 1 walks its at most three differing positions, looks each
+ * factor up in the model's 4 x 4 plain-base blocks (2 KB, in LDS) and adds s into the query's sum and maximum beside its count.
+ * CALITAS_ENOMEM when the tables do not fit the device, CALITAS_ENODEV on a host-only context. */
+typedef struct { uint64_t sum_q32, max_q32; } calitas_near_score_t;
+int calitas_score_near(calitas_ctx* ctx, const calitas_guide_t* pattern, int32_t max_mismatches, const calitas_score_model_t* model,
+                       int32_t chrom_index, uint64_t start, uint64_t end, const char* queries, uint64_t n_queries, uint64_t* near,
+                       calitas_near_score_t* scores);
+/* The host twin of calitas_score_near: a base-by-base walk over the packed reference of the context, which may be host-only; plain
+ * Hamming distances against every distinct query, the score letter by letter from the caller's table.  No reference counterpart. */
+int calitas_score_near_host(const calitas_ctx* ctx, const calitas_guide_t* pattern, int32_t max_mismatches, const calitas_score_model_t* model,
+                            int32_t chrom_index, uint64_t start, uint64_t end, const char* queries, uint64_t n_queries, uint64_t* near,
+                            calitas_near_score_t* scores);
+
 /* The K highest-scoring imperfect hits of a guide, from the pass that scores them.  No reference counterpart.
  * The candidates are the kept hits that are not perfect (total_mm_plus_gaps != 0); they are ordered by score_q32 descending, and among
  * equal scores the hit whose row comes earlier in the hits.txt of the same call comes first.  That is a total order: the n records are

@@ -4,6 +4,7 @@ round in ONE process: python tools/near_speed.py [scale] [rounds] [--existing] [
   count plain       : calitas_count_sites of NNNNNNNNNNNNNNNNNNNNnrg over the whole genome, no filter -- the same match work
   copies 10 kb      : calitas_count_copies over the whole genome, the queries the protospacers of every site of a 10-kb region (K = 20)
   near 10 kb M=1..3 : calitas_count_near of the same queries at max_mismatches 1, 2, 3
+  scored 10 kb M=.. : calitas_score_near of the same queries and M under a model (every factor 0.6), beside each K = 20 near row
   ... K=12 M=2      : the PAM-proximal 12 bases as the key, copies and near at M = 2
   ... 1 Mb          : the same rows for the guides of a 1-Mb region
 
@@ -18,8 +19,8 @@ sets counted over their own region against the host twin.
 The bench genome is independent random bases with short tandem repeats planted (bench.gen_contig): it has almost no near-duplicate
 20-mers, so what a real genome's repeat families cost -- long buckets and hot counters -- is NOT measured here.
 
---existing: the two calls that existed before calitas_count_near alone, `count plain` and `copies 10 kb`, which the parent commit's
-checkout has too; --tree DIR takes package and library from another checkout (built).  With both, two builds are compared, whole
+--existing: the calls that existed before calitas_score_near alone -- `count plain`, `copies 10 kb` and `near 10 kb M=2` -- which the
+parent commit's checkout has too; --tree DIR takes package and library from another checkout (built).  With both, two builds are compared, whole
 processes alternated:  python tools/near_speed.py 1.0 20 --existing --tree PARENT  against  ... --existing."""
 import ctypes
 import os
@@ -98,6 +99,16 @@ def main():
                                 out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64))))
         return out[:len(keys)]
 
+    model = None if existing else C.ScoreModel.uniform(L, mismatch=39322).to_c()
+
+    def scored(keys, M, chrom=-1, start=0, end=0, host=False):
+        out = np.zeros((max(1, len(keys)), M + 1), dtype=np.uint64)
+        words = np.zeros((max(1, len(keys)), 2), dtype=np.uint64)
+        fn = lib.calitas_score_near_host if host else lib.calitas_score_near
+        C._lib.check(ctx._h, fn(ctx._h, ctypes.byref(g), M, ctypes.byref(model), chrom, start, end, keys.ctypes.data_as(ctypes.c_char_p), len(keys),
+                                out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), words.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64))))
+        return out[:len(keys)], words[:len(keys)]
+
     calls = {"count plain": lambda: ctx.count_sites(n20)}
     info = {"count plain": "%d sites" % total}
     first = {}
@@ -118,14 +129,14 @@ def main():
             assert int(exact.min()) >= 1, "a guide cut from the reference does not count itself"
             calls["copies " + tag] = lambda keys=keys, K=K: copies(keys, K)
             info["copies " + tag] = "%d queries, %d with more than one copy | the search: %.1f s" % (len(keys), int((exact > 1).sum()), len(keys) * search_ms / 1e3)
-            for M in () if existing else Ms:
+            for M in (2,) if existing else Ms:
                 name = "near %s M=%d" % (tag, M)
                 t0 = time.perf_counter()
                 got = near(keys, K, M)
                 first[name] = time.perf_counter() - t0
                 print("%-22s first call %.3f s" % (name, first[name]), flush=True)
                 assert got[:, 0].tobytes() == exact.tobytes(), "column 0 is not the copies count"
-                if size == 10_000:
+                if size == 10_000 and not existing:
                     assert near(keys, K, M, big, r0, r1).tobytes() == near(keys, K, M, big, r0, r1, host=True).tobytes(), "the kernel and the host twin differ"
                 others = got.sum(axis=1) - 1
                 info[name] = "%d queries, %d with another copy within %d, most %d | the search: %.1f s" % (
@@ -134,8 +145,24 @@ def main():
                     calls[name] = lambda keys=keys, K=K, M=M: near(keys, K, M)
                 else:
                     print("%-22s scale %g: one call %.1f ms | %s" % (name, scale, first[name] * 1e3, info[name]), flush=True)
+                if existing or K != L:
+                    continue
+                sname = "scored %s M=%d" % (tag, M)
+                t0 = time.perf_counter()
+                rows, words = scored(keys, M)
+                first[sname] = time.perf_counter() - t0
+                print("%-22s first call %.3f s" % (sname, first[sname]), flush=True)
+                assert rows.tobytes() == got.tobytes(), "the scored call's counts are not count_near's"
+                if size == 10_000:
+                    a, b = scored(keys, M, big, r0, r1), scored(keys, M, big, r0, r1, host=True)
+                    assert a[0].tobytes() == b[0].tobytes() and a[1].tobytes() == b[1].tobytes(), "the scored kernel and the host twin differ"
+                info[sname] = "%d queries, %d with a scored copy, largest sum %.3f" % (len(keys), int((words[:, 0] > 0).sum()), int(words[:, 0].max()) / 2.0 ** 32)
+                if first[sname] <= ONCE_OVER_S:
+                    calls[sname] = lambda keys=keys, M=M: scored(keys, M)
+                else:
+                    print("%-22s scale %g: one call %.1f ms | %s" % (sname, scale, first[sname] * 1e3, info[sname]), flush=True)
     if not existing:
-        print("checked: column 0 against the copies count; the 10-kb sets over their own region against the host twin", flush=True)
+        print("checked: column 0 against the copies count; the scored calls' counts against count_near; the 10-kb sets over their own region against the host twin", flush=True)
 
     res = {k: [] for k in calls}
     for r in range(rounds + 2):                                 # (two rounds of warm-up: buffers sized, clocks up)
