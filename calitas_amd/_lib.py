@@ -100,7 +100,15 @@ class RegionsT(ctypes.Structure):
                 ("by_class", ctypes.POINTER(ScoresT))]
 
 
+class NearHitT(ctypes.Structure):
+    _fields_ = [("score_q32", ctypes.c_uint64), ("contig_index", ctypes.c_int32), ("protospacer_start", ctypes.c_int32), ("target_lo", ctypes.c_uint32),
+                ("target_hi", ctypes.c_uint32), ("diff_mask", ctypes.c_uint32), ("strand", ctypes.c_int8), ("pam_index", ctypes.c_int8),
+                ("mismatches", ctypes.c_uint8), ("reserved", ctypes.c_uint8)]
+
+
 TOP_MAX = 256
+NEAR_LIST_MAX = 4096
+assert ctypes.sizeof(NearHitT) == 32
 REGION_CLASSES_MAX = 8
 assert ctypes.sizeof(TopHitT) == 24
 
@@ -116,7 +124,7 @@ SYMBOLS = ["calitas_create", "calitas_destroy", "calitas_last_error", "calitas_f
            "calitas_find_sites", "calitas_count_sites", "calitas_find_sites_host",
            "calitas_find_sites_filtered", "calitas_count_sites_filtered", "calitas_find_sites_filtered_host",
            "calitas_count_copies", "calitas_count_copies_host", "calitas_count_near", "calitas_count_near_host",
-           "calitas_score_near", "calitas_score_near_host"]
+           "calitas_score_near", "calitas_score_near_host", "calitas_list_near", "calitas_list_near_host"]
 
 if not os.path.exists(LIB_PATH):
     raise ImportError("%s is missing: build it with `make -C calitas_amd/csrc` (hipcc, gfx950). "
@@ -195,6 +203,11 @@ lib.calitas_count_near_host.argtypes = lib.calitas_count_near.argtypes
 lib.calitas_score_near.argtypes = [ctypes.c_void_p, ctypes.POINTER(GuideT), ctypes.c_int32, ctypes.POINTER(ScoreModelT), ctypes.c_int32, ctypes.c_uint64,
                                    ctypes.c_uint64, ctypes.c_char_p, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]
 lib.calitas_score_near_host.argtypes = lib.calitas_score_near.argtypes
+if hasattr(lib, "calitas_list_near"):      # (an older build behind CALITAS_LIB_PATH, for A/B runs, does not have it)
+    lib.calitas_list_near.argtypes = [ctypes.c_void_p, ctypes.POINTER(GuideT), ctypes.c_int32, ctypes.POINTER(ScoreModelT), ctypes.c_int32, ctypes.c_uint64,
+                                      ctypes.c_uint64, ctypes.c_char_p, ctypes.c_uint64, ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint64),
+                                      ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.POINTER(NearHitT)), ctypes.POINTER(ctypes.c_uint64)]
+    lib.calitas_list_near_host.argtypes = lib.calitas_list_near.argtypes
 lib.calitas_search_scores.argtypes = [ctypes.c_void_p, ctypes.POINTER(GuideT), ctypes.POINTER(ParamsT), ctypes.POINTER(ScoreModelT),
                                       ctypes.POINTER(ctypes.POINTER(ScoresT))]
 lib.calitas_search_scores_batch.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.POINTER(GuideT), ctypes.POINTER(ParamsT),

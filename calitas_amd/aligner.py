@@ -622,6 +622,46 @@ class Context:
         n = len(queries)
         return NearScores(near[:n], words[:n, 0].copy(), words[:n, 1].copy())
 
+    def list_near(self, pattern, queries, max_mismatches, model=None, limit=1000, chrom=None, start=0, end=None, host=False):
+        """calitas_list_near: count_near over the whole protospacer, and per query the records of its sites at d = 0 .. M -- where they
+        stand, what differs and the pair's score under `model` (a ScoreModel; None: no weights, every score 2^32) -- a NearList.  A
+        query whose counts sum to more than `limit` (1 .. 4096) lists nothing.  near_hits_of is the contract on one query.  host=True:
+        the host twin (calitas_list_near_host), also on a host-only context."""
+        import numpy as np
+        pattern, index, start, end = self._site_region(pattern, chrom, start, end)
+        queries = [q.decode() if isinstance(q, bytes) else str(q) for q in queries]
+        L = pattern.protospacer_length
+        M = int(max_mismatches)
+        for i, q in enumerate(queries):
+            if len(q) != L:
+                raise ValueError("queries[%d] has %d letters, the key has %d" % (i, len(q), L))
+        limit = int(limit)
+        if not 0 <= limit < 1 << 32:
+            raise ValueError("limit is 1 .. %d, not %d" % (_lib.NEAR_LIST_MAX, limit))
+        g = pattern.to_c()
+        m = model.to_c() if model is not None else None
+        row = min(max(M, 0), 3) + 1                   # (an M outside 0 .. 3 is the library's to refuse)
+        n = len(queries)
+        near = np.zeros((max(1, n), row), dtype=np.uint64)
+        offsets = np.zeros(n + 1, dtype=np.uint64)
+        text = "".join(queries).encode("latin-1", "replace")
+        out = ctypes.POINTER(_lib.NearHitT)()
+        n_hits = ctypes.c_uint64()
+        fn = lib.calitas_list_near_host if host else lib.calitas_list_near
+        rc = fn(self._h, ctypes.byref(g), M, ctypes.byref(m) if m is not None else None, index, start, end, text, n, limit,
+                near.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), offsets.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), ctypes.byref(out),
+                ctypes.byref(n_hits))
+        _lib.check(self._h, rc)
+        try:
+            if n_hits.value == 0:
+                hits = np.zeros(0, dtype=NEAR_HIT_DTYPE)
+            else:
+                block = (ctypes.c_char * (n_hits.value * ctypes.sizeof(_lib.NearHitT))).from_address(ctypes.addressof(out.contents))
+                hits = np.frombuffer(block, dtype=NEAR_HIT_DTYPE).copy()
+        finally:
+            lib.calitas_free(out)
+        return NearList(near[:n], offsets, hits, limit, L)
+
     @staticmethod
     def _scores_of(c):
         """A calitas_scores_t as a Scores object (the table is copied)."""
@@ -999,6 +1039,10 @@ class SearchReference:
 SITE_DTYPE = [("contig_index", "<i4"), ("protospacer_start", "<i4"), ("pam_start", "<i4"), ("strand", "S1"), ("pam_index", "i1"),
               ("pam_length", "u1"), ("protospacer_length", "u1")]
 
+# calitas_near_hit_t
+NEAR_HIT_DTYPE = [("score_q32", "<u8"), ("contig_index", "<i4"), ("protospacer_start", "<i4"), ("target_lo", "<u4"), ("target_hi", "<u4"),
+                  ("diff_mask", "<u4"), ("strand", "S1"), ("pam_index", "i1"), ("mismatches", "u1"), ("reserved", "u1")]
+
 _IUPAC_COMPLEMENT = str.maketrans("ACGTUMRWSYKVHDBN", "TGCAAKYWSRMBDHVN")
 
 
@@ -1317,6 +1361,88 @@ class NearScores:
 
     def __repr__(self):
         return "NearScores(n=%d, M=%d)" % (self.near.shape[0], self.near.shape[1] - 1)
+
+
+def near_hits_of(query, sites, max_mismatches, model=None):
+    """The contract of calitas_list_near on one query, in plain Python: `sites` is an iterable of (contig_index, protospacer_start,
+    strand '+' / '-', pam_index, protospacer as the guide reads it -- letters A C G T in either case, U as T).  Returns the query's
+    stretch, whatever its length: a list of dicts with the fields of calitas_near_hit_t (strand as a str, and `target`, the site's
+    letters) for the sites within max_mismatches substitutions of the query, ordered by contig_index, protospacer_start, '+' before
+    '-'.  score_q32 is near_score's integer, 2^32 at distance 0 and wherever model is None."""
+    q = query.upper().replace("U", "T")
+    out = []
+    for contig, start, strand, pam_index, target in sites:
+        t = target.upper().replace("U", "T")
+        if len(t) != len(q):
+            raise ValueError("a site of %d letters cannot be held against a query of %d" % (len(t), len(q)))
+        at = [i for i in range(len(q)) if q[i] != t[i]]
+        if len(at) > max_mismatches:
+            continue
+        score = near_score(q, t, model) if model is not None and at else 1 << 32
+        out.append({"score_q32": score, "contig_index": int(contig), "protospacer_start": int(start),
+                    "target_lo": sum((_LETTER[c] & 1) << i for i, c in enumerate(t)), "target_hi": sum((_LETTER[c] >> 1) << i for i, c in enumerate(t)),
+                    "diff_mask": sum(1 << i for i in at), "strand": strand, "pam_index": int(pam_index), "mismatches": len(at), "reserved": 0,
+                    "target": t})
+    out.sort(key=lambda h: (h["contig_index"], h["protospacer_start"], h["strand"] != "+"))
+    return out
+
+
+class NearList:
+    """What Context.list_near returns for n queries: near (uint64, shape (n, M + 1): count_near's table over the whole protospacer),
+    offsets (uint64, n + 1), hits (a numpy array of NEAR_HIT_DTYPE: query i's records are hits[offsets[i]:offsets[i + 1]], ordered by
+    contig_index, protospacer_start, '+' before '-'), limit and L, the protospacer's length.  A query whose row of near sums to more
+    than limit lists nothing."""
+    __slots__ = ("near", "offsets", "hits", "limit", "L")
+
+    def __init__(self, near, offsets, hits, limit, L):
+        self.near, self.offsets, self.hits, self.limit, self.L = near, offsets, hits, int(limit), int(L)
+
+    def of(self, i):
+        """Query i's records."""
+        return self.hits[int(self.offsets[i]):int(self.offsets[i + 1])]
+
+    def listed(self, i):
+        """Whether query i's copies are listed: its row of near sums to limit at most."""
+        return int(self.near[i].sum()) <= self.limit
+
+    def target(self, hit):
+        """The protospacer of a record's site as the guide reads it, lower case where it differs from the query."""
+        lo, hi, diff = int(hit["target_lo"]), int(hit["target_hi"]), int(hit["diff_mask"])
+        letters = ["ACGT"[((lo >> i) & 1) | (((hi >> i) & 1) << 1)] for i in range(self.L)]
+        return "".join(c.lower() if (diff >> i) & 1 else c for i, c in enumerate(letters))
+
+    def merge(self, *others):
+        """The same queries and limit over disjoint contig sets: the counts add, a query's stretches concatenate in contig order, and a
+        query whose summed counts exceed the limit lists nothing."""
+        import numpy as np
+        parts = (self,) + others
+        near = self.near.copy()
+        for o in others:
+            if o.near.shape != near.shape or o.limit != self.limit or o.L != self.L:
+                raise ValueError("near lists of different queries, max_mismatches or limits do not merge")
+            near = near + o.near
+        n = near.shape[0]
+        offsets = np.zeros(n + 1, dtype=np.uint64)
+        stretches = []
+        for i in range(n):
+            length = 0
+            if int(near[i].sum()) <= self.limit:
+                both = np.concatenate([p.of(i) for p in parts])
+                stretches.append(both[np.argsort(both["contig_index"], kind="stable")])
+                length = len(both)
+            offsets[i + 1] = offsets[i] + np.uint64(length)
+        hits = np.concatenate(stretches) if stretches else np.zeros(0, dtype=NEAR_HIT_DTYPE)
+        return NearList(near, offsets, hits, self.limit, self.L)
+
+    def __eq__(self, o):
+        import numpy as np
+        return (isinstance(o, NearList) and self.limit == o.limit and self.L == o.L and self.near.shape == o.near.shape and bool(np.array_equal(self.near, o.near)) and
+                bool(np.array_equal(self.offsets, o.offsets)) and self.hits.tobytes() == o.hits.tobytes())
+
+    __hash__ = None
+
+    def __repr__(self):
+        return "NearList(n=%d, M=%d, hits=%d, limit=%d)" % (self.near.shape[0], self.near.shape[1] - 1, len(self.hits), self.limit)
 
 
 def scores_of_rows(rows, model, shape=None):

@@ -865,6 +865,24 @@ int calitas_score_near_host(const calitas_ctx* ctx, const calitas_guide_t* patte
   return calitas_score_near_host_impl(ctx, pattern, max_mismatches, model, chrom_index, start, end, queries, n_queries, near, scores);
 }
 
+int calitas_list_near(calitas_ctx* ctx, const calitas_guide_t* pattern, int32_t max_mismatches, const calitas_score_model_t* model, int32_t chrom_index,
+                      uint64_t start, uint64_t end, const char* queries, uint64_t n_queries, uint32_t limit, uint64_t* near, uint64_t* offsets,
+                      calitas_near_hit_t** hits, uint64_t* n_hits) {
+  if (!ctx) return CALITAS_EINVAL;
+  if (!pattern || !offsets || !hits || !n_hits || (n_queries && (!queries || !near))) return fail(ctx, CALITAS_EINVAL, "NULL argument");
+  *hits = nullptr; *n_hits = 0;
+  return calitas_list_near_impl(ctx, pattern, max_mismatches, model, chrom_index, start, end, queries, n_queries, limit, near, offsets, hits, n_hits);
+}
+
+int calitas_list_near_host(const calitas_ctx* ctx, const calitas_guide_t* pattern, int32_t max_mismatches, const calitas_score_model_t* model,
+                           int32_t chrom_index, uint64_t start, uint64_t end, const char* queries, uint64_t n_queries, uint32_t limit, uint64_t* near,
+                           uint64_t* offsets, calitas_near_hit_t** hits, uint64_t* n_hits) {
+  if (!ctx) return CALITAS_EINVAL;
+  if (!pattern || !offsets || !hits || !n_hits || (n_queries && (!queries || !near))) return fail(const_cast<calitas_ctx*>(ctx), CALITAS_EINVAL, "NULL argument");
+  *hits = nullptr; *n_hits = 0;
+  return calitas_list_near_host_impl(ctx, pattern, max_mismatches, model, chrom_index, start, end, queries, n_queries, limit, near, offsets, hits, n_hits);
+}
+
 // A guide's scores as the ABI hands them over: struct, table and cells in one block of the library's.
 static calitas_scores_t* scores_block(const CountsShape& shape, const uint64_t* table, uint64_t rows, const ScoreWords& w) {
   const size_t cells = shape.cells();

@@ -35,6 +35,7 @@ static void usage() {
     "         [--near-copies M (0 .. 3: the columns copies_mm0 .. copies_mmM, the sites whose protospacer differs at exactly that many positions)]\n"
     "         [--max-near-copies N (drop rows whose copies_mm columns sum to more; needs --near-copies)]\n"
     "         [--near-scores model.tsv (with --near-copies: near_sum_q32 near_max_q32 near_specificity, the near copies' scores from the same pass)]\n"
+    "         [--near-list out.tsv (with --near-copies: every kept guide's copies within M substitutions, one per line)] [--near-list-limit N (1 .. 4096, default 1000)]\n"
     "         [--device N (-1: the host twin, no GPU)]\n");
 }
 
@@ -274,6 +275,9 @@ static int find_guides_main(int argc, char** argv) {
   long long near_m = 0, max_near = 0;
   bool have_near = false, have_max_near = false;
   std::string near_scores;     // --near-scores MODEL.tsv
+  std::string near_list;       // --near-list FILE
+  long long near_list_limit = 1000;
+  bool have_list_limit = false;
   for (int i = 2; i < argc; i++) {
     std::string a = argv[i], val;
     size_t eq = a.find('=');
@@ -303,6 +307,8 @@ static int find_guides_main(int argc, char** argv) {
     else if (a == "--near-copies") { near_m = std::atoll(next().c_str()); have_near = true; }
     else if (a == "--max-near-copies") { max_near = std::atoll(next().c_str()); have_max_near = true; }
     else if (a == "--near-scores") near_scores = next();
+    else if (a == "--near-list") near_list = next();
+    else if (a == "--near-list-limit") { near_list_limit = std::atoll(next().c_str()); have_list_limit = true; }
     else { std::fprintf(stderr, "unknown argument %s\n", a.c_str()); usage(); return 2; }
   }
   if (pattern.empty() || ref.empty()) { usage(); return 2; }
@@ -326,6 +332,10 @@ static int find_guides_main(int argc, char** argv) {
   if (have_max_near && max_near < 1) { std::fprintf(stderr, "calitas: --max-near-copies N: N is at least 1 (a guide counts itself)\n"); return 2; }
   const bool have_near_scores = !near_scores.empty();
   if (have_near_scores && !have_near) { std::fprintf(stderr, "calitas: --near-scores requires --near-copies M\n"); return 2; }
+  const bool have_near_list = !near_list.empty();
+  if (have_near_list && !have_near) { std::fprintf(stderr, "calitas: --near-list requires --near-copies M\n"); return 2; }
+  if (have_list_limit && !have_near_list) { std::fprintf(stderr, "calitas: --near-list-limit requires --near-list FILE\n"); return 2; }
+  if (have_list_limit && (near_list_limit < 1 || near_list_limit > CALITAS_NEAR_LIST_MAX)) { std::fprintf(stderr, "calitas: --near-list-limit N: N is 1 .. %d\n", CALITAS_NEAR_LIST_MAX); return 2; }
   ScoreModelFile near_model;
   if (have_near_scores) {
     std::string err;
@@ -421,6 +431,7 @@ static int find_guides_main(int argc, char** argv) {
     }
   }
   uint64_t n_rows = 0;
+  std::vector<uint64_t> kept;      // the rows written, for --near-list
   for (uint64_t i = 0; i < n_sites; i++) {
     if (have_max_near) {
       uint64_t sum = 0;
@@ -430,6 +441,7 @@ static int find_guides_main(int argc, char** argv) {
     if (have_max && n_copies[(size_t)i] > (uint64_t)max_copies) continue;
     if (have_max_seed && n_seed[(size_t)i] > (uint64_t)max_seed_copies) continue;
     n_rows++;
+    kept.push_back(i);
     const calitas_site_t& s = sites[i];
     const char* name; uint64_t len;
     calitas_contig_name(ctx, s.contig_index, &name, &len);
@@ -449,6 +461,45 @@ static int find_guides_main(int argc, char** argv) {
     std::fprintf(f, "\n");
   }
   if (f != stdout) std::fclose(f);
+  // the kept rows' copies within near_m substitutions, a line per record (tools.py guide_near_list, near_list_tsv)
+  if (have_near_list) {
+    FILE* lf = std::fopen(near_list.c_str(), "w");
+    if (!lf) { std::fprintf(stderr, "cannot write %s\n", near_list.c_str()); calitas_free(sites); calitas_destroy(ctx); return 1; }
+    std::fprintf(lf, "guide_id\tchromosome\tstart\tend\tstrand\tpam_index\tmismatches\ttarget\tscore_q32\tscore\n");
+    if (kept.size() > (1ull << 24)) { std::fprintf(stderr, "calitas: more than 16777216 guides: list them in pieces\n"); calitas_free(sites); calitas_destroy(ctx); return 1; }
+    std::string keys;
+    for (uint64_t i : kept) keys += protos[(size_t)i];
+    std::vector<uint64_t> l_near((kept.size() + 1) * near_row, 0), l_off(kept.size() + 1, 0);
+    calitas_score_model_t m;
+    m.protospacer_length = near_model.L; m.gap = near_model.gap; m.pam_mismatch = near_model.pam; m.mismatch = near_model.mm.data();
+    calitas_near_hit_t* found = nullptr; uint64_t n_found = 0;
+    const int rc2 = device < 0 ? calitas_list_near_host(ctx, &g, (int32_t)near_m, have_near_scores ? &m : nullptr, -1, 0, 0, keys.data(), kept.size(), (uint32_t)near_list_limit,
+                                                        l_near.data(), l_off.data(), &found, &n_found)
+                               : calitas_list_near(ctx, &g, (int32_t)near_m, have_near_scores ? &m : nullptr, -1, 0, 0, keys.data(), kept.size(), (uint32_t)near_list_limit,
+                                                   l_near.data(), l_off.data(), &found, &n_found);
+    if (rc2 != CALITAS_OK) die("listing near copies");
+    for (size_t r = 0; r < kept.size(); r++) {
+      const calitas_site_t& s = sites[kept[r]];
+      const char* name; uint64_t len;
+      calitas_contig_name(ctx, s.contig_index, &name, &len);
+      const int64_t lo = s.pam_start < 0 ? s.protospacer_start : std::min<int64_t>(s.protospacer_start, s.pam_start);
+      for (uint64_t at = l_off[r]; at < l_off[r + 1]; at++) {
+        const calitas_near_hit_t& h = found[at];
+        const char* where; uint64_t where_len;
+        calitas_contig_name(ctx, h.contig_index, &where, &where_len);
+        std::string target((size_t)L, 'N');
+        for (int64_t b = 0; b < L; b++) {
+          const char c = "ACGT"[((h.target_lo >> b) & 1u) | (((h.target_hi >> b) & 1u) << 1)];
+          target[(size_t)b] = ((h.diff_mask >> b) & 1u) ? (char)std::tolower((unsigned char)c) : c;
+        }
+        std::fprintf(lf, "%s:%lld:%c\t%s\t%lld\t%lld\t%c\t%d\t%u\t%s\t%llu\t%.6f\n", name, (long long)lo, (char)s.strand, where, (long long)h.protospacer_start,
+                     (long long)h.protospacer_start + (long long)L, (char)h.strand, (int)h.pam_index, (unsigned)h.mismatches, target.c_str(),
+                     (unsigned long long)h.score_q32, (double)h.score_q32 / 4294967296.0);
+      }
+    }
+    calitas_free(found);
+    std::fclose(lf);
+  }
   std::fprintf(stderr, "calitas: %llu guides\n", (unsigned long long)n_rows);
   calitas_free(sites); calitas_destroy(ctx);
   return 0;

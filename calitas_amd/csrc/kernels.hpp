@@ -231,6 +231,31 @@ static_assert(MAX_L == 32, "a row of the packed model per guide position");
 CAL_HD inline uint32_t near_model_index(uint32_t position, uint32_t query_letter, uint32_t site_letter) { return position * 16u + query_letter * 4u + site_letter; }
 CAL_HD inline size_t near_model_offset(int M, int w) { return (size_t)(M + 1) * (((size_t)1 << (2 * w)) + 1); }
 hipError_t launch_sites_near_score(const SitesArgs& a, hipStream_t stream);
+
+// calitas_list_near: the near kernel's pass run a second time (K = L, the model's table in LDS as above), every (site, query) pair
+// that counts written as a record.  The fields no KEYS_* mode reads carry the layout the host made from the first pass's counts:
+//   wg_offset[k]        the first record of distinct key k's stretch in `out`
+//   wg_count[2 k]       the key's cursor, zero at launch: a pair takes its slot with a returning 32-bit atomicAdd
+//   wg_count[2 k + 1]   the stretch's length -- the key's count of the first pass -- or NEAR_LIST_SKIP: the key lists nothing
+//   wg_count[2 n_keys]  the call's error flag, zero at launch: a slot at or beyond the length is not stored, it raises the flag
+//   out, out_capacity   NearHit records (the field's type is the site listing's), all stretches together
+// near_order_kernel then writes every stretch in position order into a second buffer of the same layout.  Both kernels are
+// near_list.hip's: it instantiates sites.hip's template for this one ending.
+struct NearHit {                   // = calitas_near_hit_t
+  uint64_t score_q32;
+  int32_t contig, proto_start;
+  uint32_t target_lo, target_hi, diff_mask;
+  int8_t strand, pam_index;
+  uint8_t mismatches, reserved;
+};
+static_assert(sizeof(NearHit) == 32, "two 16-byte stores per record");
+constexpr uint32_t NEAR_LIST_SKIP = 0xFFFFFFFFu;
+constexpr uint32_t NEAR_ORDER_SHORT = 64;                   // stretches up to here: one wave, a record per lane
+constexpr uint32_t NEAR_ORDER_LONG = 4096;                  // up to here: a workgroup, the position keys in 32 KB of LDS; beyond: copied as they are
+hipError_t launch_sites_near_list(const SitesArgs& a, hipStream_t stream);
+// keys[0 .. n_short): the distinct keys with stretches of 1 .. NEAR_ORDER_SHORT records, keys[n_short .. n_short + n_long): the longer ones
+hipError_t launch_near_order(const NearHit* in, NearHit* out, const uint64_t* base, uint32_t* cursors, const uint32_t* keys, uint32_t n_short, uint32_t n_long,
+                             uint32_t flag_index, hipStream_t stream);
 static_assert(sizeof(SitesArgs) == 176, "a longer argument block costs every sites_kernel launch (DESIGN 4.15)");
 
 }  // namespace calitas

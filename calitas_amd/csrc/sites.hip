@@ -23,6 +23,9 @@
 // held against the query keys that share one of its M + 1 pieces, and a query at Hamming distance d <= M gets 1 in its counter d (near_keys).
 // NEAR SCORE (calitas_score_near): sites_kernel<false, false, KEYS_NEAR_SCORE>, the near kernel's ending with the pair's score besides --
 // a product of Q16 factors of a model table kept in LDS -- added into a sum and a maximum per query behind its counts.
+// NEAR LIST (calitas_list_near): sites_kernel<false, false, KEYS_NEAR_LIST>, the pass run again after the host has laid out a stretch per
+// query key from the counts -- every pair that counts stores a 32-byte record at a slot taken from its key's cursor.  It is
+// instantiated in near_list.hip, beside near_order_kernel, which puts each stretch in position order by ranking.
 // FILTER (calitas_find_sites_filtered): a keep vector per strand from the same registers -- G + C count, base runs and motifs of the
 // protospacer, chain positions 32 + j .. 32 + j + L - 1 -- ANDed into the match vectors in both passes (site_keep).
 #include <hip/hip_runtime.h>
@@ -340,8 +343,16 @@ CAL_DEV void count_keys(const SitesArgs& a, const LaneSites& s, const uint32_t (
 // under the model -- the set bits of m in ascending order, three at most, each one factor of `model` (near_model_index: position, the
 // query's letter, the site's letter; both letters from the four planes) multiplied into s = 2^32 with a truncation by 16 bits -- and
 // the key's row of M + 3 counters takes the count, s into the sum and s into the maximum.
-template <bool SCORE>
-CAL_DEV void near_keys(const SitesArgs& a, const LaneSites& s, const uint32_t (&c_lo)[4], const uint32_t (&c_hi)[4], int L, const uint32_t* model) {
+// LIST (calitas_list_near; the second run of the pass, K = L): a member that counts, and whose key lists, takes the next slot of its
+// key's stretch with a returning atomicAdd on the key's cursor and stores the pair's record there -- the score (2^32 at d = 0), the
+// site's contig, start, strand and PAM index (contig, base0 + j, kp / km), both planes of its key, m and d -- as two 16-byte stores.
+// The slots' order is whatever the waves' order was; near_order_kernel puts the stretch in position order.  A slot the host's layout
+// has no room for is not stored: it raises the call's flag.  Nothing is counted.
+constexpr int NEAR_COUNT = 0, NEAR_SCORE = 1, NEAR_LIST = 2;
+template <int MODE>
+CAL_DEV void near_keys(const SitesArgs& a, const LaneSites& s, const uint32_t (&c_lo)[4], const uint32_t (&c_hi)[4], int L, const uint32_t* model,
+                       uint32_t contig = 0u, int64_t base0 = 0, bool pamless = false) {
+  constexpr bool SCORE = MODE == NEAR_SCORE;
   const int K = a.key_len, M = a.near_m, w = a.near_w;
   const bool first = a.key_first != 0;
   const uint32_t per_table = (1u << (2 * w)) + 1u, piece = (1u << w) - 1u, row = (uint32_t)M + (SCORE ? 3u : 1u);
@@ -374,7 +385,33 @@ CAL_DEV void near_keys(const SitesArgs& a, const LaneSites& s, const uint32_t (&
 #pragma unroll
         for (int e = 0; e < NEAR_MAX_M; e++)
           if (e < p) counts = counts && (m & (piece << (e * w))) != 0u;
-        if constexpr (!SCORE) {
+        if constexpr (MODE == NEAR_LIST) {
+          if (!counts) continue;
+          const uint32_t len = a.wg_count[2u * q.z + 1u];
+          if (len == NEAR_LIST_SKIP) continue;
+          uint64_t sc = 1ull << 32;
+          uint32_t left = m;
+#pragma unroll
+          for (int e = 0; e < NEAR_MAX_M; e++) {
+            if (left == 0u) break;
+            const uint32_t pos = (uint32_t)__builtin_ctz(left);
+            left &= left - 1u;
+            const uint32_t g = ((q.x >> pos) & 1u) | (((q.y >> pos) & 1u) << 1), t = ((k_lo >> pos) & 1u) | (((k_hi >> pos) & 1u) << 1);
+            sc = (sc * model[near_model_index(pos, g, t)]) >> 16;
+          }
+          const uint32_t (&kb)[3] = minus ? s.km : s.kp;
+          const uint32_t pam = ((kb[0] >> j) & 1u) | (((kb[1] >> j) & 1u) << 1) | (((kb[2] >> j) & 1u) << 2);
+          const uint32_t tail = (minus ? (uint32_t)'-' : (uint32_t)'+') | ((pamless ? 0xFFu : pam) << 8) | (d << 16);
+          const uint32_t slot = atomicAdd(&a.wg_count[2u * q.z], 1u);
+          const uint64_t at = a.wg_offset[q.z] + slot;
+          if (slot < len && at < a.out_capacity) {
+            uint4* rec = reinterpret_cast<uint4*>(reinterpret_cast<NearHit*>(a.out) + at);
+            rec[0] = make_uint4((uint32_t)sc, (uint32_t)(sc >> 32), contig, (uint32_t)(int32_t)(base0 + j));
+            rec[1] = make_uint4(k_lo, k_hi, m, tail);
+          } else {
+            a.wg_count[2u * a.n_keys] = 1u;                 // the layout has no room for this pair: the error flag
+          }
+        } else if constexpr (!SCORE) {
           if (counts) (void)atomicAdd(&a.key_counts[q.z * row + d], 1ull);
         } else if (counts) {
           unsigned long long* out = a.key_counts + (uint64_t)q.z * row;
@@ -404,7 +441,8 @@ CAL_DEV void near_keys(const SitesArgs& a, const LaneSites& s, const uint32_t (&
 // their way from memory while it matches the current one's (a workgroup per segment is bound by the rate at which workgroups start).
 // KEYS_NEAR_SCORE: near_keys with the score; the model's packed table stands behind the near kernel's offsets in device memory and is
 // copied to LDS once per workgroup, ahead of the first segment.
-constexpr int KEYS_NONE = 0, KEYS_EXACT = 1, KEYS_NEAR = 2, KEYS_NEAR_SCORE = 3;
+// KEYS_NEAR_LIST: near_keys with the records (calitas_list_near's second run of the pass); the model's table as in KEYS_NEAR_SCORE.
+constexpr int KEYS_NONE = 0, KEYS_EXACT = 1, KEYS_NEAR = 2, KEYS_NEAR_SCORE = 3, KEYS_NEAR_LIST = 4;
 // (a function's own LDS: it belongs to the one instantiation that calls this)
 CAL_DEV uint32_t* near_model_lds() {
   __shared__ uint32_t s_model[NEAR_MODEL_WORDS];
@@ -418,7 +456,7 @@ __global__ __launch_bounds__(SITES_BLOCK_WORDS) void sites_kernel(SitesArgs a) {
   const uint32_t seg0 = blockIdx.x * a.segs_per_wg, seg1 = min(seg0 + a.segs_per_wg, a.n_segs);
   PatConst* pat = (PatConst*)a.pat;
   uint32_t* s_model = nullptr;
-  if constexpr (KEYS == KEYS_NEAR_SCORE) {
+  if constexpr (KEYS == KEYS_NEAR_SCORE || KEYS == KEYS_NEAR_LIST) {
     static_assert(NEAR_MODEL_WORDS == 2 * SITES_BLOCK_WORDS, "two words per lane fill the table");
     s_model = near_model_lds();
     const uint32_t* g_model = a.near_offsets + near_model_offset(a.near_m, a.near_w);
@@ -476,8 +514,9 @@ __global__ __launch_bounds__(SITES_BLOCK_WORDS) void sites_kernel(SitesArgs a) {
     const int64_t base0 = (int64_t)((wb + tid) * 32u) - (int64_t)ci.gbase;
     const LaneSites s = match_word<FILTER>(pat, c_lo, c_hi, c_ex, base0, r_start, r_end);
     if constexpr (KEYS != KEYS_NONE) {
-      if constexpr (KEYS == KEYS_NEAR_SCORE) near_keys<true>(a, s, c_lo, c_hi, pat->proto_len, s_model);
-      else if constexpr (KEYS == KEYS_NEAR) near_keys<false>(a, s, c_lo, c_hi, pat->proto_len, nullptr);
+      if constexpr (KEYS == KEYS_NEAR_LIST) near_keys<NEAR_LIST>(a, s, c_lo, c_hi, pat->proto_len, s_model, ti.contig, base0, pat->pamless != 0);
+      else if constexpr (KEYS == KEYS_NEAR_SCORE) near_keys<NEAR_SCORE>(a, s, c_lo, c_hi, pat->proto_len, s_model);
+      else if constexpr (KEYS == KEYS_NEAR) near_keys<NEAR_COUNT>(a, s, c_lo, c_hi, pat->proto_len, nullptr);
       else count_keys(a, s, c_lo, c_hi, pat->proto_len);
       __syncthreads();                                      // (every lane has its chain out of LDS before the next segment goes in)
       continue;
@@ -528,6 +567,9 @@ __global__ __launch_bounds__(SITES_BLOCK_WORDS) void sites_kernel(SitesArgs a) {
   if (!WRITE && KEYS == KEYS_NONE && tid == 0) flush_totals();
 }
 
+// near_list.hip takes everything above -- for its one instantiation, KEYS_NEAR_LIST -- by including this file with
+// CALITAS_SITES_KERNEL_ONLY defined: its kernels get a code object of their own, and this file's stays what it was without them.
+#ifndef CALITAS_SITES_KERNEL_ONLY
 // Exclusive scan of the workgroups' counts by one workgroup: a stretch per thread, the stretches' sums scanned in LDS.
 constexpr int OFFSETS_THREADS = 1024;
 __global__ __launch_bounds__(OFFSETS_THREADS) void sites_offsets_kernel(const uint32_t* wg_count, uint64_t* wg_offset, uint32_t n) {
@@ -550,8 +592,10 @@ __global__ __launch_bounds__(OFFSETS_THREADS) void sites_offsets_kernel(const ui
   if (tid == OFFSETS_THREADS - 1) wg_offset[n] = s_sum[tid];
 }
 
+#endif
 }  // namespace
 
+#ifndef CALITAS_SITES_KERNEL_ONLY
 hipError_t launch_sites_count(const SitesArgs& a, bool filtered, hipStream_t stream) {
   if (a.n_segs == 0) return hipSuccess;
   const uint32_t n_blocks = (a.n_segs + a.segs_per_wg - 1) / a.segs_per_wg;
@@ -594,4 +638,5 @@ hipError_t launch_sites_near_score(const SitesArgs& a, hipStream_t stream) {
   return hipGetLastError();
 }
 
+#endif
 }  // namespace calitas

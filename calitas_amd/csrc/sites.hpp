@@ -50,3 +50,11 @@ int calitas_score_near_host_impl(const calitas_ctx* ctx, const calitas_guide_t* 
                                  calitas_near_score_t* scores);
 int calitas_score_near_impl(calitas_ctx* ctx, const calitas_guide_t* pattern, int32_t max_mismatches, const calitas_score_model_t* model, int32_t chrom_index,
                             uint64_t start, uint64_t end, const char* queries, uint64_t n_queries, uint64_t* near, calitas_near_score_t* scores);
+// near: as above; hits[offsets[i] .. offsets[i + 1]): a record per site of query i at d = 0 .. M in position order, none where the row of near sums
+// to more than limit; model may be null (every score 2^32)
+int calitas_list_near_host_impl(const calitas_ctx* ctx, const calitas_guide_t* pattern, int32_t max_mismatches, const calitas_score_model_t* model,
+                                int32_t chrom_index, uint64_t start, uint64_t end, const char* queries, uint64_t n_queries, uint32_t limit, uint64_t* near,
+                                uint64_t* offsets, calitas_near_hit_t** hits, uint64_t* n_hits);
+int calitas_list_near_impl(calitas_ctx* ctx, const calitas_guide_t* pattern, int32_t max_mismatches, const calitas_score_model_t* model, int32_t chrom_index,
+                           uint64_t start, uint64_t end, const char* queries, uint64_t n_queries, uint32_t limit, uint64_t* near, uint64_t* offsets,
+                           calitas_near_hit_t** hits, uint64_t* n_hits);

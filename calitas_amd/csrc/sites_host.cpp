@@ -4,7 +4,9 @@
 // kernel.  calitas_count_near / calitas_count_near_host: the pieces' bucket tables, the host twin (plain Hamming distances, no buckets) and
 // the driver of the near kernel.  calitas_score_near / calitas_score_near_host: the same driver with the model's packed table behind the
 // offsets and rows of M + 3 counters, the host twin (the score letter by letter from the caller's table) and the correction of sums and
-// maxima around a U.  No reference counterpart.
+// maxima around a U.  calitas_list_near / calitas_list_near_host: the near driver for the counts, the layout of a stretch of records per
+// distinct query, the pass's second run and the order kernel (near_list.hip), the patch of the stretches beside a U, and the host twin
+// (every pair a record, every stretch through std::sort).  No reference counterpart.
 #include "sites.hpp"
 #include "tuning.hpp"
 
@@ -206,6 +208,15 @@ struct SitesWork {
   size_t near_offsets_cap = 0;
   uint4* d_near_members = nullptr;
   size_t near_members_cap = 0;
+  // calitas_list_near: the stretches' first records, {cursor, length} per distinct key (+ 1: the error flag), the keys whose stretches
+  // are put in order, and the records as the pass stored them (list_in) and in position order (list_out)
+  uint64_t* d_list_base = nullptr;
+  uint32_t* d_list_cursors = nullptr;
+  uint32_t* d_list_order = nullptr;
+  size_t list_keys_cap = 0;
+  NearHit* d_list_in = nullptr;
+  NearHit* d_list_out = nullptr;
+  size_t list_cap = 0;
   // the U / u runs of the resident reference (a U is a plain base to a site and an exception base to the kernels)
   uint64_t u_serial = ~0ull;
   std::vector<Run> u_runs;
@@ -216,6 +227,7 @@ void sites_destroy(SitesWork* w) {
   (void)hipFree(w->d_pat); (void)hipFree(w->d_count); (void)hipFree(w->d_off); (void)hipFree(w->d_totals); (void)hipFree(w->d_out);
   (void)hipFree(w->d_keys); (void)hipFree(w->d_key_index); (void)hipFree(w->d_key_counts);
   (void)hipFree(w->d_near_offsets); (void)hipFree(w->d_near_members);
+  (void)hipFree(w->d_list_base); (void)hipFree(w->d_list_cursors); (void)hipFree(w->d_list_order); (void)hipFree(w->d_list_in); (void)hipFree(w->d_list_out);
   delete w;
 }
 
@@ -645,9 +657,12 @@ namespace {
 // The near kernel's launch for a planned call: the pieces' bucket tables, the members, the counters zeroed, one pass, one copy-back.
 // model == nullptr: calitas_count_near, counts of n_keys rows of M + 1 words.  Otherwise NEAR_MODEL_WORDS words, the packed table of
 // calitas_score_near: it rides behind the offsets, and the rows have M + 3 words (the counts, the sum, the maximum).
-int run_near(calitas_ctx* ctx, const NearCall& call, int32_t chrom_index, uint64_t start, uint64_t end, const uint32_t* model, std::vector<uint64_t>& counts) {
+// again != nullptr (calitas_list_near, with a model): the table rides along, the counts alone are taken (rows of M + 1 words), and
+// *again receives the launch's arguments -- tables, members and patterns stay on the device for the pass's second run.
+int run_near(calitas_ctx* ctx, const NearCall& call, int32_t chrom_index, uint64_t start, uint64_t end, const uint32_t* model, std::vector<uint64_t>& counts,
+             SitesArgs* again = nullptr) {
   const std::vector<uint64_t>& keys = call.copies.keys;
-  const size_t n_keys = keys.size(), row = (size_t)call.M + 1, n_counters = n_keys * (row + (model ? 2 : 0));
+  const size_t n_keys = keys.size(), row = (size_t)call.M + 1, n_counters = n_keys * (row + (model && !again ? 2 : 0));
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   if (!ctx->sites) ctx->sites = new SitesWork();
   SitesWork* w = ctx->sites;
@@ -697,9 +712,10 @@ int run_near(calitas_ctx* ctx, const NearCall& call, int32_t chrom_index, uint64
   HIP_TRY(ctx, hipMemcpyAsync(w->d_near_offsets, offsets.data(), offsets.size() * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
   HIP_TRY(ctx, hipMemcpyAsync(w->d_near_members, members.data(), n_members * sizeof(uint4), hipMemcpyHostToDevice, ctx->stream));
   HIP_TRY(ctx, hipMemsetAsync(w->d_key_counts, 0, n_counters * sizeof(unsigned long long), ctx->stream));
-  HIP_TRY(ctx, model ? launch_sites_near_score(a, ctx->stream) : launch_sites_near(a, ctx->stream));
+  HIP_TRY(ctx, model && !again ? launch_sites_near_score(a, ctx->stream) : launch_sites_near(a, ctx->stream));
   HIP_TRY(ctx, hipMemcpyAsync(counts.data(), w->d_key_counts, n_counters * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  if (again) *again = a;
   return CALITAS_OK;
 }
 
@@ -737,11 +753,8 @@ struct NearScoreCall {
   const uint32_t* mismatch = nullptr;                // the caller's [L][5][5]
 };
 
-// checked in this order: what calitas_count_near checks (the key is the whole protospacer), then the model as calitas_search_scores
-// checks it -- of which this call reads the mismatch table alone
-int plan_near_score(calitas_ctx* c, const calitas_guide_t* pattern, int32_t max_mismatches, const calitas_score_model_t* model, int32_t chrom_index,
-                    uint64_t start, uint64_t end, const char* queries, uint64_t n_queries, NearScoreCall& call) {
-  if (int rc = plan_near(c, pattern, 0, max_mismatches, chrom_index, start, end, queries, n_queries, call.near)) return rc;
+// the model as calitas_search_scores checks it -- of which the near calls read the mismatch table alone
+int check_near_model(calitas_ctx* c, const calitas_score_model_t* model, NearScoreCall& call) {
   const int L = call.near.copies.L;
   if (!model || !model->mismatch) return calitas_fail(c, CALITAS_EINVAL, "the score model has no mismatch table");
   if (model->protospacer_length != L)
@@ -750,6 +763,13 @@ int plan_near_score(calitas_ctx* c, const calitas_guide_t* pattern, int32_t max_
     if (model->mismatch[i] > 65536u) return calitas_fail(c, CALITAS_EINVAL, "a factor of the score model is above 65536 (1.0)");
   call.mismatch = model->mismatch;
   return CALITAS_OK;
+}
+
+// checked in this order: what calitas_count_near checks (the key is the whole protospacer), then the model
+int plan_near_score(calitas_ctx* c, const calitas_guide_t* pattern, int32_t max_mismatches, const calitas_score_model_t* model, int32_t chrom_index,
+                    uint64_t start, uint64_t end, const char* queries, uint64_t n_queries, NearScoreCall& call) {
+  if (int rc = plan_near(c, pattern, 0, max_mismatches, chrom_index, start, end, queries, n_queries, call.near)) return rc;
+  return check_near_model(c, model, call);
 }
 
 // The contract's loop on two keys of L positions, letter by letter from the planes: the factors of the differing positions in
@@ -849,4 +869,237 @@ int calitas_score_near_impl(calitas_ctx* ctx, const calitas_guide_t* pattern, in
   add_near_scores(ref, call, kernel_has, false, rows);
   near_score_rows(call, rows, n_queries, near, scores);
   return CALITAS_OK;
+}
+
+// ---- calitas_list_near: where every query's copies within M substitutions stand ----
+
+namespace {
+
+struct NearListCall {
+  NearScoreCall score;                               // K = L; mismatch == nullptr: no weights, every score is 2^32
+  uint32_t limit = 0;
+};
+
+// checked in this order: what calitas_score_near checks, a NULL model being legal; then the limit
+int plan_near_list(calitas_ctx* c, const calitas_guide_t* pattern, int32_t max_mismatches, const calitas_score_model_t* model, int32_t chrom_index,
+                   uint64_t start, uint64_t end, const char* queries, uint64_t n_queries, uint32_t limit, NearListCall& call) {
+  if (int rc = plan_near(c, pattern, 0, max_mismatches, chrom_index, start, end, queries, n_queries, call.score.near)) return rc;
+  if (model)
+    if (int rc = check_near_model(c, model, call.score)) return rc;
+  if (limit < 1 || limit > CALITAS_NEAR_LIST_MAX)
+    return calitas_fail(c, CALITAS_EINVAL, "limit is " + std::to_string(limit) + ": it is 1 .. " + std::to_string(CALITAS_NEAR_LIST_MAX));
+  call.limit = limit;
+  return CALITAS_OK;
+}
+
+bool hit_less(const calitas_near_hit_t& a, const calitas_near_hit_t& b) {
+  if (a.contig_index != b.contig_index) return a.contig_index < b.contig_index;
+  if (a.protospacer_start != b.protospacer_start) return a.protospacer_start < b.protospacer_start;
+  return a.strand == '+' && b.strand == '-';
+}
+
+// the record of a site whose key is within M of a query's, from the host's side: the twin's, and the ones a U keeps from the kernel
+calitas_near_hit_t near_hit(const NearListCall& call, const calitas_site_t& s, uint64_t site_key, uint64_t query_key) {
+  const uint64_t x = site_key ^ query_key;
+  calitas_near_hit_t h;
+  std::memset(&h, 0, sizeof(h));
+  h.score_q32 = call.score.mismatch ? near_pair_score(call.score.mismatch, call.score.near.copies.L, query_key, site_key) : 1ull << 32;
+  h.contig_index = s.contig_index; h.protospacer_start = s.protospacer_start;
+  h.target_lo = (uint32_t)site_key; h.target_hi = (uint32_t)(site_key >> 32);
+  h.diff_mask = (uint32_t)x | (uint32_t)(x >> 32);
+  h.strand = s.strand; h.pam_index = s.pam_index; h.mismatches = (uint8_t)__builtin_popcount(h.diff_mask);
+  return h;
+}
+
+typedef std::pair<const calitas_near_hit_t*, size_t> HitSpan;
+
+// What the call hands over, from the distinct keys' counts and ordered stretches: near, the stretches laid out in query order -- a
+// key over the limit lists nothing, a duplicate gets its key's stretch again -- and the one block of records.
+int near_list_block(calitas_ctx* c, const NearListCall& call, const std::vector<uint64_t>& counts, const std::vector<HitSpan>& spans, uint64_t n_queries,
+                    uint64_t* near, uint64_t* offsets, calitas_near_hit_t** hits, uint64_t* n_hits) {
+  const NearCall& nc = call.score.near;
+  const size_t row = (size_t)nc.M + 1;
+  if (n_queries) near_rows(nc, counts, n_queries, near);
+  uint64_t run = 0;
+  for (uint64_t q = 0; q < n_queries; q++) {
+    const size_t k = nc.copies.of_query[(size_t)q];
+    uint64_t sum = 0;
+    for (size_t d = 0; d < row; d++) sum += counts[k * row + d];
+    offsets[q] = run;
+    if (sum > call.limit) continue;
+    if (spans[k].second != sum) return calitas_fail(c, CALITAS_EHIP, "calitas_list_near: a query's records are not as many as its counts (internal error)");
+    run += sum;
+  }
+  offsets[n_queries] = run;
+  calitas_near_hit_t* block = (calitas_near_hit_t*)calitas_out_alloc(std::max<uint64_t>(1, run) * sizeof(calitas_near_hit_t));
+  if (!block) return calitas_fail(c, CALITAS_ENOMEM, "the records do not fit the host's memory: list the queries in pieces");
+  for (uint64_t q = 0; q < n_queries; q++) {
+    const uint64_t n = offsets[q + 1] - offsets[q];
+    if (n) std::memcpy(block + offsets[q], spans[nc.copies.of_query[(size_t)q]].first, n * sizeof(calitas_near_hit_t));
+  }
+  *hits = block; *n_hits = run;
+  return CALITAS_OK;
+}
+
+}  // namespace
+
+int calitas_list_near_host_impl(const calitas_ctx* ctx, const calitas_guide_t* pattern, int32_t max_mismatches, const calitas_score_model_t* model,
+                                int32_t chrom_index, uint64_t start, uint64_t end, const char* queries, uint64_t n_queries, uint32_t limit, uint64_t* near,
+                                uint64_t* offsets, calitas_near_hit_t** hits, uint64_t* n_hits) {
+  calitas_ctx* c = const_cast<calitas_ctx*>(ctx);
+  NearListCall call;
+  if (int rc = plan_near_list(c, pattern, max_mismatches, model, chrom_index, start, end, queries, n_queries, limit, call)) return rc;
+  const NearCall& nc = call.score.near;
+  const CopiesCall& cc = nc.copies;
+  const size_t n_keys = cc.keys.size(), row = (size_t)nc.M + 1;
+  std::vector<uint64_t> counts(n_keys * row, 0);
+  std::vector<std::vector<calitas_near_hit_t>> lists(n_keys);
+  std::vector<calitas_site_t> found;
+  for (int i = cc.site.c_first; i <= cc.site.c_last && n_keys; i++) {
+    const uint64_t len = ctx->ref.contigs[(size_t)i].len;
+    found.clear();
+    host_sites(ctx->ref, cc.site.tab.pat, nullptr, i, 0, (int64_t)len, (int64_t)std::min(start, len), (int64_t)region_end(len, end), found, nullptr);
+    for (const calitas_site_t& s : found) {
+      const uint64_t key = key_at(ctx->ref, ctx->ref.contigs[(size_t)s.contig_index].gbase, s.protospacer_start, cc, s.strand == '-');
+      for (size_t k = 0; k < n_keys; k++) {
+        const int d = key_distance(key, cc.keys[k]);
+        if (d > nc.M) continue;
+        counts[k * row + (size_t)d]++;
+        if (lists[k].size() <= call.limit) lists[k].push_back(near_hit(call, s, key, cc.keys[k]));   // (one beyond the limit: such a key lists nothing)
+      }
+    }
+  }
+  std::vector<HitSpan> spans(n_keys);
+  for (size_t k = 0; k < n_keys; k++) {
+    std::sort(lists[k].begin(), lists[k].end(), hit_less);
+    spans[k] = HitSpan(lists[k].data(), lists[k].size());
+  }
+  return near_list_block(c, call, counts, spans, n_queries, near, offsets, hits, n_hits);
+}
+
+int calitas_list_near_impl(calitas_ctx* ctx, const calitas_guide_t* pattern, int32_t max_mismatches, const calitas_score_model_t* model, int32_t chrom_index,
+                           uint64_t start, uint64_t end, const char* queries, uint64_t n_queries, uint32_t limit, uint64_t* near, uint64_t* offsets,
+                           calitas_near_hit_t** hits, uint64_t* n_hits) {
+  if (ctx->device < 0) return calitas_fail(ctx, CALITAS_ENODEV, "host-only context: calitas_list_near needs a GPU (there is no CPU fallback; calitas_list_near_host is the host twin)");
+  static_assert(sizeof(NearHit) == sizeof(calitas_near_hit_t) && offsetof(NearHit, score_q32) == offsetof(calitas_near_hit_t, score_q32) &&
+                offsetof(NearHit, contig) == offsetof(calitas_near_hit_t, contig_index) && offsetof(NearHit, proto_start) == offsetof(calitas_near_hit_t, protospacer_start) &&
+                offsetof(NearHit, target_lo) == offsetof(calitas_near_hit_t, target_lo) && offsetof(NearHit, target_hi) == offsetof(calitas_near_hit_t, target_hi) &&
+                offsetof(NearHit, diff_mask) == offsetof(calitas_near_hit_t, diff_mask) && offsetof(NearHit, strand) == offsetof(calitas_near_hit_t, strand) &&
+                offsetof(NearHit, pam_index) == offsetof(calitas_near_hit_t, pam_index) && offsetof(NearHit, mismatches) == offsetof(calitas_near_hit_t, mismatches),
+                "the kernel writes calitas_near_hit_t");
+  NearListCall call;
+  if (int rc = plan_near_list(ctx, pattern, max_mismatches, model, chrom_index, start, end, queries, n_queries, limit, call)) return rc;
+  const NearCall& nc = call.score.near;
+  const std::vector<uint64_t>& keys = nc.copies.keys;
+  const PackedRef& ref = ctx->ref;
+  const size_t n_keys = keys.size(), row = (size_t)nc.M + 1;
+  std::vector<uint64_t> counts(n_keys * row, 0);
+  std::vector<HitSpan> spans(n_keys, HitSpan(nullptr, 0));
+  if (n_keys == 0 || ref.contigs.empty())            // nothing to look up, or nothing to scan
+    return near_list_block(ctx, call, counts, spans, n_queries, near, offsets, hits, n_hits);
+
+  // pass 1: the counts.  The model's 4 x 4 blocks as the kernel indexes them ride along for pass 2; without a model every factor is 1.0
+  std::vector<uint32_t> packed(NEAR_MODEL_WORDS, call.score.mismatch ? 0u : 65536u);
+  for (uint32_t i = 0; call.score.mismatch && i < (uint32_t)nc.copies.L; i++)
+    for (uint32_t g = 0; g < 4; g++)
+      for (uint32_t t = 0; t < 4; t++) packed[near_model_index(i, g, t)] = call.score.mismatch[(size_t)i * 25 + g * 5 + t];
+  SitesArgs a{};
+  if (int rc = run_near(ctx, nc, chrom_index, start, end, packed.data(), counts, &a)) return rc;
+
+  // The layout.  A U is a T to a site and an exception base to the kernel, so the counts are corrected as calitas_count_near's are,
+  // and the corrected counts decide whether a key lists.  A key that does gets room for what the KERNEL will store, its own count;
+  // where the two differ the host patches the stretch below.
+  std::vector<uint64_t> kernel_sum(n_keys, 0);
+  for (size_t k = 0; k < n_keys; k++)
+    for (size_t d = 0; d < row; d++) kernel_sum[k] += counts[k * row + d];
+  std::vector<calitas_site_t> with_u, kernel_has;
+  sites_with_u(ctx, nc.copies.site, start, end, with_u, kernel_has);
+  add_near_sites(ref, nc, with_u, 1, counts);
+  add_near_sites(ref, nc, kernel_has, ~0ull, counts);       // (- 1)
+  std::vector<uint64_t> base(n_keys, 0);
+  std::vector<uint32_t> cursors(2 * n_keys + 1, 0), order, longer;
+  uint64_t total = 0;
+  for (size_t k = 0; k < n_keys; k++) {
+    uint64_t sum = 0;
+    for (size_t d = 0; d < row; d++) sum += counts[k * row + d];
+    base[k] = total;
+    cursors[2 * k + 1] = NEAR_LIST_SKIP;
+    if (sum > call.limit) continue;
+    if (kernel_sum[k] >= NEAR_LIST_SKIP) return calitas_fail(ctx, CALITAS_ENOMEM, "the records do not fit the device: list the queries in pieces");
+    cursors[2 * k + 1] = (uint32_t)kernel_sum[k];
+    total += kernel_sum[k];
+    if (kernel_sum[k] > NEAR_ORDER_SHORT) longer.push_back((uint32_t)k);
+    else if (kernel_sum[k]) order.push_back((uint32_t)k);
+  }
+  const uint32_t n_short = (uint32_t)order.size(), n_long = (uint32_t)longer.size();
+  order.insert(order.end(), longer.begin(), longer.end());
+
+  // pass 2, the order, one copy-back
+  std::vector<calitas_near_hit_t> dev;
+  if (total) {
+    SitesWork* w = ctx->sites;
+    try { dev.resize((size_t)total); } catch (const std::bad_alloc&) { return calitas_fail(ctx, CALITAS_ENOMEM, "the records do not fit the host's memory: list the queries in pieces"); }
+    if (w->list_keys_cap < n_keys) {
+      (void)hipFree(w->d_list_base); (void)hipFree(w->d_list_cursors); (void)hipFree(w->d_list_order);
+      w->d_list_base = nullptr; w->d_list_cursors = nullptr; w->d_list_order = nullptr; w->list_keys_cap = 0;
+      HIP_TRY(ctx, hipMalloc((void**)&w->d_list_base, n_keys * sizeof(uint64_t)));
+      HIP_TRY(ctx, hipMalloc((void**)&w->d_list_cursors, (2 * n_keys + 1) * sizeof(uint32_t)));
+      HIP_TRY(ctx, hipMalloc((void**)&w->d_list_order, n_keys * sizeof(uint32_t)));
+      w->list_keys_cap = n_keys;
+    }
+    if (w->list_cap < total) {
+      (void)hipFree(w->d_list_in); (void)hipFree(w->d_list_out); w->d_list_in = nullptr; w->d_list_out = nullptr; w->list_cap = 0;
+      if (hipMalloc((void**)&w->d_list_in, total * sizeof(NearHit)) != hipSuccess || hipMalloc((void**)&w->d_list_out, total * sizeof(NearHit)) != hipSuccess) {
+        (void)hipGetLastError();
+        (void)hipFree(w->d_list_in); w->d_list_in = nullptr;
+        return calitas_fail(ctx, CALITAS_ENOMEM, "the records do not fit the device: list the queries in pieces");
+      }
+      w->list_cap = total;
+    }
+    a.wg_offset = w->d_list_base; a.wg_count = w->d_list_cursors; a.out = reinterpret_cast<SiteRecord*>(w->d_list_in); a.out_capacity = total;
+    uint32_t flag = 0;
+    HIP_TRY(ctx, hipMemcpyAsync(w->d_list_base, base.data(), n_keys * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(w->d_list_cursors, cursors.data(), (2 * n_keys + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(w->d_list_order, order.data(), order.size() * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, launch_sites_near_list(a, ctx->stream));
+    HIP_TRY(ctx, launch_near_order(w->d_list_in, w->d_list_out, w->d_list_base, w->d_list_cursors, w->d_list_order, n_short, n_long, (uint32_t)(2 * n_keys), ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(&flag, w->d_list_cursors + 2 * n_keys, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(dev.data(), w->d_list_out, total * sizeof(NearHit), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if (flag != 0) return calitas_fail(ctx, CALITAS_EHIP, "calitas_list_near: the second pass found other pairs than the first counted (internal error)");
+  }
+  for (size_t k = 0; k < n_keys; k++)
+    if (cursors[2 * k + 1] != NEAR_LIST_SKIP) spans[k] = HitSpan(dev.data() + base[k], cursors[2 * k + 1]);
+
+  // Beside a U: the stretches of the keys within M of such a site lose the records the kernel has in its place, gain the site's own
+  // and are put in order again -- also the few a U made longer than the order kernel takes.
+  std::vector<std::vector<calitas_near_hit_t>> fixed;
+  if (!with_u.empty() || !kernel_has.empty()) {
+    std::vector<uint64_t> key_in(with_u.size()), key_out(kernel_has.size());
+    for (size_t i = 0; i < with_u.size(); i++) key_in[i] = key_at(ref, ref.contigs[(size_t)with_u[i].contig_index].gbase, with_u[i].protospacer_start, nc.copies, with_u[i].strand == '-');
+    for (size_t i = 0; i < kernel_has.size(); i++) key_out[i] = key_at(ref, ref.contigs[(size_t)kernel_has[i].contig_index].gbase, kernel_has[i].protospacer_start, nc.copies, kernel_has[i].strand == '-');
+    fixed.reserve(n_keys);                                  // (the spans point into its elements)
+    for (size_t k = 0; k < n_keys; k++) {
+      if (cursors[2 * k + 1] == NEAR_LIST_SKIP) continue;
+      bool touched = false;
+      for (size_t i = 0; i < key_in.size() && !touched; i++) touched = key_distance(key_in[i], keys[k]) <= nc.M;
+      for (size_t i = 0; i < key_out.size() && !touched; i++) touched = key_distance(key_out[i], keys[k]) <= nc.M;
+      if (!touched) continue;
+      fixed.emplace_back(spans[k].first, spans[k].first + spans[k].second);
+      std::vector<calitas_near_hit_t>& v = fixed.back();
+      for (size_t i = 0; i < key_out.size(); i++) {
+        if (key_distance(key_out[i], keys[k]) > nc.M) continue;
+        const calitas_site_t& s = kernel_has[i];
+        const auto at = std::find_if(v.begin(), v.end(), [&](const calitas_near_hit_t& h) {
+          return h.contig_index == s.contig_index && h.protospacer_start == s.protospacer_start && h.strand == s.strand; });
+        if (at == v.end()) return calitas_fail(ctx, CALITAS_EHIP, "calitas_list_near: a record the kernel should have written beside a U is not there (internal error)");
+        v.erase(at);
+      }
+      for (size_t i = 0; i < key_in.size(); i++)
+        if (key_distance(key_in[i], keys[k]) <= nc.M) v.push_back(near_hit(call, with_u[i], key_in[i], keys[k]));
+      std::sort(v.begin(), v.end(), hit_less);
+      spans[k] = HitSpan(v.data(), v.size());
+    }
+  }
+  return near_list_block(ctx, call, counts, spans, n_queries, near, offsets, hits, n_hits);
 }

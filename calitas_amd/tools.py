@@ -459,6 +459,37 @@ def guide_near_scores(ctx, pattern, rows, max_mismatches, model, host=False):
     return NearScores(np.concatenate([p.near for p in parts]), np.concatenate([p.sum_q32 for p in parts]), np.concatenate([p.max_q32 for p in parts]))
 
 
+NEAR_LIST_COLUMNS = ["guide_id", "chromosome", "start", "end", "strand", "pam_index", "mismatches", "target", "score_q32", "score"]
+
+
+def guide_near_list(ctx, pattern, rows, max_mismatches, model=None, limit=1000, host=False):
+    """Context.list_near for the GuideSites of find_guides: per row the records of its protospacer's copies within max_mismatches
+    substitutions in the WHOLE resident reference, its own site among them, scored under `model` (None: no weights).  A NearList
+    aligned with rows; a row whose copies are more than `limit` lists nothing."""
+    if not isinstance(pattern, Guide):
+        pattern = Guide(pattern)
+    L = pattern.protospacer_length
+    five = pattern.pam_is_five_prime and bool(pattern.pams)
+    keys = [r.guide[len(r.guide) - L:] if five else r.guide[:L] for r in rows]
+    if len(keys) > COPIES_MAX_QUERIES:
+        raise ValueError("more than %d guides: list them in pieces" % COPIES_MAX_QUERIES)
+    return ctx.list_near(pattern, keys, int(max_mismatches), model, limit=limit, host=host)
+
+
+def near_list_tsv(rows, names, listing):
+    """The --near-list table: NEAR_LIST_COLUMNS, a line per record of `listing` (guide_near_list of `rows`) in the rows' and the
+    records' order.  guide_id is the row's; chromosome (names: the contigs' names), start and end (0-based, half open), strand and
+    pam_index are the copy's protospacer's; target is its letters as the guide reads them, lower case where they differ from the
+    guide's; score is score_q32 / 2^32 (%.6f).  A row over the limit writes no line."""
+    lines = ["\t".join(NEAR_LIST_COLUMNS)]
+    for i, r in enumerate(rows):
+        for h in listing.of(i):
+            start = int(h["protospacer_start"])
+            lines.append("\t".join([r.guide_id, names[int(h["contig_index"])], str(start), str(start + listing.L), h["strand"].decode(), str(int(h["pam_index"])),
+                                    str(int(h["mismatches"])), listing.target(h), str(int(h["score_q32"])), "%.6f" % (int(h["score_q32"]) / 4294967296.0)]))
+    return "\n".join(lines) + "\n"
+
+
 def guides_tsv(rows, tables=None, scores=None, copies=None, seed_copies=None, near=None, near_scores=None):
     """The FindGuides table: GUIDE_COLUMNS, one row per GuideSite; with tables (guide_counts) also hits -- the table's sum -- and
     hits_mm0 .. hits_mmE, the hits per number of protospacer mismatches, summed over strands, gaps and PAM mismatches; with scores
@@ -538,7 +569,7 @@ def site_filter_of_flags(L, gc_min=None, gc_max=None, max_run=None, avoid=()):
 
 def find_guides_tool(ref, pattern, auxiliary_pams=(), chrom=None, start=0, end=None, output=None, counts=False, device=0, scores=None,
                      gc_min=None, gc_max=None, max_run=None, avoid=(), copies=False, seed_copies=None, max_copies=None, max_seed_copies=None,
-                     near_copies=None, max_near_copies=None, near_scores=None, **search):
+                     near_copies=None, max_near_copies=None, near_scores=None, near_list=None, near_list_limit=None, **search):
     """`python -m calitas_amd FindGuides`: the guides of a region as a TSV (guides_tsv); counts=True: every distinct guide also goes
     through the off-target search with the SearchReference flags in `search` (make_params names); scores=ScoreModel (or its file):
     through search_scores_batch instead, which adds perfect and specificity.  gc_min, gc_max, max_run, avoid: the site filter's flags
@@ -550,7 +581,9 @@ def find_guides_tool(ref, pattern, auxiliary_pams=(), chrom=None, start=0, end=N
     protospacer); max_near_copies=N (N >= 1, needs near_copies) drops the rows whose columns sum to more than N, likewise before
     anything is searched.  near_scores=ScoreModel (or its file; needs near_copies, the model's length is the protospacer's): the
     columns near_sum_q32, near_max_q32 and near_specificity, from the one guide_near_scores pass that then gives the copies_mm columns
-    as well.  These seven work with device -1 through the host twin.  Returns the text."""
+    as well.  near_list=FILE (needs near_copies): the kept rows' copies within M substitutions, one per line, to FILE (near_list_tsv;
+    scored under near_scores' model when given); near_list_limit=N (1 .. 4096, default 1000): a row with more copies writes no line.
+    These nine work with device -1 through the host twin.  Returns the text."""
     if (counts or scores is not None) and device < 0:
         raise ValueError("--counts and --scores search on the GPU: they cannot run with --device -1")
     if isinstance(scores, str):
@@ -581,6 +614,12 @@ def find_guides_tool(ref, pattern, auxiliary_pams=(), chrom=None, start=0, end=N
         near_scores = ScoreModel.read(near_scores)
     if near_scores is not None and near_scores.L != pat.protospacer_length:
         raise ValueError("--near-scores: the model is for protospacers of %d bases, the pattern's has %d" % (near_scores.L, pat.protospacer_length))
+    if near_list is not None and near_copies is None:
+        raise ValueError("--near-list requires --near-copies M")
+    if near_list_limit is not None and near_list is None:
+        raise ValueError("--near-list-limit requires --near-list FILE")
+    if near_list_limit is not None and not 1 <= int(near_list_limit) <= 4096:
+        raise ValueError("--near-list-limit N: N is 1 .. 4096")
     ctx = Context(device)
     try:
         ctx.set_reference_fasta(ref)
@@ -607,6 +646,10 @@ def find_guides_tool(ref, pattern, auxiliary_pams=(), chrom=None, start=0, end=N
         tables = guide_counts(ctx, [r.guide for r in rows], make_params(**search)) if counts and scores is None else None
         scored = guide_scores(ctx, [r.guide for r in rows], make_params(**search), scores) if scores is not None else None
         text = guides_tsv(rows, tables, scored, copies=n_copies, seed_copies=n_seed, near=n_near, near_scores=scored_near)
+        if near_list is not None:
+            listing = guide_near_list(ctx, pat, rows, int(near_copies), near_scores, limit=1000 if near_list_limit is None else int(near_list_limit), host=device < 0)
+            with open(near_list, "w") as f:
+                f.write(near_list_tsv(rows, ctx.contig_names, listing))
         if output is not None:
             with open(output, "w") as f:
                 f.write(text)

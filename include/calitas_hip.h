@@ -464,6 +464,46 @@ int calitas_score_near_host(const calitas_ctx* ctx, const calitas_guide_t* patte
                             int32_t chrom_index, uint64_t start, uint64_t end, const char* queries, uint64_t n_queries, uint64_t* near,
                             calitas_near_score_t* scores);
 
+/* Near copies listed: WHERE every query's copies within M substitutions stand.  No reference counterpart.
+ * Sites, region rules, absent contigs, one site per (contig, strand, protospacer start), the queries' letters (U as T), the key (the
+ * whole protospacer: queries holds n_queries * L letters) and the limit of 2^24 queries are those of calitas_score_near; near receives
+ * exactly what calitas_count_near(pattern, 0, M, ...) returns.
+ * Query q's records are (*hits)[offsets[q] .. offsets[q + 1]); offsets has n_queries + 1 entries and is non-decreasing, *n_hits is its
+ * last one.  A stretch holds one record for every (site, query) pair at d = 0 .. M -- d = 0 included: the guide's own site and its exact
+ * copies -- ordered by contig_index, then protospacer_start, then '+' before '-'.  That order is total within a stretch, so the device,
+ * the host twin and repeated calls return the same bytes.  A query whose row of near sums to more than `limit` (1 ..
+ * CALITAS_NEAR_LIST_MAX) lists nothing: its stretch is empty, and its row of near says why.  Duplicated queries each get the full stretch.
+ * score_q32 is the pair's score as calitas_score_near defines it, 1 << 32 at d = 0; model == NULL means no weights: every score is
+ * 1 << 32.  Over disjoint contig sets a query's lists concatenate in contig order (and a query over the limit in the sum lists nothing).
+ * *hits is one block for calitas_free, also when it holds no record; n_queries == 0 is legal.
+ * CALITAS_EINVAL, with a message that names the field: what calitas_score_near refuses, in its order, except that a NULL model is
+ * legal; then a limit outside 1 .. CALITAS_NEAR_LIST_MAX.
+ * Runs on the device: the near kernel's pass once for the counts; the host lays a stretch per distinct query out of them; the pass
+ * again, every pair that counts storing its record at a slot it takes from its query's cursor; a small kernel that puts every stretch
+ * in position order by ranking; one copy-back.  Stretches next to a U in the reference are corrected on the host.
+ * CALITAS_ENOMEM when the records or the tables do not fit, CALITAS_ENODEV on a host-only context. */
+#define CALITAS_NEAR_LIST_MAX 4096
+typedef struct {                 /* 32 bytes */
+  uint64_t score_q32;
+  int32_t  contig_index;
+  int32_t  protospacer_start;    /* leftmost base, forward coordinates, 0-based: calitas_site_t's */
+  uint32_t target_lo, target_hi; /* the site's protospacer as the guide reads it, as bit-planes: bit i of target_lo / target_hi = low / high
+                                    bit of the code of guide position i (A 0, C 1, G 2, T 3) */
+  uint32_t diff_mask;            /* bit i: guide position i differs from the query */
+  int8_t   strand;               /* '+' or '-' */
+  int8_t   pam_index;            /* the first PAM that matches; -1 for a PAM-less pattern */
+  uint8_t  mismatches;           /* popcount(diff_mask), 0 .. M */
+  uint8_t  reserved;             /* 0 */
+} calitas_near_hit_t;
+int calitas_list_near(calitas_ctx* ctx, const calitas_guide_t* pattern, int32_t max_mismatches, const calitas_score_model_t* model /* may be NULL */,
+                      int32_t chrom_index, uint64_t start, uint64_t end, const char* queries, uint64_t n_queries, uint32_t limit,
+                      uint64_t* near /* n_queries * (M + 1) */, uint64_t* offsets /* n_queries + 1 */, calitas_near_hit_t** hits, uint64_t* n_hits);
+/* The host twin of calitas_list_near: the base-by-base walk of calitas_score_near_host, every pair a record, every stretch through
+ * std::sort; also on a host-only context.  No reference counterpart. */
+int calitas_list_near_host(const calitas_ctx* ctx, const calitas_guide_t* pattern, int32_t max_mismatches, const calitas_score_model_t* model,
+                           int32_t chrom_index, uint64_t start, uint64_t end, const char* queries, uint64_t n_queries, uint32_t limit,
+                           uint64_t* near, uint64_t* offsets, calitas_near_hit_t** hits, uint64_t* n_hits);
+
 /* The K highest-scoring imperfect hits of a guide, from the pass that scores them.  No reference counterpart.
  * The candidates are the kept hits that are not perfect (total_mm_plus_gaps != 0); they are ordered by score_q32 descending, and among
  * equal scores the hit whose row comes earlier in the hits.txt of the same call comes first.  That is a total order: the n records are

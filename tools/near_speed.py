@@ -1,10 +1,12 @@
 """calitas_count_near timed on the bench genome recipe (bench.build_genome; scale 1 = hg38-sized), alone on the chip, interleaved round by
-round in ONE process: python tools/near_speed.py [scale] [rounds] [--existing] [--tree DIR] [--search-ms MS]
+round in ONE process: python tools/near_speed.py [scale] [rounds] [--existing | --list] [--tree DIR] [--search-ms MS]
 
   count plain       : calitas_count_sites of NNNNNNNNNNNNNNNNNNNNnrg over the whole genome, no filter -- the same match work
   copies 10 kb      : calitas_count_copies over the whole genome, the queries the protospacers of every site of a 10-kb region (K = 20)
   near 10 kb M=1..3 : calitas_count_near of the same queries at max_mismatches 1, 2, 3
   scored 10 kb M=.. : calitas_score_near of the same queries and M under a model (every factor 0.6), beside each K = 20 near row
+  listed 10 kb M=.. : calitas_list_near of the same queries, M and model with limit 1000, beside each scored row: the records returned
+                      and the queries over the limit stand in the row
   ... K=12 M=2      : the PAM-proximal 12 bases as the key, copies and near at M = 2
   ... 1 Mb          : the same rows for the guides of a 1-Mb region
 
@@ -19,8 +21,9 @@ sets counted over their own region against the host twin.
 The bench genome is independent random bases with short tandem repeats planted (bench.gen_contig): it has almost no near-duplicate
 20-mers, so what a real genome's repeat families cost -- long buckets and hot counters -- is NOT measured here.
 
---existing: the calls that existed before calitas_score_near alone -- `count plain`, `copies 10 kb` and `near 10 kb M=2` -- which the
-parent commit's checkout has too; --tree DIR takes package and library from another checkout (built).  With both, two builds are compared, whole
+--list: the K = 20 rows alone (near, scored, listed), for a look at the listing by itself or under a profiler.
+--existing: the calls that existed before calitas_list_near alone -- `count plain`, `copies 10 kb`, `near 10 kb M=2` and `scored 10 kb
+M=2` -- which the parent commit's checkout has too; --tree DIR takes package and library from another checkout (built).  With both, two builds are compared, whole
 processes alternated:  python tools/near_speed.py 1.0 20 --existing --tree PARENT  against  ... --existing."""
 import ctypes
 import os
@@ -58,6 +61,7 @@ def region_keys(np, ctx, sites, chrom, K):
 def main():
     argv = sys.argv[1:]
     existing = "--existing" in argv
+    only_list = "--list" in argv
     search_ms = 2.4
     skip = set()
     for flag in ("--tree", "--search-ms"):
@@ -99,7 +103,7 @@ def main():
                                 out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64))))
         return out[:len(keys)]
 
-    model = None if existing else C.ScoreModel.uniform(L, mismatch=39322).to_c()
+    model = C.ScoreModel.uniform(L, mismatch=39322).to_c()
 
     def scored(keys, M, chrom=-1, start=0, end=0, host=False):
         out = np.zeros((max(1, len(keys)), M + 1), dtype=np.uint64)
@@ -108,6 +112,19 @@ def main():
         C._lib.check(ctx._h, fn(ctx._h, ctypes.byref(g), M, ctypes.byref(model), chrom, start, end, keys.ctypes.data_as(ctypes.c_char_p), len(keys),
                                 out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), words.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64))))
         return out[:len(keys)], words[:len(keys)]
+
+    def listed(keys, M, chrom=-1, start=0, end=0, host=False, limit=1000):
+        """(near, offsets, the records' bytes when asked for the host comparison else None, the number of records)"""
+        out = np.zeros((max(1, len(keys)), M + 1), dtype=np.uint64)
+        offsets = np.zeros(len(keys) + 1, dtype=np.uint64)
+        hits, n = ctypes.POINTER(C._lib.NearHitT)(), ctypes.c_uint64()
+        fn = lib.calitas_list_near_host if host else lib.calitas_list_near
+        C._lib.check(ctx._h, fn(ctx._h, ctypes.byref(g), M, ctypes.byref(model), chrom, start, end, keys.ctypes.data_as(ctypes.c_char_p), len(keys), limit,
+                                out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), offsets.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), ctypes.byref(hits),
+                                ctypes.byref(n)))
+        data = ctypes.string_at(hits, n.value * 32) if chrom >= 0 else None
+        lib.calitas_free(hits)
+        return out[:len(keys)], offsets, data, n.value
 
     calls = {"count plain": lambda: ctx.count_sites(n20)}
     info = {"count plain": "%d sites" % total}
@@ -119,7 +136,7 @@ def main():
         r0 = max(0, r1 - size)
         sites = ctx.find_sites(n20, chrom=big, start=r0, end=r1)
         for K, Ms in ((20, (1, 2, 3)), (12, (2,))):
-            if existing and K != 20:
+            if (existing or only_list) and K != 20:
                 continue
             keys = region_keys(np, ctx, sites, big, K)
             tag = label if K == 20 else "%s K=%d" % (label, K)
@@ -145,7 +162,7 @@ def main():
                     calls[name] = lambda keys=keys, K=K, M=M: near(keys, K, M)
                 else:
                     print("%-22s scale %g: one call %.1f ms | %s" % (name, scale, first[name] * 1e3, info[name]), flush=True)
-                if existing or K != L:
+                if K != L:
                     continue
                 sname = "scored %s M=%d" % (tag, M)
                 t0 = time.perf_counter()
@@ -153,7 +170,7 @@ def main():
                 first[sname] = time.perf_counter() - t0
                 print("%-22s first call %.3f s" % (sname, first[sname]), flush=True)
                 assert rows.tobytes() == got.tobytes(), "the scored call's counts are not count_near's"
-                if size == 10_000:
+                if size == 10_000 and not existing:
                     a, b = scored(keys, M, big, r0, r1), scored(keys, M, big, r0, r1, host=True)
                     assert a[0].tobytes() == b[0].tobytes() and a[1].tobytes() == b[1].tobytes(), "the scored kernel and the host twin differ"
                 info[sname] = "%d queries, %d with a scored copy, largest sum %.3f" % (len(keys), int((words[:, 0] > 0).sum()), int(words[:, 0].max()) / 2.0 ** 32)
@@ -161,8 +178,26 @@ def main():
                     calls[sname] = lambda keys=keys, M=M: scored(keys, M)
                 else:
                     print("%-22s scale %g: one call %.1f ms | %s" % (sname, scale, first[sname] * 1e3, info[sname]), flush=True)
+                if existing:
+                    continue
+                lname = "listed %s M=%d" % (tag, M)
+                t0 = time.perf_counter()
+                rows, offsets, _, n_records = listed(keys, M)
+                first[lname] = time.perf_counter() - t0
+                print("%-22s first call %.3f s" % (lname, first[lname]), flush=True)
+                assert rows.tobytes() == got.tobytes() and int(offsets[-1]) == n_records, "the listing's counts are not count_near's"
+                over = rows.sum(axis=1) > 1000
+                assert n_records == int(rows.sum(axis=1)[~over].sum()), "the records are not as many as the listed queries' counts"
+                if size == 10_000:
+                    a, b = listed(keys, M, big, r0, r1), listed(keys, M, big, r0, r1, host=True)
+                    assert a[0].tobytes() == b[0].tobytes() and a[1].tobytes() == b[1].tobytes() and a[2] == b[2], "the listing kernels and the host twin differ"
+                info[lname] = "%d queries, %d over the limit of 1000, %d records (%.1f MB)" % (len(keys), int(over.sum()), n_records, n_records * 32 / 1e6)
+                if first[lname] <= ONCE_OVER_S:
+                    calls[lname] = lambda keys=keys, M=M: listed(keys, M)
+                else:
+                    print("%-22s scale %g: one call %.1f ms | %s" % (lname, scale, first[lname] * 1e3, info[lname]), flush=True)
     if not existing:
-        print("checked: column 0 against the copies count; the scored calls' counts against count_near; the 10-kb sets over their own region against the host twin", flush=True)
+        print("checked: column 0 against the copies count; the scored and the listing calls' counts against count_near; the records against the counts; the 10-kb sets over their own region against the host twin", flush=True)
 
     res = {k: [] for k in calls}
     for r in range(rounds + 2):                                 # (two rounds of warm-up: buffers sized, clocks up)
