@@ -146,6 +146,9 @@ class Alignment:
         return a
 
 
+_KeyCall = collections.namedtuple("_KeyCall", ("pattern", "K", "M", "text", "n", "row", "index", "start", "end"))
+
+
 class Context:
     """One GPU (device >= 0) or a host-only context (device = -1) holding a packed reference."""
 
@@ -504,6 +507,34 @@ class Context:
             index = int(chrom)
         return pattern, index, int(start), 0 if end is None else int(end)
 
+    def _key_call(self, pattern, queries, key_length, chrom, start, end, max_mismatches=0):
+        """What count_copies, count_near, score_near and list_near begin with, as a _KeyCall: the pattern as a Guide, K (key_length
+        None: the whole protospacer), M, the queries as one byte per letter (text) and their number n, the width of a row of counts,
+        the region's contig index, start and end."""
+        pattern, index, start, end = self._site_region(pattern, chrom, start, end)
+        queries = [q.decode() if isinstance(q, bytes) else str(q) for q in queries]
+        K = pattern.protospacer_length if key_length is None else int(key_length)
+        M = int(max_mismatches)
+        for i, q in enumerate(queries):
+            if len(q) != K:
+                raise ValueError("queries[%d] has %d letters, the key has %d" % (i, len(q), K))
+        # (latin-1 keeps one byte per letter whatever the letter: the library names a bad one by its query's index)
+        text = "".join(queries).encode("latin-1", "replace")
+        row = min(max(M, 0), 3) + 1                   # (an M outside 0 .. 3 is the library's to refuse)
+        return _KeyCall(pattern, K, M, text, len(queries), row, index, start, end)
+
+    @staticmethod
+    def _take_records(out, n, ctype, dtype):
+        """A block of n records the library allocated, as a numpy structured array of its own; the block is freed."""
+        import numpy as np
+        try:
+            if n == 0:
+                return np.zeros(0, dtype=dtype)
+            block = (ctypes.c_char * (n * ctypes.sizeof(ctype))).from_address(ctypes.addressof(out.contents))
+            return np.frombuffer(block, dtype=dtype).copy()
+        finally:
+            lib.calitas_free(out)
+
     def find_sites(self, pattern, chrom=None, start=0, end=None, host=False, filter=None):
         """calitas_find_sites: every place of the region where a guide of the IUPAC `pattern` (a Guide or its `-i` string, e.g.
         "NNNNNNNNNNNNNNNNNNNNnrg"; aux PAMs through Guide(..., aux)) can be cut out, as a numpy structured array with the fields of
@@ -511,7 +542,6 @@ class Context:
         name, an index or None (every contig); [start, end) in 0-based contig coordinates, end None: the contig's end.  host=True: the
         host twin (calitas_find_sites_host), which also works on a host-only context.  filter: a SiteFilter -- only the sites whose
         protospacer passes it (calitas_find_sites_filtered, on the device inside the same kernel); None: the unfiltered entry points."""
-        import numpy as np
         pattern, index, start, end = self._site_region(pattern, chrom, start, end)
         g = pattern.to_c()
         out, n = ctypes.POINTER(SiteT)(), ctypes.c_uint64()
@@ -523,13 +553,7 @@ class Context:
             fn = lib.calitas_find_sites_filtered_host if host else lib.calitas_find_sites_filtered
             rc = fn(self._h, ctypes.byref(g), ctypes.byref(f), index, start, end, ctypes.byref(out), ctypes.byref(n))
         _lib.check(self._h, rc)
-        try:
-            if n.value == 0:
-                return np.zeros(0, dtype=SITE_DTYPE)
-            block = (ctypes.c_char * (n.value * ctypes.sizeof(SiteT))).from_address(ctypes.addressof(out.contents))
-            return np.frombuffer(block, dtype=SITE_DTYPE).copy()
-        finally:
-            lib.calitas_free(out)
+        return self._take_records(out, n.value, SiteT, SITE_DTYPE)
 
     def count_sites(self, pattern, chrom=None, start=0, end=None, filter=None):
         """calitas_count_sites: (total, per_contig_strand) -- the number of sites find_sites would list and a numpy uint64 array
@@ -557,21 +581,14 @@ class Context:
         A guide cut from the reference counts itself.  host=True: the host twin (calitas_count_copies_host), also on a host-only
         context."""
         import numpy as np
-        pattern, index, start, end = self._site_region(pattern, chrom, start, end)
-        queries = [q.decode() if isinstance(q, bytes) else str(q) for q in queries]
-        K = pattern.protospacer_length if key_length is None else int(key_length)
-        for i, q in enumerate(queries):
-            if len(q) != K:
-                raise ValueError("queries[%d] has %d letters, the key has %d" % (i, len(q), K))
-        g = pattern.to_c()
-        out = np.zeros(max(1, len(queries)), dtype=np.uint64)
-        # (latin-1 keeps one byte per letter whatever the letter: the library names a bad one by its query's index)
-        text = "".join(queries).encode("latin-1", "replace")
+        c = self._key_call(pattern, queries, key_length, chrom, start, end)
+        g = c.pattern.to_c()
+        out = np.zeros(max(1, c.n), dtype=np.uint64)
         fn = lib.calitas_count_copies_host if host else lib.calitas_count_copies
-        rc = fn(self._h, ctypes.byref(g), 0 if key_length is None else K, index, start, end, text, len(queries),
+        rc = fn(self._h, ctypes.byref(g), 0 if key_length is None else c.K, c.index, c.start, c.end, c.text, c.n,
                 out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)))
         _lib.check(self._h, rc)
-        return out[:len(queries)]
+        return out[:c.n]
 
     def count_near(self, pattern, queries, max_mismatches, key_length=None, chrom=None, start=0, end=None, host=False):
         """calitas_count_near: per query the number of sites of `pattern` (as count_sites counts them, unfiltered) whose key differs from
@@ -580,46 +597,30 @@ class Context:
         Hamming count over the key next to a PAM that matches the pattern: no gaps, no PAM mismatches.  host=True: the host twin
         (calitas_count_near_host; sites x queries comparisons), also on a host-only context."""
         import numpy as np
-        pattern, index, start, end = self._site_region(pattern, chrom, start, end)
-        queries = [q.decode() if isinstance(q, bytes) else str(q) for q in queries]
-        K = pattern.protospacer_length if key_length is None else int(key_length)
-        M = int(max_mismatches)
-        for i, q in enumerate(queries):
-            if len(q) != K:
-                raise ValueError("queries[%d] has %d letters, the key has %d" % (i, len(q), K))
-        g = pattern.to_c()
-        row = min(max(M, 0), 3) + 1                   # (an M outside 0 .. 3 is the library's to refuse)
-        out = np.zeros((max(1, len(queries)), row), dtype=np.uint64)
-        text = "".join(queries).encode("latin-1", "replace")
+        c = self._key_call(pattern, queries, key_length, chrom, start, end, max_mismatches)
+        g = c.pattern.to_c()
+        out = np.zeros((max(1, c.n), c.row), dtype=np.uint64)
         fn = lib.calitas_count_near_host if host else lib.calitas_count_near
-        rc = fn(self._h, ctypes.byref(g), 0 if key_length is None else K, M, index, start, end, text, len(queries),
+        rc = fn(self._h, ctypes.byref(g), 0 if key_length is None else c.K, c.M, c.index, c.start, c.end, c.text, c.n,
                 out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)))
         _lib.check(self._h, rc)
-        return out[:len(queries)]
+        return out[:c.n]
 
     def score_near(self, pattern, queries, max_mismatches, model, chrom=None, start=0, end=None, host=False):
         """calitas_score_near: count_near over the whole protospacer, and per query the sum and the maximum of its near copies' scores
         under `model` (a ScoreModel of the protospacer's length; near_score is the contract on one pair) -- a NearScores.  Sites at
         d = 0 are counted, not scored.  host=True: the host twin (calitas_score_near_host), also on a host-only context."""
         import numpy as np
-        pattern, index, start, end = self._site_region(pattern, chrom, start, end)
-        queries = [q.decode() if isinstance(q, bytes) else str(q) for q in queries]
-        L = pattern.protospacer_length
-        M = int(max_mismatches)
-        for i, q in enumerate(queries):
-            if len(q) != L:
-                raise ValueError("queries[%d] has %d letters, the key has %d" % (i, len(q), L))
-        g = pattern.to_c()
+        c = self._key_call(pattern, queries, None, chrom, start, end, max_mismatches)
+        g = c.pattern.to_c()
         m = model.to_c() if model is not None else None
-        row = min(max(M, 0), 3) + 1                   # (an M outside 0 .. 3 is the library's to refuse)
-        near = np.zeros((max(1, len(queries)), row), dtype=np.uint64)
-        words = np.zeros((max(1, len(queries)), 2), dtype=np.uint64)
-        text = "".join(queries).encode("latin-1", "replace")
+        n = c.n
+        near = np.zeros((max(1, n), c.row), dtype=np.uint64)
+        words = np.zeros((max(1, n), 2), dtype=np.uint64)
         fn = lib.calitas_score_near_host if host else lib.calitas_score_near
-        rc = fn(self._h, ctypes.byref(g), M, ctypes.byref(m) if m is not None else None, index, start, end, text, len(queries),
+        rc = fn(self._h, ctypes.byref(g), c.M, ctypes.byref(m) if m is not None else None, c.index, c.start, c.end, c.text, n,
                 near.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), words.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)))
         _lib.check(self._h, rc)
-        n = len(queries)
         return NearScores(near[:n], words[:n, 0].copy(), words[:n, 1].copy())
 
     def list_near(self, pattern, queries, max_mismatches, model=None, limit=1000, chrom=None, start=0, end=None, host=False):
@@ -628,39 +629,24 @@ class Context:
         query whose counts sum to more than `limit` (1 .. 4096) lists nothing.  near_hits_of is the contract on one query.  host=True:
         the host twin (calitas_list_near_host), also on a host-only context."""
         import numpy as np
-        pattern, index, start, end = self._site_region(pattern, chrom, start, end)
-        queries = [q.decode() if isinstance(q, bytes) else str(q) for q in queries]
-        L = pattern.protospacer_length
-        M = int(max_mismatches)
-        for i, q in enumerate(queries):
-            if len(q) != L:
-                raise ValueError("queries[%d] has %d letters, the key has %d" % (i, len(q), L))
+        c = self._key_call(pattern, queries, None, chrom, start, end, max_mismatches)
         limit = int(limit)
         if not 0 <= limit < 1 << 32:
             raise ValueError("limit is 1 .. %d, not %d" % (_lib.NEAR_LIST_MAX, limit))
-        g = pattern.to_c()
+        g = c.pattern.to_c()
         m = model.to_c() if model is not None else None
-        row = min(max(M, 0), 3) + 1                   # (an M outside 0 .. 3 is the library's to refuse)
-        n = len(queries)
-        near = np.zeros((max(1, n), row), dtype=np.uint64)
+        n = c.n
+        near = np.zeros((max(1, n), c.row), dtype=np.uint64)
         offsets = np.zeros(n + 1, dtype=np.uint64)
-        text = "".join(queries).encode("latin-1", "replace")
         out = ctypes.POINTER(_lib.NearHitT)()
         n_hits = ctypes.c_uint64()
         fn = lib.calitas_list_near_host if host else lib.calitas_list_near
-        rc = fn(self._h, ctypes.byref(g), M, ctypes.byref(m) if m is not None else None, index, start, end, text, n, limit,
+        rc = fn(self._h, ctypes.byref(g), c.M, ctypes.byref(m) if m is not None else None, c.index, c.start, c.end, c.text, n, limit,
                 near.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), offsets.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), ctypes.byref(out),
                 ctypes.byref(n_hits))
         _lib.check(self._h, rc)
-        try:
-            if n_hits.value == 0:
-                hits = np.zeros(0, dtype=NEAR_HIT_DTYPE)
-            else:
-                block = (ctypes.c_char * (n_hits.value * ctypes.sizeof(_lib.NearHitT))).from_address(ctypes.addressof(out.contents))
-                hits = np.frombuffer(block, dtype=NEAR_HIT_DTYPE).copy()
-        finally:
-            lib.calitas_free(out)
-        return NearList(near[:n], offsets, hits, limit, L)
+        hits = self._take_records(out, n_hits.value, _lib.NearHitT, NEAR_HIT_DTYPE)
+        return NearList(near[:n], offsets, hits, limit, c.pattern.protospacer_length)
 
     @staticmethod
     def _scores_of(c):

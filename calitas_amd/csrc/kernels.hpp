@@ -138,6 +138,26 @@ struct SiteRecord {                // = calitas_site_t
   int8_t strand, pam_index;
   uint8_t pam_len, proto_len;
 };
+// The one argument block of every sites_kernel launch.  The fields up to `end` mean the same in every mode; the rest are reused, so
+// that the block stays the size it was however many modes there are.  What each mode reads there ("-": nothing):
+//   field                     | find pass 1        | find pass 2       | copies          | near / near score       | near list (pass 2)
+//   wg_count                  | sites per segment  | -                 | -               | -                       | cursors (a)
+//   totals, 0 at launch       | per (contig, strand)| -                | -               | -                       | -
+//   wg_offset                 | -                  | scan of wg_count  | -               | -                       | [k]: first record of key k's stretch
+//   out, out_capacity         | -                  | SiteRecords       | -               | -                       | NearHits, all stretches (b)
+//   keys / near_offsets       | -                  | -                 | slot table (c)  | bucket tables (d)       | as near score
+//   key_index / near_members  | -                  | -                 | index per slot  | members (e)             | as near
+//   key_counts, 0 at launch   | -                  | -                 | [k]: key k's sites, [n_keys]: the error flag | n_keys rows (f) | -
+//   table_mask, table_shift   | -                  | -                 | a key's first slot is (key * COPIES_HASH) >> table_shift
+//    / near_m, near_w         | -                  | -                 | -               | M, 0 .. NEAR_MAX_M; bases per piece, 1 .. NEAR_MAX_W: piece p is positions [p w, (p + 1) w)
+//   n_keys, key_len, key_first| -                  | -                 | the distinct keys; K, 1 .. proto_len; 1: the guide's first K bases (a 5' PAM), 0: its last K
+//   ones_index                | -                  | -                 | the index of the key COPIES_EMPTY itself (all T at K = 32), COPIES_NONE: no query | - | -
+// (a) [2 k]: key k's cursor, 0 at launch; [2 k + 1]: its stretch's length or NEAR_LIST_SKIP; [2 n_keys]: the error flag.  (b) the field's
+//     type is the site listing's.  (c) open addressing, table_mask + 1 slots (a power of two, at most half taken), COPIES_EMPTY: free.
+// (d) near_m + 1 tables of 4^near_w + 1 offsets, one behind the other: the members of piece p's bucket b are near_members[o[b] .. o[b + 1]),
+//     o = near_offsets + p (4^near_w + 1); near score and near list: the model's packed table behind them (near_model_offset).
+// (e) {the key's low plane, its high plane, its index among the distinct keys, 0}: every key once per piece.  (f) near: near_m + 1
+//     counters; near score: near_m + 3, the counters, the sum, the maximum.  Copies and near never run in one launch: they share fields.
 struct SitesArgs {
   const uint2* planes;
   const uint32_t* mask;
@@ -151,36 +171,31 @@ struct SitesArgs {
   uint32_t tile_words;             // 32-base words per scan tile, a multiple of SITES_BLOCK_WORDS: a segment never spans two tiles
   int32_t chrom_index;
   uint64_t start, end;             // the region, in contig coordinates; end == 0: the contig's end
-  uint32_t* wg_count;              // pass 1: sites per segment
-  unsigned long long* totals;      // pass 1: sites per (contig, strand), zero at launch
-  const uint64_t* wg_offset;       // pass 2: exclusive scan of wg_count
-  SiteRecord* out;                 // pass 2
+  uint32_t* wg_count;              // (from here on: the table above)
+  unsigned long long* totals;
+  const uint64_t* wg_offset;
+  SiteRecord* out;
   uint64_t out_capacity;
-  // copies_kernel only (calitas_count_copies): the table of the caller's distinct query keys
-  // (the near kernel's tables take the places of the copies table's: the two kernels never run in one launch, and the argument block
-  // every sites_kernel is launched with stays the size it was)
   union {
-    const uint64_t* keys;          // open addressing, table_mask + 1 slots (a power of two, at most half of them taken), COPIES_EMPTY: free
-    const uint32_t* near_offsets;  // near kernel: near_m + 1 bucket tables of 4^near_w + 1 offsets each, one behind the other: the members of
-  };                               // piece p's bucket b are near_members[o[b] .. o[b + 1]), o = near_offsets + p (4^near_w + 1)
+    const uint64_t* keys;
+    const uint32_t* near_offsets;
+  };
   union {
-    const uint32_t* key_index;     // per taken slot: the key's index among the distinct keys
-    const uint4* near_members;     // near kernel: {the key's low plane, its high plane, its index among the distinct keys, 0}: every key
-  };                               // once per piece
-  unsigned long long* key_counts;  // per distinct key: its sites, zero at launch; [n_keys]: the call's error flag
-                                   // near kernel: n_keys rows of near_m + 1 counters, zero at launch, and no flag
-                                   // (near_m + 3 with the score: calitas_score_near, below)
+    const uint32_t* key_index;
+    const uint4* near_members;
+  };
+  unsigned long long* key_counts;
   union {
-    struct { uint32_t table_mask, table_shift; };   // a key's first slot is (key * COPIES_HASH) >> table_shift
-    struct {                       // near kernel (calitas_count_near; it reads n_keys, key_len and key_first as well)
-      int32_t near_m;              // M, 0 .. NEAR_MAX_M
-      int32_t near_w;              // bases per piece, 1 .. NEAR_MAX_W: piece p is the key's positions [p w, (p + 1) w)
+    struct { uint32_t table_mask, table_shift; };
+    struct {
+      int32_t near_m;
+      int32_t near_w;
     };
   };
   uint32_t n_keys;
-  uint32_t ones_index;             // the index of the key COPIES_EMPTY itself (all T at K = 32), COPIES_NONE when it is no query
-  int32_t key_len;                 // K, 1 .. proto_len
-  int32_t key_first;               // 1: the guide's first K bases (a 5' PAM), 0: its last K
+  uint32_t ones_index;
+  int32_t key_len;
+  int32_t key_first;
 };
 // filtered: a.pat's SiteTables holds a filter, and the match vectors are ANDed with it in both passes
 hipError_t launch_sites_count(const SitesArgs& a, bool filtered, hipStream_t stream);
@@ -233,12 +248,9 @@ CAL_HD inline size_t near_model_offset(int M, int w) { return (size_t)(M + 1) * 
 hipError_t launch_sites_near_score(const SitesArgs& a, hipStream_t stream);
 
 // calitas_list_near: the near kernel's pass run a second time (K = L, the model's table in LDS as above), every (site, query) pair
-// that counts written as a record.  The fields no KEYS_* mode reads carry the layout the host made from the first pass's counts:
-//   wg_offset[k]        the first record of distinct key k's stretch in `out`
-//   wg_count[2 k]       the key's cursor, zero at launch: a pair takes its slot with a returning 32-bit atomicAdd
-//   wg_count[2 k + 1]   the stretch's length -- the key's count of the first pass -- or NEAR_LIST_SKIP: the key lists nothing
-//   wg_count[2 n_keys]  the call's error flag, zero at launch: a slot at or beyond the length is not stored, it raises the flag
-//   out, out_capacity   NearHit records (the field's type is the site listing's), all stretches together
+// that counts written as a record.  The fields no other KEYS_* mode reads carry the layout the host made from the first pass's counts
+// (the table at SitesArgs): a pair takes its slot with a returning 32-bit atomicAdd on its key's cursor, the stretch's length is the
+// key's count of the first pass, and a slot at or beyond the length is not stored, it raises the call's flag.
 // near_order_kernel then writes every stretch in position order into a second buffer of the same layout.  Both kernels are
 // near_list.hip's: it instantiates sites.hip's template for this one ending.
 struct NearHit {                   // = calitas_near_hit_t

@@ -361,3 +361,42 @@ def test_tools_end_to_end(C, tmp_path):
             assert int(f[8]) == int(ctx.search_counts(C.Guide(f[6]), params).sum())
     finally:
         ctx.close()
+
+
+def test_site_listing_interleaved_with_key_calls(C):
+    """The site listing and the key calls share one context's pattern block and device buffers: listings and counts, filtered and
+    not, between count_copies, list_near and count_near, each held byte for byte against the same call on the host twin.  Two
+    contigs of 20 kb (more than two segments of 8192 bases each), one U inside a site's footprint."""
+    rng = random.Random(20261019)
+    seqs = ["".join(rng.choice("ACGT") for _ in range(n)) for n in (20011, 19997)]
+    seqs[0] = seqs[0][:5000] + "ACGUACGTAGG" + seqs[0][5011:]          # the '+' site at 5000 holds the U
+    pattern = C.Guide("NNNNNNNNngg")
+    keep = C.SiteFilter(gc_min=2, gc_max=6, avoid=("TTT",))
+    model = C.ScoreModel.uniform(8, mismatch=39322)
+    ctx = C.Context(0)
+    try:
+        ctx.set_reference(["chrA", "chrB"], [s.encode() for s in seqs])
+        every = ctx.find_sites(pattern, host=True)
+        kept = ctx.find_sites(pattern, host=True, filter=keep)
+        at_u = every[(every["contig_index"] == 0) & (every["protospacer_start"] == 5000) & (every["strand"] == b"+")]
+        assert len(at_u) == 1 and 0 < len(kept) < len(every)
+        plus = every[every["strand"] == b"+"]
+        keys = [seqs[s["contig_index"]][s["protospacer_start"]:s["protospacer_start"] + 8].replace("U", "T") for s in plus[::len(plus) // 38][:38]]
+        keys += ["ACGTACGT", keys[0]]
+        assert len(keys) == 40
+
+        assert ctx.find_sites(pattern, filter=keep).tobytes() == kept.tobytes()
+        assert ctx.count_copies(pattern, keys).tobytes() == ctx.count_copies(pattern, keys, host=True).tobytes()
+        assert ctx.find_sites(pattern).tobytes() == every.tobytes()
+        got, twin = ctx.list_near(pattern, keys, 1, model=model), ctx.list_near(pattern, keys, 1, model=model, host=True)
+        assert got.near.tobytes() == twin.near.tobytes() and got.offsets.tobytes() == twin.offsets.tobytes() and got.hits.tobytes() == twin.hits.tobytes()
+        assert len(got.hits) >= 40 and int(got.near[38].sum()) >= 1          # every key lists itself, the one at the U as well
+        n, table = ctx.count_sites(pattern, filter=keep)
+        want = np.zeros((2, 2), dtype=np.uint64)
+        for s in kept:
+            want[s["contig_index"], 1 if s["strand"] == b"-" else 0] += 1
+        assert n == len(kept) and table.tobytes() == want.tobytes()
+        assert ctx.find_sites(pattern, filter=keep).tobytes() == kept.tobytes()
+        assert ctx.count_near(pattern, keys, 2).tobytes() == ctx.count_near(pattern, keys, 2, host=True).tobytes()
+    finally:
+        ctx.close()
