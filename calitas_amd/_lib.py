@@ -106,8 +106,17 @@ class NearHitT(ctypes.Structure):
                 ("mismatches", ctypes.c_uint8), ("reserved", ctypes.c_uint8)]
 
 
+class ActivityModelT(ctypes.Structure):
+    _fields_ = [("protospacer_length", ctypes.c_int32), ("up", ctypes.c_int32), ("down", ctypes.c_int32), ("link", ctypes.c_int32),
+                ("intercept", ctypes.c_int32), ("single", ctypes.POINTER(ctypes.c_int32)), ("pair", ctypes.POINTER(ctypes.c_int32)),
+                ("gc", ctypes.POINTER(ctypes.c_int32))]
+
+
 TOP_MAX = 256
 NEAR_LIST_MAX = 4096
+ACTIVITY_NONE = -(1 << 31)
+ACTIVITY_MAX_FLANK = 16
+ACTIVITY_MAX_WEIGHT = 1 << 20
 assert ctypes.sizeof(NearHitT) == 32
 REGION_CLASSES_MAX = 8
 assert ctypes.sizeof(TopHitT) == 24
@@ -124,7 +133,8 @@ SYMBOLS = ["calitas_create", "calitas_destroy", "calitas_last_error", "calitas_f
            "calitas_find_sites", "calitas_count_sites", "calitas_find_sites_host",
            "calitas_find_sites_filtered", "calitas_count_sites_filtered", "calitas_find_sites_filtered_host",
            "calitas_count_copies", "calitas_count_copies_host", "calitas_count_near", "calitas_count_near_host",
-           "calitas_score_near", "calitas_score_near_host", "calitas_list_near", "calitas_list_near_host"]
+           "calitas_score_near", "calitas_score_near_host", "calitas_list_near", "calitas_list_near_host",
+           "calitas_find_sites_scored", "calitas_find_sites_scored_host"]
 
 if not os.path.exists(LIB_PATH):
     raise ImportError("%s is missing: build it with `make -C calitas_amd/csrc` (hipcc, gfx950). "
@@ -208,6 +218,11 @@ if hasattr(lib, "calitas_list_near"):      # (an older build behind CALITAS_LIB_
                                       ctypes.c_uint64, ctypes.c_char_p, ctypes.c_uint64, ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint64),
                                       ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.POINTER(NearHitT)), ctypes.POINTER(ctypes.c_uint64)]
     lib.calitas_list_near_host.argtypes = lib.calitas_list_near.argtypes
+if hasattr(lib, "calitas_find_sites_scored"):      # (an older build behind CALITAS_LIB_PATH, for A/B runs, does not have it)
+    lib.calitas_find_sites_scored.argtypes = [ctypes.c_void_p, ctypes.POINTER(GuideT), ctypes.POINTER(SiteFilterT), ctypes.POINTER(ActivityModelT), ctypes.c_int32,
+                                              ctypes.c_int32, ctypes.c_uint64, ctypes.c_uint64, ctypes.POINTER(ctypes.POINTER(SiteT)),
+                                              ctypes.POINTER(ctypes.POINTER(ctypes.c_int32)), ctypes.POINTER(ctypes.c_uint64)]
+    lib.calitas_find_sites_scored_host.argtypes = lib.calitas_find_sites_scored.argtypes
 lib.calitas_search_scores.argtypes = [ctypes.c_void_p, ctypes.POINTER(GuideT), ctypes.POINTER(ParamsT), ctypes.POINTER(ScoreModelT),
                                       ctypes.POINTER(ctypes.POINTER(ScoresT))]
 lib.calitas_search_scores_batch.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.POINTER(GuideT), ctypes.POINTER(ParamsT),

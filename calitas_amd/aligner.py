@@ -648,6 +648,44 @@ class Context:
         hits = self._take_records(out, n_hits.value, _lib.NearHitT, NEAR_HIT_DTYPE)
         return NearList(near[:n], offsets, hits, limit, c.pattern.protospacer_length)
 
+    def find_sites_scored(self, pattern, model, min_score=None, filter=None, chrom=None, start=0, end=None, host=False):
+        """calitas_find_sites_scored: (sites, scores) -- the records of find_sites(pattern, filter=filter) and, in an int32 array beside
+        them, each site's on-target activity under `model` (an ActivityModel; activity_of is the contract on one context), Q16.  A site
+        whose window leaves its contig or holds a letter other than A C G T U has ACTIVITY_NONE.  min_score: a Q16 integer -- only the
+        sites that score at least that much, which drops the unscored ones too; None keeps everything.  host=True: the host twin
+        (calitas_find_sites_scored_host), also on a host-only context."""
+        import numpy as np
+        pattern, index, start, end = self._site_region(pattern, chrom, start, end)
+        floor = _lib.ACTIVITY_NONE if min_score is None else int(min_score)
+        if not -(1 << 31) <= floor < 1 << 31:
+            raise ValueError("min_score is a 32-bit Q16 integer, not %d" % floor)
+        g = pattern.to_c()
+        f = filter.to_c() if filter is not None else None
+        m = model.to_c() if model is not None else None
+        out, words, n = ctypes.POINTER(SiteT)(), ctypes.POINTER(ctypes.c_int32)(), ctypes.c_uint64()
+        fn = lib.calitas_find_sites_scored_host if host else lib.calitas_find_sites_scored
+        rc = fn(self._h, ctypes.byref(g), ctypes.byref(f) if f is not None else None, ctypes.byref(m) if m is not None else None, floor, index, start, end,
+                ctypes.byref(out), ctypes.byref(words), ctypes.byref(n))
+        _lib.check(self._h, rc)
+        try:
+            scores = np.ctypeslib.as_array(words, shape=(n.value,)).astype(np.int32) if n.value else np.zeros(0, dtype=np.int32)   # (astype copies)
+        finally:
+            lib.calitas_free(words)
+        return self._take_records(out, n.value, SiteT, SITE_DTYPE), scores
+
+    def count_sites_scored(self, pattern, model, min_score=None, filter=None, chrom=None, start=0, end=None, host=False):
+        """calitas_find_sites_scored without its blocks: the number of sites find_sites_scored would return."""
+        pattern, index, start, end = self._site_region(pattern, chrom, start, end)
+        g = pattern.to_c()
+        f = filter.to_c() if filter is not None else None
+        m = model.to_c()
+        n = ctypes.c_uint64()
+        fn = lib.calitas_find_sites_scored_host if host else lib.calitas_find_sites_scored
+        rc = fn(self._h, ctypes.byref(g), ctypes.byref(f) if f is not None else None, ctypes.byref(m), _lib.ACTIVITY_NONE if min_score is None else int(min_score),
+                index, start, end, None, None, ctypes.byref(n))
+        _lib.check(self._h, rc)
+        return n.value
+
     @staticmethod
     def _scores_of(c):
         """A calitas_scores_t as a Scores object (the table is copied)."""
@@ -1698,3 +1736,204 @@ def read_hits(path_or_text):
     lines = text.splitlines()
     header = lines[0].split("\t")
     return [dict(zip(header, ln.split("\t"))) for ln in lines[1:]]
+
+
+# ---- the on-target activity score (include/calitas_hip.h has the contract) ----
+
+ACTIVITY_NONE = _lib.ACTIVITY_NONE
+ACTIVITY_LINKS = ("identity", "logistic")
+_ACTIVITY_DECIMAL = None
+
+
+def _activity_q16(x):
+    """A decimal of an activity model file in [-16, 16] as Q16: floor(x * 65536 + 0.5) in double.  Digits with at most one point and an
+    optional sign, nothing else: what both tools read alike."""
+    import math
+    import re
+    global _ACTIVITY_DECIMAL
+    if _ACTIVITY_DECIMAL is None:
+        _ACTIVITY_DECIMAL = re.compile(r"[+-]?([0-9]+\.?[0-9]*|\.[0-9]+)", re.ASCII)
+    if not _ACTIVITY_DECIMAL.fullmatch(x) or not -16.0 <= float(x) <= 16.0:
+        raise ValueError("a weight of an activity model is a decimal in [-16, 16], not %r" % (x,))
+    return int(math.floor(float(x) * 65536.0 + 0.5))
+
+
+def _activity_int(x):
+    if not (x.isascii() and x.isdigit() and len(x) <= 4):
+        raise ValueError("%r is not a number of an activity model" % (x,))
+    return int(x)
+
+
+class ActivityModel:
+    """The weights of an on-target activity score (calitas_activity_model_t), all signed Q16 within +-16.0: for protospacers of L bases
+    with `up` bases 5' and `down` bases 3' of them as the guide reads (0 .. 16 each; the context has W = up + L + down letters),
+    single[W][4] by context position and base (A C G T), pair[W - 1][16] by position i and 4 * base(i) + base(i + 1), gc[L + 1] by the
+    protospacer's G + C count, an intercept, and link: "identity" or "logistic" -- how a tool prints the score, nothing else.  The
+    library ships no published table: read() loads any table of this additive form from a TSV with `#` comments and the lines
+
+        length<TAB>L
+        context<TAB>UP<TAB>DOWN
+        link<TAB>identity|logistic
+        intercept<TAB>x
+        single<TAB>POS<TAB>BASE<TAB>x
+        pair<TAB>POS<TAB>BASE<TAB>BASE<TAB>x
+        gc<TAB>COUNT<TAB>x
+
+    POS is 1-based in the context as the guide reads (UP + 1 is the protospacer's first base; a pair sits at its first letter's
+    position, 1 .. W - 1), COUNT runs 0 .. L, `*` stands for every index; x is a decimal in [-16, 16]; entries not given are 0, later
+    lines override earlier ones, a file without a `context` line has no flanks."""
+
+    def __init__(self, L, up, down, single, pair, gc, intercept=0, link="identity"):
+        import numpy as np
+        self.L, self.up, self.down = int(L), int(up), int(down)
+        W = self.W = self.up + self.L + self.down
+        self.single = np.ascontiguousarray(single, dtype=np.int32)
+        self.pair = np.ascontiguousarray(pair, dtype=np.int32)
+        self.gc = np.ascontiguousarray(gc, dtype=np.int32)
+        if W < 1 or self.single.shape != (W, 4) or self.pair.shape != (W - 1, 16) or self.gc.shape != (self.L + 1,):
+            raise ValueError("an activity model of W = %d letters has single (W, 4), pair (W - 1, 16) and gc (L + 1,), not %r, %r, %r"
+                             % (W, self.single.shape, self.pair.shape, self.gc.shape))
+        self.intercept = int(intercept)
+        if link not in ACTIVITY_LINKS:
+            raise ValueError("link is identity or logistic, not %r" % (link,))
+        self.link = link
+
+    @classmethod
+    def zeros(cls, L, up=0, down=0, link="identity"):
+        import numpy as np
+        W = int(up) + int(L) + int(down)
+        return cls(L, up, down, np.zeros((W, 4), np.int32), np.zeros((max(W - 1, 0), 16), np.int32), np.zeros(int(L) + 1, np.int32), 0, link)
+
+    def __eq__(self, other):
+        import numpy as np
+        return (isinstance(other, ActivityModel) and (self.L, self.up, self.down, self.intercept, self.link) ==
+                (other.L, other.up, other.down, other.intercept, other.link) and np.array_equal(self.single, other.single) and
+                np.array_equal(self.pair, other.pair) and np.array_equal(self.gc, other.gc))
+
+    __hash__ = None
+
+    def to_c(self):
+        import numpy as np
+        m = _lib.ActivityModelT()
+        m.protospacer_length, m.up, m.down, m.link, m.intercept = self.L, self.up, self.down, ACTIVITY_LINKS.index(self.link), self.intercept
+        pair = self.pair if self.pair.size else np.zeros(16, np.int32)         # (W = 1: no pair, and no NULL table either)
+        ptr = ctypes.POINTER(ctypes.c_int32)
+        m.single, m.pair, m.gc = self.single.ctypes.data_as(ptr), pair.ctypes.data_as(ptr), self.gc.ctypes.data_as(ptr)
+        m._keep = (self.single, pair, self.gc)
+        return m
+
+    @classmethod
+    def read(cls, path):
+        L, up, down, link, intercept, lines = None, 0, 0, "identity", 0, []
+        with open(path) as f:
+            for ln in f:
+                ln = ln.split("#", 1)[0].strip()
+                if not ln:
+                    continue
+                fld = ln.split("\t")
+                try:
+                    if fld[0] == "length" and len(fld) == 2:
+                        L = _activity_int(fld[1])
+                    elif fld[0] == "context" and len(fld) == 3:
+                        up, down = _activity_int(fld[1]), _activity_int(fld[2])
+                    elif fld[0] == "link" and len(fld) == 2 and fld[1] in ACTIVITY_LINKS:
+                        link = fld[1]
+                    elif fld[0] == "intercept" and len(fld) == 2:
+                        intercept = _activity_q16(fld[1])
+                    elif (fld[0], len(fld)) in (("single", 4), ("pair", 5), ("gc", 3)):
+                        lines.append(fld)
+                    else:
+                        raise ValueError("not a line of an activity model: %r" % ln)
+                except ValueError as e:
+                    raise ValueError("%s: %s" % (path, e)) from None
+        if L is None or not 1 <= L <= 32:
+            raise ValueError("%s: an activity model needs a `length` line with 1 <= L <= 32" % path)
+        if up > _lib.ACTIVITY_MAX_FLANK or down > _lib.ACTIVITY_MAX_FLANK:
+            raise ValueError("%s: the `context` of an activity model is 0 .. 16 bases on either side" % path)
+        model = cls.zeros(L, up, down, link)
+        model.intercept = intercept
+        W = model.W
+
+        def axis(word, n, names):
+            if word == "*":
+                return range(n)
+            if names is None:
+                k = _activity_int(word)
+            else:
+                k = names.find(word.upper()) if len(word) == 1 else -1
+            if not 0 <= k < n:
+                raise ValueError("%r is not a position, a count or a base of this activity model" % (word,))
+            return [k]
+        try:
+            for fld in lines:
+                v = _activity_q16(fld[-1])
+                if fld[0] == "single":
+                    for i in axis(fld[1], W + 1, None):
+                        for b in axis(fld[2], 4, _MODEL_LETTERS):
+                            if i >= 1:
+                                model.single[i - 1, b] = v
+                            elif fld[1] != "*":
+                                raise ValueError("positions of an activity model count from 1")
+                elif fld[0] == "pair":
+                    for i in axis(fld[1], W, None):
+                        for a in axis(fld[2], 4, _MODEL_LETTERS):
+                            for b in axis(fld[3], 4, _MODEL_LETTERS):
+                                if i >= 1:
+                                    model.pair[i - 1, 4 * a + b] = v
+                                elif fld[1] != "*":
+                                    raise ValueError("positions of an activity model count from 1")
+                else:
+                    for k in axis(fld[1], L + 1, None):
+                        model.gc[k] = v
+        except ValueError as e:
+            raise ValueError("%s: %s" % (path, e)) from None
+        return model
+
+    def write(self, path):
+        """The model as a file read() gives back exactly: every weight as the shortest decimal that rounds to it."""
+        def dec(q):
+            for digits in range(1, 12):
+                t = "%.*f" % (digits, q / 65536.0)
+                if _activity_q16(t) == q:
+                    return t
+            raise ValueError("weight %r is not a Q16 value within +-16.0" % (q,))
+        with open(path, "w") as f:
+            f.write("# calitas activity model: signed Q16 weights as decimals (x -> floor(x * 65536 + 0.5)); entries not given are 0\n")
+            f.write("length\t%d\ncontext\t%d\t%d\nlink\t%s\nintercept\t%s\n" % (self.L, self.up, self.down, self.link, dec(self.intercept)))
+            for i in range(self.W):
+                for b in range(4):
+                    if int(self.single[i, b]):
+                        f.write("single\t%d\t%s\t%s\n" % (i + 1, _MODEL_LETTERS[b], dec(int(self.single[i, b]))))
+            for i in range(self.W - 1):
+                for ab in range(16):
+                    if int(self.pair[i, ab]):
+                        f.write("pair\t%d\t%s\t%s\t%s\n" % (i + 1, _MODEL_LETTERS[ab >> 2], _MODEL_LETTERS[ab & 3], dec(int(self.pair[i, ab]))))
+            for k in range(self.L + 1):
+                if int(self.gc[k]):
+                    f.write("gc\t%d\t%s\n" % (k, dec(int(self.gc[k]))))
+
+
+def activity_of(context, model):
+    """The contract of calitas_find_sites_scored on one context -- W letters as the guide reads, `up` before the protospacer and `down`
+    behind it -- in plain Python integers; None when a letter is not one of A C G T U (either case)."""
+    if len(context) != model.W:
+        raise ValueError("the context has %d letters, the model's has %d" % (len(context), model.W))
+    codes = [_LETTER.get(ch, -1) for ch in context.upper().replace("U", "T")]
+    if min(codes) < 0:
+        return None
+    total = model.intercept
+    for i, c in enumerate(codes):
+        total += int(model.single[i, c])
+    for i in range(model.W - 1):
+        total += int(model.pair[i, 4 * codes[i] + codes[i + 1]])
+    return total + int(model.gc[sum(1 for c in codes[model.up:model.up + model.L] if c in (1, 2))])
+
+
+def activity_value(score_q16, model):
+    """The number a tool prints for a score: score / 65536 under link identity, 1 / (1 + exp(-score / 65536)) under logistic, in
+    double; None for ACTIVITY_NONE or None."""
+    import math
+    if score_q16 is None or int(score_q16) == ACTIVITY_NONE:
+        return None
+    x = int(score_q16) / 65536.0
+    return x if model.link == "identity" else 1.0 / (1.0 + math.exp(-x))

@@ -1302,4 +1302,27 @@ int calitas_padded_strings(const calitas_ctx* ctx, const calitas_guide_t* guide,
   return CALITAS_OK;
 }
 
+// Activity scores (sites_host.cpp, activity.hip): no reference counterpart.  The newest entry points stand last, so that everything
+// above keeps its place in the object file.
+// (the model is the implementation's to check: it comes after everything calitas_find_sites_filtered refuses)
+int calitas_find_sites_scored(calitas_ctx* ctx, const calitas_guide_t* pattern, const calitas_site_filter_t* filter, const calitas_activity_model_t* model,
+                              int32_t min_score_q16, int32_t chrom_index, uint64_t start, uint64_t end, calitas_site_t** sites, int32_t** scores,
+                              uint64_t* n_sites) {
+  if (!ctx) return CALITAS_EINVAL;
+  if (!pattern || !n_sites || (sites == nullptr) != (scores == nullptr)) return fail(ctx, CALITAS_EINVAL, "NULL argument");
+  *n_sites = 0;
+  if (sites) { *sites = nullptr; *scores = nullptr; }
+  return calitas_find_sites_scored_impl(ctx, pattern, filter, model, min_score_q16, chrom_index, start, end, sites, scores, n_sites);
+}
+
+int calitas_find_sites_scored_host(const calitas_ctx* ctx, const calitas_guide_t* pattern, const calitas_site_filter_t* filter,
+                                   const calitas_activity_model_t* model, int32_t min_score_q16, int32_t chrom_index, uint64_t start, uint64_t end,
+                                   calitas_site_t** sites, int32_t** scores, uint64_t* n_sites) {
+  if (!ctx) return CALITAS_EINVAL;
+  if (!pattern || !n_sites || (sites == nullptr) != (scores == nullptr)) return fail(const_cast<calitas_ctx*>(ctx), CALITAS_EINVAL, "NULL argument");
+  *n_sites = 0;
+  if (sites) { *sites = nullptr; *scores = nullptr; }
+  return calitas_find_sites_scored_host_impl(ctx, pattern, filter, model, min_score_q16, chrom_index, start, end, sites, scores, n_sites);
+}
+
 }  // extern "C"

@@ -1,4 +1,4 @@
-// kernels.hpp -- launch interface of scan_columns.hip, scan_rows.hip, align.hip, trace.hip, setup.hip and sites.hip (device pointers only).
+// kernels.hpp -- launch interface of scan_columns.hip, scan_rows.hip, align.hip, trace.hip, setup.hip, sites.hip and activity.hip (device pointers only).
 #pragma once
 #include "mailbox.hpp"
 #include <hip/hip_runtime_api.h>
@@ -269,5 +269,38 @@ hipError_t launch_sites_near_list(const SitesArgs& a, hipStream_t stream);
 hipError_t launch_near_order(const NearHit* in, NearHit* out, const uint64_t* base, uint32_t* cursors, const uint32_t* keys, uint32_t n_short, uint32_t n_long,
                              uint32_t flag_index, hipStream_t stream);
 static_assert(sizeof(SitesArgs) == 176, "a longer argument block costs every sites_kernel launch (DESIGN 4.15)");
+
+// activity.hip: calitas_find_sites_scored.  The records launch_sites_write left on the device, one lane per record: the window of
+// W = up + L + down bases around the protospacer, from the planes, under the model's tables.  The host folds `single` into the pair
+// table -- integer sums, so exactly -- and lays everything out as one block of words that a workgroup copies to LDS:
+//   [0, 16 (W - 1))   pair'[i][4 a + b] = pair[i][4 a + b] + single[i][a]
+//   then 4            single[W - 1][.], the last position's
+//   then L + 1        gc[.]
+//   then 1            intercept
+constexpr int ACTIVITY_THREADS = 256;
+constexpr int ACTIVITY_MAX_W = 64;
+constexpr int ACTIVITY_TABLE_MAX_WORDS = 16 * (ACTIVITY_MAX_W - 1) + 4 + (MAX_L + 1) + 1;
+constexpr int32_t ACTIVITY_NONE = INT32_MIN;             // = CALITAS_ACTIVITY_NONE
+constexpr int32_t ACTIVITY_HOST_DECIDES = INT32_MIN + 1; // the window holds an exception base (N, IUPAC code, U): scored on the host, always kept
+CAL_HD inline uint32_t activity_table_words(int L, int W) { return (uint32_t)(16 * (W - 1) + 4 + (L + 1) + 1); }
+struct ActivityArgs {
+  const uint2* planes;
+  const uint32_t* mask;
+  const ContigInfo* contigs;
+  const int32_t* table;            // device memory: activity_table_words(L, W) words
+  const SiteRecord* recs;          // n records, 16-byte aligned
+  int32_t* scores;                 // n
+  uint32_t* wg_kept;               // per workgroup: records kept (score >= min_score, or the host decides); nullptr: no threshold
+  uint64_t n;
+  uint64_t n_words;                // 32-base words of the packed space
+  int32_t n_contigs;
+  int32_t L, up, down;
+  int32_t min_score;
+};
+hipError_t launch_activity_score(const ActivityArgs& a, hipStream_t stream);
+// The kept records and their scores, in order: record i of workgroup g goes to wg_offset[g] + its rank among g's kept records.
+hipError_t launch_activity_compact(const SiteRecord* recs, const int32_t* scores, uint64_t n, int32_t min_score, const uint64_t* wg_offset,
+                                   SiteRecord* out_recs, int32_t* out_scores, uint64_t out_capacity, hipStream_t stream);
+inline uint32_t activity_blocks(uint64_t n) { return (uint32_t)((n + ACTIVITY_THREADS - 1) / ACTIVITY_THREADS); }
 
 }  // namespace calitas

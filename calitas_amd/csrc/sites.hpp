@@ -58,3 +58,10 @@ int calitas_list_near_host_impl(const calitas_ctx* ctx, const calitas_guide_t* p
 int calitas_list_near_impl(calitas_ctx* ctx, const calitas_guide_t* pattern, int32_t max_mismatches, const calitas_score_model_t* model, int32_t chrom_index,
                            uint64_t start, uint64_t end, const char* queries, uint64_t n_queries, uint32_t limit, uint64_t* near, uint64_t* offsets,
                            calitas_near_hit_t** hits, uint64_t* n_hits);
+// the records of calitas_find_sites_filtered whose activity score under the model is >= min_score, and the scores; CALITAS_ACTIVITY_NONE keeps all
+int calitas_find_sites_scored_host_impl(const calitas_ctx* ctx, const calitas_guide_t* pattern, const calitas_site_filter_t* filter,
+                                        const calitas_activity_model_t* model, int32_t min_score, int32_t chrom_index, uint64_t start, uint64_t end,
+                                        calitas_site_t** sites, int32_t** scores, uint64_t* n_sites);
+int calitas_find_sites_scored_impl(calitas_ctx* ctx, const calitas_guide_t* pattern, const calitas_site_filter_t* filter, const calitas_activity_model_t* model,
+                                   int32_t min_score, int32_t chrom_index, uint64_t start, uint64_t end, calitas_site_t** sites, int32_t** scores,
+                                   uint64_t* n_sites);

@@ -6,7 +6,9 @@
 // offsets and rows of M + 3 counters, the host twin (the score letter by letter from the caller's table) and the correction of sums and
 // maxima around a U.  calitas_list_near / calitas_list_near_host: the near driver for the counts, the layout of a stretch of records per
 // distinct query, the pass's second run and the order kernel (near_list.hip), the patch of the stretches beside a U, and the host twin
-// (every pair a record, every stretch through std::sort).  No reference counterpart.
+// (every pair a record, every stretch through std::sort).  calitas_find_sites_scored / calitas_find_sites_scored_host: the model's checks
+// and its folded table, the per-site score base by base, the host twin, and the driver of activity.hip's kernels behind the site
+// kernel's two passes with the correction of records and scores beside a U.  No reference counterpart.
 #include "sites.hpp"
 #include "tuning.hpp"
 
@@ -217,6 +219,17 @@ struct SitesWork {
   NearHit* d_list_in = nullptr;
   NearHit* d_list_out = nullptr;
   size_t list_cap = 0;
+  // calitas_find_sites_scored: the model's folded table, a score per record of d_out, the workgroups' kept counts and their scan, and
+  // the kept records and scores in order
+  int32_t* d_act_table = nullptr;
+  int32_t* d_act_scores = nullptr;
+  size_t act_scores_cap = 0;
+  uint32_t* d_act_count = nullptr;
+  uint64_t* d_act_off = nullptr;
+  size_t act_blocks_cap = 0;
+  SiteRecord* d_act_out = nullptr;
+  int32_t* d_act_out_scores = nullptr;
+  size_t act_out_cap = 0;
   // the U / u runs of the resident reference (a U is a plain base to a site and an exception base to the kernels)
   uint64_t u_serial = ~0ull;
   std::vector<Run> u_runs;
@@ -228,6 +241,7 @@ void sites_destroy(SitesWork* w) {
   (void)hipFree(w->d_keys); (void)hipFree(w->d_key_index); (void)hipFree(w->d_key_counts);
   (void)hipFree(w->d_near_offsets); (void)hipFree(w->d_near_members);
   (void)hipFree(w->d_list_base); (void)hipFree(w->d_list_cursors); (void)hipFree(w->d_list_order); (void)hipFree(w->d_list_in); (void)hipFree(w->d_list_out);
+  (void)hipFree(w->d_act_table); (void)hipFree(w->d_act_scores); (void)hipFree(w->d_act_count); (void)hipFree(w->d_act_off); (void)hipFree(w->d_act_out); (void)hipFree(w->d_act_out_scores);
   delete w;
 }
 
@@ -1102,4 +1116,285 @@ int calitas_list_near_impl(calitas_ctx* ctx, const calitas_guide_t* pattern, int
     }
   }
   return near_list_block(ctx, call, counts, spans, n_queries, near, offsets, hits, n_hits);
+}
+
+// ---- calitas_find_sites_scored: every site's on-target activity under a linear model of its sequence context ----
+
+namespace {
+
+struct ActivityCall {
+  SiteCall site;
+  const calitas_activity_model_t* model = nullptr;
+  int L = 0, W = 0;
+  int32_t min_score = CALITAS_ACTIVITY_NONE;
+  bool threshold = false;            // min_score != CALITAS_ACTIVITY_NONE: sites below it, the unscored ones among them, are dropped
+};
+
+// checked in this order: what calitas_find_sites_filtered checks (plan_sites), then the model, field by field
+int plan_activity(calitas_ctx* c, const calitas_guide_t* pattern, const calitas_site_filter_t* filter, const calitas_activity_model_t* model,
+                  int32_t min_score, int32_t chrom_index, uint64_t start, uint64_t end, ActivityCall& call) {
+  static_assert(CALITAS_ACTIVITY_MAX_FLANK + MAX_L + CALITAS_ACTIVITY_MAX_FLANK == ACTIVITY_MAX_W, "the kernel's three words hold the widest window");
+  static_assert(ACTIVITY_NONE == CALITAS_ACTIVITY_NONE, "the kernel stores the contract's value");
+  if (int rc = plan_sites(c, pattern, filter, chrom_index, start, end, call.site)) return rc;
+  const int L = call.site.tab.pat.proto_len;
+  if (!model) return calitas_fail(c, CALITAS_EINVAL, "activity model: model is NULL");
+  if (!model->single) return calitas_fail(c, CALITAS_EINVAL, "activity model: single is NULL");
+  if (!model->pair) return calitas_fail(c, CALITAS_EINVAL, "activity model: pair is NULL");
+  if (!model->gc) return calitas_fail(c, CALITAS_EINVAL, "activity model: gc is NULL");
+  if (model->protospacer_length != L)
+    return calitas_fail(c, CALITAS_EINVAL, "activity model: protospacer_length is " + std::to_string(model->protospacer_length) + ", the pattern's protospacer has " + std::to_string(L) + " bases");
+  if (model->up < 0 || model->up > CALITAS_ACTIVITY_MAX_FLANK) return calitas_fail(c, CALITAS_EINVAL, "activity model: up is " + std::to_string(model->up) + ": it is 0 .. 16");
+  if (model->down < 0 || model->down > CALITAS_ACTIVITY_MAX_FLANK) return calitas_fail(c, CALITAS_EINVAL, "activity model: down is " + std::to_string(model->down) + ": it is 0 .. 16");
+  if (model->link < 0 || model->link > 1) return calitas_fail(c, CALITAS_EINVAL, "activity model: link is " + std::to_string(model->link) + ": it is 0 (identity) or 1 (logistic)");
+  const int W = model->up + L + model->down;
+  const auto outside = [](int32_t v) { return v < -CALITAS_ACTIVITY_MAX_WEIGHT || v > CALITAS_ACTIVITY_MAX_WEIGHT; };
+  if (outside(model->intercept)) return calitas_fail(c, CALITAS_EINVAL, "activity model: intercept lies outside +-1048576 (16.0)");
+  const struct { const char* name; const int32_t* at; int n; } tables[3] = {{"single", model->single, 4 * W}, {"pair", model->pair, 16 * (W - 1)}, {"gc", model->gc, L + 1}};
+  for (const auto& t : tables)
+    for (int i = 0; i < t.n; i++)
+      if (outside(t.at[i])) return calitas_fail(c, CALITAS_EINVAL, std::string("activity model: ") + t.name + "[" + std::to_string(i) + "] lies outside +-1048576 (16.0)");
+  call.model = model; call.L = L; call.W = W; call.min_score = min_score; call.threshold = min_score != CALITAS_ACTIVITY_NONE;
+  return CALITAS_OK;
+}
+
+// The contract on one site, base by base: the window's letters from PackedRef::base_upper, turned as the guide reads, the three sums
+// from the caller's tables as they stand.  *flagged: the window lies in the contig and holds an exception base -- a U among them --
+// which is when the kernel leaves the site to the host.
+int32_t activity_at(const PackedRef& ref, const calitas_activity_model_t& m, const calitas_site_t& s, bool* flagged) {
+  const int L = m.protospacer_length, W = m.up + L + m.down;
+  const bool minus = s.strand == '-';
+  const ContigInfo& ci = ref.contigs[(size_t)s.contig_index];
+  const int64_t left = (int64_t)s.protospacer_start - (minus ? m.down : m.up);
+  *flagged = false;
+  if (left < 0 || (uint64_t)(left + W) > ci.len) return CALITAS_ACTIVITY_NONE;
+  int code[ACTIVITY_MAX_W];                                    // the context, 5' to 3' as the guide reads
+  bool plain = true;
+  for (int j = 0; j < W; j++) {
+    const uint64_t g = ci.gbase + (uint64_t)(left + j);
+    if ((ref.mask[g >> 5] >> (g & 31)) & 1u) *flagged = true;
+    const char ch = ref.base_upper(g);
+    const int c = ch == 'A' ? 0 : ch == 'C' ? 1 : ch == 'G' ? 2 : (ch == 'T' || ch == 'U') ? 3 : -1;
+    if (c < 0) plain = false;
+    code[minus ? W - 1 - j : j] = minus ? 3 - c : c;
+  }
+  if (!plain) return CALITAS_ACTIVITY_NONE;
+  int32_t sum = m.intercept;
+  int gc = 0;
+  for (int i = 0; i < W; i++) sum += m.single[4 * i + code[i]];
+  for (int i = 0; i + 1 < W; i++) sum += m.pair[16 * i + 4 * code[i] + code[i + 1]];
+  for (int i = m.up; i < m.up + L; i++) gc += code[i] == 1 || code[i] == 2;
+  return sum + m.gc[gc];
+}
+
+inline bool activity_passes(const ActivityCall& call, int32_t score) { return score >= call.min_score; }   // (NONE passes NONE alone)
+
+// the two blocks of the call: room for n records and n scores (at least one each)
+int activity_blocks_alloc(calitas_ctx* c, uint64_t n, calitas_site_t** sites, int32_t** scores) {
+  *sites = (calitas_site_t*)calitas_out_alloc(std::max<uint64_t>(1, n) * sizeof(calitas_site_t));
+  *scores = (int32_t*)calitas_out_alloc(std::max<uint64_t>(1, n) * sizeof(int32_t));
+  if (*sites && *scores) return CALITAS_OK;
+  calitas_free(*sites); calitas_free(*scores);
+  *sites = nullptr; *scores = nullptr;
+  return calitas_fail(c, CALITAS_EINVAL, "out of memory");
+}
+
+// what the caller gets: the blocks, or the number alone
+void activity_hand_over(calitas_site_t* block, int32_t* block_scores, uint64_t n, calitas_site_t** sites, int32_t** scores, uint64_t* n_sites) {
+  *n_sites = n;
+  if (sites) { *sites = block; *scores = block_scores; }
+  else { calitas_free(block); calitas_free(block_scores); }
+}
+
+}  // namespace
+
+int calitas_find_sites_scored_host_impl(const calitas_ctx* ctx, const calitas_guide_t* pattern, const calitas_site_filter_t* filter,
+                                        const calitas_activity_model_t* model, int32_t min_score, int32_t chrom_index, uint64_t start, uint64_t end,
+                                        calitas_site_t** sites, int32_t** scores, uint64_t* n_sites) {
+  calitas_ctx* c = const_cast<calitas_ctx*>(ctx);
+  ActivityCall call;
+  if (int rc = plan_activity(c, pattern, filter, model, min_score, chrom_index, start, end, call)) return rc;
+  std::vector<calitas_site_t> found;
+  for (int i = call.site.c_first; i <= call.site.c_last; i++) {
+    const uint64_t len = ctx->ref.contigs[(size_t)i].len;
+    host_sites(ctx->ref, call.site.tab.pat, filter, i, 0, (int64_t)len, (int64_t)std::min(start, len), (int64_t)region_end(len, end), found, nullptr);
+  }
+  calitas_site_t* block = nullptr;
+  int32_t* block_scores = nullptr;
+  if (int rc = activity_blocks_alloc(c, found.size(), &block, &block_scores)) return rc;
+  uint64_t n = 0;
+  for (const calitas_site_t& s : found) {
+    bool flagged = false;
+    const int32_t score = activity_at(ctx->ref, *model, s, &flagged);
+    if (!activity_passes(call, score)) continue;
+    block[n] = s; block_scores[n] = score; n++;
+  }
+  activity_hand_over(block, block_scores, n, sites, scores, n_sites);
+  return CALITAS_OK;
+}
+
+int calitas_find_sites_scored_impl(calitas_ctx* ctx, const calitas_guide_t* pattern, const calitas_site_filter_t* filter, const calitas_activity_model_t* model,
+                                   int32_t min_score, int32_t chrom_index, uint64_t start, uint64_t end, calitas_site_t** sites, int32_t** scores,
+                                   uint64_t* n_sites) {
+  ActivityCall call;
+  if (int rc = plan_activity(ctx, pattern, filter, model, min_score, chrom_index, start, end, call)) return rc;
+  if (ctx->device < 0) return calitas_fail(ctx, CALITAS_ENODEV, "host-only context: calitas_find_sites_scored needs a GPU (there is no CPU fallback; calitas_find_sites_scored_host is the host twin)");
+  const PackedRef& ref = ctx->ref;
+  const size_t nc = ref.contigs.size();
+  calitas_site_t* block = nullptr;
+  int32_t* block_scores = nullptr;
+  if (nc == 0) {                                  // nothing to scan
+    if (int rc = activity_blocks_alloc(ctx, 0, &block, &block_scores)) return rc;
+    activity_hand_over(block, block_scores, 0, sites, scores, n_sites);
+    return CALITAS_OK;
+  }
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  if (!ctx->sites) ctx->sites = new SitesWork();
+  SitesWork* w = ctx->sites;
+
+  // calitas_find_sites' two passes as they are; the records stay in d_out
+  SitesArgs a{};
+  if (int rc = site_launch(ctx, call.site, chrom_index, start, end, w, a)) return rc;
+  const uint32_t n_blocks = a.n_segs;
+  if (w->blocks_cap < (size_t)n_blocks + 1) {
+    (void)hipFree(w->d_count); (void)hipFree(w->d_off); w->d_count = nullptr; w->d_off = nullptr; w->blocks_cap = 0;
+    HIP_TRY(ctx, hipMalloc((void**)&w->d_count, ((size_t)n_blocks + 1) * sizeof(uint32_t)));
+    HIP_TRY(ctx, hipMalloc((void**)&w->d_off, ((size_t)n_blocks + 1) * sizeof(uint64_t)));
+    w->blocks_cap = (size_t)n_blocks + 1;
+  }
+  if (w->totals_cap < 2 * nc) {
+    (void)hipFree(w->d_totals); w->d_totals = nullptr; w->totals_cap = 0;
+    HIP_TRY(ctx, hipMalloc((void**)&w->d_totals, 2 * nc * sizeof(unsigned long long)));
+    w->totals_cap = 2 * nc;
+  }
+  a.wg_count = w->d_count; a.totals = w->d_totals; a.wg_offset = w->d_off; a.out = nullptr; a.out_capacity = 0;
+  uint64_t n_dev = 0;
+  HIP_TRY(ctx, hipMemcpyAsync(w->d_pat, &call.site.tab, filter ? sizeof(SiteTables) : sizeof(SitePatterns), hipMemcpyHostToDevice, ctx->stream));
+  HIP_TRY(ctx, hipMemsetAsync(w->d_totals, 0, 2 * nc * sizeof(unsigned long long), ctx->stream));
+  HIP_TRY(ctx, launch_sites_count(a, filter != nullptr, ctx->stream));
+  HIP_TRY(ctx, launch_sites_offsets(w->d_count, w->d_off, n_blocks, ctx->stream));
+  HIP_TRY(ctx, hipMemcpyAsync(&n_dev, w->d_off + n_blocks, sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  const char* const no_room = "the site records and their scores do not fit the device: list the region in pieces";
+  if (n_dev / ACTIVITY_THREADS >= 0x7FFFFFFFull) return calitas_fail(ctx, CALITAS_ENOMEM, no_room);
+  uint64_t n_kept = n_dev;
+  const SiteRecord* d_recs = nullptr;
+  const int32_t* d_scores = nullptr;
+  std::vector<int32_t> table;                     // (uploaded from here: it lives until the call's last wait)
+  if (n_dev) {
+    if (w->out_cap < n_dev) {
+      (void)hipFree(w->d_out); w->d_out = nullptr; w->out_cap = 0;
+      if (hipMalloc((void**)&w->d_out, n_dev * sizeof(SiteRecord)) != hipSuccess) { (void)hipGetLastError(); return calitas_fail(ctx, CALITAS_ENOMEM, no_room); }
+      w->out_cap = n_dev;
+    }
+    if (w->act_scores_cap < n_dev) {
+      (void)hipFree(w->d_act_scores); w->d_act_scores = nullptr; w->act_scores_cap = 0;
+      if (hipMalloc((void**)&w->d_act_scores, n_dev * sizeof(int32_t)) != hipSuccess) { (void)hipGetLastError(); return calitas_fail(ctx, CALITAS_ENOMEM, no_room); }
+      w->act_scores_cap = n_dev;
+    }
+    const uint32_t act_blocks = activity_blocks(n_dev);
+    if (call.threshold && w->act_blocks_cap < (size_t)act_blocks + 1) {
+      (void)hipFree(w->d_act_count); (void)hipFree(w->d_act_off); w->d_act_count = nullptr; w->d_act_off = nullptr; w->act_blocks_cap = 0;
+      HIP_TRY(ctx, hipMalloc((void**)&w->d_act_count, ((size_t)act_blocks + 1) * sizeof(uint32_t)));
+      HIP_TRY(ctx, hipMalloc((void**)&w->d_act_off, ((size_t)act_blocks + 1) * sizeof(uint64_t)));
+      w->act_blocks_cap = (size_t)act_blocks + 1;
+    }
+    if (!w->d_act_table) HIP_TRY(ctx, hipMalloc((void**)&w->d_act_table, ACTIVITY_TABLE_MAX_WORDS * sizeof(int32_t)));
+    a.out = w->d_out; a.out_capacity = n_dev;
+
+    // the model as the kernel reads it: single folded into pair (integer sums: exact), the last position's single, gc, the intercept
+    const int W = call.W, L = call.L;
+    table.resize(activity_table_words(L, W));
+    for (int i = 0; i + 1 < W; i++)
+      for (int ab = 0; ab < 16; ab++) table[(size_t)(16 * i + ab)] = model->pair[16 * i + ab] + model->single[4 * i + (ab >> 2)];
+    int32_t* tail = table.data() + 16 * (W - 1);
+    for (int b = 0; b < 4; b++) tail[b] = model->single[4 * (W - 1) + b];
+    for (int g = 0; g <= L; g++) tail[4 + g] = model->gc[g];
+    tail[4 + L + 1] = model->intercept;
+
+    ActivityArgs s{};
+    s.planes = ctx->d_planes; s.mask = ctx->d_mask; s.contigs = ctx->d_contigs; s.table = w->d_act_table; s.recs = w->d_out; s.scores = w->d_act_scores;
+    s.wg_kept = call.threshold ? w->d_act_count : nullptr;
+    s.n = n_dev; s.n_words = ref.total_packed / 32; s.n_contigs = (int32_t)nc; s.L = L; s.up = model->up; s.down = model->down; s.min_score = min_score;
+    HIP_TRY(ctx, launch_sites_write(a, filter != nullptr, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(w->d_act_table, table.data(), table.size() * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, launch_activity_score(s, ctx->stream));
+    d_recs = w->d_out; d_scores = w->d_act_scores;
+    if (call.threshold) {
+      HIP_TRY(ctx, launch_sites_offsets(w->d_act_count, w->d_act_off, act_blocks, ctx->stream));
+      HIP_TRY(ctx, hipMemcpyAsync(&n_kept, w->d_act_off + act_blocks, sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
+      HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));             // (the table's host copy is done with as well)
+      if (n_kept > n_dev) return calitas_fail(ctx, CALITAS_EHIP, "calitas_find_sites_scored: more records kept than written (internal error)");
+      if (n_kept && w->act_out_cap < n_kept) {
+        (void)hipFree(w->d_act_out); (void)hipFree(w->d_act_out_scores); w->d_act_out = nullptr; w->d_act_out_scores = nullptr; w->act_out_cap = 0;
+        if (hipMalloc((void**)&w->d_act_out, n_kept * sizeof(SiteRecord)) != hipSuccess || hipMalloc((void**)&w->d_act_out_scores, n_kept * sizeof(int32_t)) != hipSuccess) {
+          (void)hipGetLastError();
+          (void)hipFree(w->d_act_out); w->d_act_out = nullptr;
+          return calitas_fail(ctx, CALITAS_ENOMEM, no_room);
+        }
+        w->act_out_cap = n_kept;
+      }
+      if (n_kept) HIP_TRY(ctx, launch_activity_compact(w->d_out, w->d_act_scores, n_dev, min_score, w->d_act_off, w->d_act_out, w->d_act_out_scores, n_kept, ctx->stream));
+      d_recs = w->d_act_out; d_scores = w->d_act_out_scores;
+    }
+  }
+
+  // a U is a T to a site and an exception base to the kernels: the sites the site kernel did not see, and what it has in their place
+  std::vector<calitas_site_t> with_u, kernel_has;
+  sites_with_u(ctx, call.site, start, end, with_u, kernel_has);
+  if (int rc = activity_blocks_alloc(ctx, n_kept + with_u.size(), &block, &block_scores)) return rc;
+  int rc = CALITAS_OK;
+  do {   // (one exit that releases the blocks)
+    hipError_t e = hipSuccess;
+    if ((n_kept && ((e = hipMemcpyAsync(block, d_recs, n_kept * sizeof(SiteRecord), hipMemcpyDeviceToHost, ctx->stream)) != hipSuccess ||
+                    (e = hipMemcpyAsync(block_scores, d_scores, n_kept * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream)) != hipSuccess)) ||
+        (e = hipStreamSynchronize(ctx->stream)) != hipSuccess) {
+      rc = calitas_fail(ctx, CALITAS_EHIP, std::string("calitas_find_sites_scored: ") + hipGetErrorString(e));
+      break;
+    }
+    // A record the site kernel has beside a U is in the block exactly when its own score passes or its window was left to the host
+    // (both lists are in output order); it goes.
+    bool gaps = false;
+    calitas_site_t* const end_dev = block + n_kept;
+    for (const calitas_site_t& s : kernel_has) {
+      bool flagged = false;
+      const int32_t score = activity_at(ref, *model, s, &flagged);
+      const bool expected = flagged || activity_passes(call, score);
+      calitas_site_t* at = std::lower_bound(block, end_dev, s, site_less);
+      const bool there = at != end_dev && std::memcmp(at, &s, sizeof(s)) == 0;
+      if (there != expected) { rc = calitas_fail(ctx, CALITAS_EHIP, "calitas_find_sites_scored: the records beside a U are not the ones the host expects (internal error)"); break; }
+      if (there) { at->contig_index = -1; gaps = true; }
+    }
+    if (rc) break;
+    // the windows the kernel left to the host: scored base by base, dropped when below the threshold
+    for (uint64_t i = 0; i < n_kept; i++) {
+      if (block_scores[i] != ACTIVITY_HOST_DECIDES || block[i].contig_index < 0) continue;
+      bool flagged = false;
+      const int32_t score = activity_at(ref, *model, block[i], &flagged);
+      if (activity_passes(call, score)) block_scores[i] = score;
+      else { block[i].contig_index = -1; gaps = true; }
+    }
+    uint64_t n = n_kept;
+    if (gaps) {
+      n = 0;
+      for (uint64_t i = 0; i < n_kept; i++)
+        if (block[i].contig_index >= 0) { block[n] = block[i]; block_scores[n] = block_scores[i]; n++; }
+    }
+    // the sites with a U in their footprint come in with the host's scores, each at its place: a merge from the back that ends
+    // with the last of them
+    std::vector<int32_t> u_scores;
+    size_t n_in = 0;
+    for (const calitas_site_t& s : with_u) {
+      bool flagged = false;
+      const int32_t score = activity_at(ref, *model, s, &flagged);
+      if (!activity_passes(call, score)) continue;
+      with_u[n_in++] = s; u_scores.push_back(score);
+    }
+    for (uint64_t i = n, j = n_in, k = n + n_in; j > 0; k--) {
+      if (i > 0 && site_less(with_u[j - 1], block[i - 1])) { block[k - 1] = block[i - 1]; block_scores[k - 1] = block_scores[i - 1]; i--; }
+      else { block[k - 1] = with_u[j - 1]; block_scores[k - 1] = u_scores[j - 1]; j--; }
+    }
+    activity_hand_over(block, block_scores, n + n_in, sites, scores, n_sites);
+  } while (0);
+  if (rc) { calitas_free(block); calitas_free(block_scores); }
+  return rc;
 }

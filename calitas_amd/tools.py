@@ -322,9 +322,10 @@ class GuideSite:
     """One site of Context.find_sites as a guide: `guide` is the `-i` string a search takes -- the protospacer as it reads on the site's
     strand, upper case, with the PATTERN's matched PAM in lower case behind it (in front of it for a 5' PAM) -- and pam_sequence the
     genomic PAM bases on that strand; [start, end) is the footprint (protospacer + PAM), 0-based half-open."""
-    __slots__ = ("chromosome", "start", "end", "strand", "pam_index", "guide", "pam_sequence", "protospacer_start")
+    __slots__ = ("chromosome", "start", "end", "strand", "pam_index", "guide", "pam_sequence", "protospacer_start", "activity_q16")
 
     def __init__(self, *v):
+        self.activity_q16 = None                       # (find_guides with a model: the site's score, ACTIVITY_NONE when it has none)
         for k, x in zip(self.__slots__, v):
             setattr(self, k, x)
 
@@ -336,12 +337,19 @@ class GuideSite:
         return [self.guide_id, self.chromosome, self.start, self.end, self.strand, self.pam_index, self.guide, self.pam_sequence]
 
 
-def find_guides(ctx, pattern, chrom=None, start=0, end=None, host=False, filter=None):
+def find_guides(ctx, pattern, chrom=None, start=0, end=None, host=False, filter=None, activity=None, min_activity=None):
     """Context.find_sites turned into guides: a list of GuideSite in the sites' order.  pattern: a Guide or its `-i` string; filter: a
-    SiteFilter -- only the sites that pass it come back at all."""
+    SiteFilter -- only the sites that pass it come back at all.  activity: an ActivityModel -- every GuideSite carries its site's
+    on-target score as activity_q16 (Context.find_sites_scored; ACTIVITY_NONE where the site has none); min_activity: a Q16 integer,
+    only the sites that score at least that much come back."""
     if not isinstance(pattern, Guide):
         pattern = Guide(pattern)
-    sites = ctx.find_sites(pattern, chrom, start, end, host=host, filter=filter)
+    if activity is None:
+        if min_activity is not None:
+            raise ValueError("min_activity needs an activity model")
+        sites, q16 = ctx.find_sites(pattern, chrom, start, end, host=host, filter=filter), None
+    else:
+        sites, q16 = ctx.find_sites_scored(pattern, activity, min_score=min_activity, filter=filter, chrom=chrom, start=start, end=end, host=host)
     out = []
     L = pattern.protospacer_length
     bounds = {}
@@ -365,6 +373,8 @@ def find_guides(ctx, pattern, chrom=None, start=0, end=None, host=False, filter=
         lo, hi = (ps, ps + L) if pm < 0 else (min(ps, pm), max(ps + L, pm + pl))
         out.append(GuideSite(ctx.contig_names[c], lo, hi, "-" if minus else "+", k, (pam + proto) if pattern.pam_is_five_prime else (proto + pam),
                              pam_seq, ps))
+        if q16 is not None:
+            out[-1].activity_q16 = int(q16[len(out) - 1])
     return out
 
 
@@ -490,15 +500,31 @@ def near_list_tsv(rows, names, listing):
     return "\n".join(lines) + "\n"
 
 
-def guides_tsv(rows, tables=None, scores=None, copies=None, seed_copies=None, near=None, near_scores=None):
+def activity_q16_of_flag(text):
+    """--min-activity X as a Q16 integer: a decimal as in a model file (digits, at most one point, an optional sign), within what a
+    score can be (+-2064 = 129 weights of 16.0), floor(x * 65536 + 0.5)."""
+    import math
+    import re
+    text = str(text)
+    if not re.fullmatch(r"[+-]?([0-9]+\.?[0-9]*|\.[0-9]+)", text, re.ASCII) or not -2064.0 <= float(text) <= 2064.0:
+        raise ValueError("--min-activity X: X is a decimal in [-2064, 2064], not %s" % text)
+    return int(math.floor(float(text) * 65536.0 + 0.5))
+
+
+def guides_tsv(rows, tables=None, scores=None, copies=None, seed_copies=None, near=None, near_scores=None, activity=None):
     """The FindGuides table: GUIDE_COLUMNS, one row per GuideSite; with tables (guide_counts) also hits -- the table's sum -- and
     hits_mm0 .. hits_mmE, the hits per number of protospacer mismatches, summed over strands, gaps and PAM mismatches; with scores
     (guide_scores) those columns come from the same pass's tables and perfect and specificity (%.6f) follow them.  copies,
     seed_copies: lists aligned with rows (guide_copies) -- the columns of those names, directly behind pam_sequence.  near: a list of
     rows of M + 1 counts aligned with rows (guide_near), or an array of that shape -- the columns copies_mm0 .. copies_mmM behind those.
     near_scores: a NearScores aligned with rows (guide_near_scores) -- near_sum_q32, near_max_q32 and near_specificity (%.6f) directly
-    behind copies_mmM."""
+    behind copies_mmM.  activity: the ActivityModel the rows were scored with (find_guides) -- activity_q16, the score as it is, and
+    activity, the number its link makes of it (activity_value, %.6f), directly behind pam_sequence and before all of the above; NA in
+    both for a site without a score."""
+    from .aligner import ACTIVITY_NONE, activity_value
     header = list(GUIDE_COLUMNS)
+    if activity is not None:
+        header += ["activity_q16", "activity"]
     if copies is not None:
         header.append("copies")
     if seed_copies is not None:
@@ -520,6 +546,9 @@ def guides_tsv(rows, tables=None, scores=None, copies=None, seed_copies=None, ne
     lines = ["\t".join(header)]
     for i, r in enumerate(rows):
         f = [str(x) for x in r.row()]
+        if activity is not None:
+            unscored = r.activity_q16 is None or r.activity_q16 == ACTIVITY_NONE
+            f += ["NA", "NA"] if unscored else [str(r.activity_q16), "%.6f" % activity_value(r.activity_q16, activity)]
         if copies is not None:
             f.append(str(int(copies[i])))
         if seed_copies is not None:
@@ -569,7 +598,8 @@ def site_filter_of_flags(L, gc_min=None, gc_max=None, max_run=None, avoid=()):
 
 def find_guides_tool(ref, pattern, auxiliary_pams=(), chrom=None, start=0, end=None, output=None, counts=False, device=0, scores=None,
                      gc_min=None, gc_max=None, max_run=None, avoid=(), copies=False, seed_copies=None, max_copies=None, max_seed_copies=None,
-                     near_copies=None, max_near_copies=None, near_scores=None, near_list=None, near_list_limit=None, **search):
+                     near_copies=None, max_near_copies=None, near_scores=None, near_list=None, near_list_limit=None, activity=None, min_activity=None,
+                     **search):
     """`python -m calitas_amd FindGuides`: the guides of a region as a TSV (guides_tsv); counts=True: every distinct guide also goes
     through the off-target search with the SearchReference flags in `search` (make_params names); scores=ScoreModel (or its file):
     through search_scores_batch instead, which adds perfect and specificity.  gc_min, gc_max, max_run, avoid: the site filter's flags
@@ -583,7 +613,10 @@ def find_guides_tool(ref, pattern, auxiliary_pams=(), chrom=None, start=0, end=N
     columns near_sum_q32, near_max_q32 and near_specificity, from the one guide_near_scores pass that then gives the copies_mm columns
     as well.  near_list=FILE (needs near_copies): the kept rows' copies within M substitutions, one per line, to FILE (near_list_tsv;
     scored under near_scores' model when given); near_list_limit=N (1 .. 4096, default 1000): a row with more copies writes no line.
-    These nine work with device -1 through the host twin.  Returns the text."""
+    activity=ActivityModel (or its file; the model's length is the protospacer's): the columns activity_q16 and activity, every site
+    scored in the listing's own call; min_activity=X (needs activity): a decimal on the LINEAR score (under link logistic a probability
+    p is X = ln(p / (1 - p))) -- the rows that score less, and those without a score, are dropped before any of the flags above looks
+    at anything, the kept rows keep their guide_ids.  These eleven work with device -1 through the host twin.  Returns the text."""
     if (counts or scores is not None) and device < 0:
         raise ValueError("--counts and --scores search on the GPU: they cannot run with --device -1")
     if isinstance(scores, str):
@@ -620,10 +653,18 @@ def find_guides_tool(ref, pattern, auxiliary_pams=(), chrom=None, start=0, end=N
         raise ValueError("--near-list-limit requires --near-list FILE")
     if near_list_limit is not None and not 1 <= int(near_list_limit) <= 4096:
         raise ValueError("--near-list-limit N: N is 1 .. 4096")
+    if min_activity is not None and activity is None:
+        raise ValueError("--min-activity requires --activity MODEL")
+    if isinstance(activity, str):
+        from .aligner import ActivityModel
+        activity = ActivityModel.read(activity)
+    if activity is not None and activity.L != pat.protospacer_length:
+        raise ValueError("--activity: the model is for protospacers of %d bases, the pattern's has %d" % (activity.L, pat.protospacer_length))
+    floor = activity_q16_of_flag(min_activity) if min_activity is not None else None
     ctx = Context(device)
     try:
         ctx.set_reference_fasta(ref)
-        rows = find_guides(ctx, pat, chrom, start, end, host=device < 0, filter=keep)
+        rows = find_guides(ctx, pat, chrom, start, end, host=device < 0, filter=keep, activity=activity, min_activity=floor)
         n_copies = guide_copies(ctx, pat, rows, host=device < 0) if copies or max_copies is not None else None
         n_seed = guide_copies(ctx, pat, rows, key_length=int(seed_copies), host=device < 0) if seed_copies is not None else None
         scored_near = guide_near_scores(ctx, pat, rows, int(near_copies), near_scores, host=device < 0) if near_scores is not None else None
@@ -645,7 +686,7 @@ def find_guides_tool(ref, pattern, auxiliary_pams=(), chrom=None, start=0, end=N
             scored_near = NearScores(n_near, scored_near.sum_q32[kept], scored_near.max_q32[kept])
         tables = guide_counts(ctx, [r.guide for r in rows], make_params(**search)) if counts and scores is None else None
         scored = guide_scores(ctx, [r.guide for r in rows], make_params(**search), scores) if scores is not None else None
-        text = guides_tsv(rows, tables, scored, copies=n_copies, seed_copies=n_seed, near=n_near, near_scores=scored_near)
+        text = guides_tsv(rows, tables, scored, copies=n_copies, seed_copies=n_seed, near=n_near, near_scores=scored_near, activity=activity)
         if near_list is not None:
             listing = guide_near_list(ctx, pat, rows, int(near_copies), near_scores, limit=1000 if near_list_limit is None else int(near_list_limit), host=device < 0)
             with open(near_list, "w") as f:

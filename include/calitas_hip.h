@@ -504,6 +504,54 @@ int calitas_list_near_host(const calitas_ctx* ctx, const calitas_guide_t* patter
                            int32_t chrom_index, uint64_t start, uint64_t end, const char* queries, uint64_t n_queries, uint32_t limit,
                            uint64_t* near, uint64_t* offsets, calitas_near_hit_t** hits, uint64_t* n_hits);
 
+/* On-target activity: how well a guide cut from a site is expected to cut, from the site's sequence context under a linear model.
+ * The CONTEXT of a site is W = up + L + down letters as the guide reads: `up` bases 5' of the protospacer, its L bases, `down` bases
+ * 3' of it.  With p the record's protospacer_start it is the forward bases [p - up, p + L + down) on '+' and the reverse complement of
+ * the forward bases [p - down, p + L + up) on '-'.  The model knows nothing of PAMs: for an ...nrg pattern and down = 6 the context holds
+ * the PAM and three bases behind it, for a 5' PAM the PAM lies in `up`; a site matched by an auxiliary PAM of another length is scored
+ * over the same window.
+ * A site is scored when the window lies inside its contig -- the contig bounds it, not the region, which bounds footprints as in
+ * calitas_find_sites -- and every base of it is a plain A C G T, in either case, or a U (read as T).  Otherwise its score is
+ * CALITAS_ACTIVITY_NONE.  With c_i the code of context letter i (A 0, C 1, G 2, T 3) the score is
+ *   intercept + sum_i single[i][c_i] + sum_{i < W - 1} pair[i][4 c_i + c_{i+1}] + gc[number of G and C among the L protospacer bases]
+ * in 32-bit signed integers, all Q16 (65536 = 1.0).  Every weight lies within +-CALITAS_ACTIVITY_MAX_WEIGHT and there are at most
+ * 2 * 64 + 1 terms, so the sum stays below 2^28 in magnitude: it never overflows and never equals CALITAS_ACTIVITY_NONE.  Integer
+ * addition has no order, so the kernel, the host twin and a plain loop give the same numbers.  `link` says how a tool prints the score
+ * (0: score / 65536, 1: 1 / (1 + exp(-score / 65536))) and changes nothing else.  The library ships the mechanism and a file format
+ * (models/example_activity30.tsv), no published weight table. */
+#define CALITAS_ACTIVITY_NONE INT32_MIN       /* this site has no score */
+#define CALITAS_ACTIVITY_MAX_FLANK 16
+#define CALITAS_ACTIVITY_MAX_WEIGHT 1048576   /* |weight| <= 16.0 in Q16 */
+typedef struct {
+  int32_t protospacer_length;   /* L: must be the pattern's */
+  int32_t up, down;             /* bases 5' and 3' of the protospacer AS THE GUIDE READS, 0 .. 16 each; W = up + L + down <= 64 */
+  int32_t link;                 /* 0 identity, 1 logistic: how a tool prints the score, nothing else */
+  int32_t intercept;            /* Q16, signed */
+  const int32_t* single;        /* [W][4]      position in the context, base A C G T */
+  const int32_t* pair;          /* [W - 1][16] position i, 4 * base(i) + base(i + 1) */
+  const int32_t* gc;            /* [L + 1]     by the protospacer's G + C count */
+} calitas_activity_model_t;
+/* The records of calitas_find_sites_filtered(pattern, filter, ...) whose score is >= min_score_q16, in that call's order and with its
+ * bytes; scores[i] belongs to sites[i].  min_score_q16 == CALITAS_ACTIVITY_NONE keeps every site, the unscored ones carrying
+ * CALITAS_ACTIVITY_NONE; any other threshold drops the unscored ones as well (one signed comparison says all of this).
+ * sites == NULL && scores == NULL: *n_sites only.  Each block takes one calitas_free.
+ * On the device the records of the site kernel's two passes stay where they are: one lane per record scores its window from the
+ * bit-planes (the model's tables in LDS), and with a threshold a second kernel compacts records and scores in order (ranks from
+ * ballots: no sort, no returning atomic) before the one copy-back.  Windows with an exception base -- a U among them, which the
+ * device cannot tell from an N -- are decided on the host.
+ * Errors, in this order: what calitas_find_sites_filtered refuses; CALITAS_EINVAL, with a message that names the field, for a NULL
+ * model or table, a protospacer_length other than the pattern's, up or down outside 0 .. 16, link outside 0 .. 1, intercept or a weight
+ * outside +-CALITAS_ACTIVITY_MAX_WEIGHT; CALITAS_ENODEV on a host-only context; CALITAS_ENOMEM when records and scores do not fit the
+ * device.  No reference counterpart. */
+int calitas_find_sites_scored(calitas_ctx* ctx, const calitas_guide_t* pattern, const calitas_site_filter_t* filter /* may be NULL */,
+                              const calitas_activity_model_t* model, int32_t min_score_q16, int32_t chrom_index, uint64_t start, uint64_t end,
+                              calitas_site_t** sites, int32_t** scores, uint64_t* n_sites);
+/* The host twin of calitas_find_sites_scored: calitas_find_sites_filtered_host's records, each scored base by base; also on a host-only
+ * context.  No reference counterpart. */
+int calitas_find_sites_scored_host(const calitas_ctx* ctx, const calitas_guide_t* pattern, const calitas_site_filter_t* filter,
+                                   const calitas_activity_model_t* model, int32_t min_score_q16, int32_t chrom_index, uint64_t start,
+                                   uint64_t end, calitas_site_t** sites, int32_t** scores, uint64_t* n_sites);
+
 /* The K highest-scoring imperfect hits of a guide, from the pass that scores them.  No reference counterpart.
  * The candidates are the kept hits that are not perfect (total_mm_plus_gaps != 0); they are ordered by score_q32 descending, and among
  * equal scores the hit whose row comes earlier in the hits.txt of the same call comes first.  That is a total order: the n records are

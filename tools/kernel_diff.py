@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Generated-code comparison of the device units (the stage units scan_columns / align / trace / mailbox / setup .hip, which replaced
-kernels.hip, and select / hits / binned .hip) against an earlier revision: the check that a move or a refactor of device code left the
+kernels.hip, select / hits / binned .hip, and the guide-site units sites / near_list / activity .hip) against an earlier revision: the check that a move or a refactor of device code left the
 compiler's output as it was.
 
   python tools/kernel_diff.py [--rev HEAD~1] [--show]
@@ -15,7 +15,8 @@ compiler's output as it was.
    shifts values down the lanes (`wave_shr:1`: the fill loops of the aligners), and whether those loops differ in more than the
    numbers of their registers.  --show prints the unified diff of a kernel that
    differs.
-Exit status 1 when a kernel differs or one is missing on either side."""
+A kernel the revision does not have is listed as new with its resources.
+Exit status 1 when a kernel differs or one of the revision's is missing."""
 import argparse
 import difflib
 import os
@@ -26,7 +27,8 @@ import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join("calitas_amd", "csrc")
-UNITS = ["kernels.hip", "scan_columns.hip", "align.hip", "trace.hip", "mailbox.hip", "setup.hip", "select.hip", "hits.hip", "binned.hip"]
+UNITS = ["kernels.hip", "scan_columns.hip", "align.hip", "trace.hip", "mailbox.hip", "setup.hip", "select.hip", "hits.hip", "binned.hip", "sites.hip",
+         "near_list.hip", "activity.hip"]
 
 
 def device_asm(csrc, out_dir):
@@ -125,8 +127,11 @@ def main():
     print("%-34s %-9s %-13s %-13s %-15s %s" % ("function", "code", "VGPR old/new", "SGPR old/new", "LDS old/new", "scratch, lane-shift loops old/new"))
     for name in sorted(set(old) | set(new), key=short):
         o, n = old.get(name), new.get(name)
-        if o is None or n is None:
-            print("%-34s only in %s" % (short(name), "the working tree" if o is None else a.rev))
+        if o is None:                                           # a new kernel: its resources, nothing to compare
+            print("%-34s new       VGPR %s  SGPR %s  LDS %s  scratch %s" % (short(name), n.get("vgpr", "-"), n.get("sgpr", "-"), n.get("lds", "-"), n.get("scratch", "-")))
+            continue
+        if n is None:
+            print("%-34s only in %s" % (short(name), a.rev))
             bad += 1
             continue
         same = o["code"] == n["code"]
