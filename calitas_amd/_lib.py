@@ -112,6 +112,10 @@ class ActivityModelT(ctypes.Structure):
                 ("gc", ctypes.POINTER(ctypes.c_int32))]
 
 
+class SiteRegionsT(ctypes.Structure):
+    _fields_ = [("class_mask", ctypes.c_uint32), ("ext_from", ctypes.c_uint8), ("ext_to", ctypes.c_uint8), ("reserved", ctypes.c_uint16)]
+
+
 TOP_MAX = 256
 NEAR_LIST_MAX = 4096
 ACTIVITY_NONE = -(1 << 31)
@@ -134,7 +138,9 @@ SYMBOLS = ["calitas_create", "calitas_destroy", "calitas_last_error", "calitas_f
            "calitas_find_sites_filtered", "calitas_count_sites_filtered", "calitas_find_sites_filtered_host",
            "calitas_count_copies", "calitas_count_copies_host", "calitas_count_near", "calitas_count_near_host",
            "calitas_score_near", "calitas_score_near_host", "calitas_list_near", "calitas_list_near_host",
-           "calitas_find_sites_scored", "calitas_find_sites_scored_host"]
+           "calitas_find_sites_scored", "calitas_find_sites_scored_host",
+           "calitas_find_sites_regions", "calitas_count_sites_regions", "calitas_find_sites_regions_host", "calitas_count_sites_regions_host",
+           "calitas_site_presence"]
 
 if not os.path.exists(LIB_PATH):
     raise ImportError("%s is missing: build it with `make -C calitas_amd/csrc` (hipcc, gfx950). "
@@ -223,6 +229,16 @@ if hasattr(lib, "calitas_find_sites_scored"):      # (an older build behind CALI
                                               ctypes.c_int32, ctypes.c_uint64, ctypes.c_uint64, ctypes.POINTER(ctypes.POINTER(SiteT)),
                                               ctypes.POINTER(ctypes.POINTER(ctypes.c_int32)), ctypes.POINTER(ctypes.c_uint64)]
     lib.calitas_find_sites_scored_host.argtypes = lib.calitas_find_sites_scored.argtypes
+if hasattr(lib, "calitas_find_sites_regions"):     # (an older build behind CALITAS_LIB_PATH, for A/B runs, does not have it)
+    lib.calitas_find_sites_regions.argtypes = [ctypes.c_void_p, ctypes.POINTER(GuideT), ctypes.POINTER(SiteFilterT), ctypes.POINTER(SiteRegionsT), ctypes.c_int32,
+                                               ctypes.c_uint64, ctypes.c_uint64, ctypes.POINTER(ctypes.POINTER(SiteT)),
+                                               ctypes.POINTER(ctypes.POINTER(ctypes.c_uint8)), ctypes.POINTER(ctypes.c_uint64)]
+    lib.calitas_find_sites_regions_host.argtypes = lib.calitas_find_sites_regions.argtypes
+    lib.calitas_count_sites_regions.argtypes = [ctypes.c_void_p, ctypes.POINTER(GuideT), ctypes.POINTER(SiteFilterT), ctypes.POINTER(SiteRegionsT), ctypes.c_int32,
+                                                ctypes.c_uint64, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]
+    lib.calitas_count_sites_regions_host.argtypes = lib.calitas_count_sites_regions.argtypes
+    lib.calitas_site_presence.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.POINTER(ctypes.c_uint8)), ctypes.POINTER(ctypes.c_uint64),
+                                          ctypes.POINTER(ctypes.c_uint64)]
 lib.calitas_search_scores.argtypes = [ctypes.c_void_p, ctypes.POINTER(GuideT), ctypes.POINTER(ParamsT), ctypes.POINTER(ScoreModelT),
                                       ctypes.POINTER(ctypes.POINTER(ScoresT))]
 lib.calitas_search_scores_batch.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.POINTER(GuideT), ctypes.POINTER(ParamsT),

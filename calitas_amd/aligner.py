@@ -686,6 +686,84 @@ class Context:
         _lib.check(self._h, rc)
         return n.value
 
+    def _site_regions_opt(self, pattern, classes, extent):
+        """The calitas_site_regions_t of classes (None: every class but "elsewhere"; names or indices of the context's Regions, or an
+        integer mask) and extent ((from, to), None: the whole protospacer)."""
+        if isinstance(classes, int) and not isinstance(classes, bool):
+            mask = classes
+        elif classes is None:
+            mask = ((1 << len(self.regions.classes)) - 2) if self.regions is not None else 0xFE
+        else:
+            names = [c for c in classes.split(",") if c] if isinstance(classes, str) else list(classes)
+            mask = 0
+            for c in names:
+                if isinstance(c, str):
+                    if self.regions is None:
+                        raise ValueError("class names need a Regions set on the context (set_regions)")
+                    mask |= self.regions.mask_of([c])
+                else:
+                    mask |= 1 << int(c)
+        if not 0 <= mask < 1 << 32:
+            raise ValueError("the class mask of a regions listing is an integer of 32 bits")
+        a, b = (0, 0) if extent is None else (int(extent[0]), int(extent[1]))
+        if not (0 <= a < 256 and 0 <= b < 256):
+            raise ValueError("extent (%d, %d): positions of the protospacer, 0 <= from < to <= its length" % (a, b))
+        if extent is not None and (a, b) == (0, 0):
+            raise ValueError("extent (0, 0) is empty: None means the whole protospacer")
+        return _lib.SiteRegionsT(mask, a, b, 0)
+
+    def find_sites_regions(self, pattern, classes=None, extent=None, filter=None, chrom=None, start=0, end=None, host=False):
+        """calitas_find_sites_regions: (sites, classes) -- the records of find_sites(pattern, filter=filter) whose class under the
+        context's regions (set_regions) is one of `classes`, and in a uint8 array beside them each record's class index.  classes:
+        names or indices (an iterable or a comma-separated string; "elsewhere" is class 0), None: every class but "elsewhere".  extent:
+        (from, to), the positions of the protospacer as the guide reads that are classed, 0-based and half-open -- (16, 18) on a 20-mer
+        with a 3' PAM is the two bases beside the Cas9 cut; None: the whole protospacer.  site_class_of states the rule on one site.
+        host=True: the host twin (calitas_find_sites_regions_host), also on a host-only context."""
+        import numpy as np
+        pattern, index, start, end = self._site_region(pattern, chrom, start, end)
+        opt = self._site_regions_opt(pattern, classes, extent)
+        g = pattern.to_c()
+        f = filter.to_c() if filter is not None else None
+        out, cls, n = ctypes.POINTER(SiteT)(), ctypes.POINTER(ctypes.c_uint8)(), ctypes.c_uint64()
+        fn = lib.calitas_find_sites_regions_host if host else lib.calitas_find_sites_regions
+        rc = fn(self._h, ctypes.byref(g), ctypes.byref(f) if f is not None else None, ctypes.byref(opt), index, start, end, ctypes.byref(out),
+                ctypes.byref(cls), ctypes.byref(n))
+        _lib.check(self._h, rc)
+        try:
+            of = np.ctypeslib.as_array(cls, shape=(n.value,)).astype(np.uint8) if n.value else np.zeros(0, dtype=np.uint8)   # (astype copies)
+        finally:
+            lib.calitas_free(cls)
+        return self._take_records(out, n.value, SiteT, SITE_DTYPE), of
+
+    def count_sites_regions(self, pattern, classes=None, extent=None, filter=None, chrom=None, start=0, end=None, host=False):
+        """calitas_count_sites_regions: a numpy uint64 array [n_classes][2] ('+' first) of the sites find_sites_regions would return,
+        per class and strand; the rows of classes outside `classes` are 0.  Nothing but the counters is copied back."""
+        import numpy as np
+        pattern, index, start, end = self._site_region(pattern, chrom, start, end)
+        opt = self._site_regions_opt(pattern, classes, extent)
+        g = pattern.to_c()
+        f = filter.to_c() if filter is not None else None
+        table = np.zeros((_lib.REGION_CLASSES_MAX, 2), dtype=np.uint64)
+        n = ctypes.c_uint64()
+        fn = lib.calitas_count_sites_regions_host if host else lib.calitas_count_sites_regions
+        rc = fn(self._h, ctypes.byref(g), ctypes.byref(f) if f is not None else None, ctypes.byref(opt), index, start, end,
+                table.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), ctypes.byref(n))
+        _lib.check(self._h, rc)
+        table = table[:len(self.regions.classes)] if self.regions is not None else table
+        assert int(table.sum()) == n.value
+        return table
+
+    def site_presence(self):
+        """(test hook) calitas_site_presence: (bytes, first_word) -- the table the regions listing skips segments by, a uint8 array with
+        one byte per 256 words (8192 bases) of the packed space from word first_word on; bit c: class c comes near the segment."""
+        import numpy as np
+        out, n, first = ctypes.POINTER(ctypes.c_uint8)(), ctypes.c_uint64(), ctypes.c_uint64()
+        _lib.check(self._h, lib.calitas_site_presence(self._h, ctypes.byref(out), ctypes.byref(n), ctypes.byref(first)))
+        try:
+            return (np.ctypeslib.as_array(out, shape=(n.value,)).astype(np.uint8) if n.value else np.zeros(0, dtype=np.uint8)), first.value
+        finally:
+            lib.calitas_free(out)
+
     @staticmethod
     def _scores_of(c):
         """A calitas_scores_t as a Scores object (the table is copied)."""
@@ -1684,6 +1762,30 @@ def class_of_row(row, regions, by_chromosome=None):
         for c, s, e, k in (regions.intervals if by_chromosome is None else by_chromosome.get(chrom, ())):
             if c == chrom and s < b and e > a and (best == 0 or k < best):
                 best = k
+    return best
+
+
+def site_class_of(site, regions, extent=None):
+    """The contract of find_sites_regions on one site, as a plain scan of the raw intervals like class_of_row.  site: a GuideSite, or
+    (chromosome, protospacer_start, strand, protospacer_length) with the strand as "+" / "-".  extent: (from, to), positions of the
+    protospacer as the guide reads, 0 its 5' base, half-open; None: all of it.  They are the forward bases [p + from, p + to) on '+'
+    and [p + L - to, p + L - from) on '-'; the class is the smallest class index among the intervals of the chromosome that overlap
+    them, 0 when there is none."""
+    if hasattr(site, "protospacer_start"):
+        chrom, p, strand = site.chromosome, int(site.protospacer_start), site.strand
+        L = sum(1 for ch in site.guide if ch.isupper())
+    else:
+        chrom, p, strand, L = site[0], int(site[1]), site[2], int(site[3])
+    if isinstance(strand, bytes):
+        strand = strand.decode()
+    a, b = (0, L) if extent is None else (int(extent[0]), int(extent[1]))
+    if not 0 <= a < b <= L:
+        raise ValueError("extent (%d, %d): 0 <= from < to <= %d, the protospacer's length" % (a, b, L))
+    lo, hi = (p + L - b, p + L - a) if strand == "-" else (p + a, p + b)
+    best = 0
+    for c, s, e, k in regions.intervals:
+        if c == chrom and s < hi and e > lo and (best == 0 or k < best):
+            best = k
     return best
 
 

@@ -1325,4 +1325,58 @@ int calitas_find_sites_scored_host(const calitas_ctx* ctx, const calitas_guide_t
   return calitas_find_sites_scored_host_impl(ctx, pattern, filter, model, min_score_q16, chrom_index, start, end, sites, scores, n_sites);
 }
 
+// Sites by annotated regions (sites_host.cpp, site_regions.hip): no reference counterpart.
+int calitas_find_sites_regions(calitas_ctx* ctx, const calitas_guide_t* pattern, const calitas_site_filter_t* filter, const calitas_site_regions_t* opt,
+                               int32_t chrom_index, uint64_t start, uint64_t end, calitas_site_t** sites, uint8_t** classes, uint64_t* n_sites) {
+  if (!ctx) return CALITAS_EINVAL;
+  if (!pattern || !n_sites || (sites == nullptr) != (classes == nullptr)) return fail(ctx, CALITAS_EINVAL, "NULL argument");
+  *n_sites = 0;
+  if (sites) { *sites = nullptr; *classes = nullptr; }
+  return calitas_find_sites_regions_impl(ctx, pattern, filter, opt, chrom_index, start, end, sites != nullptr, sites, classes, nullptr, n_sites);
+}
+
+int calitas_count_sites_regions(calitas_ctx* ctx, const calitas_guide_t* pattern, const calitas_site_filter_t* filter, const calitas_site_regions_t* opt,
+                                int32_t chrom_index, uint64_t start, uint64_t end, uint64_t* per_class_strand, uint64_t* n_sites) {
+  if (!ctx) return CALITAS_EINVAL;
+  if (!pattern || !n_sites) return fail(ctx, CALITAS_EINVAL, "NULL argument");
+  *n_sites = 0;
+  return calitas_find_sites_regions_impl(ctx, pattern, filter, opt, chrom_index, start, end, false, nullptr, nullptr, per_class_strand, n_sites);
+}
+
+int calitas_find_sites_regions_host(const calitas_ctx* ctx, const calitas_guide_t* pattern, const calitas_site_filter_t* filter,
+                                    const calitas_site_regions_t* opt, int32_t chrom_index, uint64_t start, uint64_t end, calitas_site_t** sites,
+                                    uint8_t** classes, uint64_t* n_sites) {
+  if (!ctx) return CALITAS_EINVAL;
+  if (!pattern || !n_sites || (sites == nullptr) != (classes == nullptr)) return fail(const_cast<calitas_ctx*>(ctx), CALITAS_EINVAL, "NULL argument");
+  *n_sites = 0;
+  if (sites) { *sites = nullptr; *classes = nullptr; }
+  return calitas_find_sites_regions_host_impl(ctx, pattern, filter, opt, chrom_index, start, end, sites != nullptr, sites, classes, nullptr, n_sites);
+}
+
+int calitas_count_sites_regions_host(const calitas_ctx* ctx, const calitas_guide_t* pattern, const calitas_site_filter_t* filter,
+                                     const calitas_site_regions_t* opt, int32_t chrom_index, uint64_t start, uint64_t end, uint64_t* per_class_strand,
+                                     uint64_t* n_sites) {
+  if (!ctx) return CALITAS_EINVAL;
+  if (!pattern || !n_sites) return fail(const_cast<calitas_ctx*>(ctx), CALITAS_EINVAL, "NULL argument");
+  *n_sites = 0;
+  return calitas_find_sites_regions_host_impl(ctx, pattern, filter, opt, chrom_index, start, end, false, nullptr, nullptr, per_class_strand, n_sites);
+}
+
+int calitas_site_presence(const calitas_ctx* ctx, uint8_t** bytes, uint64_t* n, uint64_t* first_word) {
+  if (!ctx) return CALITAS_EINVAL;
+  calitas_ctx* c = const_cast<calitas_ctx*>(ctx);
+  if (!bytes || !n || !first_word) return fail(c, CALITAS_EINVAL, "NULL argument");
+  *bytes = nullptr; *n = 0; *first_word = 0;
+  if (!ctx->has_ref) return fail(c, CALITAS_ESTATE, "calitas_set_reference has not been called");
+  if (ctx->regions.empty()) return fail(c, CALITAS_EINVAL, "site regions: the context has no regions (calitas_set_regions)");
+  const std::vector<uint8_t>* table = nullptr;
+  const std::string e = site_presence(c, &table);
+  if (!e.empty()) return fail(c, CALITAS_EINVAL, e);
+  *bytes = (uint8_t*)calitas_out_alloc(std::max<size_t>(1, table->size()));
+  if (!*bytes) return fail(c, CALITAS_EINVAL, "out of memory");
+  if (!table->empty()) std::memcpy(*bytes, table->data(), table->size());
+  *n = table->size();
+  return CALITAS_OK;
+}
+
 }  // extern "C"

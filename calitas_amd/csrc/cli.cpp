@@ -39,6 +39,9 @@ static void usage() {
     "         [--activity model.tsv (the columns activity_q16 and activity: every site's on-target score under the activity model, NA where it has none)]\n"
     "         [--min-activity X (with --activity: drop rows whose LINEAR score is below the decimal X, and those without a score, before any\n"
     "          other flag looks at them; under `link logistic` a probability p is X = ln(p / (1 - p)))]\n"
+    "         [--regions file.bed (chromosome start end class: only the sites in the named classes' intervals, and the column class)]\n"
+    "         [--classes name,... (with --regions: the classes to keep; elsewhere: outside every interval)]\n"
+    "         [--class-extent FROM:TO (with --regions: class these positions of the protospacer as the guide reads, 0-based half-open; default all)]\n"
     "         [--device N (-1: the host twin, no GPU)]\n");
 }
 
@@ -375,6 +378,8 @@ static int find_guides_main(int argc, char** argv) {
   bool have_list_limit = false;
   std::string activity, min_activity;     // --activity MODEL.tsv [--min-activity X]
   bool have_min_activity = false;
+  std::string regions_path, class_names, class_extent;     // --regions FILE.bed [--classes name,...] [--class-extent FROM:TO]
+  bool have_classes = false, have_extent = false;
   for (int i = 2; i < argc; i++) {
     std::string a = argv[i], val;
     size_t eq = a.find('=');
@@ -408,6 +413,9 @@ static int find_guides_main(int argc, char** argv) {
     else if (a == "--near-list-limit") { near_list_limit = std::atoll(next().c_str()); have_list_limit = true; }
     else if (a == "--activity") activity = next();
     else if (a == "--min-activity") { min_activity = next(); have_min_activity = true; }
+    else if (a == "--regions") regions_path = next();
+    else if (a == "--classes") { class_names = next(); have_classes = true; }
+    else if (a == "--class-extent") { class_extent = next(); have_extent = true; }
     else { std::fprintf(stderr, "unknown argument %s\n", a.c_str()); usage(); return 2; }
   }
   if (pattern.empty() || ref.empty()) { usage(); return 2; }
@@ -458,6 +466,18 @@ static int find_guides_main(int argc, char** argv) {
     // (+-2064: 129 weights of 16.0, what a score can be)
     if (have_min_activity && !activity_decimal(min_activity, 2064.0, &min_score)) { std::fprintf(stderr, "calitas: --min-activity X: X is a decimal in [-2064, 2064], not %s\n", min_activity.c_str()); return 2; }
   }
+  const bool have_regions = !regions_path.empty();
+  if (!have_regions && (have_classes || have_extent)) { std::fprintf(stderr, "calitas: --classes and --class-extent require --regions FILE.bed\n"); return 2; }
+  calitas_site_regions_t by_class{0, 0, 0, 0};
+  if (have_extent) {
+    const size_t colon = class_extent.find(':');
+    const std::string from = class_extent.substr(0, colon), to = colon == std::string::npos ? std::string() : class_extent.substr(colon + 1);
+    const auto digits = [](const std::string& t) { return !t.empty() && t.size() <= 6 && t.find_first_not_of("0123456789") == std::string::npos; };
+    if (!digits(from) || !digits(to)) { std::fprintf(stderr, "calitas: --class-extent FROM:TO: two integers, 0-based and half-open in the protospacer, not %s\n", class_extent.c_str()); return 2; }
+    const long a = std::atol(from.c_str()), b = std::atol(to.c_str());
+    if (!(a < b && b <= (long)pg.proto.size())) { std::fprintf(stderr, "calitas: --class-extent FROM:TO: 0 <= FROM < TO <= %zu, the protospacer's length\n", pg.proto.size()); return 2; }
+    by_class.ext_from = (uint8_t)a; by_class.ext_to = (uint8_t)b;
+  }
   calitas_ctx* ctx = nullptr;
   if (calitas_create(device, &ctx) != CALITAS_OK) { std::fprintf(stderr, "calitas: %s\n", calitas_last_error(nullptr)); return 1; }
   auto die = [&](const char* what) { std::fprintf(stderr, "calitas: %s: %s\n", what, calitas_last_error(ctx)); calitas_destroy(ctx); std::exit(1); };
@@ -468,7 +488,17 @@ static int find_guides_main(int argc, char** argv) {
     for (int32_t i = 0; i < n; i++) { const char* nm; uint64_t len; calitas_contig_name(ctx, i, &nm, &len); if (chrom == nm) chrom_index = i; }
     if (chrom_index < 0) { std::fprintf(stderr, "Unknown chromosome: %s\n", chrom.c_str()); calitas_destroy(ctx); return 1; }
   }
+  // --regions: the set goes to the context, the listing keeps the sites of the wanted classes (tools.py find_guides_tool)
+  std::vector<std::string> classes;
+  if (have_regions) {
+    std::string err;
+    if (!set_regions_from_bed(ctx, regions_path, classes, err)) { std::fprintf(stderr, "calitas: %s\n", err.c_str()); calitas_destroy(ctx); return 2; }
+    if (have_classes) {
+      if (!class_mask(classes, class_names, by_class.class_mask, err)) { std::fprintf(stderr, "calitas: %s\n", err.c_str()); calitas_destroy(ctx); return 2; }
+    } else by_class.class_mask = ((1u << classes.size()) - 1u) & ~1u;        // every named class
+  }
   calitas_site_t* sites = nullptr; uint64_t n_sites = 0;
+  uint8_t* site_class = nullptr;       // with --regions: a class per site
   int32_t* activity_q16 = nullptr;     // with --activity: a score per site, from the listing's own call (tools.py find_guides)
   int rc;
   if (have_activity) {
@@ -477,15 +507,38 @@ static int find_guides_main(int argc, char** argv) {
     m.single = act.single.data(); m.pair = act.pair.data(); m.gc = act.gc.data();
     rc = device < 0 ? calitas_find_sites_scored_host(ctx, &g, keep, &m, min_score, chrom_index, start, end, &sites, &activity_q16, &n_sites)
                     : calitas_find_sites_scored(ctx, &g, keep, &m, min_score, chrom_index, start, end, &sites, &activity_q16, &n_sites);
+  } else if (have_regions) {
+    rc = device < 0 ? calitas_find_sites_regions_host(ctx, &g, keep, &by_class, chrom_index, start, end, &sites, &site_class, &n_sites)
+                    : calitas_find_sites_regions(ctx, &g, keep, &by_class, chrom_index, start, end, &sites, &site_class, &n_sites);
   } else {
     rc = device < 0 ? calitas_find_sites_filtered_host(ctx, &g, keep, chrom_index, start, end, &sites, &n_sites)
                     : calitas_find_sites_filtered(ctx, &g, keep, chrom_index, start, end, &sites, &n_sites);
   }
   if (rc != CALITAS_OK) die("finding sites");
+  if (have_regions && have_activity) {
+    // both listings over the same region, joined on (contig, protospacer start, strand) in one walk: both are in that order.  The
+    // scored listing keeps the rows that are in both (a classed site below --min-activity has no partner and goes).
+    calitas_site_t* classed = nullptr; uint64_t n_classed = 0;
+    rc = device < 0 ? calitas_find_sites_regions_host(ctx, &g, keep, &by_class, chrom_index, start, end, &classed, &site_class, &n_classed)
+                    : calitas_find_sites_regions(ctx, &g, keep, &by_class, chrom_index, start, end, &classed, &site_class, &n_classed);
+    if (rc != CALITAS_OK) die("finding sites by regions");
+    const auto less = [](const calitas_site_t& x, const calitas_site_t& y) {
+      if (x.contig_index != y.contig_index) return x.contig_index < y.contig_index;
+      if (x.protospacer_start != y.protospacer_start) return x.protospacer_start < y.protospacer_start;
+      return x.strand == '+' && y.strand == '-';
+    };
+    uint64_t n = 0;
+    for (uint64_t i = 0, j = 0; i < n_classed; i++) {
+      while (j < n_sites && less(sites[j], classed[i])) j++;
+      if (j < n_sites && !less(classed[i], sites[j])) { sites[n] = sites[j]; activity_q16[n] = activity_q16[j]; site_class[n] = site_class[i]; n++; }
+    }
+    n_sites = n;
+    calitas_free(classed);
+  }
   FILE* f = output.empty() ? stdout : std::fopen(output.c_str(), "w");
-  if (!f) { std::fprintf(stderr, "cannot write %s\n", output.c_str()); calitas_free(sites); calitas_free(activity_q16); calitas_destroy(ctx); return 1; }
-  std::fprintf(f, "guide_id\tchromosome\tstart\tend\tstrand\tpam_index\tguide\tpam_sequence%s%s%s", have_activity ? "\tactivity_q16\tactivity" : "", copies ? "\tcopies" : "",
-               have_seed ? "\tseed_copies" : "");
+  if (!f) { std::fprintf(stderr, "cannot write %s\n", output.c_str()); calitas_free(sites); calitas_free(activity_q16); calitas_free(site_class); calitas_destroy(ctx); return 1; }
+  std::fprintf(f, "guide_id\tchromosome\tstart\tend\tstrand\tpam_index\tguide\tpam_sequence%s%s%s%s", have_regions ? "\tclass" : "", have_activity ? "\tactivity_q16\tactivity" : "",
+               copies ? "\tcopies" : "", have_seed ? "\tseed_copies" : "");
   for (long long d = 0; have_near && d <= near_m; d++) std::fprintf(f, "\tcopies_mm%lld", d);
   if (have_near_scores) std::fprintf(f, "\tnear_sum_q32\tnear_max_q32\tnear_specificity");
   std::fprintf(f, "\n");
@@ -576,6 +629,7 @@ static int find_guides_main(int argc, char** argv) {
     const std::string guide = pg.pam5 ? pat_pam + proto : proto + pat_pam;
     std::fprintf(f, "%s:%lld:%c\t%s\t%lld\t%lld\t%c\t%d\t%s\t%s", name, (long long)lo, (char)s.strand, name, (long long)lo, (long long)hi,
                  (char)s.strand, (int)s.pam_index, guide.c_str(), pam.c_str());
+    if (have_regions) std::fprintf(f, "\t%s", classes[site_class[i]].c_str());
     if (have_activity && activity_q16[i] == CALITAS_ACTIVITY_NONE) std::fprintf(f, "\tNA\tNA");
     else if (have_activity) {
       const double x = (double)activity_q16[i] / 65536.0;
@@ -630,7 +684,7 @@ static int find_guides_main(int argc, char** argv) {
     std::fclose(lf);
   }
   std::fprintf(stderr, "calitas: %llu guides\n", (unsigned long long)n_rows);
-  calitas_free(sites); calitas_free(activity_q16); calitas_destroy(ctx);
+  calitas_free(sites); calitas_free(activity_q16); calitas_free(site_class); calitas_destroy(ctx);
   return 0;
 }
 

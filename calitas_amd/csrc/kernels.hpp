@@ -152,12 +152,18 @@ struct SiteRecord {                // = calitas_site_t
 //    / near_m, near_w         | -                  | -                 | -               | M, 0 .. NEAR_MAX_M; bases per piece, 1 .. NEAR_MAX_W: piece p is positions [p w, (p + 1) w)
 //   n_keys, key_len, key_first| -                  | -                 | the distinct keys; K, 1 .. proto_len; 1: the guide's first K bases (a 5' PAM), 0: its last K
 //   ones_index                | -                  | -                 | the index of the key COPIES_EMPTY itself (all T at K = 32), COPIES_NONE: no query | - | -
+// The regions passes (calitas_find_sites_regions: sites_kernel<., ., KEYS_REGIONS>, site_regions.hip) read what find pass 1 and 2 read and
+// two fields more, which the find passes leave alone:
+//   keys / presence           | the presence table (g), whole packed space: byte w0 / SITES_BLOCK_WORDS + seg is the launch's segment seg
+//   table_mask / class_mask   | the classes the call keeps, bit c = class c; a segment whose byte shares no bit with it is dead
 // (a) [2 k]: key k's cursor, 0 at launch; [2 k + 1]: its stretch's length or NEAR_LIST_SKIP; [2 n_keys]: the error flag.  (b) the field's
 //     type is the site listing's.  (c) open addressing, table_mask + 1 slots (a power of two, at most half taken), COPIES_EMPTY: free.
 // (d) near_m + 1 tables of 4^near_w + 1 offsets, one behind the other: the members of piece p's bucket b are near_members[o[b] .. o[b + 1]),
 //     o = near_offsets + p (4^near_w + 1); near score and near list: the model's packed table behind them (near_model_offset).
 // (e) {the key's low plane, its high plane, its index among the distinct keys, 0}: every key once per piece.  (f) near: near_m + 1
 //     counters; near score: near_m + 3, the counters, the sum, the maximum.  Copies and near never run in one launch: they share fields.
+// (g) one byte per SITES_BLOCK_WORDS words: bit c is set when a base of class c (0: of no interval) of the segment's contig lies within
+//     SITE_MAX_FOOT of the segment -- so every site that starts in the segment has a class whose bit is set.
 struct SitesArgs {
   const uint2* planes;
   const uint32_t* mask;
@@ -179,6 +185,7 @@ struct SitesArgs {
   union {
     const uint64_t* keys;
     const uint32_t* near_offsets;
+    const uint8_t* presence;
   };
   union {
     const uint32_t* key_index;
@@ -187,6 +194,7 @@ struct SitesArgs {
   unsigned long long* key_counts;
   union {
     struct { uint32_t table_mask, table_shift; };
+    struct { uint32_t class_mask, class_pad; };
     struct {
       int32_t near_m;
       int32_t near_w;

@@ -2,6 +2,7 @@
 // class a hit: regions_kernel (hits.hip), bin_regions_kernel (binned.hip) and the host stage (post.cpp, hits_regions).
 #pragma once
 #include <algorithm>
+#include <atomic>
 #include <cstddef>
 #include <cstdint>
 #include <string>
@@ -56,13 +57,18 @@ CAL_HD inline uint32_t region_class(const RegionsView& rv, uint32_t c, int64_t s
 
 // The set as the context keeps it on the host: the caller's intervals as they came (calitas_hits_regions and the tests' yardsticks
 // need nothing of them; they are what a later question about the set is answered from) and the flattened tables.
+// Every flattened set has a number of its own (never 0), so that what is derived from a context's set -- the site listing's presence
+// table -- knows when the set is another one.
+inline uint64_t regions_next_serial() { static std::atomic<uint64_t> n{0}; return ++n; }
+
 struct RegionsHost {
   uint32_t n_classes = 0;
+  uint64_t serial = 0;
   std::vector<calitas_region_t> raw;
   std::vector<RegionSeg> seg;
   std::vector<uint32_t> coarse, contig;
   bool empty() const { return n_classes == 0; }
-  void clear() { n_classes = 0; raw.clear(); seg.clear(); coarse.clear(); contig.clear(); }
+  void clear() { n_classes = 0; serial = 0; raw.clear(); seg.clear(); coarse.clear(); contig.clear(); }
   RegionsView view() const { return RegionsView{seg.data(), coarse.data(), contig.data(), n_classes}; }
 };
 
@@ -118,6 +124,7 @@ inline std::string regions_flatten(const std::vector<uint64_t>& lens, Absent abs
   }
   out.contig[2 * lens.size()] = (uint32_t)out.seg.size();
   out.n_classes = n_classes;
+  out.serial = regions_next_serial();
   out.raw.assign(iv, iv + n);
   return "";
 }

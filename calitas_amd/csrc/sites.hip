@@ -442,7 +442,10 @@ CAL_DEV void near_keys(const SitesArgs& a, const LaneSites& s, const uint32_t (&
 // KEYS_NEAR_SCORE: near_keys with the score; the model's packed table stands behind the near kernel's offsets in device memory and is
 // copied to LDS once per workgroup, ahead of the first segment.
 // KEYS_NEAR_LIST: near_keys with the records (calitas_list_near's second run of the pass); the model's table as in KEYS_NEAR_SCORE.
-constexpr int KEYS_NONE = 0, KEYS_EXACT = 1, KEYS_NEAR = 2, KEYS_NEAR_SCORE = 3, KEYS_NEAR_LIST = 4;
+// KEYS_REGIONS (calitas_find_sites_regions; instantiated in site_regions.hip): the two find passes as they are, with one more reason
+// for a segment to be dead -- a.presence, one byte per segment of the packed space, shares no bit with a.class_mask: no site that starts
+// in the segment can have a wanted class.  Such a segment counts 0 and, its turn as the next segment included, loads no plane or mask word.
+constexpr int KEYS_NONE = 0, KEYS_EXACT = 1, KEYS_NEAR = 2, KEYS_NEAR_SCORE = 3, KEYS_NEAR_LIST = 4, KEYS_REGIONS = 5;
 // (a function's own LDS: it belongs to the one instantiation that calls this)
 CAL_DEV uint32_t* near_model_lds() {
   __shared__ uint32_t s_model[NEAR_MODEL_WORDS];
@@ -454,6 +457,7 @@ __global__ __launch_bounds__(SITES_BLOCK_WORDS) void sites_kernel(SitesArgs a) {
   __shared__ uint32_t s_wave[SITES_BLOCK_WORDS / 64];
   const uint32_t tid = threadIdx.x, wave = tid >> 6, wl = tid & 63u;
   const uint32_t seg0 = blockIdx.x * a.segs_per_wg, seg1 = min(seg0 + a.segs_per_wg, a.n_segs);
+  constexpr bool LIST = KEYS == KEYS_NONE || KEYS == KEYS_REGIONS;     // the find passes: counts, offsets, records
   PatConst* pat = (PatConst*)a.pat;
   uint32_t* s_model = nullptr;
   if constexpr (KEYS == KEYS_NEAR_SCORE || KEYS == KEYS_NEAR_LIST) {
@@ -470,10 +474,15 @@ __global__ __launch_bounds__(SITES_BLOCK_WORDS) void sites_kernel(SitesArgs a) {
   auto live = [&](const TileInfo ti) {
     return !(ti.flag == 2u || ti.contig == 0xFFFFFFFFu || (a.chrom_index >= 0 && ti.contig != (uint32_t)a.chrom_index));
   };
+  // KEYS_REGIONS: some wanted class comes near the segment (seg < n_segs: the table covers the packed space)
+  [[maybe_unused]] auto wanted = [&](uint32_t seg) { return (a.presence[a.w0 / SITES_BLOCK_WORDS + seg] & a.class_mask) != 0u; };
   // the words wb - 1 .. wb + 257 of a segment (wb >= one tile: the packed space starts with a tile of padding)
   auto fetch = [&](uint32_t seg) {
     Fetched f{make_uint2(0u, 0u), make_uint2(0u, 0u), 0xFFFFFFFFu, 0xFFFFFFFFu};
     if (seg >= seg1 || !live(tile_of(seg))) return f;
+    if constexpr (KEYS == KEYS_REGIONS) {
+      if (!wanted(seg)) return f;
+    }
     const uint64_t wb = a.w0 + (uint64_t)seg * SITES_BLOCK_WORDS;
     const uint64_t w = wb + tid, h = tid == 0 ? wb - 1 : wb + SITES_BLOCK_WORDS - 1 + tid;
     if (w < a.n_words) { f.pl = a.planes[w]; f.ex = a.mask[w]; }
@@ -492,9 +501,16 @@ __global__ __launch_bounds__(SITES_BLOCK_WORDS) void sites_kernel(SitesArgs a) {
   for (uint32_t seg = seg0; seg < seg1; seg++) {
     const TileInfo ti = tile_of(seg);
     if (!live(ti)) {
-      if (!WRITE && KEYS == KEYS_NONE && tid == 0) a.wg_count[seg] = 0u;
+      if (!WRITE && LIST && tid == 0) a.wg_count[seg] = 0u;
       f = fetch(seg + 1);
       continue;
+    }
+    if constexpr (KEYS == KEYS_REGIONS) {
+      if (!wanted(seg)) {
+        if (!WRITE && tid == 0) a.wg_count[seg] = 0u;
+        f = fetch(seg + 1);
+        continue;
+      }
     }
     s_lo[tid + 1] = f.pl.x; s_hi[tid + 1] = f.pl.y; s_ex[tid + 1] = f.ex;
     if (tid < 3u) {
@@ -513,7 +529,7 @@ __global__ __launch_bounds__(SITES_BLOCK_WORDS) void sites_kernel(SitesArgs a) {
     const int64_t r_end = (int64_t)((a.end == 0 || a.end > ci.len) ? ci.len : a.end);
     const int64_t base0 = (int64_t)((wb + tid) * 32u) - (int64_t)ci.gbase;
     const LaneSites s = match_word<FILTER>(pat, c_lo, c_hi, c_ex, base0, r_start, r_end);
-    if constexpr (KEYS != KEYS_NONE) {
+    if constexpr (!LIST) {
       if constexpr (KEYS == KEYS_NEAR_LIST) near_keys<NEAR_LIST>(a, s, c_lo, c_hi, pat->proto_len, s_model, ti.contig, base0, pat->pamless != 0);
       else if constexpr (KEYS == KEYS_NEAR_SCORE) near_keys<NEAR_SCORE>(a, s, c_lo, c_hi, pat->proto_len, s_model);
       else if constexpr (KEYS == KEYS_NEAR) near_keys<NEAR_COUNT>(a, s, c_lo, c_hi, pat->proto_len, nullptr);
@@ -564,7 +580,7 @@ __global__ __launch_bounds__(SITES_BLOCK_WORDS) void sites_kernel(SitesArgs a) {
       }
     }
   }
-  if (!WRITE && KEYS == KEYS_NONE && tid == 0) flush_totals();
+  if (!WRITE && LIST && tid == 0) flush_totals();
 }
 
 // near_list.hip takes everything above -- for its one instantiation, KEYS_NEAR_LIST -- by including this file with

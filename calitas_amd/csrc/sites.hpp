@@ -23,6 +23,9 @@ inline uint64_t region_end(uint64_t len, uint64_t end) { return (end == 0 || end
 // filter != nullptr: none but the sites that pass it, in `out` and in *kernel_has alike (the kernel filters what it writes).
 void host_sites(const PackedRef& ref, const SitePatterns& pat, const calitas_site_filter_t* filter, int contig, int64_t p_lo, int64_t p_hi,
                 int64_t r_start, int64_t r_end, std::vector<calitas_site_t>& out, std::vector<calitas_site_t>* kernel_has);
+// The presence table of the context's region set (calitas_find_sites_regions), made when the set or the reference is another one than
+// the table's; returns an error text or "".  Needs no device.
+std::string site_presence(calitas_ctx* c, const std::vector<uint8_t>** out);
 struct SitesWork;                 // device scratch of a context, kept between calls
 void sites_destroy(SitesWork* w);
 
@@ -65,3 +68,11 @@ int calitas_find_sites_scored_host_impl(const calitas_ctx* ctx, const calitas_gu
 int calitas_find_sites_scored_impl(calitas_ctx* ctx, const calitas_guide_t* pattern, const calitas_site_filter_t* filter, const calitas_activity_model_t* model,
                                    int32_t min_score, int32_t chrom_index, uint64_t start, uint64_t end, calitas_site_t** sites, int32_t** scores,
                                    uint64_t* n_sites);
+// the records of calitas_find_sites_filtered whose class under opt has its bit in opt->class_mask, and the classes; listing false: the
+// numbers alone (per_class_strand may be null)
+int calitas_find_sites_regions_host_impl(const calitas_ctx* ctx, const calitas_guide_t* pattern, const calitas_site_filter_t* filter,
+                                         const calitas_site_regions_t* opt, int32_t chrom_index, uint64_t start, uint64_t end, bool listing,
+                                         calitas_site_t** sites, uint8_t** classes, uint64_t* per_class_strand, uint64_t* n_sites);
+int calitas_find_sites_regions_impl(calitas_ctx* ctx, const calitas_guide_t* pattern, const calitas_site_filter_t* filter, const calitas_site_regions_t* opt,
+                                    int32_t chrom_index, uint64_t start, uint64_t end, bool listing, calitas_site_t** sites, uint8_t** classes,
+                                    uint64_t* per_class_strand, uint64_t* n_sites);

@@ -38,6 +38,7 @@ constexpr Switch kSwitches[] = {
   {"CALITAS_CHUNKS", "k | a:b:c", "T: contig ranges of a chunked calitas_search_hits (default 5.8:2.9:1.3 from 2 Gb, 5:3 from 600 Mb, 3:2 from 256 Mb)"},
   {"CALITAS_CHUNK", "64..512", "T: bases per scan lane chunk (set_reference; default by genome size)"},
   {"CALITAS_SITES_SEGS", "1..16", "T: segments of 256 words a workgroup of sites_kernel takes (default: segments / 2048, at least 1, at most 16)"},
+  {"CALITAS_SITES_SKIP", "0", "F: calitas_find_sites_regions matches every segment instead of skipping those no wanted class comes near (the same bytes, the slow way)"},
   {"CALITAS_LANE_SETUP", "0", "F: separate stream commands instead of the one-launch lane setup"},
   {"CALITAS_ALIGN_LPJ", "32", "F: two jobs of 32 lanes per aligner wave even for guides of up to 20 rows"},
   {"CALITAS_ALIGN_PACK", "0", "F: one job per lane group in the aligner (align_kernel) where two would fit (align_pk_kernel: cells in sixteen bits)"},

@@ -322,10 +322,11 @@ class GuideSite:
     """One site of Context.find_sites as a guide: `guide` is the `-i` string a search takes -- the protospacer as it reads on the site's
     strand, upper case, with the PATTERN's matched PAM in lower case behind it (in front of it for a 5' PAM) -- and pam_sequence the
     genomic PAM bases on that strand; [start, end) is the footprint (protospacer + PAM), 0-based half-open."""
-    __slots__ = ("chromosome", "start", "end", "strand", "pam_index", "guide", "pam_sequence", "protospacer_start", "activity_q16")
+    __slots__ = ("chromosome", "start", "end", "strand", "pam_index", "guide", "pam_sequence", "protospacer_start", "activity_q16", "region_class")
 
     def __init__(self, *v):
         self.activity_q16 = None                       # (find_guides with a model: the site's score, ACTIVITY_NONE when it has none)
+        self.region_class = None                       # (find_guides with classes or an extent: the site's class index under the context's regions)
         for k, x in zip(self.__slots__, v):
             setattr(self, k, x)
 
@@ -337,14 +338,36 @@ class GuideSite:
         return [self.guide_id, self.chromosome, self.start, self.end, self.strand, self.pam_index, self.guide, self.pam_sequence]
 
 
-def find_guides(ctx, pattern, chrom=None, start=0, end=None, host=False, filter=None, activity=None, min_activity=None):
+def find_guides(ctx, pattern, chrom=None, start=0, end=None, host=False, filter=None, activity=None, min_activity=None, classes=None, extent=None,
+                by_regions=False):
     """Context.find_sites turned into guides: a list of GuideSite in the sites' order.  pattern: a Guide or its `-i` string; filter: a
     SiteFilter -- only the sites that pass it come back at all.  activity: an ActivityModel -- every GuideSite carries its site's
     on-target score as activity_q16 (Context.find_sites_scored; ACTIVITY_NONE where the site has none); min_activity: a Q16 integer,
-    only the sites that score at least that much come back."""
+    only the sites that score at least that much come back.  classes, extent (or by_regions=True for their defaults): only the sites
+    whose class under the context's regions is one of `classes` come back (Context.find_sites_regions), each with its class index as
+    region_class.  Together with activity both listings are made over the same region and joined on (contig, protospacer start,
+    strand) in one walk over the two: both are in that order."""
     if not isinstance(pattern, Guide):
         pattern = Guide(pattern)
-    if activity is None:
+    cls_of = None
+    if classes is not None or extent is not None or by_regions:
+        if activity is None and min_activity is not None:
+            raise ValueError("min_activity needs an activity model")
+        sites, cls_of = ctx.find_sites_regions(pattern, classes=classes, extent=extent, filter=filter, chrom=chrom, start=start, end=end, host=host)
+        q16 = None
+        if activity is not None:
+            scored, all_q16 = ctx.find_sites_scored(pattern, activity, min_score=min_activity, filter=filter, chrom=chrom, start=start, end=end, host=host)
+            keep, q16, j = [], [], 0
+            key = lambda r: (int(r["contig_index"]), int(r["protospacer_start"]), r["strand"] == b"-")
+            for i in range(len(sites)):                # the merge walk: a classed site below the threshold has no partner and goes
+                k = key(sites[i])
+                while j < len(scored) and key(scored[j]) < k:
+                    j += 1
+                if j < len(scored) and key(scored[j]) == k:
+                    keep.append(i)
+                    q16.append(int(all_q16[j]))
+            sites, cls_of = sites[keep], cls_of[keep]
+    elif activity is None:
         if min_activity is not None:
             raise ValueError("min_activity needs an activity model")
         sites, q16 = ctx.find_sites(pattern, chrom, start, end, host=host, filter=filter), None
@@ -375,6 +398,8 @@ def find_guides(ctx, pattern, chrom=None, start=0, end=None, host=False, filter=
                              pam_seq, ps))
         if q16 is not None:
             out[-1].activity_q16 = int(q16[len(out) - 1])
+        if cls_of is not None:
+            out[-1].region_class = int(cls_of[len(out) - 1])
     return out
 
 
@@ -511,7 +536,7 @@ def activity_q16_of_flag(text):
     return int(math.floor(float(text) * 65536.0 + 0.5))
 
 
-def guides_tsv(rows, tables=None, scores=None, copies=None, seed_copies=None, near=None, near_scores=None, activity=None):
+def guides_tsv(rows, tables=None, scores=None, copies=None, seed_copies=None, near=None, near_scores=None, activity=None, class_names=None):
     """The FindGuides table: GUIDE_COLUMNS, one row per GuideSite; with tables (guide_counts) also hits -- the table's sum -- and
     hits_mm0 .. hits_mmE, the hits per number of protospacer mismatches, summed over strands, gaps and PAM mismatches; with scores
     (guide_scores) those columns come from the same pass's tables and perfect and specificity (%.6f) follow them.  copies,
@@ -520,9 +545,12 @@ def guides_tsv(rows, tables=None, scores=None, copies=None, seed_copies=None, ne
     near_scores: a NearScores aligned with rows (guide_near_scores) -- near_sum_q32, near_max_q32 and near_specificity (%.6f) directly
     behind copies_mmM.  activity: the ActivityModel the rows were scored with (find_guides) -- activity_q16, the score as it is, and
     activity, the number its link makes of it (activity_value, %.6f), directly behind pam_sequence and before all of the above; NA in
-    both for a site without a score."""
+    both for a site without a score.  class_names: the names of the regions' classes ("elsewhere" first) -- the column class, the name
+    of the row's region_class (find_guides with classes), directly behind pam_sequence and ahead of activity_q16."""
     from .aligner import ACTIVITY_NONE, activity_value
     header = list(GUIDE_COLUMNS)
+    if class_names is not None:
+        header.append("class")
     if activity is not None:
         header += ["activity_q16", "activity"]
     if copies is not None:
@@ -546,6 +574,8 @@ def guides_tsv(rows, tables=None, scores=None, copies=None, seed_copies=None, ne
     lines = ["\t".join(header)]
     for i, r in enumerate(rows):
         f = [str(x) for x in r.row()]
+        if class_names is not None:
+            f.append(class_names[r.region_class])
         if activity is not None:
             unscored = r.activity_q16 is None or r.activity_q16 == ACTIVITY_NONE
             f += ["NA", "NA"] if unscored else [str(r.activity_q16), "%.6f" % activity_value(r.activity_q16, activity)]
@@ -599,7 +629,7 @@ def site_filter_of_flags(L, gc_min=None, gc_max=None, max_run=None, avoid=()):
 def find_guides_tool(ref, pattern, auxiliary_pams=(), chrom=None, start=0, end=None, output=None, counts=False, device=0, scores=None,
                      gc_min=None, gc_max=None, max_run=None, avoid=(), copies=False, seed_copies=None, max_copies=None, max_seed_copies=None,
                      near_copies=None, max_near_copies=None, near_scores=None, near_list=None, near_list_limit=None, activity=None, min_activity=None,
-                     **search):
+                     regions=None, classes=None, class_extent=None, **search):
     """`python -m calitas_amd FindGuides`: the guides of a region as a TSV (guides_tsv); counts=True: every distinct guide also goes
     through the off-target search with the SearchReference flags in `search` (make_params names); scores=ScoreModel (or its file):
     through search_scores_batch instead, which adds perfect and specificity.  gc_min, gc_max, max_run, avoid: the site filter's flags
@@ -616,7 +646,19 @@ def find_guides_tool(ref, pattern, auxiliary_pams=(), chrom=None, start=0, end=N
     activity=ActivityModel (or its file; the model's length is the protospacer's): the columns activity_q16 and activity, every site
     scored in the listing's own call; min_activity=X (needs activity): a decimal on the LINEAR score (under link logistic a probability
     p is X = ln(p / (1 - p))) -- the rows that score less, and those without a score, are dropped before any of the flags above looks
-    at anything, the kept rows keep their guide_ids.  These eleven work with device -1 through the host twin.  Returns the text."""
+    at anything, the kept rows keep their guide_ids.  regions=FILE.bed (the parser and rules of SearchReference --regions): the column
+    class, and only the sites of the named classes; classes="name,..." (needs regions) the classes to keep instead, "elsewhere" among
+    them if wanted; class_extent="FROM:TO" (needs regions) the positions of the protospacer as the guide reads, 0-based and half-open,
+    that are classed instead of all of it.  The dropped rows are gone before any of the flags above looks at anything, the kept rows
+    keep their guide_ids.  These fourteen work with device -1 through the host twin.  Returns the text."""
+    if regions is None and (classes is not None or class_extent is not None):
+        raise ValueError("--classes and --class-extent require --regions FILE.bed")
+    extent = None
+    if class_extent is not None:
+        a, sep, b = str(class_extent).partition(":")
+        if not (sep and a.isdigit() and b.isdigit()):
+            raise ValueError("--class-extent FROM:TO: two integers, 0-based and half-open in the protospacer, not %s" % class_extent)
+        extent = (int(a), int(b))
     if (counts or scores is not None) and device < 0:
         raise ValueError("--counts and --scores search on the GPU: they cannot run with --device -1")
     if isinstance(scores, str):
@@ -664,7 +706,20 @@ def find_guides_tool(ref, pattern, auxiliary_pams=(), chrom=None, start=0, end=N
     ctx = Context(device)
     try:
         ctx.set_reference_fasta(ref)
-        rows = find_guides(ctx, pat, chrom, start, end, host=device < 0, filter=keep, activity=activity, min_activity=floor)
+        class_names = None
+        if regions is not None:
+            from .aligner import Regions
+            if extent is not None and not 0 <= extent[0] < extent[1] <= pat.protospacer_length:
+                raise ValueError("--class-extent FROM:TO: 0 <= FROM < TO <= %d, the protospacer's length" % pat.protospacer_length)
+            reg = Regions.read_bed(regions, dict(zip(ctx.contig_names, ctx.contig_lengths)))
+            if classes is not None:
+                reg.mask_of(classes)                   # (an unknown name is refused here, by name)
+            if not reg.intervals:
+                raise ValueError("--regions: no interval lies on a chromosome of the reference")
+            ctx.set_regions(reg)
+            class_names = reg.classes
+        rows = find_guides(ctx, pat, chrom, start, end, host=device < 0, filter=keep, activity=activity, min_activity=floor, classes=classes, extent=extent,
+                           by_regions=regions is not None)
         n_copies = guide_copies(ctx, pat, rows, host=device < 0) if copies or max_copies is not None else None
         n_seed = guide_copies(ctx, pat, rows, key_length=int(seed_copies), host=device < 0) if seed_copies is not None else None
         scored_near = guide_near_scores(ctx, pat, rows, int(near_copies), near_scores, host=device < 0) if near_scores is not None else None
@@ -686,7 +741,7 @@ def find_guides_tool(ref, pattern, auxiliary_pams=(), chrom=None, start=0, end=N
             scored_near = NearScores(n_near, scored_near.sum_q32[kept], scored_near.max_q32[kept])
         tables = guide_counts(ctx, [r.guide for r in rows], make_params(**search)) if counts and scores is None else None
         scored = guide_scores(ctx, [r.guide for r in rows], make_params(**search), scores) if scores is not None else None
-        text = guides_tsv(rows, tables, scored, copies=n_copies, seed_copies=n_seed, near=n_near, near_scores=scored_near, activity=activity)
+        text = guides_tsv(rows, tables, scored, copies=n_copies, seed_copies=n_seed, near=n_near, near_scores=scored_near, activity=activity, class_names=class_names)
         if near_list is not None:
             listing = guide_near_list(ctx, pat, rows, int(near_copies), near_scores, limit=1000 if near_list_limit is None else int(near_list_limit), host=device < 0)
             with open(near_list, "w") as f:

@@ -630,6 +630,49 @@ int calitas_search_regions(calitas_ctx* ctx, const calitas_guide_t* guide, const
 int calitas_search_regions_batch(calitas_ctx* ctx, int32_t n_guides, const calitas_guide_t* guides, const calitas_params_t* params,
                                  const calitas_score_model_t* model, uint32_t k, uint32_t list_mask, calitas_regions_t** out);
 
+/* Guide sites by annotated regions: which of a pattern's sites lie where the caller wants to cut.  No reference counterpart.
+ * THE CLASS OF A SITE.  Positions ext_from .. ext_to - 1 of the protospacer are counted as the guide reads it, 0 its 5' base,
+ * 0 <= ext_from < ext_to <= L; {0, 0} means {0, L}, the whole protospacer.  With p the record's protospacer_start they are the forward
+ * bases [p + ext_from, p + ext_to) on '+' and [p + L - ext_to, p + L - ext_from) on '-'.  The site's class is the smallest cls among
+ * the intervals of its contig that overlap that extent, 0 when there is none: the rule calitas_search_regions classes a hit by.
+ * {16, 18} on a 20-mer with a 3' PAM is the two bases beside the Cas9 cut, {k, k + 1} one base; the PAM is never part of the extent. */
+typedef struct {
+  uint32_t class_mask;         /* bit c: keep the sites of class c (0 = elsewhere).  Bits >= n_classes are ignored. */
+  uint8_t ext_from, ext_to;    /* the part of the protospacer that is classed; {0, 0} means {0, L} */
+  uint16_t reserved;           /* 0 */
+} calitas_site_regions_t;
+/* The records of calitas_find_sites_filtered(pattern, filter, chrom_index, start, end) whose class has its bit in opt->class_mask, in
+ * that call's order and with its bytes; classes[i] is the class of sites[i].  sites == NULL && classes == NULL: *n_sites only.  Each
+ * block takes one calitas_free.  With every bit below n_classes set, sites is the filtered listing byte for byte; masks that partition
+ * the classes partition the records.
+ * On the device the site kernel's two passes skip every segment of 8192 bases that no wanted class comes near -- a table of one byte
+ * per segment, made from the flattened set at the first such call and kept on the context, decides before a word is loaded -- then one
+ * lane per record classes its extent, and a second kernel compacts records and classes in order (ranks from ballots: no sort, no
+ * returning atomic) before the one copy-back.  Sites beside a U are classed on the host, as calitas_find_sites finds them there.
+ * Errors, in this order: CALITAS_ENODEV on a host-only context (the device calls); what calitas_find_sites_filtered refuses;
+ * CALITAS_EINVAL, with a message that names the field, for a NULL opt, a context without regions, a class_mask without a bit below
+ * n_classes, ext_from >= ext_to or ext_to > L other than {0, 0}, reserved != 0. */
+int calitas_find_sites_regions(calitas_ctx* ctx, const calitas_guide_t* pattern, const calitas_site_filter_t* filter /* may be NULL */,
+                               const calitas_site_regions_t* opt, int32_t chrom_index, uint64_t start, uint64_t end, calitas_site_t** sites,
+                               uint8_t** classes, uint64_t* n_sites);
+/* The same chain without the records: *n_sites and, when per_class_strand is not NULL, the kept sites per class and strand
+ * ([n_classes][2], '+' first; the cells of classes outside the mask are 0, and the cells sum to *n_sites). */
+int calitas_count_sites_regions(calitas_ctx* ctx, const calitas_guide_t* pattern, const calitas_site_filter_t* filter, const calitas_site_regions_t* opt,
+                                int32_t chrom_index, uint64_t start, uint64_t end, uint64_t* per_class_strand, uint64_t* n_sites);
+/* The host twins: calitas_find_sites_filtered_host's records, each classed through the host's flattened set; also on a host-only
+ * context. */
+int calitas_find_sites_regions_host(const calitas_ctx* ctx, const calitas_guide_t* pattern, const calitas_site_filter_t* filter,
+                                    const calitas_site_regions_t* opt, int32_t chrom_index, uint64_t start, uint64_t end, calitas_site_t** sites,
+                                    uint8_t** classes, uint64_t* n_sites);
+int calitas_count_sites_regions_host(const calitas_ctx* ctx, const calitas_guide_t* pattern, const calitas_site_filter_t* filter,
+                                     const calitas_site_regions_t* opt, int32_t chrom_index, uint64_t start, uint64_t end, uint64_t* per_class_strand,
+                                     uint64_t* n_sites);
+/* (test hook) A copy of the presence table the regions listing skips by, made if need be; needs no device.  bytes[i] belongs to the
+ * 256 words of the packed space from word *first_word + 256 i on (calitas_contig_packed_base gives a contig's first base there): bit c
+ * is set when a base of class c of the segment's contig -- bit 0: a base of no interval -- lies within 48 bases (the longest footprint)
+ * of the segment.  *bytes is one block for calitas_free.  CALITAS_EINVAL when the context has no regions. */
+int calitas_site_presence(const calitas_ctx* ctx, uint8_t** bytes, uint64_t* n, uint64_t* first_word);
+
 /* SequentialGuideAligner.align on explicit (guide, target) pairs -- the per-task call of PairwiseAlignSequences
  * (PairwiseAlignSequences.scala:64 -> alignBest, SequentialGuideAligner.scala:333-345) and AlignToReference
  * (AlignToReference.scala:114-135 -> alignToRef / alignToRefBest, SequentialGuideAligner.scala:359-418).  Task t aligns
