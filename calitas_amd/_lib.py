@@ -116,6 +116,18 @@ class SiteRegionsT(ctypes.Structure):
     _fields_ = [("class_mask", ctypes.c_uint32), ("ext_from", ctypes.c_uint8), ("ext_to", ctypes.c_uint8), ("reserved", ctypes.c_uint16)]
 
 
+class SitePairsT(ctypes.Structure):
+    _fields_ = [("min_distance", ctypes.c_int32), ("max_distance", ctypes.c_int32), ("cut_offset", ctypes.c_uint8), ("orientations", ctypes.c_uint8),
+                ("reserved", ctypes.c_uint8 * 2)]
+
+
+class SitePairT(ctypes.Structure):
+    _fields_ = [("left", ctypes.c_uint32), ("right", ctypes.c_uint32), ("distance", ctypes.c_int32), ("orientation", ctypes.c_uint8),
+                ("reserved", ctypes.c_uint8 * 3)]
+
+
+PAIR_MAX_DISTANCE = 65535
+assert ctypes.sizeof(SitePairsT) == 12 and ctypes.sizeof(SitePairT) == 16
 TOP_MAX = 256
 NEAR_LIST_MAX = 4096
 ACTIVITY_NONE = -(1 << 31)
@@ -140,7 +152,8 @@ SYMBOLS = ["calitas_create", "calitas_destroy", "calitas_last_error", "calitas_f
            "calitas_score_near", "calitas_score_near_host", "calitas_list_near", "calitas_list_near_host",
            "calitas_find_sites_scored", "calitas_find_sites_scored_host",
            "calitas_find_sites_regions", "calitas_count_sites_regions", "calitas_find_sites_regions_host", "calitas_count_sites_regions_host",
-           "calitas_site_presence"]
+           "calitas_site_presence",
+           "calitas_find_site_pairs", "calitas_count_site_pairs", "calitas_find_site_pairs_host", "calitas_count_site_pairs_host"]
 
 if not os.path.exists(LIB_PATH):
     raise ImportError("%s is missing: build it with `make -C calitas_amd/csrc` (hipcc, gfx950). "
@@ -239,6 +252,15 @@ if hasattr(lib, "calitas_find_sites_regions"):     # (an older build behind CALI
     lib.calitas_count_sites_regions_host.argtypes = lib.calitas_count_sites_regions.argtypes
     lib.calitas_site_presence.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.POINTER(ctypes.c_uint8)), ctypes.POINTER(ctypes.c_uint64),
                                           ctypes.POINTER(ctypes.c_uint64)]
+if hasattr(lib, "calitas_find_site_pairs"):        # (an older build behind CALITAS_LIB_PATH, for A/B runs, does not have it)
+    lib.calitas_find_site_pairs.argtypes = [ctypes.c_void_p, ctypes.POINTER(GuideT), ctypes.POINTER(SiteFilterT), ctypes.POINTER(SitePairsT), ctypes.c_int32,
+                                            ctypes.c_uint64, ctypes.c_uint64, ctypes.POINTER(ctypes.POINTER(SiteT)), ctypes.POINTER(ctypes.c_uint64),
+                                            ctypes.POINTER(ctypes.POINTER(SitePairT)), ctypes.POINTER(ctypes.c_uint64)]
+    lib.calitas_find_site_pairs_host.argtypes = lib.calitas_find_site_pairs.argtypes
+    lib.calitas_count_site_pairs.argtypes = [ctypes.c_void_p, ctypes.POINTER(GuideT), ctypes.POINTER(SiteFilterT), ctypes.POINTER(SitePairsT), ctypes.c_int32,
+                                             ctypes.c_uint64, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64),
+                                             ctypes.POINTER(ctypes.c_uint64)]
+    lib.calitas_count_site_pairs_host.argtypes = lib.calitas_count_site_pairs.argtypes
 lib.calitas_search_scores.argtypes = [ctypes.c_void_p, ctypes.POINTER(GuideT), ctypes.POINTER(ParamsT), ctypes.POINTER(ScoreModelT),
                                       ctypes.POINTER(ctypes.POINTER(ScoresT))]
 lib.calitas_search_scores_batch.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.POINTER(GuideT), ctypes.POINTER(ParamsT),

@@ -753,6 +753,44 @@ class Context:
         assert int(table.sum()) == n.value
         return table
 
+    def find_site_pairs(self, pattern, spec, filter=None, chrom=None, start=0, end=None, host=False):
+        """calitas_find_site_pairs: (sites, pairs) -- the records of find_sites(pattern, filter=filter) and, as a numpy structured array
+        with the fields of calitas_site_pair_t (SITE_PAIR_DTYPE), the pairs of them that `spec` (a SitePairs) admits: left and right
+        index `sites`, distance is the right cut minus the left one, orientation (left is '-') + 2 (right is '-').  Ordered by the
+        smaller and then the larger of the two indices.  site_pairs_of is the contract as a plain double loop.  host=True: the host
+        twin (calitas_find_site_pairs_host), also on a host-only context."""
+        pattern, index, start, end = self._site_region(pattern, chrom, start, end)
+        opt = spec.to_c(pattern)
+        g = pattern.to_c()
+        f = filter.to_c() if filter is not None else None
+        out, n = ctypes.POINTER(SiteT)(), ctypes.c_uint64()
+        out_pairs, n_pairs = ctypes.POINTER(_lib.SitePairT)(), ctypes.c_uint64()
+        fn = lib.calitas_find_site_pairs_host if host else lib.calitas_find_site_pairs
+        rc = fn(self._h, ctypes.byref(g), ctypes.byref(f) if f is not None else None, ctypes.byref(opt), index, start, end, ctypes.byref(out),
+                ctypes.byref(n), ctypes.byref(out_pairs), ctypes.byref(n_pairs))
+        _lib.check(self._h, rc)
+        try:
+            pairs = self._take_records(out_pairs, n_pairs.value, _lib.SitePairT, SITE_PAIR_DTYPE)
+        finally:
+            sites = self._take_records(out, n.value, SiteT, SITE_DTYPE)
+        return sites, pairs
+
+    def count_site_pairs(self, pattern, spec, filter=None, chrom=None, start=0, end=None, host=False):
+        """calitas_count_site_pairs: (n_sites, n_pairs, per_orientation) of what find_site_pairs would return, per_orientation a numpy
+        uint64 array of the four orientations' pairs ("++", "-+", "+-", "--").  Nothing but the counters is copied back."""
+        import numpy as np
+        pattern, index, start, end = self._site_region(pattern, chrom, start, end)
+        opt = spec.to_c(pattern)
+        g = pattern.to_c()
+        f = filter.to_c() if filter is not None else None
+        by = np.zeros(4, dtype=np.uint64)
+        n, n_pairs = ctypes.c_uint64(), ctypes.c_uint64()
+        fn = lib.calitas_count_site_pairs_host if host else lib.calitas_count_site_pairs
+        rc = fn(self._h, ctypes.byref(g), ctypes.byref(f) if f is not None else None, ctypes.byref(opt), index, start, end, ctypes.byref(n),
+                ctypes.byref(n_pairs), by.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)))
+        _lib.check(self._h, rc)
+        return n.value, n_pairs.value, by
+
     def site_presence(self):
         """(test hook) calitas_site_presence: (bytes, first_word) -- the table the regions listing skips segments by, a uint8 array with
         one byte per 256 words (8192 bases) of the packed space from word first_word on; bit c: class c comes near the segment."""
@@ -1787,6 +1825,115 @@ def site_class_of(site, regions, extent=None):
         if c == chrom and s < hi and e > lo and (best == 0 or k < best):
             best = k
     return best
+
+
+# calitas_site_pair_t
+SITE_PAIR_DTYPE = [("left", "<u4"), ("right", "<u4"), ("distance", "<i4"), ("orientation", "u1"), ("reserved", "u1", (3,))]
+PAIR_CODES = ("++", "-+", "+-", "--")          # orientation o: (left is '-') + 2 (right is '-')
+PAIR_MAX_DISTANCE = _lib.PAIR_MAX_DISTANCE
+
+
+class SitePairs:
+    """calitas_site_pairs_t: which two sites of a pattern make a pair.  min_distance .. max_distance: the bounds on the distance of
+    their cuts, 0 .. PAIR_MAX_DISTANCE.  cut_offset: where a site is cut, a position 0 .. L in the protospacer as the guide reads
+    it; None: L - 3, the Cas9 cut, which needs a 3' PAM.  orientations: "out" (the PAMs face outwards: "-+" with a 3' PAM, "+-" with a
+    5' PAM -- the paired-nickase layout), "in" (the other of the two), "same" ("++" and "--"), "any", or a list (or comma-separated
+    string) of the codes "++", "-+", "+-", "--": the left member's strand, then the right one's.  The names need a pattern with a PAM
+    and are translated with its pam_is_five_prime; a PAM-less pattern takes codes only."""
+
+    def __init__(self, min_distance, max_distance, cut_offset=None, orientations="out"):
+        self.min_distance, self.max_distance = int(min_distance), int(max_distance)
+        self.cut_offset = None if cut_offset is None else int(cut_offset)
+        if isinstance(orientations, str):
+            orientations = [o for o in orientations.split(",") if o]
+        self.orientations = [str(o) for o in orientations]
+        if not self.orientations:
+            raise ValueError("orientations is empty: out, in, same, any, or codes among ++ -+ +- --")
+        for o in self.orientations:
+            if o not in ("out", "in", "same", "any") and o not in PAIR_CODES:
+                raise ValueError("orientation %r: out, in, same, any, or a code among ++ -+ +- --" % o)
+
+    def cut_of(self, pattern):
+        """cut_offset, None resolved on the pattern (a Guide)."""
+        if self.cut_offset is not None:
+            return self.cut_offset
+        if not pattern.pam_is_three_prime:
+            raise ValueError("cut_offset is needed: the default, L - 3, is the Cas9 cut of a pattern with a 3' PAM")
+        return pattern.protospacer_length - 3
+
+    def mask_of(self, pattern):
+        """The orientations as the mask of calitas_site_pairs_t, bit o = PAIR_CODES[o]."""
+        mask = 0
+        for o in self.orientations:
+            if o in PAIR_CODES:
+                mask |= 1 << PAIR_CODES.index(o)
+            elif not pattern.pams:
+                raise ValueError("orientation %r needs a PAM: a pattern without one takes the codes ++ -+ +- --" % o)
+            elif o == "any":
+                mask |= 15
+            elif o == "same":
+                mask |= 9
+            else:
+                mask |= 2 if (o == "out") == pattern.pam_is_three_prime else 4
+        return mask
+
+    def name_of(self, orientation, pattern):
+        """What the pairs file calls an orientation code 0 .. 3: out / in / same, or the code itself for a PAM-less pattern."""
+        if not pattern.pams:
+            return PAIR_CODES[orientation]
+        if orientation in (0, 3):
+            return "same"
+        return "out" if (orientation == 1) == pattern.pam_is_three_prime else "in"
+
+    def to_c(self, pattern):
+        cut = self.cut_of(pattern)
+        if not 0 <= cut < 256:
+            raise ValueError("cut_offset %d: a position of the protospacer, 0 .. its length" % cut)
+        if not (-(1 << 31) <= self.min_distance < 1 << 31 and -(1 << 31) <= self.max_distance < 1 << 31):
+            raise ValueError("the distances of a pair are 0 .. %d" % PAIR_MAX_DISTANCE)
+        t = _lib.SitePairsT()
+        t.min_distance, t.max_distance, t.cut_offset, t.orientations = self.min_distance, self.max_distance, cut, self.mask_of(pattern)
+        return t
+
+    def __repr__(self):
+        return "SitePairs(%d, %d, cut_offset=%r, orientations=%r)" % (self.min_distance, self.max_distance, self.cut_offset, ",".join(self.orientations))
+
+
+def site_cut_of(protospacer_start, strand, L, cut_offset):
+    """Where a site is cut: protospacer_start + c on '+', protospacer_start + L - c on '-'."""
+    if isinstance(strand, bytes):
+        strand = strand.decode()
+    return int(protospacer_start) + (L - cut_offset if strand == "-" else cut_offset)
+
+
+def site_pairs_of(sites, spec, pattern):
+    """The contract of find_site_pairs as a plain double loop.  sites: the listing in its order -- records of SITE_DTYPE, or
+    (contig, protospacer_start, strand) tuples; spec: a SitePairs; pattern: the Guide (or its string) the sites are of.  Returns the
+    pairs as (left, right, distance, orientation) tuples in (i, j) order: two different sites i < j of one contig whose cuts are
+    min_distance .. max_distance apart and whose orientation is wanted; the left member has the smaller cut, at equal cuts the
+    smaller index."""
+    if not isinstance(pattern, Guide):
+        pattern = Guide(pattern)
+    L, c, mask = pattern.protospacer_length, spec.cut_of(pattern), spec.mask_of(pattern)
+    flat = []
+    for s in sites:
+        contig, p, strand = (s["contig_index"], s["protospacer_start"], s["strand"]) if hasattr(s, "dtype") else (s[0], s[1], s[2])
+        if isinstance(strand, bytes):
+            strand = strand.decode()
+        flat.append((int(contig) if not isinstance(contig, str) else contig, site_cut_of(p, strand, L, c), strand == "-"))
+    pairs = []
+    for i in range(len(flat)):
+        for j in range(i + 1, len(flat)):
+            if flat[i][0] != flat[j][0]:
+                continue
+            d = flat[j][1] - flat[i][1]
+            left, right = (j, i) if d < 0 else (i, j)
+            if not spec.min_distance <= abs(d) <= spec.max_distance:
+                continue
+            o = (1 if flat[left][2] else 0) + (2 if flat[right][2] else 0)
+            if (mask >> o) & 1:
+                pairs.append((left, right, abs(d), o))
+    return pairs
 
 
 def regions_of_rows(rows, model, regions, k, list_mask=None, shape=None):

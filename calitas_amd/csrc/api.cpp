@@ -1379,4 +1379,40 @@ int calitas_site_presence(const calitas_ctx* ctx, uint8_t** bytes, uint64_t* n, 
   return CALITAS_OK;
 }
 
+// Sites in pairs (sites_host.cpp, site_pairs.hip): no reference counterpart.
+int calitas_find_site_pairs(calitas_ctx* ctx, const calitas_guide_t* pattern, const calitas_site_filter_t* filter, const calitas_site_pairs_t* opt,
+                            int32_t chrom_index, uint64_t start, uint64_t end, calitas_site_t** sites, uint64_t* n_sites, calitas_site_pair_t** pairs,
+                            uint64_t* n_pairs) {
+  if (!ctx) return CALITAS_EINVAL;
+  if (!pattern || !sites || !n_sites || !pairs || !n_pairs) return fail(ctx, CALITAS_EINVAL, "NULL argument");
+  *sites = nullptr; *n_sites = 0; *pairs = nullptr; *n_pairs = 0;
+  return calitas_find_site_pairs_impl(ctx, pattern, filter, opt, chrom_index, start, end, true, sites, n_sites, pairs, n_pairs, nullptr);
+}
+
+int calitas_count_site_pairs(calitas_ctx* ctx, const calitas_guide_t* pattern, const calitas_site_filter_t* filter, const calitas_site_pairs_t* opt,
+                             int32_t chrom_index, uint64_t start, uint64_t end, uint64_t* n_sites, uint64_t* n_pairs, uint64_t* per_orientation) {
+  if (!ctx) return CALITAS_EINVAL;
+  if (!pattern || !n_sites || !n_pairs) return fail(ctx, CALITAS_EINVAL, "NULL argument");
+  *n_sites = 0; *n_pairs = 0;
+  return calitas_find_site_pairs_impl(ctx, pattern, filter, opt, chrom_index, start, end, false, nullptr, n_sites, nullptr, n_pairs, per_orientation);
+}
+
+int calitas_find_site_pairs_host(const calitas_ctx* ctx, const calitas_guide_t* pattern, const calitas_site_filter_t* filter,
+                                 const calitas_site_pairs_t* opt, int32_t chrom_index, uint64_t start, uint64_t end, calitas_site_t** sites,
+                                 uint64_t* n_sites, calitas_site_pair_t** pairs, uint64_t* n_pairs) {
+  if (!ctx) return CALITAS_EINVAL;
+  if (!pattern || !sites || !n_sites || !pairs || !n_pairs) return fail(const_cast<calitas_ctx*>(ctx), CALITAS_EINVAL, "NULL argument");
+  *sites = nullptr; *n_sites = 0; *pairs = nullptr; *n_pairs = 0;
+  return calitas_find_site_pairs_host_impl(ctx, pattern, filter, opt, chrom_index, start, end, true, sites, n_sites, pairs, n_pairs, nullptr);
+}
+
+int calitas_count_site_pairs_host(const calitas_ctx* ctx, const calitas_guide_t* pattern, const calitas_site_filter_t* filter,
+                                  const calitas_site_pairs_t* opt, int32_t chrom_index, uint64_t start, uint64_t end, uint64_t* n_sites,
+                                  uint64_t* n_pairs, uint64_t* per_orientation) {
+  if (!ctx) return CALITAS_EINVAL;
+  if (!pattern || !n_sites || !n_pairs) return fail(const_cast<calitas_ctx*>(ctx), CALITAS_EINVAL, "NULL argument");
+  *n_sites = 0; *n_pairs = 0;
+  return calitas_find_site_pairs_host_impl(ctx, pattern, filter, opt, chrom_index, start, end, false, nullptr, n_sites, nullptr, n_pairs, per_orientation);
+}
+
 }  // extern "C"

@@ -42,6 +42,9 @@ static void usage() {
     "         [--regions file.bed (chromosome start end class: only the sites in the named classes' intervals, and the column class)]\n"
     "         [--classes name,... (with --regions: the classes to keep; elsewhere: outside every interval)]\n"
     "         [--class-extent FROM:TO (with --regions: class these positions of the protospacer as the guide reads, 0-based half-open; default all)]\n"
+    "         [--pairs out.tsv (the pairs of the kept guides, one per line) --pair-distance MIN:MAX (of the two cuts, 0 .. 65535)]\n"
+    "         [--pair-cut N (with --pairs: the cut's position 0 .. L in the protospacer as the guide reads; default L - 3 with a 3' PAM)]\n"
+    "         [--pair-orientation out|in|same|any|CODE,... (with --pairs: default out, the PAMs facing outwards; codes ++ -+ +- --)]\n"
     "         [--device N (-1: the host twin, no GPU)]\n");
 }
 
@@ -380,6 +383,8 @@ static int find_guides_main(int argc, char** argv) {
   bool have_min_activity = false;
   std::string regions_path, class_names, class_extent;     // --regions FILE.bed [--classes name,...] [--class-extent FROM:TO]
   bool have_classes = false, have_extent = false;
+  std::string pairs_path, pair_distance, pair_cut, pair_orientation;     // --pairs FILE --pair-distance MIN:MAX [--pair-cut N] [--pair-orientation ...]
+  bool have_pair_distance = false, have_pair_cut = false, have_pair_orientation = false;
   for (int i = 2; i < argc; i++) {
     std::string a = argv[i], val;
     size_t eq = a.find('=');
@@ -416,6 +421,10 @@ static int find_guides_main(int argc, char** argv) {
     else if (a == "--regions") regions_path = next();
     else if (a == "--classes") { class_names = next(); have_classes = true; }
     else if (a == "--class-extent") { class_extent = next(); have_extent = true; }
+    else if (a == "--pairs") pairs_path = next();
+    else if (a == "--pair-distance") { pair_distance = next(); have_pair_distance = true; }
+    else if (a == "--pair-cut") { pair_cut = next(); have_pair_cut = true; }
+    else if (a == "--pair-orientation") { pair_orientation = next(); have_pair_orientation = true; }
     else { std::fprintf(stderr, "unknown argument %s\n", a.c_str()); usage(); return 2; }
   }
   if (pattern.empty() || ref.empty()) { usage(); return 2; }
@@ -477,6 +486,50 @@ static int find_guides_main(int argc, char** argv) {
     const long a = std::atol(from.c_str()), b = std::atol(to.c_str());
     if (!(a < b && b <= (long)pg.proto.size())) { std::fprintf(stderr, "calitas: --class-extent FROM:TO: 0 <= FROM < TO <= %zu, the protospacer's length\n", pg.proto.size()); return 2; }
     by_class.ext_from = (uint8_t)a; by_class.ext_to = (uint8_t)b;
+  }
+  // --pairs: the rule of a pair from its flags (tools.py site_pairs_of_flags)
+  const bool have_pairs = !pairs_path.empty();
+  if (!have_pairs && (have_pair_distance || have_pair_cut || have_pair_orientation)) { std::fprintf(stderr, "calitas: --pair-distance, --pair-cut and --pair-orientation require --pairs FILE\n"); return 2; }
+  if (have_pairs && !have_pair_distance) { std::fprintf(stderr, "calitas: --pairs requires --pair-distance MIN:MAX\n"); return 2; }
+  calitas_site_pairs_t pair_rule{0, 0, 0, 0, {0, 0}};
+  const bool pattern_has_pam = !pg.pams.empty(), three_prime = pattern_has_pam && !pg.pam5;
+  if (have_pairs) {
+    const auto digits = [](const std::string& t, size_t most) { return !t.empty() && t.size() <= most && t.find_first_not_of("0123456789") == std::string::npos; };
+    const size_t colon = pair_distance.find(':');
+    const std::string lo = pair_distance.substr(0, colon), hi = colon == std::string::npos ? std::string() : pair_distance.substr(colon + 1);
+    if (!digits(lo, 9) || !digits(hi, 9) || !(std::atol(lo.c_str()) <= std::atol(hi.c_str()) && std::atol(hi.c_str()) <= CALITAS_PAIR_MAX_DISTANCE)) {
+      std::fprintf(stderr, "calitas: --pair-distance MIN:MAX: two integers, 0 <= MIN <= MAX <= %d, not %s\n", CALITAS_PAIR_MAX_DISTANCE, pair_distance.c_str());
+      return 2;
+    }
+    pair_rule.min_distance = (int32_t)std::atol(lo.c_str()); pair_rule.max_distance = (int32_t)std::atol(hi.c_str());
+    if (!have_pair_cut && !three_prime) { std::fprintf(stderr, "calitas: --pair-cut N is required: the default, L - 3, is the Cas9 cut of a pattern with a 3' PAM\n"); return 2; }
+    if (have_pair_cut && !(digits(pair_cut, 3) && std::atol(pair_cut.c_str()) <= (long)pg.proto.size())) {
+      std::fprintf(stderr, "calitas: --pair-cut N: N is 0 .. %zu, the protospacer's length, not %s\n", pg.proto.size(), pair_cut.c_str());
+      return 2;
+    }
+    const long cut = have_pair_cut ? std::atol(pair_cut.c_str()) : (long)pg.proto.size() - 3;
+    if (cut < 0) { std::fprintf(stderr, "calitas: --pair-cut N is required: the protospacer has fewer than 3 bases\n"); return 2; }
+    pair_rule.cut_offset = (uint8_t)cut;
+    const std::string names = have_pair_orientation ? pair_orientation : std::string("out");
+    unsigned mask = 0;
+    bool any_name = false;
+    for (size_t at = 0; at <= names.size();) {
+      size_t comma = names.find(',', at);
+      if (comma == std::string::npos) comma = names.size();
+      const std::string o = names.substr(at, comma - at);
+      at = comma + 1;
+      if (o.empty()) continue;
+      any_name = true;
+      static const char* const codes[4] = {"++", "-+", "+-", "--"};
+      int code = -1;
+      for (int k = 0; k < 4; k++) if (o == codes[k]) code = k;
+      if (code >= 0) { mask |= 1u << code; continue; }
+      if (o != "out" && o != "in" && o != "same" && o != "any") { std::fprintf(stderr, "calitas: --pair-orientation: %s: out, in, same, any, or a code among ++ -+ +- --\n", o.c_str()); return 2; }
+      if (!pattern_has_pam) { std::fprintf(stderr, "calitas: --pair-orientation: %s needs a PAM: a pattern without one takes the codes ++ -+ +- --\n", o.c_str()); return 2; }
+      mask |= o == "any" ? 15u : o == "same" ? 9u : ((o == "out") == three_prime) ? 2u : 4u;
+    }
+    if (!any_name) { std::fprintf(stderr, "calitas: --pair-orientation is empty: out, in, same, any, or codes among ++ -+ +- --\n"); return 2; }
+    pair_rule.orientations = (uint8_t)mask;
   }
   calitas_ctx* ctx = nullptr;
   if (calitas_create(device, &ctx) != CALITAS_OK) { std::fprintf(stderr, "calitas: %s\n", calitas_last_error(nullptr)); return 1; }
@@ -682,6 +735,49 @@ static int find_guides_main(int argc, char** argv) {
     }
     calitas_free(found);
     std::fclose(lf);
+  }
+  // the pairs of the kept rows (tools.py guide_pairs, pairs_tsv): the region's listing paired in one call, joined to the rows on
+  // (contig, protospacer start, strand) in one walk -- both are in that order -- and a pair written when both members are rows
+  if (have_pairs) {
+    FILE* pf = std::fopen(pairs_path.c_str(), "w");
+    if (!pf) { std::fprintf(stderr, "cannot write %s\n", pairs_path.c_str()); calitas_free(sites); calitas_free(activity_q16); calitas_free(site_class); calitas_destroy(ctx); return 1; }
+    std::fprintf(pf, "pair_id\tleft_guide_id\tright_guide_id\tchromosome\tleft_cut\tright_cut\tdistance\tleft_strand\tright_strand\torientation\n");
+    calitas_site_t* listed = nullptr; uint64_t n_listed = 0;
+    calitas_site_pair_t* found = nullptr; uint64_t n_found = 0;
+    const int rc2 = device < 0 ? calitas_find_site_pairs_host(ctx, &g, keep, &pair_rule, chrom_index, start, end, &listed, &n_listed, &found, &n_found)
+                               : calitas_find_site_pairs(ctx, &g, keep, &pair_rule, chrom_index, start, end, &listed, &n_listed, &found, &n_found);
+    if (rc2 != CALITAS_OK) die("pairing sites");
+    const auto less = [](const calitas_site_t& x, const calitas_site_t& y) {
+      if (x.contig_index != y.contig_index) return x.contig_index < y.contig_index;
+      if (x.protospacer_start != y.protospacer_start) return x.protospacer_start < y.protospacer_start;
+      return x.strand == '+' && y.strand == '-';
+    };
+    const uint64_t no_row = ~0ull;
+    std::vector<uint64_t> row_of((size_t)n_listed, no_row);
+    for (uint64_t i = 0, r = 0; i < n_listed; i++) {
+      while (r < kept.size() && less(sites[kept[r]], listed[i])) r++;
+      if (r < kept.size() && !less(listed[i], sites[kept[r]])) row_of[(size_t)i] = kept[r];
+    }
+    const auto id_of = [&](const calitas_site_t& s, const char* name) {
+      const int64_t lo = s.pam_start < 0 ? s.protospacer_start : std::min<int64_t>(s.protospacer_start, s.pam_start);
+      return std::string(name) + ":" + std::to_string((long long)lo) + ":" + (char)s.strand;
+    };
+    const auto cut_of = [&](const calitas_site_t& s) { return (long long)s.protospacer_start + (s.strand == '-' ? L - pair_rule.cut_offset : (int64_t)pair_rule.cut_offset); };
+    uint64_t pair_id = 0;
+    for (uint64_t k = 0; k < n_found; k++) {
+      const uint64_t a = row_of[found[k].left], b = row_of[found[k].right];
+      if (a == no_row || b == no_row) continue;
+      const calitas_site_t &left = sites[a], &right = sites[b];
+      const char* name; uint64_t len;
+      calitas_contig_name(ctx, left.contig_index, &name, &len);
+      const unsigned o = found[k].orientation;
+      static const char* const codes[4] = {"++", "-+", "+-", "--"};
+      const char* called = !pattern_has_pam ? codes[o & 3u] : (o == 0 || o == 3) ? "same" : ((o == 1) == three_prime) ? "out" : "in";
+      std::fprintf(pf, "%llu\t%s\t%s\t%s\t%lld\t%lld\t%d\t%c\t%c\t%s\n", (unsigned long long)++pair_id, id_of(left, name).c_str(), id_of(right, name).c_str(), name,
+                   cut_of(left), cut_of(right), (int)found[k].distance, (char)left.strand, (char)right.strand, called);
+    }
+    calitas_free(listed); calitas_free(found);
+    std::fclose(pf);
   }
   std::fprintf(stderr, "calitas: %llu guides\n", (unsigned long long)n_rows);
   calitas_free(sites); calitas_free(activity_q16); calitas_free(site_class); calitas_destroy(ctx);

@@ -1,4 +1,4 @@
-// kernels.hpp -- launch interface of scan_columns.hip, scan_rows.hip, align.hip, trace.hip, setup.hip, sites.hip and activity.hip (device pointers only).
+// kernels.hpp -- launch interface of scan_columns.hip, scan_rows.hip, align.hip, trace.hip, setup.hip, sites.hip, activity.hip and site_pairs.hip (device pointers only).
 #pragma once
 #include "mailbox.hpp"
 #include <hip/hip_runtime_api.h>
@@ -310,5 +310,47 @@ hipError_t launch_activity_score(const ActivityArgs& a, hipStream_t stream);
 hipError_t launch_activity_compact(const SiteRecord* recs, const int32_t* scores, uint64_t n, int32_t min_score, const uint64_t* wg_offset,
                                    SiteRecord* out_recs, int32_t* out_scores, uint64_t out_capacity, hipStream_t stream);
 inline uint32_t activity_blocks(uint64_t n) { return (uint32_t)((n + ACTIVITY_THREADS - 1) / ACTIVITY_THREADS); }
+
+// site_pairs.hip: calitas_find_site_pairs.  The records launch_sites_write left on the device, in listing order, one lane per record.
+// The rule of a pair (calitas_hip.h, calitas_site_pairs_t) in the two functions the kernels and the host twin share:
+// a site's cut, and whether two cuts and strands make a pair -- integers only.
+constexpr int SITE_PAIR_THREADS = 256;
+constexpr int32_t SITE_PAIR_MAX_DISTANCE = 65535;         // = CALITAS_PAIR_MAX_DISTANCE
+struct SitePairRule {
+  int32_t min_distance, max_distance;
+  int32_t L, cut;                  // the protospacer's length; the cut's position in it as the guide reads, 0 .. L
+  int32_t slack;                   // |L - 2 cut|: how far the difference of two cuts can be from that of the two starts
+  uint32_t orientations;           // bit o: pairs of orientation o count
+};
+struct SitePair {                  // = calitas_site_pair_t
+  uint32_t left, right;
+  int32_t distance;
+  uint8_t orientation, reserved[3];
+};
+static_assert(sizeof(SitePair) == 16, "one 16-byte store per record");
+CAL_HD inline int32_t site_cut(const SitePairRule& r, int32_t proto_start, bool minus) { return minus ? proto_start + r.L - r.cut : proto_start + r.cut; }
+// Sites i < j of one contig with these cuts and strands: the pair's orientation (left is '-') + 2 (right is '-'), the left member the
+// one with the smaller cut and at equal cuts i; -1: no pair.
+CAL_HD inline int site_pair_orientation(const SitePairRule& r, int32_t cut_i, bool minus_i, int32_t cut_j, bool minus_j) {
+  const int32_t d = cut_j - cut_i, distance = d < 0 ? -d : d;
+  if (distance < r.min_distance || distance > r.max_distance) return -1;
+  const int o = ((d < 0 ? minus_j : minus_i) ? 1 : 0) + ((d < 0 ? minus_i : minus_j) ? 2 : 0);
+  return ((r.orientations >> o) & 1u) ? o : -1;
+}
+struct SitePairArgs {
+  const SiteRecord* recs;          // n records in listing order (contig, protospacer start, '+' first), 16-byte aligned
+  uint64_t n;                      // < 2^32
+  uint32_t* lane_count;            // n: the pairs (i, j > i) of record i
+  uint32_t* wg_count;              // per workgroup: the sum of its lanes' counts
+  unsigned long long* per_orientation;   // 4, 0 at launch (the count kernel)
+  const uint64_t* wg_offset;       // the scan of wg_count (the write kernel)
+  SitePair* out;
+  uint64_t out_capacity;
+  SitePairRule rule;
+};
+inline uint32_t site_pair_blocks(uint64_t n) { return (uint32_t)((n + SITE_PAIR_THREADS - 1) / SITE_PAIR_THREADS); }
+hipError_t launch_site_pairs_count(const SitePairArgs& a, hipStream_t stream);
+// The pairs in (i, j) order: pair k of record i of workgroup g goes to wg_offset[g] + the counts of g's lanes before i + k.
+hipError_t launch_site_pairs_write(const SitePairArgs& a, hipStream_t stream);
 
 }  // namespace calitas

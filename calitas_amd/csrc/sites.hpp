@@ -76,3 +76,11 @@ int calitas_find_sites_regions_host_impl(const calitas_ctx* ctx, const calitas_g
 int calitas_find_sites_regions_impl(calitas_ctx* ctx, const calitas_guide_t* pattern, const calitas_site_filter_t* filter, const calitas_site_regions_t* opt,
                                     int32_t chrom_index, uint64_t start, uint64_t end, bool listing, calitas_site_t** sites, uint8_t** classes,
                                     uint64_t* per_class_strand, uint64_t* n_sites);
+// the listing of calitas_find_sites_filtered and its pairs under opt; listing false: the numbers alone (per_orientation may be null)
+int calitas_find_site_pairs_host_impl(const calitas_ctx* ctx, const calitas_guide_t* pattern, const calitas_site_filter_t* filter,
+                                      const calitas_site_pairs_t* opt, int32_t chrom_index, uint64_t start, uint64_t end, bool listing,
+                                      calitas_site_t** sites, uint64_t* n_sites, calitas_site_pair_t** pairs, uint64_t* n_pairs,
+                                      uint64_t* per_orientation);
+int calitas_find_site_pairs_impl(calitas_ctx* ctx, const calitas_guide_t* pattern, const calitas_site_filter_t* filter, const calitas_site_pairs_t* opt,
+                                 int32_t chrom_index, uint64_t start, uint64_t end, bool listing, calitas_site_t** sites, uint64_t* n_sites,
+                                 calitas_site_pair_t** pairs, uint64_t* n_pairs, uint64_t* per_orientation);

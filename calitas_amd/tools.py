@@ -525,6 +525,72 @@ def near_list_tsv(rows, names, listing):
     return "\n".join(lines) + "\n"
 
 
+PAIR_COLUMNS = ["pair_id", "left_guide_id", "right_guide_id", "chromosome", "left_cut", "right_cut", "distance", "left_strand", "right_strand", "orientation"]
+
+
+def guide_pairs(ctx, pattern, rows, spec, chrom=None, start=0, end=None, host=False, filter=None):
+    """Context.find_site_pairs for the GuideSites of find_guides: the pairs of the region's sites under `spec` (a SitePairs) both of
+    whose members are among `rows` -- what is left of the listing after the other cuts (activity, regions, copies, near copies).
+    pattern, filter and the region are those the rows were listed with.  The two listings are joined on (contig, protospacer start,
+    strand).  A list of (left row, right row, left cut, right cut, distance, orientation) in the pairs' order, the first two indices
+    into rows."""
+    from .aligner import site_cut_of
+    if not isinstance(pattern, Guide):
+        pattern = Guide(pattern)
+    sites, pairs = ctx.find_site_pairs(pattern, spec, filter=filter, chrom=chrom, start=start, end=end, host=host)
+    at = {(r.chromosome, r.protospacer_start, r.strand): i for i, r in enumerate(rows)}
+    row_of = [at.get((ctx.contig_names[int(s["contig_index"])], int(s["protospacer_start"]), s["strand"].decode())) for s in sites]
+    L, c = pattern.protospacer_length, spec.cut_of(pattern)
+    out = []
+    for p in pairs:
+        a, b = row_of[int(p["left"])], row_of[int(p["right"])]
+        if a is None or b is None:
+            continue
+        cuts = [site_cut_of(rows[i].protospacer_start, rows[i].strand, L, c) for i in (a, b)]
+        out.append((a, b, cuts[0], cuts[1], int(p["distance"]), int(p["orientation"])))
+    return out
+
+
+def pairs_tsv(rows, names, pairs):
+    """The --pairs table: PAIR_COLUMNS, a line per pair of guide_pairs(rows) in its order, pair_id from 1.  names: what the four
+    orientation codes are called (SitePairs.name_of: out / in / same, or the code itself for a PAM-less pattern); the cuts are 0-based
+    positions between two bases of the chromosome: the number of bases to the cut's left."""
+    lines = ["\t".join(PAIR_COLUMNS)]
+    for k, (a, b, left_cut, right_cut, distance, o) in enumerate(pairs):
+        lines.append("\t".join([str(k + 1), rows[a].guide_id, rows[b].guide_id, rows[a].chromosome, str(left_cut), str(right_cut), str(distance),
+                                rows[a].strand, rows[b].strand, names[o]]))
+    return "\n".join(lines) + "\n"
+
+
+def site_pairs_of_flags(pattern, pairs=None, pair_distance=None, pair_cut=None, pair_orientation=None):
+    """The SitePairs of FindGuides' --pair-* flags for `pattern` (a Guide), None without --pairs.  pair_distance "MIN:MAX" is required
+    with --pairs; pair_cut N: default L - 3 with a 3' PAM, required otherwise; pair_orientation: out | in | same | any | CODE,...,
+    default out."""
+    from .aligner import PAIR_MAX_DISTANCE, SitePairs
+    if pairs is None:
+        if pair_distance is not None or pair_cut is not None or pair_orientation is not None:
+            raise ValueError("--pair-distance, --pair-cut and --pair-orientation require --pairs FILE")
+        return None
+    if pair_distance is None:
+        raise ValueError("--pairs requires --pair-distance MIN:MAX")
+    a, sep, b = str(pair_distance).partition(":")
+    if not (sep and a.isdigit() and b.isdigit() and len(a) <= 9 and len(b) <= 9):
+        raise ValueError("--pair-distance MIN:MAX: two integers, 0 <= MIN <= MAX <= %d, not %s" % (PAIR_MAX_DISTANCE, pair_distance))
+    if not int(a) <= int(b) <= PAIR_MAX_DISTANCE:
+        raise ValueError("--pair-distance MIN:MAX: two integers, 0 <= MIN <= MAX <= %d, not %s" % (PAIR_MAX_DISTANCE, pair_distance))
+    L = pattern.protospacer_length
+    if pair_cut is None and not pattern.pam_is_three_prime:
+        raise ValueError("--pair-cut N is required: the default, L - 3, is the Cas9 cut of a pattern with a 3' PAM")
+    if pair_cut is not None and not (str(pair_cut).isdigit() and len(str(pair_cut)) <= 3 and int(pair_cut) <= L):
+        raise ValueError("--pair-cut N: N is 0 .. %d, the protospacer's length, not %s" % (L, pair_cut))
+    try:
+        spec = SitePairs(int(a), int(b), None if pair_cut is None else int(pair_cut), "out" if pair_orientation is None else str(pair_orientation))
+        spec.mask_of(pattern)
+    except ValueError as e:
+        raise ValueError("--pair-orientation: %s" % e)
+    return spec
+
+
 def activity_q16_of_flag(text):
     """--min-activity X as a Q16 integer: a decimal as in a model file (digits, at most one point, an optional sign), within what a
     score can be (+-2064 = 129 weights of 16.0), floor(x * 65536 + 0.5)."""
@@ -629,7 +695,7 @@ def site_filter_of_flags(L, gc_min=None, gc_max=None, max_run=None, avoid=()):
 def find_guides_tool(ref, pattern, auxiliary_pams=(), chrom=None, start=0, end=None, output=None, counts=False, device=0, scores=None,
                      gc_min=None, gc_max=None, max_run=None, avoid=(), copies=False, seed_copies=None, max_copies=None, max_seed_copies=None,
                      near_copies=None, max_near_copies=None, near_scores=None, near_list=None, near_list_limit=None, activity=None, min_activity=None,
-                     regions=None, classes=None, class_extent=None, **search):
+                     regions=None, classes=None, class_extent=None, pairs=None, pair_distance=None, pair_cut=None, pair_orientation=None, **search):
     """`python -m calitas_amd FindGuides`: the guides of a region as a TSV (guides_tsv); counts=True: every distinct guide also goes
     through the off-target search with the SearchReference flags in `search` (make_params names); scores=ScoreModel (or its file):
     through search_scores_batch instead, which adds perfect and specificity.  gc_min, gc_max, max_run, avoid: the site filter's flags
@@ -650,7 +716,10 @@ def find_guides_tool(ref, pattern, auxiliary_pams=(), chrom=None, start=0, end=N
     class, and only the sites of the named classes; classes="name,..." (needs regions) the classes to keep instead, "elsewhere" among
     them if wanted; class_extent="FROM:TO" (needs regions) the positions of the protospacer as the guide reads, 0-based and half-open,
     that are classed instead of all of it.  The dropped rows are gone before any of the flags above looks at anything, the kept rows
-    keep their guide_ids.  These fourteen work with device -1 through the host twin.  Returns the text."""
+    keep their guide_ids.  pairs=FILE: the pairs of the kept rows (guide_pairs, pairs_tsv) to FILE, the table itself unchanged;
+    pair_distance="MIN:MAX" (required with pairs) the bounds on the distance of the two cuts; pair_cut=N the cut's position in the
+    protospacer as the guide reads (default L - 3 with a 3' PAM, required otherwise); pair_orientation=out|in|same|any|CODE,...
+    (default out).  These eighteen work with device -1 through the host twin.  Returns the text."""
     if regions is None and (classes is not None or class_extent is not None):
         raise ValueError("--classes and --class-extent require --regions FILE.bed")
     extent = None
@@ -666,6 +735,7 @@ def find_guides_tool(ref, pattern, auxiliary_pams=(), chrom=None, start=0, end=N
         scores = ScoreModel.read(scores)
     pat = Guide(pattern, auxiliary_pams)
     keep = site_filter_of_flags(pat.protospacer_length, gc_min, gc_max, max_run, avoid)
+    pair_spec = site_pairs_of_flags(pat, pairs, pair_distance, pair_cut, pair_orientation)
     if seed_copies is not None and not 1 <= int(seed_copies) <= pat.protospacer_length:
         raise ValueError("--seed-copies K: K is 1 .. %d, the protospacer's length" % pat.protospacer_length)
     if max_copies is not None and int(max_copies) < 1:
@@ -746,6 +816,10 @@ def find_guides_tool(ref, pattern, auxiliary_pams=(), chrom=None, start=0, end=N
             listing = guide_near_list(ctx, pat, rows, int(near_copies), near_scores, limit=1000 if near_list_limit is None else int(near_list_limit), host=device < 0)
             with open(near_list, "w") as f:
                 f.write(near_list_tsv(rows, ctx.contig_names, listing))
+        if pair_spec is not None:
+            paired = guide_pairs(ctx, pat, rows, pair_spec, chrom, start, end, host=device < 0, filter=keep)
+            with open(pairs, "w") as f:
+                f.write(pairs_tsv(rows, [pair_spec.name_of(o, pat) for o in range(4)], paired))
         if output is not None:
             with open(output, "w") as f:
                 f.write(text)

@@ -673,6 +673,59 @@ int calitas_count_sites_regions_host(const calitas_ctx* ctx, const calitas_guide
  * of the segment.  *bytes is one block for calitas_free.  CALITAS_EINVAL when the context has no regions. */
 int calitas_site_presence(const calitas_ctx* ctx, uint8_t** bytes, uint64_t* n, uint64_t* first_word);
 
+/* Guide sites in pairs: which two sites of a pattern can be used together -- paired nickases (opposite strands, PAMs facing outwards,
+ * cuts a few tens of bases apart) or an excision (two cuts a chosen distance apart).  No reference counterpart.
+ * THE LISTING.  The records of calitas_find_sites_filtered(pattern, filter, chrom_index, start, end) in its order; site i is the record
+ * at index i.  L is the protospacer's length.
+ * THE CUT OF A SITE.  cut_offset = c, 0 .. L, is a position in the protospacer as the guide reads it (as ext_from / ext_to above):
+ * cut = protospacer_start + c on '+' and protospacer_start + L - c on '-'.  c = L - 3 with a 3' PAM is the Cas9 cut.
+ * A PAIR.  Two different sites i < j of one contig with min_distance <= |cut_j - cut_i| <= max_distance whose orientation has its bit in
+ * `orientations`.  The left member is the one with the smaller cut, at equal cuts the one with the smaller index;
+ * distance = cut_right - cut_left >= 0; orientation = (left is '-') + 2 (right is '-'): 0 "++", 1 "-+" (PAM-out for a 3' PAM), 2 "+-"
+ * (PAM-in for a 3' PAM, PAM-out for a 5' PAM), 3 "--".  Sites of different contigs never pair, a site never pairs with itself; two
+ * records at one protospacer_start on opposite strands are two sites and may pair.
+ * THE ORDER.  Pairs come ordered by (i, j), that is by (min(left, right), max(left, right)): a total order, so the device, the host
+ * twin and repeated calls return the same bytes. */
+#define CALITAS_PAIR_MAX_DISTANCE 65535
+typedef struct {
+  int32_t min_distance, max_distance;   /* 0 <= min_distance <= max_distance <= CALITAS_PAIR_MAX_DISTANCE */
+  uint8_t cut_offset;                   /* 0 .. L */
+  uint8_t orientations;                 /* bit o: pairs of orientation o; 1 .. 15 */
+  uint8_t reserved[2];                  /* 0 */
+} calitas_site_pairs_t;
+typedef struct {
+  uint32_t left, right;                 /* indices into the listing */
+  int32_t distance;
+  uint8_t orientation;
+  uint8_t reserved[3];                  /* 0 */
+} calitas_site_pair_t;
+/* *sites: the listing, exactly the bytes of calitas_find_sites_filtered; *pairs: its pairs under opt.  Each is one block for
+ * calitas_free.  On the device the site kernel's two passes leave the records in device memory; one lane per record walks the records
+ * behind it -- up to the first whose start is more than max_distance + |L - 2c| beyond its own, from the first, found by bisection,
+ * that min_distance does not rule out -- and counts its partners; after a scan of the workgroups' sums the same walk stores every pair
+ * at its place (no sort, no returning atomic), and the records and the pairs are copied back once each.  When the reference has a U
+ * beside a site of the region the listing is corrected on the host as calitas_find_sites corrects it and the pairs are made there, by
+ * the host twin's walk over the final listing.
+ * Errors, in this order: CALITAS_ENODEV on a host-only context (the device calls); what calitas_find_sites_filtered refuses;
+ * CALITAS_EINVAL, with a message that names the field, for a NULL opt, orientations of 0 or above 15, reserved != 0, min_distance < 0,
+ * min_distance > max_distance, max_distance > CALITAS_PAIR_MAX_DISTANCE, cut_offset > L, and for a listing of 2^32 sites or more (pair
+ * the region in pieces); CALITAS_ENOMEM when the records do not fit the device. */
+int calitas_find_site_pairs(calitas_ctx* ctx, const calitas_guide_t* pattern, const calitas_site_filter_t* filter /* may be NULL */,
+                            const calitas_site_pairs_t* opt, int32_t chrom_index, uint64_t start, uint64_t end, calitas_site_t** sites,
+                            uint64_t* n_sites, calitas_site_pair_t** pairs, uint64_t* n_pairs);
+/* The same chain without the blocks: *n_sites, *n_pairs and, when per_orientation is not NULL, the pairs per orientation ([4]; they
+ * sum to *n_pairs).  Neither records nor pairs are copied back. */
+int calitas_count_site_pairs(calitas_ctx* ctx, const calitas_guide_t* pattern, const calitas_site_filter_t* filter, const calitas_site_pairs_t* opt,
+                             int32_t chrom_index, uint64_t start, uint64_t end, uint64_t* n_sites, uint64_t* n_pairs,
+                             uint64_t* per_orientation /* [4], may be NULL */);
+/* The host twins: calitas_find_sites_filtered_host's records and one walk over them; also on a host-only context. */
+int calitas_find_site_pairs_host(const calitas_ctx* ctx, const calitas_guide_t* pattern, const calitas_site_filter_t* filter,
+                                 const calitas_site_pairs_t* opt, int32_t chrom_index, uint64_t start, uint64_t end, calitas_site_t** sites,
+                                 uint64_t* n_sites, calitas_site_pair_t** pairs, uint64_t* n_pairs);
+int calitas_count_site_pairs_host(const calitas_ctx* ctx, const calitas_guide_t* pattern, const calitas_site_filter_t* filter,
+                                  const calitas_site_pairs_t* opt, int32_t chrom_index, uint64_t start, uint64_t end, uint64_t* n_sites,
+                                  uint64_t* n_pairs, uint64_t* per_orientation);
+
 /* SequentialGuideAligner.align on explicit (guide, target) pairs -- the per-task call of PairwiseAlignSequences
  * (PairwiseAlignSequences.scala:64 -> alignBest, SequentialGuideAligner.scala:333-345) and AlignToReference
  * (AlignToReference.scala:114-135 -> alignToRef / alignToRefBest, SequentialGuideAligner.scala:359-418).  Task t aligns
