@@ -119,6 +119,11 @@ def main(argv=None):
                     help="with --pairs: where a site is cut, a position 0 .. L of the protospacer as the guide reads (default L - 3, the Cas9 cut, with a 3' PAM; required otherwise)")
     fg.add_argument("--pair-orientation", metavar="out|in|same|any|CODE,...",
                     help="with --pairs: the orientations to keep -- out (PAMs facing outwards, the default), in, same, any, or codes among ++ -+ +- -- (left strand, right strand)")
+    fg.add_argument("--alleles", metavar="FILE.vcf[.gz]",
+                    help="with --allele-sites: the SNVs (single-letter REF and ALT of A C G T) whose position lies in the region; the table itself does not change")
+    fg.add_argument("--allele-sites", metavar="OUT.tsv",
+                    help="with --alleles: write the sites each SNV creates (allele alt), destroys (ref) or changes (both) to OUT.tsv, one per line")
+    fg.add_argument("--allele-kinds", metavar="alt,ref,both", help="with --alleles: the kinds of lines to write (default all three)")
     fg.add_argument("-d", "--max-guide-diffs", type=int, default=Defaults.MaxGuideDiffs)
     fg.add_argument("-p", "--max-pam-mismatches", type=int, default=Defaults.MaxPamMismatches)
     fg.add_argument("-g", "--max-gaps-between-guide-and-pam", type=int, default=Defaults.MaxGapsBetweenGuideAndPam)
@@ -166,7 +171,8 @@ def main(argv=None):
     elif a.tool == "FindGuides":
         text = find_guides_tool(a.ref, a.guide, a.auxiliary_pams, chrom=a.chrom, start=a.start, end=a.end, output=a.output, counts=a.counts, scores=a.scores,
                                 device=a.device, gc_min=a.gc_min, gc_max=a.gc_max, max_run=a.max_run, avoid=a.avoid, copies=a.copies,
-                                seed_copies=a.seed_copies, max_copies=a.max_copies, max_seed_copies=a.max_seed_copies, near_copies=a.near_copies, max_near_copies=a.max_near_copies, near_scores=a.near_scores, near_list=a.near_list, near_list_limit=a.near_list_limit, activity=a.activity, min_activity=a.min_activity, regions=a.regions, classes=a.classes, class_extent=a.class_extent, pairs=a.pairs, pair_distance=a.pair_distance, pair_cut=a.pair_cut, pair_orientation=a.pair_orientation, max_guide_diffs=a.max_guide_diffs, max_pam_mismatches=a.max_pam_mismatches,
+                                seed_copies=a.seed_copies, max_copies=a.max_copies, max_seed_copies=a.max_seed_copies, near_copies=a.near_copies, max_near_copies=a.max_near_copies, near_scores=a.near_scores, near_list=a.near_list, near_list_limit=a.near_list_limit, activity=a.activity, min_activity=a.min_activity, regions=a.regions, classes=a.classes, class_extent=a.class_extent, pairs=a.pairs, pair_distance=a.pair_distance, pair_cut=a.pair_cut, pair_orientation=a.pair_orientation, alleles=a.alleles, allele_sites=a.allele_sites, allele_kinds=a.allele_kinds,
+                                max_guide_diffs=a.max_guide_diffs, max_pam_mismatches=a.max_pam_mismatches,
                                 max_gaps_between_guide_and_pam=a.max_gaps_between_guide_and_pam, max_total_diffs=a.max_total_diffs,
                                 max_overlap=a.max_overlap, guide_mismatch_net_cost=a.guide_mismatch_net_cost,
                                 pam_mismatch_net_cost=a.pam_mismatch_net_cost, genome_gap_net_cost=a.genome_gap_net_cost,

@@ -126,6 +126,16 @@ class SitePairT(ctypes.Structure):
                 ("reserved", ctypes.c_uint8 * 3)]
 
 
+class SnvT(ctypes.Structure):
+    _fields_ = [("contig_index", ctypes.c_int32), ("position", ctypes.c_int32), ("ref", ctypes.c_char), ("alt", ctypes.c_char), ("reserved", ctypes.c_uint16)]
+
+
+class AlleleSiteT(ctypes.Structure):
+    _fields_ = [("site", SiteT), ("snv_index", ctypes.c_uint32), ("kind", ctypes.c_uint8), ("other_pam_index", ctypes.c_int8), ("guide_offset", ctypes.c_int8),
+                ("reserved", ctypes.c_uint8), ("guide_lo", ctypes.c_uint32), ("guide_hi", ctypes.c_uint32)]
+
+
+assert ctypes.sizeof(SnvT) == 12 and ctypes.sizeof(AlleleSiteT) == 32
 PAIR_MAX_DISTANCE = 65535
 assert ctypes.sizeof(SitePairsT) == 12 and ctypes.sizeof(SitePairT) == 16
 TOP_MAX = 256
@@ -153,7 +163,8 @@ SYMBOLS = ["calitas_create", "calitas_destroy", "calitas_last_error", "calitas_f
            "calitas_find_sites_scored", "calitas_find_sites_scored_host",
            "calitas_find_sites_regions", "calitas_count_sites_regions", "calitas_find_sites_regions_host", "calitas_count_sites_regions_host",
            "calitas_site_presence",
-           "calitas_find_site_pairs", "calitas_count_site_pairs", "calitas_find_site_pairs_host", "calitas_count_site_pairs_host"]
+           "calitas_find_site_pairs", "calitas_count_site_pairs", "calitas_find_site_pairs_host", "calitas_count_site_pairs_host",
+           "calitas_find_allele_sites", "calitas_count_allele_sites", "calitas_find_allele_sites_host", "calitas_count_allele_sites_host"]
 
 if not os.path.exists(LIB_PATH):
     raise ImportError("%s is missing: build it with `make -C calitas_amd/csrc` (hipcc, gfx950). "
@@ -261,6 +272,13 @@ if hasattr(lib, "calitas_find_site_pairs"):        # (an older build behind CALI
                                              ctypes.c_uint64, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64),
                                              ctypes.POINTER(ctypes.c_uint64)]
     lib.calitas_count_site_pairs_host.argtypes = lib.calitas_count_site_pairs.argtypes
+if hasattr(lib, "calitas_find_allele_sites"):      # (an older build behind CALITAS_LIB_PATH, for A/B runs, does not have it)
+    lib.calitas_find_allele_sites.argtypes = [ctypes.c_void_p, ctypes.POINTER(GuideT), ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(ctypes.POINTER(AlleleSiteT)),
+                                              ctypes.POINTER(ctypes.c_uint64), ctypes.c_void_p]
+    lib.calitas_find_allele_sites_host.argtypes = lib.calitas_find_allele_sites.argtypes
+    lib.calitas_count_allele_sites.argtypes = [ctypes.c_void_p, ctypes.POINTER(GuideT), ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64),
+                                               ctypes.POINTER(ctypes.c_uint64), ctypes.c_void_p]
+    lib.calitas_count_allele_sites_host.argtypes = lib.calitas_count_allele_sites.argtypes
 lib.calitas_search_scores.argtypes = [ctypes.c_void_p, ctypes.POINTER(GuideT), ctypes.POINTER(ParamsT), ctypes.POINTER(ScoreModelT),
                                       ctypes.POINTER(ctypes.POINTER(ScoresT))]
 lib.calitas_search_scores_batch.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.POINTER(GuideT), ctypes.POINTER(ParamsT),

@@ -791,6 +791,46 @@ class Context:
         _lib.check(self._h, rc)
         return n.value, n_pairs.value, by
 
+    def _snv_array(self, snvs):
+        import numpy as np
+        if not (hasattr(snvs, "dtype") and snvs.dtype == np.dtype(SNV_DTYPE)):
+            snvs = snvs_of(snvs, self)
+        return np.ascontiguousarray(snvs)
+
+    def find_allele_sites(self, pattern, snvs, host=False):
+        """calitas_find_allele_sites: the sites each single-nucleotide variant creates (kind 1), destroys (kind 2) or changes (kind 3),
+        as an AlleleSites -- records with the fields of calitas_allele_site_t (ALLELE_SITE_DTYPE) ordered by snv_index, protospacer
+        start, '+' before '-', and a status byte per SNV.  snvs: an array of SNV_DTYPE, or (chrom, pos1, ref, alt) tuples (snvs_of).
+        allele_sites_of is the contract in plain Python.  host=True: the host twin, also on a host-only context."""
+        import numpy as np
+        if not isinstance(pattern, Guide):
+            pattern = Guide(pattern)
+        snvs = self._snv_array(snvs)
+        g = pattern.to_c()
+        status = np.zeros(max(1, len(snvs)), dtype=np.uint8)
+        out, n = ctypes.POINTER(_lib.AlleleSiteT)(), ctypes.c_uint64()
+        fn = lib.calitas_find_allele_sites_host if host else lib.calitas_find_allele_sites
+        rc = fn(self._h, ctypes.byref(g), snvs.ctypes.data if len(snvs) else None, len(snvs), ctypes.byref(out), ctypes.byref(n), status.ctypes.data)
+        _lib.check(self._h, rc)
+        return AlleleSites(self._take_records(out, n.value, _lib.AlleleSiteT, ALLELE_SITE_DTYPE), status[:len(snvs)], pattern)
+
+    def count_allele_sites(self, pattern, snvs, host=False):
+        """calitas_count_allele_sites: (n, per_kind, status) of what find_allele_sites would return; per_kind a numpy uint64 array of
+        four, [0] always 0.  No record is copied back."""
+        import numpy as np
+        if not isinstance(pattern, Guide):
+            pattern = Guide(pattern)
+        snvs = self._snv_array(snvs)
+        g = pattern.to_c()
+        status = np.zeros(max(1, len(snvs)), dtype=np.uint8)
+        by = np.zeros(4, dtype=np.uint64)
+        n = ctypes.c_uint64()
+        fn = lib.calitas_count_allele_sites_host if host else lib.calitas_count_allele_sites
+        rc = fn(self._h, ctypes.byref(g), snvs.ctypes.data if len(snvs) else None, len(snvs), by.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)),
+                ctypes.byref(n), status.ctypes.data)
+        _lib.check(self._h, rc)
+        return n.value, by, status[:len(snvs)]
+
     def site_presence(self):
         """(test hook) calitas_site_presence: (bytes, first_word) -- the table the regions listing skips segments by, a uint8 array with
         one byte per 256 words (8192 bases) of the packed space from word first_word on; bit c: class c comes near the segment."""
@@ -1934,6 +1974,126 @@ def site_pairs_of(sites, spec, pattern):
             if (mask >> o) & 1:
                 pairs.append((left, right, abs(d), o))
     return pairs
+
+
+# calitas_snv_t and calitas_allele_site_t
+SNV_DTYPE = [("contig_index", "<i4"), ("position", "<i4"), ("ref", "S1"), ("alt", "S1"), ("reserved", "<u2")]
+ALLELE_SITE_DTYPE = SITE_DTYPE + [("snv_index", "<u4"), ("kind", "u1"), ("other_pam_index", "i1"), ("guide_offset", "i1"), ("reserved", "u1"),
+                                  ("guide_lo", "<u4"), ("guide_hi", "<u4")]
+ALLELE_KINDS = ("", "alt", "ref", "both")       # kind k: (a site on alt) + 2 (a site on the reference)
+
+
+def snvs_of(records, ctx):
+    """(chrom, pos1, ref, alt) tuples -- chrom a name of ctx's contigs or an index, pos1 1-based as in a VCF, ref None or "" for "not
+    checked" -- as an array of SNV_DTYPE."""
+    import numpy as np
+    out = np.zeros(len(records), dtype=SNV_DTYPE)
+    index = {nm: i for i, nm in enumerate(ctx.contig_names)}
+    for k, (chrom, pos1, ref, alt) in enumerate(records):
+        if isinstance(chrom, str) and chrom not in index:
+            raise ValueError("Unknown chromosome: %s" % chrom)
+        out[k] = (index[chrom] if isinstance(chrom, str) else int(chrom), int(pos1) - 1, (ref or "").encode(), alt.encode(), 0)
+    return out
+
+
+class AlleleSites:
+    """What Context.find_allele_sites returns.  sites: the records (ALLELE_SITE_DTYPE) in (snv_index, protospacer_start, strand) order;
+    status: a byte per SNV -- 0 examined, 1 `ref` differs from the reference's base, 2 the reference's base is no A C G T U, 3 `alt`
+    is the reference's base; pattern: the Guide."""
+
+    def __init__(self, sites, status, pattern):
+        self.sites, self.status, self.pattern = sites, status, pattern
+
+    def __len__(self):
+        return len(self.sites)
+
+    def of(self, i):
+        """The records of SNV i."""
+        import numpy as np
+        lo, hi = np.searchsorted(self.sites["snv_index"], [i, i + 1])
+        return self.sites[lo:hi]
+
+    def protospacer(self, rec):
+        """The protospacer of the record's allele as the guide reads it, from guide_lo / guide_hi."""
+        lo, hi = int(rec["guide_lo"]), int(rec["guide_hi"])
+        return "".join("ACGT"[((lo >> i) & 1) | (((hi >> i) & 1) << 1)] for i in range(int(rec["protospacer_length"])))
+
+    def guide(self, rec):
+        """The `-i` string a search takes for the record: the protospacer of the allele named, the pattern's matched PAM in lower case
+        behind it (in front of it for a 5' PAM)."""
+        k = int(rec["pam_index"])
+        pam = self.pattern.pams[k] if k >= 0 else ""
+        proto = self.protospacer(rec)
+        return (pam + proto) if self.pattern.pam_is_five_prime else (proto + pam)
+
+    def merge(self, other):
+        """This listing followed by `other`, the listing of the SNVs that came behind this one's in one list: other's snv_index moves
+        up by this one's number of SNVs."""
+        import numpy as np
+        moved = other.sites.copy()
+        moved["snv_index"] += len(self.status)
+        return AlleleSites(np.concatenate([self.sites, moved]), np.concatenate([self.status, other.status]), self.pattern)
+
+
+def allele_sites_of(contig_seqs, pattern, snvs):
+    """The contract of find_allele_sites in plain Python: a letter of a string replaced, every start and PAM tried letter by letter.
+    contig_seqs: the contigs' strings; snvs: (contig_index, position0, ref, alt) tuples or records of SNV_DTYPE.  Returns (records,
+    status): records as tuples in ALLELE_SITE_DTYPE's field order, status a list."""
+    if not isinstance(pattern, Guide):
+        pattern = Guide(pattern)
+    sets = {"A": "A", "C": "C", "G": "G", "T": "T", "U": "T", "M": "AC", "R": "AG", "W": "AT", "S": "CG", "Y": "CT", "K": "GT", "V": "ACG",
+            "H": "ACT", "D": "AGT", "B": "CGT", "N": "ACGT"}
+    comp = {"A": "T", "C": "G", "G": "C", "T": "A"}
+    L, five, pams = pattern.protospacer_length, pattern.pam_is_five_prime, pattern.pams or [""]
+
+    def site(seq, p, strand):
+        """(pam index, footprint lo, hi, pam_start, protospacer as the guide reads) of the first PAM that matches, or None."""
+        for k, pam in enumerate(pams):
+            pl = len(pam)
+            left = five != (strand == "-")
+            lo = p - pl if left else p
+            hi = lo + L + pl
+            if lo < 0 or hi > len(seq):
+                continue
+            foot = seq[lo:hi].upper().replace("U", "T")
+            if any(c not in "ACGT" for c in foot):
+                continue
+            read = foot if strand == "+" else "".join(comp[c] for c in reversed(foot))
+            want = ((pam + pattern.guide) if five else (pattern.guide + pam)).upper()
+            if all(r in sets[w] for r, w in zip(read, want)):
+                proto = read[pl:] if five else read[:L]
+                return k, lo, hi, (lo if left else p + L), proto
+        return None
+
+    records, status = [], []
+    for i, v in enumerate(snvs):
+        ci, pos, ref, alt = (int(v["contig_index"]), int(v["position"]), v["ref"].decode(), v["alt"].decode()) if hasattr(v, "dtype") else v
+        seq = contig_seqs[ci]
+        letter = lambda c: c.upper().replace("U", "T")
+        here = letter(seq[pos])
+        if here not in "ACGT":
+            status.append(2)
+            continue
+        if ref and letter(ref) != here:
+            status.append(1)
+            continue
+        if letter(alt) == here:
+            status.append(3)
+            continue
+        status.append(0)
+        with_alt = seq[:pos] + letter(alt) + seq[pos + 1:]
+        for p in range(pos - 47, pos + 17):
+            for strand in "+-":
+                on_ref, on_alt = site(seq, p, strand), site(with_alt, p, strand)
+                if not any(s is not None and s[1] <= pos < s[2] for s in (on_ref, on_alt)):
+                    continue
+                kind = (1 if on_alt else 0) + (2 if on_ref else 0)
+                k, lo, hi, pam_start, proto = on_alt or on_ref
+                bits = ["ACGT".index(c) for c in proto]
+                records.append((ci, p, pam_start if pattern.pams else -1, strand.encode(), k if pattern.pams else -1, hi - lo - L, L, i, kind,
+                                on_ref[0] if kind == 3 and pattern.pams else -1, (p + L - 1 - pos) if strand == "-" else (pos - p), 0,
+                                sum((b & 1) << j for j, b in enumerate(bits)), sum((b >> 1) << j for j, b in enumerate(bits))))
+    return records, status
 
 
 def regions_of_rows(rows, model, regions, k, list_mask=None, shape=None):

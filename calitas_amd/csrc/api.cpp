@@ -1415,4 +1415,37 @@ int calitas_count_site_pairs_host(const calitas_ctx* ctx, const calitas_guide_t*
   return calitas_find_site_pairs_host_impl(ctx, pattern, filter, opt, chrom_index, start, end, false, nullptr, n_sites, nullptr, n_pairs, per_orientation);
 }
 
+// Allele-specific sites (sites_host.cpp, allele_sites.hip): no reference counterpart.
+int calitas_find_allele_sites(calitas_ctx* ctx, const calitas_guide_t* pattern, const calitas_snv_t* snvs, uint64_t n_snvs, calitas_allele_site_t** sites,
+                              uint64_t* n_sites, uint8_t* status) {
+  if (!ctx) return CALITAS_EINVAL;
+  if (!pattern || !sites || !n_sites) return fail(ctx, CALITAS_EINVAL, "NULL argument");
+  *sites = nullptr; *n_sites = 0;
+  return calitas_find_allele_sites_impl(ctx, pattern, snvs, n_snvs, true, sites, nullptr, n_sites, status);
+}
+
+int calitas_count_allele_sites(calitas_ctx* ctx, const calitas_guide_t* pattern, const calitas_snv_t* snvs, uint64_t n_snvs, uint64_t* per_kind,
+                               uint64_t* n_sites, uint8_t* status) {
+  if (!ctx) return CALITAS_EINVAL;
+  if (!pattern || !n_sites) return fail(ctx, CALITAS_EINVAL, "NULL argument");
+  *n_sites = 0;
+  return calitas_find_allele_sites_impl(ctx, pattern, snvs, n_snvs, false, nullptr, per_kind, n_sites, status);
+}
+
+int calitas_find_allele_sites_host(const calitas_ctx* ctx, const calitas_guide_t* pattern, const calitas_snv_t* snvs, uint64_t n_snvs,
+                                   calitas_allele_site_t** sites, uint64_t* n_sites, uint8_t* status) {
+  if (!ctx) return CALITAS_EINVAL;
+  if (!pattern || !sites || !n_sites) return fail(const_cast<calitas_ctx*>(ctx), CALITAS_EINVAL, "NULL argument");
+  *sites = nullptr; *n_sites = 0;
+  return calitas_find_allele_sites_host_impl(ctx, pattern, snvs, n_snvs, true, sites, nullptr, n_sites, status);
+}
+
+int calitas_count_allele_sites_host(const calitas_ctx* ctx, const calitas_guide_t* pattern, const calitas_snv_t* snvs, uint64_t n_snvs, uint64_t* per_kind,
+                                    uint64_t* n_sites, uint8_t* status) {
+  if (!ctx) return CALITAS_EINVAL;
+  if (!pattern || !n_sites) return fail(const_cast<calitas_ctx*>(ctx), CALITAS_EINVAL, "NULL argument");
+  *n_sites = 0;
+  return calitas_find_allele_sites_host_impl(ctx, pattern, snvs, n_snvs, false, nullptr, per_kind, n_sites, status);
+}
+
 }  // extern "C"

@@ -45,6 +45,8 @@ static void usage() {
     "         [--pairs out.tsv (the pairs of the kept guides, one per line) --pair-distance MIN:MAX (of the two cuts, 0 .. 65535)]\n"
     "         [--pair-cut N (with --pairs: the cut's position 0 .. L in the protospacer as the guide reads; default L - 3 with a 3' PAM)]\n"
     "         [--pair-orientation out|in|same|any|CODE,... (with --pairs: default out, the PAMs facing outwards; codes ++ -+ +- --)]\n"
+    "         [--alleles FILE.vcf[.gz] --allele-sites out.tsv (the sites each SNV of the region creates, destroys or changes, one per line)]\n"
+    "         [--allele-kinds alt,ref,both (with --alleles: the kinds of lines to write; default all three)]\n"
     "         [--device N (-1: the host twin, no GPU)]\n");
 }
 
@@ -385,6 +387,8 @@ static int find_guides_main(int argc, char** argv) {
   bool have_classes = false, have_extent = false;
   std::string pairs_path, pair_distance, pair_cut, pair_orientation;     // --pairs FILE --pair-distance MIN:MAX [--pair-cut N] [--pair-orientation ...]
   bool have_pair_distance = false, have_pair_cut = false, have_pair_orientation = false;
+  std::string alleles_path, allele_sites_path, allele_kinds;             // --alleles FILE.vcf --allele-sites OUT.tsv [--allele-kinds alt,ref,both]
+  bool have_allele_kinds = false;
   for (int i = 2; i < argc; i++) {
     std::string a = argv[i], val;
     size_t eq = a.find('=');
@@ -425,6 +429,9 @@ static int find_guides_main(int argc, char** argv) {
     else if (a == "--pair-distance") { pair_distance = next(); have_pair_distance = true; }
     else if (a == "--pair-cut") { pair_cut = next(); have_pair_cut = true; }
     else if (a == "--pair-orientation") { pair_orientation = next(); have_pair_orientation = true; }
+    else if (a == "--alleles") alleles_path = next();
+    else if (a == "--allele-sites") allele_sites_path = next();
+    else if (a == "--allele-kinds") { allele_kinds = next(); have_allele_kinds = true; }
     else { std::fprintf(stderr, "unknown argument %s\n", a.c_str()); usage(); return 2; }
   }
   if (pattern.empty() || ref.empty()) { usage(); return 2; }
@@ -486,6 +493,22 @@ static int find_guides_main(int argc, char** argv) {
     const long a = std::atol(from.c_str()), b = std::atol(to.c_str());
     if (!(a < b && b <= (long)pg.proto.size())) { std::fprintf(stderr, "calitas: --class-extent FROM:TO: 0 <= FROM < TO <= %zu, the protospacer's length\n", pg.proto.size()); return 2; }
     by_class.ext_from = (uint8_t)a; by_class.ext_to = (uint8_t)b;
+  }
+  // --alleles: the kinds of lines to write (tools.py allele_sites_tool)
+  const bool have_alleles = !alleles_path.empty();
+  if (have_alleles != !allele_sites_path.empty()) { std::fprintf(stderr, "calitas: --alleles FILE.vcf and --allele-sites OUT.tsv require each other\n"); return 2; }
+  if (have_allele_kinds && !have_alleles) { std::fprintf(stderr, "calitas: --allele-kinds requires --alleles FILE.vcf and --allele-sites OUT.tsv\n"); return 2; }
+  unsigned kinds_wanted = have_allele_kinds ? 0u : 14u;                  // bit k: lines of kind k (1 alt, 2 ref, 3 both)
+  if (have_allele_kinds) {
+    bool ok = true;
+    for (size_t at = 0; at <= allele_kinds.size();) {
+      size_t comma = allele_kinds.find(',', at);
+      if (comma == std::string::npos) comma = allele_kinds.size();
+      const std::string k = allele_kinds.substr(at, comma - at);
+      if (k == "alt") kinds_wanted |= 2u; else if (k == "ref") kinds_wanted |= 4u; else if (k == "both") kinds_wanted |= 8u; else if (!k.empty()) ok = false;
+      at = comma + 1;
+    }
+    if (!ok || kinds_wanted == 0) { std::fprintf(stderr, "calitas: --allele-kinds: names among alt, ref, both, separated by commas, not %s\n", allele_kinds.c_str()); return 2; }
   }
   // --pairs: the rule of a pair from its flags (tools.py site_pairs_of_flags)
   const bool have_pairs = !pairs_path.empty();
@@ -778,6 +801,86 @@ static int find_guides_main(int argc, char** argv) {
     }
     calitas_free(listed); calitas_free(found);
     std::fclose(pf);
+  }
+  // the sites the VCF's SNVs create, destroy or change (tools.py snvs_of_vcf, allele_sites_tool, allele_sites_tsv)
+  if (have_alleles) {
+    char* text = nullptr; uint64_t n_records = 0;
+    if (calitas_vcf_records(ctx, alleles_path.c_str(), nullptr, &text, &n_records) != CALITAS_OK) die("reading the VCF");
+    struct SnvRow { std::string chrom, id, ref, alt; long long pos1; };
+    std::vector<SnvRow> snv_rows;
+    std::vector<calitas_snv_t> snvs;
+    unsigned long long other = 0, lacks = 0, beyond = 0;
+    int32_t n_contigs = 0; calitas_reference_info(ctx, &n_contigs, nullptr, nullptr);
+    for (const char* line = text; *line;) {
+      const char* eol = std::strchr(line, '\n');
+      if (!eol) eol = line + std::strlen(line);
+      std::vector<std::string> fld;
+      for (const char* at = line;;) {
+        const char* tab = (const char*)std::memchr(at, '\t', (size_t)(eol - at));
+        fld.emplace_back(at, tab ? tab : eol);
+        if (!tab) break;
+        at = tab + 1;
+      }
+      line = *eol ? eol + 1 : eol;
+      if (fld.size() < 6) continue;
+      int32_t ci = -1; uint64_t len = 0;
+      for (int32_t i = 0; i < n_contigs && ci < 0; i++) { const char* nm; uint64_t l; calitas_contig_name(ctx, i, &nm, &l); if (fld[0] == nm) { ci = i; len = l; } }
+      if (ci < 0) { lacks++; continue; }
+      const long long pos1 = std::atoll(fld[1].c_str());
+      if ((chrom_index >= 0 && ci != chrom_index) || pos1 - 1 < (long long)start || (end != 0 && pos1 - 1 >= (long long)end)) continue;
+      const std::string& ref_allele = fld[4];
+      for (size_t at = 0; at <= fld[5].size();) {
+        size_t comma = fld[5].find(',', at);
+        if (comma == std::string::npos) comma = fld[5].size();
+        const std::string alt = fld[5].substr(at, comma - at);
+        at = comma + 1;
+        const auto base = [](const std::string& t) { return t.size() == 1 && std::strchr("ACGT", t[0]) != nullptr; };
+        if (!base(ref_allele) || !base(alt)) other++;
+        else if ((uint64_t)pos1 > len) beyond++;
+        else {
+          snv_rows.push_back(SnvRow{fld[0], fld[3], ref_allele, alt, pos1});
+          snvs.push_back(calitas_snv_t{ci, (int32_t)(pos1 - 1), ref_allele[0], alt[0], 0});
+        }
+      }
+    }
+    calitas_free(text);
+    calitas_allele_site_t* found = nullptr; uint64_t n_found = 0;
+    std::vector<uint8_t> status(snvs.size() + 1, 0);
+    const int rc2 = device < 0 ? calitas_find_allele_sites_host(ctx, &g, snvs.data(), snvs.size(), &found, &n_found, status.data())
+                               : calitas_find_allele_sites(ctx, &g, snvs.data(), snvs.size(), &found, &n_found, status.data());
+    if (rc2 != CALITAS_OK) die("finding allele sites");
+    FILE* af = std::fopen(allele_sites_path.c_str(), "w");
+    if (!af) { std::fprintf(stderr, "cannot write %s\n", allele_sites_path.c_str()); calitas_free(found); calitas_free(sites); calitas_free(activity_q16); calitas_free(site_class); calitas_destroy(ctx); return 1; }
+    std::fprintf(af, "chromosome\tposition\tid\tref\talt\tallele\tstart\tend\tstrand\tpam_index\tsnv_offset\tguide\tpam_sequence\tother_pam_index\n");
+    static const char* const kind_names[4] = {"", "alt", "ref", "both"};
+    for (uint64_t k = 0; k < n_found; k++) {
+      const calitas_allele_site_t& r = found[k];
+      if (!((kinds_wanted >> r.kind) & 1u)) continue;
+      const calitas_site_t& s = r.site;
+      const SnvRow& v = snv_rows[r.snv_index];
+      const int64_t lo = s.pam_start < 0 ? s.protospacer_start : std::min<int64_t>(s.protospacer_start, s.pam_start);
+      const int64_t hi = s.pam_start < 0 ? s.protospacer_start + L : std::max<int64_t>(s.protospacer_start + L, (int64_t)s.pam_start + s.pam_length);
+      std::string proto((size_t)L, 'N'), pam((size_t)s.pam_length, 'N');
+      for (int64_t i = 0; i < L; i++) proto[(size_t)i] = "ACGT"[((r.guide_lo >> i) & 1u) | (((r.guide_hi >> i) & 1u) << 1)];
+      if (s.pam_start >= 0 && s.pam_length) {
+        if (calitas_fetch_bases(ctx, s.contig_index, (uint64_t)s.pam_start, s.pam_length, &pam[0]) != CALITAS_OK) die("fetching bases");
+        if (r.kind != 2 && v.pos1 - 1 >= s.pam_start && v.pos1 - 1 < (long long)s.pam_start + s.pam_length) pam[(size_t)(v.pos1 - 1 - s.pam_start)] = v.alt[0];
+        pam = on_strand(pam, s.strand == '-');
+        for (auto& c : pam) if (c == 'U') c = 'T';
+      }
+      const std::string pattern_pam = s.pam_index >= 0 ? pg.pams[(size_t)s.pam_index] : std::string();
+      const std::string guide = five ? pattern_pam + proto : proto + pattern_pam;
+      std::fprintf(af, "%s\t%lld\t%s\t%s\t%s\t%s\t%lld\t%lld\t%c\t%d\t%d\t%s\t%s\t", v.chrom.c_str(), v.pos1, v.id.empty() ? "." : v.id.c_str(), v.ref.c_str(),
+                   v.alt.c_str(), kind_names[r.kind & 3u], (long long)lo, (long long)hi, (char)s.strand, (int)s.pam_index, (int)r.guide_offset, guide.c_str(), pam.c_str());
+      if (r.kind == 3) std::fprintf(af, "%d\n", (int)r.other_pam_index); else std::fprintf(af, ".\n");
+    }
+    std::fclose(af);
+    unsigned long long by[4] = {0, 0, 0, 0};
+    for (size_t i = 0; i < snvs.size(); i++) by[status[i] & 3u]++;
+    std::fprintf(stderr, "alleles: %llu SNVs examined, %llu records; skipped: %llu other alleles, %llu records on chromosomes the reference lacks, %llu beyond a contig's end, "
+                         "%llu with another REF than the reference, %llu on a base that is not A C G T, %llu with ALT equal to the reference\n",
+                 by[0], (unsigned long long)n_found, other, lacks, beyond, by[1], by[2], by[3]);
+    calitas_free(found);
   }
   std::fprintf(stderr, "calitas: %llu guides\n", (unsigned long long)n_rows);
   calitas_free(sites); calitas_free(activity_q16); calitas_free(site_class); calitas_destroy(ctx);

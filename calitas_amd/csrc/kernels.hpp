@@ -1,4 +1,4 @@
-// kernels.hpp -- launch interface of scan_columns.hip, scan_rows.hip, align.hip, trace.hip, setup.hip, sites.hip, activity.hip and site_pairs.hip (device pointers only).
+// kernels.hpp -- launch interface of scan_columns.hip, scan_rows.hip, align.hip, trace.hip, setup.hip, sites.hip, activity.hip, site_pairs.hip and allele_sites.hip (device pointers only).
 #pragma once
 #include "mailbox.hpp"
 #include <hip/hip_runtime_api.h>
@@ -352,5 +352,48 @@ inline uint32_t site_pair_blocks(uint64_t n) { return (uint32_t)((n + SITE_PAIR_
 hipError_t launch_site_pairs_count(const SitePairArgs& a, hipStream_t stream);
 // The pairs in (i, j) order: pair k of record i of workgroup g goes to wg_offset[g] + the counts of g's lanes before i + k.
 hipError_t launch_site_pairs_write(const SitePairArgs& a, hipStream_t stream);
+
+// allele_sites.hip: calitas_find_allele_sites.  One lane per SNV; the 64 protospacer starts p of (position - 48, position + 16] are the
+// ones whose footprint [p + lo, p + hi) can hold the SNV, one 64-bit match vector per (allele, PAM, strand).
+constexpr int ALLELE_THREADS = 256;
+constexpr uint32_t ALLELE_MAX_RECORDS = 2 * SITE_MAX_FOOT;   // per SNV
+constexpr uint16_t ALLELE_HOST_DECIDES = 1;                  // Snv::reserved of the device's copy: a U within reach, the host twin decides
+struct Snv {                       // = calitas_snv_t
+  int32_t contig, position;
+  char ref, alt;
+  uint16_t reserved;
+};
+struct AlleleSite {                // = calitas_allele_site_t
+  SiteRecord site;
+  uint32_t snv_index;
+  uint8_t kind;
+  int8_t other_pam_index, guide_offset;
+  uint8_t reserved;
+  uint32_t guide_lo, guide_hi;
+};
+static_assert(sizeof(Snv) == 12 && sizeof(AlleleSite) == 32, "two 16-byte stores per record");
+// 2-bit code of A C G T U in either case (the host has checked the letter)
+CAL_HD inline uint32_t allele_code(char ch) { const int c = ch & 0xDF; return c == 'A' ? 0u : c == 'C' ? 1u : c == 'G' ? 2u : 3u; }
+struct AlleleArgs {
+  const uint2* planes;
+  const uint32_t* mask;
+  const ContigInfo* contigs;
+  const SitePatterns* pat;         // device memory: the head of a SiteTables
+  const Snv* snvs;
+  uint64_t n;                      // < 2^32
+  uint64_t n_words;                // 32-base words of the packed space
+  int32_t n_contigs;
+  uint32_t* lane_count;            // n: the records of SNV i
+  uint8_t* status;                 // n
+  uint32_t* wg_count;              // per workgroup: the sum of its lanes' counts
+  unsigned long long* per_kind;    // 4, 0 at launch (the count kernel)
+  const uint64_t* wg_offset;       // the scan of wg_count (the write kernel)
+  AlleleSite* out;
+  uint64_t out_capacity;
+};
+inline uint32_t allele_blocks(uint64_t n) { return (uint32_t)((n + ALLELE_THREADS - 1) / ALLELE_THREADS); }
+hipError_t launch_allele_count(const AlleleArgs& a, hipStream_t stream);
+// The records in (SNV, start, strand) order: record k of SNV i of workgroup g goes to wg_offset[g] + the counts of g's lanes before i + k.
+hipError_t launch_allele_write(const AlleleArgs& a, hipStream_t stream);
 
 }  // namespace calitas

@@ -12,7 +12,9 @@
 // their host twins: the checks, the presence table, the host twin (every record classed through the host's flattened set) and the driver
 // of site_regions.hip's kernels around the site kernel's two passes, with the records beside a U classed on the host.  calitas_find_site_pairs /
 // calitas_count_site_pairs and their host twins: the checks, the one walk over a sorted listing (pair_walk) that the twins and the
-// listings beside a U share, and the driver of site_pairs.hip's kernels behind the site kernel's two passes.  No reference counterpart.
+// listings beside a U share, and the driver of site_pairs.hip's kernels behind the site kernel's two passes.  calitas_find_allele_sites / calitas_count_allele_sites and
+// their host twins: the checks, the twin (a base-by-base walk with one base replaced) that also decides the SNVs beside a U, and the
+// driver of allele_sites.hip's two kernels.  No reference counterpart.
 #include "sites.hpp"
 #include "site_regions.hpp"
 #include "tuning.hpp"
@@ -259,6 +261,18 @@ struct SitesWork {
   unsigned long long* d_pair_by = nullptr;
   SitePair* d_pair_out = nullptr;
   size_t pair_out_cap = 0;
+  // calitas_find_allele_sites: the SNVs, a count and a status byte per SNV, the workgroups' sums and their scan, the per-kind counters,
+  // and the records in order
+  Snv* d_snvs = nullptr;
+  uint32_t* d_al_lanes = nullptr;
+  uint8_t* d_al_status = nullptr;
+  size_t al_snvs_cap = 0;
+  uint32_t* d_al_count = nullptr;
+  uint64_t* d_al_off = nullptr;
+  size_t al_blocks_cap = 0;
+  unsigned long long* d_al_by = nullptr;
+  AlleleSite* d_al_out = nullptr;
+  size_t al_out_cap = 0;
   // the U / u runs of the resident reference (a U is a plain base to a site and an exception base to the kernels)
   uint64_t u_serial = ~0ull;
   std::vector<Run> u_runs;
@@ -273,6 +287,7 @@ void sites_destroy(SitesWork* w) {
   (void)hipFree(w->d_presence); (void)hipFree(w->d_reg_cls); (void)hipFree(w->d_reg_count); (void)hipFree(w->d_reg_off); (void)hipFree(w->d_reg_cells); (void)hipFree(w->d_reg_out); (void)hipFree(w->d_reg_out_cls);
   (void)hipFree(w->d_act_table); (void)hipFree(w->d_act_scores); (void)hipFree(w->d_act_count); (void)hipFree(w->d_act_off); (void)hipFree(w->d_act_out); (void)hipFree(w->d_act_out_scores);
   (void)hipFree(w->d_pair_lanes); (void)hipFree(w->d_pair_count); (void)hipFree(w->d_pair_off); (void)hipFree(w->d_pair_by); (void)hipFree(w->d_pair_out);
+  (void)hipFree(w->d_snvs); (void)hipFree(w->d_al_lanes); (void)hipFree(w->d_al_status); (void)hipFree(w->d_al_count); (void)hipFree(w->d_al_off); (void)hipFree(w->d_al_by); (void)hipFree(w->d_al_out);
   delete w;
 }
 
@@ -287,9 +302,8 @@ struct SiteCall {
   bool pam5 = false;                 // the pattern has PAMs and they stand in front of the protospacer
 };
 
-// arguments every entry point shares: the pattern, the filter, the contigs, the region
-int plan_sites(calitas_ctx* c, const calitas_guide_t* pattern, const calitas_site_filter_t* filter, int32_t chrom_index, uint64_t start, uint64_t end,
-               SiteCall& call) {
+// the first half of plan_sites: the pattern and the filter
+int plan_site_pattern(calitas_ctx* c, const calitas_guide_t* pattern, const calitas_site_filter_t* filter, SiteCall& call) {
   if (!c->has_ref) return calitas_fail(c, CALITAS_ESTATE, "calitas_set_reference has not been called");
   GuideHost gh;
   std::string e = make_guide_host(*pattern, gh);
@@ -298,6 +312,13 @@ int plan_sites(calitas_ctx* c, const calitas_guide_t* pattern, const calitas_sit
   call.pam5 = gh.pam5 && !gh.pams.empty();
   if (e.empty() && filter) e = make_site_filter(*filter, call.tab.pat.proto_len, call.tab.filter);
   if (!e.empty()) return calitas_fail(c, CALITAS_EINVAL, e);
+  return CALITAS_OK;
+}
+
+// arguments every entry point shares: the pattern, the filter, the contigs, the region
+int plan_sites(calitas_ctx* c, const calitas_guide_t* pattern, const calitas_site_filter_t* filter, int32_t chrom_index, uint64_t start, uint64_t end,
+               SiteCall& call) {
+  if (int rc = plan_site_pattern(c, pattern, filter, call)) return rc;
   const PackedRef& ref = c->ref;
   const int nc = (int)ref.contigs.size();
   if (chrom_index >= nc) return calitas_fail(c, CALITAS_EINVAL, "chrom_index out of range");
@@ -1952,5 +1973,262 @@ int calitas_find_site_pairs_impl(calitas_ctx* ctx, const calitas_guide_t* patter
   } while (0);
   if (rc) { calitas_free(block); calitas_free(block_pairs); return rc; }
   *sites = block; *pairs = block_pairs;
+  return CALITAS_OK;
+}
+
+// ---- calitas_find_allele_sites: the sites a single-nucleotide variant creates, destroys or changes ----
+
+namespace {
+
+inline bool allele_letter(char ch) { const int c = ch & 0xDF; return c == 'A' || c == 'C' || c == 'G' || c == 'T' || c == 'U'; }
+
+// checked in this order: the pattern as calitas_find_sites checks it (plan_site_pattern), n_snvs, then the SNVs field by field -- of
+// the first field that some SNV has wrong, the first SNV that has it wrong
+int plan_allele_sites(calitas_ctx* c, const calitas_guide_t* pattern, const calitas_snv_t* snvs, uint64_t n_snvs, SiteCall& call) {
+  if (int rc = plan_site_pattern(c, pattern, nullptr, call)) return rc;
+  if (n_snvs >= (1ull << 32)) return calitas_fail(c, CALITAS_EINVAL, "allele sites: n_snvs " + std::to_string(n_snvs) + " is 2^32 or more: pass the SNVs in pieces");
+  if (n_snvs && !snvs) return calitas_fail(c, CALITAS_EINVAL, "allele sites: snvs is NULL");
+  const PackedRef& ref = c->ref;
+  const int64_t nc = (int64_t)ref.contigs.size();
+  constexpr uint64_t none = ~0ull;
+  uint64_t bad[5] = {none, none, none, none, none};     // contig_index, position, alt, ref, reserved
+  for (uint64_t i = 0; i < n_snvs; i++) {
+    const calitas_snv_t& v = snvs[i];
+    const bool contig_ok = v.contig_index >= 0 && v.contig_index < nc && !ref.is_absent((size_t)v.contig_index);
+    if (!contig_ok) { if (bad[0] == none) bad[0] = i; continue; }
+    if (bad[1] == none && (v.position < 0 || (uint64_t)v.position >= ref.contigs[(size_t)v.contig_index].len)) bad[1] = i;
+    if (bad[2] == none && !allele_letter(v.alt)) bad[2] = i;
+    if (bad[3] == none && v.ref != 0 && !allele_letter(v.ref)) bad[3] = i;
+    if (bad[4] == none && v.reserved != 0) bad[4] = i;
+  }
+  if (bad[0] != none) {
+    const int32_t ci = snvs[bad[0]].contig_index;
+    const bool absent = ci >= 0 && ci < nc;
+    return calitas_fail(c, CALITAS_EINVAL, "allele sites: snvs[" + std::to_string(bad[0]) + "].contig_index " + std::to_string(ci) +
+                                               (absent ? " is absent from this context (calitas_set_reference with bases == NULL)" : " is out of range"));
+  }
+  if (bad[1] != none)
+    return calitas_fail(c, CALITAS_EINVAL, "allele sites: snvs[" + std::to_string(bad[1]) + "].position " + std::to_string(snvs[bad[1]].position) +
+                                               " does not lie on the contig (length " + std::to_string(ref.contigs[(size_t)snvs[bad[1]].contig_index].len) + ")");
+  if (bad[2] != none) return calitas_fail(c, CALITAS_EINVAL, "allele sites: snvs[" + std::to_string(bad[2]) + "].alt is not one of A C G T U");
+  if (bad[3] != none) return calitas_fail(c, CALITAS_EINVAL, "allele sites: snvs[" + std::to_string(bad[3]) + "].ref is not 0 or one of A C G T U");
+  if (bad[4] != none) return calitas_fail(c, CALITAS_EINVAL, "allele sites: snvs[" + std::to_string(bad[4]) + "].reserved must be 0");
+  return CALITAS_OK;
+}
+
+// A contig's text with one base replaced, letter by letter: the 2-bit code of position x, -1 for a base that is not A C G T U and
+// outside the contig.  with < 0: the reference as it is.
+struct AlleleText {
+  const PackedRef& ref;
+  uint64_t gbase;
+  int64_t len, at;
+  int with;
+  int code(int64_t x) const {
+    if (x < 0 || x >= len) return -1;
+    if (x == at && with >= 0) return with;
+    switch (ref.base_upper(gbase + (uint64_t)x)) {
+      case 'A': return 0;  case 'C': return 1;  case 'G': return 2;  case 'T': case 'U': return 3;
+      default: return -1;
+    }
+  }
+};
+
+// the first PAM whose pattern the text shows at protospacer start p on strand st, or -1
+int allele_first_pam(const AlleleText& text, const SitePatterns& pat, int64_t p, int st) {
+  for (int k = 0; k < pat.n_pams; k++) {
+    const SitePattern& sp = pat.p[k][st];
+    bool ok = true;
+    for (int d = sp.lo; d < sp.hi && ok; d++) {
+      const int code = text.code(p + d);
+      const uint32_t set = (sp.sets[(d + 16) >> 3] >> (4 * ((d + 16) & 7))) & 15u;
+      ok = code >= 0 && ((set >> code) & 1u) != 0;
+    }
+    if (ok) return k;
+  }
+  return -1;
+}
+
+// The contract on one SNV, base by base: its status; its records appended to *out (may be null) and counted by kind.
+uint8_t allele_sites_of_snv(const PackedRef& ref, const SitePatterns& pat, const calitas_snv_t& v, uint32_t index, std::vector<calitas_allele_site_t>* out,
+                            uint64_t (&by)[4]) {
+  const ContigInfo& ci = ref.contigs[(size_t)v.contig_index];
+  const int64_t pos = v.position;
+  const AlleleText on_ref{ref, ci.gbase, (int64_t)ci.len, pos, -1};
+  const int ref_code = on_ref.code(pos);
+  if (ref_code < 0) return 2;
+  if (v.ref != 0 && (int)allele_code(v.ref) != ref_code) return 1;
+  if ((int)allele_code(v.alt) == ref_code) return 3;
+  const AlleleText on_alt{ref, ci.gbase, (int64_t)ci.len, pos, (int)allele_code(v.alt)};
+  const int L = pat.proto_len;
+  for (int64_t p = pos - (SITE_MAX_FOOT - 1); p <= pos + MAX_PAM_LEN; p++) {
+    for (int st = 0; st < 2; st++) {
+      const int k_ref = allele_first_pam(on_ref, pat, p, st), k_alt = allele_first_pam(on_alt, pat, p, st);
+      bool covers = false;
+      if (k_ref >= 0) covers = pos >= p + pat.p[k_ref][st].lo && pos < p + pat.p[k_ref][st].hi;
+      if (k_alt >= 0 && !covers) covers = pos >= p + pat.p[k_alt][st].lo && pos < p + pat.p[k_alt][st].hi;
+      if (!covers) continue;
+      const int kind = (k_alt >= 0 ? 1 : 0) + (k_ref >= 0 ? 2 : 0);
+      by[kind]++;
+      if (!out) continue;
+      const AlleleText& text = k_alt >= 0 ? on_alt : on_ref;
+      calitas_allele_site_t r;
+      std::memset(&r, 0, sizeof(r));
+      r.site = site_record(pat, v.contig_index, p, st, k_alt >= 0 ? k_alt : k_ref);
+      r.snv_index = index;
+      r.kind = (uint8_t)kind;
+      r.other_pam_index = (kind == 3 && !pat.pamless) ? (int8_t)k_ref : (int8_t)-1;
+      r.guide_offset = (int8_t)(st ? p + L - 1 - pos : pos - p);
+      for (int i = 0; i < L; i++) {                               // the guide's bases, 5' to 3'
+        const int c = st ? 3 - text.code(p + L - 1 - i) : text.code(p + i);
+        r.guide_lo |= (uint32_t)(c & 1) << i;
+        r.guide_hi |= (uint32_t)(c >> 1) << i;
+      }
+      out->push_back(r);
+    }
+  }
+  return 0;
+}
+
+int allele_block_out(calitas_ctx* c, const std::vector<calitas_allele_site_t>& found, calitas_allele_site_t** sites) {
+  *sites = (calitas_allele_site_t*)calitas_out_alloc(std::max<size_t>(1, found.size()) * sizeof(calitas_allele_site_t));
+  if (!*sites) return calitas_fail(c, CALITAS_EINVAL, "out of memory");
+  if (!found.empty()) std::memcpy(*sites, found.data(), found.size() * sizeof(calitas_allele_site_t));
+  return CALITAS_OK;
+}
+
+}  // namespace
+
+int calitas_find_allele_sites_host_impl(const calitas_ctx* ctx, const calitas_guide_t* pattern, const calitas_snv_t* snvs, uint64_t n_snvs, bool listing,
+                                        calitas_allele_site_t** sites, uint64_t* per_kind, uint64_t* n_sites, uint8_t* status) {
+  calitas_ctx* c = const_cast<calitas_ctx*>(ctx);
+  SiteCall call;
+  if (int rc = plan_allele_sites(c, pattern, snvs, n_snvs, call)) return rc;
+  std::vector<calitas_allele_site_t> found;
+  uint64_t by[4] = {};
+  for (uint64_t i = 0; i < n_snvs; i++) {
+    const uint8_t s = allele_sites_of_snv(ctx->ref, call.tab.pat, snvs[i], (uint32_t)i, listing ? &found : nullptr, by);
+    if (status) status[i] = s;
+  }
+  *n_sites = by[1] + by[2] + by[3];
+  if (per_kind) std::memcpy(per_kind, by, sizeof(by));
+  return listing ? allele_block_out(c, found, sites) : CALITAS_OK;
+}
+
+int calitas_find_allele_sites_impl(calitas_ctx* ctx, const calitas_guide_t* pattern, const calitas_snv_t* snvs, uint64_t n_snvs, bool listing,
+                                   calitas_allele_site_t** sites, uint64_t* per_kind, uint64_t* n_sites, uint8_t* status) {
+  if (ctx->device < 0) return calitas_fail(ctx, CALITAS_ENODEV, "host-only context: calitas_find_allele_sites needs a GPU (there is no CPU fallback; calitas_find_allele_sites_host is the host twin)");
+  SiteCall call;
+  if (int rc = plan_allele_sites(ctx, pattern, snvs, n_snvs, call)) return rc;
+  static_assert(sizeof(Snv) == sizeof(calitas_snv_t) && offsetof(Snv, contig) == offsetof(calitas_snv_t, contig_index) &&
+                offsetof(Snv, position) == offsetof(calitas_snv_t, position) && offsetof(Snv, ref) == offsetof(calitas_snv_t, ref) &&
+                offsetof(Snv, alt) == offsetof(calitas_snv_t, alt) && offsetof(Snv, reserved) == offsetof(calitas_snv_t, reserved), "the kernel reads calitas_snv_t");
+  static_assert(sizeof(AlleleSite) == sizeof(calitas_allele_site_t) && offsetof(AlleleSite, snv_index) == offsetof(calitas_allele_site_t, snv_index) &&
+                offsetof(AlleleSite, kind) == offsetof(calitas_allele_site_t, kind) && offsetof(AlleleSite, other_pam_index) == offsetof(calitas_allele_site_t, other_pam_index) &&
+                offsetof(AlleleSite, guide_offset) == offsetof(calitas_allele_site_t, guide_offset) && offsetof(AlleleSite, guide_lo) == offsetof(calitas_allele_site_t, guide_lo) &&
+                offsetof(AlleleSite, guide_hi) == offsetof(calitas_allele_site_t, guide_hi), "the kernel writes calitas_allele_site_t");
+  static_assert(ALLELE_MAX_RECORDS == 96 && SITE_MAX_FOOT - 1 + 1 + MAX_PAM_LEN == 64, "the window of starts is one 64-bit vector");
+  uint64_t by[4] = {};
+  if (per_kind) std::memcpy(per_kind, by, sizeof(by));
+  std::vector<calitas_allele_site_t> on_host;
+  if (n_snvs == 0) return listing ? allele_block_out(ctx, on_host, sites) : CALITAS_OK;
+  const PackedRef& ref = ctx->ref;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  if (!ctx->sites) ctx->sites = new SitesWork();
+  SitesWork* w = ctx->sites;
+
+  // A U is a T to a site and an exception base to the kernel.  The SNVs with one within the 63 bases either side that a footprint over
+  // the SNV can reach are decided here, by the twin's walk; the device's copy of such a SNV says so and the kernel leaves it alone.
+  if (w->u_serial != ctx->ref_serial) {
+    w->u_runs.clear();
+    for (const Run& r : ref.runs) if (r.ch == 'U' || r.ch == 'u') w->u_runs.push_back(r);
+    w->u_serial = ctx->ref_serial;
+  }
+  std::vector<Snv> marked;
+  std::vector<uint64_t> host_snvs;
+  if (!w->u_runs.empty()) {
+    for (uint64_t i = 0; i < n_snvs; i++) {
+      const uint64_t g = ref.contigs[(size_t)snvs[i].contig_index].gbase + (uint64_t)snvs[i].position;
+      const uint64_t from = g >= 63 ? g - 63 : 0;
+      const auto at = std::partition_point(w->u_runs.begin(), w->u_runs.end(), [&](const Run& r) { return r.start + r.len <= from; });
+      if (at != w->u_runs.end() && at->start <= g + 63) host_snvs.push_back(i);
+    }
+    if (!host_snvs.empty()) {
+      marked.resize(n_snvs);
+      std::memcpy(marked.data(), snvs, n_snvs * sizeof(Snv));
+      for (uint64_t i : host_snvs) marked[i].reserved = ALLELE_HOST_DECIDES;
+    }
+  }
+
+  const char* const no_room = "the SNVs and their records do not fit the device: pass the SNVs in pieces";
+  const uint32_t n_blocks = allele_blocks(n_snvs);
+  if (!w->d_pat) HIP_TRY(ctx, hipMalloc((void**)&w->d_pat, sizeof(SiteTables)));
+  if (w->al_snvs_cap < n_snvs) {
+    (void)hipFree(w->d_snvs); (void)hipFree(w->d_al_lanes); (void)hipFree(w->d_al_status);
+    w->d_snvs = nullptr; w->d_al_lanes = nullptr; w->d_al_status = nullptr; w->al_snvs_cap = 0;
+    if (hipMalloc((void**)&w->d_snvs, n_snvs * sizeof(Snv)) != hipSuccess || hipMalloc((void**)&w->d_al_lanes, n_snvs * sizeof(uint32_t)) != hipSuccess ||
+        hipMalloc((void**)&w->d_al_status, n_snvs) != hipSuccess) {
+      (void)hipGetLastError();
+      (void)hipFree(w->d_snvs); (void)hipFree(w->d_al_lanes); (void)hipFree(w->d_al_status);
+      w->d_snvs = nullptr; w->d_al_lanes = nullptr; w->d_al_status = nullptr;
+      return calitas_fail(ctx, CALITAS_ENOMEM, no_room);
+    }
+    w->al_snvs_cap = n_snvs;
+  }
+  if (w->al_blocks_cap < (size_t)n_blocks + 1) {
+    (void)hipFree(w->d_al_count); (void)hipFree(w->d_al_off); w->d_al_count = nullptr; w->d_al_off = nullptr; w->al_blocks_cap = 0;
+    HIP_TRY(ctx, hipMalloc((void**)&w->d_al_count, ((size_t)n_blocks + 1) * sizeof(uint32_t)));
+    HIP_TRY(ctx, hipMalloc((void**)&w->d_al_off, ((size_t)n_blocks + 1) * sizeof(uint64_t)));
+    w->al_blocks_cap = (size_t)n_blocks + 1;
+  }
+  if (!w->d_al_by) HIP_TRY(ctx, hipMalloc((void**)&w->d_al_by, 4 * sizeof(unsigned long long)));
+
+  AlleleArgs a{};
+  a.planes = ctx->d_planes; a.mask = ctx->d_mask; a.contigs = ctx->d_contigs; a.pat = &w->d_pat->pat; a.snvs = w->d_snvs; a.n = n_snvs;
+  a.n_words = ref.total_packed / 32; a.n_contigs = (int32_t)ref.contigs.size();
+  a.lane_count = w->d_al_lanes; a.status = w->d_al_status; a.wg_count = w->d_al_count; a.per_kind = w->d_al_by; a.wg_offset = w->d_al_off;
+  a.out = nullptr; a.out_capacity = 0;
+  uint64_t total = 0;
+  HIP_TRY(ctx, hipMemcpyAsync(w->d_pat, &call.tab, sizeof(SitePatterns), hipMemcpyHostToDevice, ctx->stream));
+  HIP_TRY(ctx, hipMemcpyAsync(w->d_snvs, marked.empty() ? (const void*)snvs : (const void*)marked.data(), n_snvs * sizeof(Snv), hipMemcpyHostToDevice, ctx->stream));
+  HIP_TRY(ctx, hipMemsetAsync(w->d_al_by, 0, 4 * sizeof(unsigned long long), ctx->stream));
+  HIP_TRY(ctx, launch_allele_count(a, ctx->stream));
+  HIP_TRY(ctx, launch_sites_offsets(w->d_al_count, w->d_al_off, n_blocks, ctx->stream));
+  HIP_TRY(ctx, hipMemcpyAsync(&total, w->d_al_off + n_blocks, sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipMemcpyAsync(by, w->d_al_by, sizeof(by), hipMemcpyDeviceToHost, ctx->stream));
+  if (status) HIP_TRY(ctx, hipMemcpyAsync(status, w->d_al_status, n_snvs, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  if (by[1] + by[2] + by[3] != total) return calitas_fail(ctx, CALITAS_EHIP, "calitas_find_allele_sites: the workgroups' sums do not add up to the kinds' (internal error)");
+
+  for (uint64_t i : host_snvs) {
+    const uint8_t s = allele_sites_of_snv(ref, call.tab.pat, snvs[i], (uint32_t)i, listing ? &on_host : nullptr, by);
+    if (status) status[i] = s;
+  }
+  *n_sites = by[1] + by[2] + by[3];
+  if (per_kind) std::memcpy(per_kind, by, sizeof(by));
+  if (!listing) return CALITAS_OK;
+
+  if (total && w->al_out_cap < total) {
+    (void)hipFree(w->d_al_out); w->d_al_out = nullptr; w->al_out_cap = 0;
+    if (hipMalloc((void**)&w->d_al_out, total * sizeof(AlleleSite)) != hipSuccess) { (void)hipGetLastError(); return calitas_fail(ctx, CALITAS_ENOMEM, no_room); }
+    w->al_out_cap = total;
+  }
+  calitas_allele_site_t* block = (calitas_allele_site_t*)calitas_out_alloc(std::max<uint64_t>(1, *n_sites) * sizeof(calitas_allele_site_t));
+  if (!block) return calitas_fail(ctx, CALITAS_EINVAL, "out of memory");
+  if (total) {
+    hipError_t e = hipSuccess;
+    a.out = w->d_al_out; a.out_capacity = total;
+    if ((e = launch_allele_write(a, ctx->stream)) != hipSuccess ||
+        (e = hipMemcpyAsync(block, w->d_al_out, total * sizeof(AlleleSite), hipMemcpyDeviceToHost, ctx->stream)) != hipSuccess ||
+        (e = hipStreamSynchronize(ctx->stream)) != hipSuccess) {
+      calitas_free(block);
+      return calitas_fail(ctx, CALITAS_EHIP, std::string("calitas_find_allele_sites: ") + hipGetErrorString(e));
+    }
+  }
+  if (!on_host.empty()) {                          // both stretches are in SNV order and share no SNV
+    std::memcpy(block + total, on_host.data(), on_host.size() * sizeof(calitas_allele_site_t));
+    std::inplace_merge(block, block + total, block + *n_sites,
+                       [](const calitas_allele_site_t& x, const calitas_allele_site_t& y) { return x.snv_index < y.snv_index; });
+  }
+  *sites = block;
   return CALITAS_OK;
 }

@@ -692,10 +692,90 @@ def site_filter_of_flags(L, gc_min=None, gc_max=None, max_run=None, avoid=()):
     return SiteFilter(g0, g1, runs, motifs)
 
 
+ALLELE_COLUMNS = ["chromosome", "position", "id", "ref", "alt", "allele", "start", "end", "strand", "pam_index", "snv_offset", "guide", "pam_sequence",
+                  "other_pam_index"]
+
+
+def snvs_of_vcf(ctx, vcf, chrom=None, start=0, end=None):
+    """The SNVs of a VCF for Context.find_allele_sites, read through the library's reader (Context.vcf_records): every ALT of a record
+    whose REF and ALT are single letters of A C G T, on the chromosome `chrom` (None: any) at a 0-based position in [start, end).
+    Returns (rows, skipped): rows a list of (chrom, pos1, id, ref, alt) and skipped a dict of counts -- "other" alleles, "lacks":
+    records on chromosomes the reference lacks, "beyond": SNVs past their contig's end."""
+    lengths = dict(zip(ctx.contig_names, ctx.contig_lengths))
+    rows, skipped = [], {"other": 0, "lacks": 0, "beyond": 0}
+    for c, pos, _, vid, ref, alts, _ in ctx.vcf_records(vcf):
+        if c not in lengths:
+            skipped["lacks"] += 1
+            continue
+        if (chrom is not None and c != chrom) or pos - 1 < start or (end and pos - 1 >= end):
+            continue
+        for alt in alts:
+            if not (len(ref) == 1 and len(alt) == 1 and ref in "ACGT" and alt in "ACGT"):
+                skipped["other"] += 1
+            elif pos > lengths[c]:
+                skipped["beyond"] += 1
+            else:
+                rows.append((c, pos, vid, ref, alt))
+    return rows, skipped
+
+
+def allele_sites_tsv(ctx, found, rows, kinds=("alt", "ref", "both")):
+    """The --allele-sites table: ALLELE_COLUMNS, a line per record of `found` (an AlleleSites over snvs_of(rows)) whose kind is among
+    `kinds`, in the call's order.  position is 1-based as in the VCF, [start, end) the footprint of the record's site, 0-based and
+    half-open; guide is the `-i` string a search takes, cut from the allele named (alt for both); pam_sequence the PAM's bases of that
+    allele on the site's strand; other_pam_index is . unless the line is both."""
+    from .aligner import ALLELE_KINDS
+    lines = ["\t".join(ALLELE_COLUMNS)]
+    L = found.pattern.protospacer_length
+    for r in found.sites:
+        name = ALLELE_KINDS[int(r["kind"])]
+        if name not in kinds:
+            continue
+        c, pos1, vid, ref, alt = rows[int(r["snv_index"])]
+        ci, ps, pm, pl = int(r["contig_index"]), int(r["protospacer_start"]), int(r["pam_start"]), int(r["pam_length"])
+        lo, hi = (ps, ps + L) if pm < 0 else (min(ps, pm), max(ps + L, pm + pl))
+        pam_seq = ""
+        if pm >= 0 and pl:
+            pam_seq = ctx.fetch_bases(ci, pm, pl)
+            if name != "ref" and pm <= pos1 - 1 < pm + pl:
+                pam_seq = pam_seq[:pos1 - 1 - pm] + alt + pam_seq[pos1 - pm:]
+            if r["strand"] == b"-":
+                pam_seq = pam_seq.translate(_RC)[::-1]
+            pam_seq = pam_seq.replace("U", "T")
+        lines.append("\t".join([c, str(pos1), vid or ".", ref, alt, name, str(lo), str(hi), r["strand"].decode(), str(int(r["pam_index"])),
+                                str(int(r["guide_offset"])), found.guide(r), pam_seq, str(int(r["other_pam_index"])) if name == "both" else "."]))
+    return "\n".join(lines) + "\n"
+
+
+def allele_sites_tool(ctx, pat, vcf, out_path, kinds=None, chrom=None, start=0, end=None, host=False):
+    """FindGuides --alleles VCF --allele-sites OUT: the table of allele_sites_tsv to out_path, and the counts of what was examined and
+    skipped as one line on stderr."""
+    import sys
+    from .aligner import snvs_of
+    names = ("alt", "ref", "both")
+    wanted = names if kinds is None else tuple(k for k in str(kinds).split(",") if k)
+    if not wanted or any(k not in names for k in wanted):
+        raise ValueError("--allele-kinds: names among alt, ref, both, separated by commas, not %s" % kinds)
+    rows, skipped = snvs_of_vcf(ctx, vcf, chrom, start, end)
+    found = ctx.find_allele_sites(pat, snvs_of([(c, pos1, ref, alt) for c, pos1, _, ref, alt in rows], ctx), host=host)
+    by = [int((found.status == k).sum()) for k in range(4)]
+    keep = [i for i in range(len(rows)) if found.status[i] == 0]
+    if len(keep) < len(rows):                          # the table speaks of the examined SNVs alone
+        new = {old: k for k, old in enumerate(keep)}
+        found.sites["snv_index"] = [new[int(i)] for i in found.sites["snv_index"]]
+        rows = [rows[i] for i in keep]
+    with open(out_path, "w") as f:
+        f.write(allele_sites_tsv(ctx, found, rows, wanted))
+    sys.stderr.write("alleles: %d SNVs examined, %d records; skipped: %d other alleles, %d records on chromosomes the reference lacks, %d beyond a contig's end, "
+                     "%d with another REF than the reference, %d on a base that is not A C G T, %d with ALT equal to the reference\n"
+                     % (by[0], len(found.sites), skipped["other"], skipped["lacks"], skipped["beyond"], by[1], by[2], by[3]))
+
+
 def find_guides_tool(ref, pattern, auxiliary_pams=(), chrom=None, start=0, end=None, output=None, counts=False, device=0, scores=None,
                      gc_min=None, gc_max=None, max_run=None, avoid=(), copies=False, seed_copies=None, max_copies=None, max_seed_copies=None,
                      near_copies=None, max_near_copies=None, near_scores=None, near_list=None, near_list_limit=None, activity=None, min_activity=None,
-                     regions=None, classes=None, class_extent=None, pairs=None, pair_distance=None, pair_cut=None, pair_orientation=None, **search):
+                     regions=None, classes=None, class_extent=None, pairs=None, pair_distance=None, pair_cut=None, pair_orientation=None, alleles=None, allele_sites=None,
+                     allele_kinds=None, **search):
     """`python -m calitas_amd FindGuides`: the guides of a region as a TSV (guides_tsv); counts=True: every distinct guide also goes
     through the off-target search with the SearchReference flags in `search` (make_params names); scores=ScoreModel (or its file):
     through search_scores_batch instead, which adds perfect and specificity.  gc_min, gc_max, max_run, avoid: the site filter's flags
@@ -719,7 +799,14 @@ def find_guides_tool(ref, pattern, auxiliary_pams=(), chrom=None, start=0, end=N
     keep their guide_ids.  pairs=FILE: the pairs of the kept rows (guide_pairs, pairs_tsv) to FILE, the table itself unchanged;
     pair_distance="MIN:MAX" (required with pairs) the bounds on the distance of the two cuts; pair_cut=N the cut's position in the
     protospacer as the guide reads (default L - 3 with a 3' PAM, required otherwise); pair_orientation=out|in|same|any|CODE,...
-    (default out).  These eighteen work with device -1 through the host twin.  Returns the text."""
+    (default out).  alleles=FILE.vcf[.gz] with allele_sites=OUT.tsv (each needs the other): the sites every SNV of the file whose
+    position lies in the region creates, destroys or changes (Context.find_allele_sites, allele_sites_tsv) to OUT, the table itself
+    unchanged; allele_kinds="alt,ref,both" the kinds to write (default all).  These twenty-one work with device -1 through the host
+    twin.  Returns the text."""
+    if (alleles is None) != (allele_sites is None):
+        raise ValueError("--alleles FILE.vcf and --allele-sites OUT.tsv require each other")
+    if allele_kinds is not None and alleles is None:
+        raise ValueError("--allele-kinds requires --alleles FILE.vcf and --allele-sites OUT.tsv")
     if regions is None and (classes is not None or class_extent is not None):
         raise ValueError("--classes and --class-extent require --regions FILE.bed")
     extent = None
@@ -820,6 +907,8 @@ def find_guides_tool(ref, pattern, auxiliary_pams=(), chrom=None, start=0, end=N
             paired = guide_pairs(ctx, pat, rows, pair_spec, chrom, start, end, host=device < 0, filter=keep)
             with open(pairs, "w") as f:
                 f.write(pairs_tsv(rows, [pair_spec.name_of(o, pat) for o in range(4)], paired))
+        if alleles is not None:
+            allele_sites_tool(ctx, pat, alleles, allele_sites, allele_kinds, chrom, start, end, host=device < 0)
         if output is not None:
             with open(output, "w") as f:
                 f.write(text)

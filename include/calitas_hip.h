@@ -726,6 +726,61 @@ int calitas_count_site_pairs_host(const calitas_ctx* ctx, const calitas_guide_t*
                                   const calitas_site_pairs_t* opt, int32_t chrom_index, uint64_t start, uint64_t end, uint64_t* n_sites,
                                   uint64_t* n_pairs, uint64_t* per_orientation);
 
+/* Allele-specific guide sites: the sites a single-nucleotide variant creates, destroys or changes -- a PAM that exists on one allele
+ * only, a protospacer that differs by the variant's base.  No reference counterpart.
+ * A SNV.  One base of a contig replaced by `alt`; `ref`, when not 0, is held against the reference's base.  Letters are A C G T U in
+ * either case; a U reads as T.
+ * A RECORD.  For SNV i and an allele X of {ref, alt} let site_X(p, s) be the record calitas_find_sites(pattern, the whole contig) would
+ * list at protospacer start p on strand s if the contig carried X's base at `position` (the first matching PAM wins, a base that is not
+ * A C G T U is in no footprint, a footprint that leaves the contig is no site), or none.  A record is written for (i, p, s) when
+ * `position` lies in the footprint -- the protospacer plus the matched PAM -- of site_ref(p, s) or of site_alt(p, s); then
+ * kind = (site_alt exists) + 2 (site_ref exists), `site` is site_alt where it exists and site_ref otherwise, guide_lo / guide_hi hold
+ * the protospacer of that allele as the guide reads it, and guide_offset is position - p on '+' and p + L - 1 - position on '-'
+ * (L: the protospacer's length).  Each SNV is taken alone on the reference background: two SNVs in one footprint do not combine.
+ * THE ORDER.  By snv_index (the input's order: SNVs need not be sorted and may repeat), then protospacer_start, then '+' before '-': a
+ * total order, so the device, the host twin and repeated calls return the same bytes.  A SNV has at most 2 x 48 records.
+ * STATUS.  status[i], one byte per SNV (caller-allocated, may be NULL), checked in this order: 2: the reference's base at `position` is
+ * not A C G T U; 1: `ref` is given and differs from the reference's base (upper case, U as T); 3: `alt` equals the reference's base;
+ * 0: examined.  A SNV whose status is not 0 has no records. */
+typedef struct {                /* 12 bytes */
+  int32_t contig_index;
+  int32_t position;             /* 0-based, forward */
+  char ref;                     /* 0: not checked; else A C G T U, either case */
+  char alt;                     /* A C G T U, either case */
+  uint16_t reserved;            /* 0 */
+} calitas_snv_t;
+typedef struct {                /* 32 bytes */
+  calitas_site_t site;          /* the alt allele's site where one stands (kind & 1), else the reference's */
+  uint32_t snv_index;
+  uint8_t kind;                 /* 1: on alt only, 2: on the reference only, 3: on both */
+  int8_t other_pam_index;       /* kind 3: the reference site's pam_index; else -1 */
+  int8_t guide_offset;          /* where the SNV is, counted as the guide reads from the protospacer's first base:
+                                   0 .. L-1 inside it, L .. L+15 in a 3' PAM, -1 .. -16 in a 5' PAM */
+  uint8_t reserved;             /* 0 */
+  uint32_t guide_lo, guide_hi;  /* protospacer of `site`'s allele as the guide reads, bit-planes as calitas_near_hit_t's target_lo/hi */
+} calitas_allele_site_t;
+/* *sites: the records, one block for calitas_free, also when there are none.  n_snvs == 0 is legal.  On the device one lane takes one
+ * SNV: it holds the SNV against the contig's bounds, loads the words of the bit-planes and of the exception mask around it, matches
+ * the 64 protospacer starts whose footprint can hold the SNV bit-parallel on both alleles, and stores its count; after a scan of the
+ * workgroups' sums the same match stores every record at its place (no sort, no returning atomic); records and status bytes are
+ * copied back once each.  A SNV with a U of the reference within 63 bases is decided on the host by the twin's walk and its records
+ * are merged into place.
+ * Errors, in this order: CALITAS_ENODEV on a host-only context (the device calls); what calitas_find_sites refuses about the pattern;
+ * CALITAS_EINVAL, with a message that names the field and the first offending index, for n_snvs >= 2^32, a contig_index out of range
+ * or absent, a position at or beyond the contig's length, an alt or a non-zero ref that is not one of the letters, reserved != 0;
+ * CALITAS_ENOMEM when the SNVs and their records do not fit the device. */
+int calitas_find_allele_sites(calitas_ctx* ctx, const calitas_guide_t* pattern, const calitas_snv_t* snvs, uint64_t n_snvs,
+                              calitas_allele_site_t** sites, uint64_t* n_sites, uint8_t* status /* [n_snvs], may be NULL */);
+/* The first pass alone: *n_sites and, when per_kind is not NULL, the records per kind ([4]; [0] stays 0, they sum to *n_sites).  No
+ * records are copied back. */
+int calitas_count_allele_sites(calitas_ctx* ctx, const calitas_guide_t* pattern, const calitas_snv_t* snvs, uint64_t n_snvs,
+                               uint64_t* per_kind /* [4], may be NULL */, uint64_t* n_sites, uint8_t* status);
+/* The host twins: a base-by-base walk with one base replaced; also on a host-only context. */
+int calitas_find_allele_sites_host(const calitas_ctx* ctx, const calitas_guide_t* pattern, const calitas_snv_t* snvs, uint64_t n_snvs,
+                                   calitas_allele_site_t** sites, uint64_t* n_sites, uint8_t* status);
+int calitas_count_allele_sites_host(const calitas_ctx* ctx, const calitas_guide_t* pattern, const calitas_snv_t* snvs, uint64_t n_snvs,
+                                    uint64_t* per_kind, uint64_t* n_sites, uint8_t* status);
+
 /* SequentialGuideAligner.align on explicit (guide, target) pairs -- the per-task call of PairwiseAlignSequences
  * (PairwiseAlignSequences.scala:64 -> alignBest, SequentialGuideAligner.scala:333-345) and AlignToReference
  * (AlignToReference.scala:114-135 -> alignToRef / alignToRefBest, SequentialGuideAligner.scala:359-418).  Task t aligns
