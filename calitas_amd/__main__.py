@@ -124,6 +124,11 @@ def main(argv=None):
     fg.add_argument("--allele-sites", metavar="OUT.tsv",
                     help="with --alleles: write the sites each SNV creates (allele alt), destroys (ref) or changes (both) to OUT.tsv, one per line")
     fg.add_argument("--allele-kinds", metavar="alt,ref,both", help="with --alleles: the kinds of lines to write (default all three)")
+    fg.add_argument("--microhomology", metavar="MODEL",
+                    help="add mh_total_q16, mh_oof_q16, mh_score and out_of_frame: the microhomology score around every site's cut and the share of it that shifts the frame, under the model file (models/example_microhomology60.tsv shows the format), NA where a site has none")
+    fg.add_argument("--mh-cut", metavar="N", help="with --microhomology: the cut's position in the protospacer as the guide reads, 0 .. L (default L - 3 with a 3' PAM, required otherwise)")
+    fg.add_argument("--min-out-of-frame", metavar="PCT",
+                    help="with --microhomology: drop guides whose out_of_frame is below the integer PCT (0 .. 100), those whose mh_total_q16 is 0 and those without a score")
     fg.add_argument("-d", "--max-guide-diffs", type=int, default=Defaults.MaxGuideDiffs)
     fg.add_argument("-p", "--max-pam-mismatches", type=int, default=Defaults.MaxPamMismatches)
     fg.add_argument("-g", "--max-gaps-between-guide-and-pam", type=int, default=Defaults.MaxGapsBetweenGuideAndPam)
@@ -171,7 +176,7 @@ def main(argv=None):
     elif a.tool == "FindGuides":
         text = find_guides_tool(a.ref, a.guide, a.auxiliary_pams, chrom=a.chrom, start=a.start, end=a.end, output=a.output, counts=a.counts, scores=a.scores,
                                 device=a.device, gc_min=a.gc_min, gc_max=a.gc_max, max_run=a.max_run, avoid=a.avoid, copies=a.copies,
-                                seed_copies=a.seed_copies, max_copies=a.max_copies, max_seed_copies=a.max_seed_copies, near_copies=a.near_copies, max_near_copies=a.max_near_copies, near_scores=a.near_scores, near_list=a.near_list, near_list_limit=a.near_list_limit, activity=a.activity, min_activity=a.min_activity, regions=a.regions, classes=a.classes, class_extent=a.class_extent, pairs=a.pairs, pair_distance=a.pair_distance, pair_cut=a.pair_cut, pair_orientation=a.pair_orientation, alleles=a.alleles, allele_sites=a.allele_sites, allele_kinds=a.allele_kinds,
+                                seed_copies=a.seed_copies, max_copies=a.max_copies, max_seed_copies=a.max_seed_copies, near_copies=a.near_copies, max_near_copies=a.max_near_copies, near_scores=a.near_scores, near_list=a.near_list, near_list_limit=a.near_list_limit, activity=a.activity, min_activity=a.min_activity, regions=a.regions, classes=a.classes, class_extent=a.class_extent, pairs=a.pairs, pair_distance=a.pair_distance, pair_cut=a.pair_cut, pair_orientation=a.pair_orientation, alleles=a.alleles, allele_sites=a.allele_sites, allele_kinds=a.allele_kinds, microhomology=a.microhomology, mh_cut=a.mh_cut, min_out_of_frame=a.min_out_of_frame,
                                 max_guide_diffs=a.max_guide_diffs, max_pam_mismatches=a.max_pam_mismatches,
                                 max_gaps_between_guide_and_pam=a.max_gaps_between_guide_and_pam, max_total_diffs=a.max_total_diffs,
                                 max_overlap=a.max_overlap, guide_mismatch_net_cost=a.guide_mismatch_net_cost,

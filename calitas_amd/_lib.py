@@ -135,7 +135,19 @@ class AlleleSiteT(ctypes.Structure):
                 ("reserved", ctypes.c_uint8), ("guide_lo", ctypes.c_uint32), ("guide_hi", ctypes.c_uint32)]
 
 
-assert ctypes.sizeof(SnvT) == 12 and ctypes.sizeof(AlleleSiteT) == 32
+class MhModelT(ctypes.Structure):
+    _fields_ = [("left", ctypes.c_int32), ("right", ctypes.c_int32), ("cut_offset", ctypes.c_int32), ("min_length", ctypes.c_int32),
+                ("weight", ctypes.POINTER(ctypes.c_uint32))]
+
+
+class MhScoreT(ctypes.Structure):
+    _fields_ = [("total_q16", ctypes.c_uint32), ("out_of_frame_q16", ctypes.c_uint32)]
+
+
+assert ctypes.sizeof(SnvT) == 12 and ctypes.sizeof(AlleleSiteT) == 32 and ctypes.sizeof(MhScoreT) == 8
+MH_NONE = 0xFFFFFFFF
+MH_MAX_SIDE = 32
+MH_MAX_WEIGHT = 1 << 16
 PAIR_MAX_DISTANCE = 65535
 assert ctypes.sizeof(SitePairsT) == 12 and ctypes.sizeof(SitePairT) == 16
 TOP_MAX = 256
@@ -164,7 +176,8 @@ SYMBOLS = ["calitas_create", "calitas_destroy", "calitas_last_error", "calitas_f
            "calitas_find_sites_regions", "calitas_count_sites_regions", "calitas_find_sites_regions_host", "calitas_count_sites_regions_host",
            "calitas_site_presence",
            "calitas_find_site_pairs", "calitas_count_site_pairs", "calitas_find_site_pairs_host", "calitas_count_site_pairs_host",
-           "calitas_find_allele_sites", "calitas_count_allele_sites", "calitas_find_allele_sites_host", "calitas_count_allele_sites_host"]
+           "calitas_find_allele_sites", "calitas_count_allele_sites", "calitas_find_allele_sites_host", "calitas_count_allele_sites_host",
+           "calitas_find_sites_microhomology", "calitas_find_sites_microhomology_host"]
 
 if not os.path.exists(LIB_PATH):
     raise ImportError("%s is missing: build it with `make -C calitas_amd/csrc` (hipcc, gfx950). "
@@ -279,6 +292,11 @@ if hasattr(lib, "calitas_find_allele_sites"):      # (an older build behind CALI
     lib.calitas_count_allele_sites.argtypes = [ctypes.c_void_p, ctypes.POINTER(GuideT), ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64),
                                                ctypes.POINTER(ctypes.c_uint64), ctypes.c_void_p]
     lib.calitas_count_allele_sites_host.argtypes = lib.calitas_count_allele_sites.argtypes
+if hasattr(lib, "calitas_find_sites_microhomology"):   # (an older build behind CALITAS_LIB_PATH, for A/B runs, does not have it)
+    lib.calitas_find_sites_microhomology.argtypes = [ctypes.c_void_p, ctypes.POINTER(GuideT), ctypes.POINTER(SiteFilterT), ctypes.POINTER(MhModelT), ctypes.c_int32,
+                                                     ctypes.c_int32, ctypes.c_uint64, ctypes.c_uint64, ctypes.POINTER(ctypes.POINTER(SiteT)),
+                                                     ctypes.POINTER(ctypes.POINTER(MhScoreT)), ctypes.POINTER(ctypes.c_uint64)]
+    lib.calitas_find_sites_microhomology_host.argtypes = lib.calitas_find_sites_microhomology.argtypes
 lib.calitas_search_scores.argtypes = [ctypes.c_void_p, ctypes.POINTER(GuideT), ctypes.POINTER(ParamsT), ctypes.POINTER(ScoreModelT),
                                       ctypes.POINTER(ctypes.POINTER(ScoresT))]
 lib.calitas_search_scores_batch.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.POINTER(GuideT), ctypes.POINTER(ParamsT),

@@ -686,6 +686,47 @@ class Context:
         _lib.check(self._h, rc)
         return n.value
 
+    def find_sites_microhomology(self, pattern, model, cut_offset=None, min_out_of_frame=0, filter=None, chrom=None, start=0, end=None, host=False):
+        """calitas_find_sites_microhomology: (sites, scores) -- the records of find_sites(pattern, filter=filter) and, in a structured array
+        beside them (MH_SCORE_DTYPE: total_q16, out_of_frame_q16), each site's microhomology score around its cut under `model` (a
+        MicrohomologyModel; microhomology_of is the contract on one window).  cut_offset: bases into the protospacer as the guide reads,
+        0 .. L; None: L - 3, the Cas9 cut, which needs a 3' PAM.  A site whose window leaves its contig or holds a letter other than
+        A C G T U has MH_NONE in both.  min_out_of_frame: a per-mille 0 .. 1000 -- 0 keeps everything, otherwise only the scored sites with
+        total > 0 and out_of_frame * 1000 >= min_out_of_frame * total.  host=True: the host twin, also on a host-only context."""
+        import numpy as np
+        pattern, index, start, end = self._site_region(pattern, chrom, start, end)
+        if cut_offset is None:
+            if not pattern.pam_is_three_prime:
+                raise ValueError("cut_offset is required unless the pattern has a 3' PAM (then it is L - 3)")
+            cut_offset = pattern.protospacer_length - 3
+        g = pattern.to_c()
+        f = filter.to_c() if filter is not None else None
+        m = model.to_c(cut_offset) if model is not None else None
+        out, words, n = ctypes.POINTER(SiteT)(), ctypes.POINTER(_lib.MhScoreT)(), ctypes.c_uint64()
+        fn = lib.calitas_find_sites_microhomology_host if host else lib.calitas_find_sites_microhomology
+        rc = fn(self._h, ctypes.byref(g), ctypes.byref(f) if f is not None else None, ctypes.byref(m) if m is not None else None, int(min_out_of_frame),
+                index, start, end, ctypes.byref(out), ctypes.byref(words), ctypes.byref(n))
+        _lib.check(self._h, rc)
+        scores = self._take_records(words, n.value, _lib.MhScoreT, MH_SCORE_DTYPE)
+        return self._take_records(out, n.value, SiteT, SITE_DTYPE), scores
+
+    def count_sites_microhomology(self, pattern, model, cut_offset=None, min_out_of_frame=0, filter=None, chrom=None, start=0, end=None, host=False):
+        """calitas_find_sites_microhomology without its blocks: the number of sites find_sites_microhomology would return."""
+        pattern, index, start, end = self._site_region(pattern, chrom, start, end)
+        if cut_offset is None:
+            if not pattern.pam_is_three_prime:
+                raise ValueError("cut_offset is required unless the pattern has a 3' PAM (then it is L - 3)")
+            cut_offset = pattern.protospacer_length - 3
+        g = pattern.to_c()
+        f = filter.to_c() if filter is not None else None
+        m = model.to_c(cut_offset)
+        n = ctypes.c_uint64()
+        fn = lib.calitas_find_sites_microhomology_host if host else lib.calitas_find_sites_microhomology
+        rc = fn(self._h, ctypes.byref(g), ctypes.byref(f) if f is not None else None, ctypes.byref(m), int(min_out_of_frame), index, start, end, None, None,
+                ctypes.byref(n))
+        _lib.check(self._h, rc)
+        return n.value
+
     def _site_regions_opt(self, pattern, classes, extent):
         """The calitas_site_regions_t of classes (None: every class but "elsewhere"; names or indices of the context's Regions, or an
         integer mask) and extent ((from, to), None: the whole protospacer)."""
@@ -2346,3 +2387,157 @@ def activity_value(score_q16, model):
         return None
     x = int(score_q16) / 65536.0
     return x if model.link == "identity" else 1.0 / (1.0 + math.exp(-x))
+
+
+# ---- the microhomology score (include/calitas_hip.h has the contract) ----
+
+MH_NONE = _lib.MH_NONE
+MH_SCORE_DTYPE = [("total_q16", "<u4"), ("out_of_frame_q16", "<u4")]
+_MH_DECIMAL = None
+
+
+def _mh_q16(x):
+    """A decimal of a microhomology model file in [0, 1] as Q16: floor(x * 65536 + 0.5) in double.  Digits with at most one point,
+    nothing else: what both tools read alike."""
+    import math
+    import re
+    global _MH_DECIMAL
+    if _MH_DECIMAL is None:
+        _MH_DECIMAL = re.compile(r"([0-9]+\.?[0-9]*|\.[0-9]+)", re.ASCII)
+    if not _MH_DECIMAL.fullmatch(x) or not 0.0 <= float(x) <= 1.0:
+        raise ValueError("a weight of a microhomology model is a decimal in [0, 1], not %r" % (x,))
+    return int(math.floor(float(x) * 65536.0 + 0.5))
+
+
+def _mh_int(x):
+    if not (x.isascii() and x.isdigit() and len(x) <= 4):
+        raise ValueError("%r is not a number of a microhomology model" % (x,))
+    return int(x)
+
+
+class MicrohomologyModel:
+    """The weights of a microhomology score (calitas_mh_model_t without its cut): a window of `left` bases 5' and `right` bases 3' of the
+    cut as the guide reads (1 .. 32 each; W = left + right), min_length (2 .. 8), the shortest run that counts, and weight[W - 1],
+    unsigned Q16 values of at most 65536 by deletion length d - 1.  The library ships no published table: exponential() gives the
+    published shape exp(-d / tau), read() loads any table from a TSV with `#` comments and the lines
+
+        window<TAB>LEFT<TAB>RIGHT
+        min_length<TAB>N
+        weight<TAB>DEL<TAB>x
+
+    DEL is a deletion length 1 .. W - 1 or `*` for every one; x is a decimal in [0, 1], converted as floor(x * 65536 + 0.5); entries not
+    given are 0, later lines override earlier ones, a file without a `min_length` line has 2."""
+
+    def __init__(self, left, right, weight, min_length=2):
+        import numpy as np
+        self.left, self.right, self.min_length = int(left), int(right), int(min_length)
+        self.W = self.left + self.right
+        self.weight = np.ascontiguousarray(weight, dtype=np.uint32)
+        if self.W < 2 or self.weight.shape != (self.W - 1,):
+            raise ValueError("a microhomology model of W = %d letters has W - 1 weights, not %r" % (self.W, self.weight.shape))
+
+    @classmethod
+    def exponential(cls, tau, left, right, min_length=2):
+        """weight[d - 1] = floor(exp(-d / tau) * 65536 + 0.5), d = 1 .. left + right - 1."""
+        import math
+        return cls(left, right, [int(math.floor(math.exp(-d / float(tau)) * 65536.0 + 0.5)) for d in range(1, int(left) + int(right))], min_length)
+
+    def __eq__(self, other):
+        import numpy as np
+        return (isinstance(other, MicrohomologyModel) and (self.left, self.right, self.min_length) == (other.left, other.right, other.min_length)
+                and np.array_equal(self.weight, other.weight))
+
+    __hash__ = None
+
+    def to_c(self, cut_offset):
+        m = _lib.MhModelT()
+        m.left, m.right, m.cut_offset, m.min_length = self.left, self.right, int(cut_offset), self.min_length
+        m.weight = self.weight.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32))
+        m._keep = self.weight
+        return m
+
+    @classmethod
+    def read(cls, path):
+        import numpy as np
+        window, min_length, lines = None, 2, []
+        with open(path) as f:
+            for ln in f:
+                ln = ln.split("#", 1)[0].strip()
+                if not ln:
+                    continue
+                fld = ln.split("\t")
+                try:
+                    if fld[0] == "window" and len(fld) == 3:
+                        window = (_mh_int(fld[1]), _mh_int(fld[2]))
+                    elif fld[0] == "min_length" and len(fld) == 2:
+                        min_length = _mh_int(fld[1])
+                    elif fld[0] == "weight" and len(fld) == 3:
+                        lines.append(fld)
+                    else:
+                        raise ValueError("not a line of a microhomology model: %r" % ln)
+                except ValueError as e:
+                    raise ValueError("%s: %s" % (path, e)) from None
+        if window is None or not (1 <= window[0] <= _lib.MH_MAX_SIDE and 1 <= window[1] <= _lib.MH_MAX_SIDE):
+            raise ValueError("%s: a microhomology model needs a `window` line with 1 .. 32 bases on either side" % path)
+        if not 2 <= min_length <= 8:
+            raise ValueError("%s: the `min_length` of a microhomology model is 2 .. 8" % path)
+        W = window[0] + window[1]
+        weight = np.zeros(W - 1, np.uint32)
+        try:
+            for fld in lines:
+                v = _mh_q16(fld[2])
+                if fld[1] == "*":
+                    weight[:] = v
+                    continue
+                d = _mh_int(fld[1])
+                if not 1 <= d <= W - 1:
+                    raise ValueError("%r is not a deletion length of this microhomology model" % (fld[1],))
+                weight[d - 1] = v
+        except ValueError as e:
+            raise ValueError("%s: %s" % (path, e)) from None
+        return cls(window[0], window[1], weight, min_length)
+
+    def write(self, path):
+        """The model as a file read() gives back exactly: every weight as the shortest decimal that rounds to it."""
+        def dec(q):
+            for digits in range(1, 12):
+                t = "%.*f" % (digits, q / 65536.0)
+                if _mh_q16(t) == q:
+                    return t
+            raise ValueError("weight %r is not a Q16 value within [0, 1]" % (q,))
+        with open(path, "w") as f:
+            f.write("# calitas microhomology model: unsigned Q16 weights by deletion length as decimals (x -> floor(x * 65536 + 0.5)); entries not given are 0\n")
+            f.write("window\t%d\t%d\nmin_length\t%d\n" % (self.left, self.right, self.min_length))
+            for d in range(1, self.W):
+                if int(self.weight[d - 1]):
+                    f.write("weight\t%d\t%s\n" % (d, dec(int(self.weight[d - 1]))))
+
+
+def microhomology_of(window, left, model):
+    """The contract of calitas_find_sites_microhomology on one window -- W letters as the guide reads, `left` of them before the cut -- in
+    plain Python integers: (total_q16, out_of_frame_q16), or None when a letter is not one of A C G T U (either case).  A plain walk
+    along every diagonal; nothing of the library is called."""
+    left = int(left)
+    W = len(window)
+    if W != model.W or left != model.left:
+        raise ValueError("the window has %d letters, %d before the cut; the model's has %d and %d" % (W, left, model.W, model.left))
+    x = window.upper().replace("U", "T")
+    if any(ch not in "ACGT" for ch in x):
+        return None
+    total = oof = 0
+    for d in range(1, W):
+        lo, hi = max(0, left - d), min(left, W - d)
+        units = k = g = 0
+        for i in range(lo, hi + 1):
+            if i < hi and x[i] == x[i + d]:
+                k += 1
+                g += x[i] in "GC"
+                continue
+            if k >= model.min_length:
+                units += k + g
+            k = g = 0
+        term = int(model.weight[d - 1]) * units
+        total += term
+        if d % 3:
+            oof += term
+    return total, oof

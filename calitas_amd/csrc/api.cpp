@@ -1448,4 +1448,26 @@ int calitas_count_allele_sites_host(const calitas_ctx* ctx, const calitas_guide_
   return calitas_find_allele_sites_host_impl(ctx, pattern, snvs, n_snvs, false, nullptr, per_kind, n_sites, status);
 }
 
+// Microhomology scores (sites_host.cpp, microhomology.hip): no reference counterpart.
+// (the model is the implementation's to check: it comes after everything calitas_find_sites_filtered refuses)
+int calitas_find_sites_microhomology(calitas_ctx* ctx, const calitas_guide_t* pattern, const calitas_site_filter_t* filter, const calitas_mh_model_t* model,
+                                     int32_t min_out_of_frame_permille, int32_t chrom_index, uint64_t start, uint64_t end, calitas_site_t** sites,
+                                     calitas_mh_score_t** scores, uint64_t* n_sites) {
+  if (!ctx) return CALITAS_EINVAL;
+  if (!pattern || !n_sites || (sites == nullptr) != (scores == nullptr)) return fail(ctx, CALITAS_EINVAL, "NULL argument");
+  *n_sites = 0;
+  if (sites) { *sites = nullptr; *scores = nullptr; }
+  return calitas_find_sites_microhomology_impl(ctx, pattern, filter, model, min_out_of_frame_permille, chrom_index, start, end, sites, scores, n_sites);
+}
+
+int calitas_find_sites_microhomology_host(const calitas_ctx* ctx, const calitas_guide_t* pattern, const calitas_site_filter_t* filter,
+                                          const calitas_mh_model_t* model, int32_t min_out_of_frame_permille, int32_t chrom_index, uint64_t start,
+                                          uint64_t end, calitas_site_t** sites, calitas_mh_score_t** scores, uint64_t* n_sites) {
+  if (!ctx) return CALITAS_EINVAL;
+  if (!pattern || !n_sites || (sites == nullptr) != (scores == nullptr)) return fail(const_cast<calitas_ctx*>(ctx), CALITAS_EINVAL, "NULL argument");
+  *n_sites = 0;
+  if (sites) { *sites = nullptr; *scores = nullptr; }
+  return calitas_find_sites_microhomology_host_impl(ctx, pattern, filter, model, min_out_of_frame_permille, chrom_index, start, end, sites, scores, n_sites);
+}
+
 }  // extern "C"

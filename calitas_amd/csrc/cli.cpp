@@ -47,6 +47,10 @@ static void usage() {
     "         [--pair-orientation out|in|same|any|CODE,... (with --pairs: default out, the PAMs facing outwards; codes ++ -+ +- --)]\n"
     "         [--alleles FILE.vcf[.gz] --allele-sites out.tsv (the sites each SNV of the region creates, destroys or changes, one per line)]\n"
     "         [--allele-kinds alt,ref,both (with --alleles: the kinds of lines to write; default all three)]\n"
+    "         [--microhomology model.tsv (the columns mh_total_q16, mh_oof_q16, mh_score and out_of_frame: the microhomology score around every site's\n"
+    "          cut and the share of it that shifts the frame, NA where a site has none)] [--mh-cut N (default L - 3 with a 3' PAM, required otherwise)]\n"
+    "         [--min-out-of-frame PCT (with --microhomology: drop rows whose out_of_frame is below the integer PCT, 0 .. 100, rows whose total is 0\n"
+    "          and rows without a score, before any other flag looks at them)]\n"
     "         [--device N (-1: the host twin, no GPU)]\n");
 }
 
@@ -251,6 +255,75 @@ static bool read_activity_model(const std::string& path, ActivityModelFile& out,
   return true;
 }
 
+// A microhomology model file (calitas_amd/aligner.py, MicrohomologyModel.read: the same lines accepted and refused, the same integers):
+// `#` comments, window / min_length / weight lines, `*` for every deletion length, later lines override earlier ones.
+struct MhModelFile {
+  int left = 0, right = 0, min_length = 2;
+  std::vector<uint32_t> weight;
+};
+// a decimal as both tools read it -- digits, at most one point, no sign -- within [0, 1], as Q16
+static bool mh_decimal(const std::string& x, uint32_t* v) {
+  size_t digits = 0, points = 0;
+  for (size_t k = 0; k < x.size(); k++) {
+    if (x[k] >= '0' && x[k] <= '9') digits++;
+    else if (x[k] == '.' && points == 0) points++;
+    else return false;
+  }
+  if (digits == 0) return false;
+  const double d = std::strtod(x.c_str(), nullptr);
+  if (!(d >= 0.0 && d <= 1.0)) return false;
+  *v = (uint32_t)std::floor(d * 65536.0 + 0.5);
+  return true;
+}
+static bool read_mh_model(const std::string& path, MhModelFile& out, std::string& err) {
+  FILE* f = std::fopen(path.c_str(), "r");
+  if (!f) { err = "cannot read " + path; return false; }
+  std::string text;
+  char buf[65536];
+  size_t got;
+  while ((got = std::fread(buf, 1, sizeof buf, f)) > 0) text.append(buf, got);
+  std::fclose(f);
+  std::vector<std::vector<std::string>> lines;
+  bool have_window = false;
+  for (size_t at = 0; at < text.size();) {
+    size_t nl = text.find('\n', at);
+    if (nl == std::string::npos) nl = text.size();
+    std::string ln = text.substr(at, nl - at);
+    at = nl + 1;
+    const size_t hash = ln.find('#');
+    if (hash != std::string::npos) ln.erase(hash);
+    while (!ln.empty() && std::isspace((unsigned char)ln.back())) ln.pop_back();
+    size_t b = 0;
+    while (b < ln.size() && std::isspace((unsigned char)ln[b])) b++;
+    ln.erase(0, b);
+    if (ln.empty()) continue;
+    std::vector<std::string> fld;
+    for (size_t i = 0;;) { const size_t t = ln.find('\t', i); fld.push_back(ln.substr(i, t == std::string::npos ? t : t - i)); if (t == std::string::npos) break; i = t + 1; }
+    bool ok = true;
+    if (fld[0] == "window" && fld.size() == 3) { ok = activity_int(fld[1], &out.left) && activity_int(fld[2], &out.right); have_window = true; }
+    else if (fld[0] == "min_length" && fld.size() == 2) ok = activity_int(fld[1], &out.min_length);
+    else if (fld[0] == "weight" && fld.size() == 3) lines.push_back(fld);
+    else ok = false;
+    if (!ok) { err = path + ": not a line of a microhomology model: " + ln; return false; }
+  }
+  if (!have_window || out.left < 1 || out.left > CALITAS_MH_MAX_SIDE || out.right < 1 || out.right > CALITAS_MH_MAX_SIDE) {
+    err = path + ": a microhomology model needs a `window` line with 1 .. 32 bases on either side";
+    return false;
+  }
+  if (out.min_length < 2 || out.min_length > 8) { err = path + ": the `min_length` of a microhomology model is 2 .. 8"; return false; }
+  const int W = out.left + out.right;
+  out.weight.assign((size_t)W - 1, 0);
+  for (auto& fld : lines) {
+    uint32_t v = 0;
+    if (!mh_decimal(fld[2], &v)) { err = path + ": a weight of a microhomology model is a decimal in [0, 1], not " + fld[2]; return false; }
+    if (fld[1] == "*") { out.weight.assign((size_t)W - 1, v); continue; }
+    int d = 0;
+    if (!activity_int(fld[1], &d) || d < 1 || d > W - 1) { err = path + ": " + fld[1] + " is not a deletion length of this microhomology model"; return false; }
+    out.weight[(size_t)d - 1] = v;
+  }
+  return true;
+}
+
 // `calitas FindGuides`: the sites of an IUPAC pattern in a region as the guides a search takes -- the table of
 // `python -m calitas_amd FindGuides`, byte for byte (calitas_amd/tools.py guides_tsv).  No reference counterpart.
 // --regions FILE.bed: four columns (chromosome, start, end, class name; more are ignored); lines that start with #, track or browser
@@ -389,6 +462,8 @@ static int find_guides_main(int argc, char** argv) {
   bool have_pair_distance = false, have_pair_cut = false, have_pair_orientation = false;
   std::string alleles_path, allele_sites_path, allele_kinds;             // --alleles FILE.vcf --allele-sites OUT.tsv [--allele-kinds alt,ref,both]
   bool have_allele_kinds = false;
+  std::string mh_path, mh_cut, min_oof;                                  // --microhomology MODEL.tsv [--mh-cut N] [--min-out-of-frame PCT]
+  bool have_mh_cut = false, have_min_oof = false;
   for (int i = 2; i < argc; i++) {
     std::string a = argv[i], val;
     size_t eq = a.find('=');
@@ -432,6 +507,9 @@ static int find_guides_main(int argc, char** argv) {
     else if (a == "--alleles") alleles_path = next();
     else if (a == "--allele-sites") allele_sites_path = next();
     else if (a == "--allele-kinds") { allele_kinds = next(); have_allele_kinds = true; }
+    else if (a == "--microhomology") mh_path = next();
+    else if (a == "--mh-cut") { mh_cut = next(); have_mh_cut = true; }
+    else if (a == "--min-out-of-frame") { min_oof = next(); have_min_oof = true; }
     else { std::fprintf(stderr, "unknown argument %s\n", a.c_str()); usage(); return 2; }
   }
   if (pattern.empty() || ref.empty()) { usage(); return 2; }
@@ -554,6 +632,29 @@ static int find_guides_main(int argc, char** argv) {
     if (!any_name) { std::fprintf(stderr, "calitas: --pair-orientation is empty: out, in, same, any, or codes among ++ -+ +- --\n"); return 2; }
     pair_rule.orientations = (uint8_t)mask;
   }
+  // --microhomology: the model, the cut and the per-mille from their flags (tools.py find_guides_tool)
+  const bool have_mh = !mh_path.empty();
+  if (!have_mh && (have_mh_cut || have_min_oof)) { std::fprintf(stderr, "calitas: --mh-cut and --min-out-of-frame require --microhomology MODEL\n"); return 2; }
+  MhModelFile mh_file;
+  calitas_mh_model_t mh_model{0, 0, 0, 0, nullptr};
+  int32_t mh_permille = 0;
+  if (have_mh) {
+    std::string err;
+    if (!read_mh_model(mh_path, mh_file, err)) { std::fprintf(stderr, "calitas: %s\n", err.c_str()); return 2; }
+    const auto digits = [](const std::string& t, size_t most) { return !t.empty() && t.size() <= most && t.find_first_not_of("0123456789") == std::string::npos; };
+    if (!have_mh_cut && !three_prime) { std::fprintf(stderr, "calitas: --mh-cut N is required: the default, L - 3, is the Cas9 cut of a pattern with a 3' PAM\n"); return 2; }
+    if (have_mh_cut && !(digits(mh_cut, 3) && std::atol(mh_cut.c_str()) <= (long)pg.proto.size())) {
+      std::fprintf(stderr, "calitas: --mh-cut N: N is 0 .. %zu, the protospacer's length, not %s\n", pg.proto.size(), mh_cut.c_str());
+      return 2;
+    }
+    if (have_min_oof && !(digits(min_oof, 3) && std::atol(min_oof.c_str()) <= 100)) {
+      std::fprintf(stderr, "calitas: --min-out-of-frame PCT: PCT is an integer 0 .. 100, not %s\n", min_oof.c_str());
+      return 2;
+    }
+    mh_model.left = mh_file.left; mh_model.right = mh_file.right; mh_model.min_length = mh_file.min_length; mh_model.weight = mh_file.weight.data();
+    mh_model.cut_offset = have_mh_cut ? (int32_t)std::atol(mh_cut.c_str()) : (int32_t)pg.proto.size() - 3;     // (below 0: the library refuses it)
+    mh_permille = have_min_oof ? 10 * (int32_t)std::atol(min_oof.c_str()) : 0;
+  }
   calitas_ctx* ctx = nullptr;
   if (calitas_create(device, &ctx) != CALITAS_OK) { std::fprintf(stderr, "calitas: %s\n", calitas_last_error(nullptr)); return 1; }
   auto die = [&](const char* what) { std::fprintf(stderr, "calitas: %s: %s\n", what, calitas_last_error(ctx)); calitas_destroy(ctx); std::exit(1); };
@@ -576,6 +677,8 @@ static int find_guides_main(int argc, char** argv) {
   calitas_site_t* sites = nullptr; uint64_t n_sites = 0;
   uint8_t* site_class = nullptr;       // with --regions: a class per site
   int32_t* activity_q16 = nullptr;     // with --activity: a score per site, from the listing's own call (tools.py find_guides)
+  calitas_mh_score_t* mh_q16 = nullptr; // with --microhomology: the two sums per site, from a listing of its own
+  const bool mh_alone = have_mh && !have_activity && !have_regions;
   int rc;
   if (have_activity) {
     calitas_activity_model_t m;
@@ -586,6 +689,9 @@ static int find_guides_main(int argc, char** argv) {
   } else if (have_regions) {
     rc = device < 0 ? calitas_find_sites_regions_host(ctx, &g, keep, &by_class, chrom_index, start, end, &sites, &site_class, &n_sites)
                     : calitas_find_sites_regions(ctx, &g, keep, &by_class, chrom_index, start, end, &sites, &site_class, &n_sites);
+  } else if (mh_alone) {
+    rc = device < 0 ? calitas_find_sites_microhomology_host(ctx, &g, keep, &mh_model, mh_permille, chrom_index, start, end, &sites, &mh_q16, &n_sites)
+                    : calitas_find_sites_microhomology(ctx, &g, keep, &mh_model, mh_permille, chrom_index, start, end, &sites, &mh_q16, &n_sites);
   } else {
     rc = device < 0 ? calitas_find_sites_filtered_host(ctx, &g, keep, chrom_index, start, end, &sites, &n_sites)
                     : calitas_find_sites_filtered(ctx, &g, keep, chrom_index, start, end, &sites, &n_sites);
@@ -611,10 +717,35 @@ static int find_guides_main(int argc, char** argv) {
     n_sites = n;
     calitas_free(classed);
   }
+  if (have_mh && !mh_alone) {
+    // the same walk again: the microhomology listing over the same region, joined on (contig, protospacer start, strand); a site the
+    // per-mille dropped has no partner and goes
+    calitas_site_t* scored = nullptr; uint64_t n_scored = 0;
+    rc = device < 0 ? calitas_find_sites_microhomology_host(ctx, &g, keep, &mh_model, mh_permille, chrom_index, start, end, &scored, &mh_q16, &n_scored)
+                    : calitas_find_sites_microhomology(ctx, &g, keep, &mh_model, mh_permille, chrom_index, start, end, &scored, &mh_q16, &n_scored);
+    if (rc != CALITAS_OK) die("scoring microhomology");
+    const auto less = [](const calitas_site_t& x, const calitas_site_t& y) {
+      if (x.contig_index != y.contig_index) return x.contig_index < y.contig_index;
+      if (x.protospacer_start != y.protospacer_start) return x.protospacer_start < y.protospacer_start;
+      return x.strand == '+' && y.strand == '-';
+    };
+    uint64_t n = 0;
+    for (uint64_t i = 0, j = 0; i < n_sites; i++) {
+      while (j < n_scored && less(scored[j], sites[i])) j++;
+      if (j < n_scored && !less(sites[i], scored[j])) {              // (n <= i and n <= j: nothing is overwritten before it is read)
+        sites[n] = sites[i]; mh_q16[n] = mh_q16[j];
+        if (activity_q16) activity_q16[n] = activity_q16[i];
+        if (site_class) site_class[n] = site_class[i];
+        n++;
+      }
+    }
+    n_sites = n;
+    calitas_free(scored);
+  }
   FILE* f = output.empty() ? stdout : std::fopen(output.c_str(), "w");
-  if (!f) { std::fprintf(stderr, "cannot write %s\n", output.c_str()); calitas_free(sites); calitas_free(activity_q16); calitas_free(site_class); calitas_destroy(ctx); return 1; }
-  std::fprintf(f, "guide_id\tchromosome\tstart\tend\tstrand\tpam_index\tguide\tpam_sequence%s%s%s%s", have_regions ? "\tclass" : "", have_activity ? "\tactivity_q16\tactivity" : "",
-               copies ? "\tcopies" : "", have_seed ? "\tseed_copies" : "");
+  if (!f) { std::fprintf(stderr, "cannot write %s\n", output.c_str()); calitas_free(sites); calitas_free(activity_q16); calitas_free(site_class); calitas_free(mh_q16); calitas_destroy(ctx); return 1; }
+  std::fprintf(f, "guide_id\tchromosome\tstart\tend\tstrand\tpam_index\tguide\tpam_sequence%s%s%s%s%s", have_regions ? "\tclass" : "", have_activity ? "\tactivity_q16\tactivity" : "",
+               have_mh ? "\tmh_total_q16\tmh_oof_q16\tmh_score\tout_of_frame" : "", copies ? "\tcopies" : "", have_seed ? "\tseed_copies" : "");
   for (long long d = 0; have_near && d <= near_m; d++) std::fprintf(f, "\tcopies_mm%lld", d);
   if (have_near_scores) std::fprintf(f, "\tnear_sum_q32\tnear_max_q32\tnear_specificity");
   std::fprintf(f, "\n");
@@ -710,6 +841,13 @@ static int find_guides_main(int argc, char** argv) {
     else if (have_activity) {
       const double x = (double)activity_q16[i] / 65536.0;
       std::fprintf(f, "\t%d\t%.6f", (int)activity_q16[i], act.link ? 1.0 / (1.0 + std::exp(-x)) : x);
+    }
+    if (have_mh && mh_q16[i].total_q16 == CALITAS_MH_NONE) std::fprintf(f, "\tNA\tNA\tNA\tNA");
+    else if (have_mh) {
+      const double total = (double)mh_q16[i].total_q16, oof = (double)mh_q16[i].out_of_frame_q16;
+      std::fprintf(f, "\t%u\t%u\t%.3f", (unsigned)mh_q16[i].total_q16, (unsigned)mh_q16[i].out_of_frame_q16, 100.0 * total / 65536.0);
+      if (mh_q16[i].total_q16) std::fprintf(f, "\t%.2f", 100.0 * oof / total);
+      else std::fprintf(f, "\tNA");
     }
     if (copies) std::fprintf(f, "\t%llu", (unsigned long long)n_copies[(size_t)i]);
     if (have_seed) std::fprintf(f, "\t%llu", (unsigned long long)n_seed[(size_t)i]);
@@ -883,7 +1021,7 @@ static int find_guides_main(int argc, char** argv) {
     calitas_free(found);
   }
   std::fprintf(stderr, "calitas: %llu guides\n", (unsigned long long)n_rows);
-  calitas_free(sites); calitas_free(activity_q16); calitas_free(site_class); calitas_destroy(ctx);
+  calitas_free(sites); calitas_free(activity_q16); calitas_free(site_class); calitas_free(mh_q16); calitas_destroy(ctx);
   return 0;
 }
 

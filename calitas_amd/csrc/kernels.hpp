@@ -1,4 +1,4 @@
-// kernels.hpp -- launch interface of scan_columns.hip, scan_rows.hip, align.hip, trace.hip, setup.hip, sites.hip, activity.hip, site_pairs.hip and allele_sites.hip (device pointers only).
+// kernels.hpp -- launch interface of scan_columns.hip, scan_rows.hip, align.hip, trace.hip, setup.hip, sites.hip, activity.hip, site_pairs.hip, allele_sites.hip and microhomology.hip (device pointers only).
 #pragma once
 #include "mailbox.hpp"
 #include <hip/hip_runtime_api.h>
@@ -395,5 +395,41 @@ inline uint32_t allele_blocks(uint64_t n) { return (uint32_t)((n + ALLELE_THREAD
 hipError_t launch_allele_count(const AlleleArgs& a, hipStream_t stream);
 // The records in (SNV, start, strand) order: record k of SNV i of workgroup g goes to wg_offset[g] + the counts of g's lanes before i + k.
 hipError_t launch_allele_write(const AlleleArgs& a, hipStream_t stream);
+
+// microhomology.hip: calitas_find_sites_microhomology.  The records launch_sites_write left on the device, one lane per record: the
+// window of W = left + right bases around the cut, from the planes, brought to bit 0 of two 64-bit planes; every deletion length d is
+// one diagonal -- two shifts, two XORs, the runs of min_length and more, a popcount.  The weights travel in the argument
+// block: d is a loop counter, so weight[d - 1] is a scalar load.
+constexpr int MH_THREADS = 256;
+constexpr int MH_MAX_W = 64;
+constexpr uint32_t MH_NONE = 0xFFFFFFFFu;                // = CALITAS_MH_NONE
+constexpr uint32_t MH_HOST_DECIDES = 0xFFFFFFFEu;        // out_of_frame beside total == MH_NONE: the window holds an exception base (N, IUPAC
+                                                         // code, U): scored on the host, always kept
+struct MhScore { uint32_t total, out_of_frame; };        // = calitas_mh_score_t
+static_assert(sizeof(MhScore) == 8, "one 8-byte store per record");
+struct MhArgs {
+  const uint2* planes;
+  const uint32_t* mask;
+  const ContigInfo* contigs;
+  const SiteRecord* recs;          // n records, 16-byte aligned
+  MhScore* scores;                 // n
+  uint32_t* wg_kept;               // per workgroup: records kept under permille (or the host decides); nullptr: no threshold
+  uint64_t n;
+  uint64_t n_words;                // 32-base words of the packed space
+  int32_t n_contigs;
+  int32_t L, left, right, cut, min_length;
+  uint32_t permille;               // 1 .. 1000 with wg_kept
+  uint32_t weight[MH_MAX_W - 1];   // [d - 1], Q16; W - 1 of them are read
+};
+// kept under a threshold of `permille` >= 1: a scored site with total > 0 whose out-of-frame share reaches it, or one the host decides
+CAL_HD inline bool mh_kept(MhScore s, uint32_t permille) {
+  if (s.total == MH_NONE) return s.out_of_frame == MH_HOST_DECIDES;
+  return s.total > 0 && (uint64_t)s.out_of_frame * 1000u >= (uint64_t)permille * s.total;
+}
+hipError_t launch_mh_score(const MhArgs& a, hipStream_t stream);
+// The kept records and their scores, in order: record i of workgroup g goes to wg_offset[g] + its rank among g's kept records.
+hipError_t launch_mh_compact(const SiteRecord* recs, const MhScore* scores, uint64_t n, uint32_t permille, const uint64_t* wg_offset,
+                             SiteRecord* out_recs, MhScore* out_scores, uint64_t out_capacity, hipStream_t stream);
+inline uint32_t mh_blocks(uint64_t n) { return (uint32_t)((n + MH_THREADS - 1) / MH_THREADS); }
 
 }  // namespace calitas

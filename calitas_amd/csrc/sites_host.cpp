@@ -14,7 +14,9 @@
 // calitas_count_site_pairs and their host twins: the checks, the one walk over a sorted listing (pair_walk) that the twins and the
 // listings beside a U share, and the driver of site_pairs.hip's kernels behind the site kernel's two passes.  calitas_find_allele_sites / calitas_count_allele_sites and
 // their host twins: the checks, the twin (a base-by-base walk with one base replaced) that also decides the SNVs beside a U, and the
-// driver of allele_sites.hip's two kernels.  No reference counterpart.
+// driver of allele_sites.hip's two kernels.  calitas_find_sites_microhomology / calitas_find_sites_microhomology_host: the model's checks, the
+// score of one site as a diagonal walk over letters, the host twin, and the driver of microhomology.hip's kernels behind the site
+// kernel's two passes with the correction of records and scores beside a U.  No reference counterpart.
 #include "sites.hpp"
 #include "site_regions.hpp"
 #include "tuning.hpp"
@@ -273,6 +275,16 @@ struct SitesWork {
   unsigned long long* d_al_by = nullptr;
   AlleleSite* d_al_out = nullptr;
   size_t al_out_cap = 0;
+  // calitas_find_sites_microhomology: a score per record of d_out, the workgroups' kept counts and their scan, and the kept records and
+  // scores in order
+  MhScore* d_mh_scores = nullptr;
+  size_t mh_scores_cap = 0;
+  uint32_t* d_mh_count = nullptr;
+  uint64_t* d_mh_off = nullptr;
+  size_t mh_blocks_cap = 0;
+  SiteRecord* d_mh_out = nullptr;
+  MhScore* d_mh_out_scores = nullptr;
+  size_t mh_out_cap = 0;
   // the U / u runs of the resident reference (a U is a plain base to a site and an exception base to the kernels)
   uint64_t u_serial = ~0ull;
   std::vector<Run> u_runs;
@@ -288,6 +300,7 @@ void sites_destroy(SitesWork* w) {
   (void)hipFree(w->d_act_table); (void)hipFree(w->d_act_scores); (void)hipFree(w->d_act_count); (void)hipFree(w->d_act_off); (void)hipFree(w->d_act_out); (void)hipFree(w->d_act_out_scores);
   (void)hipFree(w->d_pair_lanes); (void)hipFree(w->d_pair_count); (void)hipFree(w->d_pair_off); (void)hipFree(w->d_pair_by); (void)hipFree(w->d_pair_out);
   (void)hipFree(w->d_snvs); (void)hipFree(w->d_al_lanes); (void)hipFree(w->d_al_status); (void)hipFree(w->d_al_count); (void)hipFree(w->d_al_off); (void)hipFree(w->d_al_by); (void)hipFree(w->d_al_out);
+  (void)hipFree(w->d_mh_scores); (void)hipFree(w->d_mh_count); (void)hipFree(w->d_mh_off); (void)hipFree(w->d_mh_out); (void)hipFree(w->d_mh_out_scores);
   delete w;
 }
 
@@ -2231,4 +2244,285 @@ int calitas_find_allele_sites_impl(calitas_ctx* ctx, const calitas_guide_t* patt
   }
   *sites = block;
   return CALITAS_OK;
+}
+
+// ---- calitas_find_sites_microhomology: every site's microhomology score and the out-of-frame share of it ----
+
+namespace {
+
+struct MhCall {
+  SiteCall site;
+  const calitas_mh_model_t* model = nullptr;
+  int L = 0, W = 0;
+  uint32_t permille = 0;             // 0: every site is kept; else mh_kept decides
+};
+
+// checked in this order: what calitas_find_sites_filtered checks (plan_sites), then the model, field by field, then the threshold
+int plan_microhomology(calitas_ctx* c, const calitas_guide_t* pattern, const calitas_site_filter_t* filter, const calitas_mh_model_t* model,
+                       int32_t permille, int32_t chrom_index, uint64_t start, uint64_t end, MhCall& call) {
+  static_assert(2 * CALITAS_MH_MAX_SIDE == MH_MAX_W, "the kernel's three words hold the widest window");
+  static_assert(MH_NONE == CALITAS_MH_NONE && sizeof(MhScore) == sizeof(calitas_mh_score_t), "the kernel stores the contract's values");
+  if (int rc = plan_sites(c, pattern, filter, chrom_index, start, end, call.site)) return rc;
+  const int L = call.site.tab.pat.proto_len;
+  if (!model) return calitas_fail(c, CALITAS_EINVAL, "microhomology model: model is NULL");
+  if (!model->weight) return calitas_fail(c, CALITAS_EINVAL, "microhomology model: weight is NULL");
+  if (model->left < 1 || model->left > CALITAS_MH_MAX_SIDE) return calitas_fail(c, CALITAS_EINVAL, "microhomology model: left is " + std::to_string(model->left) + ": it is 1 .. 32");
+  if (model->right < 1 || model->right > CALITAS_MH_MAX_SIDE) return calitas_fail(c, CALITAS_EINVAL, "microhomology model: right is " + std::to_string(model->right) + ": it is 1 .. 32");
+  if (model->cut_offset < 0 || model->cut_offset > L)
+    return calitas_fail(c, CALITAS_EINVAL, "microhomology model: cut_offset is " + std::to_string(model->cut_offset) + ": it is 0 .. " + std::to_string(L) + ", the protospacer's length");
+  if (model->min_length < 2 || model->min_length > 8) return calitas_fail(c, CALITAS_EINVAL, "microhomology model: min_length is " + std::to_string(model->min_length) + ": it is 2 .. 8");
+  const int W = model->left + model->right;
+  for (int d = 1; d < W; d++)
+    if (model->weight[d - 1] > CALITAS_MH_MAX_WEIGHT) return calitas_fail(c, CALITAS_EINVAL, "microhomology model: weight[" + std::to_string(d - 1) + "] lies above 65536 (1.0)");
+  if (permille < 0 || permille > 1000) return calitas_fail(c, CALITAS_EINVAL, "min_out_of_frame_permille is " + std::to_string(permille) + ": it is 0 .. 1000");
+  call.model = model; call.L = L; call.W = W; call.permille = (uint32_t)permille;
+  return CALITAS_OK;
+}
+
+const calitas_mh_score_t MH_UNSCORED = {CALITAS_MH_NONE, CALITAS_MH_NONE};
+
+// The contract on one site, letter by letter: the window's letters from PackedRef::base_upper, turned as the guide reads, then every
+// diagonal d walked from lo(d) to hi(d) with the current run's length and its G + C count.  *flagged: the window lies in the contig
+// and holds an exception base -- a U among them -- which is when the kernel leaves the site to the host.
+calitas_mh_score_t mh_at(const PackedRef& ref, const calitas_mh_model_t& m, int L, const calitas_site_t& s, bool* flagged) {
+  const int left = m.left, right = m.right, W = left + right;
+  const bool minus = s.strand == '-';
+  const ContigInfo& ci = ref.contigs[(size_t)s.contig_index];
+  const int64_t cut = (int64_t)s.protospacer_start + (minus ? L - m.cut_offset : m.cut_offset);
+  const int64_t first = cut - (minus ? right : left);
+  *flagged = false;
+  if (first < 0 || (uint64_t)(first + W) > ci.len) return MH_UNSCORED;
+  char x[MH_MAX_W];                                            // the window, 5' to 3' as the guide reads
+  bool plain = true;
+  for (int j = 0; j < W; j++) {
+    const uint64_t g = ci.gbase + (uint64_t)(first + j);
+    if ((ref.mask[g >> 5] >> (g & 31)) & 1u) *flagged = true;
+    char ch = ref.base_upper(g);
+    if (ch == 'U') ch = 'T';
+    if (ch != 'A' && ch != 'C' && ch != 'G' && ch != 'T') plain = false;
+    if (minus) ch = ch == 'A' ? 'T' : ch == 'C' ? 'G' : ch == 'G' ? 'C' : ch == 'T' ? 'A' : ch;
+    x[minus ? W - 1 - j : j] = ch;
+  }
+  if (!plain) return MH_UNSCORED;
+  calitas_mh_score_t out = {0, 0};
+  for (int d = 1; d < W; d++) {
+    const int from = std::max(0, left - d), to = std::min(left, W - d);
+    uint32_t units = 0;                                        // the sum of k + g over the diagonal's runs
+    int k = 0, g = 0;
+    for (int i = from; i <= to; i++) {
+      if (i < to && x[i] == x[i + d]) { k++; g += x[i] == 'G' || x[i] == 'C'; continue; }
+      if (k >= m.min_length) units += (uint32_t)(k + g);
+      k = 0; g = 0;
+    }
+    const uint32_t term = m.weight[d - 1] * units;
+    out.total_q16 += term;
+    if (d % 3 != 0) out.out_of_frame_q16 += term;
+  }
+  return out;
+}
+
+inline bool mh_passes(const MhCall& call, const calitas_mh_score_t& v) {
+  if (call.permille == 0) return true;
+  return v.total_q16 != CALITAS_MH_NONE && v.total_q16 > 0 && (uint64_t)v.out_of_frame_q16 * 1000u >= (uint64_t)call.permille * v.total_q16;
+}
+
+// the two blocks of the call: room for n records and n scores (at least one each)
+int mh_blocks_alloc(calitas_ctx* c, uint64_t n, calitas_site_t** sites, calitas_mh_score_t** scores) {
+  *sites = (calitas_site_t*)calitas_out_alloc(std::max<uint64_t>(1, n) * sizeof(calitas_site_t));
+  *scores = (calitas_mh_score_t*)calitas_out_alloc(std::max<uint64_t>(1, n) * sizeof(calitas_mh_score_t));
+  if (*sites && *scores) return CALITAS_OK;
+  calitas_free(*sites); calitas_free(*scores);
+  *sites = nullptr; *scores = nullptr;
+  return calitas_fail(c, CALITAS_EINVAL, "out of memory");
+}
+
+// what the caller gets: the blocks, or the number alone
+void mh_hand_over(calitas_site_t* block, calitas_mh_score_t* block_scores, uint64_t n, calitas_site_t** sites, calitas_mh_score_t** scores, uint64_t* n_sites) {
+  *n_sites = n;
+  if (sites) { *sites = block; *scores = block_scores; }
+  else { calitas_free(block); calitas_free(block_scores); }
+}
+
+}  // namespace
+
+int calitas_find_sites_microhomology_host_impl(const calitas_ctx* ctx, const calitas_guide_t* pattern, const calitas_site_filter_t* filter,
+                                               const calitas_mh_model_t* model, int32_t permille, int32_t chrom_index, uint64_t start, uint64_t end,
+                                               calitas_site_t** sites, calitas_mh_score_t** scores, uint64_t* n_sites) {
+  calitas_ctx* c = const_cast<calitas_ctx*>(ctx);
+  MhCall call;
+  if (int rc = plan_microhomology(c, pattern, filter, model, permille, chrom_index, start, end, call)) return rc;
+  std::vector<calitas_site_t> found;
+  for (int i = call.site.c_first; i <= call.site.c_last; i++) {
+    const uint64_t len = ctx->ref.contigs[(size_t)i].len;
+    host_sites(ctx->ref, call.site.tab.pat, filter, i, 0, (int64_t)len, (int64_t)std::min(start, len), (int64_t)region_end(len, end), found, nullptr);
+  }
+  calitas_site_t* block = nullptr;
+  calitas_mh_score_t* block_scores = nullptr;
+  if (int rc = mh_blocks_alloc(c, found.size(), &block, &block_scores)) return rc;
+  uint64_t n = 0;
+  for (const calitas_site_t& s : found) {
+    bool flagged = false;
+    const calitas_mh_score_t score = mh_at(ctx->ref, *model, call.L, s, &flagged);
+    if (!mh_passes(call, score)) continue;
+    block[n] = s; block_scores[n] = score; n++;
+  }
+  mh_hand_over(block, block_scores, n, sites, scores, n_sites);
+  return CALITAS_OK;
+}
+
+int calitas_find_sites_microhomology_impl(calitas_ctx* ctx, const calitas_guide_t* pattern, const calitas_site_filter_t* filter, const calitas_mh_model_t* model,
+                                          int32_t permille, int32_t chrom_index, uint64_t start, uint64_t end, calitas_site_t** sites,
+                                          calitas_mh_score_t** scores, uint64_t* n_sites) {
+  MhCall call;
+  if (int rc = plan_microhomology(ctx, pattern, filter, model, permille, chrom_index, start, end, call)) return rc;
+  if (ctx->device < 0) return calitas_fail(ctx, CALITAS_ENODEV, "host-only context: calitas_find_sites_microhomology needs a GPU (there is no CPU fallback; calitas_find_sites_microhomology_host is the host twin)");
+  const PackedRef& ref = ctx->ref;
+  const size_t nc = ref.contigs.size();
+  calitas_site_t* block = nullptr;
+  calitas_mh_score_t* block_scores = nullptr;
+  if (nc == 0) {                                  // nothing to scan
+    if (int rc = mh_blocks_alloc(ctx, 0, &block, &block_scores)) return rc;
+    mh_hand_over(block, block_scores, 0, sites, scores, n_sites);
+    return CALITAS_OK;
+  }
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  if (!ctx->sites) ctx->sites = new SitesWork();
+  SitesWork* w = ctx->sites;
+
+  // calitas_find_sites' two passes as they are; the records stay in d_out
+  SitesArgs a{};
+  if (int rc = site_launch(ctx, call.site, chrom_index, start, end, w, a)) return rc;
+  const uint32_t n_blocks = a.n_segs;
+  if (w->blocks_cap < (size_t)n_blocks + 1) {
+    (void)hipFree(w->d_count); (void)hipFree(w->d_off); w->d_count = nullptr; w->d_off = nullptr; w->blocks_cap = 0;
+    HIP_TRY(ctx, hipMalloc((void**)&w->d_count, ((size_t)n_blocks + 1) * sizeof(uint32_t)));
+    HIP_TRY(ctx, hipMalloc((void**)&w->d_off, ((size_t)n_blocks + 1) * sizeof(uint64_t)));
+    w->blocks_cap = (size_t)n_blocks + 1;
+  }
+  if (w->totals_cap < 2 * nc) {
+    (void)hipFree(w->d_totals); w->d_totals = nullptr; w->totals_cap = 0;
+    HIP_TRY(ctx, hipMalloc((void**)&w->d_totals, 2 * nc * sizeof(unsigned long long)));
+    w->totals_cap = 2 * nc;
+  }
+  a.wg_count = w->d_count; a.totals = w->d_totals; a.wg_offset = w->d_off; a.out = nullptr; a.out_capacity = 0;
+  uint64_t n_dev = 0;
+  HIP_TRY(ctx, hipMemcpyAsync(w->d_pat, &call.site.tab, filter ? sizeof(SiteTables) : sizeof(SitePatterns), hipMemcpyHostToDevice, ctx->stream));
+  HIP_TRY(ctx, hipMemsetAsync(w->d_totals, 0, 2 * nc * sizeof(unsigned long long), ctx->stream));
+  HIP_TRY(ctx, launch_sites_count(a, filter != nullptr, ctx->stream));
+  HIP_TRY(ctx, launch_sites_offsets(w->d_count, w->d_off, n_blocks, ctx->stream));
+  HIP_TRY(ctx, hipMemcpyAsync(&n_dev, w->d_off + n_blocks, sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  const char* const no_room = "the site records and their microhomology scores do not fit the device: list the region in pieces";
+  if (n_dev / MH_THREADS >= 0x7FFFFFFFull) return calitas_fail(ctx, CALITAS_ENOMEM, no_room);
+  const bool threshold = call.permille != 0;
+  uint64_t n_kept = n_dev;
+  const SiteRecord* d_recs = nullptr;
+  const MhScore* d_scores = nullptr;
+  if (n_dev) {
+    if (w->out_cap < n_dev) {
+      (void)hipFree(w->d_out); w->d_out = nullptr; w->out_cap = 0;
+      if (hipMalloc((void**)&w->d_out, n_dev * sizeof(SiteRecord)) != hipSuccess) { (void)hipGetLastError(); return calitas_fail(ctx, CALITAS_ENOMEM, no_room); }
+      w->out_cap = n_dev;
+    }
+    if (w->mh_scores_cap < n_dev) {
+      (void)hipFree(w->d_mh_scores); w->d_mh_scores = nullptr; w->mh_scores_cap = 0;
+      if (hipMalloc((void**)&w->d_mh_scores, n_dev * sizeof(MhScore)) != hipSuccess) { (void)hipGetLastError(); return calitas_fail(ctx, CALITAS_ENOMEM, no_room); }
+      w->mh_scores_cap = n_dev;
+    }
+    const uint32_t mh_wgs = mh_blocks(n_dev);
+    if (threshold && w->mh_blocks_cap < (size_t)mh_wgs + 1) {
+      (void)hipFree(w->d_mh_count); (void)hipFree(w->d_mh_off); w->d_mh_count = nullptr; w->d_mh_off = nullptr; w->mh_blocks_cap = 0;
+      HIP_TRY(ctx, hipMalloc((void**)&w->d_mh_count, ((size_t)mh_wgs + 1) * sizeof(uint32_t)));
+      HIP_TRY(ctx, hipMalloc((void**)&w->d_mh_off, ((size_t)mh_wgs + 1) * sizeof(uint64_t)));
+      w->mh_blocks_cap = (size_t)mh_wgs + 1;
+    }
+    a.out = w->d_out; a.out_capacity = n_dev;
+
+    MhArgs s{};                                    // (the weights travel in the argument block)
+    s.planes = ctx->d_planes; s.mask = ctx->d_mask; s.contigs = ctx->d_contigs; s.recs = w->d_out; s.scores = w->d_mh_scores;
+    s.wg_kept = threshold ? w->d_mh_count : nullptr;
+    s.n = n_dev; s.n_words = ref.total_packed / 32; s.n_contigs = (int32_t)nc; s.L = call.L; s.left = model->left; s.right = model->right;
+    s.cut = model->cut_offset; s.min_length = model->min_length; s.permille = call.permille;
+    for (int d = 1; d < call.W; d++) s.weight[d - 1] = model->weight[d - 1];
+    HIP_TRY(ctx, launch_sites_write(a, filter != nullptr, ctx->stream));
+    HIP_TRY(ctx, launch_mh_score(s, ctx->stream));
+    d_recs = w->d_out; d_scores = w->d_mh_scores;
+    if (threshold) {
+      HIP_TRY(ctx, launch_sites_offsets(w->d_mh_count, w->d_mh_off, mh_wgs, ctx->stream));
+      HIP_TRY(ctx, hipMemcpyAsync(&n_kept, w->d_mh_off + mh_wgs, sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
+      HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+      if (n_kept > n_dev) return calitas_fail(ctx, CALITAS_EHIP, "calitas_find_sites_microhomology: more records kept than written (internal error)");
+      if (n_kept && w->mh_out_cap < n_kept) {
+        (void)hipFree(w->d_mh_out); (void)hipFree(w->d_mh_out_scores); w->d_mh_out = nullptr; w->d_mh_out_scores = nullptr; w->mh_out_cap = 0;
+        if (hipMalloc((void**)&w->d_mh_out, n_kept * sizeof(SiteRecord)) != hipSuccess || hipMalloc((void**)&w->d_mh_out_scores, n_kept * sizeof(MhScore)) != hipSuccess) {
+          (void)hipGetLastError();
+          (void)hipFree(w->d_mh_out); w->d_mh_out = nullptr;
+          return calitas_fail(ctx, CALITAS_ENOMEM, no_room);
+        }
+        w->mh_out_cap = n_kept;
+      }
+      if (n_kept) HIP_TRY(ctx, launch_mh_compact(w->d_out, w->d_mh_scores, n_dev, call.permille, w->d_mh_off, w->d_mh_out, w->d_mh_out_scores, n_kept, ctx->stream));
+      d_recs = w->d_mh_out; d_scores = w->d_mh_out_scores;
+    }
+  }
+
+  // a U is a T to a site and an exception base to the kernels: the sites the site kernel did not see, and what it has in their place
+  std::vector<calitas_site_t> with_u, kernel_has;
+  sites_with_u(ctx, call.site, start, end, with_u, kernel_has);
+  if (int rc = mh_blocks_alloc(ctx, n_kept + with_u.size(), &block, &block_scores)) return rc;
+  int rc = CALITAS_OK;
+  do {   // (one exit that releases the blocks)
+    hipError_t e = hipSuccess;
+    if ((n_kept && ((e = hipMemcpyAsync(block, d_recs, n_kept * sizeof(SiteRecord), hipMemcpyDeviceToHost, ctx->stream)) != hipSuccess ||
+                    (e = hipMemcpyAsync(block_scores, d_scores, n_kept * sizeof(MhScore), hipMemcpyDeviceToHost, ctx->stream)) != hipSuccess)) ||
+        (e = hipStreamSynchronize(ctx->stream)) != hipSuccess) {
+      rc = calitas_fail(ctx, CALITAS_EHIP, std::string("calitas_find_sites_microhomology: ") + hipGetErrorString(e));
+      break;
+    }
+    // A record the site kernel has beside a U is in the block exactly when its own score passes or its window was left to the host
+    // (both lists are in output order); it goes.
+    bool gaps = false;
+    calitas_site_t* const end_dev = block + n_kept;
+    for (const calitas_site_t& s : kernel_has) {
+      bool flagged = false;
+      const calitas_mh_score_t score = mh_at(ref, *model, call.L, s, &flagged);
+      const bool expected = flagged || mh_passes(call, score);
+      calitas_site_t* at = std::lower_bound(block, end_dev, s, site_less);
+      const bool there = at != end_dev && std::memcmp(at, &s, sizeof(s)) == 0;
+      if (there != expected) { rc = calitas_fail(ctx, CALITAS_EHIP, "calitas_find_sites_microhomology: the records beside a U are not the ones the host expects (internal error)"); break; }
+      if (there) { at->contig_index = -1; gaps = true; }
+    }
+    if (rc) break;
+    // the windows the kernel left to the host: walked letter by letter, dropped when below the threshold
+    for (uint64_t i = 0; i < n_kept; i++) {
+      if (block_scores[i].total_q16 != MH_NONE || block_scores[i].out_of_frame_q16 != MH_HOST_DECIDES || block[i].contig_index < 0) continue;
+      bool flagged = false;
+      const calitas_mh_score_t score = mh_at(ref, *model, call.L, block[i], &flagged);
+      if (mh_passes(call, score)) block_scores[i] = score;
+      else { block[i].contig_index = -1; gaps = true; }
+    }
+    uint64_t n = n_kept;
+    if (gaps) {
+      n = 0;
+      for (uint64_t i = 0; i < n_kept; i++)
+        if (block[i].contig_index >= 0) { block[n] = block[i]; block_scores[n] = block_scores[i]; n++; }
+    }
+    // the sites with a U in their footprint come in with the host's scores, each at its place: a merge from the back that ends
+    // with the last of them
+    std::vector<calitas_mh_score_t> u_scores;
+    size_t n_in = 0;
+    for (const calitas_site_t& s : with_u) {
+      bool flagged = false;
+      const calitas_mh_score_t score = mh_at(ref, *model, call.L, s, &flagged);
+      if (!mh_passes(call, score)) continue;
+      with_u[n_in++] = s; u_scores.push_back(score);
+    }
+    for (uint64_t i = n, j = n_in, k = n + n_in; j > 0; k--) {
+      if (i > 0 && site_less(with_u[j - 1], block[i - 1])) { block[k - 1] = block[i - 1]; block_scores[k - 1] = block_scores[i - 1]; i--; }
+      else { block[k - 1] = with_u[j - 1]; block_scores[k - 1] = u_scores[j - 1]; j--; }
+    }
+    mh_hand_over(block, block_scores, n + n_in, sites, scores, n_sites);
+  } while (0);
+  if (rc) { calitas_free(block); calitas_free(block_scores); }
+  return rc;
 }

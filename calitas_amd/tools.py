@@ -322,9 +322,11 @@ class GuideSite:
     """One site of Context.find_sites as a guide: `guide` is the `-i` string a search takes -- the protospacer as it reads on the site's
     strand, upper case, with the PATTERN's matched PAM in lower case behind it (in front of it for a 5' PAM) -- and pam_sequence the
     genomic PAM bases on that strand; [start, end) is the footprint (protospacer + PAM), 0-based half-open."""
-    __slots__ = ("chromosome", "start", "end", "strand", "pam_index", "guide", "pam_sequence", "protospacer_start", "activity_q16", "region_class")
+    __slots__ = ("chromosome", "start", "end", "strand", "pam_index", "guide", "pam_sequence", "protospacer_start", "activity_q16", "region_class", "mh_total_q16",
+                 "mh_oof_q16")
 
     def __init__(self, *v):
+        self.mh_total_q16 = self.mh_oof_q16 = None     # (find_guides with a microhomology model: the site's two sums, MH_NONE where it has none)
         self.activity_q16 = None                       # (find_guides with a model: the site's score, ACTIVITY_NONE when it has none)
         self.region_class = None                       # (find_guides with classes or an extent: the site's class index under the context's regions)
         for k, x in zip(self.__slots__, v):
@@ -339,17 +341,27 @@ class GuideSite:
 
 
 def find_guides(ctx, pattern, chrom=None, start=0, end=None, host=False, filter=None, activity=None, min_activity=None, classes=None, extent=None,
-                by_regions=False):
+                by_regions=False, microhomology=None, mh_cut=None, min_out_of_frame=0):
     """Context.find_sites turned into guides: a list of GuideSite in the sites' order.  pattern: a Guide or its `-i` string; filter: a
     SiteFilter -- only the sites that pass it come back at all.  activity: an ActivityModel -- every GuideSite carries its site's
     on-target score as activity_q16 (Context.find_sites_scored; ACTIVITY_NONE where the site has none); min_activity: a Q16 integer,
     only the sites that score at least that much come back.  classes, extent (or by_regions=True for their defaults): only the sites
     whose class under the context's regions is one of `classes` come back (Context.find_sites_regions), each with its class index as
     region_class.  Together with activity both listings are made over the same region and joined on (contig, protospacer start,
-    strand) in one walk over the two: both are in that order."""
+    strand) in one walk over the two: both are in that order.  microhomology: a MicrohomologyModel -- every GuideSite carries its site's
+    microhomology score around the cut as mh_total_q16 and mh_oof_q16 (Context.find_sites_microhomology; MH_NONE in both where the
+    site has none); mh_cut: the cut's position in the protospacer as the guide reads (None: L - 3, with a 3' PAM); min_out_of_frame: a
+    per-mille 0 .. 1000, only the sites whose out-of-frame share reaches it come back.  With activity or regions this listing is
+    joined to the others in the same way."""
     if not isinstance(pattern, Guide):
         pattern = Guide(pattern)
-    cls_of = None
+    if microhomology is None and (mh_cut is not None or min_out_of_frame):
+        raise ValueError("mh_cut and min_out_of_frame need a microhomology model")
+    cls_of = mh = None
+    plain = activity is None and classes is None and extent is None and not by_regions
+    if microhomology is not None:
+        mh_sites, mh_scores = ctx.find_sites_microhomology(pattern, microhomology, cut_offset=mh_cut, min_out_of_frame=min_out_of_frame, filter=filter,
+                                                           chrom=chrom, start=start, end=end, host=host)
     if classes is not None or extent is not None or by_regions:
         if activity is None and min_activity is not None:
             raise ValueError("min_activity needs an activity model")
@@ -370,9 +382,24 @@ def find_guides(ctx, pattern, chrom=None, start=0, end=None, host=False, filter=
     elif activity is None:
         if min_activity is not None:
             raise ValueError("min_activity needs an activity model")
-        sites, q16 = ctx.find_sites(pattern, chrom, start, end, host=host, filter=filter), None
+        sites, q16 = (mh_sites if microhomology is not None else ctx.find_sites(pattern, chrom, start, end, host=host, filter=filter)), None
     else:
         sites, q16 = ctx.find_sites_scored(pattern, activity, min_score=min_activity, filter=filter, chrom=chrom, start=start, end=end, host=host)
+    if microhomology is not None and plain:
+        mh = mh_scores
+    elif microhomology is not None:                    # the merge walk again: a site the per-mille dropped has no partner and goes
+        keep, rows, j = [], [], 0
+        key = lambda r: (int(r["contig_index"]), int(r["protospacer_start"]), r["strand"] == b"-")
+        for i in range(len(sites)):
+            k = key(sites[i])
+            while j < len(mh_sites) and key(mh_sites[j]) < k:
+                j += 1
+            if j < len(mh_sites) and key(mh_sites[j]) == k:
+                keep.append(i)
+                rows.append(j)
+        sites, mh = sites[keep], mh_scores[rows]
+        q16 = None if q16 is None else [q16[i] for i in keep]
+        cls_of = None if cls_of is None else cls_of[keep]
     out = []
     L = pattern.protospacer_length
     bounds = {}
@@ -400,6 +427,8 @@ def find_guides(ctx, pattern, chrom=None, start=0, end=None, host=False, filter=
             out[-1].activity_q16 = int(q16[len(out) - 1])
         if cls_of is not None:
             out[-1].region_class = int(cls_of[len(out) - 1])
+        if mh is not None:
+            out[-1].mh_total_q16, out[-1].mh_oof_q16 = int(mh[len(out) - 1]["total_q16"]), int(mh[len(out) - 1]["out_of_frame_q16"])
     return out
 
 
@@ -602,7 +631,8 @@ def activity_q16_of_flag(text):
     return int(math.floor(float(text) * 65536.0 + 0.5))
 
 
-def guides_tsv(rows, tables=None, scores=None, copies=None, seed_copies=None, near=None, near_scores=None, activity=None, class_names=None):
+def guides_tsv(rows, tables=None, scores=None, copies=None, seed_copies=None, near=None, near_scores=None, activity=None, class_names=None,
+               microhomology=None):
     """The FindGuides table: GUIDE_COLUMNS, one row per GuideSite; with tables (guide_counts) also hits -- the table's sum -- and
     hits_mm0 .. hits_mmE, the hits per number of protospacer mismatches, summed over strands, gaps and PAM mismatches; with scores
     (guide_scores) those columns come from the same pass's tables and perfect and specificity (%.6f) follow them.  copies,
@@ -612,13 +642,18 @@ def guides_tsv(rows, tables=None, scores=None, copies=None, seed_copies=None, ne
     behind copies_mmM.  activity: the ActivityModel the rows were scored with (find_guides) -- activity_q16, the score as it is, and
     activity, the number its link makes of it (activity_value, %.6f), directly behind pam_sequence and before all of the above; NA in
     both for a site without a score.  class_names: the names of the regions' classes ("elsewhere" first) -- the column class, the name
-    of the row's region_class (find_guides with classes), directly behind pam_sequence and ahead of activity_q16."""
-    from .aligner import ACTIVITY_NONE, activity_value
+    of the row's region_class (find_guides with classes), directly behind pam_sequence and ahead of activity_q16.  microhomology: the
+    MicrohomologyModel the rows were scored with (find_guides) -- mh_total_q16 and mh_oof_q16, the two sums as they are, mh_score,
+    100 * total / 65536 (%.3f), and out_of_frame, 100 * oof / total (%.2f), directly behind activity; NA in all four for a site
+    without a score and in out_of_frame where the total is 0."""
+    from .aligner import ACTIVITY_NONE, MH_NONE, activity_value
     header = list(GUIDE_COLUMNS)
     if class_names is not None:
         header.append("class")
     if activity is not None:
         header += ["activity_q16", "activity"]
+    if microhomology is not None:
+        header += ["mh_total_q16", "mh_oof_q16", "mh_score", "out_of_frame"]
     if copies is not None:
         header.append("copies")
     if seed_copies is not None:
@@ -645,6 +680,12 @@ def guides_tsv(rows, tables=None, scores=None, copies=None, seed_copies=None, ne
         if activity is not None:
             unscored = r.activity_q16 is None or r.activity_q16 == ACTIVITY_NONE
             f += ["NA", "NA"] if unscored else [str(r.activity_q16), "%.6f" % activity_value(r.activity_q16, activity)]
+        if microhomology is not None:
+            total, oof = r.mh_total_q16, r.mh_oof_q16
+            if total is None or total == MH_NONE:
+                f += ["NA"] * 4
+            else:
+                f += [str(total), str(oof), "%.3f" % (100.0 * total / 65536.0), "%.2f" % (100.0 * oof / total) if total else "NA"]
         if copies is not None:
             f.append(str(int(copies[i])))
         if seed_copies is not None:
@@ -775,7 +816,7 @@ def find_guides_tool(ref, pattern, auxiliary_pams=(), chrom=None, start=0, end=N
                      gc_min=None, gc_max=None, max_run=None, avoid=(), copies=False, seed_copies=None, max_copies=None, max_seed_copies=None,
                      near_copies=None, max_near_copies=None, near_scores=None, near_list=None, near_list_limit=None, activity=None, min_activity=None,
                      regions=None, classes=None, class_extent=None, pairs=None, pair_distance=None, pair_cut=None, pair_orientation=None, alleles=None, allele_sites=None,
-                     allele_kinds=None, **search):
+                     allele_kinds=None, microhomology=None, mh_cut=None, min_out_of_frame=None, **search):
     """`python -m calitas_amd FindGuides`: the guides of a region as a TSV (guides_tsv); counts=True: every distinct guide also goes
     through the off-target search with the SearchReference flags in `search` (make_params names); scores=ScoreModel (or its file):
     through search_scores_batch instead, which adds perfect and specificity.  gc_min, gc_max, max_run, avoid: the site filter's flags
@@ -801,8 +842,12 @@ def find_guides_tool(ref, pattern, auxiliary_pams=(), chrom=None, start=0, end=N
     protospacer as the guide reads (default L - 3 with a 3' PAM, required otherwise); pair_orientation=out|in|same|any|CODE,...
     (default out).  alleles=FILE.vcf[.gz] with allele_sites=OUT.tsv (each needs the other): the sites every SNV of the file whose
     position lies in the region creates, destroys or changes (Context.find_allele_sites, allele_sites_tsv) to OUT, the table itself
-    unchanged; allele_kinds="alt,ref,both" the kinds to write (default all).  These twenty-one work with device -1 through the host
-    twin.  Returns the text."""
+    unchanged; allele_kinds="alt,ref,both" the kinds to write (default all).  microhomology=MicrohomologyModel (or its file): the
+    columns mh_total_q16, mh_oof_q16, mh_score and out_of_frame, every site's window around its cut scored in a listing of its own
+    (joined to the others as find_guides does); mh_cut=N the cut's position in the protospacer as the guide reads (default L - 3 with a
+    3' PAM, required otherwise); min_out_of_frame=PCT (0 .. 100, needs microhomology): the rows whose out-of-frame share is below PCT
+    per cent, those with a total of 0 and those without a score are dropped before any of the flags above looks at anything, the kept
+    rows keep their guide_ids.  These twenty-four work with device -1 through the host twin.  Returns the text."""
     if (alleles is None) != (allele_sites is None):
         raise ValueError("--alleles FILE.vcf and --allele-sites OUT.tsv require each other")
     if allele_kinds is not None and alleles is None:
@@ -860,6 +905,23 @@ def find_guides_tool(ref, pattern, auxiliary_pams=(), chrom=None, start=0, end=N
     if activity is not None and activity.L != pat.protospacer_length:
         raise ValueError("--activity: the model is for protospacers of %d bases, the pattern's has %d" % (activity.L, pat.protospacer_length))
     floor = activity_q16_of_flag(min_activity) if min_activity is not None else None
+    if microhomology is None and (mh_cut is not None or min_out_of_frame is not None):
+        raise ValueError("--mh-cut and --min-out-of-frame require --microhomology MODEL")
+    if isinstance(microhomology, str):
+        from .aligner import MicrohomologyModel
+        microhomology = MicrohomologyModel.read(microhomology)
+    permille = 0
+    if microhomology is not None:
+        L = pat.protospacer_length
+        if mh_cut is None and not pat.pam_is_three_prime:
+            raise ValueError("--mh-cut N is required: the default, L - 3, is the Cas9 cut of a pattern with a 3' PAM")
+        if mh_cut is not None and not (str(mh_cut).isdigit() and len(str(mh_cut)) <= 3 and int(mh_cut) <= L):
+            raise ValueError("--mh-cut N: N is 0 .. %d, the protospacer's length, not %s" % (L, mh_cut))
+        mh_cut = L - 3 if mh_cut is None else int(mh_cut)
+        if min_out_of_frame is not None:
+            if not (str(min_out_of_frame).isdigit() and len(str(min_out_of_frame)) <= 3 and int(min_out_of_frame) <= 100):
+                raise ValueError("--min-out-of-frame PCT: PCT is an integer 0 .. 100, not %s" % min_out_of_frame)
+            permille = 10 * int(min_out_of_frame)
     ctx = Context(device)
     try:
         ctx.set_reference_fasta(ref)
@@ -876,7 +938,7 @@ def find_guides_tool(ref, pattern, auxiliary_pams=(), chrom=None, start=0, end=N
             ctx.set_regions(reg)
             class_names = reg.classes
         rows = find_guides(ctx, pat, chrom, start, end, host=device < 0, filter=keep, activity=activity, min_activity=floor, classes=classes, extent=extent,
-                           by_regions=regions is not None)
+                           by_regions=regions is not None, microhomology=microhomology, mh_cut=mh_cut, min_out_of_frame=permille)
         n_copies = guide_copies(ctx, pat, rows, host=device < 0) if copies or max_copies is not None else None
         n_seed = guide_copies(ctx, pat, rows, key_length=int(seed_copies), host=device < 0) if seed_copies is not None else None
         scored_near = guide_near_scores(ctx, pat, rows, int(near_copies), near_scores, host=device < 0) if near_scores is not None else None
@@ -898,7 +960,8 @@ def find_guides_tool(ref, pattern, auxiliary_pams=(), chrom=None, start=0, end=N
             scored_near = NearScores(n_near, scored_near.sum_q32[kept], scored_near.max_q32[kept])
         tables = guide_counts(ctx, [r.guide for r in rows], make_params(**search)) if counts and scores is None else None
         scored = guide_scores(ctx, [r.guide for r in rows], make_params(**search), scores) if scores is not None else None
-        text = guides_tsv(rows, tables, scored, copies=n_copies, seed_copies=n_seed, near=n_near, near_scores=scored_near, activity=activity, class_names=class_names)
+        text = guides_tsv(rows, tables, scored, copies=n_copies, seed_copies=n_seed, near=n_near, near_scores=scored_near, activity=activity, class_names=class_names,
+                          microhomology=microhomology)
         if near_list is not None:
             listing = guide_near_list(ctx, pat, rows, int(near_copies), near_scores, limit=1000 if near_list_limit is None else int(near_list_limit), host=device < 0)
             with open(near_list, "w") as f:

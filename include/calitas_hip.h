@@ -781,6 +781,56 @@ int calitas_find_allele_sites_host(const calitas_ctx* ctx, const calitas_guide_t
 int calitas_count_allele_sites_host(const calitas_ctx* ctx, const calitas_guide_t* pattern, const calitas_snv_t* snvs, uint64_t n_snvs,
                                     uint64_t* per_kind, uint64_t* n_sites, uint8_t* status);
 
+/* Microhomology and frameshift odds: what the cut of a site is likely to become.  A double-strand break with microhomologies either
+ * side of it is repaired by MMEJ into a few predictable deletions; a guide whose likely deletions are multiples of three leaves the
+ * protein in frame.  No reference counterpart.
+ * THE WINDOW.  `left` bases 5' and `right` bases 3' of the cut as the guide reads, 1 .. 32 each, W = left + right <= 64.  The cut is
+ * cut_offset bases into the protospacer as the guide reads, 0 .. L (calitas_site_pairs_t's cut_offset: L - 3 is the Cas9 cut with a
+ * 3' PAM).  With p the record's protospacer_start the forward cut is c = p + cut_offset on '+' and c = p + L - cut_offset on '-'; the
+ * window is the forward bases [c - left, c + right) on '+' and the reverse complement of the forward bases [c - right, c + left) on
+ * '-'.  Call its letters x[0 .. W): the cut lies between x[left - 1] and x[left].
+ * A site is scored when the window lies inside its contig -- the contig bounds it, not the region -- and every base of it is a plain
+ * A C G T, in either case, or a U (read as T).  Otherwise both numbers are CALITAS_MH_NONE.
+ * THE SCORE.  For every deletion length d = 1 .. W - 1 let lo(d) = max(0, left - d) and hi(d) = min(left, W - d).  Position i in
+ * [lo(d), hi(d)) is a match when x[i] == x[i + d]: the left copy lies left of the cut, the right copy right of it.  A microhomology
+ * is a maximal run of matches, maximal within [lo(d), hi(d)), of length k >= min_length (2 .. 8); its term is weight[d - 1] * (k + g)
+ * with g the number of G and C among its k bases.  `weight` is W - 1 unsigned Q16 values, each <= CALITAS_MH_MAX_WEIGHT; a weight
+ * exp(-d / 20) gives the published shape.  total_q16 is the sum of all terms, out_of_frame_q16 the sum of those with d % 3 != 0.
+ * The sum of 2 (hi(d) - lo(d)) * 65536 over d is at most 2^27 (64 G's at left = right = 32 under unit weights reach 133 955 584), so
+ * neither sum overflows nor equals CALITAS_MH_NONE.  Integer addition has no order, so the kernel, the host twin and a plain loop
+ * give the same numbers.  The library ships the mechanism and a file format (models/example_microhomology60.tsv), no published
+ * weight table. */
+#define CALITAS_MH_NONE 0xFFFFFFFFu           /* this site has no score */
+#define CALITAS_MH_MAX_SIDE 32
+#define CALITAS_MH_MAX_WEIGHT 65536u          /* 1.0 in Q16 */
+typedef struct {
+  int32_t left, right;          /* bases 5' and 3' of the cut AS THE GUIDE READS, 1 .. 32 each */
+  int32_t cut_offset;           /* 0 .. L */
+  int32_t min_length;           /* 2 .. 8: the shortest run that counts */
+  const uint32_t* weight;       /* [left + right - 1] by deletion length d - 1, Q16, each <= CALITAS_MH_MAX_WEIGHT */
+} calitas_mh_model_t;
+typedef struct { uint32_t total_q16, out_of_frame_q16; } calitas_mh_score_t;   /* 8 bytes */
+/* The records of calitas_find_sites_filtered(pattern, filter, ...), in that call's order and with its bytes; scores[i] belongs to
+ * sites[i].  min_out_of_frame_permille == 0 keeps every site, the unscored ones carrying CALITAS_MH_NONE twice; 1 .. 1000 keeps the
+ * scored sites with total_q16 > 0 and (uint64_t)out_of_frame_q16 * 1000 >= (uint64_t)permille * total_q16.
+ * sites == NULL && scores == NULL: *n_sites only.  Each block takes one calitas_free.
+ * On the device the records of the site kernel's two passes stay where they are: one lane per record brings its window down to bit 0
+ * of a pair of 64-bit planes and takes each diagonal d with two shifts, two XORs and a popcount; with a threshold a second kernel
+ * compacts records and scores in order (ranks from ballots: no sort, no returning atomic) before the one copy-back.  Windows with an
+ * exception base -- a U among them, which the device cannot tell from an N -- are decided on the host.
+ * Errors, in this order: what calitas_find_sites_filtered refuses; CALITAS_EINVAL, with a message that names the field, for a NULL
+ * model or weight, left or right outside 1 .. 32, cut_offset outside 0 .. L, min_length outside 2 .. 8, a weight above
+ * CALITAS_MH_MAX_WEIGHT, a permille outside 0 .. 1000; CALITAS_ENODEV on a host-only context; CALITAS_ENOMEM when records and scores
+ * do not fit the device. */
+int calitas_find_sites_microhomology(calitas_ctx* ctx, const calitas_guide_t* pattern, const calitas_site_filter_t* filter /* may be NULL */,
+                                     const calitas_mh_model_t* model, int32_t min_out_of_frame_permille, int32_t chrom_index, uint64_t start,
+                                     uint64_t end, calitas_site_t** sites, calitas_mh_score_t** scores, uint64_t* n_sites);
+/* The host twin: calitas_find_sites_filtered_host's records, each window walked diagonal by diagonal, letter by letter; also on a
+ * host-only context. */
+int calitas_find_sites_microhomology_host(const calitas_ctx* ctx, const calitas_guide_t* pattern, const calitas_site_filter_t* filter,
+                                          const calitas_mh_model_t* model, int32_t min_out_of_frame_permille, int32_t chrom_index, uint64_t start,
+                                          uint64_t end, calitas_site_t** sites, calitas_mh_score_t** scores, uint64_t* n_sites);
+
 /* SequentialGuideAligner.align on explicit (guide, target) pairs -- the per-task call of PairwiseAlignSequences
  * (PairwiseAlignSequences.scala:64 -> alignBest, SequentialGuideAligner.scala:333-345) and AlignToReference
  * (AlignToReference.scala:114-135 -> alignToRef / alignToRefBest, SequentialGuideAligner.scala:359-418).  Task t aligns
