@@ -120,10 +120,17 @@ def main(argv=None):
     fg.add_argument("--pair-orientation", metavar="out|in|same|any|CODE,...",
                     help="with --pairs: the orientations to keep -- out (PAMs facing outwards, the default), in, same, any, or codes among ++ -+ +- -- (left strand, right strand)")
     fg.add_argument("--alleles", metavar="FILE.vcf[.gz]",
-                    help="with --allele-sites: the SNVs (single-letter REF and ALT of A C G T) whose position lies in the region; the table itself does not change")
+                    help="with --allele-sites or --edit-sites: the SNVs (single-letter REF and ALT of A C G T) whose position lies in the region; the table itself does not change")
     fg.add_argument("--allele-sites", metavar="OUT.tsv",
                     help="with --alleles: write the sites each SNV creates (allele alt), destroys (ref) or changes (both) to OUT.tsv, one per line")
     fg.add_argument("--allele-kinds", metavar="alt,ref,both", help="with --alleles: the kinds of lines to write (default all three)")
+    fg.add_argument("--edit-sites", metavar="OUT.tsv",
+                    help="with --alleles, --editor and --edit-window: write the guides that put each SNV into the base editor's window on the strand it can change it on, and their bystanders, to OUT.tsv, one per line")
+    fg.add_argument("--editor", metavar="FROM:TO", help="with --edit-sites: the editor's change, two different letters of A C G T (C:T a CBE, A:G an ABE, C:G a CGBE)")
+    fg.add_argument("--edit-window", metavar="FROM:TO", help="with --edit-sites: the positions of the protospacer as the guide reads that the editor reaches, 0-based and half-open")
+    fg.add_argument("--edit-context", metavar="LETTER", help="with --edit-sites: the IUPAC letter the base 5' of an edited base must lie in (default N: any)")
+    fg.add_argument("--edit-mode", metavar="install|correct", help="with --edit-sites: install (default): the cell carries REF and the edit makes ALT; correct: the cell carries ALT and the edit makes REF")
+    fg.add_argument("--max-bystanders", metavar="N", help="with --edit-sites: only the guides with at most N other editable bases in the window (0 .. 31)")
     fg.add_argument("--microhomology", metavar="MODEL",
                     help="add mh_total_q16, mh_oof_q16, mh_score and out_of_frame: the microhomology score around every site's cut and the share of it that shifts the frame, under the model file (models/example_microhomology60.tsv shows the format), NA where a site has none")
     fg.add_argument("--mh-cut", metavar="N", help="with --microhomology: the cut's position in the protospacer as the guide reads, 0 .. L (default L - 3 with a 3' PAM, required otherwise)")
@@ -176,7 +183,7 @@ def main(argv=None):
     elif a.tool == "FindGuides":
         text = find_guides_tool(a.ref, a.guide, a.auxiliary_pams, chrom=a.chrom, start=a.start, end=a.end, output=a.output, counts=a.counts, scores=a.scores,
                                 device=a.device, gc_min=a.gc_min, gc_max=a.gc_max, max_run=a.max_run, avoid=a.avoid, copies=a.copies,
-                                seed_copies=a.seed_copies, max_copies=a.max_copies, max_seed_copies=a.max_seed_copies, near_copies=a.near_copies, max_near_copies=a.max_near_copies, near_scores=a.near_scores, near_list=a.near_list, near_list_limit=a.near_list_limit, activity=a.activity, min_activity=a.min_activity, regions=a.regions, classes=a.classes, class_extent=a.class_extent, pairs=a.pairs, pair_distance=a.pair_distance, pair_cut=a.pair_cut, pair_orientation=a.pair_orientation, alleles=a.alleles, allele_sites=a.allele_sites, allele_kinds=a.allele_kinds, microhomology=a.microhomology, mh_cut=a.mh_cut, min_out_of_frame=a.min_out_of_frame,
+                                seed_copies=a.seed_copies, max_copies=a.max_copies, max_seed_copies=a.max_seed_copies, near_copies=a.near_copies, max_near_copies=a.max_near_copies, near_scores=a.near_scores, near_list=a.near_list, near_list_limit=a.near_list_limit, activity=a.activity, min_activity=a.min_activity, regions=a.regions, classes=a.classes, class_extent=a.class_extent, pairs=a.pairs, pair_distance=a.pair_distance, pair_cut=a.pair_cut, pair_orientation=a.pair_orientation, alleles=a.alleles, allele_sites=a.allele_sites, allele_kinds=a.allele_kinds, microhomology=a.microhomology, mh_cut=a.mh_cut, min_out_of_frame=a.min_out_of_frame, edit_sites=a.edit_sites, editor=a.editor, edit_window=a.edit_window, edit_context=a.edit_context, edit_mode=a.edit_mode, max_bystanders=a.max_bystanders,
                                 max_guide_diffs=a.max_guide_diffs, max_pam_mismatches=a.max_pam_mismatches,
                                 max_gaps_between_guide_and_pam=a.max_gaps_between_guide_and_pam, max_total_diffs=a.max_total_diffs,
                                 max_overlap=a.max_overlap, guide_mismatch_net_cost=a.guide_mismatch_net_cost,

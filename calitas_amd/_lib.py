@@ -135,6 +135,15 @@ class AlleleSiteT(ctypes.Structure):
                 ("reserved", ctypes.c_uint8), ("guide_lo", ctypes.c_uint32), ("guide_hi", ctypes.c_uint32)]
 
 
+class BaseEditT(ctypes.Structure):
+    _fields_ = [("from_base", ctypes.c_char), ("to_base", ctypes.c_char), ("window_from", ctypes.c_uint8), ("window_to", ctypes.c_uint8), ("context", ctypes.c_char),
+                ("correct", ctypes.c_uint8), ("max_bystanders", ctypes.c_uint8), ("reserved", ctypes.c_uint8)]
+
+
+class EditSiteT(ctypes.Structure):
+    _fields_ = [("site", SiteT), ("snv_index", ctypes.c_uint32), ("editable", ctypes.c_uint32), ("guide_lo", ctypes.c_uint32), ("guide_hi", ctypes.c_uint32)]
+
+
 class MhModelT(ctypes.Structure):
     _fields_ = [("left", ctypes.c_int32), ("right", ctypes.c_int32), ("cut_offset", ctypes.c_int32), ("min_length", ctypes.c_int32),
                 ("weight", ctypes.POINTER(ctypes.c_uint32))]
@@ -145,6 +154,8 @@ class MhScoreT(ctypes.Structure):
 
 
 assert ctypes.sizeof(SnvT) == 12 and ctypes.sizeof(AlleleSiteT) == 32 and ctypes.sizeof(MhScoreT) == 8
+assert ctypes.sizeof(BaseEditT) == 8 and ctypes.sizeof(EditSiteT) == 32
+EDIT_NO_BOUND = 255
 MH_NONE = 0xFFFFFFFF
 MH_MAX_SIDE = 32
 MH_MAX_WEIGHT = 1 << 16
@@ -177,6 +188,7 @@ SYMBOLS = ["calitas_create", "calitas_destroy", "calitas_last_error", "calitas_f
            "calitas_site_presence",
            "calitas_find_site_pairs", "calitas_count_site_pairs", "calitas_find_site_pairs_host", "calitas_count_site_pairs_host",
            "calitas_find_allele_sites", "calitas_count_allele_sites", "calitas_find_allele_sites_host", "calitas_count_allele_sites_host",
+           "calitas_find_edit_sites", "calitas_count_edit_sites", "calitas_find_edit_sites_host", "calitas_count_edit_sites_host",
            "calitas_find_sites_microhomology", "calitas_find_sites_microhomology_host"]
 
 if not os.path.exists(LIB_PATH):
@@ -292,6 +304,13 @@ if hasattr(lib, "calitas_find_allele_sites"):      # (an older build behind CALI
     lib.calitas_count_allele_sites.argtypes = [ctypes.c_void_p, ctypes.POINTER(GuideT), ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64),
                                                ctypes.POINTER(ctypes.c_uint64), ctypes.c_void_p]
     lib.calitas_count_allele_sites_host.argtypes = lib.calitas_count_allele_sites.argtypes
+if hasattr(lib, "calitas_find_edit_sites"):        # (an older build behind CALITAS_LIB_PATH, for A/B runs, does not have it)
+    lib.calitas_find_edit_sites.argtypes = [ctypes.c_void_p, ctypes.POINTER(GuideT), ctypes.POINTER(BaseEditT), ctypes.c_void_p, ctypes.c_uint64,
+                                            ctypes.POINTER(ctypes.POINTER(EditSiteT)), ctypes.POINTER(ctypes.c_uint64), ctypes.c_void_p]
+    lib.calitas_find_edit_sites_host.argtypes = lib.calitas_find_edit_sites.argtypes
+    lib.calitas_count_edit_sites.argtypes = [ctypes.c_void_p, ctypes.POINTER(GuideT), ctypes.POINTER(BaseEditT), ctypes.c_void_p, ctypes.c_uint64,
+                                             ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64), ctypes.c_void_p]
+    lib.calitas_count_edit_sites_host.argtypes = lib.calitas_count_edit_sites.argtypes
 if hasattr(lib, "calitas_find_sites_microhomology"):   # (an older build behind CALITAS_LIB_PATH, for A/B runs, does not have it)
     lib.calitas_find_sites_microhomology.argtypes = [ctypes.c_void_p, ctypes.POINTER(GuideT), ctypes.POINTER(SiteFilterT), ctypes.POINTER(MhModelT), ctypes.c_int32,
                                                      ctypes.c_int32, ctypes.c_uint64, ctypes.c_uint64, ctypes.POINTER(ctypes.POINTER(SiteT)),

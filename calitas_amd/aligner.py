@@ -872,6 +872,42 @@ class Context:
         _lib.check(self._h, rc)
         return n.value, by, status[:len(snvs)]
 
+    def find_edit_sites(self, pattern, edit, snvs, host=False):
+        """calitas_find_edit_sites: the guides that put each single-nucleotide variant into the window of the base editor `edit` (a
+        BaseEdit) on the strand it can change it on, as an EditSites -- records with the fields of calitas_edit_site_t
+        (EDIT_SITE_DTYPE) ordered by snv_index, then protospacer start, and a status byte per SNV.  snvs: an array of SNV_DTYPE, or
+        (chrom, pos1, ref, alt) tuples (snvs_of).  edit_sites_of is the contract in plain Python.  host=True: the host twin, also on
+        a host-only context."""
+        import numpy as np
+        if not isinstance(pattern, Guide):
+            pattern = Guide(pattern)
+        snvs = self._snv_array(snvs)
+        g, e = pattern.to_c(), edit.to_c()
+        status = np.zeros(max(1, len(snvs)), dtype=np.uint8)
+        out, n = ctypes.POINTER(_lib.EditSiteT)(), ctypes.c_uint64()
+        fn = lib.calitas_find_edit_sites_host if host else lib.calitas_find_edit_sites
+        rc = fn(self._h, ctypes.byref(g), ctypes.byref(e), snvs.ctypes.data if len(snvs) else None, len(snvs), ctypes.byref(out), ctypes.byref(n),
+                status.ctypes.data)
+        _lib.check(self._h, rc)
+        return EditSites(self._take_records(out, n.value, _lib.EditSiteT, EDIT_SITE_DTYPE), status[:len(snvs)], pattern, edit, snvs)
+
+    def count_edit_sites(self, pattern, edit, snvs, host=False):
+        """calitas_count_edit_sites: (n, per_bystanders, status) of what find_edit_sites would return; per_bystanders a numpy uint64
+        array of the records with 0, 1, 2 and 3 or more bystanders.  No record is copied back."""
+        import numpy as np
+        if not isinstance(pattern, Guide):
+            pattern = Guide(pattern)
+        snvs = self._snv_array(snvs)
+        g, e = pattern.to_c(), edit.to_c()
+        status = np.zeros(max(1, len(snvs)), dtype=np.uint8)
+        by = np.zeros(4, dtype=np.uint64)
+        n = ctypes.c_uint64()
+        fn = lib.calitas_count_edit_sites_host if host else lib.calitas_count_edit_sites
+        rc = fn(self._h, ctypes.byref(g), ctypes.byref(e), snvs.ctypes.data if len(snvs) else None, len(snvs),
+                by.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), ctypes.byref(n), status.ctypes.data)
+        _lib.check(self._h, rc)
+        return n.value, by, status[:len(snvs)]
+
     def site_presence(self):
         """(test hook) calitas_site_presence: (bytes, first_word) -- the table the regions listing skips segments by, a uint8 array with
         one byte per 256 words (8192 bases) of the packed space from word first_word on; bit c: class c comes near the segment."""
@@ -2134,6 +2170,148 @@ def allele_sites_of(contig_seqs, pattern, snvs):
                 records.append((ci, p, pam_start if pattern.pams else -1, strand.encode(), k if pattern.pams else -1, hi - lo - L, L, i, kind,
                                 on_ref[0] if kind == 3 and pattern.pams else -1, (p + L - 1 - pos) if strand == "-" else (pos - p), 0,
                                 sum((b & 1) << j for j, b in enumerate(bits)), sum((b >> 1) << j for j, b in enumerate(bits))))
+    return records, status
+
+
+# calitas_base_edit_t and calitas_edit_site_t
+EDIT_SITE_DTYPE = SITE_DTYPE + [("snv_index", "<u4"), ("editable", "<u4"), ("guide_lo", "<u4"), ("guide_hi", "<u4")]
+_IUPAC_SETS = {"A": "A", "C": "C", "G": "G", "T": "T", "U": "T", "M": "AC", "R": "AG", "W": "AT", "S": "CG", "Y": "CT", "K": "GT", "V": "ACG",
+               "H": "ACT", "D": "AGT", "B": "CGT", "N": "ACGT"}
+
+
+class BaseEdit:
+    """A base editor (calitas_base_edit_t): it turns from_base into to_base ("C", "T": a CBE; "A", "G": an ABE; "C", "G": a CGBE) at
+    the positions window = (FROM, TO) of the protospacer as the guide reads, 0-based and half-open, where the base 5' of the edited
+    one lies in the IUPAC letter `context` ("N": any).  correct=False: install -- the cell carries REF and the edit makes ALT;
+    correct=True: the cell carries ALT and the edit makes REF.  max_bystanders=N (0 .. 31): only guides with at most N other
+    editable bases in the window; None: no bound."""
+
+    def __init__(self, from_base, to_base, window, context="N", correct=False, max_bystanders=None):
+        self.from_base, self.to_base, self.window, self.context = from_base, to_base, (int(window[0]), int(window[1])), context or "N"
+        self.correct, self.max_bystanders = bool(correct), max_bystanders
+
+    def to_c(self):
+        for name, v in (("from_base", self.from_base), ("to_base", self.to_base), ("context", self.context)):
+            if not (isinstance(v, str) and len(v) == 1 and ord(v) < 128):
+                raise ValueError("BaseEdit: %s is one letter, not %r" % (name, v))
+        if not all(0 <= w <= 255 for w in self.window):
+            raise ValueError("BaseEdit: window is (FROM, TO) with 0 <= FROM < TO <= the protospacer's length, not %r" % (self.window,))
+        by = _lib.EDIT_NO_BOUND if self.max_bystanders is None else int(self.max_bystanders)
+        if not 0 <= by <= 255:
+            raise ValueError("BaseEdit: max_bystanders is 0 .. 31 or None, not %r" % (self.max_bystanders,))
+        return _lib.BaseEditT(self.from_base.encode(), self.to_base.encode(), self.window[0], self.window[1], self.context.encode(),
+                              1 if self.correct else 0, by, 0)
+
+
+class EditSites:
+    """What Context.find_edit_sites returns.  sites: the records (EDIT_SITE_DTYPE) in (snv_index, protospacer_start) order; status: a
+    byte per SNV -- 0 examined, 1 `ref` differs from the reference's base, 2 the reference's base is no A C G T U, 3 `alt` is the
+    reference's base, 4 the change is not the editor's on either strand, 5 the target's 5' neighbour fails the context; pattern: the
+    Guide; edit: the BaseEdit; snvs: the call's SNVs (SNV_DTYPE)."""
+
+    def __init__(self, sites, status, pattern, edit, snvs):
+        self.sites, self.status, self.pattern, self.edit, self.snvs = sites, status, pattern, edit, snvs
+
+    def __len__(self):
+        return len(self.sites)
+
+    def of(self, i):
+        """The records of SNV i."""
+        import numpy as np
+        lo, hi = np.searchsorted(self.sites["snv_index"], [i, i + 1])
+        return self.sites[lo:hi]
+
+    def offset(self, rec):
+        """Where the record's SNV is in the protospacer as the guide reads."""
+        pos, p = int(self.snvs[int(rec["snv_index"])]["position"]), int(rec["protospacer_start"])
+        return (p + int(rec["protospacer_length"]) - 1 - pos) if rec["strand"] == b"-" else (pos - p)
+
+    def bystanders(self, rec):
+        """The other editable positions of the record's window, as the guide reads, ascending."""
+        o, bits = self.offset(rec), int(rec["editable"])
+        return [i for i in range(int(rec["protospacer_length"])) if (bits >> i) & 1 and i != o]
+
+    def protospacer(self, rec):
+        """The background allele's protospacer as the guide reads it, from guide_lo / guide_hi."""
+        lo, hi = int(rec["guide_lo"]), int(rec["guide_hi"])
+        return "".join("ACGT"[((lo >> i) & 1) | (((hi >> i) & 1) << 1)] for i in range(int(rec["protospacer_length"])))
+
+    def guide(self, rec):
+        """The `-i` string a search takes for the record: the background allele's protospacer, the pattern's matched PAM in lower
+        case behind it (in front of it for a 5' PAM)."""
+        k = int(rec["pam_index"])
+        pam = self.pattern.pams[k] if k >= 0 else ""
+        proto = self.protospacer(rec)
+        return (pam + proto) if self.pattern.pam_is_five_prime else (proto + pam)
+
+
+def edit_sites_of(contig_seqs, pattern, edit, snvs):
+    """The contract of find_edit_sites in plain Python: string surgery -- the background contig as a string, the guide as a slice of
+    it or of its reverse complement, every start and PAM tried letter by letter.  contig_seqs: the contigs' strings; snvs:
+    (contig_index, position0, ref, alt) tuples or records of SNV_DTYPE.  Returns (records, status): records as tuples in
+    EDIT_SITE_DTYPE's field order, status a list."""
+    if not isinstance(pattern, Guide):
+        pattern = Guide(pattern)
+    comp = {"A": "T", "C": "G", "G": "C", "T": "A"}
+    letter = lambda c: c.upper().replace("U", "T")
+    L, five, pams = pattern.protospacer_length, pattern.pam_is_five_prime, pattern.pams or [""]
+    f, t = letter(edit.from_base), letter(edit.to_base)
+    w0, w1 = edit.window
+    allowed = _IUPAC_SETS[letter(edit.context)] if edit.context.upper() != "N" else None
+    records, status = [], []
+    for i, v in enumerate(snvs):
+        ci, pos, ref, alt = (int(v["contig_index"]), int(v["position"]), v["ref"].decode(), v["alt"].decode()) if hasattr(v, "dtype") else v
+        seq = contig_seqs[ci]
+        here = letter(seq[pos])
+        if here not in "ACGT":
+            status.append(2)
+            continue
+        if ref and letter(ref) != here:
+            status.append(1)
+            continue
+        if letter(alt) == here:
+            status.append(3)
+            continue
+        b, p_ = (letter(alt), here) if edit.correct else (here, letter(alt))
+        if (b, p_) == (f, t):
+            strand = "+"
+        elif (comp[b], comp[p_]) == (f, t):
+            strand = "-"
+        else:
+            status.append(4)
+            continue
+        text = seq[:pos] + b + seq[pos + 1:]
+        # what the guide's strand shows, 5' to 3': the text, or its reverse complement with every other letter kept as a placeholder
+        shown = text.upper().replace("U", "T")
+        if strand == "-":
+            shown = "".join(comp.get(c, "?") for c in reversed(shown))
+        at = pos if strand == "+" else len(seq) - 1 - pos          # the target on that strand
+        if allowed is not None and (at == 0 or shown[at - 1] not in allowed):
+            status.append(5)
+            continue
+        status.append(0)
+        for q in (range(at - w1 + 1, at - w0 + 1) if strand == "+" else range(at - w0, at - w1, -1)):   # the protospacer's start on the guide's strand
+            p = q if strand == "+" else len(seq) - q - L         # ... and its leftmost forward base, ascending either way
+            if q < 0 or q + L > len(seq):
+                continue
+            proto = shown[q:q + L]
+            for k, pam in enumerate(pams):
+                lo, hi = (q - len(pam), q + L) if five else (q, q + L + len(pam))
+                if lo < 0 or hi > len(seq) or any(c not in "ACGT" for c in shown[lo:hi]):
+                    continue
+                want = ((pam + pattern.guide) if five else (pattern.guide + pam)).upper()
+                if all(r in _IUPAC_SETS[w_] for r, w_ in zip(shown[lo:hi], want)):
+                    break
+            else:
+                continue
+            editable = [j for j in range(w0, w1) if proto[j] == f and (allowed is None or (q + j > 0 and shown[q + j - 1] in allowed))]
+            if at - q not in editable or (edit.max_bystanders is not None and len(editable) - 1 > edit.max_bystanders):
+                continue
+            pam_q = lo if five else q + L                       # the PAM's first base on the guide's strand
+            pam_start = -1 if not pattern.pams else (pam_q if strand == "+" else len(seq) - pam_q - len(pam))
+            bits = ["ACGT".index(c) for c in proto]
+            records.append((ci, p, pam_start, strand.encode(), k if pattern.pams else -1, len(pam), L, i, sum(1 << j for j in editable),
+                            sum((c & 1) << j for j, c in enumerate(bits)), sum((c >> 1) << j for j, c in enumerate(bits))))
     return records, status
 
 

@@ -1448,6 +1448,39 @@ int calitas_count_allele_sites_host(const calitas_ctx* ctx, const calitas_guide_
   return calitas_find_allele_sites_host_impl(ctx, pattern, snvs, n_snvs, false, nullptr, per_kind, n_sites, status);
 }
 
+// Base-editor guides of a SNV (sites_host.cpp, edit_sites.hip): no reference counterpart.
+int calitas_find_edit_sites(calitas_ctx* ctx, const calitas_guide_t* pattern, const calitas_base_edit_t* edit, const calitas_snv_t* snvs, uint64_t n_snvs,
+                            calitas_edit_site_t** sites, uint64_t* n_sites, uint8_t* status) {
+  if (!ctx) return CALITAS_EINVAL;
+  if (!pattern || !edit || !sites || !n_sites) return fail(ctx, CALITAS_EINVAL, "NULL argument");
+  *sites = nullptr; *n_sites = 0;
+  return calitas_find_edit_sites_impl(ctx, pattern, edit, snvs, n_snvs, true, sites, nullptr, n_sites, status);
+}
+
+int calitas_count_edit_sites(calitas_ctx* ctx, const calitas_guide_t* pattern, const calitas_base_edit_t* edit, const calitas_snv_t* snvs, uint64_t n_snvs,
+                             uint64_t* per_bystanders, uint64_t* n_sites, uint8_t* status) {
+  if (!ctx) return CALITAS_EINVAL;
+  if (!pattern || !edit || !n_sites) return fail(ctx, CALITAS_EINVAL, "NULL argument");
+  *n_sites = 0;
+  return calitas_find_edit_sites_impl(ctx, pattern, edit, snvs, n_snvs, false, nullptr, per_bystanders, n_sites, status);
+}
+
+int calitas_find_edit_sites_host(const calitas_ctx* ctx, const calitas_guide_t* pattern, const calitas_base_edit_t* edit, const calitas_snv_t* snvs,
+                                 uint64_t n_snvs, calitas_edit_site_t** sites, uint64_t* n_sites, uint8_t* status) {
+  if (!ctx) return CALITAS_EINVAL;
+  if (!pattern || !edit || !sites || !n_sites) return fail(const_cast<calitas_ctx*>(ctx), CALITAS_EINVAL, "NULL argument");
+  *sites = nullptr; *n_sites = 0;
+  return calitas_find_edit_sites_host_impl(ctx, pattern, edit, snvs, n_snvs, true, sites, nullptr, n_sites, status);
+}
+
+int calitas_count_edit_sites_host(const calitas_ctx* ctx, const calitas_guide_t* pattern, const calitas_base_edit_t* edit, const calitas_snv_t* snvs,
+                                  uint64_t n_snvs, uint64_t* per_bystanders, uint64_t* n_sites, uint8_t* status) {
+  if (!ctx) return CALITAS_EINVAL;
+  if (!pattern || !edit || !n_sites) return fail(const_cast<calitas_ctx*>(ctx), CALITAS_EINVAL, "NULL argument");
+  *n_sites = 0;
+  return calitas_find_edit_sites_host_impl(ctx, pattern, edit, snvs, n_snvs, false, nullptr, per_bystanders, n_sites, status);
+}
+
 // Microhomology scores (sites_host.cpp, microhomology.hip): no reference counterpart.
 // (the model is the implementation's to check: it comes after everything calitas_find_sites_filtered refuses)
 int calitas_find_sites_microhomology(calitas_ctx* ctx, const calitas_guide_t* pattern, const calitas_site_filter_t* filter, const calitas_mh_model_t* model,

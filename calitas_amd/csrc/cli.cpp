@@ -47,6 +47,10 @@ static void usage() {
     "         [--pair-orientation out|in|same|any|CODE,... (with --pairs: default out, the PAMs facing outwards; codes ++ -+ +- --)]\n"
     "         [--alleles FILE.vcf[.gz] --allele-sites out.tsv (the sites each SNV of the region creates, destroys or changes, one per line)]\n"
     "         [--allele-kinds alt,ref,both (with --alleles: the kinds of lines to write; default all three)]\n"
+    "         [--alleles FILE.vcf[.gz] --edit-sites out.tsv --editor FROM:TO --edit-window FROM:TO (the guides that put each SNV of the region into the\n"
+    "          base editor's window on the strand it can change it on, and their bystanders, one per line; C:T a CBE, A:G an ABE; the window 0-based\n"
+    "          half-open in the protospacer as the guide reads)] [--edit-context LETTER (IUPAC: the base 5' of an edited base; default N)]\n"
+    "         [--edit-mode install|correct (default install: the cell carries REF)] [--max-bystanders N (0 .. 31)]\n"
     "         [--microhomology model.tsv (the columns mh_total_q16, mh_oof_q16, mh_score and out_of_frame: the microhomology score around every site's\n"
     "          cut and the share of it that shifts the frame, NA where a site has none)] [--mh-cut N (default L - 3 with a 3' PAM, required otherwise)]\n"
     "         [--min-out-of-frame PCT (with --microhomology: drop rows whose out_of_frame is below the integer PCT, 0 .. 100, rows whose total is 0\n"
@@ -462,6 +466,8 @@ static int find_guides_main(int argc, char** argv) {
   bool have_pair_distance = false, have_pair_cut = false, have_pair_orientation = false;
   std::string alleles_path, allele_sites_path, allele_kinds;             // --alleles FILE.vcf --allele-sites OUT.tsv [--allele-kinds alt,ref,both]
   bool have_allele_kinds = false;
+  std::string edit_sites_path, editor, edit_window, edit_context, edit_mode, max_bystanders;   // --edit-sites OUT.tsv --editor FROM:TO --edit-window FROM:TO [...]
+  bool have_editor = false, have_edit_window = false, have_edit_context = false, have_edit_mode = false, have_max_bystanders = false;
   std::string mh_path, mh_cut, min_oof;                                  // --microhomology MODEL.tsv [--mh-cut N] [--min-out-of-frame PCT]
   bool have_mh_cut = false, have_min_oof = false;
   for (int i = 2; i < argc; i++) {
@@ -507,6 +513,12 @@ static int find_guides_main(int argc, char** argv) {
     else if (a == "--alleles") alleles_path = next();
     else if (a == "--allele-sites") allele_sites_path = next();
     else if (a == "--allele-kinds") { allele_kinds = next(); have_allele_kinds = true; }
+    else if (a == "--edit-sites") edit_sites_path = next();
+    else if (a == "--editor") { editor = next(); have_editor = true; }
+    else if (a == "--edit-window") { edit_window = next(); have_edit_window = true; }
+    else if (a == "--edit-context") { edit_context = next(); have_edit_context = true; }
+    else if (a == "--edit-mode") { edit_mode = next(); have_edit_mode = true; }
+    else if (a == "--max-bystanders") { max_bystanders = next(); have_max_bystanders = true; }
     else if (a == "--microhomology") mh_path = next();
     else if (a == "--mh-cut") { mh_cut = next(); have_mh_cut = true; }
     else if (a == "--min-out-of-frame") { min_oof = next(); have_min_oof = true; }
@@ -573,9 +585,45 @@ static int find_guides_main(int argc, char** argv) {
     by_class.ext_from = (uint8_t)a; by_class.ext_to = (uint8_t)b;
   }
   // --alleles: the kinds of lines to write (tools.py allele_sites_tool)
-  const bool have_alleles = !alleles_path.empty();
-  if (have_alleles != !allele_sites_path.empty()) { std::fprintf(stderr, "calitas: --alleles FILE.vcf and --allele-sites OUT.tsv require each other\n"); return 2; }
-  if (have_allele_kinds && !have_alleles) { std::fprintf(stderr, "calitas: --allele-kinds requires --alleles FILE.vcf and --allele-sites OUT.tsv\n"); return 2; }
+  const bool have_alleles = !alleles_path.empty(), have_allele_sites = !allele_sites_path.empty(), have_edit_sites = !edit_sites_path.empty();
+  if (have_edit_sites && !(have_alleles && have_editor && have_edit_window)) { std::fprintf(stderr, "calitas: --edit-sites OUT.tsv requires --alleles FILE.vcf, --editor FROM:TO and --edit-window FROM:TO\n"); return 2; }
+  if (!have_edit_sites && (have_editor || have_edit_window || have_edit_context || have_edit_mode || have_max_bystanders)) {
+    std::fprintf(stderr, "calitas: --editor, --edit-window, --edit-context, --edit-mode and --max-bystanders require --edit-sites OUT.tsv\n");
+    return 2;
+  }
+  if (!have_alleles && have_allele_sites) { std::fprintf(stderr, "calitas: --alleles FILE.vcf and --allele-sites OUT.tsv require each other\n"); return 2; }
+  if (have_alleles && !have_allele_sites && !have_edit_sites) { std::fprintf(stderr, "calitas: --alleles FILE.vcf requires --allele-sites OUT.tsv or --edit-sites OUT.tsv\n"); return 2; }
+  if (have_allele_kinds && !have_allele_sites) { std::fprintf(stderr, "calitas: --allele-kinds requires --alleles FILE.vcf and --allele-sites OUT.tsv\n"); return 2; }
+  // --edit-sites: the editor from its flags (tools.py base_edit_of_flags)
+  calitas_base_edit_t edit{};
+  if (have_edit_sites) {
+    const auto base = [](char c) { return c != 0 && std::strchr("ACGT", c) != nullptr; };
+    if (!(editor.size() == 3 && editor[1] == ':' && base(editor[0]) && base(editor[2]) && editor[0] != editor[2])) {
+      std::fprintf(stderr, "calitas: --editor FROM:TO: two different letters of A C G T (C:T a CBE, A:G an ABE), not %s\n", editor.c_str());
+      return 2;
+    }
+    const size_t colon = edit_window.find(':');
+    const std::string from = edit_window.substr(0, colon), to = colon == std::string::npos ? std::string() : edit_window.substr(colon + 1);
+    const auto digits = [](const std::string& t) { return !t.empty() && t.size() <= 9 && t.find_first_not_of("0123456789") == std::string::npos; };
+    if (!digits(from) || !digits(to)) { std::fprintf(stderr, "calitas: --edit-window FROM:TO: two integers, 0-based and half-open in the protospacer, not %s\n", edit_window.c_str()); return 2; }
+    const long w0 = std::atol(from.c_str()), w1 = std::atol(to.c_str());
+    if (!(w0 < w1 && w1 <= (long)pg.proto.size())) { std::fprintf(stderr, "calitas: --edit-window FROM:TO: 0 <= FROM < TO <= %zu, the protospacer's length\n", pg.proto.size()); return 2; }
+    char context = 'N';
+    if (have_edit_context) {
+      context = edit_context.size() == 1 ? (char)std::toupper((unsigned char)edit_context[0]) : 0;
+      if (context == 0 || !std::strchr("ACGTUMRWSYKVHDBN", context)) { std::fprintf(stderr, "calitas: --edit-context: one IUPAC letter, not %s\n", edit_context.c_str()); return 2; }
+    }
+    if (have_edit_mode && edit_mode != "install" && edit_mode != "correct") { std::fprintf(stderr, "calitas: --edit-mode: install or correct, not %s\n", edit_mode.c_str()); return 2; }
+    if (have_max_bystanders && !(digits(max_bystanders) && std::atol(max_bystanders.c_str()) <= 31)) {
+      std::fprintf(stderr, "calitas: --max-bystanders N: an integer 0 .. 31, not %s\n", max_bystanders.c_str());
+      return 2;
+    }
+    edit.from_base = editor[0]; edit.to_base = editor[2];
+    edit.window_from = (uint8_t)w0; edit.window_to = (uint8_t)w1;
+    edit.context = context;
+    edit.correct = edit_mode == "correct" ? 1 : 0;
+    edit.max_bystanders = have_max_bystanders ? (uint8_t)std::atol(max_bystanders.c_str()) : 255;
+  }
   unsigned kinds_wanted = have_allele_kinds ? 0u : 14u;                  // bit k: lines of kind k (1 alt, 2 ref, 3 both)
   if (have_allele_kinds) {
     bool ok = true;
@@ -982,43 +1030,93 @@ static int find_guides_main(int argc, char** argv) {
       }
     }
     calitas_free(text);
-    calitas_allele_site_t* found = nullptr; uint64_t n_found = 0;
-    std::vector<uint8_t> status(snvs.size() + 1, 0);
-    const int rc2 = device < 0 ? calitas_find_allele_sites_host(ctx, &g, snvs.data(), snvs.size(), &found, &n_found, status.data())
-                               : calitas_find_allele_sites(ctx, &g, snvs.data(), snvs.size(), &found, &n_found, status.data());
-    if (rc2 != CALITAS_OK) die("finding allele sites");
-    FILE* af = std::fopen(allele_sites_path.c_str(), "w");
-    if (!af) { std::fprintf(stderr, "cannot write %s\n", allele_sites_path.c_str()); calitas_free(found); calitas_free(sites); calitas_free(activity_q16); calitas_free(site_class); calitas_destroy(ctx); return 1; }
-    std::fprintf(af, "chromosome\tposition\tid\tref\talt\tallele\tstart\tend\tstrand\tpam_index\tsnv_offset\tguide\tpam_sequence\tother_pam_index\n");
-    static const char* const kind_names[4] = {"", "alt", "ref", "both"};
-    for (uint64_t k = 0; k < n_found; k++) {
-      const calitas_allele_site_t& r = found[k];
-      if (!((kinds_wanted >> r.kind) & 1u)) continue;
-      const calitas_site_t& s = r.site;
-      const SnvRow& v = snv_rows[r.snv_index];
-      const int64_t lo = s.pam_start < 0 ? s.protospacer_start : std::min<int64_t>(s.protospacer_start, s.pam_start);
-      const int64_t hi = s.pam_start < 0 ? s.protospacer_start + L : std::max<int64_t>(s.protospacer_start + L, (int64_t)s.pam_start + s.pam_length);
-      std::string proto((size_t)L, 'N'), pam((size_t)s.pam_length, 'N');
-      for (int64_t i = 0; i < L; i++) proto[(size_t)i] = "ACGT"[((r.guide_lo >> i) & 1u) | (((r.guide_hi >> i) & 1u) << 1)];
-      if (s.pam_start >= 0 && s.pam_length) {
-        if (calitas_fetch_bases(ctx, s.contig_index, (uint64_t)s.pam_start, s.pam_length, &pam[0]) != CALITAS_OK) die("fetching bases");
-        if (r.kind != 2 && v.pos1 - 1 >= s.pam_start && v.pos1 - 1 < (long long)s.pam_start + s.pam_length) pam[(size_t)(v.pos1 - 1 - s.pam_start)] = v.alt[0];
-        pam = on_strand(pam, s.strand == '-');
-        for (auto& c : pam) if (c == 'U') c = 'T';
+    if (have_allele_sites) {
+      calitas_allele_site_t* found = nullptr; uint64_t n_found = 0;
+      std::vector<uint8_t> status(snvs.size() + 1, 0);
+      const int rc2 = device < 0 ? calitas_find_allele_sites_host(ctx, &g, snvs.data(), snvs.size(), &found, &n_found, status.data())
+                                 : calitas_find_allele_sites(ctx, &g, snvs.data(), snvs.size(), &found, &n_found, status.data());
+      if (rc2 != CALITAS_OK) die("finding allele sites");
+      FILE* af = std::fopen(allele_sites_path.c_str(), "w");
+      if (!af) { std::fprintf(stderr, "cannot write %s\n", allele_sites_path.c_str()); calitas_free(found); calitas_free(sites); calitas_free(activity_q16); calitas_free(site_class); calitas_destroy(ctx); return 1; }
+      std::fprintf(af, "chromosome\tposition\tid\tref\talt\tallele\tstart\tend\tstrand\tpam_index\tsnv_offset\tguide\tpam_sequence\tother_pam_index\n");
+      static const char* const kind_names[4] = {"", "alt", "ref", "both"};
+      for (uint64_t k = 0; k < n_found; k++) {
+        const calitas_allele_site_t& r = found[k];
+        if (!((kinds_wanted >> r.kind) & 1u)) continue;
+        const calitas_site_t& s = r.site;
+        const SnvRow& v = snv_rows[r.snv_index];
+        const int64_t lo = s.pam_start < 0 ? s.protospacer_start : std::min<int64_t>(s.protospacer_start, s.pam_start);
+        const int64_t hi = s.pam_start < 0 ? s.protospacer_start + L : std::max<int64_t>(s.protospacer_start + L, (int64_t)s.pam_start + s.pam_length);
+        std::string proto((size_t)L, 'N'), pam((size_t)s.pam_length, 'N');
+        for (int64_t i = 0; i < L; i++) proto[(size_t)i] = "ACGT"[((r.guide_lo >> i) & 1u) | (((r.guide_hi >> i) & 1u) << 1)];
+        if (s.pam_start >= 0 && s.pam_length) {
+          if (calitas_fetch_bases(ctx, s.contig_index, (uint64_t)s.pam_start, s.pam_length, &pam[0]) != CALITAS_OK) die("fetching bases");
+          if (r.kind != 2 && v.pos1 - 1 >= s.pam_start && v.pos1 - 1 < (long long)s.pam_start + s.pam_length) pam[(size_t)(v.pos1 - 1 - s.pam_start)] = v.alt[0];
+          pam = on_strand(pam, s.strand == '-');
+          for (auto& c : pam) if (c == 'U') c = 'T';
+        }
+        const std::string pattern_pam = s.pam_index >= 0 ? pg.pams[(size_t)s.pam_index] : std::string();
+        const std::string guide = five ? pattern_pam + proto : proto + pattern_pam;
+        std::fprintf(af, "%s\t%lld\t%s\t%s\t%s\t%s\t%lld\t%lld\t%c\t%d\t%d\t%s\t%s\t", v.chrom.c_str(), v.pos1, v.id.empty() ? "." : v.id.c_str(), v.ref.c_str(),
+                     v.alt.c_str(), kind_names[r.kind & 3u], (long long)lo, (long long)hi, (char)s.strand, (int)s.pam_index, (int)r.guide_offset, guide.c_str(), pam.c_str());
+        if (r.kind == 3) std::fprintf(af, "%d\n", (int)r.other_pam_index); else std::fprintf(af, ".\n");
       }
-      const std::string pattern_pam = s.pam_index >= 0 ? pg.pams[(size_t)s.pam_index] : std::string();
-      const std::string guide = five ? pattern_pam + proto : proto + pattern_pam;
-      std::fprintf(af, "%s\t%lld\t%s\t%s\t%s\t%s\t%lld\t%lld\t%c\t%d\t%d\t%s\t%s\t", v.chrom.c_str(), v.pos1, v.id.empty() ? "." : v.id.c_str(), v.ref.c_str(),
-                   v.alt.c_str(), kind_names[r.kind & 3u], (long long)lo, (long long)hi, (char)s.strand, (int)s.pam_index, (int)r.guide_offset, guide.c_str(), pam.c_str());
-      if (r.kind == 3) std::fprintf(af, "%d\n", (int)r.other_pam_index); else std::fprintf(af, ".\n");
+      std::fclose(af);
+      unsigned long long by[4] = {0, 0, 0, 0};
+      for (size_t i = 0; i < snvs.size(); i++) by[status[i] & 3u]++;
+      std::fprintf(stderr, "alleles: %llu SNVs examined, %llu records; skipped: %llu other alleles, %llu records on chromosomes the reference lacks, %llu beyond a contig's end, "
+                           "%llu with another REF than the reference, %llu on a base that is not A C G T, %llu with ALT equal to the reference\n",
+                   by[0], (unsigned long long)n_found, other, lacks, beyond, by[1], by[2], by[3]);
+      calitas_free(found);
     }
-    std::fclose(af);
-    unsigned long long by[4] = {0, 0, 0, 0};
-    for (size_t i = 0; i < snvs.size(); i++) by[status[i] & 3u]++;
-    std::fprintf(stderr, "alleles: %llu SNVs examined, %llu records; skipped: %llu other alleles, %llu records on chromosomes the reference lacks, %llu beyond a contig's end, "
-                         "%llu with another REF than the reference, %llu on a base that is not A C G T, %llu with ALT equal to the reference\n",
-                 by[0], (unsigned long long)n_found, other, lacks, beyond, by[1], by[2], by[3]);
-    calitas_free(found);
+    // the guides that put the SNVs into the base editor's window (tools.py edit_sites_tool, edit_sites_tsv)
+    if (have_edit_sites) {
+      calitas_edit_site_t* found = nullptr; uint64_t n_found = 0;
+      std::vector<uint8_t> status(snvs.size() + 1, 0);
+      const int rc2 = device < 0 ? calitas_find_edit_sites_host(ctx, &g, &edit, snvs.data(), snvs.size(), &found, &n_found, status.data())
+                                 : calitas_find_edit_sites(ctx, &g, &edit, snvs.data(), snvs.size(), &found, &n_found, status.data());
+      if (rc2 != CALITAS_OK) die("finding edit sites");
+      FILE* ef = std::fopen(edit_sites_path.c_str(), "w");
+      if (!ef) { std::fprintf(stderr, "cannot write %s\n", edit_sites_path.c_str()); calitas_free(found); calitas_free(sites); calitas_free(activity_q16); calitas_free(site_class); calitas_destroy(ctx); return 1; }
+      std::fprintf(ef, "chromosome\tposition\tid\tref\talt\tmode\tstart\tend\tstrand\tpam_index\tedit_offset\tguide\tpam_sequence\tbystanders\tbystander_offsets\tedited\n");
+      const char product = (char)std::tolower((unsigned char)edit.to_base);
+      for (uint64_t k = 0; k < n_found; k++) {
+        const calitas_edit_site_t& r = found[k];
+        const calitas_site_t& s = r.site;
+        const SnvRow& v = snv_rows[r.snv_index];
+        const int64_t lo = s.pam_start < 0 ? s.protospacer_start : std::min<int64_t>(s.protospacer_start, s.pam_start);
+        const int64_t hi = s.pam_start < 0 ? s.protospacer_start + L : std::max<int64_t>(s.protospacer_start + L, (int64_t)s.pam_start + s.pam_length);
+        const int offset = (int)(s.strand == '-' ? s.protospacer_start + L - 1 - (v.pos1 - 1) : (v.pos1 - 1) - s.protospacer_start);
+        std::string proto((size_t)L, 'N'), pam((size_t)s.pam_length, 'N'), offsets;
+        for (int64_t i = 0; i < L; i++) proto[(size_t)i] = "ACGT"[((r.guide_lo >> i) & 1u) | (((r.guide_hi >> i) & 1u) << 1)];
+        std::string edited = proto;
+        int bystanders = 0;
+        for (int i = 0; i < (int)L; i++) {
+          if (!((r.editable >> i) & 1u)) continue;
+          edited[(size_t)i] = product;
+          if (i == offset) continue;
+          offsets += (bystanders++ ? "," : "") + std::to_string(i);
+        }
+        if (s.pam_start >= 0 && s.pam_length) {
+          if (calitas_fetch_bases(ctx, s.contig_index, (uint64_t)s.pam_start, s.pam_length, &pam[0]) != CALITAS_OK) die("fetching bases");
+          pam = on_strand(pam, s.strand == '-');
+          for (auto& c : pam) if (c == 'U') c = 'T';
+        }
+        const std::string pattern_pam = s.pam_index >= 0 ? pg.pams[(size_t)s.pam_index] : std::string();
+        const std::string guide = five ? pattern_pam + proto : proto + pattern_pam;
+        std::fprintf(ef, "%s\t%lld\t%s\t%s\t%s\t%s\t%lld\t%lld\t%c\t%d\t%d\t%s\t%s\t%d\t%s\t%s\n", v.chrom.c_str(), v.pos1, v.id.empty() ? "." : v.id.c_str(),
+                     v.ref.c_str(), v.alt.c_str(), edit.correct ? "correct" : "install", (long long)lo, (long long)hi, (char)s.strand, (int)s.pam_index, offset,
+                     guide.c_str(), pam.c_str(), bystanders, offsets.empty() ? "." : offsets.c_str(), edited.c_str());
+      }
+      std::fclose(ef);
+      unsigned long long by[6] = {0, 0, 0, 0, 0, 0};
+      for (size_t i = 0; i < snvs.size(); i++) by[status[i] < 6 ? status[i] : 0]++;
+      std::fprintf(stderr, "edits: %llu SNVs examined, %llu records; skipped: %llu other alleles, %llu records on chromosomes the reference lacks, %llu beyond a contig's end, "
+                           "%llu with another REF than the reference, %llu on a base that is not A C G T, %llu with ALT equal to the reference, "
+                           "%llu that are not the editor's change, %llu whose 5' neighbour fails the context\n",
+                   by[0], (unsigned long long)n_found, other, lacks, beyond, by[1], by[2], by[3], by[4], by[5]);
+      calitas_free(found);
+    }
   }
   std::fprintf(stderr, "calitas: %llu guides\n", (unsigned long long)n_rows);
   calitas_free(sites); calitas_free(activity_q16); calitas_free(site_class); calitas_free(mh_q16); calitas_destroy(ctx);

@@ -1,4 +1,4 @@
-// kernels.hpp -- launch interface of scan_columns.hip, scan_rows.hip, align.hip, trace.hip, setup.hip, sites.hip, activity.hip, site_pairs.hip, allele_sites.hip and microhomology.hip (device pointers only).
+// kernels.hpp -- launch interface of scan_columns.hip, scan_rows.hip, align.hip, trace.hip, setup.hip, sites.hip, activity.hip, site_pairs.hip, allele_sites.hip, microhomology.hip and edit_sites.hip (device pointers only).
 #pragma once
 #include "mailbox.hpp"
 #include <hip/hip_runtime_api.h>
@@ -431,5 +431,54 @@ hipError_t launch_mh_score(const MhArgs& a, hipStream_t stream);
 hipError_t launch_mh_compact(const SiteRecord* recs, const MhScore* scores, uint64_t n, uint32_t permille, const uint64_t* wg_offset,
                              SiteRecord* out_recs, MhScore* out_scores, uint64_t out_capacity, hipStream_t stream);
 inline uint32_t mh_blocks(uint64_t n) { return (uint32_t)((n + MH_THREADS - 1) / MH_THREADS); }
+
+// edit_sites.hip: calitas_find_edit_sites.  One lane per SNV (Snv, as the allele call reads it); the at most 32 protospacer starts
+// whose protospacer can hold the SNV, p = position - 31 + j, are one 32-bit match vector per PAM, matched on the background allele
+// alone and on the SNV's strand alone.
+constexpr int EDIT_THREADS = 256;
+constexpr uint32_t EDIT_MAX_RECORDS = MAX_L;                // per SNV: window_to - window_from
+constexpr uint32_t EDIT_NO_BOUND = 255;                     // EditRule::max_bystanders
+struct EditRule {                  // calitas_base_edit_t after validation
+  uint32_t from, to;               // 2-bit codes
+  uint32_t window_from, window_to; // 0 <= from < to <= L
+  uint32_t context;                // the set the base 5' of an edited base must be in, bit c = code c; 15: any
+  uint32_t correct;                // 0: the background allele is the reference's base, 1: it is alt
+  uint32_t max_bystanders;         // 0 .. 31, EDIT_NO_BOUND
+};
+struct EditSite {                  // = calitas_edit_site_t
+  SiteRecord site;
+  uint32_t snv_index;
+  uint32_t editable;
+  uint32_t guide_lo, guide_hi;
+};
+static_assert(sizeof(EditSite) == 32, "two 16-byte stores per record");
+// the set of the complements of a set's bases
+CAL_HD inline uint32_t edit_complement_set(uint32_t set) { return ((set & 1u) << 3) | ((set & 2u) << 1) | ((set & 4u) >> 1) | ((set & 8u) >> 3); }
+// The strand on which background base b becoming p is the editor's change: 0 '+', 1 '-', -1 neither.
+CAL_HD inline int edit_strand(const EditRule& e, uint32_t b, uint32_t p) {
+  return (b == e.from && p == e.to) ? 0 : (3u - b == e.from && 3u - p == e.to) ? 1 : -1;
+}
+struct EditArgs {
+  const uint2* planes;
+  const uint32_t* mask;
+  const ContigInfo* contigs;
+  const SitePatterns* pat;         // device memory: the head of a SiteTables
+  const Snv* snvs;                 // reserved == ALLELE_HOST_DECIDES: a U within reach, the host twin decides
+  uint64_t n;                      // < 2^32
+  uint64_t n_words;                // 32-base words of the packed space
+  int32_t n_contigs;
+  uint32_t* lane_count;            // n: the records of SNV i
+  uint8_t* status;                 // n
+  uint32_t* wg_count;              // per workgroup: the sum of its lanes' counts
+  unsigned long long* per_bystanders;   // 4 (0, 1, 2, 3 or more), 0 at launch (the count kernel)
+  const uint64_t* wg_offset;       // the scan of wg_count (the write kernel)
+  EditSite* out;
+  uint64_t out_capacity;
+  EditRule rule;
+};
+inline uint32_t edit_blocks(uint64_t n) { return (uint32_t)((n + EDIT_THREADS - 1) / EDIT_THREADS); }
+hipError_t launch_edit_count(const EditArgs& a, hipStream_t stream);
+// The records in (SNV, start) order: record k of SNV i of workgroup g goes to wg_offset[g] + the counts of g's lanes before i + k.
+hipError_t launch_edit_write(const EditArgs& a, hipStream_t stream);
 
 }  // namespace calitas

@@ -89,6 +89,11 @@ int calitas_find_allele_sites_host_impl(const calitas_ctx* ctx, const calitas_gu
                                         calitas_allele_site_t** sites, uint64_t* per_kind, uint64_t* n_sites, uint8_t* status);
 int calitas_find_allele_sites_impl(calitas_ctx* ctx, const calitas_guide_t* pattern, const calitas_snv_t* snvs, uint64_t n_snvs, bool listing,
                                    calitas_allele_site_t** sites, uint64_t* per_kind, uint64_t* n_sites, uint8_t* status);
+// the records of the SNVs in input order; listing false: the numbers alone (per_bystanders and status may be null)
+int calitas_find_edit_sites_host_impl(const calitas_ctx* ctx, const calitas_guide_t* pattern, const calitas_base_edit_t* edit, const calitas_snv_t* snvs,
+                                      uint64_t n_snvs, bool listing, calitas_edit_site_t** sites, uint64_t* per_bystanders, uint64_t* n_sites, uint8_t* status);
+int calitas_find_edit_sites_impl(calitas_ctx* ctx, const calitas_guide_t* pattern, const calitas_base_edit_t* edit, const calitas_snv_t* snvs, uint64_t n_snvs,
+                                 bool listing, calitas_edit_site_t** sites, uint64_t* per_bystanders, uint64_t* n_sites, uint8_t* status);
 // the records of calitas_find_sites_filtered kept under permille (0: all of them) and their microhomology scores under the model
 int calitas_find_sites_microhomology_host_impl(const calitas_ctx* ctx, const calitas_guide_t* pattern, const calitas_site_filter_t* filter,
                                                const calitas_mh_model_t* model, int32_t permille, int32_t chrom_index, uint64_t start, uint64_t end,

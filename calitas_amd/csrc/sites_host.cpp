@@ -14,7 +14,9 @@
 // calitas_count_site_pairs and their host twins: the checks, the one walk over a sorted listing (pair_walk) that the twins and the
 // listings beside a U share, and the driver of site_pairs.hip's kernels behind the site kernel's two passes.  calitas_find_allele_sites / calitas_count_allele_sites and
 // their host twins: the checks, the twin (a base-by-base walk with one base replaced) that also decides the SNVs beside a U, and the
-// driver of allele_sites.hip's two kernels.  calitas_find_sites_microhomology / calitas_find_sites_microhomology_host: the model's checks, the
+// driver of allele_sites.hip's two kernels.  calitas_find_edit_sites / calitas_count_edit_sites and their host twins: the editor's
+// checks, the twin (a base-by-base walk of the background allele on the SNV's strand) that also decides the SNVs beside a U, and the
+// driver of edit_sites.hip's two kernels.  calitas_find_sites_microhomology / calitas_find_sites_microhomology_host: the model's checks, the
 // score of one site as a diagonal walk over letters, the host twin, and the driver of microhomology.hip's kernels behind the site
 // kernel's two passes with the correction of records and scores beside a U.  No reference counterpart.
 #include "sites.hpp"
@@ -285,6 +287,18 @@ struct SitesWork {
   SiteRecord* d_mh_out = nullptr;
   MhScore* d_mh_out_scores = nullptr;
   size_t mh_out_cap = 0;
+  // calitas_find_edit_sites: the SNVs, a count and a status byte per SNV, the workgroups' sums and their scan, the four bystander
+  // counters, and the records in order
+  Snv* d_ed_snvs = nullptr;
+  uint32_t* d_ed_lanes = nullptr;
+  uint8_t* d_ed_status = nullptr;
+  size_t ed_snvs_cap = 0;
+  uint32_t* d_ed_count = nullptr;
+  uint64_t* d_ed_off = nullptr;
+  size_t ed_blocks_cap = 0;
+  unsigned long long* d_ed_by = nullptr;
+  EditSite* d_ed_out = nullptr;
+  size_t ed_out_cap = 0;
   // the U / u runs of the resident reference (a U is a plain base to a site and an exception base to the kernels)
   uint64_t u_serial = ~0ull;
   std::vector<Run> u_runs;
@@ -301,6 +315,7 @@ void sites_destroy(SitesWork* w) {
   (void)hipFree(w->d_pair_lanes); (void)hipFree(w->d_pair_count); (void)hipFree(w->d_pair_off); (void)hipFree(w->d_pair_by); (void)hipFree(w->d_pair_out);
   (void)hipFree(w->d_snvs); (void)hipFree(w->d_al_lanes); (void)hipFree(w->d_al_status); (void)hipFree(w->d_al_count); (void)hipFree(w->d_al_off); (void)hipFree(w->d_al_by); (void)hipFree(w->d_al_out);
   (void)hipFree(w->d_mh_scores); (void)hipFree(w->d_mh_count); (void)hipFree(w->d_mh_off); (void)hipFree(w->d_mh_out); (void)hipFree(w->d_mh_out_scores);
+  (void)hipFree(w->d_ed_snvs); (void)hipFree(w->d_ed_lanes); (void)hipFree(w->d_ed_status); (void)hipFree(w->d_ed_count); (void)hipFree(w->d_ed_off); (void)hipFree(w->d_ed_by); (void)hipFree(w->d_ed_out);
   delete w;
 }
 
@@ -2241,6 +2256,235 @@ int calitas_find_allele_sites_impl(calitas_ctx* ctx, const calitas_guide_t* patt
     std::memcpy(block + total, on_host.data(), on_host.size() * sizeof(calitas_allele_site_t));
     std::inplace_merge(block, block + total, block + *n_sites,
                        [](const calitas_allele_site_t& x, const calitas_allele_site_t& y) { return x.snv_index < y.snv_index; });
+  }
+  *sites = block;
+  return CALITAS_OK;
+}
+
+// ---- calitas_find_edit_sites: the base-editor guides of a single-nucleotide variant and their bystanders ----
+
+namespace {
+
+// checked in this order: the pattern as calitas_find_sites checks it, the editor field by field, the SNVs as calitas_find_allele_sites
+// checks them (plan_allele_sites: its messages name the SNV's field and index)
+int plan_edit_sites(calitas_ctx* c, const calitas_guide_t* pattern, const calitas_base_edit_t* edit, const calitas_snv_t* snvs, uint64_t n_snvs, SiteCall& call,
+                    EditRule& rule) {
+  if (int rc = plan_site_pattern(c, pattern, nullptr, call)) return rc;
+  const int L = call.tab.pat.proto_len;
+  if (!allele_letter(edit->from_base)) return calitas_fail(c, CALITAS_EINVAL, "edit sites: from_base is not one of A C G T U");
+  if (!allele_letter(edit->to_base)) return calitas_fail(c, CALITAS_EINVAL, "edit sites: to_base is not one of A C G T U");
+  if (allele_code(edit->from_base) == allele_code(edit->to_base)) return calitas_fail(c, CALITAS_EINVAL, "edit sites: from_base and to_base are the same base");
+  if (edit->window_from >= edit->window_to)
+    return calitas_fail(c, CALITAS_EINVAL, "edit sites: window_from " + std::to_string(edit->window_from) + " .. window_to " + std::to_string(edit->window_to) + " is an empty window");
+  if (edit->window_to > L)
+    return calitas_fail(c, CALITAS_EINVAL, "edit sites: window_to " + std::to_string(edit->window_to) + " lies past the protospacer's " + std::to_string(L) + " bases");
+  const int context = edit->context == 0 ? 15 : iupac_mask((unsigned char)edit->context);
+  if (context == 0) return calitas_fail(c, CALITAS_EINVAL, "edit sites: context is no IUPAC letter");
+  if (edit->correct > 1) return calitas_fail(c, CALITAS_EINVAL, "edit sites: correct is 0 (install) or 1 (correct), not " + std::to_string(edit->correct));
+  if (edit->max_bystanders >= 32 && edit->max_bystanders != EDIT_NO_BOUND)
+    return calitas_fail(c, CALITAS_EINVAL, "edit sites: max_bystanders is 0 .. 31 or 255 (no bound), not " + std::to_string(edit->max_bystanders));
+  if (edit->reserved != 0) return calitas_fail(c, CALITAS_EINVAL, "edit sites: reserved must be 0");
+  rule.from = allele_code(edit->from_base); rule.to = allele_code(edit->to_base);
+  rule.window_from = edit->window_from; rule.window_to = edit->window_to;
+  rule.context = (uint32_t)context; rule.correct = edit->correct; rule.max_bystanders = edit->max_bystanders;
+  return plan_allele_sites(c, pattern, snvs, n_snvs, call);
+}
+
+// The contract on one SNV, base by base: its status; its records appended to *out (may be null) and counted by bystanders.
+uint8_t edit_sites_of_snv(const PackedRef& ref, const SitePatterns& pat, const EditRule& e, const calitas_snv_t& v, uint32_t index,
+                          std::vector<calitas_edit_site_t>* out, uint64_t (&by)[4]) {
+  const ContigInfo& ci = ref.contigs[(size_t)v.contig_index];
+  const int64_t pos = v.position;
+  const AlleleText on_ref{ref, ci.gbase, (int64_t)ci.len, pos, -1};
+  const int ref_code = on_ref.code(pos);
+  if (ref_code < 0) return 2;
+  if (v.ref != 0 && (int)allele_code(v.ref) != ref_code) return 1;
+  const int alt_code = (int)allele_code(v.alt);
+  if (alt_code == ref_code) return 3;
+  const int background = e.correct ? alt_code : ref_code, product = e.correct ? ref_code : alt_code;
+  const int st = edit_strand(e, (uint32_t)background, (uint32_t)product);
+  if (st < 0) return 4;
+  const AlleleText text{ref, ci.gbase, (int64_t)ci.len, pos, background};
+  const int L = pat.proto_len;
+  // base i of the guide at start p, -1 .. L - 1: its code, -1 where there is none
+  const auto guide_base = [&](int64_t p, int i) {
+    const int c = st ? text.code(p + L - 1 - i) : text.code(p + i);
+    return c < 0 ? -1 : st ? 3 - c : c;
+  };
+  const auto editable = [&](int64_t p, int i) {
+    if (i < (int)e.window_from || i >= (int)e.window_to || guide_base(p, i) != (int)e.from) return false;
+    if (e.context == 15u) return true;
+    const int before = guide_base(p, i - 1);
+    return before >= 0 && ((e.context >> before) & 1u) != 0;
+  };
+  {   // the target's own 5' neighbour: the same bases whatever the start
+    const int64_t p = st ? pos - L + 1 + (int64_t)e.window_from : pos - (int64_t)e.window_from;
+    if (!editable(p, (int)e.window_from)) return 5;
+  }
+  const int64_t p0 = st ? pos - L + 1 + (int64_t)e.window_from : pos - (int64_t)e.window_to + 1;   // the first start that holds the SNV in the window
+  for (int64_t p = p0; p < p0 + (int64_t)(e.window_to - e.window_from); p++) {
+    const int k = allele_first_pam(text, pat, p, st);
+    if (k < 0) continue;
+    calitas_edit_site_t r;
+    std::memset(&r, 0, sizeof(r));
+    for (int i = 0; i < L; i++) {
+      const int c = guide_base(p, i);
+      r.editable |= (uint32_t)(editable(p, i) ? 1 : 0) << i;
+      r.guide_lo |= (uint32_t)(c & 1) << i;
+      r.guide_hi |= (uint32_t)(c >> 1) << i;
+    }
+    const int64_t o = st ? p + L - 1 - pos : pos - p;
+    if (!((r.editable >> o) & 1u)) continue;                        // (cannot happen: status 5 otherwise)
+    const uint32_t bystanders = (uint32_t)__builtin_popcount(r.editable) - 1u;
+    if (e.max_bystanders != EDIT_NO_BOUND && bystanders > e.max_bystanders) continue;
+    by[bystanders < 3u ? bystanders : 3u]++;
+    if (!out) continue;
+    r.site = site_record(pat, v.contig_index, p, st, k);
+    r.snv_index = index;
+    out->push_back(r);
+  }
+  return 0;
+}
+
+int edit_block_out(calitas_ctx* c, const std::vector<calitas_edit_site_t>& found, calitas_edit_site_t** sites) {
+  *sites = (calitas_edit_site_t*)calitas_out_alloc(std::max<size_t>(1, found.size()) * sizeof(calitas_edit_site_t));
+  if (!*sites) return calitas_fail(c, CALITAS_EINVAL, "out of memory");
+  if (!found.empty()) std::memcpy(*sites, found.data(), found.size() * sizeof(calitas_edit_site_t));
+  return CALITAS_OK;
+}
+
+}  // namespace
+
+int calitas_find_edit_sites_host_impl(const calitas_ctx* ctx, const calitas_guide_t* pattern, const calitas_base_edit_t* edit, const calitas_snv_t* snvs,
+                                      uint64_t n_snvs, bool listing, calitas_edit_site_t** sites, uint64_t* per_bystanders, uint64_t* n_sites, uint8_t* status) {
+  calitas_ctx* c = const_cast<calitas_ctx*>(ctx);
+  SiteCall call;
+  EditRule rule{};
+  if (int rc = plan_edit_sites(c, pattern, edit, snvs, n_snvs, call, rule)) return rc;
+  std::vector<calitas_edit_site_t> found;
+  uint64_t by[4] = {};
+  for (uint64_t i = 0; i < n_snvs; i++) {
+    const uint8_t s = edit_sites_of_snv(ctx->ref, call.tab.pat, rule, snvs[i], (uint32_t)i, listing ? &found : nullptr, by);
+    if (status) status[i] = s;
+  }
+  *n_sites = by[0] + by[1] + by[2] + by[3];
+  if (per_bystanders) std::memcpy(per_bystanders, by, sizeof(by));
+  return listing ? edit_block_out(c, found, sites) : CALITAS_OK;
+}
+
+int calitas_find_edit_sites_impl(calitas_ctx* ctx, const calitas_guide_t* pattern, const calitas_base_edit_t* edit, const calitas_snv_t* snvs, uint64_t n_snvs,
+                                 bool listing, calitas_edit_site_t** sites, uint64_t* per_bystanders, uint64_t* n_sites, uint8_t* status) {
+  if (ctx->device < 0) return calitas_fail(ctx, CALITAS_ENODEV, "host-only context: calitas_find_edit_sites needs a GPU (there is no CPU fallback; calitas_find_edit_sites_host is the host twin)");
+  SiteCall call;
+  EditRule rule{};
+  if (int rc = plan_edit_sites(ctx, pattern, edit, snvs, n_snvs, call, rule)) return rc;
+  static_assert(sizeof(EditSite) == sizeof(calitas_edit_site_t) && offsetof(EditSite, snv_index) == offsetof(calitas_edit_site_t, snv_index) &&
+                offsetof(EditSite, editable) == offsetof(calitas_edit_site_t, editable) && offsetof(EditSite, guide_lo) == offsetof(calitas_edit_site_t, guide_lo) &&
+                offsetof(EditSite, guide_hi) == offsetof(calitas_edit_site_t, guide_hi), "the kernel writes calitas_edit_site_t");
+  static_assert(sizeof(calitas_base_edit_t) == 8 && EDIT_MAX_RECORDS == 32 && MAX_L - 1 + MAX_PAM_LEN + SITE_MAX_FOOT <= 96, "the window of starts is one 32-bit vector, its text 96 bases");
+  uint64_t by[4] = {};
+  if (per_bystanders) std::memcpy(per_bystanders, by, sizeof(by));
+  std::vector<calitas_edit_site_t> on_host;
+  if (n_snvs == 0) return listing ? edit_block_out(ctx, on_host, sites) : CALITAS_OK;
+  const PackedRef& ref = ctx->ref;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  if (!ctx->sites) ctx->sites = new SitesWork();
+  SitesWork* w = ctx->sites;
+
+  // A U is a T to a site and an exception base to the kernel.  Every base a lane's records depend on lies within 63 of its SNV (a
+  // footprint over a start that holds the SNV in the window, the base 5' of a protospacer): the SNVs with a U that near are decided
+  // here, by the twin's walk; the device's copy of such a SNV says so and the kernel leaves it alone.
+  if (w->u_serial != ctx->ref_serial) {
+    w->u_runs.clear();
+    for (const Run& r : ref.runs) if (r.ch == 'U' || r.ch == 'u') w->u_runs.push_back(r);
+    w->u_serial = ctx->ref_serial;
+  }
+  std::vector<Snv> marked;
+  std::vector<uint64_t> host_snvs;
+  if (!w->u_runs.empty()) {
+    for (uint64_t i = 0; i < n_snvs; i++) {
+      const uint64_t g = ref.contigs[(size_t)snvs[i].contig_index].gbase + (uint64_t)snvs[i].position;
+      const uint64_t from = g >= 63 ? g - 63 : 0;
+      const auto at = std::partition_point(w->u_runs.begin(), w->u_runs.end(), [&](const Run& r) { return r.start + r.len <= from; });
+      if (at != w->u_runs.end() && at->start <= g + 63) host_snvs.push_back(i);
+    }
+    if (!host_snvs.empty()) {
+      marked.resize(n_snvs);
+      std::memcpy(marked.data(), snvs, n_snvs * sizeof(Snv));
+      for (uint64_t i : host_snvs) marked[i].reserved = ALLELE_HOST_DECIDES;
+    }
+  }
+
+  const char* const no_room = "the SNVs and their records do not fit the device: pass the SNVs in pieces";
+  const uint32_t n_blocks = edit_blocks(n_snvs);
+  if (!w->d_pat) HIP_TRY(ctx, hipMalloc((void**)&w->d_pat, sizeof(SiteTables)));
+  if (w->ed_snvs_cap < n_snvs) {
+    (void)hipFree(w->d_ed_snvs); (void)hipFree(w->d_ed_lanes); (void)hipFree(w->d_ed_status);
+    w->d_ed_snvs = nullptr; w->d_ed_lanes = nullptr; w->d_ed_status = nullptr; w->ed_snvs_cap = 0;
+    if (hipMalloc((void**)&w->d_ed_snvs, n_snvs * sizeof(Snv)) != hipSuccess || hipMalloc((void**)&w->d_ed_lanes, n_snvs * sizeof(uint32_t)) != hipSuccess ||
+        hipMalloc((void**)&w->d_ed_status, n_snvs) != hipSuccess) {
+      (void)hipGetLastError();
+      (void)hipFree(w->d_ed_snvs); (void)hipFree(w->d_ed_lanes); (void)hipFree(w->d_ed_status);
+      w->d_ed_snvs = nullptr; w->d_ed_lanes = nullptr; w->d_ed_status = nullptr;
+      return calitas_fail(ctx, CALITAS_ENOMEM, no_room);
+    }
+    w->ed_snvs_cap = n_snvs;
+  }
+  if (w->ed_blocks_cap < (size_t)n_blocks + 1) {
+    (void)hipFree(w->d_ed_count); (void)hipFree(w->d_ed_off); w->d_ed_count = nullptr; w->d_ed_off = nullptr; w->ed_blocks_cap = 0;
+    HIP_TRY(ctx, hipMalloc((void**)&w->d_ed_count, ((size_t)n_blocks + 1) * sizeof(uint32_t)));
+    HIP_TRY(ctx, hipMalloc((void**)&w->d_ed_off, ((size_t)n_blocks + 1) * sizeof(uint64_t)));
+    w->ed_blocks_cap = (size_t)n_blocks + 1;
+  }
+  if (!w->d_ed_by) HIP_TRY(ctx, hipMalloc((void**)&w->d_ed_by, 4 * sizeof(unsigned long long)));
+
+  EditArgs a{};
+  a.planes = ctx->d_planes; a.mask = ctx->d_mask; a.contigs = ctx->d_contigs; a.pat = &w->d_pat->pat; a.snvs = w->d_ed_snvs; a.n = n_snvs;
+  a.n_words = ref.total_packed / 32; a.n_contigs = (int32_t)ref.contigs.size();
+  a.lane_count = w->d_ed_lanes; a.status = w->d_ed_status; a.wg_count = w->d_ed_count; a.per_bystanders = w->d_ed_by; a.wg_offset = w->d_ed_off;
+  a.out = nullptr; a.out_capacity = 0;
+  a.rule = rule;
+  uint64_t total = 0;
+  HIP_TRY(ctx, hipMemcpyAsync(w->d_pat, &call.tab, sizeof(SitePatterns), hipMemcpyHostToDevice, ctx->stream));
+  HIP_TRY(ctx, hipMemcpyAsync(w->d_ed_snvs, marked.empty() ? (const void*)snvs : (const void*)marked.data(), n_snvs * sizeof(Snv), hipMemcpyHostToDevice, ctx->stream));
+  HIP_TRY(ctx, hipMemsetAsync(w->d_ed_by, 0, 4 * sizeof(unsigned long long), ctx->stream));
+  HIP_TRY(ctx, launch_edit_count(a, ctx->stream));
+  HIP_TRY(ctx, launch_sites_offsets(w->d_ed_count, w->d_ed_off, n_blocks, ctx->stream));
+  HIP_TRY(ctx, hipMemcpyAsync(&total, w->d_ed_off + n_blocks, sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipMemcpyAsync(by, w->d_ed_by, sizeof(by), hipMemcpyDeviceToHost, ctx->stream));
+  if (status) HIP_TRY(ctx, hipMemcpyAsync(status, w->d_ed_status, n_snvs, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  if (by[0] + by[1] + by[2] + by[3] != total) return calitas_fail(ctx, CALITAS_EHIP, "calitas_find_edit_sites: the workgroups' sums do not add up to the bystander bins' (internal error)");
+
+  for (uint64_t i : host_snvs) {
+    const uint8_t s = edit_sites_of_snv(ref, call.tab.pat, rule, snvs[i], (uint32_t)i, listing ? &on_host : nullptr, by);
+    if (status) status[i] = s;
+  }
+  *n_sites = by[0] + by[1] + by[2] + by[3];
+  if (per_bystanders) std::memcpy(per_bystanders, by, sizeof(by));
+  if (!listing) return CALITAS_OK;
+
+  if (total && w->ed_out_cap < total) {
+    (void)hipFree(w->d_ed_out); w->d_ed_out = nullptr; w->ed_out_cap = 0;
+    if (hipMalloc((void**)&w->d_ed_out, total * sizeof(EditSite)) != hipSuccess) { (void)hipGetLastError(); return calitas_fail(ctx, CALITAS_ENOMEM, no_room); }
+    w->ed_out_cap = total;
+  }
+  calitas_edit_site_t* block = (calitas_edit_site_t*)calitas_out_alloc(std::max<uint64_t>(1, *n_sites) * sizeof(calitas_edit_site_t));
+  if (!block) return calitas_fail(ctx, CALITAS_EINVAL, "out of memory");
+  if (total) {
+    hipError_t e = hipSuccess;
+    a.out = w->d_ed_out; a.out_capacity = total;
+    if ((e = launch_edit_write(a, ctx->stream)) != hipSuccess ||
+        (e = hipMemcpyAsync(block, w->d_ed_out, total * sizeof(EditSite), hipMemcpyDeviceToHost, ctx->stream)) != hipSuccess ||
+        (e = hipStreamSynchronize(ctx->stream)) != hipSuccess) {
+      calitas_free(block);
+      return calitas_fail(ctx, CALITAS_EHIP, std::string("calitas_find_edit_sites: ") + hipGetErrorString(e));
+    }
+  }
+  if (!on_host.empty()) {                          // both stretches are in SNV order and share no SNV
+    std::memcpy(block + total, on_host.data(), on_host.size() * sizeof(calitas_edit_site_t));
+    std::inplace_merge(block, block + total, block + *n_sites,
+                       [](const calitas_edit_site_t& x, const calitas_edit_site_t& y) { return x.snv_index < y.snv_index; });
   }
   *sites = block;
   return CALITAS_OK;

@@ -812,11 +812,86 @@ def allele_sites_tool(ctx, pat, vcf, out_path, kinds=None, chrom=None, start=0, 
                      % (by[0], len(found.sites), skipped["other"], skipped["lacks"], skipped["beyond"], by[1], by[2], by[3]))
 
 
+EDIT_COLUMNS = ["chromosome", "position", "id", "ref", "alt", "mode", "start", "end", "strand", "pam_index", "edit_offset", "guide", "pam_sequence",
+                "bystanders", "bystander_offsets", "edited"]
+
+
+def _ascii_digits(text):
+    """1 .. 9 of the digits 0 .. 9: what the command line tool takes for a number."""
+    return 1 <= len(text) <= 9 and all(c in "0123456789" for c in text)
+
+
+def base_edit_of_flags(pat, editor, edit_window, edit_context=None, edit_mode=None, max_bystanders=None):
+    """The BaseEdit of FindGuides' flags: --editor FROM:TO (two different letters of A C G T), --edit-window FROM:TO (positions of the
+    protospacer as the guide reads, 0-based and half-open), --edit-context LETTER (IUPAC; default N), --edit-mode install|correct
+    (default install), --max-bystanders N (0 .. 31; default no bound)."""
+    from .aligner import _IUPAC_SETS, BaseEdit
+    a, sep, b = str(editor).partition(":")
+    if not (sep and len(a) == 1 and len(b) == 1 and a in "ACGT" and b in "ACGT" and a != b):
+        raise ValueError("--editor FROM:TO: two different letters of A C G T (C:T a CBE, A:G an ABE), not %s" % editor)
+    w0, sep, w1 = str(edit_window).partition(":")
+    if not (sep and _ascii_digits(w0) and _ascii_digits(w1)):
+        raise ValueError("--edit-window FROM:TO: two integers, 0-based and half-open in the protospacer, not %s" % edit_window)
+    if not int(w0) < int(w1) <= pat.protospacer_length:
+        raise ValueError("--edit-window FROM:TO: 0 <= FROM < TO <= %d, the protospacer's length" % pat.protospacer_length)
+    context = "N" if edit_context is None else str(edit_context)
+    if not (len(context) == 1 and context.upper() in _IUPAC_SETS):
+        raise ValueError("--edit-context: one IUPAC letter, not %s" % edit_context)
+    if edit_mode not in (None, "install", "correct"):
+        raise ValueError("--edit-mode: install or correct, not %s" % edit_mode)
+    if max_bystanders is not None and not (_ascii_digits(str(max_bystanders)) and int(max_bystanders) <= 31):
+        raise ValueError("--max-bystanders N: an integer 0 .. 31, not %s" % max_bystanders)
+    return BaseEdit(a, b, (int(w0), int(w1)), context.upper(), edit_mode == "correct", None if max_bystanders is None else int(max_bystanders))
+
+
+def edit_sites_tsv(ctx, found, rows):
+    """The --edit-sites table: EDIT_COLUMNS, a line per record of `found` (an EditSites over snvs_of(rows)), in the call's order.
+    position is 1-based as in the VCF, [start, end) the footprint of the record's site, 0-based and half-open; edit_offset where the
+    SNV is in the protospacer as the guide reads; guide is the `-i` string a search takes, cut from the background allele;
+    pam_sequence the PAM's bases on the site's strand; bystanders their number and bystander_offsets their positions, comma-separated
+    or . for none; edited the protospacer with every editable base replaced by the editor's product in lower case."""
+    lines = ["\t".join(EDIT_COLUMNS)]
+    L = found.pattern.protospacer_length
+    mode, to = "correct" if found.edit.correct else "install", found.edit.to_base.lower().replace("u", "t")
+    for r in found.sites:
+        c, pos1, vid, ref, alt = rows[int(r["snv_index"])]
+        ci, ps, pm, pl = int(r["contig_index"]), int(r["protospacer_start"]), int(r["pam_start"]), int(r["pam_length"])
+        lo, hi = (ps, ps + L) if pm < 0 else (min(ps, pm), max(ps + L, pm + pl))
+        pam_seq = ""
+        if pm >= 0 and pl:
+            pam_seq = ctx.fetch_bases(ci, pm, pl)
+            if r["strand"] == b"-":
+                pam_seq = pam_seq.translate(_RC)[::-1]
+            pam_seq = pam_seq.replace("U", "T")
+        by, bits = found.bystanders(r), int(r["editable"])
+        edited = "".join(to if (bits >> i) & 1 else ch for i, ch in enumerate(found.protospacer(r)))
+        lines.append("\t".join([c, str(pos1), vid or ".", ref, alt, mode, str(lo), str(hi), r["strand"].decode(), str(int(r["pam_index"])), str(found.offset(r)),
+                                found.guide(r), pam_seq, str(len(by)), ",".join(map(str, by)) or ".", edited]))
+    return "\n".join(lines) + "\n"
+
+
+def edit_sites_tool(ctx, pat, vcf, out_path, edit, chrom=None, start=0, end=None, host=False):
+    """FindGuides --alleles VCF --edit-sites OUT: the table of edit_sites_tsv to out_path, and the counts of what was examined and
+    skipped as one line on stderr."""
+    import sys
+    from .aligner import snvs_of
+    rows, skipped = snvs_of_vcf(ctx, vcf, chrom, start, end)
+    found = ctx.find_edit_sites(pat, edit, snvs_of([(c, pos1, ref, alt) for c, pos1, _, ref, alt in rows], ctx), host=host)
+    by = [int((found.status == k).sum()) for k in range(6)]
+    with open(out_path, "w") as f:
+        f.write(edit_sites_tsv(ctx, found, rows))
+    sys.stderr.write("edits: %d SNVs examined, %d records; skipped: %d other alleles, %d records on chromosomes the reference lacks, %d beyond a contig's end, "
+                     "%d with another REF than the reference, %d on a base that is not A C G T, %d with ALT equal to the reference, "
+                     "%d that are not the editor's change, %d whose 5' neighbour fails the context\n"
+                     % (by[0], len(found.sites), skipped["other"], skipped["lacks"], skipped["beyond"], by[1], by[2], by[3], by[4], by[5]))
+
+
 def find_guides_tool(ref, pattern, auxiliary_pams=(), chrom=None, start=0, end=None, output=None, counts=False, device=0, scores=None,
                      gc_min=None, gc_max=None, max_run=None, avoid=(), copies=False, seed_copies=None, max_copies=None, max_seed_copies=None,
                      near_copies=None, max_near_copies=None, near_scores=None, near_list=None, near_list_limit=None, activity=None, min_activity=None,
                      regions=None, classes=None, class_extent=None, pairs=None, pair_distance=None, pair_cut=None, pair_orientation=None, alleles=None, allele_sites=None,
-                     allele_kinds=None, microhomology=None, mh_cut=None, min_out_of_frame=None, **search):
+                     allele_kinds=None, microhomology=None, mh_cut=None, min_out_of_frame=None, edit_sites=None, editor=None, edit_window=None, edit_context=None, edit_mode=None,
+                     max_bystanders=None, **search):
     """`python -m calitas_amd FindGuides`: the guides of a region as a TSV (guides_tsv); counts=True: every distinct guide also goes
     through the off-target search with the SearchReference flags in `search` (make_params names); scores=ScoreModel (or its file):
     through search_scores_batch instead, which adds perfect and specificity.  gc_min, gc_max, max_run, avoid: the site filter's flags
@@ -847,10 +922,20 @@ def find_guides_tool(ref, pattern, auxiliary_pams=(), chrom=None, start=0, end=N
     (joined to the others as find_guides does); mh_cut=N the cut's position in the protospacer as the guide reads (default L - 3 with a
     3' PAM, required otherwise); min_out_of_frame=PCT (0 .. 100, needs microhomology): the rows whose out-of-frame share is below PCT
     per cent, those with a total of 0 and those without a score are dropped before any of the flags above looks at anything, the kept
-    rows keep their guide_ids.  These twenty-four work with device -1 through the host twin.  Returns the text."""
-    if (alleles is None) != (allele_sites is None):
+    rows keep their guide_ids.  edit_sites=OUT.tsv (needs alleles, editor="FROM:TO" and edit_window="FROM:TO"; alleles now needs
+    allele_sites or edit_sites, and may have both): the guides that put every SNV of the file whose position lies in the region into
+    the base editor's window, and their bystanders (Context.find_edit_sites, edit_sites_tsv) to OUT, the table itself unchanged;
+    edit_context=LETTER, edit_mode="install"|"correct" and max_bystanders=N as base_edit_of_flags reads them.  These thirty work with
+    device -1 through the host twin.  Returns the text."""
+    if edit_sites is not None and (alleles is None or editor is None or edit_window is None):
+        raise ValueError("--edit-sites OUT.tsv requires --alleles FILE.vcf, --editor FROM:TO and --edit-window FROM:TO")
+    if edit_sites is None and any(x is not None for x in (editor, edit_window, edit_context, edit_mode, max_bystanders)):
+        raise ValueError("--editor, --edit-window, --edit-context, --edit-mode and --max-bystanders require --edit-sites OUT.tsv")
+    if alleles is None and allele_sites is not None:
         raise ValueError("--alleles FILE.vcf and --allele-sites OUT.tsv require each other")
-    if allele_kinds is not None and alleles is None:
+    if alleles is not None and allele_sites is None and edit_sites is None:
+        raise ValueError("--alleles FILE.vcf requires --allele-sites OUT.tsv or --edit-sites OUT.tsv")
+    if allele_kinds is not None and allele_sites is None:
         raise ValueError("--allele-kinds requires --alleles FILE.vcf and --allele-sites OUT.tsv")
     if regions is None and (classes is not None or class_extent is not None):
         raise ValueError("--classes and --class-extent require --regions FILE.bed")
@@ -868,6 +953,7 @@ def find_guides_tool(ref, pattern, auxiliary_pams=(), chrom=None, start=0, end=N
     pat = Guide(pattern, auxiliary_pams)
     keep = site_filter_of_flags(pat.protospacer_length, gc_min, gc_max, max_run, avoid)
     pair_spec = site_pairs_of_flags(pat, pairs, pair_distance, pair_cut, pair_orientation)
+    edit = base_edit_of_flags(pat, editor, edit_window, edit_context, edit_mode, max_bystanders) if edit_sites is not None else None
     if seed_copies is not None and not 1 <= int(seed_copies) <= pat.protospacer_length:
         raise ValueError("--seed-copies K: K is 1 .. %d, the protospacer's length" % pat.protospacer_length)
     if max_copies is not None and int(max_copies) < 1:
@@ -970,8 +1056,10 @@ def find_guides_tool(ref, pattern, auxiliary_pams=(), chrom=None, start=0, end=N
             paired = guide_pairs(ctx, pat, rows, pair_spec, chrom, start, end, host=device < 0, filter=keep)
             with open(pairs, "w") as f:
                 f.write(pairs_tsv(rows, [pair_spec.name_of(o, pat) for o in range(4)], paired))
-        if alleles is not None:
+        if allele_sites is not None:
             allele_sites_tool(ctx, pat, alleles, allele_sites, allele_kinds, chrom, start, end, host=device < 0)
+        if edit_sites is not None:
+            edit_sites_tool(ctx, pat, alleles, edit_sites, edit, chrom, start, end, host=device < 0)
         if output is not None:
             with open(output, "w") as f:
                 f.write(text)

@@ -781,6 +781,70 @@ int calitas_find_allele_sites_host(const calitas_ctx* ctx, const calitas_guide_t
 int calitas_count_allele_sites_host(const calitas_ctx* ctx, const calitas_guide_t* pattern, const calitas_snv_t* snvs, uint64_t n_snvs,
                                     uint64_t* per_kind, uint64_t* n_sites, uint8_t* status);
 
+/* Base-editor guides of a SNV and their bystanders: the guides that put a single-nucleotide variant into a base editor's activity
+ * window on the strand the editor can change it on, and the other editable bases that share the window.  No reference counterpart.
+ * Letters are upper-cased and a U reads as T throughout; L is the pattern's protospacer length (at most 32).  Targets are
+ * calitas_snv_t.  For SNV i:
+ * ALLELES.  R is the reference's base at `position`.  The background allele B is R when installing (correct == 0: the cell carries
+ * REF, the edit makes ALT) and `alt` when correcting (correct == 1: the cell carries ALT, the edit makes REF); the product P is the
+ * other one.  The background contig is the contig with B at `position`.  Each SNV is taken alone.
+ * STRAND.  '+' when (B, P) == (from_base, to_base), '-' when (complement of B, complement of P) == (from_base, to_base); at most one
+ * holds.
+ * SITE.  site_B(p, s) is the record calitas_find_sites(pattern, the whole contig) would list at protospacer start p on strand s of the
+ * background contig (the first matching PAM wins, a base that is not A C G T U is in no footprint, a footprint that leaves the contig
+ * is no site), or none.
+ * GUIDE BASES.  g_0 .. g_{L-1} are the site's protospacer as the guide reads; g_{-1} is the base 5' of it -- on '+' the contig's base
+ * p - 1, on '-' the complement of base p + L -- and is absent outside the contig and where that base is not A C G T U.
+ * EDITABLE.  Position i is editable when window_from <= i < window_to, g_i == from_base, and the context is any or g_{i-1} is present
+ * and in the context's set.
+ * A RECORD is written for (i, p) on the SNV's strand when site_B(p, s) exists, the target's offset o (position - p on '+',
+ * p + L - 1 - position on '-') lies in the window, position o is editable, and popcount(editable) - 1 <= max_bystanders.  `site` is
+ * site_B(p, s), bit i of `editable` says that position i is editable (the target's bit is set), guide_lo / guide_hi hold the
+ * background allele's protospacer as the guide reads (calitas_allele_site_t's planes).
+ * THE ORDER.  By snv_index (the input's order: SNVs need not be sorted and may repeat), then protospacer_start: a total order, so the
+ * device, the host twin and repeated calls return the same bytes.  A SNV has at most window_to - window_from records.
+ * STATUS.  status[i], one byte per SNV (caller-allocated, may be NULL), checked in this order: 2: the reference's base at `position` is
+ * not A C G T U; 1: `ref` is given and differs from the reference's base; 3: `alt` equals the reference's base; 4: the change is not
+ * this editor's on either strand; 5: it is, but the target's own 5' neighbour fails `context` (this depends on the contig alone, not
+ * on the guide); 0: examined.  A SNV whose status is not 0 has no records. */
+typedef struct {                /* 8 bytes */
+  char from_base, to_base;      /* A C G T U, either case; distinct.  C->T: a CBE, A->G: an ABE, C->G: a CGBE */
+  uint8_t window_from, window_to; /* positions of the protospacer as the guide reads, 0-based half-open: 0 <= from < to <= L */
+  char context;                 /* IUPAC letter the base 5' of an edited base (as the guide reads) must lie in; 0 or N: any */
+  uint8_t correct;              /* 0 install: the cell carries REF, the edit makes ALT.  1 correct: the cell carries ALT, the edit makes REF */
+  uint8_t max_bystanders;       /* 0 .. 31: keep records with at most this many; 255: no bound */
+  uint8_t reserved;             /* 0 */
+} calitas_base_edit_t;
+typedef struct {                /* 32 bytes: two 16-byte stores */
+  calitas_site_t site;          /* the site on the background allele */
+  uint32_t snv_index;
+  uint32_t editable;            /* bit i: protospacer position i (as the guide reads) is editable; the target's bit is set */
+  uint32_t guide_lo, guide_hi;  /* the background allele's protospacer as the guide reads: calitas_allele_site_t's planes */
+} calitas_edit_site_t;
+/* *sites: the records, one block for calitas_free, also when there are none.  n_snvs == 0 is legal.  On the device one lane takes one
+ * SNV: it holds the SNV against the contig's bounds, loads in one round the words of the bit-planes and of the exception mask that
+ * cover the 95 bases from position - 47 (every footprint of the 32 protospacer starts position - 31 .. position, on either strand),
+ * takes the reference's base from that window (it decides the strand, which from there on is a select), matches the 32 starts
+ * bit-parallel on the background allele, keeps those that hold the SNV in the editor's window, and stores its count; after a scan
+ * of the workgroups' sums the same match stores every record at its place (no sort, no returning atomic); records and status bytes
+ * are copied back once each.  A SNV with a U of the reference within 63 bases is decided on the host by the twin's walk and its
+ * records are merged into place.
+ * Errors, in this order: CALITAS_ENODEV on a host-only context (the device calls); what calitas_find_sites refuses about the pattern;
+ * CALITAS_EINVAL, with a message that names the field, for a from_base or to_base that is not one of the letters or the two equal, a
+ * window that is empty or ends past L, a context that is no IUPAC letter, correct > 1, max_bystanders of 32 .. 254, reserved != 0;
+ * what calitas_find_allele_sites refuses about the SNVs; CALITAS_ENOMEM when the SNVs and their records do not fit the device. */
+int calitas_find_edit_sites(calitas_ctx* ctx, const calitas_guide_t* pattern, const calitas_base_edit_t* edit, const calitas_snv_t* snvs,
+                            uint64_t n_snvs, calitas_edit_site_t** sites, uint64_t* n_sites, uint8_t* status /* [n_snvs], may be NULL */);
+/* The first pass alone: *n_sites and, when per_bystanders is not NULL, the records with 0, 1, 2 and 3 or more bystanders ([4], they
+ * sum to *n_sites).  No records are copied back. */
+int calitas_count_edit_sites(calitas_ctx* ctx, const calitas_guide_t* pattern, const calitas_base_edit_t* edit, const calitas_snv_t* snvs,
+                             uint64_t n_snvs, uint64_t* per_bystanders /* [4], may be NULL */, uint64_t* n_sites, uint8_t* status);
+/* The host twins: a base-by-base walk of the background contig; also on a host-only context. */
+int calitas_find_edit_sites_host(const calitas_ctx* ctx, const calitas_guide_t* pattern, const calitas_base_edit_t* edit,
+                                 const calitas_snv_t* snvs, uint64_t n_snvs, calitas_edit_site_t** sites, uint64_t* n_sites, uint8_t* status);
+int calitas_count_edit_sites_host(const calitas_ctx* ctx, const calitas_guide_t* pattern, const calitas_base_edit_t* edit,
+                                  const calitas_snv_t* snvs, uint64_t n_snvs, uint64_t* per_bystanders, uint64_t* n_sites, uint8_t* status);
+
 /* Microhomology and frameshift odds: what the cut of a site is likely to become.  A double-strand break with microhomologies either
  * side of it is repaired by MMEJ into a few predictable deletions; a guide whose likely deletions are multiples of three leaves the
  * protein in frame.  No reference counterpart.

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Generated-code comparison of the device units (the stage units scan_columns / align / trace / mailbox / setup .hip, which replaced
-kernels.hip, select / hits / binned .hip, and the guide-site units sites / near_list / activity / site_regions / site_pairs / allele_sites / microhomology .hip) against an earlier revision: the check that a move or a refactor of device code left the
+kernels.hip, select / hits / binned .hip, and the guide-site units sites / near_list / activity / site_regions / site_pairs / allele_sites / microhomology / edit_sites .hip) against an earlier revision: the check that a move or a refactor of device code left the
 compiler's output as it was.
 
   python tools/kernel_diff.py [--rev HEAD~1] [--show]
@@ -28,7 +28,7 @@ import tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join("calitas_amd", "csrc")
 UNITS = ["kernels.hip", "scan_columns.hip", "align.hip", "trace.hip", "mailbox.hip", "setup.hip", "select.hip", "hits.hip", "binned.hip", "sites.hip",
-         "near_list.hip", "activity.hip", "site_regions.hip", "site_pairs.hip", "allele_sites.hip", "microhomology.hip"]
+         "near_list.hip", "activity.hip", "site_regions.hip", "site_pairs.hip", "allele_sites.hip", "microhomology.hip", "edit_sites.hip"]
 
 
 def device_asm(csrc, out_dir):
