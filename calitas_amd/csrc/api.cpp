@@ -779,7 +779,7 @@ int calitas_search_counts_batch(calitas_ctx* ctx, int32_t n_guides, const calita
   return rc;
 }
 
-// Guide sites (sites_host.cpp): no reference counterpart.  The unfiltered calls are the filtered ones without a filter.
+// Guide sites (sites_host.cpp; the copies and near calls below: sites_copies.cpp): no reference counterpart.  The unfiltered calls are the filtered ones without a filter.
 int calitas_find_sites_filtered(calitas_ctx* ctx, const calitas_guide_t* pattern, const calitas_site_filter_t* filter, int32_t chrom_index,
                                 uint64_t start, uint64_t end, calitas_site_t** sites, uint64_t* n_sites) {
   if (!ctx) return CALITAS_EINVAL;
@@ -1302,7 +1302,7 @@ int calitas_padded_strings(const calitas_ctx* ctx, const calitas_guide_t* guide,
   return CALITAS_OK;
 }
 
-// Activity scores (sites_host.cpp, activity.hip): no reference counterpart.  The newest entry points stand last, so that everything
+// Activity scores (sites_scored.cpp, activity.hip): no reference counterpart.  The newest entry points stand last, so that everything
 // above keeps its place in the object file.
 // (the model is the implementation's to check: it comes after everything calitas_find_sites_filtered refuses)
 int calitas_find_sites_scored(calitas_ctx* ctx, const calitas_guide_t* pattern, const calitas_site_filter_t* filter, const calitas_activity_model_t* model,
@@ -1325,7 +1325,7 @@ int calitas_find_sites_scored_host(const calitas_ctx* ctx, const calitas_guide_t
   return calitas_find_sites_scored_host_impl(ctx, pattern, filter, model, min_score_q16, chrom_index, start, end, sites, scores, n_sites);
 }
 
-// Sites by annotated regions (sites_host.cpp, site_regions.hip): no reference counterpart.
+// Sites by annotated regions (sites_regions.cpp, site_regions.hip): no reference counterpart.
 int calitas_find_sites_regions(calitas_ctx* ctx, const calitas_guide_t* pattern, const calitas_site_filter_t* filter, const calitas_site_regions_t* opt,
                                int32_t chrom_index, uint64_t start, uint64_t end, calitas_site_t** sites, uint8_t** classes, uint64_t* n_sites) {
   if (!ctx) return CALITAS_EINVAL;
@@ -1379,7 +1379,7 @@ int calitas_site_presence(const calitas_ctx* ctx, uint8_t** bytes, uint64_t* n, 
   return CALITAS_OK;
 }
 
-// Sites in pairs (sites_host.cpp, site_pairs.hip): no reference counterpart.
+// Sites in pairs (sites_pairs.cpp, site_pairs.hip): no reference counterpart.
 int calitas_find_site_pairs(calitas_ctx* ctx, const calitas_guide_t* pattern, const calitas_site_filter_t* filter, const calitas_site_pairs_t* opt,
                             int32_t chrom_index, uint64_t start, uint64_t end, calitas_site_t** sites, uint64_t* n_sites, calitas_site_pair_t** pairs,
                             uint64_t* n_pairs) {
@@ -1415,7 +1415,7 @@ int calitas_count_site_pairs_host(const calitas_ctx* ctx, const calitas_guide_t*
   return calitas_find_site_pairs_host_impl(ctx, pattern, filter, opt, chrom_index, start, end, false, nullptr, n_sites, nullptr, n_pairs, per_orientation);
 }
 
-// Allele-specific sites (sites_host.cpp, allele_sites.hip): no reference counterpart.
+// Allele-specific sites (sites_snv.cpp, allele_sites.hip): no reference counterpart.
 int calitas_find_allele_sites(calitas_ctx* ctx, const calitas_guide_t* pattern, const calitas_snv_t* snvs, uint64_t n_snvs, calitas_allele_site_t** sites,
                               uint64_t* n_sites, uint8_t* status) {
   if (!ctx) return CALITAS_EINVAL;
@@ -1448,7 +1448,7 @@ int calitas_count_allele_sites_host(const calitas_ctx* ctx, const calitas_guide_
   return calitas_find_allele_sites_host_impl(ctx, pattern, snvs, n_snvs, false, nullptr, per_kind, n_sites, status);
 }
 
-// Base-editor guides of a SNV (sites_host.cpp, edit_sites.hip): no reference counterpart.
+// Base-editor guides of a SNV (sites_snv.cpp, edit_sites.hip): no reference counterpart.
 int calitas_find_edit_sites(calitas_ctx* ctx, const calitas_guide_t* pattern, const calitas_base_edit_t* edit, const calitas_snv_t* snvs, uint64_t n_snvs,
                             calitas_edit_site_t** sites, uint64_t* n_sites, uint8_t* status) {
   if (!ctx) return CALITAS_EINVAL;
@@ -1481,7 +1481,7 @@ int calitas_count_edit_sites_host(const calitas_ctx* ctx, const calitas_guide_t*
   return calitas_find_edit_sites_host_impl(ctx, pattern, edit, snvs, n_snvs, false, nullptr, per_bystanders, n_sites, status);
 }
 
-// Microhomology scores (sites_host.cpp, microhomology.hip): no reference counterpart.
+// Microhomology scores (sites_scored.cpp, microhomology.hip): no reference counterpart.
 // (the model is the implementation's to check: it comes after everything calitas_find_sites_filtered refuses)
 int calitas_find_sites_microhomology(calitas_ctx* ctx, const calitas_guide_t* pattern, const calitas_site_filter_t* filter, const calitas_mh_model_t* model,
                                      int32_t min_out_of_frame_permille, int32_t chrom_index, uint64_t start, uint64_t end, calitas_site_t** sites,

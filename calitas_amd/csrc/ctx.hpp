@@ -22,7 +22,7 @@
 #include "dma.hpp"
 #include "mailbox.hpp"
 
-namespace calitas { struct SitesWork; }   // sites.hpp
+namespace calitas { struct SitesWork; }   // sites_work.hpp
 using namespace calitas;
 
 struct calitas_ctx {
@@ -73,10 +73,10 @@ struct calitas_ctx {
   RegionSeg* d_region_seg = nullptr;
   uint32_t *d_region_coarse = nullptr, *d_region_contig = nullptr;
   // calitas_find_sites_regions: which classes come near each segment of the site pass, made from `regions` and the reference at the first
-  // regions listing (sites_host.cpp, site_presence) and made again when either is another one
+  // regions listing (sites_regions.cpp, site_presence) and made again when either is another one
   std::vector<uint8_t> site_presence;
   uint64_t site_presence_regions = 0, site_presence_ref = ~0ull;
-  SitesWork* sites = nullptr;       // calitas_find_sites: device scratch kept between calls (sites_host.cpp)
+  SitesWork* sites = nullptr;       // calitas_find_sites: device scratch kept between calls (sites_work.hpp)
   double align_ms_by_stamps = -1;   // lane: >= 0: align_kernel + trace_kernel of the current search ran without an event behind them (binned.hpp, BIN_BOX_STAMPS)
   int rows_ev0 = 4;                 // lane: ev[rows_ev0] .. ev[5] bracket the row stage of the last call
   bool binned_late_check = false;   // lane: the text being copied comes from the binned rows kernel (its late flags are checked after the copy's wait)

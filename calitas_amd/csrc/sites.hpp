@@ -1,4 +1,5 @@
-// sites.hpp -- private: guide-site enumeration (sites_host.cpp; kernels in sites.hip, launch interface in kernels.hpp).
+// sites.hpp -- private: guide-site enumeration as api.cpp sees it (sites_host.cpp, sites_copies.cpp, sites_scored.cpp, sites_regions.cpp,
+// sites_pairs.cpp, sites_snv.cpp; what those share: sites_work.hpp; kernels in sites.hip and the feature units, launch interface in kernels.hpp).
 #pragma once
 #include <string>
 #include <vector>
@@ -26,7 +27,7 @@ void host_sites(const PackedRef& ref, const SitePatterns& pat, const calitas_sit
 // The presence table of the context's region set (calitas_find_sites_regions), made when the set or the reference is another one than
 // the table's; returns an error text or "".  Needs no device.
 std::string site_presence(calitas_ctx* c, const std::vector<uint8_t>** out);
-struct SitesWork;                 // device scratch of a context, kept between calls
+struct SitesWork;                 // device scratch of a context, kept between calls (sites_work.hpp)
 void sites_destroy(SitesWork* w);
 
 }  // namespace calitas
